@@ -7,16 +7,23 @@ sliding_window=4096, one 4096-token prefill, then greedy batch-1 decode.  A "ste
 with the ring full (4096 keys per layer).  Inputs (weights, K/V rings, token ids) are resident in HBM.
 
     python bench.py --gpus 1 --steps 64 --warmup 8
+    python bench.py --gpus 1 --steps 64 --warmup 8 --full                  # + every other measurement below
+    python bench.py --gpus 1 --steps 64 --warmup 8 --dump-outputs DIR      # + the timed path's outputs as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W        # pipeline stages over RCCL
 
+A plain run does only what the headline needs: build the model, one prefill to fill the rings, W warm-up steps, the K timed
+steps, then the result line (and the outputs, with --dump-outputs).  Everything else is measured with --full:
+
 N > 1 (one rank per GPU, layer ranges as pipeline stages): the headline `value` stays the BASELINE metric - ONE sequence relayed
 through the N stages, what the reference's pipeline does (transformer.py:195-237; "scaling": "strong": the same work on more
-GPUs, and by construction no faster than on one).  The pipeline's THROUGHPUT mode - N independent sequences in flight, one per
-stage at any time (mistral_inference/pipeline_decode.py) - is reported beside it under `pipeline_throughput`.
+GPUs, and by construction no faster than on one).  With --full, the pipeline's THROUGHPUT mode - N independent sequences in
+flight, one per stage at any time (mistral_inference/pipeline_decode.py) - is reported beside it under `pipeline_throughput`,
+with every stage's own roofline and a Mixtral sub-measurement over the same stages.
 
-N = 1 additionally carries, as sub-objects of the same line: `nemo` and `mixtral` (BASELINE configs[2] and [3] measured by this
-same script in a subprocess each), `parity` (the configs[0] model against the CPU oracle in this run) and `cpu_baseline`.
+N = 1 with --full additionally carries, as sub-objects of the same line: the prefill timing, the dominant kernel's `roofline`,
+`nemo` and `mixtral` (BASELINE configs[2] and [3] measured by this same script in a subprocess each), `parity` (the configs[0]
+model against the CPU oracle in this run) and `cpu_baseline`.
 
 Prints ONE JSON line on rank 0 (see README/DESIGN.md section 6 for the roofline / cpu_baseline definitions).
 """
@@ -243,11 +250,10 @@ def stage_roofline(model, cache, params: dict, rank: int, world: int, iters: int
 
 def reference_baseline(params: dict, ctx: int, steps: int = 6):
     """The UNMODIFIED reference timed on this box's host cores (oracle/time_reference.py in a subprocess: the reference
-    shares the product's package name).  None where the reference source is absent (the GPU box)."""
+    shares the product's package name).  None where neither its source nor its bytecode is present."""
     import subprocess
-    # the source tree where it exists (the build container), else its byte-compiled form oracle/build_ref.py put under
-    # oracle/_ref/ (git-ignored, travels with the working tree to the GPU box like the built .so does)
-    ref = os.environ.get("MISTRAL_REFERENCE_SRC", "/root/reference/src")
+    # the source tree named by MISTRAL_REFERENCE_SRC, else the byte-compiled form build() put under oracle/_ref/ (git-ignored)
+    ref = os.environ.get("MISTRAL_REFERENCE_SRC", "")
     if not os.path.isdir(os.path.join(ref, "mistral_inference")):
         ref = os.path.join(ROOT, "oracle", "_ref")
     if not os.path.isdir(os.path.join(ref, "mistral_inference")):
@@ -349,7 +355,7 @@ def sub_measurement(model_key: str, prefill: int, steps: int, warmup: int, timeo
     reader needs.  `extra`: further command-line flags (`--layers 7`: one pipeline stage; `--batch 3`: the mistral-demo shape)."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--model", model_key, "--prefill", str(prefill), "--steps", str(steps),
-           "--warmup", str(warmup), "--no-cpu-baseline", "--no-extras", *extra]
+           "--warmup", str(warmup), "--full", "--no-cpu-baseline", "--no-extras", *extra]
     t0 = time.perf_counter()
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s)
@@ -386,9 +392,10 @@ def parity_in_this_run() -> dict:
 
 
 def timed_run(opt, params: dict, rank: int, world: int, dev: str, T0: int, K: int, Wm: int, sync):
-    """Build the model (this rank's pipeline stage), run one untimed and one timed T0-token prefill, W warm-up decode steps,
-    then time exactly K decode steps between two synchronisations (+ barriers).  Returns the model, its cache, the last
-    token, the decode seconds and the prefill seconds (both the maximum over ranks)."""
+    """Build the model (this rank's pipeline stage), run the T0-token prefill, W warm-up decode steps, then time exactly K
+    decode steps between two synchronisations (+ barriers).  Returns the model, its cache, the last token, the decode seconds
+    and the prefill seconds (both the maximum over ranks; the prefill is timed with --full only, else None).  The outputs of the
+    timed steps are left in timed_run.outputs on the rank that samples (the last one)."""
     from mistral_inference.cache import BufferCache
     model = build_model(params, rank, world, dev)
     a = model.args
@@ -396,13 +403,16 @@ def timed_run(opt, params: dict, rank: int, world: int, dev: str, T0: int, K: in
                         dtype=torch.bfloat16)
     cache.reset()
     prompt = torch.randint(0, a.vocab_size, (T0,), generator=torch.Generator().manual_seed(0)).to(dev)
+    timed_run.outputs = None
     with torch.inference_mode():
-        # ---- prefill: one untimed pass (allocates the workspace / logits buffers), then the timed pass on a
-        # reset cache; includes the [T, V] fp32 LM head the API contract requires
+        # ---- prefill: one untimed pass (allocates the workspace / logits buffers) - all the decode steps need; with --full
+        # then the timed passes on a reset cache; includes the [T, V] fp32 LM head the API contract requires
         logits = model.forward(prompt, [T0], cache)
+        nxt = torch.argmax(logits[-1:], dim=-1)
         del logits
-        prefill_all = []
-        for _ in range(3):  # three timed passes, the MEDIAN is reported (a single sample of a power-capped quantity is noise)
+        prefill_all, prefill_s = [], None
+        # three timed passes, the MEDIAN is reported (a single sample of a power-capped quantity is noise)
+        for _ in range(3 if opt.full else 0):
             cache.reset()
             sync()
             t0 = time.perf_counter()
@@ -411,7 +421,8 @@ def timed_run(opt, params: dict, rank: int, world: int, dev: str, T0: int, K: in
             prefill_all.append(time.perf_counter() - t0)
             nxt = torch.argmax(logits[-1:], dim=-1)
             del logits
-        prefill_s = sorted(prefill_all)[1]
+        if prefill_all:
+            prefill_s = sorted(prefill_all)[1]
         # ---- decode: the generate() loop body - forward(next_token, [1], cache) under the decode hipGraph context
         # (capture happens inside the warm-up steps; W >= 2 keeps it out of the timed region)
         if opt.loop == "greedy":
@@ -431,7 +442,7 @@ def timed_run(opt, params: dict, rank: int, world: int, dev: str, T0: int, K: in
                 sess.run(W - 1)
             else:
                 sess.run(W)
-            dt, left, collect_s, ev_ms = 0.0, K, 0.0, 0.0
+            dt, left, collect_s, ev_ms, all_toks, all_lps = 0.0, K, 0.0, 0.0, [], []
             stream = torch.cuda.current_stream(dev)  # (the stream mi_forward launches on and the captured step is replayed on)
             # (events are created BEFORE the bracket's synchronisation: whatever the host does between that synchronisation and the
             # first launch is idle GPU time inside the timed region)
@@ -448,10 +459,16 @@ def timed_run(opt, params: dict, rank: int, world: int, dev: str, T0: int, K: in
                 t1 = time.perf_counter()
                 dt += t1 - t0
                 ev_ms += e0.elapsed_time(e1)
-                toks, _ = sess.collect()         # verifies that the device completed every step (and which path ran)
+                toks, lps = sess.collect()       # verifies that the device completed every step (and which path ran)
                 collect_s += time.perf_counter() - t1   # generate() pays this once per chunk (32 steps with an eos_id, else 1024)
                 left -= n
+                all_toks.append(toks[-n:])       # (the first chunk also returns the two uncollected warm-up steps)
+                all_lps.append(lps[-n:])
             nxt = toks[-1]
+            if sess.is_last:
+                # what generate() hands its caller for the K timed steps (sampled ids, their logprobs) and the logits the
+                # last step wrote
+                timed_run.outputs = {"tokens": torch.cat(all_toks), "logprobs": torch.cat(all_lps), "logits": sess.logits}
             timed_run.used_graph = bool(sess._use_graph)
             timed_run.collect_s = collect_s
             timed_run.event_us_per_step = ev_ms * 1e3 / K
@@ -464,13 +481,16 @@ def timed_run(opt, params: dict, rank: int, world: int, dev: str, T0: int, K: in
                 sync()
                 t0 = time.perf_counter()
                 for _ in range(K):
-                    nxt = torch.argmax(model.forward(nxt, [1], cache), dim=-1)
+                    logits = model.forward(nxt, [1], cache)
+                    nxt = torch.argmax(logits, dim=-1)
                 sync()
                 dt = time.perf_counter() - t0
+            if rank == world - 1:  # the last step's logits and the token sampled from them
+                timed_run.outputs = {"tokens": nxt, "logits": logits}
     if world > 1:
-        tmax = torch.tensor([dt, prefill_s], device=dev, dtype=torch.float64)
+        tmax = torch.tensor([dt, prefill_s or 0.0], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
-        dt, prefill_s = tmax.tolist()
+        dt, prefill_s = tmax[0].item(), (tmax[1].item() if prefill_all else None)
     timed_run.prefill_all = prefill_all
     return model, cache, nxt, dt, prefill_s
 
@@ -513,7 +533,8 @@ def batch_run(opt, params: dict, B: int, dev: str, T0: int, K: int, Wm: int) -> 
         sess.run(K)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        sess.collect()
+        toks, lps = sess.collect()
+        batch_run.outputs = {"tokens": toks[-K:], "logprobs": lps[-K:], "logits": sess.logits}
     st = _hip.decode_engine_status(model._backend._workspace)
     ctx_len = T0 + W + K // 2
     w_bytes = decode_bytes_per_token(params, ctx_len)
@@ -532,6 +553,25 @@ def batch_run(opt, params: dict, B: int, dev: str, T0: int, K: int, Wm: int) -> 
             "hbm_roofline_step": {"bytes_per_step": step_bytes, "weights_once_plus_kv_per_sequence": [w_bytes - kv_one, kv_one],
                                   "achieved_GBs": round(gbs, 1), "peak_GBs": HBM_PEAK_GBS, "frac": round(gbs / HBM_PEAK_GBS, 4)},
             "per_sequence_tokens_per_s": round(K / dt, 2)}
+
+
+DUMP_MAX_BYTES = 60 << 20  # (under 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: each output of the timed path as out_dir/<name>.npy - sampled token ids as float64 (exact), everything
+    else as float32.  Past DUMP_MAX_BYTES in all, an array is cut to a fixed seeded sample of its elements (flattened)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_MAX_BYTES
+    for name, t in arrays.items():
+        a = t.detach().cpu().to(torch.float64 if name == "tokens" else torch.float32)
+        if a.numel() * a.element_size() > left:
+            keep = left // a.element_size()
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            a = a.reshape(-1)[idx]
+        left -= a.numel() * a.element_size()
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy())
 
 
 def interleaved_run(opt, model, rank: int, world: int, dev: str, T0: int, K: int, Wm: int, sync):
@@ -593,16 +633,24 @@ def main() -> None:
     ap.add_argument("--prefill", type=int, default=4096, help="prompt tokens (BASELINE configs[1]: 4096)")
     ap.add_argument("--layers", type=int, default=None, help="debug only: fewer layers => NOT the named config")
     ap.add_argument("--model", default="mistral-7b", choices=sorted(PRESETS), help="default = BASELINE configs[1]")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the `cpu_baseline` sub-object")
     ap.add_argument("--no-graph", action="store_true", help="enqueue decode steps launch by launch (no hipGraph replay)")
     ap.add_argument("--loop", default="greedy", choices=["greedy", "forward"],
                     help="greedy: generate()'s temperature-0 loop (sample fused into the step); forward: forward() + torch.argmax per token")
-    ap.add_argument("--no-mixtral", action="store_true", help="N > 1: skip the Mixtral sub-measurement")
+    ap.add_argument("--no-mixtral", action="store_true", help="--full, N > 1: skip the Mixtral sub-measurement")
     ap.add_argument("--batch", type=int, default=1, help="evidence run: B sequences decoded together (mistral-demo runs 3); 1 = the headline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="N = 1: skip the `nemo` / `mixtral` / `parity` sub-objects (the headline fields are the same either way)")
+                    help="--full, N = 1: skip the `nemo` / `mixtral` / `parity` sub-objects (the headline fields are the same either way)")
     ap.add_argument("--mixtral-layers", type=int, default=None, help="debug only: layers of the N > 1 Mixtral sub-measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: prefill timing, rooflines, cpu_baseline, parity and the other "
+                         "BASELINE configs (N = 1), the pipeline's throughput mode, per-stage rooflines and Mixtral (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed (sampled ids and logprobs of the timed steps, the last step's "
+                         "logits) as DIR/<name>.npy")
     opt = ap.parse_args()
+    if opt.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if opt.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: spawn the N ranks ourselves (one process per GPU, RCCL over xGMI) exactly as the
@@ -635,13 +683,18 @@ def main() -> None:
 
     if opt.batch > 1:
         assert world == 1, "--batch is a single-GPU evidence run"
-        print(json.dumps(batch_run(opt, params, opt.batch, dev, T0, K, Wm)), flush=True)
+        line = batch_run(opt, params, opt.batch, dev, T0, K, Wm)
+        if opt.dump_outputs:
+            dump_outputs(opt.dump_outputs, batch_run.outputs)
+        print(json.dumps(line), flush=True)
         return
 
     model, cache, nxt, dt, prefill_s = timed_run(opt, params, rank, world, dev, T0, K, Wm, sync)
-    # N > 1: a single sequence is a relay through the stages (dt above: N GPUs decode no faster than one); the pipeline's
-    # throughput is measured with one sequence per stage in flight.  MI_BENCH_INTERLEAVE=0 skips it.
-    interleave = world > 1 and opt.loop == "greedy" and os.environ.get("MI_BENCH_INTERLEAVE", "1") != "0"
+    if opt.dump_outputs and timed_run.outputs is not None:
+        dump_outputs(opt.dump_outputs, timed_run.outputs)
+    # N > 1: a single sequence is a relay through the stages (dt above: N GPUs decode no faster than one); with --full the
+    # pipeline's throughput is measured with one sequence per stage in flight.  MI_BENCH_INTERLEAVE=0 skips it.
+    interleave = opt.full and world > 1 and opt.loop == "greedy" and os.environ.get("MI_BENCH_INTERLEAVE", "1") != "0"
     dt_il = None
     if interleave:
         ok = 1
@@ -693,12 +746,13 @@ def main() -> None:
                        f"{torch.distributed.get_backend()})"},
             "hbm_roofline_step": {"bytes_per_token": step_bytes, "achieved_GBs": round(step_gbs, 1), "peak_GBs": HBM_PEAK_GBS,
                                   "frac": round(step_gbs / HBM_PEAK_GBS, 4), "frac_of_measured_copy_6290": round(step_gbs / 6290.0, 4)},
-            "prefill": {"tokens": T0, "seconds": round(prefill_s, 4), "timing": "median of 3 timed passes",
-                        "seconds_all": [round(x, 4) for x in getattr(timed_run, "prefill_all", [])],
-                        "tokens_per_s": round(T0 / prefill_s, 1),
-                        "tflops": round(prefill_flops(params, T0) / prefill_s / 1e12, 1), "mfma_peak_tflops": 2500.0,
-                        "mfma_frac": round(prefill_flops(params, T0) / prefill_s / 2.5e15, 4)},
         }
+        if prefill_s is not None:
+            out["prefill"] = {"tokens": T0, "seconds": round(prefill_s, 4), "timing": "median of 3 timed passes",
+                              "seconds_all": [round(x, 4) for x in getattr(timed_run, "prefill_all", [])],
+                              "tokens_per_s": round(T0 / prefill_s, 1),
+                              "tflops": round(prefill_flops(params, T0) / prefill_s / 1e12, 1), "mfma_peak_tflops": 2500.0,
+                              "mfma_frac": round(prefill_flops(params, T0) / prefill_s / 2.5e15, 4)}
         if opt.loop == "greedy":
             # not inside the K-step bracket: the once-per-chunk read-back of the samples (status copy + host sync + gather)
             out["collect_ms_per_chunk"] = round(getattr(timed_run, "collect_s", 0.0) * 1e3, 3)
@@ -724,6 +778,8 @@ def main() -> None:
                 "tick_form": getattr(interleaved_run, "tick_form", "eager"),
                 "note": "one sequence per stage in flight, ring of grouped send+recv per tick (mistral_inference/pipeline_decode.py); "
                         "tick_host_us = host time per tick of the loop (max over ranks)"}
+        if not opt.full:
+            return out
         # the dominant kernel is timed on this rank's own layers (any N)
         if engine["engine_launches"] > 0 and world == 1:
             with torch.inference_mode():
@@ -744,7 +800,7 @@ def main() -> None:
         return out
 
     out = report() if rank == 0 else None
-    if world > 1:  # the other ranks wait here while rank 0 times its dominant kernel
+    if world > 1 and opt.full:  # the other ranks wait here while rank 0 times its dominant kernel
         torch.distributed.barrier()
         # every stage's own decode call (no hop: Backend.run_stack directly, as the throughput mode issues it) against the
         # bytes of its own layers (+ the LM head on the last stage)
@@ -754,7 +810,7 @@ def main() -> None:
         torch.distributed.all_gather_object(per_rank, mine)
         if out is not None:
             out["roofline_per_rank"] = per_rank
-    if world == 1 and opt.model == "mistral-7b" and not opt.layers and not opt.no_extras:
+    if opt.full and world == 1 and opt.model == "mistral-7b" and not opt.layers and not opt.no_extras:
         # the other BASELINE configs and parity, in the one line the driver records (the headline fields above are final -
         # they go to stderr right away, so that a time-out or a crash in an extra cannot lose a measured headline)
         print("[bench] headline measured (sub-objects follow): " + json.dumps(out), file=sys.stderr, flush=True)
@@ -776,7 +832,7 @@ def main() -> None:
         out["x22b_stage"] = sub_measurement("mixtral-8x22b", T0, Ks, Ws, extra=("--layers", "7"))
         # the mistral-demo shape: three prompts decoded together (reference main.py:124,220), launch path
         out["batch3"] = sub_measurement("mistral-7b", T0, Ks, Ws, extra=("--batch", "3"))
-    if world > 1 and not opt.no_mixtral and opt.model == "mistral-7b" and (not opt.layers or opt.mixtral_layers):
+    if opt.full and world > 1 and not opt.no_mixtral and opt.model == "mistral-7b" and (not opt.layers or opt.mixtral_layers):
         # north_star: "Mixtral-8x7B pipeline-parallel tokens/sec reported at 1/2/4/8 GPUs" (BASELINE configs[3], and
         # configs[4] - Mixtral-8x22B over 8 stages - where 8 GPUs are present).  The N = 1 headline line is untouched; a
         # multi-GPU run additionally measures the Mixtral model over the same N stages and reports it as a sub-object.

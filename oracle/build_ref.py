@@ -22,13 +22,13 @@ SRC = os.environ.get("MISTRAL_REFERENCE_SRC", "/root/reference/src")
 DST = os.path.join(HERE, "_ref")
 
 
-def build(verbose: bool = True) -> bool:
-    pkg = os.path.join(SRC, "mistral_inference")
+def build(verbose: bool = True, src: str = SRC, dst: str = DST) -> bool:
+    pkg = os.path.join(src, "mistral_inference")
     if not os.path.isdir(pkg):
         if verbose:
             print(f"oracle/build_ref.py: {pkg} not found - nothing to do (the GPU box uses the prebuilt oracle/_ref)")
         return False
-    out = os.path.join(DST, "mistral_inference")
+    out = os.path.join(dst, "mistral_inference")
     shutil.rmtree(out, ignore_errors=True)
     os.makedirs(out)
     n = 0
@@ -36,7 +36,7 @@ def build(verbose: bool = True) -> bool:
         if name.endswith(".py"):
             py_compile.compile(os.path.join(pkg, name), cfile=os.path.join(out, name + "c"), doraise=True, optimize=0)
             n += 1
-    with open(os.path.join(DST, "README"), "w") as f:
+    with open(os.path.join(dst, "README"), "w") as f:
         f.write(f"sourceless bytecode of {pkg} ({n} modules), python {sys.version.split()[0]}; made by oracle/build_ref.py\n")
     if verbose:
         print(f"oracle/build_ref.py: {n} modules -> {out}")

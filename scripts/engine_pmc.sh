@@ -31,7 +31,7 @@ V=$REPO/mistral-inference_amd/lib/variants/libmistral_hip_e_trace0.so
 for name in shipped e_trace0; do
   if [ $name == e_trace0 ]; then export MISTRAL_HIP_LIB=$V; else unset MISTRAL_HIP_LIB; fi
   # un-profiled timing of the same command first (a profiled pass clocks differently: never compare across)
-  python bench.py --steps 12 --warmup 4 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$name', 'ms_per_step', d['ms_per_step'], 'kernel_us', d['roofline']['avg_launch_us'])" | tee -a $OUT/table.txt
+  python bench.py --steps 12 --warmup 4 --full --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$name', 'ms_per_step', d['ms_per_step'], 'kernel_us', d['roofline']['avg_launch_us'])" | tee -a $OUT/table.txt
   i=0
   while read -r set; do
     i=$((i+1))

@@ -104,6 +104,7 @@ def test_sub_measurement_reports_an_error_instead_of_raising(monkeypatch):
     monkeypatch.setattr(subprocess, "run", run3)
     out = bench.sub_measurement("mistral-7b", 4096, 32, 2, extra=("--batch", "3"))
     assert out["tokens_per_s"] == 800.0 and out["bytes_per_step"] == 123 and "error" not in out and seen["cmd"][-2:] == ["--batch", "3"]
+    assert "--full" in seen["cmd"]  # (the child's roofline and prefill objects are --full measurements)
 
     def boom(*a, **k):
         raise subprocess.TimeoutExpired("bench.py", 1)
@@ -111,19 +112,46 @@ def test_sub_measurement_reports_an_error_instead_of_raising(monkeypatch):
     assert "TimeoutExpired" in bench.sub_measurement("mixtral-8x7b", 4096, 4, 2)["error"]
 
 
-def test_reference_bytecode_recipe():
+def test_reference_bytecode_recipe(tmp_path):
     """oracle/build_ref.py: the unmodified reference byte-compiled into oracle/_ref/ (what lets bench.py's cpu_baseline time the
-    reference itself on the GPU box).  Where /root/reference exists: rebuild, then import the SOURCELESS package through the shim."""
+    reference itself on the GPU box).  The recipe runs on a stand-in package of the reference's layout (imports between its
+    modules and from the shim), which must then import SOURCELESS through the shim; where build() made oracle/_ref/, the
+    reference's own bytecode must import the same way."""
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if not os.path.isdir("/root/reference/src/mistral_inference"):
-        import pytest
-        pytest.skip("no reference source on this machine (the GPU box uses the prebuilt oracle/_ref)")
-    r = subprocess.run([sys.executable, os.path.join(root, "oracle", "build_ref.py")], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import build_ref
+    pkg = tmp_path / "src" / "mistral_inference"
+    pkg.mkdir(parents=True)
+    (pkg / "__init__.py").write_text("")
+    (pkg / "cache.py").write_text("from xformers.ops.fmha.attn_bias import BlockDiagonalCausalMask\nMASK = BlockDiagonalCausalMask\n")
+    (pkg / "transformer.py").write_text("from simple_parsing.helpers import Serializable\nfrom .cache import MASK\n")
+    assert build_ref.build(verbose=False, src=str(tmp_path / "src"), dst=str(tmp_path / "ref"))
+    assert sorted(os.listdir(tmp_path / "ref" / "mistral_inference")) == ["__init__.pyc", "cache.pyc", "transformer.pyc"]
     code = ("import sys, os; sys.path[:0] = [%r, %r]; import mistral_inference.transformer as t, mistral_inference.cache as c; "
             "assert t.__file__.endswith('.pyc') and c.__file__.endswith('.pyc'), t.__file__; "
-            "assert not os.path.exists(t.__file__[:-1]); print('ok')"
-            % (os.path.join(root, "oracle", "shim"), os.path.join(root, "oracle", "_ref")))
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stderr[-1500:]
+            "assert not os.path.exists(t.__file__[:-1]); print('ok')")
+    shim = os.path.join(ROOT, "oracle", "shim")
+    built = [str(tmp_path / "ref")]
+    if os.path.isdir(os.path.join(ROOT, "oracle", "_ref", "mistral_inference")):
+        built.append(os.path.join(ROOT, "oracle", "_ref"))
+    for ref in built:
+        r = subprocess.run([sys.executable, "-c", code % (shim, ref)], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0 and "ok" in r.stdout, (ref, r.stderr[-1500:])
+
+
+def test_dump_outputs_writes_float_arrays_within_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: one DIR/<name>.npy per output, sampled ids in float64 (exact), the rest in float32; past the size cap an
+    array becomes a fixed seeded sample of its elements, the same in every run."""
+    import numpy as np
+    import torch
+    outs = {"tokens": torch.tensor([[5], [32767], [0]]), "logprobs": torch.tensor([[-0.5], [-1.25], [0.0]]),
+            "logits": torch.arange(4000, dtype=torch.float32).reshape(1, 4000)}
+    bench.dump_outputs(str(tmp_path / "a"), outs)
+    t, lp, lg = (np.load(tmp_path / "a" / f"{n}.npy") for n in ("tokens", "logprobs", "logits"))
+    assert t.dtype == np.float64 and t.tolist() == [[5.0], [32767.0], [0.0]]
+    assert lp.dtype == np.float32 and lg.dtype == np.float32 and lg.shape == (1, 4000) and lg[0, 3999] == 3999.0
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 3 * 8 + 3 * 4 + 1000 * 4)
+    bench.dump_outputs(str(tmp_path / "b"), outs)
+    bench.dump_outputs(str(tmp_path / "c"), outs)
+    s1, s2 = np.load(tmp_path / "b" / "logits.npy"), np.load(tmp_path / "c" / "logits.npy")
+    assert s1.shape == (1000,) and np.array_equal(s1, s2) and np.all(np.diff(s1) > 0)

@@ -115,7 +115,7 @@ def test_bench_two_ranks_prints_one_json_line():
     env = dict(os.environ, MI_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1", MI_DECODE_ENGINE="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29377", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-           "--layers", "4", "--prefill", "256", "--mixtral-layers", "2"]
+           "--layers", "4", "--prefill", "256", "--mixtral-layers", "2", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
