@@ -33,8 +33,10 @@ PER_FILE_FLAGS = {"decode_engine.hip": os.environ.get("MI_ENGINE_FLAGS", "-mllvm
 # (abort word read every 1024th spin; consumers at s_setprio 1; holders fetch from the K/V stage on; the loader's weight DMAs from
 #  inline asm in the SGPR-base form - which is what makes the build WITHOUT the debug stamp sites as fast as the one with them)
 # round 6: + the loader is not stopped during the hid sweep (ENG_NOSTOP=32: the ring is empty there; +0.1..0.7 % on six boxes)
+# round 7: + the holders' loads wait for the loader's ring-full waits or its Wo rows (ENG_HOLD_GATE=1; -1.5 .. -1.9 % per step on
+# three boxes, profiles/EXPERIMENTS.md round 7; a fourth held unit is kept as scripts/probes/decode_engine_round7_hold_split.patch)
 ENGINE_NEXT_FLAGS = ["-DENG_SUFFIX=_next", "-DENG_HEADLINE_ONLY=1", "-DENG_ABORT_RARE=1", "-DENG_CONS_PRIO=1", "-DENG_HOLD_STAGE=2",
-                     "-DENG_SADDR=2", "-DENG_TRACE=0", "-DENG_NOSTOP=32"]
+                     "-DENG_SADDR=2", "-DENG_TRACE=0", "-DENG_NOSTOP=32", "-DENG_HOLD_GATE=1"]
 # round 6: Mistral-Nemo dims (dim 5120: rows of 10 pieces, contiguous units) on the 8-fill ring with every DMA from inline asm
 ENGINE_NEMO_FLAGS = ["-DENG_SUFFIX=_nemo", "-DENG_HEADLINE_ONLY=2", "-DENG_WIDE=2", "-DENG_ABORT_RARE=1", "-DENG_CONS_PRIO=1",
                      "-DENG_SADDR=2", "-DENG_TRACE=0", "-DENG_NOSTOP=32", "-DENG_CLEAN_ENTRY=1"]  # (without the clean entry: 52 leaked

@@ -143,6 +143,22 @@ constexpr int NCONS = 4;
 #ifndef ENG_HOLD_STAGE
 #define ENG_HOLD_STAGE 3  // the holders' fetch of a layer's units may begin when the loader has issued: 0 nothing yet, 1 q|k|v, 2 + K/V, 3 + Wo
 #endif
+// ENG_HOLD_GATE = 1 (round 7, the `next` build): the holders' loads are tied to the window in which this CU's HBM stream idles.
+// The loader raises C_LFULL while it waits for a free ring slot (fill_begin) and sets C_LWO once the layer's Wo rows are issued;
+// a holder issues its next 8 loads only while no sweep is in progress AND (the ring is full OR the Wo rows are on their way),
+// or - whatever the loader does - once ffn_norm(h1) stands in LDS (C_XREADY: the hid values are due, no deadlock).
+#ifndef ENG_HOLD_GATE
+#define ENG_HOLD_GATE 0
+#endif
+// ENG_STALL_TRACE = 1 (with ENG_TRACE = 1): the loader also times its ring-full waits - trace event TR_CONS + 7 of a layer holds
+// the 100 MHz ticks it spent waiting for a free ring slot during the attention block (q|k|v, K/V, Wo: low word) and during the
+// FFN (W1|W3, W2: high word); scripts/engine_trace.py reports them.
+#ifndef ENG_STALL_TRACE
+#define ENG_STALL_TRACE 0
+#endif
+#if ENG_STALL_TRACE && ENG_TRACE != 1
+#error "ENG_STALL_TRACE needs the stamp sites (ENG_TRACE = 1)"
+#endif
 constexpr int NHOLD = ENG_HOLDERS;
 constexpr int NTHREADS = (NCONS + 1 + NHOLD) * 64;
 constexpr int PIECE = 1024;          // bytes per DMA instruction: 64 lanes x 16 B
@@ -185,6 +201,10 @@ enum : int {
   C_XREADY = 13,    // (layer + 1) once ffn_norm(h1) of that layer stands in the activation region (consumers -> holders)
   C_HDONE = 14,     // W1|W3 units finished by holder waves since the launch began (holders -> consumers)
   C_ARRIVED = 15,   // 1 once every workgroup of the launch is known to be resident (consumer wave 0 -> the other waves)
+#if ENG_HOLD_GATE
+  C_LFULL = 16,     // ENG_HOLD_GATE: 1 while the loader waits for a free ring slot (loader -> holders)
+  C_LWO = 17,       // ENG_HOLD_GATE: (layer + 1) once this layer's Wo rows are issued (loader -> holders)
+#endif
   C_XA = 21,        // ENG_QKV_HOLD: (layer + 1) once attention_norm(h) of that layer stands in the activation region (-> holders)
   C_HGO = 23,       // ENG_QKV_HOLD = 2: (layer + 1) once this workgroup has h1 of that layer (the router runs next: no sweep for a while)
   C_HQDONE = 22,    // ENG_QKV_HOLD: holder waves done with their q|k|v units since the launch began (-> consumers)
@@ -337,6 +357,10 @@ struct Loader {
   uint32_t g = 0;    // pieces issued
   uint32_t pub = 0;  // fills published
   uint32_t stalls = 0;  // fills that had to wait for a free ring slot (trace only)
+#if ENG_STALL_TRACE
+  bool ffn = false;                          // from the layer's W1|W3 rows on
+  uint32_t st_attn = 0u, st_ffn = 0u;        // ring-full wait of this layer: attention block, FFN (100 MHz ticks)
+#endif
 #if ENG_SADDR
   uint32_t lane16 = 0;  // this lane's byte offset inside a piece (set by run_loader)
 #endif
@@ -359,9 +383,23 @@ struct Loader {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         publish(f);  // everything issued has landed: consumers must not starve while we wait for them
         ++stalls;
+#if ENG_STALL_TRACE
+        const uint32_t t_stall = (uint32_t)__builtin_amdgcn_s_memrealtime();
+#endif
+#if ENG_HOLD_GATE
+        sh.ctl[C_LFULL] = 1;
+#endif
         uint32_t spins = 0;
         while (min_done() < need)
           if (!spin_ok(sh, spins, 0x100)) break;
+#if ENG_HOLD_GATE
+        sh.ctl[C_LFULL] = 0;
+#endif
+#if ENG_STALL_TRACE
+        const uint32_t dt = (uint32_t)__builtin_amdgcn_s_memrealtime() - t_stall;
+        if (ffn) st_ffn += dt;
+        else st_attn += dt;
+#endif
       }
     }
   }
@@ -659,6 +697,12 @@ __device__ __forceinline__ void run_loader(const EngArgs& a, const Shared& sh, i
     ld.pairs(L.wo, p.o0, p.o1, a.H * DH);
     trace_ev(sh, c, l, TR_CONS + 3, tr);
     if (NHOLD && ENG_HOLD_STAGE == 3) sh.ctl[C_LSTAGE] = (uint32_t)(l + 1);  // the latency-critical small phases are issued: holders may fetch
+#if ENG_HOLD_GATE
+    if (NHOLD) sh.ctl[C_LWO] = (uint32_t)(l + 1);
+#endif
+#if ENG_STALL_TRACE
+    ld.ffn = true;
+#endif
     if constexpr (!MOE) {
       const int f_ring = p.f1 - holder_units(a, p.f1 - p.f0);
       for (int j = p.f0; j < f_ring; ++j) {
@@ -695,6 +739,11 @@ __device__ __forceinline__ void run_loader(const EngArgs& a, const Shared& sh, i
     trace_ev(sh, c, l, TR_CONS + 5, tr);
 #if ENG_TRACE == 1
     if (sh.trace && tr) sh.trace[((size_t)c * ENG_MAXL + l) * TR_EVENTS + TR_CONS + 6] = ld.stalls;
+#if ENG_STALL_TRACE
+    if (sh.trace && tr) sh.trace[((size_t)c * ENG_MAXL + l) * TR_EVENTS + TR_CONS + 7] = ((unsigned long long)ld.st_ffn << 32) | ld.st_attn;
+    ld.ffn = false;
+    ld.st_attn = ld.st_ffn = 0u;
+#endif
 #endif
   }
   if (a.head) {
@@ -2079,6 +2128,78 @@ __device__ __forceinline__ void run_holder(const EngArgs& a, const Shared& sh, i
   }
 }
 
+#if ENG_HOLD_GATE
+// run_holder with the round-7 fetch gate (run_holder itself stays token for token what the frozen default object compiles): the
+// same units, the same loads, the same reduction - only the moments at which the loads are issued differ.
+__device__ __forceinline__ bool hold_may_fetch(const Shared& sh, int l) {
+  if (sh.ctl[C_XREADY] >= (uint32_t)(l + 1)) return true;  // the hid values are due: fetch whatever the loader does
+  return !sh.ctl[C_GATHERING] && (sh.ctl[C_LFULL] || sh.ctl[C_LWO] >= (uint32_t)(l + 1));
+}
+
+__device__ __forceinline__ void run_holder_x(const EngArgs& a, const Shared& sh, int c, int hi, int lane, int pos, uint32_t epoch) {
+  gu64* G = (gu64*)a.gran;
+  const int PD = a.D >> 9;
+  const lchar* xl = sh.xs + lane * 16;
+  for (int l = 0; l < a.n_layers; ++l) {
+    const EngLayer& L = a.L[l];
+    LayerPlan p;
+    plan_layer(a, L, c, pos, p);
+    const int n_hold = holder_units(a, p.f1 - p.f0);
+    if (hi >= n_hold) continue;
+    const int j = p.f1 - n_hold + hi;
+    uint32_t spins = 0;
+    while (sh.ctl[C_LSTAGE] < (uint32_t)(l + 1))  // not before the layer's q|k|v and K/V streams are on their way
+      if (!spin_ok(sh, spins, 0x600)) return;
+    const size_t r0 = (size_t)(2 * j) * a.D + lane * 8;
+    const bf16_t* rows[4] = {L.w1 + r0, L.w3 + r0, L.w1 + r0 + a.D, L.w3 + r0 + a.D};
+    u32x4 hw[HOLD_GROUPS][4][4];  // [group][row][piece in group]: constant indices only -> registers
+#pragma unroll
+    for (int grp = 0; grp < HOLD_GROUPS; ++grp) {
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {  // 8 loads, then look again whether this CU's HBM stream has room for them
+        spins = 0;
+        while (!hold_may_fetch(sh, l))
+          if (!spin_ok(sh, spins, 0x600)) return;
+#pragma unroll
+        for (int r = 2 * half; r < 2 * half + 2; ++r) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int piece = min(grp * 4 + q, PD - 1);  // groups beyond the row are never used (holder_units: PD <= 8)
+            hw[grp][r][q] = ld16_nt(rows[r] + (size_t)piece * 512);
+          }
+        }
+      }
+    }
+    spins = 0;
+    while (sh.ctl[C_XREADY] < (uint32_t)(l + 1))
+      if (!spin_ok(sh, spins, 0x600)) return;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int grp = 0; grp < HOLD_GROUPS; ++grp)
+      if (grp * 4 < PD) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const u32x4 xv = lds16(xl + (grp * 4 + q) * PIECE);
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[r] = dot2_bf16(hw[grp][r][q][i], xv[i], acc[r]);
+        }
+      }
+    float v[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = wave_sum(acc[r]);
+    if (lane == 0) {
+      const uint32_t tag = (epoch << 12) | (uint32_t)((a.seq_base + l) * 8 + 5 + 1);
+      const uint32_t packed = (uint32_t)f_to_bf(swiglu_bf(v[0], v[1])) | ((uint32_t)f_to_bf(swiglu_bf(v[2], v[3])) << 16);
+      __hip_atomic_store(G + a.g_hid + j, ((unsigned long long)tag << 32) | packed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      // the LDS reads of x above were consumed by the dots: the region may be overwritten once every holder says so
+      __hip_atomic_fetch_add((lu32*)(sh.ctl + C_HDONE), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+  }
+}
+#endif
+
 // MOE is a separate instantiation: the dense kernel must not pay registers for the router / two-expert code (it sits at
 // 247 of 256 VGPRs and spilled with the MoE path compiled in)
 template <int R, bool MOE, bool ALL4>
@@ -2115,7 +2236,11 @@ __global__ __launch_bounds__(NTHREADS, 1) void decode_engine_kernel(const EngArg
 #endif
   else if (w > NCONS && MOE) run_qkv_holder(a, sh, c, w - NCONS - 1, lane, pos, seq, epoch);
 #endif
+#if ENG_HOLD_GATE
+  else if (w > NCONS) run_holder_x(a, sh, c, w - NCONS - 1, lane, pos, epoch);
+#else
   else if (w > NCONS) run_holder(a, sh, c, w - NCONS - 1, lane, pos, epoch);
+#endif
   else {
     // residency census: every workgroup counts itself in; consumers check the total before their first side effect
     uint32_t arrive_target = 0;

@@ -133,6 +133,14 @@ ENGINE_SLOTS = {
     "ce_hid": _N0 + _CE + ("-DENG_NOSTOP=32",),
     "ns_ce": _NS + _CE,                                             # (with the stamp sites: timelines)
     "ns_hid": _NS + ("-DENG_NOSTOP=32",),
+    # round 7: the holders' fetch tied to the loader's ring-full waits (ENG_HOLD_GATE; the fourth held unit, ENG_HOLD_SPLIT, is kept as
+    # scripts/probes/decode_engine_round7_hold_split.patch); the t_* slots keep the stamp sites and time the loader's ring-full waits
+    "r7_ce": _N0 + _CE + ("-DENG_NOSTOP=32",),
+    "r7_gate": _N0 + ("-DENG_NOSTOP=32", "-DENG_HOLD_GATE=1"),
+    # timelines of the round-6 and the shipped round-7 flags, built the same way: with the stamp sites and the clean entry (without
+    # it both stamp builds carry 30 / 31 DMA-queue drains in the loader's loops - scripts/engine_loader_waits.py)
+    "r7_t_base": _NS + _CE + ("-DENG_NOSTOP=32", "-DENG_STALL_TRACE=1"),
+    "r7_t_gate": _NS + _CE + ("-DENG_NOSTOP=32", "-DENG_STALL_TRACE=1", "-DENG_HOLD_GATE=1"),
 }
 
 

@@ -99,7 +99,30 @@ def report(t, nl):
     seg = (t[:, 2:nl - 2, 23] - t[:, 2:nl - 2, 18]) * us
     print("loader time per layer: mean %.2f us, min %.2f, max %.2f  (1.70 MB per CU per layer -> %.1f GB/s per CU, %.2f TB/s chip)"
           % (seg.mean(), seg.min(), seg.max(), 1.70e6 / seg.mean() / 1e3, 1.70e6 / seg.mean() / 1e3 * nb / 1e3))
+    ring_full_waits(t, nl)
     handoffs(t, nl)
+
+
+def ring_full_waits(t, nl):
+    """Builds with ENG_STALL_TRACE = 1: how long the loader waited for a free ring slot per layer, split into the attention
+    block (q|k|v, K/V and Wo rows: low word of event 25) and the FFN (W1|W3 and W2 rows: high word).  Other builds leave the
+    event 0 and print nothing here."""
+    w = t[:, :nl, 25].astype(np.int64)
+    if not w.any():
+        return
+    us = 0.01
+    mid = slice(2, max(3, nl - 2))
+    attn = (w[:, mid] & 0xffffffff) * us  # [cu, layer]
+    ffn = ((w[:, mid] >> 32) & 0xffffffff) * us
+    print("\nloader ring-full waits per layer (us; mean over CUs and middle layers | min..max over CUs of the layer mean):")
+    for name, x in (("attention block", attn), ("FFN", ffn), ("whole layer", attn + ffn)):
+        per_cu = x.mean(axis=1)
+        print(f"  {name:16s} {x.mean():7.2f}   {per_cu.min():6.2f} .. {per_cu.max():6.2f}")
+    # where in the layer the waits fall: the consumer-side phase lengths next to them (wave 0, mean over CUs)
+    att_span = ((t[:, mid, 13] - t[:, mid, 0]) * us).mean()
+    ffn_span = ((t[:, mid, 17] - t[:, mid, 13]) * us).mean()
+    print(f"  consumer wave 0: start -> normed2 {att_span:.2f} us (attention block), normed2 -> end {ffn_span:.2f} us (FFN); "
+          f"W1|W3 phase {((t[:, mid, 14] - t[:, mid, 13]) * us).mean():.2f} us")
 
 
 def handoffs(t, nl):
