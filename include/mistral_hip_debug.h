@@ -27,15 +27,23 @@ int mi_debug_set_engine_trace(void* dev_buffer);
 int mi_debug_set_engine_knobs(int thin, int depth);
 /* holder waves on (1) / off (0) / environment default (-1); results never depend on it (bit-identical either way) */
 int mi_debug_set_engine_holders(int on);
-/* The engine source is compiled four times: the default build (frozen since round 3: dense models), the `next` build (round 5:
- * the dense GQA-4 shapes whose rows are multiples of 4 pieces, i.e. the headline model), a "wide" build for the shapes those
- * decline (GQA ratio 6 with a 32 KiB hid vector; rows of an even number of pieces that is not a multiple of 4) and a MoE build
- * (Mixtral-8x7B shapes).  0 (default; environment MI_ENGINE_VARIANT): dense models the `next` build where it applies, else the
- * default build; MoE models the MoE build, else the wide build; 1: the wide build wherever it applies (tests compare its code
- * paths with the launch path at small sizes; also admits shapes that measured slower than the launch path); 2: the default
- * (frozen) build first for every model - the A/B partner of `next`, and the build that carries the timeline stamp sites.
- * Returns the previous setting. */
+/* The engine source is compiled once per build (csrc/kernels.h: EngineBuild): `default` (frozen since round 3: dense models),
+ * `next` (the dense GQA-4 shapes whose rows are multiples of 4 pieces, i.e. the headline model), `nemo` (dense GQA-4 models of a
+ * large dim whose rows are not: Mistral-Nemo; opt-in, MI_ENGINE_NEMO=1), `wide` (GQA ratio 6 with a 32 KiB hid vector; rows of an
+ * even number of pieces that is not a multiple of 4) and `moe` (Mixtral-8x7B shapes).  A further build is its flags in
+ * build_native.py, one accessor in kernels.h, one line in api.hip's kBuilds and one clause in its engine_route().
+ * 0 (default; environment MI_ENGINE_VARIANT): dense models the `next` build where it applies, else the default build; MoE models
+ * the MoE build, else the wide build; 1: the wide build wherever it applies (tests compare its code paths with the launch path
+ * at small sizes; also admits shapes that measured slower than the launch path); 2: the default (frozen) build first for every
+ * model - the A/B partner of `next`, and the build that carries the timeline stamp sites; 3: as 2 with the `nemo` build first
+ * where it applies (tests).  Returns the previous setting. */
 int mi_debug_set_engine_variant(int variant);
+/* Which engine builds mi_forward would try, in order, for a batch-1 decode step of a model with these dimensions (every layer's
+ * K/V ring of cache_size slots, a device of n_cus CUs, engine variant as above, nemo_opt_in = MI_ENGINE_NEMO): writes their
+ * names comma-separated ("next,default", "moe", ... ; "" = launch path).  Pure host arithmetic; touches no device and no global
+ * state. */
+int mi_debug_engine_route(int dim, int n_heads, int n_kv_heads, int hidden_dim, int vocab, int num_experts, int top_k,
+                          int n_layers, int cache_size, int n_cus, int variant, int nemo_opt_in, char* out, size_t out_len);
 /* Test hook: the next `launches` engine launches on this workspace (hipGraph replays included: the count lives in the
  * workspace) wait for one workgroup more than exist, i.e. fail their residency gate after its ~50 ms bound exactly as a
  * launch with a missing workgroup would (status 0x700, nothing written).  Synchronises the stream. */

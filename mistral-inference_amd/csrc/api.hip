@@ -18,13 +18,8 @@
 #include "../../include/mistral_hip_debug.h"
 #include "kernels.h"
 
-#ifdef MI_SLOT_LIST  // experiment libraries: see g_slots below
-#define X(n)                                                                         \
-  bool decode_engine_applicable_x##n(const EngProblem&, char*, size_t);             \
-  hipError_t launch_decode_engine_x##n(const EngProblem&, hipStream_t, bool*);      \
-  void decode_engine_set_trace_x##n(void*);                                          \
-  void decode_engine_set_knobs_x##n(int, int);                                       \
-  void decode_engine_set_holders_x##n(int);
+#ifdef MI_SLOT_LIST  // experiment libraries: see kBuilds below
+#define X(n) const EngineBuild& decode_engine_build_x##n();
 MI_SLOT_LIST
 #undef X
 #endif
@@ -77,23 +72,49 @@ int engine_variant() {
   }
   return g_engine_variant;
 }
-// Experiment libraries only (scripts/build_variants.py engine_slots -> -DMI_SLOT_LIST="X(0) X(1) ..."): further compiles of the
-// engine source under the names *_x<N>, selected at run time by mi_debug_set_engine_slot (scripts/engine_ab.py: one process,
-// one set of weights, every variant timed in turn on the same box).  Not compiled into the shipped library.
+// Every compile of the engine source (kernels.h: EngineBuild).  Experiment libraries (scripts/build_variants.py engine_slots ->
+// -DMI_SLOT_LIST="X(0) X(1) ...") append further compiles under the names *_x<N>, selected at run time by mi_debug_set_engine_slot
+// (scripts/engine_ab.py: one process, one set of weights, every slot timed in turn on the same box).
+enum { B_DEFAULT, B_NEXT, B_NEMO, B_WIDE, B_MOE, N_SHIPPED };
 #ifdef MI_SLOT_LIST
-struct EngSlot {
-  bool (*applicable)(const EngProblem&, char*, size_t);
-  hipError_t (*launch)(const EngProblem&, hipStream_t, bool*);
-  void (*set_trace)(void*);
-  void (*set_knobs)(int, int);
-  void (*set_holders)(int);
-};
-#define X(n) {decode_engine_applicable_x##n, launch_decode_engine_x##n, decode_engine_set_trace_x##n, decode_engine_set_knobs_x##n, decode_engine_set_holders_x##n},
-const EngSlot g_slots[] = {MI_SLOT_LIST};
-#undef X
-constexpr int N_SLOTS = (int)(sizeof(g_slots) / sizeof(g_slots[0]));
-int g_slot = -1;
+#define X(n) &decode_engine_build_x##n(),
+#define ENGINE_SLOTS MI_SLOT_LIST
+#else
+#define ENGINE_SLOTS
 #endif
+const EngineBuild* const kBuilds[] = {&decode_engine_build(), &decode_engine_build_next(), &decode_engine_build_nemo(),
+                                      &decode_engine_build_wide(), &decode_engine_build_moe(), ENGINE_SLOTS};
+constexpr int N_SLOTS = (int)(sizeof(kBuilds) / sizeof(kBuilds[0])) - N_SHIPPED;
+int g_slot = -1;  // experiment slot that mi_forward tries first (-1: none)
+
+// Which builds a batch-1 decode step tries, in order: calls try_build(build) for each applicable one until it returns true (the
+// step is finished, or failed); a build whose launch declined (residency census) returns false and the next stage is asked.
+// Lazy: on the headline model `next` is the only applicable() called per step.  variant: mi_debug_set_engine_variant;
+// pr.forced = (variant == 1) is the caller's.  Returns whether a try_build returned true (false: take the launch path).
+template <class Try>
+bool engine_route(int variant, bool nemo_opt_in, const EngineBuild* slot, const EngProblem& pr, Try&& try_build) {
+  const bool moe = pr.E > 0;
+  auto takes = [&](int b) { return kBuilds[b]->applicable(pr, nullptr, 0); };
+  if (slot && slot->applicable(pr, nullptr, 0) && try_build(*slot)) return true;
+  // the dense GQA-4 headline shapes: the `next` compile (build_native.ENGINE_NEXT_FLAGS)
+  if (!moe && variant == 0 && takes(B_NEXT) && try_build(*kBuilds[B_NEXT])) return true;
+  // large dims whose rows are not multiples of 4 pieces (Mistral-Nemo): the `nemo` compile - bit-equal, in a clean regime
+  // (scripts/engine_loader_waits.py) and still 4 % slower than the launch path at those dims (contiguous 20- / 40-piece units:
+  // four consumer waves cannot all hold one in the 128-piece ring), so it is opt-in: MI_ENGINE_NEMO=1 or engine variant 3 (tests)
+  if (!moe && (variant == 3 || (variant == 0 && nemo_opt_in)) && takes(B_NEMO) && try_build(*kBuilds[B_NEMO])) return true;
+  // Exactly one of the rest.  MoE models: the 8-fill MoE build where the model fits it (Mixtral-8x7B), else the 7-fill wide build
+  // (Mixtral-8x22B) wherever it applies - both carry the round-4 router (two experts per wave, batched loads: -8..-11 us per
+  // layer), which the default object - frozen, see decode_engine.hip - does not.  Dense models: the default build, and the wide
+  // one for what it declines (GQA ratio 6; rows of 10 pieces when forced).  Variant 1 (tests) prefers the wide build wherever
+  // it applies, so that its code paths can be compared bit for bit at small sizes; variant 2 = default build first for every model.
+  const bool wide_first = variant == 1 || (variant == 0 && moe);
+  const int last = (moe && variant == 0 && takes(B_MOE)) ? B_MOE
+                   : (wide_first && takes(B_WIDE))       ? B_WIDE
+                   : takes(B_DEFAULT)                    ? B_DEFAULT
+                   : (!wide_first && takes(B_WIDE))      ? B_WIDE
+                                                         : -1;
+  return last >= 0 && try_build(*kBuilds[last]);
+}
 int engine_mode() {
   if (g_engine_mode < 0) {
     const char* e = getenv("MI_DECODE_ENGINE");
@@ -524,11 +545,8 @@ int mi_debug_engine_sabotage(void* workspace, int launches, mi_stream_t stream) 
 }
 
 int mi_decode_engine_census(int forget) {
-  if (forget) decode_engine_forget_census_next();
-  if (forget) decode_engine_forget_census_nemo();
-  if (forget) decode_engine_forget_census_wide();
-  if (forget) decode_engine_forget_census_moe();
-  if (forget) decode_engine_forget_census();
+  if (forget)
+    for (const EngineBuild* b : kBuilds) b->forget_census();
   return MI_OK;
 }
 
@@ -540,31 +558,35 @@ int mi_decode_engine_status(const void* workspace, mi_stream_t stream, uint32_t 
 
 size_t mi_debug_engine_trace_bytes(void) { return decode_engine_trace_bytes(device_cus()); }
 int mi_debug_set_engine_knobs(int thin, int depth) {
-  decode_engine_set_knobs(thin, depth);
-  decode_engine_set_knobs_next(thin, depth);
-  decode_engine_set_knobs_nemo(thin, depth);
-#ifdef MI_SLOT_LIST
-  for (const EngSlot& sl : g_slots) sl.set_knobs(thin, depth);
-#endif
-  decode_engine_set_knobs_wide(thin, depth);
-  decode_engine_set_knobs_moe(thin, depth);
+  for (const EngineBuild* b : kBuilds) b->set_knobs(thin, depth);
   return MI_OK;
 }
 int mi_debug_set_engine_holders(int on) {
-  decode_engine_set_holders(on);
-  decode_engine_set_holders_next(on);
-  decode_engine_set_holders_nemo(on);
-#ifdef MI_SLOT_LIST
-  for (const EngSlot& sl : g_slots) sl.set_holders(on);
-#endif
-  decode_engine_set_holders_wide(on);
-  decode_engine_set_holders_moe(on);
+  for (const EngineBuild* b : kBuilds) b->set_holders(on);
   return MI_OK;
 }
 int mi_debug_set_engine_variant(int variant) {
   const int prev = engine_variant();
   g_engine_variant = variant < 0 || variant > 3 ? 0 : variant;
   return prev;
+}
+int mi_debug_engine_route(int dim, int n_heads, int n_kv_heads, int hidden_dim, int vocab, int num_experts, int top_k, int n_layers,
+                          int cache_size, int n_cus, int variant, int nemo_opt_in, char* out, size_t out_len) {
+  if (!out || !out_len || n_layers <= 0 || n_layers > 4096 || n_cus <= 0) return fail(MI_ERR_ARG, "mi_debug_engine_route");
+  int32_t W[4096];
+  for (int l = 0; l < n_layers; ++l) W[l] = cache_size;
+  EngProblem pr;
+  memset(&pr, 0, sizeof(pr));
+  pr.D = dim; pr.H = n_heads; pr.Hkv = n_kv_heads; pr.F = hidden_dim; pr.V = vocab; pr.n_layers = n_layers; pr.NB = n_cus;
+  pr.E = num_experts; pr.top_k = top_k; pr.W = W;
+  pr.forced = variant == 1;
+  size_t n = 0;
+  out[0] = 0;
+  engine_route(variant, nemo_opt_in != 0, nullptr, pr, [&](const EngineBuild& b) {  // "declined": the whole chain is listed
+    if (n < out_len) n += snprintf(out + n, out_len - n, "%s%s", n ? "," : "", b.name);
+    return false;
+  });
+  return n < out_len ? MI_OK : fail(MI_ERR_ARG, "mi_debug_engine_route: out_len %zu", out_len);
 }
 #ifdef MI_SLOT_LIST
 extern "C" int mi_debug_set_engine_slot(int slot) {  // -1: the library's own routing; returns the number of slots
@@ -578,14 +600,7 @@ int mi_debug_set_prefill_kernels(int attn_waves, int gemm_tail) {
   return MI_OK;
 }
 int mi_debug_set_engine_trace(void* dev_buffer) {
-  decode_engine_set_trace(dev_buffer);
-  decode_engine_set_trace_next(dev_buffer);
-  decode_engine_set_trace_nemo(dev_buffer);
-#ifdef MI_SLOT_LIST
-  for (const EngSlot& sl : g_slots) sl.set_trace(dev_buffer);
-#endif
-  decode_engine_set_trace_wide(dev_buffer);
-  decode_engine_set_trace_moe(dev_buffer);
+  for (const EngineBuild* b : kBuilds) b->set_trace(dev_buffer);
   return MI_OK;
 }
 
@@ -664,69 +679,20 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
     for (int l = 0; l < m->n_layers; ++l)
       dense_ok = dense_ok && (m->num_experts ? (m->layers[l].gate && m->layers[l].expert_w_dev)
                                              : (m->layers[l].w1 && m->layers[l].w2 && m->layers[l].w3));
-    // the shipped build of the engine first (the headline shapes); the "wide" build of the same source for what it declines
-    // (GQA ratio 6 + 32 KiB hid vector: Mixtral-8x22B; rows of 10 pieces: Mistral-Nemo).  g_engine_variant = 1 (tests) prefers
-    // the wide build wherever it applies, so that its code paths can be compared bit for bit at small sizes.
-    // MoE models take the wide build wherever it applies: it carries the round-4 router (two experts per wave, batched loads:
-    // -8..-11 us per layer), which the shipped object - frozen, see decode_engine.hip - does not.  Variant 2 = shipped build
-    // first for every model (the A/B of that choice).
-    // (MoE: the 8-fill MoE build where the model fits it - Mixtral-8x7B -, else the 7-fill wide build - Mixtral-8x22B.)
-#ifdef MI_SLOT_LIST
-    if (g_slot >= 0 && dense_ok && g_slots[g_slot].applicable(pr, nullptr, 0)) {
+    const EngineBuild* slot = g_slot >= 0 ? kBuilds[N_SHIPPED + g_slot] : nullptr;
+    int rc = MI_OK;
+    auto try_build = [&](const EngineBuild& b) {  // true: the step is finished, rc says how; false: the build declined
       bool declined = false;
-      MI_TRY(hip_rc(g_slots[g_slot].launch(pr, s, &declined), "decode engine (experiment slot)"));
-      if (!declined) {
-        if (m->final_norm && !bt->logits) MI_TRY(hip_rc(launch_rmsnorm(h, h, m->final_norm, T, D, m->norm_eps, s), "final norm"));
-        if (want_topp) MI_TRY(sample_step());
-        return MI_OK;
+      rc = hip_rc(b.launch(pr, s, &declined), &b == slot ? "decode engine (experiment slot)" : "decode engine");
+      if (rc == MI_OK && declined) {
+        if (&b != slot) snprintf(g_detail, sizeof(g_detail), "decode engine declined: %s", b.census_detail());  // informational
+        return false;
       }
-    }
-#endif
-    // the dense GQA-4 headline shapes take the `next` compile (build_native.ENGINE_NEXT_FLAGS: abort word read rarely, consumers at
-    // s_setprio 1, holders fetch from the K/V stage on, every DMA from inline asm in the SGPR-base form, no stamp sites, the
-    // loader not stopped during the hid sweep)
-    const bool next_ok = dense_ok && m->num_experts == 0 && engine_variant() == 0 && decode_engine_applicable_next(pr, nullptr, 0);
-    if (next_ok) {
-      bool declined = false;
-      MI_TRY(hip_rc(launch_decode_engine_next(pr, s, &declined), "decode engine"));
-      if (!declined) {
-        if (m->final_norm && !bt->logits) MI_TRY(hip_rc(launch_rmsnorm(h, h, m->final_norm, T, D, m->norm_eps, s), "final norm"));
-        if (want_topp) MI_TRY(sample_step());
-        return MI_OK;
-      }
-      snprintf(g_detail, sizeof(g_detail), "decode engine declined: %s", decode_engine_census_detail_next());  // informational
-    }
-    // large dims whose rows are not multiples of 4 pieces (Mistral-Nemo): the `nemo` compile - bit-equal, in a clean regime
-    // (scripts/engine_loader_waits.py) and still 4 % slower than the launch path at those dims (contiguous 20- / 40-piece units:
-    // four consumer waves cannot all hold one in the 128-piece ring), so it is opt-in: MI_ENGINE_NEMO=1 or engine variant 3 (tests)
-    const bool nemo_ok = dense_ok && m->num_experts == 0 && (engine_variant() == 3 || (engine_variant() == 0 && nemo_engine_enabled())) &&
-                         decode_engine_applicable_nemo(pr, nullptr, 0);
-    if (nemo_ok) {
-      bool declined = false;
-      MI_TRY(hip_rc(launch_decode_engine_nemo(pr, s, &declined), "decode engine"));
-      if (!declined) {
-        if (m->final_norm && !bt->logits) MI_TRY(hip_rc(launch_rmsnorm(h, h, m->final_norm, T, D, m->norm_eps, s), "final norm"));
-        if (want_topp) MI_TRY(sample_step());
-        return MI_OK;
-      }
-      snprintf(g_detail, sizeof(g_detail), "decode engine declined: %s", decode_engine_census_detail_nemo());  // informational
-    }
-    const bool moe_ok = dense_ok && m->num_experts > 0 && engine_variant() == 0 && decode_engine_applicable_moe(pr, nullptr, 0);
-    const bool wide_ok = !moe_ok && dense_ok && decode_engine_applicable_wide(pr, nullptr, 0);
-    const bool wide_first = engine_variant() == 1 || (engine_variant() == 0 && m->num_experts > 0);
-    const bool base_ok = !moe_ok && dense_ok && !(wide_first && wide_ok) && decode_engine_applicable(pr, nullptr, 0);
-    if (moe_ok || base_ok || wide_ok) {
-      bool declined = false;
-      MI_TRY(hip_rc(moe_ok ? launch_decode_engine_moe(pr, s, &declined)
-                           : (base_ok ? launch_decode_engine(pr, s, &declined) : launch_decode_engine_wide(pr, s, &declined)), "decode engine"));
-      if (!declined) {
-        if (m->final_norm && !bt->logits) MI_TRY(hip_rc(launch_rmsnorm(h, h, m->final_norm, T, D, m->norm_eps, s), "final norm"));
-        if (want_topp) MI_TRY(sample_step());
-        return MI_OK;
-      }
-      snprintf(g_detail, sizeof(g_detail), "decode engine declined: %s",
-               moe_ok ? decode_engine_census_detail_moe() : (base_ok ? decode_engine_census_detail() : decode_engine_census_detail_wide()));  // informational
-    }
+      if (rc == MI_OK && m->final_norm && !bt->logits) rc = hip_rc(launch_rmsnorm(h, h, m->final_norm, T, D, m->norm_eps, s), "final norm");
+      if (rc == MI_OK && want_topp) rc = sample_step();
+      return true;
+    };
+    if (dense_ok && engine_route(engine_variant(), nemo_engine_enabled(), slot, pr, try_build)) return rc;
   }
 
   if (branch == MI_BRANCH_DECODE && embed) {

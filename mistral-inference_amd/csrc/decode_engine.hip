@@ -61,25 +61,25 @@
 #endif
 #define ENG_CAT_(a, b) a##b
 #define ENG_CAT(a, b) ENG_CAT_(a, b)
+#define ENG_STR_(x) #x
+#define ENG_STR(x) ENG_STR_(x)
+// What needs a linker name of its own per compile: the accessor to this build's descriptor (kernels.h: EngineBuild, at the end of
+// this file) and the census kernel.  Every other host function is local to the object.
 #if defined(ENG_SUFFIX)
 #define ENG_NAME(x) ENG_CAT(x, ENG_SUFFIX)
+#define ENG_BUILD_NAME (ENG_STR(ENG_SUFFIX) + 1)  // "_next" -> "next"
 #elif ENG_WIDE == 1
 #define ENG_NAME(x) x##_wide
+#define ENG_BUILD_NAME "wide"
 #elif ENG_WIDE == 2
 #define ENG_NAME(x) x##_moe
+#define ENG_BUILD_NAME "moe"
+#else
+#define ENG_NAME(x) x
+#define ENG_BUILD_NAME "default"
+#define ENG_DEFAULT_BUILD 1
 #endif
-#if ENG_WIDE || defined(ENG_SUFFIX)
-#define launch_decode_engine ENG_NAME(launch_decode_engine)
-#define decode_engine_applicable ENG_NAME(decode_engine_applicable)
-#define decode_engine_granule_bytes ENG_NAME(decode_engine_granule_bytes)
-#define decode_engine_set_holders ENG_NAME(decode_engine_set_holders)
-#define decode_engine_set_knobs ENG_NAME(decode_engine_set_knobs)
-#define decode_engine_set_trace ENG_NAME(decode_engine_set_trace)
-#define decode_engine_trace_bytes ENG_NAME(decode_engine_trace_bytes)
-#define decode_engine_census_detail ENG_NAME(decode_engine_census_detail)
-#define decode_engine_forget_census ENG_NAME(decode_engine_forget_census)
 #define engine_census_kernel ENG_NAME(engine_census_kernel)
-#endif
 
 namespace {
 
@@ -2285,13 +2285,16 @@ GranLayout gran_layout(int D, int H, int Hkv, int F, int max_splits) {
 }
 }  // namespace
 
+#ifdef ENG_DEFAULT_BUILD  // the same for every build: compiled into the default object only
 size_t decode_engine_granule_bytes(int D, int H, int Hkv, int F, int maxW) {
   if (Hkv <= 0 || H % Hkv) return 0;
   (void)maxW;  // sized for the maximum of 32 splits so that the layout depends on the model only
   return (size_t)gran_layout(D, H, Hkv, F, 32).total * 8;
 }
+size_t decode_engine_trace_bytes(int NB) { return (size_t)NB * ENG_MAXL * TR_EVENTS * sizeof(uint64_t); }
+#endif
 
-bool decode_engine_applicable(const EngProblem& pr, char* why, size_t why_len) {
+static bool decode_engine_applicable(const EngProblem& pr, char* why, size_t why_len) {
   auto no = [&](const char* m) {
     if (why) snprintf(why, why_len, "%s", m);
     return false;
@@ -2375,14 +2378,13 @@ bool decode_engine_applicable(const EngProblem& pr, char* why, size_t why_len) {
 namespace {
 uint64_t* g_trace = nullptr;
 int g_thin = -1, g_depth = -1, g_holders = -1;
-}
 void decode_engine_set_holders(int on) { g_holders = on; }
 void decode_engine_set_knobs(int thin, int depth) {
   g_thin = thin;
   g_depth = depth;
 }
 void decode_engine_set_trace(void* dev_buffer) { g_trace = (uint64_t*)dev_buffer; }
-size_t decode_engine_trace_bytes(int NB) { return (size_t)NB * ENG_MAXL * TR_EVENTS * sizeof(uint64_t); }
+}  // namespace
 
 // ---- residency census (once per device and process, outside any stream capture) ------------------------------------------
 // The engine's hand-offs need all NB workgroups resident at once.  hipOccupancy... answers for an empty device; a CU mask,
@@ -2435,11 +2437,11 @@ int engine_census(int dev, int nb, uint32_t* ctrl, hipStream_t s) {
   }
   return g_census[dev] = 1;
 }
-}  // namespace
 const char* decode_engine_census_detail() { return g_census_why; }
 void decode_engine_forget_census() { memset(g_census, 0, sizeof(g_census)); }
+}  // namespace
 
-hipError_t launch_decode_engine(const EngProblem& pr, hipStream_t s, bool* declined) {
+static hipError_t launch_decode_engine(const EngProblem& pr, hipStream_t s, bool* declined) {
   if (declined) *declined = false;
   int dev = 0;
   (void)hipGetDevice(&dev);
@@ -2551,4 +2553,13 @@ hipError_t launch_decode_engine(const EngProblem& pr, hipStream_t s, bool* decli
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+// This compile's descriptor.  (A function-local static: a namespace-scope object would also be emitted by the device pass, whose
+// link then misses the host functions it names.)
+const EngineBuild& ENG_NAME(decode_engine_build)() {
+  static const EngineBuild build = {ENG_BUILD_NAME, decode_engine_applicable, launch_decode_engine, decode_engine_census_detail,
+                                    decode_engine_forget_census, decode_engine_set_trace, decode_engine_set_knobs,
+                                    decode_engine_set_holders};
+  return build;
 }

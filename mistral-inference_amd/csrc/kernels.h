@@ -282,58 +282,33 @@ struct EngProblem {
   int forced;                // mi_debug_set_engine_variant(1): take shapes that measured slower than the launch path too (traces, tests)
 };
 static_assert(sizeof(EngArgs) <= 4096, "EngArgs must fit the kernel-argument segment");
-size_t decode_engine_granule_bytes(int D, int H, int Hkv, int F, int maxW);
-bool decode_engine_applicable(const EngProblem& pr, char* why, size_t why_len);
-// *declined = true (and nothing enqueued): the residency census failed on this device - take the launch path
-hipError_t launch_decode_engine(const EngProblem& pr, hipStream_t s, bool* declined);
-const char* decode_engine_census_detail();
-void decode_engine_forget_census();  // tests
-void decode_engine_set_trace(void* dev_buffer);  // debug: nullptr disables
-void decode_engine_set_knobs(int thin, int depth);  // debug / tuning
-void decode_engine_set_holders(int on);             // debug / A/B: -1 = environment default
-
+size_t decode_engine_granule_bytes(int D, int H, int Hkv, int F, int maxW);  // the same for every build (default object only)
 size_t decode_engine_trace_bytes(int NB);
-// The same source compiled a second time with -DENG_WIDE=1 (decode_engine_wide.o): the shapes the shipped instantiations
-// decline - GQA ratio 6 with a 32 KiB hid vector (Mixtral-8x22B: 7-fill ring), rows of an even number of pieces that is not a
-// multiple of 4 (Mistral-Nemo: contiguous units).  Same EngProblem, same granule layout, bit-identical results.
-bool decode_engine_applicable_wide(const EngProblem& pr, char* why, size_t why_len);
-hipError_t launch_decode_engine_wide(const EngProblem& pr, hipStream_t s, bool* declined);
-const char* decode_engine_census_detail_wide();
-void decode_engine_forget_census_wide();
-void decode_engine_set_trace_wide(void* dev_buffer);
-void decode_engine_set_knobs_wide(int thin, int depth);
-void decode_engine_set_holders_wide(int on);
-// ... and a third time with -DENG_WIDE=2 (decode_engine_moe.o): the wide build's additions on the shipped 8-fill ring, for MoE
-// models whose hid vector fits beside it (Mixtral-8x7B: the four consumers' W1|W3 units span exactly 8 fills at dim 4096).
-bool decode_engine_applicable_moe(const EngProblem& pr, char* why, size_t why_len);
-hipError_t launch_decode_engine_moe(const EngProblem& pr, hipStream_t s, bool* declined);
-const char* decode_engine_census_detail_moe();
-void decode_engine_forget_census_moe();
-void decode_engine_set_trace_moe(void* dev_buffer);
-void decode_engine_set_knobs_moe(int thin, int depth);
-void decode_engine_set_holders_moe(int on);
-// ... and a fourth time (decode_engine_next.o: -DENG_SUFFIX=_next -DENG_HEADLINE_ONLY=1 + build_native.ENGINE_NEXT_FLAGS:
-// ENG_ABORT_RARE, ENG_CONS_PRIO, ENG_HOLD_STAGE=2, ENG_SADDR=2, ENG_TRACE=0, ENG_NOSTOP=32): the dense GQA-4 shapes with rows of
-// 4-piece groups, i.e. the headline model.  The default object stays in the library (every other dense shape;
-// MI_ENGINE_VARIANT=2 routes the headline to it for A/B).
-bool decode_engine_applicable_next(const EngProblem& pr, char* why, size_t why_len);
-hipError_t launch_decode_engine_next(const EngProblem& pr, hipStream_t s, bool* declined);
-const char* decode_engine_census_detail_next();
-void decode_engine_forget_census_next();
-void decode_engine_set_trace_next(void* dev_buffer);
-void decode_engine_set_knobs_next(int thin, int depth);
-void decode_engine_set_holders_next(int on);
-// ... and a fifth time (round 6, decode_engine_nemo.o: build_native.ENGINE_NEMO_FLAGS): dense GQA-4 models of a large dim whose
-// rows are not multiples of 4 pieces - Mistral-Nemo (dim 5120).  Rounds 4-5 measured such dims slower on the wide build than on
-// the launch path; round 6 found that build's dense kernels in the slow regime (hipcc drains the builtin-DMA queue in
-// fill_begin: scripts/engine_loader_waits.py) - this build issues every DMA from inline asm.
-bool decode_engine_applicable_nemo(const EngProblem& pr, char* why, size_t why_len);
-hipError_t launch_decode_engine_nemo(const EngProblem& pr, hipStream_t s, bool* declined);
-const char* decode_engine_census_detail_nemo();
-void decode_engine_forget_census_nemo();
-void decode_engine_set_trace_nemo(void* dev_buffer);
-void decode_engine_set_knobs_nemo(int thin, int depth);
-void decode_engine_set_holders_nemo(int on);
+// decode_engine.hip is compiled once per build below (build_native.py: VARIANT_OBJECTS); every compile exports one accessor to
+// this descriptor and nothing else.  Same EngProblem, same granule layout, bit-identical results.
+struct EngineBuild {
+  const char* name;  // "default", "next", "nemo", "wide", "moe"; "x<N>": a slot of an experiment library
+  bool (*applicable)(const EngProblem& pr, char* why, size_t why_len);
+  // *declined = true (and nothing enqueued): the residency census failed on this device - take the launch path
+  hipError_t (*launch)(const EngProblem& pr, hipStream_t s, bool* declined);
+  const char* (*census_detail)();
+  void (*forget_census)();                 // tests
+  void (*set_trace)(void* dev_buffer);     // debug: nullptr disables
+  void (*set_knobs)(int thin, int depth);  // debug / tuning
+  void (*set_holders)(int on);             // debug / A/B: -1 = environment default
+};
+// frozen since round 3: every dense shape the others decline; MI_ENGINE_VARIANT=2 routes the headline to it for A/B
+const EngineBuild& decode_engine_build();
+// build_native.ENGINE_NEXT_FLAGS: the dense GQA-4 shapes with rows of 4-piece groups, i.e. the headline model
+const EngineBuild& decode_engine_build_next();
+// build_native.ENGINE_NEMO_FLAGS: dense GQA-4 models of a large dim whose rows are not multiples of 4 pieces (Mistral-Nemo, dim
+// 5120), every DMA from inline asm (the wide build's dense kernels drain the builtin-DMA queue: scripts/engine_loader_waits.py)
+const EngineBuild& decode_engine_build_nemo();
+// -DENG_WIDE=1: GQA ratio 6 with a 32 KiB hid vector (Mixtral-8x22B: 7-fill ring), rows of an even number of pieces that is not
+// a multiple of 4 (contiguous units)
+const EngineBuild& decode_engine_build_wide();
+// -DENG_WIDE=2: the wide build's additions on the 8-fill ring, for MoE models whose hid vector fits beside it (Mixtral-8x7B)
+const EngineBuild& decode_engine_build_moe();
 
 // ---------------------------------------------------------------------------------------------- generic storage dtype
 // generic.hip: the operator sequence of the hot path for fp32 / fp16 storage (and for bf16 shapes the tuned kernels

@@ -120,6 +120,7 @@ _SIGS = {
     "mi_debug_engine_sabotage": (C.c_int, [_vp, C.c_int, _vp]),
     "mi_debug_set_engine_holders": (C.c_int, [C.c_int]),
     "mi_debug_set_engine_variant": (C.c_int, [C.c_int]),
+    "mi_debug_engine_route": (C.c_int, [C.c_int] * 12 + [C.c_char_p, C.c_size_t]),
     "mi_debug_set_prefill_kernels": (C.c_int, [C.c_int, C.c_int]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)

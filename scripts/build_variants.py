@@ -106,8 +106,10 @@ FILE_VARIANTS = {
 _AP = ("-DENG_ABORT_RARE=1", "-DENG_CONS_PRIO=1")   # round-5 calls 1-2: abort word read rarely (-0.8 %), consumers at priority 1 (-0.25 %)
 _NS = _AP + ("-DENG_HOLD_STAGE=2", "-DENG_SADDR=2")
 _CE = ("-DENG_CLEAN_ENTRY=1",)                     # round 6: the loader's wait-count scoreboard emptied at its entry (decode_engine.hip)
-_N0 = _NS + ("-DENG_TRACE=0",)                      # = build_native.ENGINE_NEXT_FLAGS (the shipped headline build) without its suffix
+_N0 = _NS + ("-DENG_TRACE=0",)                      # the round-5 shipped flags (the slots below are the record of what was measured)
 ENGINE_SLOTS = {
+    # today's shipped headline build, whatever it is (build_engine_slots supplies the suffix and ENG_HEADLINE_ONLY)
+    "shipped": tuple(f for f in b.ENGINE_NEXT_FLAGS if not f.startswith(("-DENG_SUFFIX=", "-DENG_HEADLINE_ONLY="))),
     "copy": (),
     "nx": _AP + ("-DENG_HOLD_STAGE=2",),
     "ns": _NS,
