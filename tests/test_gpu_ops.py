@@ -343,6 +343,10 @@ def test_attn_prefill(H, Hkv, W, seen, new):
             ref = mo._attend(rows[:, :nq].reshape(s, H, Dh), keys, vals, torch.arange(p, p + s), kpos, W, causal=True)
         # P is rounded to bf16 for the P.V MFMA (as in every flash kernel, xformers' included; SURVEY.md
         # Appendix A): absolute error <= ~2^-9 * max|V| + one output rounding, independent of |out|
+        # What this bound sees at W = 4096: with N(0,1) inputs the output there has rms 2.5e-2 and max 0.15, so 2.5e-2 is about the
+        # size of the signal - gross damage only.  A window that is off by one key ((4096, [4096], [2048]) with kp = qp - W visible)
+        # moves the output by 1.0e-2 and passes, and no row rescales after its first tile.  Single keys and the rescale are held by
+        # test_gpu_attn_structured.py (inputs and measured teeth: attn_cases.py).
         err = (got[o:o + s].float() - ref.float()).abs().max().item()
         assert err <= 2.5e-2, (b, err)
         o += s
