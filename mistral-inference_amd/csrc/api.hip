@@ -186,9 +186,62 @@ Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base) {
   return w;
 }
 
+// ---- GemvArgs of the fused modes, one builder each: the only places in this file that name the mode (mi_linear maps the
+// public epilogue codes itself).  Pointers are to 2-byte elements of either compile of gemv.hip; T is set per pass below.
+GemvArgs gemv_common(const void* x, int ldx, int K, int N, const void* norm_w, float eps, void* out, int ldo) {
+  GemvArgs a;
+  memset(&a, 0, sizeof(a));
+  a.K = K; a.N = N; a.x = (const bf16_t*)x; a.ldx = ldx; a.norm_w = (const bf16_t*)norm_w; a.eps = eps; a.out = out; a.ldo = ldo;
+  return a;
+}
+struct RingWrite {  // the K/V ring of one layer, for the launch whose epilogue writes it
+  void *k, *v;
+  int W, layout;
+};
+// qkv[T, ldo] = rope(rmsnorm(x) @ [wq; wk; wv]^T); ring != nullptr: the k | v columns also go to slot tok_pos % W of tok_seq's ring.
+// Without a ring the four ring fields stay 0: the kernel reads them only under write_kv (gemv_core.cuh), so there is no pos % 0.
+GemvArgs gemv_qkv_rope(const void* x, int ldx, int D, const void* norm_w, float eps, const void* wq, const void* wk, const void* wv,
+                       int nq, int nkv, void* qkv, int ldo, const float* rope_cs, const int32_t* tok_pos, const int32_t* tok_seq,
+                       int head_dim, const RingWrite* ring) {
+  GemvArgs a = gemv_common(x, ldx, D, nq + 2 * nkv, norm_w, eps, qkv, ldo);
+  a.mode = GEMV_QKV_ROPE;
+  a.w0 = (const bf16_t*)wq; a.w1 = (const bf16_t*)wk; a.w2 = (const bf16_t*)wv; a.n0 = nq; a.n1 = nq + nkv;
+  a.rope_cs = rope_cs; a.tok_pos = tok_pos; a.tok_seq = tok_seq; a.head_dim = head_dim;
+  if (ring) { a.write_kv = 1; a.cache_k = ring->k; a.cache_v = ring->v; a.W = ring->W; a.kv_layout = ring->layout; }
+  return a;
+}
+// h[T, D] += x[T, K] @ w^T   (Wo, W2)
+GemvArgs gemv_residual(const void* x, int K, const void* w, void* h, int D) {
+  GemvArgs a = gemv_common(x, K, K, D, nullptr, 0.f, h, D);
+  a.mode = GEMV_RESIDUAL;
+  a.w0 = (const bf16_t*)w; a.n0 = a.n1 = D; a.residual = (const bf16_t*)h;
+  return a;
+}
+// hid[T, F] = silu(xn @ w1^T) * (xn @ w3^T), xn = rmsnorm(h[T, D])
+GemvArgs gemv_swiglu(const void* h, int D, const void* norm_w, float eps, const void* w1, const void* w3, void* hid, int F) {
+  GemvArgs a = gemv_common(h, D, D, F, norm_w, eps, hid, F);
+  a.mode = GEMV_SWIGLU;
+  a.w0 = (const bf16_t*)w1; a.w1 = (const bf16_t*)w3; a.n0 = a.n1 = F;
+  return a;
+}
+// logits[T, V] (fp32) = rmsnorm(h[T, D]) @ w^T
+GemvArgs gemv_logits(const void* h, int D, const void* norm_w, float eps, const void* w, float* logits, int V) {
+  GemvArgs a = gemv_common(h, D, D, V, norm_w, eps, logits, V);
+  a.mode = GEMV_LOGITS;
+  a.w0 = (const bf16_t*)w; a.n0 = a.n1 = V;
+  return a;
+}
+
+// The two compiles of gemv.hip: bf16 payloads (mi_forward, the bf16 leaves) and fp16 payloads (mi_forward_generic).
+struct GemvKernels {
+  int (*max_tokens)(int K);
+  hipError_t (*launch)(const GemvArgs&, hipStream_t);
+};
+constexpr GemvKernels kGemvBf16 = {gemv_max_tokens, launch_gemv}, kGemvF16 = {gemv_max_tokens_f16, launch_gemv_f16};
+
 // GEMV over T <= 8 tokens, in passes when T * K does not fit the LDS budget.
-int gemv_passes(GemvArgs a, int T, hipStream_t s, const char* what) {
-  const int cap = gemv_max_tokens(a.K);
+int gemv_passes(const GemvKernels& k, GemvArgs a, int T, hipStream_t s, const char* what) {
+  const int cap = k.max_tokens(a.K);
   const size_t out_elt = (a.mode == GEMV_LOGITS) ? 4 : 2;
   for (int t0 = 0; t0 < T; t0 += cap) {
     GemvArgs p = a;
@@ -198,10 +251,140 @@ int gemv_passes(GemvArgs a, int T, hipStream_t s, const char* what) {
     if (a.residual) p.residual = a.residual + (size_t)t0 * a.ldo;
     if (a.tok_pos) p.tok_pos = a.tok_pos + t0;
     if (a.tok_seq) p.tok_seq = a.tok_seq + t0;
-    MI_TRY(hip_rc(launch_gemv(p, s), what));
+    MI_TRY(hip_rc(k.launch(p, s), what));
   }
   return MI_OK;
 }
+
+// out[M, N] = epi(a[M, K] @ w0^T (, a @ w1^T)): the plain GEMM of one weight matrix, or of W1 and W3 for GEMM_SWIGLU
+GemmArgs gemm_args(int epi, const bf16_t* a, int M, int K, const void* w0, const void* w1, int N, void* out, const bf16_t* residual) {
+  GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.epi = epi; g.M = M; g.N = N; g.K = K; g.a = a; g.lda = K;
+  g.w0 = (const bf16_t*)w0; g.w1 = (const bf16_t*)w1; g.n0 = g.n1 = N; g.out = out; g.ldo = N; g.residual = residual;
+  return g;
+}
+
+// ---- MoE FFN of T <= 8 tokens: per (token, slot) gate | up + SwiGLU into hid [T * top_k, F], then per token the down
+// projections, the weighted combine and the residual
+int moe_decode(void* out, const void* residual, const void* x, int ldx, int T, int D, int F, const void* const* expert_tab,
+               const int32_t* sel_idx, const float* sel_w, int top_k, const void* norm_w, float eps, void* hid, hipStream_t s) {
+  GemvArgs a = gemv_common(x, ldx, D, F, norm_w, eps, hid, F);
+  a.mode = GEMV_MOE_W13; a.T = T;
+  a.expert_tab = expert_tab; a.sel_idx = sel_idx; a.sel_w = sel_w; a.top_k = top_k;
+  MI_TRY(hip_rc(launch_gemv(a, s), "moe w13 gemv"));
+  a = gemv_common(hid, F, F, D, nullptr, 0.f, out, D);
+  a.mode = GEMV_MOE_W2; a.T = T; a.residual = (const bf16_t*)residual;
+  a.expert_tab = expert_tab; a.sel_idx = sel_idx; a.sel_w = sel_w; a.top_k = top_k;
+  return hip_rc(launch_gemv(a, s), "moe w2 gemv");
+}
+
+struct MoeScratch {
+  bf16_t* hid;       // [T * top_k, F]
+  bf16_t* y;         // expert outputs, compact rows      [T * top_k, D]
+  int32_t* tok_of;   // token of compact row r            [T * top_k]
+  int32_t* row_of;   // compact row of (token, slot)      [T * top_k]
+  int32_t* tile_tab; // grouped-GEMM m-tile table         [max_tiles][4]
+  int32_t* n_tiles;
+  int max_tiles;
+  size_t total;
+};
+// ---- MoE FFN of a prefill: x [T, D] dense rows (already normed).  One token-grouped launch per projection covers all experts
+// (tile table built on the device: no host sync), then the weighted combine and the residual.
+int moe_grouped(void* out, const void* residual, const void* x, int T, int D, int F, int E, int k, const void* const* expert_tab,
+                const int32_t* sel_idx, const float* sel_w, const MoeScratch& w, hipStream_t s) {
+  // 256-row m-tiles (gemm256.hip) once an expert averages a few of them, else 128-row tiles (gemm.hip)
+  const int tile_rows = ((long)T * k >= 512L * E && D % 64 == 0 && F % 64 == 0) ? 256 : 128;
+  const int max_m_tiles = (T * k + tile_rows - 1) / tile_rows + E;  // <= the scratch's max_tiles (sized for 128-row tiles)
+  MI_TRY(hip_rc(launch_moe_lists(sel_idx, T, E, k, w.tok_of, w.row_of, w.tile_tab, w.n_tiles, tile_rows, s), "moe_lists"));
+  GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.epi = GEMM_SWIGLU; g.M = T * k; g.N = F; g.K = D; g.a = (const bf16_t*)x; g.lda = D; g.n0 = g.n1 = F;
+  g.out = w.hid; g.ldo = F;
+  g.tile_tab = w.tile_tab; g.n_tiles_ptr = w.n_tiles; g.max_m_tiles = max_m_tiles; g.tile_rows = tile_rows;
+  g.expert_tab = expert_tab; g.w_sel0 = 0; g.w_sel1 = 2; g.a_gather = w.tok_of;
+  MI_TRY(hip_rc(launch_gemm(g, s), "moe w13 grouped gemm"));
+  memset(&g, 0, sizeof(g));
+  g.epi = GEMM_STORE; g.M = T * k; g.N = D; g.K = F; g.a = w.hid; g.lda = F; g.n0 = g.n1 = D;
+  g.out = w.y; g.ldo = D;
+  g.tile_tab = w.tile_tab; g.n_tiles_ptr = w.n_tiles; g.max_m_tiles = max_m_tiles; g.tile_rows = tile_rows;
+  g.expert_tab = expert_tab; g.w_sel0 = 1; g.w_sel1 = -1;
+  MI_TRY(hip_rc(launch_gemm(g, s), "moe w2 grouped gemm"));
+  return hip_rc(launch_moe_combine(out, residual, w.y, sel_idx, sel_w, w.row_of, T, D, k, s), "moe combine");
+}
+
+// ---- attention arguments (scratch = the tickets block and the split partials behind it)
+AttnDecodeArgs attn_decode_args(void* out, const void* q, int ldq, const void* cache_k, const void* cache_v, int kv_layout, int W,
+                                int B, int H, int Hkv, int Dh, const int32_t* tok_pos, int32_t* tickets, float* partial) {
+  AttnDecodeArgs a = {};  // (kv_groups: launch_attn_decode sets it)
+  a.out = out; a.q = (const bf16_t*)q; a.ldq = ldq; a.cache_k = (const bf16_t*)cache_k; a.cache_v = (const bf16_t*)cache_v;
+  a.kv_layout = kv_layout;
+  a.W = W; a.B = B; a.H = H; a.Hkv = Hkv; a.Dh = Dh; a.tok_pos = tok_pos;
+  a.tickets = tickets; a.partial = partial; a.n_splits = attn_decode_splits(W);
+  return a;
+}
+// softmax_scale <= 0: 1 / sqrt(head_dim)
+AttnPrefillArgs attn_prefill_args(void* out, const void* qkv, int ld, const void* cache_k, const void* cache_v, int kv_layout, int W,
+                                  int B, int max_q_len, int H, int Hkv, int Dh, const int32_t* q_start, const int32_t* kv_before,
+                                  int causal, float softmax_scale) {
+  AttnPrefillArgs a = {};
+  a.out = out; a.qkv = (const bf16_t*)qkv; a.ld = ld; a.cache_k = (const bf16_t*)cache_k; a.cache_v = (const bf16_t*)cache_v;
+  a.kv_layout = kv_layout;
+  a.W = W; a.B = B; a.max_q_len = max_q_len; a.H = H; a.Hkv = Hkv; a.Dh = Dh;
+  a.q_start = q_start; a.kv_before = kv_before; a.causal = causal;
+  a.scale = softmax_scale > 0.f ? softmax_scale : 1.0f / sqrtf((float)Dh);
+  return a;
+}
+
+// ---- what mi_forward and mi_forward_generic check of a batch, in the order the checks fire
+struct BatchInfo {
+  int T, B, branch, kv_layout;
+  bool has_cache;
+  bool want_sample;  // the step's token is picked on the device behind the LM head ...
+  bool want_topp;    // ... by a nucleus draw instead of the argmax (ABI v5; generate.py:126 at temperature > 0)
+};
+// The checks before the workspace is sized.  attn_rows: mi_forward's decode attention keeps one word per (sequence, kv head)
+// in the TICKET_BYTES block.
+int check_batch(const char* entry, const mi_model_t* m, const mi_batch_t* bt, bool attn_rows, BatchInfo* info) {
+  if (!bt || bt->T <= 0 || bt->B <= 0 || !bt->h || !bt->workspace) return fail(MI_ERR_ARG, "%s: batch", entry);
+  if (!bt->q_start || !bt->kv_before || !bt->tok_seq || !bt->tok_pos) return fail(MI_ERR_ARG, "%s: metadata", entry);
+  BatchInfo& b = *info;
+  b.T = bt->T; b.B = bt->B; b.branch = bt->branch; b.kv_layout = bt->kv_layout;
+  b.has_cache = b.branch != MI_BRANCH_NOCACHE;
+  if (b.has_cache && (!bt->cache_k || !bt->cache_v || !bt->cache_sizes)) return fail(MI_ERR_ARG, "%s: cache", entry);
+  if (!kv_layout_ok(bt->kv_layout)) return fail(MI_ERR_ARG, "%s: kv_layout", entry);
+  if (b.branch == MI_BRANCH_DECODE && (b.T != b.B || !bt->kv_seqlens)) return fail(MI_ERR_ARG, "%s: decode needs T == B", entry);
+  if (attn_rows && (size_t)b.B * m->n_kv_heads * 4 > TICKET_BYTES) return fail(MI_ERR_SHAPE, "B * n_kv_heads > 1024");
+  if (bt->logits && (!m->final_norm || !m->output)) return fail(MI_ERR_ARG, "%s: logits on a rank without LM head", entry);
+  return MI_OK;
+}
+// The checks behind it: the entry's carved size against the caller's, then the sample request.
+int check_workspace_and_sample(const char* entry, const mi_batch_t* bt, size_t required, BatchInfo* info) {
+  if (required > bt->workspace_bytes) return fail(MI_ERR_WORKSPACE, "workspace %zu < required %zu", bt->workspace_bytes, required);
+  BatchInfo& b = *info;
+  b.want_sample = b.branch == MI_BRANCH_DECODE && bt->logits && bt->greedy_token && bt->greedy_logprob;
+  if (bt->greedy_token && !b.want_sample)
+    return fail(MI_ERR_ARG, "%s: greedy_token needs the DECODE branch, logits and greedy_logprob", entry);
+  if (b.want_sample && bt->hist_len > 0 && (!bt->hist_token || !bt->hist_logprob))
+    return fail(MI_ERR_ARG, "%s: hist_len > 0 without history buffers", entry);
+  b.want_topp = b.want_sample && bt->sample_temperature > 0.f;
+  if (bt->sample_temperature < 0.f || (b.want_topp && !(bt->sample_top_p >= 0.f && bt->sample_top_p <= 1.f)))
+    return fail(MI_ERR_ARG, "%s: sample_temperature %g / sample_top_p %g", entry, (double)bt->sample_temperature, (double)bt->sample_top_p);
+  return MI_OK;
+}
+
+// The step's sample behind the LM head of either entry (generate.py:124-136; one block per sequence); ctrl: the control words
+// of the workspace - it reads the step counter the step advanced.
+int sample_step(const mi_batch_t* bt, const mi_model_t* m, bool topp, const uint32_t* ctrl, hipStream_t s) {
+  if (topp)
+    return hip_rc(launch_sample_top_p(bt->logits, m->vocab_size, bt->B, m->vocab_size, bt->sample_temperature, bt->sample_top_p,
+                                      bt->sample_seed, bt->sample_offset, nullptr, bt->greedy_token, bt->greedy_logprob, bt->hist_token,
+                                      bt->hist_logprob, bt->hist_len, ctrl, s), "top-p sample");
+  return hip_rc(launch_greedy_rows(bt->logits, m->vocab_size, bt->B, m->vocab_size, bt->greedy_token, bt->greedy_logprob,
+                                   bt->hist_token, bt->hist_logprob, bt->hist_len, ctrl, s), "greedy sample");
+}
+
+bool dtype_ok(int dtype) { return dtype == G_DT_BF16 || dtype == G_DT_FP16 || dtype == G_DT_FP32; }
 
 int check_model(const mi_model_t* m) {
   if (!m || !m->layers) return fail(MI_ERR_ARG, "null model");
@@ -269,18 +452,17 @@ int mi_linear(void* out, int ldo, const void* x, int ldx, int M, int K, const vo
   hipStream_t s = (hipStream_t)stream;
   const int n0 = n_rows[0], n1 = n0 + (w[1] ? n_rows[1] : 0), n2 = n1 + (w[2] ? n_rows[2] : 0);
   if (M <= GEMV_MAX_T) {
-    GemvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.K = K; a.x = (const bf16_t*)x; a.ldx = ldx; a.norm_w = (const bf16_t*)norm_w; a.eps = eps;
-    a.w0 = (const bf16_t*)w[0]; a.w1 = (const bf16_t*)w[1]; a.w2 = (const bf16_t*)w[2];
-    a.out = out; a.ldo = ldo; a.residual = (const bf16_t*)residual;
+    GemvArgs a = gemv_common(x, ldx, K, 0, norm_w, eps, out, ldo);
+    a.w0 = (const bf16_t*)w[0]; a.w1 = (const bf16_t*)w[1]; a.w2 = (const bf16_t*)w[2]; a.residual = (const bf16_t*)residual;
+    a.mode = epilogue == MI_EPI_SWIGLU   ? GEMV_SWIGLU  // (the one other place that names a mode: the public epilogue codes)
+             : epilogue == MI_EPI_STORE  ? GEMV_STORE
+             : epilogue == MI_EPI_RESIDUAL ? GEMV_RESIDUAL : GEMV_LOGITS;
     if (epilogue == MI_EPI_SWIGLU) {
-      a.mode = GEMV_SWIGLU; a.N = n0; a.n0 = a.n1 = n0;
+      a.N = n0; a.n0 = a.n1 = n0;
     } else {
-      a.mode = epilogue == MI_EPI_STORE ? GEMV_STORE : epilogue == MI_EPI_RESIDUAL ? GEMV_RESIDUAL : GEMV_LOGITS;
       a.N = n2; a.n0 = n0; a.n1 = n1;
     }
-    return gemv_passes(a, M, s, "gemv");
+    return gemv_passes(kGemvBf16, a, M, s, "gemv");
   }
   if (norm_w) return fail(MI_ERR_UNSUPPORTED, "mi_linear: fused RMSNorm only on the M <= 8 path");
   GemmArgs g;
@@ -299,6 +481,25 @@ int mi_linear(void* out, int ldo, const void* x, int ldx, int M, int K, const vo
 
 namespace {
 constexpr int LOGPROB_ROW_CHUNK = 128;  // rows per pass of the unfused route (bounds its scratch)
+MoeScratch moe_carve(int T, int D, int F, int E, int top_k, char* base) {
+  MoeScratch w;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* p = base ? base + off : nullptr;
+    off += align_up(bytes);
+    return p;
+  };
+  const size_t rows = (size_t)T * top_k;
+  w.hid = (bf16_t*)take(rows * F * 2);
+  w.y = (bf16_t*)take(rows * D * 2);
+  w.tok_of = (int32_t*)take(rows * 4);
+  w.row_of = (int32_t*)take(rows * 4);
+  w.max_tiles = (int)((rows + 127) / 128) + E;
+  w.tile_tab = (int32_t*)take((size_t)w.max_tiles * 16);
+  w.n_tiles = (int32_t*)take(256);
+  w.total = off;
+  return w;
+}
 }
 
 size_t mi_lm_head_logprobs_scratch_bytes(int M, int vocab) {
@@ -356,12 +557,8 @@ int mi_attn_decode(void* out, const void* q, int ldq, const void* cache_k, const
     return fail(MI_ERR_ARG, "mi_attn_decode");
   if (head_dim != 128) return fail(MI_ERR_SHAPE, "head_dim must be 128");
   if ((size_t)B * n_kv_heads * 4 > TICKET_BYTES) return fail(MI_ERR_SHAPE, "B * n_kv_heads > 1024");
-  AttnDecodeArgs a;
-  a.out = out; a.q = (const bf16_t*)q; a.ldq = ldq; a.cache_k = (const bf16_t*)cache_k; a.cache_v = (const bf16_t*)cache_v;
-  a.kv_layout = kv_layout;
-  a.W = W; a.B = B; a.H = n_heads; a.Hkv = n_kv_heads; a.Dh = head_dim; a.tok_pos = tok_pos;
-  a.tickets = (int32_t*)scratch; a.partial = (float*)((char*)scratch + TICKET_BYTES);
-  a.n_splits = attn_decode_splits(W);
+  const AttnDecodeArgs a = attn_decode_args(out, q, ldq, cache_k, cache_v, kv_layout, W, B, n_heads, n_kv_heads, head_dim, tok_pos,
+                                            (int32_t*)scratch, (float*)((char*)scratch + TICKET_BYTES));
   return hip_rc(launch_attn_decode(a, (hipStream_t)stream), "attn_decode");
 }
 
@@ -374,12 +571,8 @@ int mi_attn_prefill(void* out, const void* qkv, int ld, const void* cache_k, con
   // the kernel forms 32-bit element offsets inside one ring (W * kv_dim) and inside the activation matrix (rows * ld)
   if ((size_t)W * n_kv_heads * head_dim >= (1ull << 31) || (size_t)B * max_q_len * (size_t)ld >= (1ull << 31))
     return fail(MI_ERR_UNSUPPORTED, "mi_attn_prefill: ring or activation matrix larger than 2^31 elements");
-  AttnPrefillArgs a;
-  a.out = out; a.qkv = (const bf16_t*)qkv; a.ld = ld; a.cache_k = (const bf16_t*)cache_k; a.cache_v = (const bf16_t*)cache_v;
-  a.kv_layout = kv_layout;
-  a.W = W; a.B = B; a.max_q_len = max_q_len; a.H = n_heads; a.Hkv = n_kv_heads; a.Dh = head_dim;
-  a.q_start = q_start; a.kv_before = kv_before; a.causal = causal;
-  a.scale = softmax_scale > 0.f ? softmax_scale : 1.0f / sqrtf((float)head_dim);
+  const AttnPrefillArgs a = attn_prefill_args(out, qkv, ld, cache_k, cache_v, kv_layout, W, B, max_q_len, n_heads, n_kv_heads, head_dim,
+                                              q_start, kv_before, causal, softmax_scale);
   return hip_rc(launch_attn_prefill(a, (hipStream_t)stream), "attn_prefill");
 }
 
@@ -406,16 +599,10 @@ int mi_qkv_rope_kvwrite(void* qkv, int ldo, const void* x, int ldx, int T, int D
   if (T > GEMV_MAX_T)
     return fail(MI_ERR_UNSUPPORTED, "mi_qkv_rope_kvwrite: T = %d > %d (the prefill path is mi_rmsnorm + mi_linear + "
                 "mi_rope_inplace + mi_kv_write)", T, GEMV_MAX_T);
-  const int nq = n_heads * head_dim, nkv = n_kv_heads * head_dim;
-  GemvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.mode = GEMV_QKV_ROPE; a.K = D; a.N = nq + 2 * nkv; a.x = (const bf16_t*)x; a.ldx = ldx;
-  a.norm_w = (const bf16_t*)norm_w; a.eps = eps;
-  a.w0 = (const bf16_t*)wq; a.w1 = (const bf16_t*)wk; a.w2 = (const bf16_t*)wv; a.n0 = nq; a.n1 = nq + nkv;
-  a.out = qkv; a.ldo = ldo;
-  a.rope_cs = rope_cs; a.tok_pos = tok_pos; a.tok_seq = tok_seq; a.head_dim = head_dim;
-  a.write_kv = cache_k != nullptr; a.cache_k = cache_k; a.cache_v = cache_v; a.W = W; a.kv_layout = kv_layout;
-  return gemv_passes(a, T, (hipStream_t)stream, "qkv gemv");
+  const RingWrite ring = {cache_k, cache_v, W, kv_layout};
+  const GemvArgs a = gemv_qkv_rope(x, ldx, D, norm_w, eps, wq, wk, wv, n_heads * head_dim, n_kv_heads * head_dim, qkv, ldo, rope_cs,
+                                   tok_pos, tok_seq, head_dim, cache_k ? &ring : nullptr);
+  return gemv_passes(kGemvBf16, a, T, (hipStream_t)stream, "qkv gemv");
 }
 
 int mi_moe_experts_decode(void* out, const void* residual, const void* x, int ldx, int T, int D, int F,
@@ -426,48 +613,8 @@ int mi_moe_experts_decode(void* out, const void* residual, const void* x, int ld
   if (T > GEMV_MAX_T) return fail(MI_ERR_UNSUPPORTED, "mi_moe_experts_decode: T = %d > %d (use mi_moe_grouped_gemm)", T, GEMV_MAX_T);
   if (!(top_k == 1 || top_k == 2 || top_k == 4)) return fail(MI_ERR_SHAPE, "MoE: top_k in {1,2,4}");
   if ((size_t)top_k * F * 2 > 65536) return fail(MI_ERR_SHAPE, "MoE: top_k * hidden_dim too large for the decode combine kernel");
-  hipStream_t s = (hipStream_t)stream;
-  GemvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.mode = GEMV_MOE_W13; a.T = T; a.K = D; a.N = F; a.x = (const bf16_t*)x; a.ldx = ldx;
-  a.norm_w = (const bf16_t*)norm_w; a.eps = eps; a.out = hidden_scratch; a.ldo = F;
-  a.expert_tab = expert_w_dev; a.sel_idx = sel_idx; a.sel_w = sel_w; a.top_k = top_k;
-  MI_TRY(hip_rc(launch_gemv(a, s), "moe w13 gemv"));
-  memset(&a, 0, sizeof(a));
-  a.mode = GEMV_MOE_W2; a.T = T; a.K = F; a.N = D; a.x = (const bf16_t*)hidden_scratch; a.ldx = F; a.out = out; a.ldo = D;
-  a.residual = (const bf16_t*)residual;
-  a.expert_tab = expert_w_dev; a.sel_idx = sel_idx; a.sel_w = sel_w; a.top_k = top_k;
-  return hip_rc(launch_gemv(a, s), "moe w2 gemv");
+  return moe_decode(out, residual, x, ldx, T, D, F, expert_w_dev, sel_idx, sel_w, top_k, norm_w, eps, hidden_scratch, (hipStream_t)stream);
 }
-
-namespace {
-struct MoeScratch {
-  bf16_t* hid;
-  bf16_t* y;
-  int32_t *tok_of, *row_of, *tile_tab, *n_tiles;
-  int max_tiles;
-  size_t total;
-};
-MoeScratch moe_carve(int T, int D, int F, int E, int top_k, char* base) {
-  MoeScratch w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += align_up(bytes);
-    return p;
-  };
-  const size_t rows = (size_t)T * top_k;
-  w.hid = (bf16_t*)take(rows * F * 2);
-  w.y = (bf16_t*)take(rows * D * 2);
-  w.tok_of = (int32_t*)take(rows * 4);
-  w.row_of = (int32_t*)take(rows * 4);
-  w.max_tiles = (int)((rows + 127) / 128) + E;
-  w.tile_tab = (int32_t*)take((size_t)w.max_tiles * 16);
-  w.n_tiles = (int32_t*)take(256);
-  w.total = off;
-  return w;
-}
-}  // namespace
 
 size_t mi_moe_grouped_gemm_scratch_bytes(int T, int D, int F, int E, int top_k) {
   if (T <= 0 || D <= 0 || F <= 0 || E <= 0 || top_k <= 0) return 0;
@@ -482,26 +629,7 @@ int mi_moe_grouped_gemm(void* out, const void* residual, const void* x, int ldx,
   if (E > 16 || top_k > 4 || top_k > E || top_k < 1) return fail(MI_ERR_SHAPE, "MoE: E <= 16, top_k <= 4");
   MoeScratch w = moe_carve(T, D, F, E, top_k, (char*)scratch);
   if (w.total > scratch_bytes) return fail(MI_ERR_WORKSPACE, "mi_moe_grouped_gemm: scratch %zu < required %zu", scratch_bytes, w.total);
-  hipStream_t s = (hipStream_t)stream;
-  const int k = top_k;
-  // 256-row m-tiles (gemm256.hip) once an expert averages a few of them, else 128-row tiles (gemm.hip)
-  const int tile_rows = ((long)T * k >= 512L * E && D % 64 == 0 && F % 64 == 0) ? 256 : 128;
-  const int max_m_tiles = (T * k + tile_rows - 1) / tile_rows + E;
-  MI_TRY(hip_rc(launch_moe_lists(sel_idx, T, E, k, w.tok_of, w.row_of, w.tile_tab, w.n_tiles, tile_rows, s), "moe_lists"));
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.epi = GEMM_SWIGLU; g.M = T * k; g.N = F; g.K = D; g.a = (const bf16_t*)x; g.lda = D; g.n0 = g.n1 = F;
-  g.out = w.hid; g.ldo = F;
-  g.tile_tab = w.tile_tab; g.n_tiles_ptr = w.n_tiles; g.max_m_tiles = max_m_tiles; g.tile_rows = tile_rows;
-  g.expert_tab = expert_w_dev; g.w_sel0 = 0; g.w_sel1 = 2; g.a_gather = w.tok_of;
-  MI_TRY(hip_rc(launch_gemm(g, s), "moe w13 grouped gemm"));
-  memset(&g, 0, sizeof(g));
-  g.epi = GEMM_STORE; g.M = T * k; g.N = D; g.K = F; g.a = w.hid; g.lda = F; g.n0 = g.n1 = D;
-  g.out = w.y; g.ldo = D;
-  g.tile_tab = w.tile_tab; g.n_tiles_ptr = w.n_tiles; g.max_m_tiles = max_m_tiles; g.tile_rows = tile_rows;
-  g.expert_tab = expert_w_dev; g.w_sel0 = 1; g.w_sel1 = -1;
-  MI_TRY(hip_rc(launch_gemm(g, s), "moe w2 grouped gemm"));
-  return hip_rc(launch_moe_combine(out, residual, w.y, sel_idx, sel_w, w.row_of, T, D, k, s), "moe combine");
+  return moe_grouped(out, residual, x, T, D, F, E, top_k, expert_w_dev, sel_idx, sel_w, w, (hipStream_t)stream);
 }
 
 int mi_set_decode_engine(int enabled) {
@@ -611,24 +739,16 @@ size_t mi_workspace_bytes(const mi_model_t* model, int T, int B, int max_cache_s
 
 int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
   MI_TRY(check_model(m));
-  if (!bt || bt->T <= 0 || bt->B <= 0 || !bt->h || !bt->workspace) return fail(MI_ERR_ARG, "mi_forward: batch");
-  if (!bt->q_start || !bt->kv_before || !bt->tok_seq || !bt->tok_pos) return fail(MI_ERR_ARG, "mi_forward: metadata");
-  const int T = bt->T, B = bt->B, branch = bt->branch;
-  const bool has_cache = branch != MI_BRANCH_NOCACHE;
-  if (has_cache && (!bt->cache_k || !bt->cache_v || !bt->cache_sizes)) return fail(MI_ERR_ARG, "mi_forward: cache");
-  if (!kv_layout_ok(bt->kv_layout)) return fail(MI_ERR_ARG, "mi_forward: kv_layout");
-  const int kvl = bt->kv_layout;
-  if (branch == MI_BRANCH_DECODE && (T != B || !bt->kv_seqlens)) return fail(MI_ERR_ARG, "mi_forward: decode needs T == B");
-  if ((size_t)B * m->n_kv_heads * 4 > TICKET_BYTES) return fail(MI_ERR_SHAPE, "B * n_kv_heads > 1024");
-  if (bt->logits && (!m->final_norm || !m->output)) return fail(MI_ERR_ARG, "mi_forward: logits on a rank without LM head");
-  hipStream_t s = (hipStream_t)stream;
-
+  BatchInfo bi;
+  MI_TRY(check_batch("mi_forward", m, bt, true, &bi));
   int maxW = 1;
-  if (has_cache)
+  if (bi.has_cache)
     for (int l = 0; l < m->n_layers; ++l) maxW = bt->cache_sizes[l] > maxW ? bt->cache_sizes[l] : maxW;
-  Workspace ws = carve(m, T, B, maxW, (char*)bt->workspace);
-  if (ws.total > bt->workspace_bytes)
-    return fail(MI_ERR_WORKSPACE, "workspace %zu < required %zu", bt->workspace_bytes, ws.total);
+  const Workspace ws = carve(m, bi.T, bi.B, maxW, (char*)bt->workspace);
+  MI_TRY(check_workspace_and_sample("mi_forward", bt, ws.total, &bi));
+  const int T = bi.T, B = bi.B, branch = bi.branch, kvl = bi.kv_layout;
+  const bool has_cache = bi.has_cache, want_greedy = bi.want_sample, want_topp = bi.want_topp;
+  hipStream_t s = (hipStream_t)stream;
 
   const int D = m->dim, H = m->n_heads, Hkv = m->n_kv_heads, Dh = m->head_dim, F = m->hidden_dim;
   const int nq = H * Dh, nkv = Hkv * Dh, qkv_cols = nq + 2 * nkv;
@@ -639,23 +759,6 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
   // embeddings of transformer.py:190-191 (text rows from mi_embedding, image rows from the vision tower)
   const bool embed = m->tok_embeddings && bt->input_ids;
   uint32_t* engine_ctrl = reinterpret_cast<uint32_t*>(ws.tickets);
-  const bool want_greedy = branch == MI_BRANCH_DECODE && bt->logits && bt->greedy_token && bt->greedy_logprob;
-  if (bt->greedy_token && !want_greedy)
-    return fail(MI_ERR_ARG, "mi_forward: greedy_token needs the DECODE branch, logits and greedy_logprob");
-  if (want_greedy && bt->hist_len > 0 && (!bt->hist_token || !bt->hist_logprob))
-    return fail(MI_ERR_ARG, "mi_forward: hist_len > 0 without history buffers");
-  // ABI v5: the step's sample is a nucleus draw instead of the argmax (generate.py:126 at temperature > 0)
-  const bool want_topp = want_greedy && bt->sample_temperature > 0.f;
-  if (bt->sample_temperature < 0.f || (want_topp && !(bt->sample_top_p >= 0.f && bt->sample_top_p <= 1.f)))
-    return fail(MI_ERR_ARG, "mi_forward: sample_temperature %g / sample_top_p %g", (double)bt->sample_temperature, (double)bt->sample_top_p);
-  auto sample_step = [&]() -> int {  // behind the LM head of either decode path; reads the step counter the step advanced
-    if (want_topp)
-      return hip_rc(launch_sample_top_p(bt->logits, m->vocab_size, B, m->vocab_size, bt->sample_temperature, bt->sample_top_p,
-                                        bt->sample_seed, bt->sample_offset, nullptr, bt->greedy_token, bt->greedy_logprob, bt->hist_token,
-                                        bt->hist_logprob, bt->hist_len, engine_ctrl, s), "top-p sample");
-    return hip_rc(launch_greedy_rows(bt->logits, m->vocab_size, B, m->vocab_size, bt->greedy_token, bt->greedy_logprob,
-                                     bt->hist_token, bt->hist_logprob, bt->hist_len, engine_ctrl, s), "greedy sample");
-  };
 
   // ---- batch-1 decode step of a dense model: every layer (and the LM head) in ONE persistent launch, which also does
   // the step's bookkeeping (position, embedding row, greedy sample): nothing else is enqueued for the token
@@ -689,7 +792,7 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
         return false;
       }
       if (rc == MI_OK && m->final_norm && !bt->logits) rc = hip_rc(launch_rmsnorm(h, h, m->final_norm, T, D, m->norm_eps, s), "final norm");
-      if (rc == MI_OK && want_topp) rc = sample_step();
+      if (rc == MI_OK && want_topp) rc = sample_step(bt, m, true, engine_ctrl, s);
       return true;
     };
     if (dense_ok && engine_route(engine_variant(), nemo_engine_enabled(), slot, pr, try_build)) return rc;
@@ -712,18 +815,17 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
     const int W = has_cache ? bt->cache_sizes[l] : 1;
     void* ck = has_cache ? bt->cache_k[l] : nullptr;
     void* cv = has_cache ? bt->cache_v[l] : nullptr;
+    auto kv_write = [&](const char* what) {
+      return hip_rc(launch_kv_write(ck, cv, W, ws.qkv + nq, ws.qkv + nq + nkv, qkv_cols, T, nkv, bt->tok_seq, bt->tok_pos, bt->q_start,
+                                    kvl, Dh, s), what);
+    };
 
     // ---- attention_norm + q|k|v + RoPE (+ ring write at decode)
     if (gemv) {
-      GemvArgs a;
-      memset(&a, 0, sizeof(a));
-      a.mode = GEMV_QKV_ROPE; a.K = D; a.N = qkv_cols; a.x = h; a.ldx = D;
-      a.norm_w = (const bf16_t*)L.attention_norm; a.eps = m->norm_eps;
-      a.w0 = (const bf16_t*)L.wq; a.w1 = (const bf16_t*)L.wk; a.w2 = (const bf16_t*)L.wv; a.n0 = nq; a.n1 = nq + nkv;
-      a.out = ws.qkv; a.ldo = qkv_cols;
-      a.rope_cs = m->rope_cs; a.tok_pos = bt->tok_pos; a.tok_seq = bt->tok_seq; a.head_dim = Dh;
-      a.write_kv = branch == MI_BRANCH_DECODE; a.cache_k = ck; a.cache_v = cv; a.W = W; a.kv_layout = kvl;
-      MI_TRY(gemv_passes(a, T, s, "qkv gemv"));
+      const RingWrite ring = {ck, cv, W, kvl};
+      MI_TRY(gemv_passes(kGemvBf16, gemv_qkv_rope(h, D, D, L.attention_norm, m->norm_eps, L.wq, L.wk, L.wv, nq, nkv, ws.qkv, qkv_cols,
+                                                  m->rope_cs, bt->tok_pos, bt->tok_seq, Dh, branch == MI_BRANCH_DECODE ? &ring : nullptr),
+                         T, s, "qkv gemv"));
     } else {
       MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, L.attention_norm, T, D, m->norm_eps, s), "attention_norm"));
       GemmArgs g;
@@ -739,139 +841,63 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
       if (!fused_rope) MI_TRY(hip_rc(launch_rope(ws.qkv, qkv_cols, T, H, Hkv, Dh, m->rope_cs, bt->tok_pos, s), "rope"));
       // decode branch with more than 8 sequences: the ring write that the GEMV epilogue does otherwise; it must
       // precede the attention (cache.py:83-92 `update` then read, transformer_layers.py:77-81)
-      if (branch == MI_BRANCH_DECODE)
-        MI_TRY(hip_rc(launch_kv_write(ck, cv, W, ws.qkv + nq, ws.qkv + nq + nkv, qkv_cols, T, nkv, bt->tok_seq, bt->tok_pos,
-                                      bt->q_start, kvl, Dh, s), "kv_write (decode)"));
+      if (branch == MI_BRANCH_DECODE) MI_TRY(kv_write("kv_write (decode)"));
     }
 
     // ---- attention
     if (branch == MI_BRANCH_DECODE) {
-      AttnDecodeArgs a;
-      a.out = ws.attn; a.q = ws.qkv; a.ldq = qkv_cols; a.cache_k = (const bf16_t*)ck; a.cache_v = (const bf16_t*)cv;
-      a.kv_layout = kvl;
-      a.W = W; a.B = B; a.H = H; a.Hkv = Hkv; a.Dh = Dh; a.tok_pos = bt->tok_pos;
-      a.partial = ws.partial; a.tickets = ws.tickets; a.n_splits = attn_decode_splits(W);
+      const AttnDecodeArgs a = attn_decode_args(ws.attn, ws.qkv, qkv_cols, ck, cv, kvl, W, B, H, Hkv, Dh, bt->tok_pos, ws.tickets, ws.partial);
       MI_TRY(hip_rc(launch_attn_decode(a, s), "attn_decode"));
     } else {
-      AttnPrefillArgs a;
-      a.out = ws.attn; a.qkv = ws.qkv; a.ld = qkv_cols; a.cache_k = (const bf16_t*)ck; a.cache_v = (const bf16_t*)cv;
-      a.kv_layout = kvl;
-      a.W = has_cache ? W : T; a.B = B; a.max_q_len = has_cache ? bt->max_q_len : T; a.H = H; a.Hkv = Hkv; a.Dh = Dh;
-      a.q_start = bt->q_start; a.kv_before = bt->kv_before; a.causal = has_cache ? 1 : 0;
-      a.scale = 1.0f / sqrtf((float)m->head_dim);
+      const AttnPrefillArgs a = attn_prefill_args(ws.attn, ws.qkv, qkv_cols, ck, cv, kvl, has_cache ? W : T, B, has_cache ? bt->max_q_len : T,
+                                                  H, Hkv, Dh, bt->q_start, bt->kv_before, has_cache ? 1 : 0, 0.f);
       MI_TRY(hip_rc(launch_attn_prefill(a, s), "attn_prefill"));
-      if (has_cache)
-        MI_TRY(hip_rc(launch_kv_write(ck, cv, W, ws.qkv + nq, ws.qkv + nq + nkv, qkv_cols, T, nkv, bt->tok_seq, bt->tok_pos,
-                                      bt->q_start, kvl, Dh, s), "kv_write"));
+      if (has_cache) MI_TRY(kv_write("kv_write"));
     }
 
     // ---- h = h + attn @ Wo^T
-    if (gemv) {
-      GemvArgs a;
-      memset(&a, 0, sizeof(a));
-      a.mode = GEMV_RESIDUAL; a.K = nq; a.N = D; a.x = ws.attn; a.ldx = nq;
-      a.w0 = (const bf16_t*)L.wo; a.n0 = a.n1 = D; a.out = h; a.ldo = D; a.residual = h;
-      MI_TRY(gemv_passes(a, T, s, "wo gemv"));
-    } else {
-      GemmArgs g;
-      memset(&g, 0, sizeof(g));
-      g.epi = GEMM_RESIDUAL; g.M = T; g.N = D; g.K = nq; g.a = ws.attn; g.lda = nq;
-      g.w0 = (const bf16_t*)L.wo; g.n0 = g.n1 = D; g.out = h; g.ldo = D; g.residual = h;
-      MI_TRY(hip_rc(launch_gemm(g, s), "wo gemm"));
-    }
+    if (gemv)
+      MI_TRY(gemv_passes(kGemvBf16, gemv_residual(ws.attn, nq, L.wo, h, D), T, s, "wo gemv"));
+    else
+      MI_TRY(hip_rc(launch_gemm(gemm_args(GEMM_RESIDUAL, ws.attn, T, nq, L.wo, nullptr, D, h, h), s), "wo gemm"));
 
     // ---- h = h + FFN(ffn_norm(h))
-    const bool moe = m->num_experts > 0;
-    if (!moe) {
+    if (m->num_experts == 0) {
       if (gemv) {
-        GemvArgs a;
-        memset(&a, 0, sizeof(a));
-        a.mode = GEMV_SWIGLU; a.K = D; a.N = F; a.x = h; a.ldx = D;
-        a.norm_w = (const bf16_t*)L.ffn_norm; a.eps = m->norm_eps;
-        a.w0 = (const bf16_t*)L.w1; a.w1 = (const bf16_t*)L.w3; a.n0 = a.n1 = F; a.out = ws.hid; a.ldo = F;
-        MI_TRY(gemv_passes(a, T, s, "w13 gemv"));
-        memset(&a, 0, sizeof(a));
-        a.mode = GEMV_RESIDUAL; a.K = F; a.N = D; a.x = ws.hid; a.ldx = F;
-        a.w0 = (const bf16_t*)L.w2; a.n0 = a.n1 = D; a.out = h; a.ldo = D; a.residual = h;
-        MI_TRY(gemv_passes(a, T, s, "w2 gemv"));
+        MI_TRY(gemv_passes(kGemvBf16, gemv_swiglu(h, D, L.ffn_norm, m->norm_eps, L.w1, L.w3, ws.hid, F), T, s, "w13 gemv"));
+        MI_TRY(gemv_passes(kGemvBf16, gemv_residual(ws.hid, F, L.w2, h, D), T, s, "w2 gemv"));
       } else {
         MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, L.ffn_norm, T, D, m->norm_eps, s), "ffn_norm"));
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.epi = GEMM_SWIGLU; g.M = T; g.N = F; g.K = D; g.a = ws.xn; g.lda = D;
-        g.w0 = (const bf16_t*)L.w1; g.w1 = (const bf16_t*)L.w3; g.n0 = g.n1 = F; g.out = ws.hid; g.ldo = F;
-        MI_TRY(hip_rc(launch_gemm(g, s), "w13 gemm"));
-        memset(&g, 0, sizeof(g));
-        g.epi = GEMM_RESIDUAL; g.M = T; g.N = D; g.K = F; g.a = ws.hid; g.lda = F;
-        g.w0 = (const bf16_t*)L.w2; g.n0 = g.n1 = D; g.out = h; g.ldo = D; g.residual = h;
-        MI_TRY(hip_rc(launch_gemm(g, s), "w2 gemm"));
+        MI_TRY(hip_rc(launch_gemm(gemm_args(GEMM_SWIGLU, ws.xn, T, D, L.w1, L.w3, F, ws.hid, nullptr), s), "w13 gemm"));
+        MI_TRY(hip_rc(launch_gemm(gemm_args(GEMM_RESIDUAL, ws.hid, T, F, L.w2, nullptr, D, h, h), s), "w2 gemm"));
       }
     } else {
       const int E = m->num_experts, k = m->top_k;
       if (!L.gate || !L.expert_w_dev || !L.expert_w_host) return fail(MI_ERR_ARG, "mi_forward: MoE layer tables");
       if (gemv) {
         MI_TRY(hip_rc(launch_moe_router(ws.sel_idx, ws.sel_w, h, D, T, D, L.gate, E, k, L.ffn_norm, m->norm_eps, s), "moe_router"));
-        GemvArgs a;
-        memset(&a, 0, sizeof(a));
-        a.mode = GEMV_MOE_W13; a.T = T; a.K = D; a.N = F; a.x = h; a.ldx = D;
-        a.norm_w = (const bf16_t*)L.ffn_norm; a.eps = m->norm_eps; a.out = ws.hid; a.ldo = F;
-        a.expert_tab = L.expert_w_dev; a.sel_idx = ws.sel_idx; a.sel_w = ws.sel_w; a.top_k = k;
-        MI_TRY(hip_rc(launch_gemv(a, s), "moe w13 gemv"));
-        memset(&a, 0, sizeof(a));
-        a.mode = GEMV_MOE_W2; a.T = T; a.K = F; a.N = D; a.x = ws.hid; a.ldx = F; a.out = h; a.ldo = D; a.residual = h;
-        a.expert_tab = L.expert_w_dev; a.sel_idx = ws.sel_idx; a.sel_w = ws.sel_w; a.top_k = k;
-        MI_TRY(hip_rc(launch_gemv(a, s), "moe w2 gemv"));
+        MI_TRY(moe_decode(h, h, h, D, T, D, F, L.expert_w_dev, ws.sel_idx, ws.sel_w, k, L.ffn_norm, m->norm_eps, ws.hid, s));
       } else {
         MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, L.ffn_norm, T, D, m->norm_eps, s), "ffn_norm"));
         MI_TRY(hip_rc(launch_moe_router(ws.sel_idx, ws.sel_w, ws.xn, D, T, D, L.gate, E, k, nullptr, 0.f, s), "moe_router"));
-        // 256-row m-tiles (gemm256.hip) once an expert averages a few of them, else 128-row tiles (gemm.hip)
-        const int tile_rows = ((long)T * k >= 512L * E && D % 64 == 0 && F % 64 == 0) ? 256 : 128;
-        const int max_m_tiles = (T * k + tile_rows - 1) / tile_rows + E;  // <= ws.max_tiles (sized for 128-row tiles)
-        MI_TRY(hip_rc(launch_moe_lists(ws.sel_idx, T, E, k, ws.tok_of, ws.row_of, ws.tile_tab, ws.n_tiles, tile_rows, s), "moe_lists"));
-        // one token-grouped launch per projection covers all experts (tile table built on the device: no host sync)
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.epi = GEMM_SWIGLU; g.M = T * k; g.N = F; g.K = D; g.a = ws.xn; g.lda = D; g.n0 = g.n1 = F;
-        g.out = ws.hid; g.ldo = F;
-        g.tile_tab = ws.tile_tab; g.n_tiles_ptr = ws.n_tiles; g.max_m_tiles = max_m_tiles; g.tile_rows = tile_rows;
-        g.expert_tab = L.expert_w_dev; g.w_sel0 = 0; g.w_sel1 = 2; g.a_gather = ws.tok_of;
-        MI_TRY(hip_rc(launch_gemm(g, s), "moe w13 grouped gemm"));
-        memset(&g, 0, sizeof(g));
-        g.epi = GEMM_STORE; g.M = T * k; g.N = D; g.K = F; g.a = ws.hid; g.lda = F; g.n0 = g.n1 = D;
-        g.out = ws.moe_y; g.ldo = D;
-        g.tile_tab = ws.tile_tab; g.n_tiles_ptr = ws.n_tiles; g.max_m_tiles = max_m_tiles; g.tile_rows = tile_rows;
-        g.expert_tab = L.expert_w_dev; g.w_sel0 = 1; g.w_sel1 = -1;
-        MI_TRY(hip_rc(launch_gemm(g, s), "moe w2 grouped gemm"));
-        MI_TRY(hip_rc(launch_moe_combine(h, h, ws.moe_y, ws.sel_idx, ws.sel_w, ws.row_of, T, D, k, s), "moe combine"));
+        const MoeScratch sc = {ws.hid, ws.moe_y, ws.tok_of, ws.row_of, ws.tile_tab, ws.n_tiles, ws.max_tiles, 0};
+        MI_TRY(moe_grouped(h, h, ws.xn, T, D, F, E, k, L.expert_w_dev, ws.sel_idx, ws.sel_w, sc, s));
       }
     }
   }
 
-  // ---- final norm (+ LM head)
-  if (m->final_norm) {
-    if (bt->logits) {
-      if (gemv) {
-        GemvArgs a;
-        memset(&a, 0, sizeof(a));
-        a.mode = GEMV_LOGITS; a.K = D; a.N = m->vocab_size; a.x = h; a.ldx = D;
-        a.norm_w = (const bf16_t*)m->final_norm; a.eps = m->norm_eps;
-        a.w0 = (const bf16_t*)m->output; a.n0 = a.n1 = m->vocab_size; a.out = bt->logits; a.ldo = m->vocab_size;
-        MI_TRY(gemv_passes(a, T, s, "lm head gemv"));
-        if (want_greedy)  // generate.py:124-136 at temperature 0, fused behind the LM head (one block per sequence)
-          MI_TRY(sample_step());
-      } else {
-        MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, m->final_norm, T, D, m->norm_eps, s), "final norm"));
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.epi = GEMM_LOGITS; g.M = T; g.N = m->vocab_size; g.K = D; g.a = ws.xn; g.lda = D;
-        g.w0 = (const bf16_t*)m->output; g.n0 = g.n1 = m->vocab_size; g.out = bt->logits; g.ldo = m->vocab_size;
-        MI_TRY(hip_rc(launch_gemm(g, s), "lm head gemm"));
-        if (want_greedy)
-          MI_TRY(sample_step());
-      }
+  // ---- final norm (+ LM head; + the step's sample: generate.py:124-136 fused behind the LM head)
+  if (m->final_norm && !bt->logits) {
+    MI_TRY(hip_rc(launch_rmsnorm(h, h, m->final_norm, T, D, m->norm_eps, s), "final norm"));
+  } else if (m->final_norm) {
+    const int V = m->vocab_size;
+    if (gemv) {
+      MI_TRY(gemv_passes(kGemvBf16, gemv_logits(h, D, m->final_norm, m->norm_eps, m->output, bt->logits, V), T, s, "lm head gemv"));
     } else {
-      MI_TRY(hip_rc(launch_rmsnorm(h, h, m->final_norm, T, D, m->norm_eps, s), "final norm"));
+      MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, m->final_norm, T, D, m->norm_eps, s), "final norm"));
+      MI_TRY(hip_rc(launch_gemm(gemm_args(GEMM_LOGITS, ws.xn, T, D, m->output, nullptr, V, bt->logits, nullptr), s), "lm head gemm"));
     }
+    if (want_greedy) MI_TRY(sample_step(bt, m, want_topp, engine_ctrl, s));
   }
   return MI_OK;
 }
@@ -922,12 +948,15 @@ GWorkspace carve_generic(const mi_model_t* m, int T, size_t es, char* base) {
 
 int check_model_generic(const mi_model_t* m, int dtype) {
   if (!m || !m->layers) return fail(MI_ERR_ARG, "null model");
-  if (dtype != G_DT_BF16 && dtype != G_DT_FP16 && dtype != G_DT_FP32) return fail(MI_ERR_ARG, "storage dtype %d", dtype);
+  if (!dtype_ok(dtype)) return fail(MI_ERR_ARG, "storage dtype %d", dtype);
   if (m->head_dim <= 0 || m->head_dim > 256 || m->head_dim % 8) return fail(MI_ERR_SHAPE, "head_dim %d: multiple of 8, <= 256", m->head_dim);
   if (m->n_kv_heads <= 0 || m->n_heads % m->n_kv_heads) return fail(MI_ERR_SHAPE, "n_heads %% n_kv_heads != 0");
   if (m->dim % 8 || m->hidden_dim % 8) return fail(MI_ERR_SHAPE, "dim/hidden_dim must be multiples of 8");
   if (m->num_experts > 0 && (m->top_k <= 0 || m->top_k > m->num_experts)) return fail(MI_ERR_SHAPE, "MoE: 0 < top_k <= num_experts");
   return MI_OK;
+}
+int check_dt(int dtype, const char* what) {
+  return dtype_ok(dtype) ? MI_OK : fail(MI_ERR_ARG, "%s: storage dtype %d", what, dtype);
 }
 
 }  // namespace
@@ -936,11 +965,6 @@ extern "C" {
 
 // ---- leaf operators in any storage dtype (ABI v6): what module-level callers of an fp16 / fp32 model bind - the Pixtral tower
 // (vision_encoder.py), RMSNorm / FeedForward modules used stand-alone.  Same kernels as mi_forward_generic.
-static int check_dt(int dtype, const char* what) {
-  if (dtype != G_DT_BF16 && dtype != G_DT_FP16 && dtype != G_DT_FP32) return fail(MI_ERR_ARG, "%s: storage dtype %d", what, dtype);
-  return MI_OK;
-}
-
 int mi_embedding_generic(void* out, const void* table, const int64_t* ids, int T, int D, int vocab, int dtype, mi_stream_t stream) {
   MI_TRY(check_dt(dtype, "mi_embedding_generic"));
   if (!out || !table || !ids || T <= 0 || D <= 0) return fail(MI_ERR_ARG, "mi_embedding_generic");
@@ -1025,33 +1049,19 @@ size_t mi_workspace_bytes_generic(const mi_model_t* model, int T, int dtype) {
 
 int mi_forward_generic(const mi_model_t* m, const mi_batch_t* bt, int dtype, mi_stream_t stream) {
   MI_TRY(check_model_generic(m, dtype));
-  if (!bt || bt->T <= 0 || bt->B <= 0 || !bt->h || !bt->workspace) return fail(MI_ERR_ARG, "mi_forward_generic: batch");
-  if (!bt->q_start || !bt->kv_before || !bt->tok_seq || !bt->tok_pos) return fail(MI_ERR_ARG, "mi_forward_generic: metadata");
-  const int T = bt->T, B = bt->B, branch = bt->branch;
-  const bool has_cache = branch != MI_BRANCH_NOCACHE;
-  if (has_cache && (!bt->cache_k || !bt->cache_v || !bt->cache_sizes)) return fail(MI_ERR_ARG, "mi_forward_generic: cache");
-  if (!kv_layout_ok(bt->kv_layout)) return fail(MI_ERR_ARG, "mi_forward_generic: kv_layout");
-  const int kvl = bt->kv_layout;
-  if (branch == MI_BRANCH_DECODE && (T != B || !bt->kv_seqlens)) return fail(MI_ERR_ARG, "mi_forward_generic: decode needs T == B");
-  if (bt->logits && (!m->final_norm || !m->output)) return fail(MI_ERR_ARG, "mi_forward_generic: logits on a rank without LM head");
-  hipStream_t s = (hipStream_t)stream;
   const int dt = dtype;
   const size_t es = g_elem_bytes(dt);
-  GWorkspace ws = carve_generic(m, T, es, (char*)bt->workspace);
-  if (ws.total > bt->workspace_bytes)
-    return fail(MI_ERR_WORKSPACE, "workspace %zu < required %zu", bt->workspace_bytes, ws.total);
+  BatchInfo bi;
+  MI_TRY(check_batch("mi_forward_generic", m, bt, false, &bi));
+  const GWorkspace ws = carve_generic(m, bi.T, es, (char*)bt->workspace);
+  MI_TRY(check_workspace_and_sample("mi_forward_generic", bt, ws.total, &bi));
+  const int T = bi.T, B = bi.B, branch = bi.branch, kvl = bi.kv_layout;
+  const bool has_cache = bi.has_cache;
+  hipStream_t s = (hipStream_t)stream;
 
   const int D = m->dim, H = m->n_heads, Hkv = m->n_kv_heads, Dh = m->head_dim, F = m->hidden_dim;
   const int nq = H * Dh, nkv = Hkv * Dh, qkv_cols = nq + 2 * nkv;
   char* h = (char*)bt->h;
-  const bool want_sample = branch == MI_BRANCH_DECODE && bt->logits && bt->greedy_token && bt->greedy_logprob;
-  if (bt->greedy_token && !want_sample)
-    return fail(MI_ERR_ARG, "mi_forward_generic: greedy_token needs the DECODE branch, logits and greedy_logprob");
-  if (want_sample && bt->hist_len > 0 && (!bt->hist_token || !bt->hist_logprob))
-    return fail(MI_ERR_ARG, "mi_forward_generic: hist_len > 0 without history buffers");
-  const bool want_topp = want_sample && bt->sample_temperature > 0.f;
-  if (bt->sample_temperature < 0.f || (want_topp && !(bt->sample_top_p >= 0.f && bt->sample_top_p <= 1.f)))
-    return fail(MI_ERR_ARG, "mi_forward_generic: sample_temperature / sample_top_p");
 
   auto linear = [&](const void* x, int ldx, const void* w, void* out, int ldo, int N, int K, int epi, const void* residual,
                     const int32_t* active, const char* what) -> int {
@@ -1060,6 +1070,16 @@ int mi_forward_generic(const mi_model_t* m, const mi_batch_t* bt, int dtype, mi_
     g.x = x; g.ldx = ldx; g.w = w; g.out = out; g.ldo = ldo; g.residual = residual; g.ldr = ldo;
     g.M = T; g.N = N; g.K = K; g.epi = epi; g.active = active;
     return hip_rc(launch_g_linear(dt, g, s), what);
+  };
+  // launch_g_linear's fused forms on x [T, D]: an RMSNorm prologue (norm_w), up to three matrices side by side (w1 / w2 from
+  // columns n0 / n1 on), or w and w1 through SiLU * mul (G_EPI_SWIGLU)
+  auto fused = [&](const void* x, const void* norm_w, const void* w, const void* w1, const void* w2, int n0, int n1, void* out, int N,
+                   int epi) {
+    GLinearArgs g;
+    memset(&g, 0, sizeof(g));
+    g.x = x; g.ldx = D; g.w = w; g.w1 = w1; g.w2 = w2; g.n0 = n0; g.n1 = n1; g.norm_w = norm_w; g.eps = norm_w ? m->norm_eps : 0.f;
+    g.out = out; g.ldo = N; g.M = T; g.N = N; g.K = D; g.epi = epi;
+    return g;
   };
   // T <= 8 (decode steps, tiny prompts): the row kernel's fused forms - RMSNorm in the prologue, q | k | v in one launch,
   // gate / up / SiLU / product in one launch: 8 launches per dense layer instead of 13
@@ -1073,21 +1093,6 @@ int mi_forward_generic(const mi_model_t* m, const mi_batch_t* bt, int dtype, mi_
     tuned_rows = e ? atoi(e) : 1;
   }
   const bool rows16 = rows && dt == G_DT_FP16 && tuned_rows != 0 && Dh % 2 == 0;
-  auto gemv16 = [&](GemvArgs a, const char* what) -> int {  // gemv_passes for the fp16 compile
-    const int cap = gemv_max_tokens_f16(a.K);
-    const size_t out_elt = (a.mode == GEMV_LOGITS) ? 4 : 2;
-    for (int t0 = 0; t0 < T; t0 += cap) {
-      GemvArgs p = a;
-      p.T = (T - t0 < cap) ? T - t0 : cap;
-      p.x = a.x + (size_t)t0 * a.ldx;
-      p.out = (char*)a.out + (size_t)t0 * a.ldo * out_elt;
-      if (a.residual) p.residual = a.residual + (size_t)t0 * a.ldo;
-      if (a.tok_pos) p.tok_pos = a.tok_pos + t0;
-      if (a.tok_seq) p.tok_seq = a.tok_seq + t0;
-      MI_TRY(hip_rc(launch_gemv_f16(p, s), what));
-    }
-    return MI_OK;
-  };
 
   if (branch == MI_BRANCH_DECODE)
     MI_TRY(hip_rc(launch_decode_prep(bt->kv_seqlens, bt->q_start, bt->kv_before, bt->tok_seq, bt->tok_pos, B, ws.ctrl, s), "decode_prep"));
@@ -1101,27 +1106,16 @@ int mi_forward_generic(const mi_model_t* m, const mi_batch_t* bt, int dtype, mi_
     void* cv = has_cache ? bt->cache_v[l] : nullptr;
     // ---- attention_norm, q | k | v, RoPE (transformer_layers.py:66-70)
     if (rows16) {
-      GemvArgs a;
-      memset(&a, 0, sizeof(a));
-      a.mode = GEMV_QKV_ROPE; a.K = D; a.N = qkv_cols; a.x = (const bf16_t*)h; a.ldx = D;
-      a.norm_w = (const bf16_t*)L.attention_norm; a.eps = m->norm_eps;
-      a.w0 = (const bf16_t*)L.wq; a.w1 = (const bf16_t*)L.wk; a.w2 = (const bf16_t*)L.wv; a.n0 = nq; a.n1 = nq + nkv;
-      a.out = ws.qkv; a.ldo = qkv_cols;
-      a.rope_cs = m->rope_cs; a.tok_pos = bt->tok_pos; a.tok_seq = bt->tok_seq; a.head_dim = Dh;
-      a.write_kv = 0;  // (the ring write follows the attention here: g_kv_write below)
-      MI_TRY(gemv16(a, "norm + q|k|v + rope (fp16 gemv)"));
+      // (no ring write in the epilogue: it follows the attention here, g_kv_write below)
+      MI_TRY(gemv_passes(kGemvF16, gemv_qkv_rope(h, D, D, L.attention_norm, m->norm_eps, L.wq, L.wk, L.wv, nq, nkv, ws.qkv, qkv_cols,
+                                                 m->rope_cs, bt->tok_pos, bt->tok_seq, Dh, nullptr),
+                         T, s, "norm + q|k|v + rope (fp16 gemv)"));
     } else if (rows) {
-      GLinearArgs g;
-      memset(&g, 0, sizeof(g));
-      g.x = h; g.ldx = D; g.w = L.wq; g.w1 = L.wk; g.w2 = L.wv; g.n0 = nq; g.n1 = nq + nkv; g.norm_w = L.attention_norm; g.eps = m->norm_eps;
-      g.out = ws.qkv; g.ldo = qkv_cols; g.M = T; g.N = qkv_cols; g.K = D; g.epi = G_EPI_STORE;
+      const GLinearArgs g = fused(h, L.attention_norm, L.wq, L.wk, L.wv, nq, nq + nkv, ws.qkv, qkv_cols, G_EPI_STORE);
       MI_TRY(hip_rc(launch_g_linear(dt, g, s), "norm + q|k|v"));
     } else {
       MI_TRY(hip_rc(launch_g_rmsnorm(dt, ws.xn, h, L.attention_norm, T, D, m->norm_eps, s), "attention_norm"));
-      GLinearArgs g;
-      memset(&g, 0, sizeof(g));
-      g.x = ws.xn; g.ldx = D; g.w = L.wq; g.w1 = L.wk; g.w2 = L.wv; g.n0 = nq; g.n1 = nq + nkv;
-      g.out = ws.qkv; g.ldo = qkv_cols; g.M = T; g.N = qkv_cols; g.K = D; g.epi = G_EPI_STORE;
+      const GLinearArgs g = fused(ws.xn, nullptr, L.wq, L.wk, L.wv, nq, nq + nkv, ws.qkv, qkv_cols, G_EPI_STORE);
       if (g_linear_fused_ok(dt, g)) {  // (fp16, at least 256 rows: one launch of the 256-tile kernel)
         MI_TRY(hip_rc(launch_g_linear(dt, g, s), "q|k|v"));
       } else {
@@ -1146,40 +1140,22 @@ int mi_forward_generic(const mi_model_t* m, const mi_batch_t* bt, int dtype, mi_
       MI_TRY(hip_rc(launch_g_kv_write(dt, ck, cv, W, ws.qkv + (size_t)nq * es, ws.qkv + (size_t)(nq + nkv) * es, qkv_cols, T, nkv,
                                       bt->tok_seq, bt->tok_pos, bt->q_start, kvl, Dh, s), "kv_write"));
     // ---- h = h + wo(attn)
-    if (rows16) {
-      GemvArgs a;
-      memset(&a, 0, sizeof(a));
-      a.mode = GEMV_RESIDUAL; a.K = nq; a.N = D; a.x = (const bf16_t*)ws.attn; a.ldx = nq;
-      a.w0 = (const bf16_t*)L.wo; a.n0 = a.n1 = D; a.out = h; a.ldo = D; a.residual = (const bf16_t*)h;
-      MI_TRY(gemv16(a, "wo (fp16 gemv)"));
-    } else {
+    if (rows16)
+      MI_TRY(gemv_passes(kGemvF16, gemv_residual(ws.attn, nq, L.wo, h, D), T, s, "wo (fp16 gemv)"));
+    else
       MI_TRY(linear(ws.attn, nq, L.wo, h, D, D, nq, G_EPI_RESIDUAL, h, nullptr, "wo"));
-    }
     // ---- h = h + FFN(ffn_norm(h))
     if (m->num_experts == 0) {
       if (!L.w1 || !L.w2 || !L.w3) return fail(MI_ERR_ARG, "mi_forward_generic: dense layer without w1/w2/w3");
       if (rows16) {
-        GemvArgs a;
-        memset(&a, 0, sizeof(a));
-        a.mode = GEMV_SWIGLU; a.K = D; a.N = F; a.x = (const bf16_t*)h; a.ldx = D;
-        a.norm_w = (const bf16_t*)L.ffn_norm; a.eps = m->norm_eps;
-        a.w0 = (const bf16_t*)L.w1; a.w1 = (const bf16_t*)L.w3; a.n0 = a.n1 = F; a.out = ws.a; a.ldo = F;
-        MI_TRY(gemv16(a, "norm + w1|w3 + swiglu (fp16 gemv)"));
-        memset(&a, 0, sizeof(a));
-        a.mode = GEMV_RESIDUAL; a.K = F; a.N = D; a.x = (const bf16_t*)ws.a; a.ldx = F;
-        a.w0 = (const bf16_t*)L.w2; a.n0 = a.n1 = D; a.out = h; a.ldo = D; a.residual = (const bf16_t*)h;
-        MI_TRY(gemv16(a, "w2 (fp16 gemv)"));
+        MI_TRY(gemv_passes(kGemvF16, gemv_swiglu(h, D, L.ffn_norm, m->norm_eps, L.w1, L.w3, ws.a, F), T, s, "norm + w1|w3 + swiglu (fp16 gemv)"));
+        MI_TRY(gemv_passes(kGemvF16, gemv_residual(ws.a, F, L.w2, h, D), T, s, "w2 (fp16 gemv)"));
       } else if (rows) {
-        GLinearArgs g;
-        memset(&g, 0, sizeof(g));
-        g.x = h; g.ldx = D; g.w = L.w1; g.w1 = L.w3; g.norm_w = L.ffn_norm; g.eps = m->norm_eps;
-        g.out = ws.a; g.ldo = F; g.M = T; g.N = F; g.K = D; g.epi = G_EPI_SWIGLU;
+        const GLinearArgs g = fused(h, L.ffn_norm, L.w1, L.w3, nullptr, 0, 0, ws.a, F, G_EPI_SWIGLU);
         MI_TRY(hip_rc(launch_g_linear(dt, g, s), "norm + w1|w3 + swiglu"));
       } else {
         MI_TRY(hip_rc(launch_g_rmsnorm(dt, ws.xn, h, L.ffn_norm, T, D, m->norm_eps, s), "ffn_norm"));
-        GLinearArgs g;
-        memset(&g, 0, sizeof(g));
-        g.x = ws.xn; g.ldx = D; g.w = L.w1; g.w1 = L.w3; g.out = ws.a; g.ldo = F; g.M = T; g.N = F; g.K = D; g.epi = G_EPI_SWIGLU;
+        const GLinearArgs g = fused(ws.xn, nullptr, L.w1, L.w3, nullptr, 0, 0, ws.a, F, G_EPI_SWIGLU);
         if (g_linear_fused_ok(dt, g)) {
           MI_TRY(hip_rc(launch_g_linear(dt, g, s), "w1|w3 + swiglu"));
         } else {
@@ -1215,31 +1191,16 @@ int mi_forward_generic(const mi_model_t* m, const mi_batch_t* bt, int dtype, mi_
   if (m->final_norm) {
     if (bt->logits) {
       if (rows16) {
-        GemvArgs a;
-        memset(&a, 0, sizeof(a));
-        a.mode = GEMV_LOGITS; a.K = D; a.N = m->vocab_size; a.x = (const bf16_t*)h; a.ldx = D;
-        a.norm_w = (const bf16_t*)m->final_norm; a.eps = m->norm_eps;
-        a.w0 = (const bf16_t*)m->output; a.n0 = a.n1 = m->vocab_size; a.out = bt->logits; a.ldo = m->vocab_size;
-        MI_TRY(gemv16(a, "final norm + lm head (fp16 gemv)"));
+        MI_TRY(gemv_passes(kGemvF16, gemv_logits(h, D, m->final_norm, m->norm_eps, m->output, bt->logits, m->vocab_size), T, s,
+                           "final norm + lm head (fp16 gemv)"));
       } else if (rows) {
-        GLinearArgs g;
-        memset(&g, 0, sizeof(g));
-        g.x = h; g.ldx = D; g.w = m->output; g.norm_w = m->final_norm; g.eps = m->norm_eps;
-        g.out = bt->logits; g.ldo = m->vocab_size; g.M = T; g.N = m->vocab_size; g.K = D; g.epi = G_EPI_LOGITS;
+        const GLinearArgs g = fused(h, m->final_norm, m->output, nullptr, nullptr, 0, 0, bt->logits, m->vocab_size, G_EPI_LOGITS);
         MI_TRY(hip_rc(launch_g_linear(dt, g, s), "final norm + lm head"));
       } else {
         MI_TRY(hip_rc(launch_g_rmsnorm(dt, ws.xn, h, m->final_norm, T, D, m->norm_eps, s), "final norm"));
         MI_TRY(linear(ws.xn, D, m->output, bt->logits, m->vocab_size, m->vocab_size, D, G_EPI_LOGITS, nullptr, nullptr, "lm head"));
       }
-      if (want_sample) {
-        if (want_topp)
-          MI_TRY(hip_rc(launch_sample_top_p(bt->logits, m->vocab_size, B, m->vocab_size, bt->sample_temperature, bt->sample_top_p,
-                                            bt->sample_seed, bt->sample_offset, nullptr, bt->greedy_token, bt->greedy_logprob,
-                                            bt->hist_token, bt->hist_logprob, bt->hist_len, ws.ctrl, s), "top-p sample"));
-        else
-          MI_TRY(hip_rc(launch_greedy_rows(bt->logits, m->vocab_size, B, m->vocab_size, bt->greedy_token, bt->greedy_logprob,
-                                           bt->hist_token, bt->hist_logprob, bt->hist_len, ws.ctrl, s), "greedy sample"));
-      }
+      if (bi.want_sample) MI_TRY(sample_step(bt, m, bi.want_topp, ws.ctrl, s));
     } else {
       MI_TRY(hip_rc(launch_g_rmsnorm(dt, h, h, m->final_norm, T, D, m->norm_eps, s), "final norm"));
     }

@@ -9,6 +9,8 @@ tests run fp32 models (tests/test_generate.py:51,100).  Parity here is against
   (c) the reference's own self-consistency tests (prefill log-probabilities == decode log-probabilities within 5e-4 in fp32,
       tests/test_generate.py:36-69,199-230) through this package's `generate()`;
 and for bf16 models whose shape `mi_forward` declines (head_dim 64, top_k = 3, 32 experts) against the bf16 oracle."""
+import os
+
 import pytest
 import torch
 
@@ -216,6 +218,38 @@ def test_shapes_the_tuned_kernels_decline(over, dtype, tmp_path):
             n += len(keep[f])
     assert n >= 0.5 * sum(sum(s) for s in schedule)
     assert worst <= {BF: 4e-2, F16: 5e-3, F32: 2e-5}[dtype], worst
+
+
+@pytest.fixture(scope="module")
+def _two_pass_model():
+    """One layer whose four weight-streaming launches each take two passes at 8 tokens: every contraction is 10240 long (dim =
+    hidden_dim = 10240; n_heads * head_dim = 512 for Wo is the exception and stays one pass), gemv_max_tokens(10240) = 6."""
+    args = mo.OracleArgs(dim=10240, n_layers=1, head_dim=128, hidden_dim=10240, n_heads=4, n_kv_heads=2, norm_eps=1e-5, vocab_size=512)
+    return args, mo.synth_weights(args, seed=11, dtype=BF)
+
+
+@pytest.mark.parametrize("dtype", [F16, BF], ids=["fp16_generic", "bf16_tuned"])
+def test_eight_token_prompt_whose_gemvs_take_two_passes(dtype, _two_pass_model, tmp_path):
+    """The pass loop of the weight-streaming GEMVs inside a whole model: one 8-token prompt (passes of 6 + 2 rows in the q|k|v,
+    gate|up, down and LM-head launches) and two decode steps, fp16 through mi_forward_generic (the fp16 compile of the kernels)
+    and bf16 through mi_forward, each against the oracle in its own dtype within this file's bound for that dtype."""
+    args, w_bf = _two_pass_model
+    # the library reads this switch once per process, so it cannot be pinned here: with 0 the fp16 model would take the generic row
+    # kernel and pass without ever reaching the fp16 compile's pass loop
+    assert os.environ.get("MI_GENERIC_GEMV_TUNED", "1") != "0", "MI_GENERIC_GEMV_TUNED=0 routes fp16 away from the loop under test"
+    w = {k: v.to(dtype) for k, v in w_bf.items()}
+    model = _load(tmp_path, args, w, dtype, max_batch_size=1)
+    assert model._backend.plan(model) is not None and model._backend.generic == (dtype == F16)
+    prompts, toks = [[(37 * i + 5) % 512 for i in range(8)]], [[101, 317]]
+    pre, dec = _replay(model, prompts, toks, None, 2, dtype)
+    o_pre, o_dec = _replay_oracle(args, w, prompts, toks, None, 2, 1, dtype)
+    assert pre[0].shape == (8, 512) and len(dec) == 2
+    worst = 0.0
+    for got, orc in zip(pre + dec, o_pre + o_dec):
+        assert torch.isfinite(got).all()
+        worst = max(worst, (got - orc).abs().max().item())
+    print(f"\ntwo-pass model {dtype}: max |HIP - oracle| {worst:.3e}, logit abs max {max(o.abs().max().item() for o in o_pre + o_dec):.3f}")
+    assert worst <= {BF: 4e-2, F16: 5e-3}[dtype], worst
 
 
 @pytest.mark.parametrize("dtype", [F32, F16])

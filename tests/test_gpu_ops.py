@@ -450,6 +450,67 @@ def test_qkv_rope_kvwrite_leaf(T, H, Hkv, D):
     assert float((got2.float() - ref.float()).abs().max()) <= float(err.max()) + 4e-2
 
 
+# K = 10240 is the smallest multiple-of-512 contraction of the shape family at which 8 rows do not fit the GEMV's LDS budget in
+# equal parts: gemv_max_tokens(10240) = 6 (147456 / 20480 = 7, stepped down to 6), so T = 8 runs as passes of 6 + 2 rows.
+PASS_K, PASS_SPLIT = 10240, 6
+
+
+@pytest.mark.parametrize("head_major", [False, True], ids=["slot_major", "head_major"])
+def test_qkv_rope_kvwrite_passes_equal_the_caller_splitting_the_rows(head_major):
+    """T = 8 at D = 10240 takes two passes inside mi_qkv_rope_kvwrite (rows 0-5, then 6-7): qkv and both rings must be bit-equal
+    to two calls on those row ranges with x, qkv, tok_pos and tok_seq offset by the caller (positions and sequence ids differ
+    from row to row, so a pass that kept the first pass's metadata or ring rows cannot pass)."""
+    h = _hip()
+    T, D, H, Hkv, Dh, W = 8, PASS_K, 4, 2, 128, 24
+    x = rnd(T, D, seed=50, scale=2.0).cuda()
+    nw = (1 + 0.1 * torch.randn(D, generator=torch.Generator().manual_seed(51))).to(BF).cuda()
+    wq, wk, wv = (rnd(n, D, seed=52 + i, scale=D ** -0.5).cuda() for i, n in enumerate((H * Dh, Hkv * Dh, Hkv * Dh)))
+    cs = mo.rope_angles(Dh, 4000, 1e6).cuda()
+    pos = torch.randint(0, 4000, (T,), generator=torch.Generator().manual_seed(55), dtype=torch.int32).cuda()
+    seq = torch.tensor([5, 2, 7, 0, 3, 6, 1, 4], dtype=torch.int32).cuda()
+
+    def ring():
+        if head_major:
+            return torch.zeros(T, Hkv, W, Dh, dtype=BF, device="cuda").permute(0, 2, 1, 3)
+        return torch.zeros(T, W, Hkv, Dh, dtype=BF, device="cuda")
+
+    def run(rows, ck, cv):
+        return h.qkv_rope_kvwrite(x[rows], wq, wk, wv, Dh, cs, pos[rows].contiguous(), norm_w=nw, eps=1e-5, cache_k=ck, cache_v=cv,
+                                  tok_seq=seq[rows].contiguous())
+
+    ck1, cv1, ck2, cv2 = ring(), ring(), ring(), ring()
+    whole = run(slice(0, T), ck1, cv1)
+    parts = torch.cat([run(slice(0, PASS_SPLIT), ck2, cv2), run(slice(PASS_SPLIT, T), ck2, cv2)])
+    assert torch.equal(whole, parts)
+    assert torch.equal(ck1, ck2) and torch.equal(cv1, cv2)
+    assert int((ck1.float().abs().amax(dim=(1, 2, 3)) > 0).sum()) == T   # every sequence's ring received its row
+    assert not torch.equal(whole[:2], whole[PASS_SPLIT:])                  # (the second pass is not a replay of the first)
+
+
+@pytest.mark.parametrize("norm", [False, True], ids=["plain", "fused_norm"])
+@pytest.mark.parametrize("epi", ["store", "residual", "swiglu", "logits"])
+def test_linear_passes_equal_the_caller_splitting_the_rows(epi, norm):
+    """mi_linear with M = 8, K = 10240, N = 512: the two passes (6 + 2 rows) are bit-equal to two calls on those row ranges, in
+    every epilogue - residual rows all different, fp32 logits (the 4-byte output stride) - with and without the fused RMSNorm."""
+    h = _hip()
+    M, K, N = 8, PASS_K, 512
+    x = rnd(M, K, seed=60, scale=2.0).cuda()
+    w1, w3 = rnd(N, K, seed=61, scale=K ** -0.5).cuda(), rnd(N, K, seed=62, scale=K ** -0.5).cuda()
+    res = rnd(M, N, seed=63).cuda()
+    nw = (1 + 0.1 * torch.randn(K, generator=torch.Generator().manual_seed(64))).to(BF).cuda() if norm else None
+    code = {"store": h.EPI_STORE, "residual": h.EPI_RESIDUAL, "swiglu": h.EPI_SWIGLU, "logits": h.EPI_LOGITS}[epi]
+
+    def run(rows):
+        return h.linear(x[rows], (w1, w3) if epi == "swiglu" else (w1,), code, residual=res[rows] if epi == "residual" else None,
+                        norm_w=nw, eps=1e-5 if norm else 0.0)
+
+    whole = run(slice(0, M))
+    parts = torch.cat([run(slice(0, PASS_SPLIT)), run(slice(PASS_SPLIT, M))])
+    assert whole.dtype == (torch.float32 if epi == "logits" else BF) and whole.shape == (M, N)
+    assert torch.equal(whole, parts)
+    assert bool((whole.float().abs().amax(dim=1) > 0).all())
+
+
 def _moe_case(T, D, Fh, E, k, seed):
     x = rnd(T, D, seed=seed, scale=1.0)
     gate = rnd(E, D, seed=seed + 1, scale=0.05)
