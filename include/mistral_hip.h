@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MI_ABI_VERSION 7
+#define MI_ABI_VERSION 8
 
 #define MI_OK 0
 #define MI_ERR_ARG (-1)        /* null pointer / non-positive size                        */
@@ -96,6 +96,21 @@ enum mi_epilogue {
  * residual: [M, ldo] (may alias out).  out is bf16 [M, ldo] (fp32 for MI_EPI_LOGITS). */
 int mi_linear(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
               int epilogue, const void* residual, const void* norm_w, float eps, mi_stream_t stream);
+
+/* ABI v8 - lora.py:71-74 LoRALinear.forward on a bf16 model: mi_linear with un-merged adapters beside the frozen weight.
+ * Segment i (w[i], n_rows[i]) has the adapter A[i] [rank, K], B[i] [n_rows[i], rank]; a NULL pair = no adapter.  With fp32
+ * accumulation in each product:
+ *     t = bf16(A x)      d = bf16(bf16(B t) * scaling)      y = bf16(bf16(W x) + d)      out = epilogue(y)
+ * where y stands exactly where bf16(acc) stands in mi_linear's epilogues (MI_EPI_STORE, MI_EPI_RESIDUAL, MI_EPI_SWIGLU:
+ * w[0] = W1, w[1] = W3 with their own adapters; MI_EPI_LOGITS has no adapter form: the LM head carries none).  The base
+ * product bf16(W x) is mi_linear's own GEMV (M <= 8) or MFMA GEMM pass; two more launches form t and apply the rest.
+ * rank: a multiple of 8 up to 64 (MI_ERR_SHAPE otherwise).  x is the linear's input; norm_w != NULL (M <= 8 only, as
+ * mi_linear) puts RMSNorm(x; norm_w, eps) in front of W and of A.  ldx must be a multiple of 8.
+ * scratch: device memory of at least mi_lora_linear_scratch_bytes(M, K, n_rows, epilogue, rank, norm_w != NULL) bytes. */
+size_t mi_lora_linear_scratch_bytes(int M, int K, const int n_rows[3], int epilogue, int rank, int fused_norm);
+int mi_lora_linear(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
+                   int epilogue, const void* residual, const void* norm_w, float eps, const void* const A[3],
+                   const void* const B[3], int rank, float scaling, void* scratch, size_t scratch_bytes, mi_stream_t stream);
 
 /* generate.py:101-118 needs, of the prompt's [T, vocab] logits (transformer.py:235-242), only log_softmax(logits)[t, next
  * token]: logprob[m] = l[m, target[m]] - logsumexp(l[m, :]) with l = float(bf16(x @ W^T)), computed in ONE pass over the
@@ -190,6 +205,13 @@ int mi_moe_grouped_gemm(void* out, const void* residual, const void* x, int ldx,
  * Whole local layer stack: Transformer.forward_partial (transformer.py:163-219) + the LM head of
  * Transformer.forward (transformer.py:229-242)
  * ---------------------------------------------------------------------------------------------- */
+/* ABI v8 - un-merged LoRA adapters of one layer (lora.py:52-61): A [rank, in], B [out, rank], bf16, for each of the seven
+ * linears.  A NULL pair: that linear has no adapter.  The MoE gate and the LM head never have one. */
+typedef struct mi_lora_layer {
+  const void *wq_a, *wq_b, *wk_a, *wk_b, *wv_a, *wv_b, *wo_a, *wo_b;
+  const void *w1_a, *w1_b, *w2_a, *w2_b, *w3_a, *w3_b;
+} mi_lora_layer_t;
+
 typedef struct mi_layer {
   const void* attention_norm; /* [D]            transformer_layers.py:143 */
   const void* wq;             /* [H*Dh, D]      transformer_layers.py:51  */
@@ -203,6 +225,7 @@ typedef struct mi_layer {
   const void* gate;           /* [E, D]  MoE router (NULL when dense) moe.py:20 */
   const void* const* expert_w_dev;  /* DEVICE array [E][3] of (w1,w2,w3) pointers, moe.py:19 */
   const void* const* expert_w_host; /* the same table in host memory */
+  const mi_lora_layer_t* lora;      /* ABI v8: host pointer, read when mi_model_t.lora_rank > 0 (NULL: no adapter in this layer) */
 } mi_layer_t;
 
 typedef struct mi_model {
@@ -216,6 +239,11 @@ typedef struct mi_model {
   const float* rope_cs;           /* fp32 [rope_len, Dh/2, 2] */
   int32_t rope_len;
   const mi_layer_t* layers;       /* host array [n_layers] */
+  /* ABI v8 - un-merged LoRA (params.json `lora`, lora.py:12-19).  0 / 0.0 (a zero-initialised struct): none.  rank > 0:
+   * every linear of every layer runs as mi_lora_linear describes, on the launch path for every T (the persistent engine
+   * declines such a model); dense bf16 models only - a MoE model and mi_forward_generic return MI_ERR_UNSUPPORTED. */
+  int32_t lora_rank;              /* multiple of 8 up to 64 */
+  float lora_scaling;
 } mi_model_t;
 
 enum mi_branch {

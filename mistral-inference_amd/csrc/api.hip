@@ -94,6 +94,7 @@ int g_slot = -1;  // experiment slot that mi_forward tries first (-1: none)
 template <class Try>
 bool engine_route(int variant, bool nemo_opt_in, const EngineBuild* slot, const EngProblem& pr, Try&& try_build) {
   const bool moe = pr.E > 0;
+  if (pr.lora_rank > 0) return false;  // un-merged LoRA adapters: no engine build carries them, the launch path does (lora.hip)
   auto takes = [&](int b) { return kBuilds[b]->applicable(pr, nullptr, 0); };
   if (slot && slot->applicable(pr, nullptr, 0) && try_build(*slot)) return true;
   // the dense GQA-4 headline shapes: the `next` compile (build_native.ENGINE_NEXT_FLAGS)
@@ -150,7 +151,9 @@ struct Workspace {
   void* gran;        // decode-engine granule regions (dense models)
   size_t gran_bytes;
   int max_tiles;
-  size_t total;
+  bf16_t* lora_t;    // un-merged LoRA (lora_rank > 0 only, behind everything else): t = bf16(A x)   [T, 3 * rank]
+  void* lora_base;   // ... and the base products of q|k|v and w1|w3  [T, max(qkv cols, 2 F)]: fp32 holding bf16 values for T <= 8
+  size_t total;      //     (the GEMV's LOGITS form, see lora_linear), bf16 above.  Wo's and W2's base product goes to xn.
 };
 
 Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base) {
@@ -182,6 +185,13 @@ Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base) {
   w.tile_tab = (int32_t*)take((size_t)w.max_tiles * 16);
   w.n_tiles = (int32_t*)take(256);
   w.moe_y = (bf16_t*)take(m->num_experts > 0 ? (size_t)T * slots * m->dim * 2 : 0);
+  w.lora_t = nullptr;
+  w.lora_base = nullptr;
+  if (m->lora_rank > 0) {  // (lora_rank == 0: the layout and the total are exactly those of ABI v7)
+    const size_t wide = (size_t)(qkv_cols > 2 * m->hidden_dim ? qkv_cols : 2 * m->hidden_dim);
+    w.lora_t = (bf16_t*)take((size_t)T * 3 * m->lora_rank * 2);
+    w.lora_base = take((size_t)T * wide * (T <= GEMV_MAX_T ? 4 : 2));
+  }
   w.total = off;
   return w;
 }
@@ -313,6 +323,100 @@ int moe_grouped(void* out, const void* residual, const void* x, int T, int D, in
   return hip_rc(launch_moe_combine(out, residual, w.y, sel_idx, sel_w, w.row_of, T, D, k, s), "moe combine");
 }
 
+// ---- un-merged LoRA linear (lora.py:71-74): the base product by the tuned GEMV / GEMM in its plain store form, then lora_down and
+// lora_up (lora.hip).  One description for the leaf (mi_lora_linear) and for the linears of mi_forward.
+struct LoraLinear {
+  const void* w[3];     // weight segments as mi_linear takes them (SWIGLU: W1, W3)
+  const void* A[3];     // [rank, K] per segment or nullptr
+  const void* B[3];     // [rows of the segment, rank] or nullptr
+  int n_rows[3];
+  int nseg;
+  int epilogue;         // MI_EPI_STORE / RESIDUAL / SWIGLU
+};
+bool lora_rank_ok(int rank) { return rank >= 8 && rank <= 64 && rank % 8 == 0; }
+// x: the input of W as the base pass reads it (pre-norm when norm_w is given: the GEMV fuses the RMSNorm); xn: the normalised
+// input (== x without norm_w), which lora_down reads.  base: [M, sum of n_rows] scratch - bf16, or with base_f32 fp32 holding
+// bf16 values: the GEMV's LOGITS form, whose fused RMSNorm is the one of the fused q|k|v and W1|W3 modes (gemv_core.cuh
+// kNormMode: same staging, same order of the sum of squares), so that a model whose adapters are zero reproduces the plain
+// model bit for bit.  M <= 8 only; needs M <= gemv passes like every GEMV launch here.
+int lora_linear(void* out, int ldo, const void* x, int ldx, const void* xn, int ldxn, int M, int K, const LoraLinear& L, const void* residual,
+                const void* norm_w, float eps, int rank, float scaling, void* base, bool base_f32, bf16_t* t, hipStream_t s) {
+  const bool swiglu = L.epilogue == MI_EPI_SWIGLU;
+  int n_total = 0;
+  for (int i = 0; i < L.nseg; ++i) n_total += L.n_rows[i];
+  const int n0 = L.n_rows[0], n1 = L.nseg > 1 ? n0 + L.n_rows[1] : n_total;
+  if (M <= GEMV_MAX_T) {
+    GemvArgs a = gemv_common(x, ldx, K, n_total, norm_w, eps, base, n_total);
+    a.mode = base_f32 ? GEMV_LOGITS : GEMV_STORE;
+    a.w0 = (const bf16_t*)L.w[0]; a.w1 = (const bf16_t*)L.w[1]; a.w2 = (const bf16_t*)L.w[2]; a.n0 = n0; a.n1 = n1;
+    MI_TRY(gemv_passes(kGemvBf16, a, M, s, "lora base gemv"));
+  } else {
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.epi = GEMM_STORE; g.M = M; g.N = n_total; g.K = K; g.a = (const bf16_t*)x; g.lda = ldx;
+    g.w0 = (const bf16_t*)L.w[0]; g.w1 = (const bf16_t*)L.w[1]; g.w2 = (const bf16_t*)L.w[2]; g.n0 = n0; g.n1 = n1;
+    g.out = base; g.ldo = n_total;
+    MI_TRY(hip_rc(launch_gemm(g, s), "lora base gemm"));
+  }
+  bool any = false;
+  for (int i = 0; i < L.nseg; ++i) any = any || (L.A[i] && L.B[i]);
+  if (any) {
+    LoraDownArgs d;
+    memset(&d, 0, sizeof(d));
+    d.x = (const bf16_t*)xn; d.ldx = ldxn; d.T = M; d.K = K; d.nseg = L.nseg; d.r = rank; d.t = t;
+    for (int i = 0; i < L.nseg; ++i) d.A[i] = (L.A[i] && L.B[i]) ? (const bf16_t*)L.A[i] : nullptr;
+    MI_TRY(hip_rc(launch_lora_down(d, s), "lora_down"));
+  }
+  LoraUpArgs u;
+  memset(&u, 0, sizeof(u));
+  u.epi = L.epilogue; u.T = M; u.N = swiglu ? n0 : n_total; u.base = base; u.ldb = n_total; u.base_f32 = base_f32 ? 1 : 0;
+  u.t = t; u.n0 = n0; u.n1 = n1; u.nseg = L.nseg; u.r = rank; u.scaling = scaling;
+  for (int i = 0; i < L.nseg; ++i) u.B[i] = (L.A[i] && L.B[i]) ? (const bf16_t*)L.B[i] : nullptr;
+  u.out = (bf16_t*)out; u.ldo = ldo; u.residual = (const bf16_t*)residual;
+  u.fast_silu = M > GEMV_MAX_T;  // (the SiLU of the path that a plain linear of this M takes: gemv_core.cuh / gemm.hip)
+  return hip_rc(launch_lora_up(u, s), "lora_up");
+}
+struct LoraScratch {
+  void* base;
+  bf16_t* t;
+  bf16_t* xn;
+  size_t total;
+};
+LoraScratch lora_carve(int M, int K, int n_total, int nseg, int rank, bool base_f32, bool fused_norm, char* p) {
+  LoraScratch w;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* q = p ? p + off : nullptr;
+    off += align_up(bytes);
+    return q;
+  };
+  w.base = take((size_t)M * n_total * (base_f32 ? 4 : 2));
+  w.t = (bf16_t*)take((size_t)M * nseg * rank * 2);
+  w.xn = (bf16_t*)take(fused_norm ? (size_t)M * K * 2 : 0);
+  w.total = off;
+  return w;
+}
+// what the leaf derives from its arguments (0 segments: refused)
+struct LoraShape {
+  int nseg, n_total;
+  bool base_f32;
+};
+LoraShape lora_shape(const int n_rows[3], int epilogue, bool fused_norm) {
+  LoraShape sh = {0, 0, false};
+  if (epilogue == MI_EPI_SWIGLU) {
+    sh.nseg = 2;
+    sh.n_total = 2 * n_rows[0];
+  } else {
+    for (int i = 0; i < 3 && n_rows[i] > 0; ++i) {
+      ++sh.nseg;
+      sh.n_total += n_rows[i];
+    }
+  }
+  // the plain linear a fused-norm SwiGLU compares with is the GEMV's norm mode; store / residual with a fused norm are not
+  sh.base_f32 = fused_norm && epilogue == MI_EPI_SWIGLU;
+  return sh;
+}
+
 // ---- attention arguments (scratch = the tickets block and the split partials behind it)
 AttnDecodeArgs attn_decode_args(void* out, const void* q, int ldq, const void* cache_k, const void* cache_v, int kv_layout, int W,
                                 int B, int H, int Hkv, int Dh, const int32_t* tok_pos, int32_t* tickets, float* partial) {
@@ -395,6 +499,11 @@ int check_model(const mi_model_t* m) {
   if (m->num_experts > 16 || m->top_k > 4 || (m->top_k == 3)) return fail(MI_ERR_SHAPE, "MoE: E <= 16, top_k in {1,2,4}");
   if (m->num_experts > 0 && (size_t)m->top_k * m->hidden_dim * 2 > 65536)
     return fail(MI_ERR_SHAPE, "MoE: top_k * hidden_dim too large for the decode combine kernel");
+  if (m->lora_rank < 0 || (m->lora_rank > 0 && !lora_rank_ok(m->lora_rank)))
+    return fail(MI_ERR_SHAPE, "LoRA rank %d: the kernels take multiples of 8 up to 64", m->lora_rank);
+  if (m->lora_rank > 0 && m->num_experts > 0)
+    return fail(MI_ERR_UNSUPPORTED, "un-merged LoRA on a MoE model is not implemented (adapters inside the experts); merge the adapter");
+  if (m->lora_rank > 0 && !(m->lora_scaling > 0.f)) return fail(MI_ERR_ARG, "lora_scaling %g must be > 0 (lora.py:19)", (double)m->lora_scaling);
   return MI_OK;
 }
 
@@ -477,6 +586,48 @@ int mi_linear(void* out, int ldo, const void* x, int ldx, int M, int K, const vo
     g.N = n2; g.n0 = n0; g.n1 = n1;
   }
   return hip_rc(launch_gemm(g, s), "gemm");
+}
+
+/* lora.py:71-74 */
+size_t mi_lora_linear_scratch_bytes(int M, int K, const int n_rows[3], int epilogue, int rank, int fused_norm) {
+  if (M <= 0 || K <= 0 || !n_rows || !lora_rank_ok(rank)) return 0;
+  const LoraShape sh = lora_shape(n_rows, epilogue, fused_norm != 0);
+  if (sh.nseg == 0) return 0;
+  return lora_carve(M, K, sh.n_total, sh.nseg, rank, sh.base_f32, fused_norm != 0, nullptr).total;
+}
+
+/* lora.py:71-74 */
+int mi_lora_linear(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
+                   int epilogue, const void* residual, const void* norm_w, float eps, const void* const A[3],
+                   const void* const B[3], int rank, float scaling, void* scratch, size_t scratch_bytes, mi_stream_t stream) {
+  if (!out || !x || !w || !n_rows || !w[0] || !A || !B || !scratch || M <= 0 || K <= 0 || K % 8 || ldx % 8 || n_rows[0] <= 0)
+    return fail(MI_ERR_ARG, "mi_lora_linear");
+  if (epilogue != MI_EPI_STORE && epilogue != MI_EPI_RESIDUAL && epilogue != MI_EPI_SWIGLU)
+    return fail(MI_ERR_ARG, "mi_lora_linear: epilogue %d (store, residual and swiglu carry adapters; the LM head has none)", epilogue);
+  if (epilogue == MI_EPI_RESIDUAL && !residual) return fail(MI_ERR_ARG, "mi_lora_linear: residual epilogue without residual");
+  if (epilogue == MI_EPI_SWIGLU && (!w[1] || n_rows[0] != n_rows[1])) return fail(MI_ERR_ARG, "mi_lora_linear: swiglu needs W1, W3");
+  if (!lora_rank_ok(rank)) return fail(MI_ERR_SHAPE, "mi_lora_linear: LoRA rank %d: the kernels take multiples of 8 up to 64", rank);
+  if (!(scaling > 0.f)) return fail(MI_ERR_ARG, "mi_lora_linear: scaling %g must be > 0 (lora.py:19)", (double)scaling);
+  if (norm_w && M > GEMV_MAX_T) return fail(MI_ERR_UNSUPPORTED, "mi_lora_linear: fused RMSNorm only on the M <= 8 path");
+  const LoraShape sh = lora_shape(n_rows, epilogue, norm_w != nullptr);
+  LoraLinear L;
+  memset(&L, 0, sizeof(L));
+  L.nseg = sh.nseg; L.epilogue = epilogue;
+  for (int i = 0; i < sh.nseg; ++i) {
+    if (!w[i]) return fail(MI_ERR_ARG, "mi_lora_linear: n_rows[%d] without a weight", i);
+    if ((A[i] == nullptr) != (B[i] == nullptr)) return fail(MI_ERR_ARG, "mi_lora_linear: adapter %d needs both A and B (or neither)", i);
+    L.w[i] = w[i]; L.A[i] = A[i]; L.B[i] = B[i]; L.n_rows[i] = epilogue == MI_EPI_SWIGLU ? n_rows[0] : n_rows[i];
+  }
+  const LoraScratch sc = lora_carve(M, K, sh.n_total, sh.nseg, rank, sh.base_f32, norm_w != nullptr, (char*)scratch);
+  if (sc.total > scratch_bytes) return fail(MI_ERR_WORKSPACE, "mi_lora_linear: scratch %zu < required %zu", scratch_bytes, sc.total);
+  hipStream_t s = (hipStream_t)stream;
+  const void* xn = x;
+  int ldxn = ldx;
+  if (norm_w) {
+    MI_TRY(hip_rc(launch_rmsnorm(sc.xn, x, norm_w, M, K, eps, s), "lora rmsnorm"));
+    xn = sc.xn; ldxn = K;
+  }
+  return lora_linear(out, ldo, x, ldx, xn, ldxn, M, K, L, residual, norm_w, eps, rank, scaling, sc.base, sh.base_f32, sc.t, s);
 }
 
 namespace {
@@ -753,6 +904,7 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
   const int D = m->dim, H = m->n_heads, Hkv = m->n_kv_heads, Dh = m->head_dim, F = m->hidden_dim;
   const int nq = H * Dh, nkv = Hkv * Dh, qkv_cols = nq + 2 * nkv;
   const bool gemv = T <= GEMV_MAX_T;
+  const bool lora = m->lora_rank > 0;
   bf16_t* h = (bf16_t*)bt->h;
 
   // input_ids == NULL: h already holds this stage's input - received from the previous pipeline rank, or the multimodal
@@ -776,7 +928,7 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
       pr.hist_tok = bt->hist_token; pr.hist_lp = bt->hist_logprob; pr.hist_len = bt->hist_len;
     }
     pr.granules = ws.gran; pr.granule_bytes = ws.gran_bytes; pr.ctrl = engine_ctrl;
-    pr.E = m->num_experts; pr.top_k = m->top_k;
+    pr.E = m->num_experts; pr.top_k = m->top_k; pr.lora_rank = m->lora_rank;
     pr.forced = engine_variant() == 1;
     bool dense_ok = true;
     for (int l = 0; l < m->n_layers; ++l)
@@ -820,8 +972,20 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
                                     kvl, Dh, s), what);
     };
 
-    // ---- attention_norm + q|k|v + RoPE (+ ring write at decode)
-    if (gemv) {
+    // ---- un-merged LoRA (ABI v8): every linear is [base product] [lora_down] [lora_up] (lora_linear above); RoPE and the ring
+    // write are the separate passes (bit-equal to the fused epilogues: same arithmetic on the same bf16 values)
+    static const mi_lora_layer_t kNoAdapters = {};
+    const mi_lora_layer_t& A = (lora && L.lora) ? *L.lora : kNoAdapters;
+    const float ls = m->lora_scaling;
+    if (lora) {
+      if (!L.w1 || !L.w2 || !L.w3) return fail(MI_ERR_ARG, "mi_forward: dense layer without w1/w2/w3");
+      MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, L.attention_norm, T, D, m->norm_eps, s), "attention_norm"));
+      const LoraLinear qkv = {{L.wq, L.wk, L.wv}, {A.wq_a, A.wk_a, A.wv_a}, {A.wq_b, A.wk_b, A.wv_b}, {nq, nkv, nkv}, 3, MI_EPI_STORE};
+      MI_TRY(lora_linear(ws.qkv, qkv_cols, gemv ? (const void*)h : ws.xn, D, ws.xn, D, T, D, qkv, nullptr, gemv ? L.attention_norm : nullptr,
+                         m->norm_eps, m->lora_rank, ls, ws.lora_base, gemv, ws.lora_t, s));
+      MI_TRY(hip_rc(launch_rope(ws.qkv, qkv_cols, T, H, Hkv, Dh, m->rope_cs, bt->tok_pos, s), "rope"));
+      if (branch == MI_BRANCH_DECODE) MI_TRY(kv_write("kv_write (decode)"));
+    } else if (gemv) {
       const RingWrite ring = {ck, cv, W, kvl};
       MI_TRY(gemv_passes(kGemvBf16, gemv_qkv_rope(h, D, D, L.attention_norm, m->norm_eps, L.wq, L.wk, L.wv, nq, nkv, ws.qkv, qkv_cols,
                                                   m->rope_cs, bt->tok_pos, bt->tok_seq, Dh, branch == MI_BRANCH_DECODE ? &ring : nullptr),
@@ -856,13 +1020,23 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
     }
 
     // ---- h = h + attn @ Wo^T
-    if (gemv)
+    if (lora) {
+      const LoraLinear wo = {{L.wo, nullptr, nullptr}, {A.wo_a, nullptr, nullptr}, {A.wo_b, nullptr, nullptr}, {D, 0, 0}, 1, MI_EPI_RESIDUAL};
+      MI_TRY(lora_linear(h, D, ws.attn, nq, ws.attn, nq, T, nq, wo, h, nullptr, 0.f, m->lora_rank, ls, ws.xn, false, ws.lora_t, s));
+    } else if (gemv)
       MI_TRY(gemv_passes(kGemvBf16, gemv_residual(ws.attn, nq, L.wo, h, D), T, s, "wo gemv"));
     else
       MI_TRY(hip_rc(launch_gemm(gemm_args(GEMM_RESIDUAL, ws.attn, T, nq, L.wo, nullptr, D, h, h), s), "wo gemm"));
 
     // ---- h = h + FFN(ffn_norm(h))
-    if (m->num_experts == 0) {
+    if (lora) {
+      MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, L.ffn_norm, T, D, m->norm_eps, s), "ffn_norm"));
+      const LoraLinear w13 = {{L.w1, L.w3, nullptr}, {A.w1_a, A.w3_a, nullptr}, {A.w1_b, A.w3_b, nullptr}, {F, F, 0}, 2, MI_EPI_SWIGLU};
+      MI_TRY(lora_linear(ws.hid, F, gemv ? (const void*)h : ws.xn, D, ws.xn, D, T, D, w13, nullptr, gemv ? L.ffn_norm : nullptr, m->norm_eps,
+                         m->lora_rank, ls, ws.lora_base, gemv, ws.lora_t, s));
+      const LoraLinear w2 = {{L.w2, nullptr, nullptr}, {A.w2_a, nullptr, nullptr}, {A.w2_b, nullptr, nullptr}, {D, 0, 0}, 1, MI_EPI_RESIDUAL};
+      MI_TRY(lora_linear(h, D, ws.hid, F, ws.hid, F, T, F, w2, h, nullptr, 0.f, m->lora_rank, ls, ws.xn, false, ws.lora_t, s));
+    } else if (m->num_experts == 0) {
       if (gemv) {
         MI_TRY(gemv_passes(kGemvBf16, gemv_swiglu(h, D, L.ffn_norm, m->norm_eps, L.w1, L.w3, ws.hid, F), T, s, "w13 gemv"));
         MI_TRY(gemv_passes(kGemvBf16, gemv_residual(ws.hid, F, L.w2, h, D), T, s, "w2 gemv"));
@@ -948,6 +1122,8 @@ GWorkspace carve_generic(const mi_model_t* m, int T, size_t es, char* base) {
 
 int check_model_generic(const mi_model_t* m, int dtype) {
   if (!m || !m->layers) return fail(MI_ERR_ARG, "null model");
+  if (m->lora_rank != 0)
+    return fail(MI_ERR_UNSUPPORTED, "un-merged LoRA on fp16 / fp32 storage (mi_forward_generic) is not implemented; merge the adapter");
   if (!dtype_ok(dtype)) return fail(MI_ERR_ARG, "storage dtype %d", dtype);
   if (m->head_dim <= 0 || m->head_dim > 256 || m->head_dim % 8) return fail(MI_ERR_SHAPE, "head_dim %d: multiple of 8, <= 256", m->head_dim);
   if (m->n_kv_heads <= 0 || m->n_heads % m->n_kv_heads) return fail(MI_ERR_SHAPE, "n_heads %% n_kv_heads != 0");

@@ -280,6 +280,7 @@ struct EngProblem {
   size_t granule_bytes;
   uint32_t* ctrl;
   int forced;                // mi_debug_set_engine_variant(1): take shapes that measured slower than the launch path too (traces, tests)
+  int lora_rank;             // > 0: the model carries un-merged LoRA adapters - no engine build takes it (api.hip engine_route)
 };
 static_assert(sizeof(EngArgs) <= 4096, "EngArgs must fit the kernel-argument segment");
 size_t decode_engine_granule_bytes(int D, int H, int Hkv, int F, int maxW);  // the same for every build (default object only)
@@ -309,6 +310,34 @@ const EngineBuild& decode_engine_build_nemo();
 const EngineBuild& decode_engine_build_wide();
 // -DENG_WIDE=2: the wide build's additions on the 8-fill ring, for MoE models whose hid vector fits beside it (Mixtral-8x7B)
 const EngineBuild& decode_engine_build_moe();
+
+// ---------------------------------------------------------------------------------------------- un-merged LoRA (lora.hip)
+// lora.py:71-74 around a base product that the tuned GEMV / GEMM has already written:  t = bf16(A x),
+// d = bf16(bf16(B t) * s), y = bf16(base + d), out = epilogue(y).  Up to three adapters share an input (q|k|v, w1|w3).
+struct LoraDownArgs {
+  const bf16_t* x;      // [T, ldx] the linear's input (already normalised)
+  int ldx, T, K;
+  const bf16_t* A[3];   // [r, K] each; nullptr: the segment has no adapter (its slice of t is neither written nor read)
+  int nseg, r;
+  bf16_t* t;            // [T, nseg * r]
+};
+struct LoraUpArgs {
+  int epi;              // MI_EPI_STORE / MI_EPI_RESIDUAL / MI_EPI_SWIGLU
+  int T, N;             // N: output columns (SWIGLU: hidden_dim; the base then holds 2 N columns, W1's then W3's)
+  const void* base;     // [T, ldb] bf16(W x): bf16, or fp32 holding bf16 values (base_f32: the GEMV's LOGITS form)
+  int ldb, base_f32;
+  const bf16_t* t;      // [T, nseg * r]
+  const bf16_t* B[3];   // [n_rows of the segment, r] each; nullptr: d = 0
+  int n0, n1;           // segment ends as in GemvArgs (STORE / RESIDUAL)
+  int nseg, r;
+  float scaling;
+  bf16_t* out;          // [T, ldo]; may alias a bf16 base (STORE / RESIDUAL) or the residual
+  int ldo;
+  const bf16_t* residual;  // [T, ldo]
+  int fast_silu;        // SiLU as the MFMA GEMM's epilogue evaluates it (swiglu_bf_fast) instead of the GEMV's (swiglu_bf)
+};
+hipError_t launch_lora_down(const LoraDownArgs& a, hipStream_t s);
+hipError_t launch_lora_up(const LoraUpArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------- generic storage dtype
 // generic.hip: the operator sequence of the hot path for fp32 / fp16 storage (and for bf16 shapes the tuned kernels

@@ -21,7 +21,7 @@ def _default_lib() -> str:
 
 LIB_PATH = os.environ.get("MISTRAL_HIP_LIB", _default_lib())
 
-MI_ABI_VERSION = 7
+MI_ABI_VERSION = 8
 EPI_STORE, EPI_RESIDUAL, EPI_SWIGLU, EPI_LOGITS = 0, 1, 2, 3
 BRANCH_NOCACHE, BRANCH_PREFILL, BRANCH_DECODE = 0, 1, 2
 GEMV_MAX_T = 8
@@ -32,9 +32,14 @@ DTYPE_CODES = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}
 _vp = C.c_void_p
 
 
+class MiLoraLayer(C.Structure):
+    """ABI v8 `mi_lora_layer_t`: A [rank, in] / B [out, rank] of the seven linears of a layer (None pair: no adapter)."""
+    _fields_ = [(f"{n}_{ab}", _vp) for n in ("wq", "wk", "wv", "wo", "w1", "w2", "w3") for ab in ("a", "b")]
+
+
 class MiLayer(C.Structure):
     _fields_ = [(n, _vp) for n in ("attention_norm", "wq", "wk", "wv", "wo", "ffn_norm", "w1", "w2", "w3", "gate",
-                                   "expert_w_dev", "expert_w_host")]
+                                   "expert_w_dev", "expert_w_host")] + [("lora", C.POINTER(MiLoraLayer))]  # ABI v8
 
 
 class MiModel(C.Structure):
@@ -44,6 +49,7 @@ class MiModel(C.Structure):
         ("num_experts", C.c_int32), ("top_k", C.c_int32), ("norm_eps", C.c_float),
         ("tok_embeddings", _vp), ("final_norm", _vp), ("output", _vp), ("rope_cs", _vp), ("rope_len", C.c_int32),
         ("layers", C.POINTER(MiLayer)),
+        ("lora_rank", C.c_int32), ("lora_scaling", C.c_float),  # ABI v8: un-merged LoRA (0: none)
     ]
 
 
@@ -72,6 +78,9 @@ _SIGS = {
     "mi_kv_write": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "mi_linear": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp), C.POINTER(C.c_int), C.c_int,
                             _vp, _vp, C.c_float, _vp]),
+    "mi_lora_linear_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int]),  # ABI v8
+    "mi_lora_linear": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp), C.POINTER(C.c_int), C.c_int,
+                                 _vp, _vp, C.c_float, C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.c_float, _vp, C.c_size_t, _vp]),
     "mi_attn_decode_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "mi_attn_decode": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),
     "mi_attn_prefill": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp,
@@ -235,6 +244,41 @@ def linear(x: torch.Tensor, weights: Sequence[torch.Tensor], epilogue: int = EPI
     nr = (C.c_int * 3)(*n_rows, *([0] * (3 - len(weights))))
     check(lib().mi_linear(dev_ptr(out, odt), out.stride(0), dev_ptr(x), x.stride(0), M, K, wp, nr, epilogue,
                           dev_ptr(residual), dev_ptr(norm_w), float(eps), stream_ptr(x.device)), "mi_linear")
+    return out
+
+
+def lora_linear(x: torch.Tensor, weights: Sequence[torch.Tensor], lora_a: Sequence[Optional[torch.Tensor]],
+                lora_b: Sequence[Optional[torch.Tensor]], scaling: float, epilogue: int = EPI_STORE,
+                residual: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`linear` with un-merged LoRA adapters (reference lora.py:71-74): segment i adds bf16(bf16(B_i bf16(A_i x)) * scaling) to
+    bf16(W_i x) before the epilogue.  lora_a[i] [rank, K] / lora_b[i] [n_rows_i, rank]; a None pair: no adapter."""
+    assert 1 <= len(weights) <= 3 and len(lora_a) == len(lora_b) == len(weights) and x.dim() == 2
+    if x.dtype != torch.bfloat16:
+        raise NotImplementedError("un-merged LoRA with fp16 / fp32 storage is not implemented (bf16 models only)")
+    M, K = x.shape
+    n_rows = [w.shape[0] for w in weights]
+    rank = next((a.shape[0] for a in lora_a if a is not None), 8)
+    for w, a, b in zip(weights, lora_a, lora_b):
+        assert w.shape[1] == K and w.is_contiguous() and (a is None) == (b is None)
+        if a is not None:
+            assert tuple(a.shape) == (rank, K) and tuple(b.shape) == (w.shape[0], rank) and a.is_contiguous() and b.is_contiguous()
+    N = n_rows[0] if epilogue == EPI_SWIGLU else sum(n_rows)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    pad = [None] * (3 - len(weights))
+    wp = (_vp * 3)(*[dev_ptr(w) for w in weights], *pad)
+    ap = (_vp * 3)(*[dev_ptr(a) for a in lora_a], *pad)
+    bp = (_vp * 3)(*[dev_ptr(b) for b in lora_b], *pad)
+    nr = (C.c_int * 3)(*n_rows, *([0] * (3 - len(weights))))
+    L = lib()
+    need = L.mi_lora_linear_scratch_bytes(M, K, nr, epilogue, rank, 1 if norm_w is not None else 0)
+    if need == 0:  # a shape the entry refuses: let it say why
+        need = 256
+    scratch = torch.empty(need, dtype=torch.uint8, device=x.device)  # per call, from the caching allocator (as lm_head_logprobs)
+    check(L.mi_lora_linear(dev_ptr(out), out.stride(0), dev_ptr(x), x.stride(0), M, K, wp, nr, epilogue, dev_ptr(residual),
+                           dev_ptr(norm_w), float(eps), ap, bp, rank, float(scaling), scratch.data_ptr(), scratch.numel(),
+                           stream_ptr(x.device)), "mi_lora_linear")
     return out
 
 

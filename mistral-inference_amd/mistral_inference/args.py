@@ -81,7 +81,7 @@ class TransformerArgs(_FromDict):
     max_batch_size: int = 0     # set by from_folder; forward asserts len(seqlens) <= max_batch_size
     rope_theta: Optional[float] = None          # None -> 1e6 (reference transformer.py:115)
     moe: Optional[MoeArgs] = None               # sparse FFN: experts and experts per token
-    lora: Optional[LoraArgs] = None             # un-merged LoRA layers are rejected; load_lora() merges adapters
+    lora: Optional[LoraArgs] = None             # un-merged LoRA layers (lora.py; dense bf16 models); without it load_lora() merges
     sliding_window: Union[None, int, List[Optional[int]]] = None   # one window, or one per layer (cycled)
     _sliding_window: Union[None, int, List[Optional[int]]] = None  # legacy spelling of the same key
     model_type: str = "transformer"

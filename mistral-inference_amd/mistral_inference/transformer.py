@@ -31,9 +31,10 @@ from torch import nn
 from . import _hip
 from .args import TransformerArgs
 from .cache import BatchMetadata, BufferCache
+from .lora import LoRALinear, check_rank
 from .model import ModelBase
 from .rope import precompute_freqs_cis
-from .transformer_layers import RMSNorm, TransformerBlock
+from .transformer_layers import LORA_MOE_REFUSAL, RMSNorm, TransformerBlock
 from .vision_encoder import PATCH_MERGE, PatchMerger, VisionLanguageAdapter, VisionTransformer
 
 ROPE_TABLE_LEN = 128_000  # reference transformer.py:116
@@ -63,6 +64,13 @@ class GreedyBuffers:
     top_p: float = 0.8
     seed: int = 0
     offset: int = 0           # added to the workspace's step counter: the session's draws start at Philox counter 1
+
+
+def refuse_lora_storage(dtype: Optional[torch.dtype]) -> None:
+    """Un-merged LoRA runs on bf16 storage only (csrc/lora.hip); fp16 / fp32 models go through mi_forward_generic, which has none."""
+    if dtype is not None and dtype != torch.bfloat16:
+        raise NotImplementedError(f"un-merged LoRA with fp16 / fp32 storage ({dtype}) is not implemented; load the model in "
+                                  "bfloat16 or merge the adapter into the weights")
 
 
 def tuned_kernels_take(a: TransformerArgs) -> bool:
@@ -98,14 +106,28 @@ class HipStackBackend:
         # (reference transformer.py:303,338 keeps any dtype; its tests build fp32 models, tests/test_generate.py:51) and bf16
         # shapes mi_forward declines with MI_ERR_SHAPE - through mi_forward_generic with the reference's rounding points
         self.generic = dt != torch.bfloat16 or not tuned_kernels_take(a)
+        if a.lora is not None:
+            refuse_lora_storage(dt)
+            if self.generic:  # bf16, but a shape mi_forward declines (head_dim != 128 ...): the generic kernels carry no adapters
+                raise NotImplementedError("un-merged LoRA on a model shape outside the tuned bf16 kernels (head_dim 128, "
+                                          "dim / hidden_dim multiples of 8) is not implemented; merge the adapter into the weights")
         self.dtype_code = _hip.DTYPE_CODES[dt]
         keep = []  # python objects that own memory referenced by raw pointers
         p = lambda t, d=dt: _hip.dev_ptr(t, d)  # noqa: E731
         E = a.moe.num_experts if a.moe is not None else 0
         layers = (_hip.MiLayer * max(1, model.n_local_layers))()
+        adapters = (_hip.MiLoraLayer * max(1, model.n_local_layers))() if a.lora is not None else None
+        keep.append(adapters)
         for j, blk in enumerate(model.layers.values()):
             L = layers[j]
             at = blk.attention
+            if adapters is not None:  # ABI v8: `.weight` below is LoRALinear's frozen `linear.weight`
+                ff = blk.feed_forward
+                for name, mod in (("wq", at.wq), ("wk", at.wk), ("wv", at.wv), ("wo", at.wo), ("w1", ff.w1), ("w2", ff.w2), ("w3", ff.w3)):
+                    assert isinstance(mod, LoRALinear) and mod.rank == a.lora.rank
+                    setattr(adapters[j], name + "_a", p(mod.lora_A.weight))
+                    setattr(adapters[j], name + "_b", p(mod.lora_B.weight))
+                L.lora = C.pointer(adapters[j])
             L.attention_norm, L.ffn_norm = p(blk.attention_norm.weight), p(blk.ffn_norm.weight)
             L.wq, L.wk, L.wv, L.wo = p(at.wq.weight), p(at.wk.weight), p(at.wv.weight), p(at.wo.weight)
             if E:
@@ -134,6 +156,8 @@ class HipStackBackend:
         m.output = p(model.output.weight) if model.output is not None else None
         m.rope_cs, m.rope_len = p(rope, torch.float32), rope.shape[0]
         m.layers = C.cast(layers, C.POINTER(_hip.MiLayer))
+        if a.lora is not None:
+            m.lora_rank, m.lora_scaling = int(a.lora.rank), float(a.lora.scaling)
         return m, keep
 
     def plan(self, model: "Transformer"):
@@ -260,8 +284,10 @@ class Transformer(ModelBase):
         self.pipeline_rank = pipeline_rank
         self.num_pipeline_ranks = num_pipeline_ranks
         self.softmax_fp32 = softmax_fp32
-        if args.lora is not None:
-            raise NotImplementedError("un-merged LoRA is outside the hot path; merge the adapter into the weights")
+        if args.lora is not None:  # un-merged adapters run on the HIP path (lora.py, csrc/lora.hip) - dense bf16 models
+            if args.moe is not None:
+                raise NotImplementedError(LORA_MOE_REFUSAL)
+            check_rank(args.lora.rank)
 
         # Rank-specific modules (reference transformer.py:52-79)
         self.tok_embeddings: Optional[nn.Embedding] = None
@@ -576,10 +602,13 @@ class Transformer(ModelBase):
         super().load_state_dict(mine, strict=strict, assign=assign)
         self._weights_changed()
 
-    # ---- LoRA (reference lora.py:92-139): adapters are MERGED into the frozen weights at load time -------------
+    # ---- LoRA (reference lora.py:92-155).  A model without `args.lora`: adapters are MERGED into the frozen weights at load
+    # time.  A model built with `args.lora`: they are copied into its LoRALinear layers and can be swapped at any time.
     def load_lora(self, lora_path: Union[Path, str], scaling: float = 2.0) -> None:
-        """Loads a LoRA checkpoint (safetensors with `<linear>.lora_A.weight` / `.lora_B.weight` keys) and folds it
-        into the weights: W <- W + (B @ A) * scaling, every nn.Linear of this rank's layers except `output`."""
+        """Loads a LoRA checkpoint (safetensors with `<linear>.lora_A.weight` / `.lora_B.weight` keys).  Without `args.lora`
+        it is folded into the weights: W <- W + (B @ A) * scaling, every nn.Linear of this rank's layers except `output`.
+        With `args.lora` the adapters replace the current ones in place (`scaling` is then `args.lora.scaling`, as in the
+        reference, lora.py:140-155); the base weights are not touched, so a second call swaps the fine-tune."""
         lora_path = Path(lora_path)
         assert lora_path.is_file(), f"{lora_path} does not exist or is not a file"
         self._load_lora_state_dict(safetensors.torch.load_file(str(lora_path)), scaling=scaling)
@@ -591,6 +620,8 @@ class Transformer(ModelBase):
         lora_dtype = lora_dtypes.pop()
         assert lora_dtype == self.dtype, f"LoRA weights dtype differs from model's dtype {lora_dtype} != {self.dtype}"
         assert all("lora" in key for key in lora_state_dict.keys())
+        if self.args.lora is not None:
+            return self._assign_lora(lora_state_dict)
         if self.dtype != torch.bfloat16 or self.device.type != "cuda":
             raise RuntimeError("load_lora: the merge runs on the GPU in bf16 (model must be on the device)")
         logging.info("Loading and merging LoRA weights...")
@@ -614,6 +645,23 @@ class Transformer(ModelBase):
         if hasattr(self._backend, "invalidate"):
             self._backend.invalidate()
 
+    def _assign_lora(self, lora_state_dict: Mapping[str, torch.Tensor]) -> None:
+        """lora.py:140-155 on a model built with `args.lora`: every adapter key of this rank's layers is copied INTO the existing
+        tensor (`copy_`, never a rebind), so that device pointers held by the native layer table, a live GreedySession or a
+        captured decode graph stay valid and see the new adapter at their next step."""
+        logging.info("Loading LoRA weights...")
+        params = dict(self.named_parameters())
+        with torch.no_grad():
+            for k, v in lora_state_dict.items():
+                if k.split(".")[1] not in self.layers:
+                    logging.debug("Skipping parameter %s at pipeline rank %d", k, self.pipeline_rank)
+                    continue
+                assert k in params, f"LoRA key {k} names no adapter of this model"
+                assert tuple(params[k].shape) == tuple(v.shape), (
+                    f"LoRA key {k}: shape {tuple(v.shape)} does not fit the model's adapter {tuple(params[k].shape)} "
+                    f"(rank {self.args.lora.rank})")
+                params[k].copy_(v)
+
     @staticmethod
     def from_folder(folder: Union[Path, str], max_batch_size: int = 1, num_pipeline_ranks: int = 1,
                     device: Union[torch.device, str] = "cuda", dtype: Optional[torch.dtype] = None,
@@ -625,6 +673,8 @@ class Transformer(ModelBase):
         with open(folder / "params.json", "r") as f:
             model_args = TransformerArgs.from_dict(json.load(f))
         model_args.max_batch_size = max_batch_size
+        if model_args.lora is not None:
+            refuse_lora_storage(dtype)   # before anything is read from disk
         pipeline_rank = torch.distributed.get_rank() if num_pipeline_ranks > 1 else 0
         with torch.device("meta"):
             model = Transformer(model_args, pipeline_rank=pipeline_rank, num_pipeline_ranks=num_pipeline_ranks,
@@ -638,16 +688,26 @@ class Transformer(ModelBase):
             model.load_state_dict(loaded, assign=True, strict=True)
             return model.to(device=device, dtype=dtype)
         wanted = set(model.state_dict().keys())
+        # a LoRA model takes both key forms (lora.py:76-89): `<name>.linear.weight` (+ optional `<name>.lora_A/B.weight`), or the
+        # plain `<name>.weight` of a base checkpoint, which LoRALinear loads with zero adapters
+        plain = {k.replace(".linear.weight", ".weight") for k in wanted if k.endswith(".linear.weight")} if model_args.lora else set()
         loaded = {}
         with safetensors.safe_open(str(st_file), framework="pt", device=str(device)) as f:
             for k in f.keys():
-                if k in wanted:
+                if k in wanted or k in plain:
                     loaded[k] = f.get_tensor(k)
                 else:
                     model._check_foreign_key(k)
-        missing = wanted - set(loaded)
+        have = set(loaded) | {k.replace(".weight", ".linear.weight") for k in loaded if k in plain}
+        missing = {k for k in wanted - have if ".lora_A." not in k and ".lora_B." not in k}  # absent adapters are not "missing"
         assert not missing, f"checkpoint is missing {sorted(missing)[:4]}..."
         nn.Module.load_state_dict(model, loaded, strict=True, assign=True)
+        for mod in model.modules():  # adapters the checkpoint did not carry start at zero: the base model
+            if isinstance(mod, LoRALinear):
+                for lin in (mod.lora_A, mod.lora_B):
+                    if lin.weight.is_meta:
+                        lin.weight = nn.Parameter(torch.zeros(lin.weight.shape, device=device, dtype=mod.linear.weight.dtype),
+                                                  requires_grad=False)
         model._weights_changed()
         return model.to(device=device, dtype=dtype)
 

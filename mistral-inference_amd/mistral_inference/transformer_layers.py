@@ -12,14 +12,23 @@ from torch import nn
 from . import _hip
 from .args import LoraArgs, MoeArgs
 from .cache import CacheView
+from .lora import LoRALinear, maybe_lora
 from .moe import MoeLayer
 
+LORA_MOE_REFUSAL = ("un-merged LoRA on a MoE model (adapters inside the experts) is not implemented; merge the adapter into the "
+                    "checkpoint first (what the reference's default CLI path does, lora.py:118-139)")
 
-def _no_lora(lora: Optional[LoraArgs]) -> None:
-    if lora is not None:
-        raise NotImplementedError(
-            "un-merged LoRA layers (params.json 'lora') are outside the hot path; merge the adapter into the "
-            "checkpoint first (what the reference's default CLI path does, lora.py:118-139)")
+
+def _no_lora(lora: Optional[LoraArgs], moe: Optional[MoeArgs]) -> None:
+    """The one refused combination at construction time (fp16 / fp32 storage is refused where the dtype is known: the first
+    forward, `_hip.lora_linear` / `HipStackBackend`)."""
+    if lora is not None and moe is not None:
+        raise NotImplementedError(LORA_MOE_REFUSAL)
+
+
+def _adapters(*mods):
+    """(lora_A weights, lora_B weights) of LoRALinear modules, for `_hip.lora_linear`."""
+    return tuple(m.lora_A.weight for m in mods), tuple(m.lora_B.weight for m in mods)
 
 
 class RMSNorm(nn.Module):
@@ -40,12 +49,16 @@ class FeedForward(nn.Module):
 
     def __init__(self, dim: int, hidden_dim: int, lora: Optional[LoraArgs] = None):
         super().__init__()
-        _no_lora(lora)
-        self.w1 = nn.Linear(dim, hidden_dim, bias=False)
-        self.w2 = nn.Linear(hidden_dim, dim, bias=False)
-        self.w3 = nn.Linear(dim, hidden_dim, bias=False)
+        linear = maybe_lora(lora)
+        self.w1 = linear(dim, hidden_dim, bias=False)
+        self.w2 = linear(hidden_dim, dim, bias=False)
+        self.w3 = linear(dim, hidden_dim, bias=False)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if isinstance(self.w1, LoRALinear):  # gate | up with their two adapters in one lora_up launch, then down
+            a, b = _adapters(self.w1, self.w3)
+            hid = _hip.lora_linear(x, (self.w1.weight, self.w3.weight), a, b, self.w1.scaling, _hip.EPI_SWIGLU)
+            return self.w2(hid)
         hid = _hip.linear(x, (self.w1.weight, self.w3.weight), _hip.EPI_SWIGLU)
         return _hip.linear(hid, (self.w2.weight,), _hip.EPI_STORE)
 
@@ -57,14 +70,14 @@ class Attention(nn.Module):
 
     def __init__(self, dim: int, n_heads: int, head_dim: int, n_kv_heads: int, lora: Optional[LoraArgs] = None):
         super().__init__()
-        _no_lora(lora)
         self.n_heads, self.head_dim, self.n_kv_heads = n_heads, head_dim, n_kv_heads
         self.repeats = n_heads // n_kv_heads
         self.scale = head_dim ** -0.5
-        self.wq = nn.Linear(dim, n_heads * head_dim, bias=False)
-        self.wk = nn.Linear(dim, n_kv_heads * head_dim, bias=False)
-        self.wv = nn.Linear(dim, n_kv_heads * head_dim, bias=False)
-        self.wo = nn.Linear(n_heads * head_dim, dim, bias=False)
+        linear = maybe_lora(lora)
+        self.wq = linear(dim, n_heads * head_dim, bias=False)
+        self.wk = linear(dim, n_kv_heads * head_dim, bias=False)
+        self.wv = linear(dim, n_kv_heads * head_dim, bias=False)
+        self.wo = linear(n_heads * head_dim, dim, bias=False)
 
     def forward(self, x: torch.Tensor, freqs_cis: torch.Tensor, cache: Optional[CacheView] = None,
                 mask=None) -> torch.Tensor:
@@ -74,7 +87,12 @@ class Attention(nn.Module):
         nq, nkv = H * Dh, Hkv * Dh
         cs = torch.view_as_real(freqs_cis).contiguous()  # rows already gathered by position (transformer.py:199)
         rows = torch.arange(T, dtype=torch.int32, device=x.device)
-        if T <= _hip.GEMV_MAX_T:  # decode-sized: projection + RoPE in the one weight-streaming launch
+        lora = isinstance(self.wq, LoRALinear)
+        if lora:  # q | k | v with their three adapters: base product, lora_down, lora_up; RoPE as its own pass
+            a, b = _adapters(self.wq, self.wk, self.wv)
+            qkv = _hip.lora_linear(x, (self.wq.weight, self.wk.weight, self.wv.weight), a, b, self.wq.scaling, _hip.EPI_STORE)
+            _hip.rope_inplace(qkv, H, Hkv, Dh, cs, rows)
+        elif T <= _hip.GEMV_MAX_T:  # decode-sized: projection + RoPE in the one weight-streaming launch
             qkv = _hip.qkv_rope_kvwrite(x, self.wq.weight, self.wk.weight, self.wv.weight, Dh, cs, rows)
         else:
             qkv = _hip.linear(x, (self.wq.weight, self.wk.weight, self.wv.weight), _hip.EPI_STORE)
@@ -92,6 +110,8 @@ class Attention(nn.Module):
             else:
                 cache.update(qkv[:, nq:nq + nkv], qkv[:, nq + nkv:])
                 out = _hip.attn_decode(qkv, cache.cache_k, cache.cache_v, H, b.tok_pos)
+        if lora:
+            return self.wo(out)
         return _hip.linear(out, (self.wo.weight,), _hip.EPI_STORE)
 
 
@@ -101,6 +121,7 @@ class TransformerBlock(nn.Module):
     def __init__(self, dim: int, hidden_dim: int, n_heads: int, n_kv_heads: int, head_dim: int, norm_eps: float,
                  lora: Optional[LoraArgs] = None, moe: Optional[MoeArgs] = None):
         super().__init__()
+        _no_lora(lora, moe)
         self.n_heads = n_heads
         self.dim = dim
         self.attention = Attention(dim=dim, n_heads=n_heads, head_dim=head_dim, n_kv_heads=n_kv_heads, lora=lora)
