@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define MI_ABI_VERSION 8
+#define MI_ABI_VERSION 9
 
 #define MI_OK 0
 #define MI_ERR_ARG (-1)        /* null pointer / non-positive size                        */
@@ -111,6 +111,18 @@ size_t mi_lora_linear_scratch_bytes(int M, int K, const int n_rows[3], int epilo
 int mi_lora_linear(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
                    int epilogue, const void* residual, const void* norm_w, float eps, const void* const A[3],
                    const void* const B[3], int rank, float scaling, void* scratch, size_t scratch_bytes, mi_stream_t stream);
+
+/* ABI v9 - mi_lora_linear with one adapter PER ROW out of a bank of `slots` adapter sets.  The reference has one adapter set per
+ * model (lora.py:52-61); row m here is what lora.py:71-74 computes for that row with the adapters of slot row_slot[m] loaded,
+ * with the rounding points of mi_lora_linear - bit for bit the row of an mi_lora_linear call on that slot's A / B.
+ * A[i] / B[i]: bases of contiguous per-slot arrays [slots, rank, K] / [slots, n_rows[i], rank] (a NULL pair: no adapter in any
+ * slot).  row_slot: device int32 [M], values -1 .. slots - 1; -1 = the row has no adapter (y = bf16(bf16(W x) + 0)); a value
+ * outside the range is the caller's error - the kernels clamp it into the bank.  row_slot == NULL: every row on slot 0, on
+ * mi_lora_linear's own kernels.  scratch: mi_lora_linear_scratch_bytes, unchanged. */
+int mi_lora_linear_slots(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
+                         int epilogue, const void* residual, const void* norm_w, float eps, const void* const A[3],
+                         const void* const B[3], int rank, float scaling, int slots, const int32_t* row_slot, void* scratch,
+                         size_t scratch_bytes, mi_stream_t stream);
 
 /* generate.py:101-118 needs, of the prompt's [T, vocab] logits (transformer.py:235-242), only log_softmax(logits)[t, next
  * token]: logprob[m] = l[m, target[m]] - logsumexp(l[m, :]) with l = float(bf16(x @ W^T)), computed in ONE pass over the
@@ -206,7 +218,9 @@ int mi_moe_grouped_gemm(void* out, const void* residual, const void* x, int ldx,
  * Transformer.forward (transformer.py:229-242)
  * ---------------------------------------------------------------------------------------------- */
 /* ABI v8 - un-merged LoRA adapters of one layer (lora.py:52-61): A [rank, in], B [out, rank], bf16, for each of the seven
- * linears.  A NULL pair: that linear has no adapter.  The MoE gate and the LM head never have one. */
+ * linears.  A NULL pair: that linear has no adapter.  The MoE gate and the LM head never have one.
+ * ABI v9 - with mi_model_t.lora_slots > 1 every non-NULL pointer is the base of a contiguous per-slot array:
+ * A [lora_slots, rank, in], B [lora_slots, out, rank]; slot 0 is what ABI v8 pointed to. */
 typedef struct mi_lora_layer {
   const void *wq_a, *wq_b, *wk_a, *wk_b, *wv_a, *wv_b, *wo_a, *wo_b;
   const void *w1_a, *w1_b, *w2_a, *w2_b, *w3_a, *w3_b;
@@ -244,6 +258,9 @@ typedef struct mi_model {
    * declines such a model); dense bf16 models only - a MoE model and mi_forward_generic return MI_ERR_UNSUPPORTED. */
   int32_t lora_rank;              /* multiple of 8 up to 64 */
   float lora_scaling;
+  /* ABI v9 - adapter bank: lora_slots adapter sets (lora.py:52-61 each) beside ONE set of frozen weights, one of them chosen per
+   * sequence by mi_batch_t.seq_adapter.  0 and 1 both mean one slot: the ABI v8 behaviour.  Needs lora_rank > 0 (MI_ERR_ARG). */
+  int32_t lora_slots;
 } mi_model_t;
 
 enum mi_branch {
@@ -305,6 +322,12 @@ typedef struct mi_batch {
   uint64_t sample_offset;
   /* ABI v7 */
   int32_t kv_layout;            /* MI_KV_SLOT_MAJOR (0, the reference's shape) or MI_KV_HEAD_MAJOR: layout of EVERY ring in cache_k / cache_v */
+  /* ABI v9 - one LoRA adapter set per sequence (lora.py:71-74 per row): the rows of sequence b are what the reference computes
+   * for that sequence with the adapters of slot seq_adapter[b] loaded.  Values -1 .. lora_slots - 1; -1 = the base model for that
+   * sequence.  Read on all three branches through tok_seq (NOCACHE: tok_seq[t] must then name the row's entry of seq_adapter).
+   * NULL: every sequence on slot 0, the ABI v8 launches.  Non-NULL with lora_rank == 0: MI_ERR_ARG.  The pointer, not the
+   * values, is what a captured step holds: a caller may rewrite the array between replays. */
+  const int32_t* seq_adapter;   /* dev [B] or NULL */
 } mi_batch_t;
 
 size_t mi_workspace_bytes(const mi_model_t* model, int T, int B, int max_cache_size);

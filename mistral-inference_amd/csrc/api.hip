@@ -332,6 +332,11 @@ struct LoraLinear {
   int n_rows[3];
   int nseg;
   int epilogue;         // MI_EPI_STORE / RESIDUAL / SWIGLU
+  // adapter banks (ABI v9; all zero: one adapter set, the single-adapter kernels).  seq_slot != nullptr: A[i] / B[i] are the
+  // bases of [slots, rank, K] / [slots, n_rows[i], rank] arrays and row m runs through slot seq_slot[tok_seq[m]] (LoraDownArgs)
+  int slots;
+  const int32_t* tok_seq;
+  const int32_t* seq_slot;
 };
 bool lora_rank_ok(int rank) { return rank >= 8 && rank <= 64 && rank % 8 == 0; }
 // x: the input of W as the base pass reads it (pre-norm when norm_w is given: the GEMV fuses the RMSNorm); xn: the normalised
@@ -364,6 +369,7 @@ int lora_linear(void* out, int ldo, const void* x, int ldx, const void* xn, int 
     LoraDownArgs d;
     memset(&d, 0, sizeof(d));
     d.x = (const bf16_t*)xn; d.ldx = ldxn; d.T = M; d.K = K; d.nseg = L.nseg; d.r = rank; d.t = t;
+    d.slots = L.slots > 1 ? L.slots : 1; d.a_stride = (int64_t)rank * K; d.tok_seq = L.tok_seq; d.seq_slot = L.seq_slot;
     for (int i = 0; i < L.nseg; ++i) d.A[i] = (L.A[i] && L.B[i]) ? (const bf16_t*)L.A[i] : nullptr;
     MI_TRY(hip_rc(launch_lora_down(d, s), "lora_down"));
   }
@@ -371,6 +377,8 @@ int lora_linear(void* out, int ldo, const void* x, int ldx, const void* xn, int 
   memset(&u, 0, sizeof(u));
   u.epi = L.epilogue; u.T = M; u.N = swiglu ? n0 : n_total; u.base = base; u.ldb = n_total; u.base_f32 = base_f32 ? 1 : 0;
   u.t = t; u.n0 = n0; u.n1 = n1; u.nseg = L.nseg; u.r = rank; u.scaling = scaling;
+  u.slots = L.slots > 1 ? L.slots : 1; u.tok_seq = L.tok_seq; u.seq_slot = L.seq_slot;
+  for (int i = 0; i < L.nseg; ++i) u.b_stride[i] = (int64_t)L.n_rows[i] * rank;
   for (int i = 0; i < L.nseg; ++i) u.B[i] = (L.A[i] && L.B[i]) ? (const bf16_t*)L.B[i] : nullptr;
   u.out = (bf16_t*)out; u.ldo = ldo; u.residual = (const bf16_t*)residual;
   u.fast_silu = M > GEMV_MAX_T;  // (the SiLU of the path that a plain linear of this M takes: gemv_core.cuh / gemm.hip)
@@ -460,6 +468,7 @@ int check_batch(const char* entry, const mi_model_t* m, const mi_batch_t* bt, bo
   if (b.branch == MI_BRANCH_DECODE && (b.T != b.B || !bt->kv_seqlens)) return fail(MI_ERR_ARG, "%s: decode needs T == B", entry);
   if (attn_rows && (size_t)b.B * m->n_kv_heads * 4 > TICKET_BYTES) return fail(MI_ERR_SHAPE, "B * n_kv_heads > 1024");
   if (bt->logits && (!m->final_norm || !m->output)) return fail(MI_ERR_ARG, "%s: logits on a rank without LM head", entry);
+  if (bt->seq_adapter && m->lora_rank <= 0) return fail(MI_ERR_ARG, "%s: seq_adapter on a model without un-merged LoRA (lora_rank 0)", entry);
   return MI_OK;
 }
 // The checks behind it: the entry's carved size against the caller's, then the sample request.
@@ -504,6 +513,8 @@ int check_model(const mi_model_t* m) {
   if (m->lora_rank > 0 && m->num_experts > 0)
     return fail(MI_ERR_UNSUPPORTED, "un-merged LoRA on a MoE model is not implemented (adapters inside the experts); merge the adapter");
   if (m->lora_rank > 0 && !(m->lora_scaling > 0.f)) return fail(MI_ERR_ARG, "lora_scaling %g must be > 0 (lora.py:19)", (double)m->lora_scaling);
+  if (m->lora_slots < 0 || (m->lora_slots > 1 && m->lora_rank == 0))
+    return fail(MI_ERR_ARG, "lora_slots %d: an adapter bank needs lora_rank > 0 and at least one slot", m->lora_slots);
   return MI_OK;
 }
 
@@ -596,30 +607,33 @@ size_t mi_lora_linear_scratch_bytes(int M, int K, const int n_rows[3], int epilo
   return lora_carve(M, K, sh.n_total, sh.nseg, rank, sh.base_f32, fused_norm != 0, nullptr).total;
 }
 
-/* lora.py:71-74 */
-int mi_lora_linear(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
-                   int epilogue, const void* residual, const void* norm_w, float eps, const void* const A[3],
-                   const void* const B[3], int rank, float scaling, void* scratch, size_t scratch_bytes, mi_stream_t stream) {
+/* lora.py:71-74; slots / row_slot: the adapter bank of mi_lora_linear_slots (1 / NULL: one adapter set) */
+static int lora_linear_leaf(const char* entry, void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3],
+                            const int n_rows[3], int epilogue, const void* residual, const void* norm_w, float eps,
+                            const void* const A[3], const void* const B[3], int rank, float scaling, int slots, const int32_t* row_slot,
+                            void* scratch, size_t scratch_bytes, mi_stream_t stream) {
   if (!out || !x || !w || !n_rows || !w[0] || !A || !B || !scratch || M <= 0 || K <= 0 || K % 8 || ldx % 8 || n_rows[0] <= 0)
-    return fail(MI_ERR_ARG, "mi_lora_linear");
+    return fail(MI_ERR_ARG, "%s", entry);
   if (epilogue != MI_EPI_STORE && epilogue != MI_EPI_RESIDUAL && epilogue != MI_EPI_SWIGLU)
-    return fail(MI_ERR_ARG, "mi_lora_linear: epilogue %d (store, residual and swiglu carry adapters; the LM head has none)", epilogue);
-  if (epilogue == MI_EPI_RESIDUAL && !residual) return fail(MI_ERR_ARG, "mi_lora_linear: residual epilogue without residual");
-  if (epilogue == MI_EPI_SWIGLU && (!w[1] || n_rows[0] != n_rows[1])) return fail(MI_ERR_ARG, "mi_lora_linear: swiglu needs W1, W3");
-  if (!lora_rank_ok(rank)) return fail(MI_ERR_SHAPE, "mi_lora_linear: LoRA rank %d: the kernels take multiples of 8 up to 64", rank);
-  if (!(scaling > 0.f)) return fail(MI_ERR_ARG, "mi_lora_linear: scaling %g must be > 0 (lora.py:19)", (double)scaling);
-  if (norm_w && M > GEMV_MAX_T) return fail(MI_ERR_UNSUPPORTED, "mi_lora_linear: fused RMSNorm only on the M <= 8 path");
+    return fail(MI_ERR_ARG, "%s: epilogue %d (store, residual and swiglu carry adapters; the LM head has none)", entry, epilogue);
+  if (epilogue == MI_EPI_RESIDUAL && !residual) return fail(MI_ERR_ARG, "%s: residual epilogue without residual", entry);
+  if (epilogue == MI_EPI_SWIGLU && (!w[1] || n_rows[0] != n_rows[1])) return fail(MI_ERR_ARG, "%s: swiglu needs W1, W3", entry);
+  if (!lora_rank_ok(rank)) return fail(MI_ERR_SHAPE, "%s: LoRA rank %d: the kernels take multiples of 8 up to 64", entry, rank);
+  if (!(scaling > 0.f)) return fail(MI_ERR_ARG, "%s: scaling %g must be > 0 (lora.py:19)", entry, (double)scaling);
+  if (norm_w && M > GEMV_MAX_T) return fail(MI_ERR_UNSUPPORTED, "%s: fused RMSNorm only on the M <= 8 path", entry);
   const LoraShape sh = lora_shape(n_rows, epilogue, norm_w != nullptr);
   LoraLinear L;
   memset(&L, 0, sizeof(L));
   L.nseg = sh.nseg; L.epilogue = epilogue;
+  if (slots < 1) return fail(MI_ERR_ARG, "%s: slots %d", entry, slots);
+  L.slots = slots; L.tok_seq = nullptr; L.seq_slot = row_slot;  // (tok_seq == nullptr: row m is its own sequence)
   for (int i = 0; i < sh.nseg; ++i) {
-    if (!w[i]) return fail(MI_ERR_ARG, "mi_lora_linear: n_rows[%d] without a weight", i);
-    if ((A[i] == nullptr) != (B[i] == nullptr)) return fail(MI_ERR_ARG, "mi_lora_linear: adapter %d needs both A and B (or neither)", i);
+    if (!w[i]) return fail(MI_ERR_ARG, "%s: n_rows[%d] without a weight", entry, i);
+    if ((A[i] == nullptr) != (B[i] == nullptr)) return fail(MI_ERR_ARG, "%s: adapter %d needs both A and B (or neither)", entry, i);
     L.w[i] = w[i]; L.A[i] = A[i]; L.B[i] = B[i]; L.n_rows[i] = epilogue == MI_EPI_SWIGLU ? n_rows[0] : n_rows[i];
   }
   const LoraScratch sc = lora_carve(M, K, sh.n_total, sh.nseg, rank, sh.base_f32, norm_w != nullptr, (char*)scratch);
-  if (sc.total > scratch_bytes) return fail(MI_ERR_WORKSPACE, "mi_lora_linear: scratch %zu < required %zu", scratch_bytes, sc.total);
+  if (sc.total > scratch_bytes) return fail(MI_ERR_WORKSPACE, "%s: scratch %zu < required %zu", entry, scratch_bytes, sc.total);
   hipStream_t s = (hipStream_t)stream;
   const void* xn = x;
   int ldxn = ldx;
@@ -628,6 +642,23 @@ int mi_lora_linear(void* out, int ldo, const void* x, int ldx, int M, int K, con
     xn = sc.xn; ldxn = K;
   }
   return lora_linear(out, ldo, x, ldx, xn, ldxn, M, K, L, residual, norm_w, eps, rank, scaling, sc.base, sh.base_f32, sc.t, s);
+}
+
+/* lora.py:71-74 */
+int mi_lora_linear(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
+                   int epilogue, const void* residual, const void* norm_w, float eps, const void* const A[3],
+                   const void* const B[3], int rank, float scaling, void* scratch, size_t scratch_bytes, mi_stream_t stream) {
+  return lora_linear_leaf("mi_lora_linear", out, ldo, x, ldx, M, K, w, n_rows, epilogue, residual, norm_w, eps, A, B, rank, scaling, 1,
+                          nullptr, scratch, scratch_bytes, stream);
+}
+
+/* lora.py:71-74, one adapter per row out of a bank of `slots` */
+int mi_lora_linear_slots(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
+                         int epilogue, const void* residual, const void* norm_w, float eps, const void* const A[3],
+                         const void* const B[3], int rank, float scaling, int slots, const int32_t* row_slot, void* scratch,
+                         size_t scratch_bytes, mi_stream_t stream) {
+  return lora_linear_leaf("mi_lora_linear_slots", out, ldo, x, ldx, M, K, w, n_rows, epilogue, residual, norm_w, eps, A, B, rank,
+                          scaling, slots, row_slot, scratch, scratch_bytes, stream);
 }
 
 namespace {
@@ -977,10 +1008,16 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
     static const mi_lora_layer_t kNoAdapters = {};
     const mi_lora_layer_t& A = (lora && L.lora) ? *L.lora : kNoAdapters;
     const float ls = m->lora_scaling;
+    // adapter banks (ABI v9): the pointers of `A` are bank bases and bt->seq_adapter picks a slot per sequence; without it
+    // every row runs through slot 0 on the single-adapter kernels
+    auto banked = [&](LoraLinear ll) {
+      ll.slots = m->lora_slots > 1 ? m->lora_slots : 1; ll.tok_seq = bt->tok_seq; ll.seq_slot = bt->seq_adapter;
+      return ll;
+    };
     if (lora) {
       if (!L.w1 || !L.w2 || !L.w3) return fail(MI_ERR_ARG, "mi_forward: dense layer without w1/w2/w3");
       MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, L.attention_norm, T, D, m->norm_eps, s), "attention_norm"));
-      const LoraLinear qkv = {{L.wq, L.wk, L.wv}, {A.wq_a, A.wk_a, A.wv_a}, {A.wq_b, A.wk_b, A.wv_b}, {nq, nkv, nkv}, 3, MI_EPI_STORE};
+      const LoraLinear qkv = banked({{L.wq, L.wk, L.wv}, {A.wq_a, A.wk_a, A.wv_a}, {A.wq_b, A.wk_b, A.wv_b}, {nq, nkv, nkv}, 3, MI_EPI_STORE});
       MI_TRY(lora_linear(ws.qkv, qkv_cols, gemv ? (const void*)h : ws.xn, D, ws.xn, D, T, D, qkv, nullptr, gemv ? L.attention_norm : nullptr,
                          m->norm_eps, m->lora_rank, ls, ws.lora_base, gemv, ws.lora_t, s));
       MI_TRY(hip_rc(launch_rope(ws.qkv, qkv_cols, T, H, Hkv, Dh, m->rope_cs, bt->tok_pos, s), "rope"));
@@ -1021,7 +1058,7 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
 
     // ---- h = h + attn @ Wo^T
     if (lora) {
-      const LoraLinear wo = {{L.wo, nullptr, nullptr}, {A.wo_a, nullptr, nullptr}, {A.wo_b, nullptr, nullptr}, {D, 0, 0}, 1, MI_EPI_RESIDUAL};
+      const LoraLinear wo = banked({{L.wo, nullptr, nullptr}, {A.wo_a, nullptr, nullptr}, {A.wo_b, nullptr, nullptr}, {D, 0, 0}, 1, MI_EPI_RESIDUAL});
       MI_TRY(lora_linear(h, D, ws.attn, nq, ws.attn, nq, T, nq, wo, h, nullptr, 0.f, m->lora_rank, ls, ws.xn, false, ws.lora_t, s));
     } else if (gemv)
       MI_TRY(gemv_passes(kGemvBf16, gemv_residual(ws.attn, nq, L.wo, h, D), T, s, "wo gemv"));
@@ -1031,10 +1068,10 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
     // ---- h = h + FFN(ffn_norm(h))
     if (lora) {
       MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, L.ffn_norm, T, D, m->norm_eps, s), "ffn_norm"));
-      const LoraLinear w13 = {{L.w1, L.w3, nullptr}, {A.w1_a, A.w3_a, nullptr}, {A.w1_b, A.w3_b, nullptr}, {F, F, 0}, 2, MI_EPI_SWIGLU};
+      const LoraLinear w13 = banked({{L.w1, L.w3, nullptr}, {A.w1_a, A.w3_a, nullptr}, {A.w1_b, A.w3_b, nullptr}, {F, F, 0}, 2, MI_EPI_SWIGLU});
       MI_TRY(lora_linear(ws.hid, F, gemv ? (const void*)h : ws.xn, D, ws.xn, D, T, D, w13, nullptr, gemv ? L.ffn_norm : nullptr, m->norm_eps,
                          m->lora_rank, ls, ws.lora_base, gemv, ws.lora_t, s));
-      const LoraLinear w2 = {{L.w2, nullptr, nullptr}, {A.w2_a, nullptr, nullptr}, {A.w2_b, nullptr, nullptr}, {D, 0, 0}, 1, MI_EPI_RESIDUAL};
+      const LoraLinear w2 = banked({{L.w2, nullptr, nullptr}, {A.w2_a, nullptr, nullptr}, {A.w2_b, nullptr, nullptr}, {D, 0, 0}, 1, MI_EPI_RESIDUAL});
       MI_TRY(lora_linear(h, D, ws.hid, F, ws.hid, F, T, F, w2, h, nullptr, 0.f, m->lora_rank, ls, ws.xn, false, ws.lora_t, s));
     } else if (m->num_experts == 0) {
       if (gemv) {

@@ -185,16 +185,198 @@ __global__ __launch_bounds__(256) void lora_up_kernel(LoraUpArgs a) {
   }
 }
 
-template <int EPI>
+// ---------------------------------------------------------------------------------------------- adapter banks (ABI v9)
+// One adapter per sequence: the slot of row m.  The address is wave-uniform wherever it is used as a scalar (a token, a row of
+// lora_up's walk).  -1: no adapter; anything else is clamped into the bank (the host has refused values outside it).
+__device__ __forceinline__ int slot_of_row(const int32_t* tok_seq, const int32_t* seq_slot, int m, int slots) {
+  const int b = tok_seq ? tok_seq[m] : m;
+  const int sl = seq_slot[b];
+  return sl < 0 ? -1 : min(sl, slots - 1);
+}
+
+// ---- lora_down, T <= 8, banks: one wave per (row of the stacked A, token); the loop of lora_down_rows_kernel<1> on the row of
+// the token's slot.  A slot's rows are read by every token on it: the repeats are L2 hits.
+__global__ __launch_bounds__(256) void lora_down_slot_rows_kernel(LoraDownArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int tok = blockIdx.y;
+  const int R = a.nseg * a.r;
+  if (row >= R) return;
+  const int seg = row / a.r;
+  const bf16_t* A = seg == 0 ? a.A[0] : (seg == 1 ? a.A[1] : a.A[2]);
+  if (A == nullptr) return;  // (wave-uniform) no adapter on this segment
+  const int slot = __builtin_amdgcn_readfirstlane(slot_of_row(a.tok_seq, a.seq_slot, tok, a.slots));
+  if (slot < 0) return;      // (wave-uniform) no adapter on this token
+  const bf16_t* arow = A + (size_t)slot * (size_t)a.a_stride + (size_t)(row - seg * a.r) * a.K;
+  const bf16_t* xrow = a.x + (size_t)tok * a.ldx;
+  const int np = a.K >> 3;
+  constexpr int U = 4;
+  float acc = 0.f;
+  for (int p0 = lane; p0 < np + lane; p0 += 64 * U) {
+    u32x4 w[U];
+    int pc[U];
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      pc[j] = min(p0 + 64 * j, np - 1);
+      w[j] = ld16_nt(arow + (size_t)pc[j] * 8);
+    }
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      const bool live = p0 + 64 * j < np;
+      const u32x4 xv = ld16(xrow + (size_t)pc[j] * 8);
+      const float s = dot8(w[j], xv, 0.f);
+      acc += live ? s : 0.f;
+    }
+  }
+  const float s = wave_sum(acc);
+  if (lane == 0) a.t[(size_t)tok * R + row] = f_to_bf(s);
+}
+
+// ---- lora_down, T > 8, banks: lora_down_mfma_kernel's tile, once per distinct slot among the wave's 16 rows.  The slot of the
+// first row still pending is taken wave-uniformly, the K loop runs against that slot's A rows, the rows on that slot are stored
+// and leave the pending set.  Rows of an MFMA do not interact: a row's value is that of a batch that is all on its slot.
+__global__ __launch_bounds__(256) void lora_down_slot_mfma_kernel(LoraDownArgs a) {
+  const int lane = threadIdx.x & 63, wid = (int)threadIdx.x >> 6;
+  const int m0 = (blockIdx.x * 4 + wid) * 16;
+  if (m0 >= a.T) return;
+  const int R = a.nseg * a.r;
+  const int c0 = blockIdx.y * 64;
+  const int fr = lane & 15, fq = lane >> 4;
+  const bf16_t* xrow = a.x + (size_t)min(m0 + fr, a.T - 1) * a.ldx;
+  const int rs = m0 + fr < a.T ? slot_of_row(a.tok_seq, a.seq_slot, m0 + fr, a.slots) : -1;  // row m0 + (lane & 15)
+  int os[4];                                                                               // rows m0 + fq * 4 + j: this lane's outputs
+#pragma unroll
+  for (int j = 0; j < 4; ++j) os[j] = slot_of_row(a.tok_seq, a.seq_slot, min(m0 + fq * 4 + j, a.T - 1), a.slots);
+  const bf16_t* brow[4];
+  bool has[4], bank[4];
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) {
+    const int n = min(c0 + ct * 16 + fr, R - 1);
+    const int seg = n / a.r;
+    const bf16_t* A = seg == 0 ? a.A[0] : (seg == 1 ? a.A[1] : a.A[2]);
+    bank[ct] = A != nullptr;
+    has[ct] = bank[ct] && c0 + ct * 16 + fr < R;
+    brow[ct] = A ? A + (size_t)(n - seg * a.r) * a.K : a.x;  // (a segment without adapter: any readable line, never stored)
+  }
+  const u32x4 z = {0u, 0u, 0u, 0u};
+  unsigned long long pending = __ballot(rs >= 0);
+  while (pending != 0ull) {  // (wave-uniform; every pass retires at least the row it took its slot from)
+    const int first = __builtin_ctzll(pending);
+    const int cur = __builtin_amdgcn_readlane(rs, first);
+    const size_t so = (size_t)cur * (size_t)a.a_stride;
+    f32x4 acc[4];
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < a.K; k0 += 32) {
+      const int k = k0 + fq * 8;
+      const bool live = k < a.K;  // K is a multiple of 8, not necessarily of 32
+      const int kc = live ? k : 0;
+      u32x4 xa = ld16(xrow + kc);
+      u32x4 b[4];
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) b[ct] = ld16(brow[ct] + (bank[ct] ? so : (size_t)0) + kc);
+      xa = live ? xa : z;
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) {
+        const u32x4 bv = live ? b[ct] : z;
+        acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, xa), __builtin_bit_cast(bf16x8, bv), acc[ct], 0, 0, 0);
+      }
+    }
+    // acc[ct][j]: row m0 + fq * 4 + j, column c0 + ct * 16 + fr
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+      if (!has[ct]) continue;
+      const int n = c0 + ct * 16 + fr;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int m = m0 + fq * 4 + j;
+        if (m < a.T && os[j] == cur) a.t[(size_t)m * R + n] = f_to_bf(acc[ct][j]);
+      }
+    }
+    pending &= ~__ballot(rs == cur);
+  }
+}
+
+// ---- lora_up, banks: lora_up_kernel with the thread's row(s) of B reloaded when the slot of the row it walks to differs from
+// the previous row's (the slot of a row is the same for the whole block).  Slot -1: d = 0, y = bf16(base + 0); t is not read.
+template <int EPI, bool F32, bool FAST>
+__global__ __launch_bounds__(256) void lora_up_slot_kernel(LoraUpArgs a) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= a.N) return;
+  const int m0 = blockIdx.y * LORA_UP_ROWS;
+  const int m1 = min(m0 + LORA_UP_ROWS, a.T);
+  const int rp = a.r >> 3;
+  const int ldt = a.nseg * a.r;
+  const bf16_t* dummy = a.t;  // a readable line for the segments without adapter
+  int loaded = -1;            // the slot the B registers hold
+  if constexpr (EPI == MI_EPI_SWIGLU) {
+    const bool h1 = a.B[0] != nullptr, h3 = a.B[1] != nullptr;
+    BRow b1 = {}, b3 = {};
+    for (int m = m0; m < m1; ++m) {
+      const int slot = __builtin_amdgcn_readfirstlane(slot_of_row(a.tok_seq, a.seq_slot, m, a.slots));
+      if (slot >= 0 && slot != loaded) {
+        b1 = load_brow(h1 ? a.B[0] + (size_t)slot * (size_t)a.b_stride[0] + (size_t)n * a.r : dummy, rp);
+        b3 = load_brow(h3 ? a.B[1] + (size_t)slot * (size_t)a.b_stride[1] + (size_t)n * a.r : dummy, rp);
+        loaded = slot;
+      }
+      float d1 = 0.f, d3 = 0.f;
+      if (slot >= 0) {
+        const bf16_t* trow = a.t + (size_t)m * ldt;
+        d1 = h1 ? lora_delta(b1, trow, rp, a.scaling) : 0.f;
+        d3 = h3 ? lora_delta(b3, trow + a.r, rp, a.scaling) : 0.f;
+      }
+      const float y1 = bf_round(base_at<F32>(a.base, (size_t)m * a.ldb + n) + d1);
+      const float y3 = bf_round(base_at<F32>(a.base, (size_t)m * a.ldb + a.N + n) + d3);
+      a.out[(size_t)m * a.ldo + n] = f_to_bf(FAST ? swiglu_bf_fast(y1, y3) : swiglu_bf(y1, y3));
+    }
+  } else {
+    const int seg = n < a.n0 ? 0 : (n < a.n1 ? 1 : 2);
+    const int start = seg == 0 ? 0 : (seg == 1 ? a.n0 : a.n1);
+    const bf16_t* B = seg == 0 ? a.B[0] : (seg == 1 ? a.B[1] : a.B[2]);
+    const size_t stride = (size_t)(seg == 0 ? a.b_stride[0] : (seg == 1 ? a.b_stride[1] : a.b_stride[2]));
+    const bool has = B != nullptr;
+    BRow b = {};
+    for (int m = m0; m < m1; ++m) {
+      const int slot = __builtin_amdgcn_readfirstlane(slot_of_row(a.tok_seq, a.seq_slot, m, a.slots));
+      if (slot >= 0 && slot != loaded) {
+        b = load_brow(has ? B + (size_t)slot * stride + (size_t)(n - start) * a.r : dummy, rp);
+        loaded = slot;
+      }
+      float d = 0.f;
+      if (slot >= 0 && has) d = lora_delta(b, a.t + (size_t)m * ldt + seg * a.r, rp, a.scaling);
+      const float y = bf_round(base_at<F32>(a.base, (size_t)m * a.ldb + n) + d);
+      if constexpr (EPI == MI_EPI_RESIDUAL)
+        a.out[(size_t)m * a.ldo + n] = f_to_bf(bf_to_f(a.residual[(size_t)m * a.ldo + n]) + y);
+      else
+        a.out[(size_t)m * a.ldo + n] = f_to_bf(y);
+    }
+  }
+}
+
+template <int EPI, bool SLOTS, bool F32, bool FAST>
+void launch_up_one(const LoraUpArgs& a, dim3 grid, hipStream_t s) {
+  if constexpr (SLOTS) hipLaunchKernelGGL((lora_up_slot_kernel<EPI, F32, FAST>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((lora_up_kernel<EPI, F32, FAST>), grid, dim3(256), 0, s, a);
+}
+template <int EPI, bool SLOTS>
 hipError_t launch_up_epi(const LoraUpArgs& a, dim3 grid, hipStream_t s) {
   if (a.base_f32) {
-    if (a.fast_silu) hipLaunchKernelGGL((lora_up_kernel<EPI, true, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((lora_up_kernel<EPI, true, false>), grid, dim3(256), 0, s, a);
+    if (a.fast_silu) launch_up_one<EPI, SLOTS, true, true>(a, grid, s);
+    else launch_up_one<EPI, SLOTS, true, false>(a, grid, s);
   } else {
-    if (a.fast_silu) hipLaunchKernelGGL((lora_up_kernel<EPI, false, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((lora_up_kernel<EPI, false, false>), grid, dim3(256), 0, s, a);
+    if (a.fast_silu) launch_up_one<EPI, SLOTS, false, true>(a, grid, s);
+    else launch_up_one<EPI, SLOTS, false, false>(a, grid, s);
   }
   return hipGetLastError();
+}
+template <bool SLOTS>
+hipError_t launch_up(const LoraUpArgs& a, dim3 grid, hipStream_t s) {
+  switch (a.epi) {
+    case MI_EPI_STORE: return launch_up_epi<MI_EPI_STORE, SLOTS>(a, grid, s);
+    case MI_EPI_RESIDUAL: return launch_up_epi<MI_EPI_RESIDUAL, SLOTS>(a, grid, s);
+    case MI_EPI_SWIGLU: return launch_up_epi<MI_EPI_SWIGLU, SLOTS>(a, grid, s);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 }  // namespace
@@ -202,6 +384,14 @@ hipError_t launch_up_epi(const LoraUpArgs& a, dim3 grid, hipStream_t s) {
 hipError_t launch_lora_down(const LoraDownArgs& a, hipStream_t s) {
   if (a.T <= 0 || a.K <= 0 || a.K % 8 || a.ldx % 8 || a.nseg < 1 || a.nseg > 3 || a.r < 8 || a.r > 64 || a.r % 8) return hipErrorInvalidValue;
   const int R = a.nseg * a.r;
+  if (a.seq_slot != nullptr) {  // adapter banks: one slot per sequence
+    if (a.slots < 1 || a.a_stride < (int64_t)a.r * a.K) return hipErrorInvalidValue;
+    if (a.T > GEMV_MAX_T)
+      hipLaunchKernelGGL(lora_down_slot_mfma_kernel, dim3((unsigned)((a.T + 63) / 64), (unsigned)((R + 63) / 64)), dim3(256), 0, s, a);
+    else
+      hipLaunchKernelGGL(lora_down_slot_rows_kernel, dim3((unsigned)((R + 3) / 4), (unsigned)a.T), dim3(256), 0, s, a);
+    return hipGetLastError();
+  }
   if (a.T > GEMV_MAX_T) {
     hipLaunchKernelGGL(lora_down_mfma_kernel, dim3((unsigned)((a.T + 63) / 64), (unsigned)((R + 63) / 64)), dim3(256), 0, s, a);
     return hipGetLastError();
@@ -220,10 +410,9 @@ hipError_t launch_lora_down(const LoraDownArgs& a, hipStream_t s) {
 hipError_t launch_lora_up(const LoraUpArgs& a, hipStream_t s) {
   if (a.T <= 0 || a.N <= 0 || a.nseg < 1 || a.nseg > 3 || a.r < 8 || a.r > 64 || a.r % 8) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((a.N + 255) / 256), (unsigned)((a.T + LORA_UP_ROWS - 1) / LORA_UP_ROWS));
-  switch (a.epi) {
-    case MI_EPI_STORE: return launch_up_epi<MI_EPI_STORE>(a, grid, s);
-    case MI_EPI_RESIDUAL: return launch_up_epi<MI_EPI_RESIDUAL>(a, grid, s);
-    case MI_EPI_SWIGLU: return launch_up_epi<MI_EPI_SWIGLU>(a, grid, s);
-    default: return hipErrorInvalidValue;
+  if (a.seq_slot != nullptr) {
+    if (a.slots < 1) return hipErrorInvalidValue;
+    return launch_up<true>(a, grid, s);
   }
+  return launch_up<false>(a, grid, s);
 }

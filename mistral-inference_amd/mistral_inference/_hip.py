@@ -21,7 +21,7 @@ def _default_lib() -> str:
 
 LIB_PATH = os.environ.get("MISTRAL_HIP_LIB", _default_lib())
 
-MI_ABI_VERSION = 8
+MI_ABI_VERSION = 9
 EPI_STORE, EPI_RESIDUAL, EPI_SWIGLU, EPI_LOGITS = 0, 1, 2, 3
 BRANCH_NOCACHE, BRANCH_PREFILL, BRANCH_DECODE = 0, 1, 2
 GEMV_MAX_T = 8
@@ -50,6 +50,7 @@ class MiModel(C.Structure):
         ("tok_embeddings", _vp), ("final_norm", _vp), ("output", _vp), ("rope_cs", _vp), ("rope_len", C.c_int32),
         ("layers", C.POINTER(MiLayer)),
         ("lora_rank", C.c_int32), ("lora_scaling", C.c_float),  # ABI v8: un-merged LoRA (0: none)
+        ("lora_slots", C.c_int32),  # ABI v9: adapter sets per LoRA linear (0 / 1: one; > 1: every adapter pointer is a bank base)
     ]
 
 
@@ -63,6 +64,7 @@ class MiBatch(C.Structure):
         ("greedy_token", _vp), ("greedy_logprob", _vp), ("hist_token", _vp), ("hist_logprob", _vp), ("hist_len", C.c_int32),
         ("sample_temperature", C.c_float), ("sample_top_p", C.c_float), ("sample_seed", C.c_uint64), ("sample_offset", C.c_uint64),  # ABI v5
         ("kv_layout", C.c_int32),  # ABI v7: KV_SLOT_MAJOR / KV_HEAD_MAJOR, the layout of every ring in cache_k / cache_v
+        ("seq_adapter", _vp),  # ABI v9: dev int32 [B], adapter slot per sequence (-1: none); None: slot 0 on the ABI v8 launches
     ]
 
 
@@ -81,6 +83,9 @@ _SIGS = {
     "mi_lora_linear_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int]),  # ABI v8
     "mi_lora_linear": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp), C.POINTER(C.c_int), C.c_int,
                                  _vp, _vp, C.c_float, C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.c_float, _vp, C.c_size_t, _vp]),
+    "mi_lora_linear_slots": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp), C.POINTER(C.c_int), C.c_int,
+                                       _vp, _vp, C.c_float, C.POINTER(_vp), C.POINTER(_vp), C.c_int, C.c_float, C.c_int, _vp, _vp,
+                                       C.c_size_t, _vp]),  # ABI v9
     "mi_attn_decode_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "mi_attn_decode": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),
     "mi_attn_prefill": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp,
@@ -250,19 +255,29 @@ def linear(x: torch.Tensor, weights: Sequence[torch.Tensor], epilogue: int = EPI
 def lora_linear(x: torch.Tensor, weights: Sequence[torch.Tensor], lora_a: Sequence[Optional[torch.Tensor]],
                 lora_b: Sequence[Optional[torch.Tensor]], scaling: float, epilogue: int = EPI_STORE,
                 residual: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0,
-                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                out: Optional[torch.Tensor] = None, row_slot: Optional[torch.Tensor] = None, banked: bool = False) -> torch.Tensor:
     """`linear` with un-merged LoRA adapters (reference lora.py:71-74): segment i adds bf16(bf16(B_i bf16(A_i x)) * scaling) to
-    bf16(W_i x) before the epilogue.  lora_a[i] [rank, K] / lora_b[i] [n_rows_i, rank]; a None pair: no adapter."""
+    bf16(W_i x) before the epilogue.  lora_a[i] [rank, K] / lora_b[i] [n_rows_i, rank]; a None pair: no adapter.
+    banked (mi_lora_linear_slots): lora_a[i] [slots, rank, K] / lora_b[i] [slots, n_rows_i, rank] and row m runs through slot
+    row_slot[m] (int32 [M] on the device, -1: no adapter); row_slot None: slot 0."""
     assert 1 <= len(weights) <= 3 and len(lora_a) == len(lora_b) == len(weights) and x.dim() == 2
+    slots = 1
+    if banked:
+        slots = next((a.shape[0] for a in lora_a if a is not None), 1)
+        assert all(a is None or (a.dim() == 3 and a.shape[0] == slots) for a in lora_a)
+        assert all(b is None or (b.dim() == 3 and b.shape[0] == slots) for b in lora_b)
+        assert row_slot is None or (row_slot.dtype == torch.int32 and tuple(row_slot.shape) == (x.shape[0],))
+    else:
+        assert row_slot is None, "row_slot needs banked adapters"
     if x.dtype != torch.bfloat16:
         raise NotImplementedError("un-merged LoRA with fp16 / fp32 storage is not implemented (bf16 models only)")
     M, K = x.shape
     n_rows = [w.shape[0] for w in weights]
-    rank = next((a.shape[0] for a in lora_a if a is not None), 8)
+    rank = next((a.shape[-2] for a in lora_a if a is not None), 8)
     for w, a, b in zip(weights, lora_a, lora_b):
         assert w.shape[1] == K and w.is_contiguous() and (a is None) == (b is None)
         if a is not None:
-            assert tuple(a.shape) == (rank, K) and tuple(b.shape) == (w.shape[0], rank) and a.is_contiguous() and b.is_contiguous()
+            assert tuple(a.shape[-2:]) == (rank, K) and tuple(b.shape[-2:]) == (w.shape[0], rank) and a.is_contiguous() and b.is_contiguous()
     N = n_rows[0] if epilogue == EPI_SWIGLU else sum(n_rows)
     if out is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
@@ -276,6 +291,11 @@ def lora_linear(x: torch.Tensor, weights: Sequence[torch.Tensor], lora_a: Sequen
     if need == 0:  # a shape the entry refuses: let it say why
         need = 256
     scratch = torch.empty(need, dtype=torch.uint8, device=x.device)  # per call, from the caching allocator (as lm_head_logprobs)
+    if banked:
+        check(L.mi_lora_linear_slots(dev_ptr(out), out.stride(0), dev_ptr(x), x.stride(0), M, K, wp, nr, epilogue, dev_ptr(residual),
+                                     dev_ptr(norm_w), float(eps), ap, bp, rank, float(scaling), slots, dev_ptr(row_slot, torch.int32),
+                                     scratch.data_ptr(), scratch.numel(), stream_ptr(x.device)), "mi_lora_linear_slots")
+        return out
     check(L.mi_lora_linear(dev_ptr(out), out.stride(0), dev_ptr(x), x.stride(0), M, K, wp, nr, epilogue, dev_ptr(residual),
                            dev_ptr(norm_w), float(eps), ap, bp, rank, float(scaling), scratch.data_ptr(), scratch.numel(),
                            stream_ptr(x.device)), "mi_lora_linear")

@@ -12,6 +12,7 @@ the end, and a decode step is a single native call with no host metadata; the on
 is the EOS test, and only when `eos_id` is given.
 """
 import contextlib
+import functools
 from typing import List, Optional, Tuple
 
 import torch
@@ -20,6 +21,20 @@ from .cache import BufferCache
 from .transformer import Transformer
 
 
+def _unpins_adapters(fn):
+    """generate() pins its per-sequence adapter slots on the model (`adapters=`) for the length of the call: whatever way the
+    call ends, forward() decides them per call again afterwards."""
+    @functools.wraps(fn)
+    def wrapper(encoded_prompts, model, *args, **kwargs):
+        try:
+            return fn(encoded_prompts, model, *args, **kwargs)
+        finally:
+            if hasattr(model, "unpin_adapters"):
+                model.unpin_adapters()
+    return wrapper
+
+
+@_unpins_adapters
 @torch.inference_mode()
 def generate(
     encoded_prompts: List[List[int]],
@@ -30,7 +45,15 @@ def generate(
     temperature: float,
     chunk_size: Optional[int] = None,
     eos_id: Optional[int] = None,
+    adapters: Optional[List[int]] = None,
 ) -> Tuple[List[List[int]], List[List[float]]]:
+    # adapters (a model built with `lora`, Transformer.set_lora_slots): one adapter slot per prompt, -1 = the base model; written
+    # to the device ONCE here, before the first prefill chunk - every forward, prompt_logprobs call and the decode session below
+    # run with it.  None: slot 0 for every sequence.
+    if hasattr(model, "pin_adapters"):
+        model.pin_adapters(adapters, len(encoded_prompts))
+    elif adapters is not None:
+        raise ValueError("adapters=...: this model runs one adapter set")
     images_torch: List[List[torch.Tensor]] = []
     if images:  # reference generate.py:54-60: one list of [C, H, W] arrays per sample; no chunking with images
         assert chunk_size is None

@@ -6,7 +6,13 @@ reference's names - and its `forward` is one `mi_lora_linear` call (csrc/lora.hi
     t = bf16(A x);  d = bf16(bf16(B t) * scaling);  y = bf16(bf16(W x) + d)
 
 A model built with `params.json` `lora` runs these through `mi_forward`; `Transformer.load_lora` then copies adapters into
-the existing tensors, so one set of base weights serves any number of fine-tunes.  bf16 dense models only."""
+the existing tensors, so one set of base weights serves any number of fine-tunes.  bf16 dense models only.
+
+Adapter banks (`Transformer.set_lora_slots`): a layer then owns `n` adapter sets in two contiguous tensors [n, rank, in] /
+[n, out, rank]; `lora_A.weight` / `lora_B.weight` are views of slot 0, and `forward(..., adapters=[...])` picks a slot per
+sequence inside one batch (csrc/lora.hip, the slot kernels)."""
+from typing import Optional
+
 import torch
 from torch import nn
 
@@ -37,6 +43,51 @@ class LoRALinear(nn.Module):
         self.linear = nn.Linear(in_features, out_features, bias=False)
 
         self.register_load_state_dict_post_hook(_forgive_absent_adapters)
+        # adapter bank (set_slots): [n, rank, in] / [n, out, rank]; None: one slot, the two parameters above own their storage
+        self.bank_A: Optional[torch.Tensor] = None
+        self.bank_B: Optional[torch.Tensor] = None
+
+    @property
+    def slots(self) -> int:
+        return 1 if self.bank_A is None else int(self.bank_A.shape[0])
+
+    @torch.no_grad()
+    def set_slots(self, n: int) -> None:
+        """A bank of `n` adapter sets: slot 0 carries the current adapters, the others are zero (the base model).  `lora_A.weight`
+        / `lora_B.weight` stay parameters of the same names and shapes - views of slot 0 - so state_dict(), load_state_dict(),
+        copies into them and `forward` (slot 0) behave as without a bank.  The frozen weight is not touched.  Called again
+        (to grow or shrink the bank), the slots that both banks have keep their adapters; the tensors are new ones."""
+        if n < 1:
+            raise ValueError(f"set_slots({n}): a bank has at least one slot")
+        a, b = self.lora_A.weight, self.lora_B.weight
+        bank_a = torch.zeros((n, *a.shape), dtype=a.dtype, device=a.device)
+        bank_b = torch.zeros((n, *b.shape), dtype=b.dtype, device=b.device)
+        if self.bank_A is not None and self.bank_B is not None and self.bank_is_bound():
+            keep = min(n, self.slots)
+            bank_a[:keep].copy_(self.bank_A[:keep])
+            bank_b[:keep].copy_(self.bank_B[:keep])
+        bank_a[0].copy_(a)   # (slot 0 is whatever the two parameters hold now, bound to the old bank or not)
+        bank_b[0].copy_(b)
+        self.bank_A, self.bank_B = bank_a, bank_b
+        self._bind_slot0()
+
+    def _bind_slot0(self) -> None:
+        assert self.bank_A is not None and self.bank_B is not None
+        for lin, bank in ((self.lora_A, self.bank_A), (self.lora_B, self.bank_B)):
+            lin.weight = nn.Parameter(bank[0], requires_grad=lin.weight.requires_grad and bank.is_floating_point())
+
+    def bank_is_bound(self) -> bool:
+        """False after something REBOUND lora_A.weight / lora_B.weight (load_state_dict(assign=True)): slot 0 of the bank is then
+        stale and set_slots has to be called again."""
+        return self.bank_A is None or (self.lora_A.weight.data_ptr() == self.bank_A.data_ptr()
+                                       and self.lora_B.weight.data_ptr() == self.bank_B.data_ptr())
+
+    def _apply(self, fn, *a, **k):  # .to() / dtype casts: the bank moves as one tensor and the two parameters are re-viewed
+        out = super()._apply(fn, *a, **k)
+        if self.bank_A is not None:
+            self.bank_A, self.bank_B = fn(self.bank_A), fn(self.bank_B)
+            self._bind_slot0()
+        return out
 
     @property
     def weight(self) -> torch.Tensor:

@@ -91,6 +91,12 @@ class HipStackBackend:
         self._workspace: Optional[torch.Tensor] = None
         self.generic = False   # set by _build_plan: this model runs through mi_forward_generic
         self.dtype_code = 0
+        # ABI v9 - adapter slot per sequence: ONE persistent int32 [max_batch_size] device tensor, allocated once and never
+        # replaced (a GreedySession or a captured step holds its pointer and stays valid when later calls write other values
+        # into it).  `_seq_adapter_now` is what the next forward carries: None (NULL: slot 0, single-adapter kernels) or the
+        # persistent tensor.
+        self._seq_adapter: Optional[torch.Tensor] = None
+        self._seq_adapter_now: Optional[torch.Tensor] = None
 
     # -- one-time: pointer tables of the weights -------------------------------------------------
     def _build_plan(self, model: "Transformer"):
@@ -125,6 +131,10 @@ class HipStackBackend:
                 ff = blk.feed_forward
                 for name, mod in (("wq", at.wq), ("wk", at.wk), ("wv", at.wv), ("wo", at.wo), ("w1", ff.w1), ("w2", ff.w2), ("w3", ff.w3)):
                     assert isinstance(mod, LoRALinear) and mod.rank == a.lora.rank
+                    if mod.slots != model.lora_slots or not mod.bank_is_bound():
+                        raise RuntimeError(f"layer adapter {name}: its bank ({mod.slots} slots) does not match the model's "
+                                           f"({model.lora_slots}), or its parameters were rebound; call set_lora_slots again")
+                    # (with a bank, lora_A.weight / lora_B.weight are views of slot 0: their pointers ARE the bank bases)
                     setattr(adapters[j], name + "_a", p(mod.lora_A.weight))
                     setattr(adapters[j], name + "_b", p(mod.lora_B.weight))
                 L.lora = C.pointer(adapters[j])
@@ -158,7 +168,31 @@ class HipStackBackend:
         m.layers = C.cast(layers, C.POINTER(_hip.MiLayer))
         if a.lora is not None:
             m.lora_rank, m.lora_scaling = int(a.lora.rank), float(a.lora.scaling)
+            m.lora_slots = int(model.lora_slots)
         return m, keep
+
+    @property
+    def adapters_on(self) -> bool:
+        return self._seq_adapter_now is not None
+
+    def set_adapters(self, model: "Transformer", adapters: Optional[List[int]]) -> None:
+        """The adapter slot of every sequence for the forwards that follow (already validated): None = slot 0 for all on the
+        single-adapter kernels (`seq_adapter` NULL); a list is copied, stream-ordered, into the persistent device tensor.  A
+        GreedySession latches the choice when it is made (`seq_adapter_now`), so later calls here do not move it."""
+        if adapters is None:
+            self._seq_adapter_now = None
+            return
+        vals = torch.tensor(adapters, dtype=torch.int32)
+        with torch.inference_mode(False):  # (generate() runs in inference mode; a later plain forward() writes here too)
+            if self._seq_adapter is None or self._seq_adapter.device != model.device:
+                self._seq_adapter = torch.zeros(max(int(model.args.max_batch_size), 1), dtype=torch.int32, device=model.device)
+        # (no forward takes more sequences than max_batch_size, with or without a cache: the tensor never has to grow)
+        assert len(adapters) <= self._seq_adapter.numel(), f"Max batch size is {self._seq_adapter.numel()}, got {len(adapters)} adapters"
+        self._seq_adapter[:len(adapters)].copy_(vals)
+        self._seq_adapter_now = self._seq_adapter
+
+    def seq_adapter_now(self) -> Optional[torch.Tensor]:
+        return self._seq_adapter_now
 
     def plan(self, model: "Transformer"):
         if self._plan is None:
@@ -233,7 +267,8 @@ class HipStackBackend:
     # -- per forward -------------------------------------------------------------------------------
     def run_stack(self, model: "Transformer", h: torch.Tensor, input_ids: Optional[torch.Tensor],
                   meta: BatchMetadata, cache: Optional[BufferCache], logits: Optional[torch.Tensor],
-                  greedy: Optional["GreedyBuffers"] = None) -> None:
+                  greedy: Optional["GreedyBuffers"] = None, seq_adapter: Any = "now") -> None:
+        """seq_adapter: the [B] adapter-slot tensor this launch carries (None: NULL); "now": what set_adapters chose last."""
         m = self.plan(model)
         T, B = h.shape[0], len(meta.seqlens)
         bt = _hip.MiBatch()
@@ -260,6 +295,11 @@ class HipStackBackend:
             bt.sample_temperature, bt.sample_top_p = float(greedy.temperature), float(greedy.top_p)
             bt.sample_seed = int(greedy.seed) & (2 ** 64 - 1)
             bt.sample_offset = int(greedy.offset) & (2 ** 64 - 1)
+        if isinstance(seq_adapter, str):
+            seq_adapter = self._seq_adapter_now
+        if seq_adapter is not None:  # ABI v9: one adapter slot per sequence (meta.tok_seq names a row's sequence on every branch)
+            assert seq_adapter.numel() >= B
+            bt.seq_adapter = _hip.dev_ptr(seq_adapter, i32)
         wsb = self._get_workspace(model, m, T, B, max_w)
         bt.workspace, bt.workspace_bytes = wsb.data_ptr(), wsb.numel()
         if self.generic:
@@ -322,6 +362,8 @@ class Transformer(ModelBase):
         self.n_local_layers = len(self.layers)
         self._backend = backend if backend is not None else HipStackBackend()
         self._graphed: Optional[dict] = None  # state of an active graphed_decode() context
+        self.lora_slots = 1                   # adapter sets per LoRA linear (set_lora_slots)
+        self._adapters_pinned = False         # between pin_adapters() and unpin_adapters(): forward() leaves the slots alone
         self._pp_comm: Optional[Any] = None   # pipeline transport (distributed.pipeline_comm), created at first use
 
     # ---- properties ----------------------------------------------------------------------------
@@ -359,10 +401,13 @@ class Transformer(ModelBase):
         return self._pp_comm
 
     # ---- forward -------------------------------------------------------------------------------
-    def _nocache_metadata(self, seqlens: List[int]) -> BatchMetadata:
+    def _nocache_metadata(self, seqlens: List[int], per_sequence: bool = False) -> BatchMetadata:
+        """The cache=None call is ONE unmasked segment to the kernels; per_sequence (adapter slots in use): tok_seq still names
+        each row's own sequence, which only the LoRA slot kernels read on this branch."""
         T = sum(seqlens)
         pos = [i for s in seqlens for i in range(s)]
-        blob = torch.tensor([0, T] + [0] + [0] * T + pos, dtype=torch.int32).to(self.device)
+        seq = [b for b, s in enumerate(seqlens) for _ in range(s)] if per_sequence else [0] * T
+        blob = torch.tensor([0, T] + [0] + seq + pos, dtype=torch.int32).to(self.device)
         return BatchMetadata(_hip.BRANCH_NOCACHE, [T], T, blob[:2], blob[2:3], blob[3:3 + T], blob[3 + T:])
 
     def embed_vision_language_features(self, input_ids: torch.Tensor, images: List[torch.Tensor]) -> torch.Tensor:
@@ -403,7 +448,8 @@ class Transformer(ModelBase):
         assert sum(seqlens) == num_toks, (sum(seqlens), num_toks)
         if self.pipeline_rank == 0:
             _hip.check_ids_on_host(input_ids, self.vocab_size)  # device-resident ids: flagged by the embedding kernel
-        meta = cache.batch_metadata(seqlens) if cache is not None else self._nocache_metadata(seqlens)
+        meta = cache.batch_metadata(seqlens) if cache is not None else self._nocache_metadata(
+            seqlens, per_sequence=bool(getattr(self._backend, "adapters_on", False)))
         # the kernels index the rotary table by position without a bound check (the reference's gather would raise)
         top = max((p + s for p, s in zip(cache._seen, seqlens)), default=0) if cache is not None else max(seqlens)
         if top > ROPE_TABLE_LEN:
@@ -431,10 +477,58 @@ class Transformer(ModelBase):
             self.pp_comm.send(h, dst=self.pipeline_rank + 1)
         return h, logits
 
+    # ---- one LoRA adapter per sequence ------------------------------------------------------------------
+    def set_lora_slots(self, n: int) -> None:
+        """Gives every LoRALinear of this model (built with `args.lora`) a bank of `n` adapter sets: slot 0 carries the current
+        adapters, the others start at zero (called again: the slots that the old and the new bank share keep theirs).  `load_lora(..., slot=)` fills a slot, `forward(..., adapters=[...])` picks one per
+        sequence.  Parameter names and shapes do not change (`lora_A.weight` / `lora_B.weight` become views of slot 0), the base
+        weights neither move nor change; the native pointer table is rebuilt, so sessions made before the call are invalid."""
+        if self.args.lora is None:
+            raise ValueError("set_lora_slots: the model was built without `lora` (adapters are merged into its weights)")
+        if int(n) < 1:
+            raise ValueError(f"set_lora_slots({n}): a bank has at least one slot")
+        for mod in self.modules():
+            if isinstance(mod, LoRALinear):
+                mod.set_slots(int(n))
+        self.lora_slots = int(n)
+        self._weights_changed()
+
+    def _check_adapters(self, adapters: Optional[List[int]], n_seqs: int) -> None:
+        """forward(adapters=...): decided on the host, before any launch."""
+        if adapters is None:
+            return
+        if self.args.lora is None:
+            raise ValueError("adapters=...: the model was built without `lora` (its adapters are merged into the weights)")
+        assert len(adapters) == n_seqs, f"adapters has {len(adapters)} entries for {n_seqs} sequences"
+        bad = [a for a in adapters if not isinstance(a, int) or not -1 <= a < self.lora_slots]
+        if bad:
+            raise ValueError(f"adapter slot {bad[0]} is outside -1 .. {self.lora_slots - 1} (set_lora_slots({self.lora_slots}))")
+
+    def _set_adapters(self, adapters: Optional[List[int]], n_seqs: int) -> None:
+        self._check_adapters(adapters, n_seqs)
+        if self._adapters_pinned:
+            assert adapters is None, "adapters are fixed for the duration of this generate() call"
+            return
+        if hasattr(self._backend, "set_adapters"):
+            self._backend.set_adapters(self, adapters)
+        elif adapters is not None:
+            raise ValueError("adapters=...: this backend runs one adapter set")
+
+    def pin_adapters(self, adapters: Optional[List[int]], n_seqs: int) -> None:
+        """generate(): the per-sequence slots are written ONCE here; until unpin_adapters() the forwards, prompt_logprobs calls
+        and the decode session all run with them."""
+        self._adapters_pinned = False
+        self._set_adapters(adapters, n_seqs)
+        self._adapters_pinned = True
+
+    def unpin_adapters(self) -> None:
+        self._adapters_pinned = False
+
     def forward_partial(self, input_ids: torch.Tensor, seqlens: List[int], cache: Optional[BufferCache] = None,
-                        images: Optional[List[torch.Tensor]] = None) -> torch.Tensor:
+                        images: Optional[List[torch.Tensor]] = None, *, adapters: Optional[List[int]] = None) -> torch.Tensor:
         """Local forward pass (reference transformer.py:163-219): the activations of this stage's last layer,
-        RMS-normalised on the last stage."""
+        RMS-normalised on the last stage.  adapters: as `forward`."""
+        self._set_adapters(adapters, len(seqlens))
         h, _ = self._run(input_ids, seqlens, cache, want_logits=False, images=images)
         return h
 
@@ -491,6 +585,7 @@ class Transformer(ModelBase):
                 return self._logits(input_ids, seqlens, cache)
             st["ids"] = input_ids.to(device=self.device, dtype=torch.long).clone()
             st["B"] = len(seqlens)
+            st["adapters_on"] = bool(getattr(self._backend, "adapters_on", False))  # (the captured step holds the pointer or NULL)
             torch.cuda.synchronize(self.device)
             graph = torch.cuda.CUDAGraph()
             seen = list(cache._seen)
@@ -524,12 +619,18 @@ class Transformer(ModelBase):
         return st["out"]
 
     def forward(self, input_ids: torch.Tensor, seqlens: List[int], cache: Optional[BufferCache] = None,
-                images: Optional[List[torch.Tensor]] = None) -> torch.Tensor:
-        """Logits [T, vocab] (reference transformer.py:221-242): fp32 unless softmax_fp32=False."""
+                images: Optional[List[torch.Tensor]] = None, *, adapters: Optional[List[int]] = None) -> torch.Tensor:
+        """Logits [T, vocab] (reference transformer.py:221-242): fp32 unless softmax_fp32=False.
+
+        adapters (a model built with `args.lora`): one adapter slot per sequence, -1 = the base model for that sequence; the rows
+        of sequence b are those of a model with the adapters of slot adapters[b] loaded (lora.py:71-74 per row).  None: slot 0
+        for every sequence.  Under pipeline parallelism every rank passes the same list, like the prompts."""
+        self._set_adapters(adapters, len(seqlens))
         st = self._graphed
+        on = bool(getattr(self._backend, "adapters_on", False))
         if (st is not None and cache is st["cache"] and cache._seen is not None and cache._seen[0] > 0
                 and all(s == 1 for s in seqlens) and len(seqlens) == len(cache._seen)
-                and (st["graph"] is None or len(seqlens) == st["B"])):
+                and (st["graph"] is None or (len(seqlens) == st["B"] and st.get("adapters_on", False) == on))):
             return self._graphed_step(input_ids, seqlens, cache, st)
         return self._logits(input_ids, seqlens, cache, images)
 
@@ -604,16 +705,26 @@ class Transformer(ModelBase):
 
     # ---- LoRA (reference lora.py:92-155).  A model without `args.lora`: adapters are MERGED into the frozen weights at load
     # time.  A model built with `args.lora`: they are copied into its LoRALinear layers and can be swapped at any time.
-    def load_lora(self, lora_path: Union[Path, str], scaling: float = 2.0) -> None:
+    def load_lora(self, lora_path: Union[Path, str], scaling: float = 2.0, slot: int = 0) -> None:
         """Loads a LoRA checkpoint (safetensors with `<linear>.lora_A.weight` / `.lora_B.weight` keys).  Without `args.lora`
         it is folded into the weights: W <- W + (B @ A) * scaling, every nn.Linear of this rank's layers except `output`.
         With `args.lora` the adapters replace the current ones in place (`scaling` is then `args.lora.scaling`, as in the
-        reference, lora.py:140-155); the base weights are not touched, so a second call swaps the fine-tune."""
+        reference, lora.py:140-155); the base weights are not touched, so a second call swaps the fine-tune.
+        slot: which adapter set of the bank (set_lora_slots) is replaced; the other slots keep serving."""
+        self._check_slot(slot)
         lora_path = Path(lora_path)
         assert lora_path.is_file(), f"{lora_path} does not exist or is not a file"
-        self._load_lora_state_dict(safetensors.torch.load_file(str(lora_path)), scaling=scaling)
+        self._load_lora_state_dict(safetensors.torch.load_file(str(lora_path)), scaling=scaling, slot=slot)
 
-    def _load_lora_state_dict(self, lora_state_dict: Mapping[str, torch.Tensor], scaling: float = 2.0) -> None:
+    def _check_slot(self, slot: int) -> None:
+        if self.args.lora is None:
+            if slot != 0:
+                raise ValueError(f"load_lora(slot={slot}): a model without `lora` merges the adapter into its weights; it has no slots")
+        elif not 0 <= slot < self.lora_slots:
+            raise ValueError(f"load_lora(slot={slot}): the bank has slots 0 .. {self.lora_slots - 1} (set_lora_slots)")
+
+    def _load_lora_state_dict(self, lora_state_dict: Mapping[str, torch.Tensor], scaling: float = 2.0, slot: int = 0) -> None:
+        self._check_slot(slot)
         lora_dtypes = set(p.dtype for p in lora_state_dict.values())
         assert len(lora_dtypes) == 1, (
             f"LoRA weights have multiple different dtypes {lora_dtypes}. All weights need to have the same dtype")
@@ -621,7 +732,7 @@ class Transformer(ModelBase):
         assert lora_dtype == self.dtype, f"LoRA weights dtype differs from model's dtype {lora_dtype} != {self.dtype}"
         assert all("lora" in key for key in lora_state_dict.keys())
         if self.args.lora is not None:
-            return self._assign_lora(lora_state_dict)
+            return self._assign_lora(lora_state_dict, slot)
         if self.dtype != torch.bfloat16 or self.device.type != "cuda":
             raise RuntimeError("load_lora: the merge runs on the GPU in bf16 (model must be on the device)")
         logging.info("Loading and merging LoRA weights...")
@@ -645,10 +756,11 @@ class Transformer(ModelBase):
         if hasattr(self._backend, "invalidate"):
             self._backend.invalidate()
 
-    def _assign_lora(self, lora_state_dict: Mapping[str, torch.Tensor]) -> None:
+    def _assign_lora(self, lora_state_dict: Mapping[str, torch.Tensor], slot: int = 0) -> None:
         """lora.py:140-155 on a model built with `args.lora`: every adapter key of this rank's layers is copied INTO the existing
         tensor (`copy_`, never a rebind), so that device pointers held by the native layer table, a live GreedySession or a
-        captured decode graph stay valid and see the new adapter at their next step."""
+        captured decode graph stay valid and see the new adapter at their next step.  slot > 0: into that slot's rows of the
+        layers' banks (slot 0 IS the parameters)."""
         logging.info("Loading LoRA weights...")
         params = dict(self.named_parameters())
         with torch.no_grad():
@@ -660,7 +772,13 @@ class Transformer(ModelBase):
                 assert tuple(params[k].shape) == tuple(v.shape), (
                     f"LoRA key {k}: shape {tuple(v.shape)} does not fit the model's adapter {tuple(params[k].shape)} "
                     f"(rank {self.args.lora.rank})")
-                params[k].copy_(v)
+                if slot == 0:
+                    params[k].copy_(v)
+                else:
+                    name, which = k.rsplit(".lora_", 1)   # "<linear>", "A.weight" / "B.weight"
+                    mod = self.get_submodule(name)
+                    assert isinstance(mod, LoRALinear) and mod.bank_A is not None and mod.bank_B is not None
+                    (mod.bank_A if which.startswith("A") else mod.bank_B)[slot].copy_(v)
 
     @staticmethod
     def from_folder(folder: Union[Path, str], max_batch_size: int = 1, num_pipeline_ranks: int = 1,
@@ -789,6 +907,9 @@ class GreedySession:
         self._pending = 0                  # steps enqueued and not yet collected
         self._n_collected = 0
         self._first = self.buf.tok.clone()  # input of the session's step 0 (a rollback to step 0 needs it again)
+        # adapter slots (ABI v9): the choice of the prefill that preceded this session, latched here - every step, eager or
+        # replayed, carries this pointer (or NULL) whatever a forward() on the same model chooses in between
+        self._adapter_kw = {"seq_adapter": be.seq_adapter_now()} if hasattr(be, "seq_adapter_now") else {}
 
     # -- one step, enqueued launch by launch
     def _step_eager(self) -> None:
@@ -798,7 +919,7 @@ class GreedySession:
         if self.rank > 0:
             m.pp_comm.recv(self.h, src=self.rank - 1)
         ids = self.buf.tok if self.rank == 0 else None
-        m._backend.run_stack(m, self.h, ids, meta, cache, self.logits, greedy=self.buf if self.is_last else None)
+        m._backend.run_stack(m, self.h, ids, meta, cache, self.logits, greedy=self.buf if self.is_last else None, **self._adapter_kw)
         if not self.is_last:
             m.pp_comm.send(self.h, dst=self.rank + 1)
         if self.world > 1:

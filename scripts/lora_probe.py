@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What un-merged LoRA costs at the Mistral-7B dims (32 layers, rank 64), one process on one box:
 
-    python scripts/lora_probe.py [--layers 32] [--rank 64] [--steps 64] [--only-lora-step]
+    python scripts/lora_probe.py [--layers 32] [--rank 64] [--steps 64] [--only-lora-step] [--slots 3 --mix "none;0,0,0;0,1,2"]
 
 Times (HIP events on the launch stream; warm-up first: the first steps size the workspace, capture the decode graph and, for the
 engine, run its residency census - same discipline as bench.py):
@@ -11,6 +11,9 @@ engine, run its residency census - same discipline as bench.py):
   * a 4096-token prefill, LoRA and merged.
 Weights are random (timing only).  `--only-lora-step` runs nothing but the LoRA model's decode steps: the form to put under
 `rocprofv3 --kernel-trace --stats -- python scripts/lora_probe.py --only-lora-step` for the per-kernel table.
+`--slots S --mix ...` runs nothing but the LoRA model's decode steps with a bank of S adapter sets, once per mix (";"-separated;
+a mix is one adapter slot per sequence, -1 = no adapter, or "none" = `adapters=None`: slot 0 on the single-adapter kernels) -
+what one adapter per sequence costs over one adapter per batch: `lora_step_us[<mix>]`.
 Prints one JSON line."""
 import argparse
 import json
@@ -61,12 +64,13 @@ def event_ms(fn, reps=3):
     return sorted(ts)[len(ts) // 2]
 
 
-def decode_step_us(model, B: int, steps: int) -> float:
+def decode_step_us(model, B: int, steps: int, **fwd) -> float:
+    """fwd: `adapters=...` of the prefill; the session's steps run with the same choice."""
     a = model.args
     cache = BufferCache(model.n_local_layers, 3, 4096, a.n_kv_heads, a.head_dim, None, device=DEV, dtype=torch.bfloat16)
     cache.reset()
     ids = torch.randint(0, a.vocab_size, (32 * B,), generator=torch.Generator().manual_seed(0)).to(DEV)
-    logits = model.forward(ids, [32] * B, cache)
+    logits = model.forward(ids, [32] * B, cache, **fwd)
     first = logits[torch.arange(B, device=DEV) * 32 + 31].argmax(-1)
     sess = model.greedy_session(cache, first)
     sess.run(8)          # warm-up: eager step, graph capture, replays
@@ -95,9 +99,26 @@ def main():
     ap.add_argument("--rank", type=int, default=64)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--only-lora-step", action="store_true")
+    ap.add_argument("--slots", type=int, default=1, help="adapter sets per LoRA linear (Transformer.set_lora_slots)")
+    ap.add_argument("--mix", default="", help='";"-separated mixes, each "none" or one slot per sequence: "none;0,0,0;0,1,2"')
     o = ap.parse_args()
     out = {"layers": o.layers, "rank": o.rank, "steps": o.steps}
     lora = build(o.layers, o.rank)
+    if o.mix:
+        out["slots"] = o.slots
+        if o.slots > 1:
+            lora.set_lora_slots(o.slots)
+            g = torch.Generator(device=DEV).manual_seed(2)
+            with torch.no_grad():
+                for mod in lora.modules():   # (timing only: every slot gets adapters of the usual scale)
+                    if getattr(mod, "bank_A", None) is not None:
+                        mod.bank_A[1:].normal_(0.0, mod.in_features ** -0.5, generator=g)
+                        mod.bank_B[1:].normal_(0.0, 0.25 * mod.rank ** -0.5, generator=g)
+        for mix in o.mix.split(";"):
+            adapters = None if mix == "none" else [int(x) for x in mix.split(",")]
+            out[f"lora_step_us[{mix}]"] = round(decode_step_us(lora, 3 if adapters is None else len(adapters), o.steps, adapters=adapters), 1)
+        print(json.dumps(out))
+        return
     out["lora_step_us_b1"] = round(decode_step_us(lora, 1, o.steps), 1)
     if not o.only_lora_step:
         out["lora_step_us_b3"] = round(decode_step_us(lora, 3, o.steps), 1)
