@@ -332,13 +332,10 @@ struct LoraLinear {
   int n_rows[3];
   int nseg;
   int epilogue;         // MI_EPI_STORE / RESIDUAL / SWIGLU
-  // adapter banks (ABI v9; all zero: one adapter set, the single-adapter kernels).  seq_slot != nullptr: A[i] / B[i] are the
-  // bases of [slots, rank, K] / [slots, n_rows[i], rank] arrays and row m runs through slot seq_slot[tok_seq[m]] (LoraDownArgs)
-  int slots;
-  const int32_t* tok_seq;
-  const int32_t* seq_slot;
+  // adapter bank (ABI v9; all zero: one adapter set, the kernels' single-adapter mode).  seq_slot != nullptr: A[i] / B[i] are the
+  // bases of [slots, rank, K] / [slots, n_rows[i], rank] arrays and row m runs through slot seq_slot[tok_seq[m]] (kernels.h)
+  LoraBank bank;
 };
-bool lora_rank_ok(int rank) { return rank >= 8 && rank <= 64 && rank % 8 == 0; }
 // x: the input of W as the base pass reads it (pre-norm when norm_w is given: the GEMV fuses the RMSNorm); xn: the normalised
 // input (== x without norm_w), which lora_down reads.  base: [M, sum of n_rows] scratch - bf16, or with base_f32 fp32 holding
 // bf16 values: the GEMV's LOGITS form, whose fused RMSNorm is the one of the fused q|k|v and W1|W3 modes (gemv_core.cuh
@@ -369,7 +366,7 @@ int lora_linear(void* out, int ldo, const void* x, int ldx, const void* xn, int 
     LoraDownArgs d;
     memset(&d, 0, sizeof(d));
     d.x = (const bf16_t*)xn; d.ldx = ldxn; d.T = M; d.K = K; d.nseg = L.nseg; d.r = rank; d.t = t;
-    d.slots = L.slots > 1 ? L.slots : 1; d.a_stride = (int64_t)rank * K; d.tok_seq = L.tok_seq; d.seq_slot = L.seq_slot;
+    d.a_stride = (int64_t)rank * K; d.bank = L.bank;
     for (int i = 0; i < L.nseg; ++i) d.A[i] = (L.A[i] && L.B[i]) ? (const bf16_t*)L.A[i] : nullptr;
     MI_TRY(hip_rc(launch_lora_down(d, s), "lora_down"));
   }
@@ -377,7 +374,7 @@ int lora_linear(void* out, int ldo, const void* x, int ldx, const void* xn, int 
   memset(&u, 0, sizeof(u));
   u.epi = L.epilogue; u.T = M; u.N = swiglu ? n0 : n_total; u.base = base; u.ldb = n_total; u.base_f32 = base_f32 ? 1 : 0;
   u.t = t; u.n0 = n0; u.n1 = n1; u.nseg = L.nseg; u.r = rank; u.scaling = scaling;
-  u.slots = L.slots > 1 ? L.slots : 1; u.tok_seq = L.tok_seq; u.seq_slot = L.seq_slot;
+  u.bank = L.bank;
   for (int i = 0; i < L.nseg; ++i) u.b_stride[i] = (int64_t)L.n_rows[i] * rank;
   for (int i = 0; i < L.nseg; ++i) u.B[i] = (L.A[i] && L.B[i]) ? (const bf16_t*)L.B[i] : nullptr;
   u.out = (bf16_t*)out; u.ldo = ldo; u.residual = (const bf16_t*)residual;
@@ -626,7 +623,7 @@ static int lora_linear_leaf(const char* entry, void* out, int ldo, const void* x
   memset(&L, 0, sizeof(L));
   L.nseg = sh.nseg; L.epilogue = epilogue;
   if (slots < 1) return fail(MI_ERR_ARG, "%s: slots %d", entry, slots);
-  L.slots = slots; L.tok_seq = nullptr; L.seq_slot = row_slot;  // (tok_seq == nullptr: row m is its own sequence)
+  L.bank = lora_bank(slots, nullptr, row_slot);  // (tok_seq == nullptr: row m is its own sequence)
   for (int i = 0; i < sh.nseg; ++i) {
     if (!w[i]) return fail(MI_ERR_ARG, "%s: n_rows[%d] without a weight", entry, i);
     if ((A[i] == nullptr) != (B[i] == nullptr)) return fail(MI_ERR_ARG, "%s: adapter %d needs both A and B (or neither)", entry, i);
@@ -1009,9 +1006,9 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
     const mi_lora_layer_t& A = (lora && L.lora) ? *L.lora : kNoAdapters;
     const float ls = m->lora_scaling;
     // adapter banks (ABI v9): the pointers of `A` are bank bases and bt->seq_adapter picks a slot per sequence; without it
-    // every row runs through slot 0 on the single-adapter kernels
+    // every row runs through slot 0 in the kernels' single-adapter mode
     auto banked = [&](LoraLinear ll) {
-      ll.slots = m->lora_slots > 1 ? m->lora_slots : 1; ll.tok_seq = bt->tok_seq; ll.seq_slot = bt->seq_adapter;
+      ll.bank = lora_bank(m->lora_slots, bt->tok_seq, bt->seq_adapter);
       return ll;
     };
     if (lora) {

@@ -315,20 +315,28 @@ const EngineBuild& decode_engine_build_moe();
 // lora.py:71-74 around a base product that the tuned GEMV / GEMM has already written:  t = bf16(A x),
 // d = bf16(bf16(B t) * s), y = bf16(base + d), out = epilogue(y).  Up to three adapters share an input (q|k|v, w1|w3).
 //
-// Adapter banks (ABI v9): with seq_slot != nullptr every A[i] / B[i] is the base of a contiguous per-slot array ([slots, r, K] /
-// [slots, n_rows, r]) and row m runs through slot seq_slot[tok_seq[m]] (tok_seq == nullptr: seq_slot[m]); -1 = no adapter on that
-// row (d = 0), any other value is clamped into the bank.  For one (row, column) the slot kernels perform the fp32 operations of
-// the single-adapter kernels in the same order.  seq_slot == nullptr: today's kernels on the pointers as given (slot 0).
+// Adapter banks (ABI v9): with bank.seq_slot != nullptr every A[i] / B[i] is the base of a contiguous per-slot array
+// ([slots, r, K] / [slots, n_rows, r]) and row m runs through slot seq_slot[tok_seq[m]] (tok_seq == nullptr: seq_slot[m]); -1 = no
+// adapter on that row (d = 0), any other value is clamped into the bank.  The bank is a compile-time mode of the same kernels:
+// for one (row, column) both modes run one loop, the same fp32 operations in the same order.  seq_slot == nullptr: the
+// single-adapter mode on the pointers as given (slot 0).
+struct LoraBank {
+  int slots;                // >= 1 (read with seq_slot only)
+  const int32_t* tok_seq;   // [T] sequence of a row, or nullptr: row m is sequence m
+  const int32_t* seq_slot;  // [B] slot of a sequence, -1 .. slots - 1; nullptr: no bank
+};
+inline LoraBank lora_bank(int slots, const int32_t* tok_seq, const int32_t* seq_slot) {
+  return {slots > 1 ? slots : 1, tok_seq, seq_slot};  // (0 slots: a model or a caller that never asked for a bank)
+}
+inline bool lora_rank_ok(int rank) { return rank >= 8 && rank <= 64 && rank % 8 == 0; }
 struct LoraDownArgs {
   const bf16_t* x;      // [T, ldx] the linear's input (already normalised)
   int ldx, T, K;
   const bf16_t* A[3];   // [r, K] each; nullptr: the segment has no adapter (its slice of t is neither written nor read)
   int nseg, r;
   bf16_t* t;            // [T, nseg * r]; a row on slot -1 is not written
-  int slots;            // >= 1 (read with seq_slot only)
+  LoraBank bank;
   int64_t a_stride;     // elements between two slots of a segment's A: r * K
-  const int32_t* tok_seq;   // [T] sequence of a row, or nullptr: row m is sequence m
-  const int32_t* seq_slot;  // [B] slot of a sequence, -1 .. slots - 1; nullptr: no bank
 };
 struct LoraUpArgs {
   int epi;              // MI_EPI_STORE / MI_EPI_RESIDUAL / MI_EPI_SWIGLU
@@ -344,10 +352,8 @@ struct LoraUpArgs {
   int ldo;
   const bf16_t* residual;  // [T, ldo]
   int fast_silu;        // SiLU as the MFMA GEMM's epilogue evaluates it (swiglu_bf_fast) instead of the GEMV's (swiglu_bf)
-  int slots;            // as LoraDownArgs
   int64_t b_stride[3];  // elements between two slots of a segment's B: n_rows of the segment * r
-  const int32_t* tok_seq;
-  const int32_t* seq_slot;
+  LoraBank bank;
 };
 hipError_t launch_lora_down(const LoraDownArgs& a, hipStream_t s);
 hipError_t launch_lora_up(const LoraUpArgs& a, hipStream_t s);

@@ -10,7 +10,7 @@ the existing tensors, so one set of base weights serves any number of fine-tunes
 
 Adapter banks (`Transformer.set_lora_slots`): a layer then owns `n` adapter sets in two contiguous tensors [n, rank, in] /
 [n, out, rank]; `lora_A.weight` / `lora_B.weight` are views of slot 0, and `forward(..., adapters=[...])` picks a slot per
-sequence inside one batch (csrc/lora.hip, the slot kernels)."""
+sequence inside one batch (csrc/lora.hip, the bank mode of its kernels)."""
 from typing import Optional
 
 import torch

@@ -93,7 +93,7 @@ class HipStackBackend:
         self.dtype_code = 0
         # ABI v9 - adapter slot per sequence: ONE persistent int32 [max_batch_size] device tensor, allocated once and never
         # replaced (a GreedySession or a captured step holds its pointer and stays valid when later calls write other values
-        # into it).  `_seq_adapter_now` is what the next forward carries: None (NULL: slot 0, single-adapter kernels) or the
+        # into it).  `_seq_adapter_now` is what the next forward carries: None (NULL: slot 0, the kernels' single-adapter mode) or the
         # persistent tensor.
         self._seq_adapter: Optional[torch.Tensor] = None
         self._seq_adapter_now: Optional[torch.Tensor] = None
@@ -176,8 +176,8 @@ class HipStackBackend:
         return self._seq_adapter_now is not None
 
     def set_adapters(self, model: "Transformer", adapters: Optional[List[int]]) -> None:
-        """The adapter slot of every sequence for the forwards that follow (already validated): None = slot 0 for all on the
-        single-adapter kernels (`seq_adapter` NULL); a list is copied, stream-ordered, into the persistent device tensor.  A
+        """The adapter slot of every sequence for the forwards that follow (already validated): None = slot 0 for all in the
+        kernels' single-adapter mode (`seq_adapter` NULL); a list is copied, stream-ordered, into the persistent device tensor.  A
         GreedySession latches the choice when it is made (`seq_adapter_now`), so later calls here do not move it."""
         if adapters is None:
             self._seq_adapter_now = None
@@ -403,7 +403,7 @@ class Transformer(ModelBase):
     # ---- forward -------------------------------------------------------------------------------
     def _nocache_metadata(self, seqlens: List[int], per_sequence: bool = False) -> BatchMetadata:
         """The cache=None call is ONE unmasked segment to the kernels; per_sequence (adapter slots in use): tok_seq still names
-        each row's own sequence, which only the LoRA slot kernels read on this branch."""
+        each row's own sequence, which only the LoRA kernels' bank mode reads on this branch."""
         T = sum(seqlens)
         pos = [i for s in seqlens for i in range(s)]
         seq = [b for b, s in enumerate(seqlens) for _ in range(s)] if per_sequence else [0] * T

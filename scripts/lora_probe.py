@@ -12,7 +12,7 @@ engine, run its residency census - same discipline as bench.py):
 Weights are random (timing only).  `--only-lora-step` runs nothing but the LoRA model's decode steps: the form to put under
 `rocprofv3 --kernel-trace --stats -- python scripts/lora_probe.py --only-lora-step` for the per-kernel table.
 `--slots S --mix ...` runs nothing but the LoRA model's decode steps with a bank of S adapter sets, once per mix (";"-separated;
-a mix is one adapter slot per sequence, -1 = no adapter, or "none" = `adapters=None`: slot 0 on the single-adapter kernels) -
+a mix is one adapter slot per sequence, -1 = no adapter, or "none" = `adapters=None`: slot 0 in the kernels' single-adapter mode) -
 what one adapter per sequence costs over one adapter per batch: `lora_step_us[<mix>]`.
 Prints one JSON line."""
 import argparse

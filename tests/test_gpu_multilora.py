@@ -1,10 +1,10 @@
-"""Several LoRA adapters in one batch, one per sequence (adapter banks, csrc/lora.hip slot kernels, ABI v9).
+"""Several LoRA adapters in one batch, one per sequence (adapter banks, the bank mode of csrc/lora.hip's kernels, ABI v9).
 
 The reference has one adapter set per model, so the meaning is defined through it: the rows of sequence b are what the reference
 computes for that sequence with adapter adapters[b] loaded.  Sequences interact only inside attention, which is per sequence, and
-the slot kernels do for one (row, column) the fp32 operations of the single-adapter kernels in the same order - so every
-comparison of a mixed batch with uniform batches here is torch.equal; only the anchor to the reference's stored logits carries
-the project's LOGIT_ATOL."""
+the bank mode of a kernel runs for one (row, column) the loop of its single-adapter mode, the same fp32 operations in the same
+order - so every comparison of a mixed batch with uniform batches here is torch.equal; only the anchors to the reference (the
+leaf's STORE output at the odd K, the model's stored logits) carry a tolerance."""
 import ctypes as C
 import itertools
 
@@ -13,6 +13,7 @@ import torch
 
 import mistral_oracle as mo
 from lora_util import BF, LoraCase, make_adapters, write_lora_checkpoint
+from test_gpu_lora import _parts, _widened_store
 
 pytestmark = pytest.mark.gpu
 LOGIT_ATOL = 4e-2   # tests/test_gpu_model.py
@@ -50,20 +51,50 @@ def _mixed_vs_uniform(h, x, ws, banks_a, banks_b, s, epi, slots, **kw):
     want = torch.stack([uniform[slots[m]][m] for m in range(M)])
     assert torch.equal(got, want), (epi, M, [m for m in range(M) if not torch.equal(got[m], want[m])])
     assert not torch.equal(uniform[0], uniform[1]) and not torch.equal(uniform[1], uniform[2]) and not torch.equal(uniform[0], uniform[-1])
-    # row_slot = NULL: slot 0 on the existing kernels
+    # row_slot = NULL: slot 0 on the kernels' single-adapter mode
     assert torch.equal(h.lora_linear(x, ws, banks_a, banks_b, s, epi, banked=True, **kw), uniform[0])
     return got
 
 
+def _store_against_the_reference(h, x, K, r, s):
+    """STORE of mi_lora_linear (136 | 64 | 64 rows, three adapters) against lora_util.lora_linear_ref, every element inside
+    test_gpu_lora's widened bound, in its unconditional form: one of the element's two addends on the neighbouring bf16 value,
+    plus what one flipped element of t moves d by - granted everywhere, not only behind an observed flip (see the caller)."""
+    rows = (136, 64, 64)
+    ws = [rnd(n, K, seed=70 + i, scale=K ** -0.5) for i, n in enumerate(rows)]
+    As = [rnd(r, K, seed=73 + i, scale=K ** -0.5) for i in range(3)]
+    Bs = [rnd(n, r, seed=76 + i, scale=0.25 * r ** -0.5) for i, n in enumerate(rows)]
+    cuda = lambda ts: tuple(t.cuda() for t in ts)  # noqa: E731
+    y, base, d, _, tflip = _parts(x.cpu(), ws, As, Bs, s)
+    wide = _widened_store(y, base, d) + tflip
+    err = (h.lora_linear(x, cuda(ws), cuda(As), cuda(Bs), s).cpu().float() - y).abs()
+    print(f"M={x.shape[0]} K={K} r={r}: store against the reference, worst err/bound {float((err / wide).max()):.3f}")
+    assert bool((err <= wide).all()), float((err / wide).max())
+    # teeth, on the CPU reference
+    assert bool(((_parts(x.cpu(), ws, As, Bs, 2 * s)[0] - y).abs() > wide).any()), "doubling s stays inside the bound"
+    ysw = _parts(x.cpu(), ws, [As[0], As[2], As[1]], [Bs[0], Bs[2], Bs[1]], s)[0]
+    assert bool(((ysw - y).abs() > wide).any()), "exchanged adapters stay inside the bound"
+
+
+# (the K = 256 cases keep the ids they had before K became a parameter)
+LEAF_CASES = [pytest.param(M, K, id=str(M) if K == 256 else f"{M}-K{K}") for K in (256, 264, 2312) for M in (1, 3, 5, 8, 9, 40)]
+
+
 @pytest.mark.parametrize("r", [8, 64])
-@pytest.mark.parametrize("M", [1, 3, 8, 9, 40])
-def test_leaf_mixed_rows_equal_uniform_calls(M, r):
+@pytest.mark.parametrize("M,K", LEAF_CASES)
+def test_leaf_mixed_rows_equal_uniform_calls(M, K, r):
     """mi_lora_linear_slots with 3 slots and row_slot cycling through [1, -1, 0, 2, 2, 0]: neighbouring rows differ, the 16-row MFMA
     tiles (M = 40) and the 8-row blocks of lora_up straddle slots.  Row m equals row m of mi_lora_linear with slot row_slot[m]'s
     A / B, bit for bit.  STORE with three unequal segments, the middle one without adapter; RESIDUAL; SWIGLU; the fused norm at
-    M <= 8.  M = 1, 3, 8 take the per-token lora_down, 9 and 40 the MFMA form."""
+    M <= 8.  M = 1, 3, 5, 8 take the row-streaming lora_down (M = 5: lora_down_rows_kernel<8> on fewer tokens than it holds, and
+    five per-token blocks with a bank), 9 and 40 the MFMA form.  K = 264 is a multiple of 8 and not of 32: the dead quarter-waves
+    of the MFMA K loop and the dead pieces of the row loop; K = 2312 is 289 pieces: a second, ragged trip of the row loop's 256.
+    Both modes of a kernel are one source, so at the new K values (M = 5, 40) the STORE output of mi_lora_linear is also compared
+    with the reference (_store_against_the_reference) - a coarse anchor: its bound admits one flipped element of t on EVERY
+    element, so it sees a wrong slot, segment or scale, not an error below s * max|B| * |t| * 2^-7 such as one dropped piece of
+    the A dot.  The fine-grained contract is test_gpu_lora.test_lora_linear_leaf's."""
     h = _hip()
-    K, s, S = 256, 1.5, 3
+    s, S = 1.5, 3
     slots = _row_slots(M)
     x = rnd(M, K, seed=20).cuda()
     bank = lambda n, m, seed, scale: rnd(S, n, m, seed=seed, scale=scale).cuda()  # noqa: E731
@@ -88,6 +119,8 @@ def test_leaf_mixed_rows_equal_uniform_calls(M, r):
         nw = (1 + 0.1 * torch.randn(K, generator=torch.Generator().manual_seed(61))).to(BF).cuda()
         _mixed_vs_uniform(h, x, ws, A, B, s, h.EPI_STORE, slots, norm_w=nw, eps=1e-5)
         _mixed_vs_uniform(h, x, w13, A2, B2, s, h.EPI_SWIGLU, slots, norm_w=nw, eps=1e-5)
+    if K != 256 and M in (5, 40):
+        _store_against_the_reference(h, x, K, r, s)
 
 
 # ------------------------------------------------------------------------------------------------ models
@@ -184,7 +217,7 @@ def test_model_mixed_batch_equals_uniform_batches(mix, models):
 
 @pytest.mark.parametrize("lens", [(12,), (7, 3, 5)], ids=["batch1", "batch3"])
 def test_none_and_all_zero_equal_the_one_slot_model(lens, models):
-    """Existing behaviour: on the 3-slot model adapters=None (the single-adapter kernels) and adapters=[0] * B (the slot kernels)
+    """Existing behaviour: on the 3-slot model adapters=None (the kernels' single-adapter mode) and adapters=[0] * B (their bank mode)
     both give the logits, tokens and log-probabilities of a one-slot model that never saw set_lora_slots and carries slot 0's set."""
     from mistral_inference.generate import generate
     bank, one = models["bank"], models["one"]
@@ -293,7 +326,7 @@ def test_swapping_one_slot_on_a_live_model(models, tmp_path):
 def test_forward_without_a_cache_reads_each_rows_own_sequence(lens, models):
     """cache=None (NOCACHE branch) with adapters.  Attention there is ONE unmasked segment over all rows, so a sequence's rows
     depend on its neighbours' adapters and cannot be compared with uniform runs; what must hold instead:
-    * [0, 0, 0] through the slot kernels equals the one-slot model's cache-less forward (tok_seq 0, 1, 2 all on slot 0);
+    * [0, 0, 0] through the bank mode equals the one-slot model's cache-less forward (tok_seq 0, 1, 2 all on slot 0);
     * [2, 0, 1] equals [0, 1, 2] on a bank whose slots carry the sets (2, 0, 1) - the same set per sequence, other slot numbers;
     * [2, 0, 1] differs from [2, 2, 2], which is what it would give if every row were taken for sequence 0."""
     one = models["one"]
