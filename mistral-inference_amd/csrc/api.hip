@@ -847,7 +847,7 @@ int mi_debug_engine_sabotage(void* workspace, int launches, mi_stream_t stream) 
   if (!workspace || launches < 0) return fail(MI_ERR_ARG, "mi_debug_engine_sabotage");
   static thread_local uint32_t v;
   v = (uint32_t)launches;
-  MI_TRY(hip_rc(hipMemcpyAsync((uint32_t*)workspace + 7, &v, 4, hipMemcpyHostToDevice, (hipStream_t)stream), "sabotage word"));
+  MI_TRY(hip_rc(hipMemcpyAsync((uint32_t*)workspace + CTRL_SABOTAGE, &v, 4, hipMemcpyHostToDevice, (hipStream_t)stream), "sabotage word"));
   return hip_rc(hipStreamSynchronize((hipStream_t)stream), "sabotage sync");
 }
 
@@ -987,7 +987,7 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
       MI_TRY(hip_rc(launch_decode_prep(bt->kv_seqlens, bt->q_start, bt->kv_before, bt->tok_seq, bt->tok_pos, B, engine_ctrl, s),
                     "decode_prep"));
     if (embed)
-      MI_TRY(hip_rc(launch_embedding(h, m->tok_embeddings, bt->input_ids, T, D, m->vocab_size, engine_ctrl + 3, s), "embedding"));
+      MI_TRY(hip_rc(launch_embedding(h, m->tok_embeddings, bt->input_ids, T, D, m->vocab_size, engine_ctrl + CTRL_BAD_ID, s), "embedding"));
   }
 
   for (int l = 0; l < m->n_layers; ++l) {
@@ -1307,7 +1307,7 @@ int mi_forward_generic(const mi_model_t* m, const mi_batch_t* bt, int dtype, mi_
   if (branch == MI_BRANCH_DECODE)
     MI_TRY(hip_rc(launch_decode_prep(bt->kv_seqlens, bt->q_start, bt->kv_before, bt->tok_seq, bt->tok_pos, B, ws.ctrl, s), "decode_prep"));
   if (m->tok_embeddings && bt->input_ids)
-    MI_TRY(hip_rc(launch_g_embedding(dt, h, m->tok_embeddings, bt->input_ids, T, D, m->vocab_size, ws.ctrl + 3, s), "embedding"));
+    MI_TRY(hip_rc(launch_g_embedding(dt, h, m->tok_embeddings, bt->input_ids, T, D, m->vocab_size, ws.ctrl + CTRL_BAD_ID, s), "embedding"));
 
   for (int l = 0; l < m->n_layers; ++l) {
     const mi_layer_t& L = m->layers[l];

@@ -23,7 +23,7 @@
 //     (Guideline 16 R2: the data is the flag - no fences, no barriers, placement-independent).  tag = (step epoch << 12)
 //     | (layer * 8 + edge + 1): unique per step and edge, so buffers are never re-initialised.  The epoch lives in
 //     device memory and is bumped by the step's first kernel (decode_prep), so hipGraph replays see fresh tags.
-//   * Every spin is bounded; on a timeout the block raises ctrl[1] (sticky) / ctrl[2] (per-step broadcast), all waits
+//   * Every spin is bounded; on a timeout the block raises CTRL_STATUS (sticky) / CTRL_ABORT (per-step broadcast), all waits
 //     fall through and the launch drains.  mi_engine_status() reads the sticky word.
 //
 // Work split per layer (NB = CUs): q/k/v/Wo/W2/LM-head rows in contiguous slabs of row PAIRS per CU; W1|W3 in slabs of
@@ -35,30 +35,120 @@
 #include "attn_decode_core.cuh"
 #include "kernels.h"
 
-// ENG_WIDE = 1: this file compiled a SECOND time (build_native.py -> decode_engine_wide.o) under other entry-point names, for
-// the model shapes the shipped instantiations decline: GQA ratio 6 and a hid vector of 32 KiB (Mixtral-8x22B: dim 6144, 48 / 8
-// heads, hidden 16384 - needs a 7-fill ring), rows that are not a multiple of 4 pieces (Mistral-Nemo: dim 5120, streamed as
-// contiguous units instead of 2-piece groups).  Every difference sits behind `#if ENG_WIDE`, so the default compile of this
-// file is token for token what it was: this kernel's speed moves by several per cent with ANY change of its code (see
-// ENG_TRACE below), and the headline configuration must not pay for shapes it never runs.  scripts/engine_isa_hash.sh
-// prints a hash of the default object's ISA; it has not changed since round 3.
+// ------------------------------------------------------------------------------------------------ compile-time switches
+// This file is compiled five times for the shipped library (build_native.py: SOURCES, VARIANT_OBJECTS) and any number of times
+// for experiment libraries (scripts/build_variants.py: VARIANTS, FILE_VARIANTS, and the `_x<N>` slots of ENGINE_SLOTS that
+// scripts/engine_ab.py times in one process).  Every build computes the same bits.  What each shipped object passes:
+//
+//   object (EngineBuild name)        WIDE HEADLINE_ONLY TRACE SADDR QKV_HOLD ABORT_RARE CONS_PRIO HOLD_STAGE NOSTOP HOLD_GATE CLEAN_ENTRY
+//   decode_engine.o       "default"    0        0         1     0      0         0          0         3        0        0          0
+//   decode_engine_next.o  "next"       0        1         0     2      0         1          1         2       32        1          0
+//   decode_engine_nemo.o  "nemo"       2        2         0     2      0         1          1         3       32        0          1
+//   decode_engine_wide.o  "wide"       1        0         1     0      2         1          1         3        0        0          0
+//   decode_engine_moe.o   "moe"        2        0         1     0      2         0          0         3        0        0          0
+//   (all five: ENG_HOLDERS 3, ENG_ALL4 1, ENG_STALL_TRACE 0; `next` and `nemo` also pass ENG_SUFFIX)
+//
+// Values that no build, test or named experiment passes are refused (the #error below the defaults), their code is gone:
+// ENG_SADDR = 1 (the SGPR-base form through hipcc's builtin), ENG_QKV_HOLD = 1 (holders released by the loader's Wo stage) and
+// ENG_HOLD_STAGE = 0.
+// The measurements behind every choice are in profiles/EXPERIMENTS.md (rounds 3-7) and DESIGN.md section 3.  Shape-specific code
+// sits behind these switches because this kernel's speed moves by several per cent with ANY change of its instruction stream, and
+// a build must not pay for shapes it never runs: scripts/engine_isa_hash.sh prints a hash of an object's ISA, and an edit that is
+// meant to leave the device code alone is held to it, object by object.
+//
+// ENG_WIDE (0, 1, 2): the model shapes the default instantiations decline.  1: GQA ratio 6 and a hid vector of 32 KiB
+//   (Mixtral-8x22B: dim 6144, 48 / 8 heads, hidden 16384) on a 7-fill ring, and rows that are not a multiple of 4 pieces (streamed
+//   as contiguous units instead of 2-piece groups).  2: the same additions on the 8-fill ring: at dim 4096 the four consumer
+//   waves' W1|W3 units span exactly 8 fills, and the 7-fill ring costs Mixtral-8x7B 6 % of its W1|W3 streaming rate.
+// ENG_HEADLINE_ONLY (0, 1, 2): 1 instantiates only decode_engine_kernel<4, dense, all rows multiples of 4 pieces> (the headline
+//   shape); 2 only <4, dense, rows NOT all multiples of 4 pieces> (Mistral-Nemo: dim 5120 = rows of 10 pieces; with ENG_WIDE = 2).
+// ENG_SUFFIX (a token such as _next): the entry-point suffix and the EngineBuild name of a further compile.
+// ENG_HOLDERS (3, 0): holder waves per workgroup; 0 is the 5-wave experiment.
+// ENG_TRACE (0, 1, 2): 1 keeps the phase-timeline stamp sites (mi_debug_set_engine_trace, scripts/engine_trace.py) although they
+//   cost a test of a null pointer each.  Compiling them out (0) makes the three builds WITHOUT ENG_SADDR 14-19 % SLOWER: hipcc then
+//   places `s_waitcnt vmcnt(0)` at the top of the loader's per-unit loops, in front of the rewrite of a DMA's 64-bit VGPR address
+//   pair - a drain of the DMA queue per unit.  So `default`, `wide` and `moe` keep the sites; with ENG_SADDR the build without
+//   them is as fast as the one with them, and `next` and `nemo` drop them.  2 replaces the stamps by bare compiler barriers
+//   (experiment).
+// ENG_SADDR (0, 2): 2 issues every LDS-DMA of the loader from inline asm, the weight and K/V-run streams in the SGPR-base form
+//   (`global_load_lds_dwordx4 v_lane_offset, s[base:base+1]`): the per-unit / per-group address arithmetic becomes scalar, no VGPR
+//   that an in-flight DMA names is ever rewritten, and hipcc's wait-count pass has no DMA left to track.  What it cures: with
+//   64-bit VGPR addresses hipcc guards every rewrite of the address pair with `s_waitcnt vmcnt(0)` - it treats the pair as the
+//   destination of a load - which drains the DMA queue once per unit in some builds and not in others (up to 30 % per step: the
+//   "regimes" of rounds 3-5).  scripts/engine_loader_waits.py finds such waits statically; tests/test_engine_build.py.
+// ENG_QKV_HOLD (0, 2): MoE models, whose holder waves have no W1|W3 unit to keep (which experts stream is decided late).  2: the
+//   three holder waves keep the LAST SIX q|k|v row-pair units of the NEXT layer in registers (two units = 4 rows = 128 VGPRs
+//   each; the wide build's rows of 12 pieces: one unit each), fetched in the one window of a MoE layer in which HBM idles - the
+//   router bubble, from the moment this workgroup has gathered h1 (C_HGO).  When attention_norm(h) of that layer stands in LDS
+//   they reduce their rows from registers (the arithmetic of Cons::unit_dot<2>: bit-identical) and run the consumers' epilogue
+//   (RoPE, ring write, granule): 96 KiB per workgroup and layer that no longer pass through the ring in the loader-bound q|k|v
+//   phase.
+// ENG_ALL4 (1, 0): 1 lets instantiations whose weight rows are all multiples of 4 pieces (dim, n_heads*128 and hidden_dim multiples
+//   of 2048 - every BASELINE model but Nemo) drop the generic-group path from the five row loops of the consumers.
+// ENG_ABORT_RARE (0, 1): 1 reads the abort word on every 1024th iteration of a spin only (one LDS read less per poll).
+// ENG_CONS_PRIO (0, 1, 2): s_setprio of the consumer waves (the loader runs at 3, holders at 0).
+// ENG_HOLD_STAGE (1, 2, 3): the holders' fetch of a layer's units may begin when the loader has issued 1 q|k|v, 2 + K/V, 3 + Wo.
+// ENG_NOSTOP (bit mask: 1 h, 2 q, 4 split merge, 8 attn, 16 h1, 32 hid): sweeps during which this workgroup's loader is NOT stopped.
+// ENG_HOLD_GATE (0, 1): 1 ties the holders' loads to the window in which this CU's HBM stream idles.  The loader raises C_LFULL
+//   while it waits for a free ring slot (fill_begin) and sets C_LWO once the layer's Wo rows are issued; a holder issues its next
+//   8 loads only while no sweep is in progress AND (the ring is full OR the Wo rows are on their way), or - whatever the loader
+//   does - once ffn_norm(h1) stands in LDS (C_XREADY: the hid values are due, no deadlock).
+// ENG_CLEAN_ENTRY (0, 1): 1 begins run_loader with a wait-count instruction that hipcc models (see there).
+// ENG_STALL_TRACE (0, 1; needs ENG_TRACE = 1): 1 makes the loader time its ring-full waits too - trace event TR_CONS + 7 of a layer
+//   holds the 100 MHz ticks it spent waiting for a free ring slot during the attention block (q|k|v, K/V, Wo: low word) and
+//   during the FFN (W1|W3, W2: high word); scripts/engine_trace.py reports them.
+// (Experiments that measured slower or within noise - sparse re-polls, lean barriers, a flag barrier, the consumer marks as one
+// 16-byte line, cached marks, per-site sleep lengths, 8-piece fills, the stamp-site bisect mask, a finer holder check - were
+// removed from this file in round 6: scripts/probes/decode_engine_experiments.patch restores them.)
 #ifndef ENG_WIDE
 #define ENG_WIDE 0
 #endif
-// ENG_WIDE = 2: the same additions with the shipped 8-fill ring, MoE models only (decode_engine_moe.o): at dim 4096 the four
-// consumer waves' W1|W3 units span exactly 8 fills, and the 7-fill ring of ENG_WIDE = 1 costs Mixtral-8x7B 6 % of its W1|W3
-// streaming rate (25.6 vs 27.2 GB/s per CU, profiles/r04_engine_trace_8x7b_*) - as much as the batched router saves.
-// ENG_HEADLINE_ONLY = 2 (round 6, decode_engine_nemo.o: + ENG_WIDE = 2, ENG_SADDR = 2): only decode_engine_kernel<4, dense, rows NOT
-// all multiples of 4 pieces> on the 8-fill ring - Mistral-Nemo (dim 5120 = rows of 10 pieces, streamed as contiguous units).
-// ENG_SUFFIX (round 5): further compiles of this source under their own entry-point names - `_next` (decode_engine_next.o: the
-// dense GQA-4 headline shape with the round-5 switches below: ENG_ABORT_RARE, ENG_CONS_PRIO, ENG_HOLD_STAGE, ENG_SADDR = 2 and
-// ENG_TRACE = 0 - build_native.py: ENGINE_NEXT_FLAGS) and the `_x<N>` slots of an experiment library (scripts/build_variants.py
-// engine_slots, scripts/engine_ab.py).  ENG_HEADLINE_ONLY = 1 instantiates only decode_engine_kernel<4, dense, all rows
-// multiples of 4 pieces>.  Why the default object is kept frozen and what made builds of this file differ by up to 30 % in speed
-// (hipcc's `s_waitcnt vmcnt(0)` in the loader's issue loop, ENG_SADDR below): DESIGN.md section 3, profiles/EXPERIMENTS.md round 5.
 #ifndef ENG_HEADLINE_ONLY
 #define ENG_HEADLINE_ONLY 0
 #endif
+#ifndef ENG_HOLDERS
+#define ENG_HOLDERS 3
+#endif
+#ifndef ENG_TRACE
+#define ENG_TRACE 1
+#endif
+#ifndef ENG_SADDR
+#define ENG_SADDR 0
+#endif
+#ifndef ENG_QKV_HOLD
+#define ENG_QKV_HOLD 0
+#endif
+#ifndef ENG_ALL4
+#define ENG_ALL4 1
+#endif
+#ifndef ENG_ABORT_RARE
+#define ENG_ABORT_RARE 0
+#endif
+#ifndef ENG_CONS_PRIO
+#define ENG_CONS_PRIO 0
+#endif
+#ifndef ENG_HOLD_STAGE
+#define ENG_HOLD_STAGE 3
+#endif
+#ifndef ENG_NOSTOP
+#define ENG_NOSTOP 0
+#endif
+#ifndef ENG_HOLD_GATE
+#define ENG_HOLD_GATE 0
+#endif
+#ifndef ENG_CLEAN_ENTRY
+#define ENG_CLEAN_ENTRY 0
+#endif
+#ifndef ENG_STALL_TRACE
+#define ENG_STALL_TRACE 0
+#endif
+#if (ENG_SADDR != 0 && ENG_SADDR != 2) || (ENG_QKV_HOLD != 0 && ENG_QKV_HOLD != 2) || ENG_HOLD_STAGE < 1 || ENG_HOLD_STAGE > 3
+#error "ENG_SADDR and ENG_QKV_HOLD take 0 or 2, ENG_HOLD_STAGE takes 1, 2 or 3: the values that are built"
+#endif
+#if ENG_STALL_TRACE && ENG_TRACE != 1
+#error "ENG_STALL_TRACE needs the stamp sites (ENG_TRACE = 1)"
+#endif
+#define GATHER_FLAG(bit) ((ENG_NOSTOP & (bit)) ? 0u : 1u)
 #define ENG_CAT_(a, b) a##b
 #define ENG_CAT(a, b) ENG_CAT_(a, b)
 #define ENG_STR_(x) #x
@@ -86,79 +176,6 @@ namespace {
 using namespace attn_core;
 
 constexpr int NCONS = 4;
-#ifndef ENG_HOLDERS
-#define ENG_HOLDERS 3  // holder waves per workgroup (0: none)
-#endif
-// (Experiments that measured slower or within noise - sparse re-polls, lean barriers, a flag barrier, the consumer marks as one
-// 16-byte line, cached marks, per-site sleep lengths, 8-piece fills, the stamp-site bisect mask, a finer holder check - were
-// removed from this file in round 6: scripts/probes/decode_engine_experiments.patch restores them; profiles/EXPERIMENTS.md has
-// every number.)
-// ENG_TRACE = 1 (default, wide and MoE builds): the phase-timeline stamp sites (mi_debug_set_engine_trace, scripts/engine_trace.py)
-// stay in the kernel although they cost a test of a null pointer each.  MEASURED: compiling them out makes THOSE builds 14-19 %
-// SLOWER (profiles/EXPERIMENTS.md rounds 3-5): without the sites hipcc places `s_waitcnt vmcnt(0)` at the top of the loader's
-// per-unit loops (in front of the rewrite of a DMA's 64-bit VGPR address pair) - a drain of the DMA queue per unit.  With the
-// DMAs out of hipcc's sight (ENG_SADDR = 2) the build without the sites is as fast as the one with them: the `next` build ships
-// ENG_TRACE = 0.  ENG_TRACE = 2 replaces the stamps by bare compiler barriers (experiment).
-#ifndef ENG_TRACE
-#define ENG_TRACE 1
-#endif
-// ENG_ALL4: instantiations whose weight rows are all multiples of 4 pieces (dim, n_heads*128 and hidden_dim multiples of
-// 2048 - every BASELINE model but Nemo) drop the generic-group path from the five row loops of the consumers.
-#ifndef ENG_ALL4
-#define ENG_ALL4 1
-#endif
-#ifndef ENG_ABORT_RARE
-#define ENG_ABORT_RARE 0  // 1: the abort word is read on every 1024th iteration of a spin only (one LDS read less per poll)
-#endif
-#ifndef ENG_CONS_PRIO
-#define ENG_CONS_PRIO 0   // s_setprio of the consumer waves (the loader runs at 3, holders at 0)
-#endif
-// ENG_QKV_HOLD = 1 (MoE models; their holder waves have no W1|W3 unit to keep - which experts stream is decided late): the
-// three holder waves keep the LAST SIX q|k|v row-pair units of the NEXT layer in registers (two units = 4 rows = 128 VGPRs
-// each), fetched in the one window of a MoE layer in which HBM idles - the router bubble: the loader has flushed behind
-// the Wo rows and waits for the expert decision (~6 us, profiles/r04_engine_trace_8x7b_*).  When attention_norm(h) of that
-// layer stands in LDS they reduce their rows from registers (the arithmetic of Cons::unit_dot<2>: bit-identical) and run
-// the consumers' epilogue (RoPE, ring write, granule).  96 KiB per workgroup and layer that no longer pass through the ring
-// in the loader-bound q|k|v phase.
-#ifndef ENG_QKV_HOLD
-#define ENG_QKV_HOLD 0
-#endif
-// ENG_SADDR = 1: the loader's weight DMAs in the SGPR-base form (`global_load_lds_dwordx4 v_lane_offset, s[base:base+1]`): the
-// per-unit / per-group address arithmetic becomes scalar and no VGPR that an in-flight DMA names is ever rewritten.  (With
-// 64-bit VGPR addresses hipcc guards every rewrite of the address pair with `s_waitcnt vmcnt(0)` - it treats the pair as
-// the destination of a load - which drains the DMA queue once per unit in some builds and not in others: one of the
-// mechanisms behind this kernel's "regimes", profiles/EXPERIMENTS.md round 5.)
-#ifndef ENG_SADDR
-#define ENG_SADDR 0
-#endif
-// ENG_NOSTOP (bit mask: 1 h, 2 q, 4 split merge, 8 attn, 16 h1, 32 hid): sweeps during which this workgroup's loader is NOT stopped
-#ifndef ENG_NOSTOP
-#define ENG_NOSTOP 0
-#endif
-#define GATHER_FLAG(bit) ((ENG_NOSTOP & (bit)) ? 0u : 1u)
-// ENG_CLEAN_ENTRY = 1: run_loader begins with a wait-count instruction that hipcc models (see there; round 6)
-#ifndef ENG_CLEAN_ENTRY
-#define ENG_CLEAN_ENTRY 0
-#endif
-#ifndef ENG_HOLD_STAGE
-#define ENG_HOLD_STAGE 3  // the holders' fetch of a layer's units may begin when the loader has issued: 0 nothing yet, 1 q|k|v, 2 + K/V, 3 + Wo
-#endif
-// ENG_HOLD_GATE = 1 (round 7, the `next` build): the holders' loads are tied to the window in which this CU's HBM stream idles.
-// The loader raises C_LFULL while it waits for a free ring slot (fill_begin) and sets C_LWO once the layer's Wo rows are issued;
-// a holder issues its next 8 loads only while no sweep is in progress AND (the ring is full OR the Wo rows are on their way),
-// or - whatever the loader does - once ffn_norm(h1) stands in LDS (C_XREADY: the hid values are due, no deadlock).
-#ifndef ENG_HOLD_GATE
-#define ENG_HOLD_GATE 0
-#endif
-// ENG_STALL_TRACE = 1 (with ENG_TRACE = 1): the loader also times its ring-full waits - trace event TR_CONS + 7 of a layer holds
-// the 100 MHz ticks it spent waiting for a free ring slot during the attention block (q|k|v, K/V, Wo: low word) and during the
-// FFN (W1|W3, W2: high word); scripts/engine_trace.py reports them.
-#ifndef ENG_STALL_TRACE
-#define ENG_STALL_TRACE 0
-#endif
-#if ENG_STALL_TRACE && ENG_TRACE != 1
-#error "ENG_STALL_TRACE needs the stamp sites (ENG_TRACE = 1)"
-#endif
 constexpr int NHOLD = ENG_HOLDERS;
 constexpr int NTHREADS = (NCONS + 1 + NHOLD) * 64;
 constexpr int PIECE = 1024;          // bytes per DMA instruction: 64 lanes x 16 B
@@ -206,15 +223,11 @@ enum : int {
   C_LWO = 17,       // ENG_HOLD_GATE: (layer + 1) once this layer's Wo rows are issued (loader -> holders)
 #endif
   C_XA = 21,        // ENG_QKV_HOLD: (layer + 1) once attention_norm(h) of that layer stands in the activation region (-> holders)
-  C_HGO = 23,       // ENG_QKV_HOLD = 2: (layer + 1) once this workgroup has h1 of that layer (the router runs next: no sweep for a while)
+  C_HGO = 23,       // ENG_QKV_HOLD: (layer + 1) once this workgroup has h1 of that layer (the router runs next: no sweep for a while)
   C_HQDONE = 22,    // ENG_QKV_HOLD: holder waves done with their q|k|v units since the launch began (-> consumers)
   C_EXPERT = 20,    // MoE: ((layer + 1) << 16) | expert A | expert B << 8 (ascending ids) once the router has decided (consumers -> loader)
   C_RLOGIT = 24     // [16] MoE: bf16-rounded router logits of the layer (fp32 words)
 };
-// global control words (workspace): [0] step epoch, [1] sticky status, [2] abort broadcast, [3] bad token id, [4] engine
-// launches completed, [5] decode steps committed (index into the greedy history ring), [6] workgroup arrivals
-// [7] test hook: engine launches that shall fail their residency gate (mi_debug_engine_sabotage)
-enum : int { G_EPOCH = 0, G_STATUS = 1, G_ABORT = 2, G_BADID = 3, G_LAUNCHES = 4, G_STEPS = 5, G_ARRIVE = 6, G_SABOTAGE = 7 };
 constexpr uint32_t ARRIVE_POLLS = 1u << 16;  // ~50 ms: far beyond the ~1 us over which a resident grid starts
 
 // Optional timeline (mi_debug_set_engine_trace): trace[c][layer][event] = 100 MHz wall clock.  Consumer wave 0 writes
@@ -229,7 +242,7 @@ struct Shared {
   lchar* xs;    // activation vector / attention scratch
   lchar* ring;
   uint32_t ring_mask;  // ring pieces - 1
-  gu32* ctrl;          // global control words (G_* below)
+  gu32* ctrl;          // global control words (kernels.h: CTRL_*)
   gu64* trace;         // optional timeline buffer
 };
 
@@ -244,9 +257,9 @@ __device__ __forceinline__ void trace_ev(const Shared& sh, int c, int layer, int
 
 __device__ __forceinline__ void raise_abort(const Shared& sh, uint32_t code) {
   sh.ctl[C_ABORT] = 1;
-  __hip_atomic_store(sh.ctrl + 2, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(sh.ctrl + CTRL_ABORT, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   uint32_t expected = 0;
-  __hip_atomic_compare_exchange_strong(sh.ctrl + 1, &expected, code, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+  __hip_atomic_compare_exchange_strong(sh.ctrl + CTRL_STATUS, &expected, code, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -257,7 +270,7 @@ __device__ __forceinline__ bool spin_ok(const Shared& sh, uint32_t& spins, uint3
   ++spins;
   if ((spins & 1023u) == 0) {
     if (ENG_ABORT_RARE && sh.ctl[C_ABORT]) return false;
-    if (__hip_atomic_load(sh.ctrl + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+    if (__hip_atomic_load(sh.ctrl + CTRL_ABORT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
       sh.ctl[C_ABORT] = 1;
       return false;
     }
@@ -426,12 +439,12 @@ struct Loader {
       if (f >= 32 / FILL) publish(f - 32 / FILL);
     }
   }
-  // The DMA itself: hipcc's builtin, or (ENG_SADDR >= 2) inline asm (cdna_hip_programming.md section 5.7 recipe: M0 is written in
+  // The DMA itself: hipcc's builtin, or (ENG_SADDR) inline asm (cdna_hip_programming.md section 5.7 recipe: M0 is written in
   // the statement that reads it and restored), which keeps the DMA out of hipcc's s_waitcnt bookkeeping.
   template <int N>
   __device__ __forceinline__ void dma_n(const void* src_lane, lchar* dst) {
-#if ENG_SADDR >= 2
-    // ENG_SADDR >= 2: NO builtin LDS-DMA is left in the loader.  The pieces that still carry per-lane addresses - K/V pieces of
+#if ENG_SADDR
+    // NO builtin LDS-DMA is left in the loader.  The pieces that still carry per-lane addresses - K/V pieces of
     // rings in the reference's layout and of splits that are not whole 16-slot groups (kv_runs) - are rare at the shapes this
     // build serves, but as builtins they are what hipcc's wait-count pass tracks: it guards every LDS read and every rewrite
     // of an address register that MAY follow one with `s_waitcnt vmcnt(0)`, e.g. in fill_begin - a drain of the DMA queue per
@@ -463,18 +476,10 @@ struct Loader {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src_lane, (LDS_AS void*)dst, 16, OFF, 2 /* nt */);
   }
 #if ENG_SADDR
-  // wave-uniform base (SGPR pair) + this lane's 32-bit byte offset (one VGPR, written once per launch)
-  template <int OFF>
-  __device__ __forceinline__ void dma_s(const char* sbase, lchar* dst) {
-    const unsigned long long b = reinterpret_cast<unsigned long long>(sbase);  // (readfirstlane: an opaque, provably uniform pair)
-    const unsigned long long bu = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
-                                  (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
-    const __attribute__((address_space(1))) char* gp = (const __attribute__((address_space(1))) char*)bu + (uint32_t)(lane * 16);
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp, (LDS_AS void*)dst, 16, OFF, 2 /* nt */);
-  }
+  // wave-uniform base (SGPR pair, readfirstlane: an opaque, provably uniform pair) + this lane's 32-bit byte offset (one VGPR,
+  // written once per launch)
   __device__ __forceinline__ void piece_s(const char* sbase) {
     if ((g & (FILL - 1)) == 0) fill_begin();
-#if ENG_SADDR >= 2
     unsigned keep;
     const uint32_t lds_addr = (uint32_t)reinterpret_cast<size_t>(slot_of(g));
     const unsigned long long b = reinterpret_cast<unsigned long long>(sbase);
@@ -483,16 +488,12 @@ struct Loader {
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 4\n\t"
                  "global_load_lds_dwordx4 %1, %2 nt\n\t"
                  "s_mov_b32 m0, %0" : "=&s"(keep) : "v"(lane16), "s"(bu), "s"(lds_addr) : "memory");
-#else
-    dma_s<0>(sbase, slot_of(g));
-#endif
     ++g;
     if ((g & (FILL - 1)) == 0) fill_end();
   }
   __device__ __forceinline__ void piece4_s(const char* sbase) {
     if ((g & (FILL - 1)) == 0) fill_begin();
     lchar* dst = slot_of(g);
-#if ENG_SADDR == 2
     // (hipcc's lowering of the builtin keeps the 64-bit VGPR address even for an SGPR base + zext(VGPR) sum: the SGPR-base
     // form is written out.  M0 carries the LDS address; it is written in the statement that reads it and restored
     // (cdna_hip_programming.md section 5.7).  hipcc does not count these loads: every wait for them is the explicit
@@ -510,12 +511,6 @@ struct Loader {
                  "global_load_lds_dwordx4 %1, %2 offset:2048 nt\n\t"
                  "global_load_lds_dwordx4 %1, %2 offset:3072 nt\n\t"
                  "s_mov_b32 m0, %0" : "=&s"(keep) : "v"(lane16), "s"(bu), "s"(lds_addr) : "memory");
-#else
-    dma_s<0>(sbase, dst);
-    dma_s<PIECE>(sbase, dst);
-    dma_s<2 * PIECE>(sbase, dst);
-    dma_s<3 * PIECE>(sbase, dst);
-#endif
     g += 4;
     if ((g & (FILL - 1)) == 0) fill_end();
   }
@@ -536,6 +531,17 @@ struct Loader {
     g += 4;
     if ((g & (FILL - 1)) == 0) fill_end();
   }
+  // Pieces of a contiguous run (a weight row, a K/V run): what lane_src() made of the run's wave-uniform base, advanced by whole
+  // pieces, goes to row1 / row4.  ENG_SADDR: the base itself (SGPR pair; the lane's offset is in lane16); otherwise this lane's address.
+#if ENG_SADDR
+  __device__ __forceinline__ const char* lane_src(const bf16_t* base) const { return reinterpret_cast<const char*>(base); }
+  __device__ __forceinline__ void row1(const char* src) { piece_s(src); }
+  __device__ __forceinline__ void row4(const char* src) { piece4_s(src); }
+#else
+  __device__ __forceinline__ const char* lane_src(const bf16_t* base) const { return reinterpret_cast<const char*>(base) + lane * 16; }
+  __device__ __forceinline__ void row1(const char* src) { piece(src); }
+  __device__ __forceinline__ void row4(const char* src) { piece4(src); }
+#endif
   // One UNIT = NR weight rows of P pieces each that a consumer wave reduces together.  Stream order inside a unit: groups
   // of G pieces, row after row - rows[0][0..G), rows[1][0..G), ..., rows[0][G..2G), ... - so that the consumer can start on
   // the first group while the rest is in flight and hand ring space back group by group (a unit of W2 is 56 pieces: four
@@ -544,31 +550,17 @@ struct Loader {
   // n pieces that are contiguous in memory (and land contiguously in the ring): four per address computation wherever the
   // stream position allows it
   __device__ __forceinline__ void seg(const bf16_t* base, int n) {
-#if ENG_SADDR
-    const char* sb = reinterpret_cast<const char*>(base);  // (wave-uniform base; the lane's offset is in lane16)
+    const char* src = lane_src(base);
     int i = 0;
     while (i < n) {
       if ((g & 3) == 0 && n - i >= 4) {
-        piece4_s(sb + (size_t)i * PIECE);
+        row4(src + (size_t)i * PIECE);
         i += 4;
       } else {
-        piece_s(sb + (size_t)i * PIECE);
+        row1(src + (size_t)i * PIECE);
         ++i;
       }
     }
-#else
-    const char* src = reinterpret_cast<const char*>(base) + lane * 16;
-    int i = 0;
-    while (i < n) {
-      if ((g & 3) == 0 && n - i >= 4) {
-        piece4(src + (size_t)i * PIECE);
-        i += 4;
-      } else {
-        piece(src + (size_t)i * PIECE);
-        ++i;
-      }
-    }
-#endif
   }
 #endif
   template <int NR>
@@ -591,21 +583,12 @@ struct Loader {
     for (int p0 = 0; p0 < P; p0 += G) {
 #pragma unroll
       for (int r = 0; r < NR; ++r) {
-#if ENG_SADDR
-        const char* sb = reinterpret_cast<const char*>(rp[r]) + (size_t)p0 * PIECE;
+        const char* src = lane_src(rp[r]) + (size_t)p0 * PIECE;
         if (G == 4 && (g & 3) == 0) {
-          piece4_s(sb);
+          row4(src);
         } else {
-          for (int i = 0; i < G; ++i) piece_s(sb + (size_t)i * PIECE);
+          for (int i = 0; i < G; ++i) row1(src + (size_t)i * PIECE);
         }
-#else
-        const char* src = reinterpret_cast<const char*>(rp[r]) + (size_t)p0 * PIECE + lane * 16;
-        if (G == 4 && (g & 3) == 0) {
-          piece4(src);
-        } else {
-          for (int i = 0; i < G; ++i) piece(src + (size_t)i * PIECE);
-        }
-#endif
       }
     }
   }
@@ -648,7 +631,6 @@ __device__ __forceinline__ void run_loader(const EngArgs& a, const Shared& sh, i
     plan_layer(a, L, c, pos, p);
     const bool tr = lane == 0;
     trace_ev(sh, c, l, TR_CONS + 0, tr);
-    if (NHOLD && ENG_HOLD_STAGE == 0) sh.ctl[C_LSTAGE] = (uint32_t)(l + 1);
 #if ENG_QKV_HOLD
     if (const int n_held = qkv_held(a, (p.q1 - p.q0) + 2 * (p.k1 - p.k0))) {  // the list without its last n_held units
       const int n_s = (p.q1 - p.q0) + 2 * (p.k1 - p.k0) - n_held;
@@ -675,13 +657,8 @@ __device__ __forceinline__ void run_loader(const EngArgs& a, const Shared& sh, i
         const bf16_t* kb = L.ck + ring0 + (size_t)p.s_begin * DH;
         const bf16_t* vb = L.cv + ring0 + (size_t)p.s_begin * DH;
         for (int j = 0; j < p.n_att; j += 4) {
-#if ENG_SADDR
-          ld.piece4_s(reinterpret_cast<const char*>(kb) + (size_t)j * PIECE);
-          ld.piece4_s(reinterpret_cast<const char*>(vb) + (size_t)j * PIECE);
-#else
-          ld.piece4(reinterpret_cast<const char*>(kb) + (size_t)j * PIECE + lane * 16);
-          ld.piece4(reinterpret_cast<const char*>(vb) + (size_t)j * PIECE + lane * 16);
-#endif
+          ld.row4(ld.lane_src(kb) + (size_t)j * PIECE);
+          ld.row4(ld.lane_src(vb) + (size_t)j * PIECE);
         }
       } else {
         const size_t base = ring0 + (lane & 15) * 8;
@@ -1367,7 +1344,7 @@ __device__ __forceinline__ void run_consumer(const EngArgs& a, const Shared& sh,
       if (a.emb) {
         long id = (long)a.ids[0];
         if (id < 0 || id >= a.V) {  // the reference's nn.Embedding raises IndexError: flagged for the host, row clamped
-          if (c == 0 && w == 0 && lane == 0) atomicMax((uint32_t*)a.ctrl + G_BADID, 1u);
+          if (c == 0 && w == 0 && lane == 0) atomicMax((uint32_t*)a.ctrl + CTRL_BAD_ID, 1u);
           id = id < 0 ? 0 : a.V - 1;
         }
         hin = a.emb + (size_t)id * a.D;
@@ -1392,11 +1369,11 @@ __device__ __forceinline__ void run_consumer(const EngArgs& a, const Shared& sh,
       // ~1 us later) it is complete on a healthy chip and the wait is one L2 read.
       if (w == 0) {
         uint32_t polls = 0;
-        while ((int)(__hip_atomic_load(sh.ctrl + G_ARRIVE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - arrive_target) < 0) {
+        while ((int)(__hip_atomic_load(sh.ctrl + CTRL_ARRIVE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - arrive_target) < 0) {
           __builtin_amdgcn_s_sleep(8);
           if (sh.ctl[C_ABORT] || ++polls >= ARRIVE_POLLS) {
             raise_abort(sh, 0x700);
-            if (c == 0 && lane == 0 && sh.ctrl[G_SABOTAGE] != 0) sh.ctrl[G_SABOTAGE] -= 1;  // (every workgroup read it at entry)
+            if (c == 0 && lane == 0 && sh.ctrl[CTRL_SABOTAGE] != 0) sh.ctrl[CTRL_SABOTAGE] -= 1;  // (every workgroup read it at entry)
             break;
           }
         }
@@ -1661,7 +1638,7 @@ __device__ __forceinline__ void run_consumer(const EngArgs& a, const Shared& sh,
     sh.ctl[C_GATHERING] = GATHER_FLAG(16);
     cs.norm_load_granules(xr, G + a.g_h1, a.D, tag_of(l, 4));
     sh.ctl[C_GATHERING] = 0;
-#if ENG_QKV_HOLD == 2
+#if ENG_QKV_HOLD
     if (MOE && w == 0) sh.ctl[C_HGO] = (uint32_t)(l + 1);
 #endif
     trace_ev(sh, c, l, 12, trc);
@@ -1838,8 +1815,8 @@ __device__ __forceinline__ void run_consumer(const EngArgs& a, const Shared& sh,
   // greedy_tok back in as ids - is written here, after the last all-to-all of the step: every workgroup read those words
   // at its entry, long before any workgroup can pass that edge.  An aborted step commits nothing.
   if (a.commit && c == 0 && w == 0 && lane == 0 && !sh.ctl[C_ABORT] &&
-      __hip_atomic_load(sh.ctrl + G_STATUS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-    const uint32_t step = sh.ctrl[G_STEPS];
+      __hip_atomic_load(sh.ctrl + CTRL_STATUS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
+    const uint32_t step = sh.ctrl[CTRL_STEPS];
     if (greedy_valid) {
       a.greedy_tok[0] = greedy_token;
       a.greedy_lp[0] = greedy_logprob;
@@ -1856,9 +1833,9 @@ __device__ __forceinline__ void run_consumer(const EngArgs& a, const Shared& sh,
       a.tok_seq[0] = 0;
       a.tok_pos[0] = pos;
     }
-    sh.ctrl[G_STEPS] = step + 1;
-    sh.ctrl[G_ARRIVE] = 0;  // every workgroup of this launch has been counted and the next launch has not begun: no wrap
-    __hip_atomic_store(sh.ctrl + G_EPOCH, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    sh.ctrl[CTRL_STEPS] = step + 1;
+    sh.ctrl[CTRL_ARRIVE] = 0;  // every workgroup of this launch has been counted and the next launch has not begun: no wrap
+    __hip_atomic_store(sh.ctrl + CTRL_EPOCH, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -1936,9 +1913,8 @@ __device__ __forceinline__ void run_qkv_holder(const EngArgs& a, const Shared& s
     if (l + 1 < a.n_layers) {
       if (l >= 0) {
         spins = 0;
-        // ENG_QKV_HOLD = 1: the loader has issued layer l's Wo rows (it flushes and waits for the router next); 2: this workgroup
-        // has gathered h1 - the attention block's sweeps are over, the router's arithmetic begins
-        while (sh.ctl[ENG_QKV_HOLD == 2 ? C_HGO : C_LSTAGE] < (uint32_t)(l + 1))
+        // this workgroup has gathered h1 - the attention block's sweeps are over, the router's arithmetic begins
+        while (sh.ctl[C_HGO] < (uint32_t)(l + 1))
           if (!spin_ok(sh, spins, 0x600)) return;
       }
       const EngLayer& L = a.L[l + 1];
@@ -2034,9 +2010,8 @@ __device__ __forceinline__ void run_qkv_holder1(const EngArgs& a, const Shared& 
     if (l + 1 < a.n_layers) {
       if (l >= 0) {
         spins = 0;
-        // ENG_QKV_HOLD = 1: the loader has issued layer l's Wo rows (it flushes and waits for the router next); 2: this workgroup
-        // has gathered h1 - the attention block's sweeps are over, the router's arithmetic begins
-        while (sh.ctl[ENG_QKV_HOLD == 2 ? C_HGO : C_LSTAGE] < (uint32_t)(l + 1))
+        // this workgroup has gathered h1 - the attention block's sweeps are over, the router's arithmetic begins
+        while (sh.ctl[C_HGO] < (uint32_t)(l + 1))
           if (!spin_ok(sh, spins, 0x600)) return;
       }
       const EngLayer& L = a.L[l + 1];
@@ -2222,13 +2197,13 @@ __global__ __launch_bounds__(NTHREADS, 1) void decode_engine_kernel(const EngArg
 
   // A workspace whose status word is raised is poisoned until the host has dealt with it (Transformer._recover_engine):
   // later launches leave at once, before any side effect - the device state stays the one of the first failed step.
-  if (__hip_atomic_load(sh.ctrl + G_STATUS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;
+  if (__hip_atomic_load(sh.ctrl + CTRL_STATUS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;
   // The step prepares itself (round 2 ran a decode_prep kernel first): position = kv_seqlens[0], batch row 0, tags of
   // epoch + 1.  Workgroup 0 commits position + 1 / epoch + 1 at the very end (run_consumer), so a launch that does not
   // complete leaves both untouched; the launches of one step (> 32 layers) all see the same values.
   const int pos = (int)a.kv_seqlens[0];
   const int seq = 0;
-  const uint32_t epoch = (__hip_atomic_load(sh.ctrl + G_EPOCH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u) & 0xfffffu;
+  const uint32_t epoch = (__hip_atomic_load(sh.ctrl + CTRL_EPOCH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u) & 0xfffffu;
   if (w == NCONS) run_loader<MOE>(a, sh, c, lane, pos, seq);
 #if ENG_QKV_HOLD
 #if ENG_WIDE == 1
@@ -2246,17 +2221,17 @@ __global__ __launch_bounds__(NTHREADS, 1) void decode_engine_kernel(const EngArg
     uint32_t arrive_target = 0;
     if (w == 0) {
       uint32_t old = 0;
-      if (lane == 0) old = __hip_atomic_fetch_add(sh.ctrl + G_ARRIVE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (lane == 0) old = __hip_atomic_fetch_add(sh.ctrl + CTRL_ARRIVE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       old = (uint32_t)__builtin_amdgcn_readfirstlane((int)old);
       arrive_target = (old / (uint32_t)a.NB + 1u) * (uint32_t)a.NB;
       // test hook: wait for one workgroup more than exist - the gate fails exactly as it would with one missing
-      if (__hip_atomic_load(sh.ctrl + G_SABOTAGE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) arrive_target += 1u;
+      if (__hip_atomic_load(sh.ctrl + CTRL_SABOTAGE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) arrive_target += 1u;
     }
     run_consumer<R, MOE, ALL4>(a, sh, c, w, lane, pos, seq, epoch, arrive_target);
   }
   // launches completed by the engine (one per <= 32 layers of a step): how a caller tells which path ran
   if (c == 0 && threadIdx.x == 0 && !sh.ctl[C_ABORT])
-    __hip_atomic_fetch_add(sh.ctrl + G_LAUNCHES, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(sh.ctrl + CTRL_LAUNCHES, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 }  // namespace
@@ -2422,7 +2397,7 @@ int engine_census(int dev, int nb, uint32_t* ctrl, hipStream_t s) {
     snprintf(g_census_why, sizeof(g_census_why), "occupancy query: %d workgroups of %d threads + %d B LDS per CU", per_cu, NTHREADS, LDS_TOTAL);
     return g_census[dev] = -1;
   }
-  uint32_t* words = ctrl + 8;  // two spare control words of the caller's workspace (the ABI never allocates)
+  uint32_t* words = ctrl + CTRL_CENSUS0;  // two spare control words of the caller's workspace (the ABI never allocates)
   uint32_t host[2] = {0, 0};
   bool ok = hipMemsetAsync(words, 0, 8, s) == hipSuccess;
   if (ok) {

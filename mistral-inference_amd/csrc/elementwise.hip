@@ -117,9 +117,9 @@ __global__ void decode_prep_kernel(int64_t* kv_seqlens, int32_t* q_start, int32_
                                    int32_t* tok_pos, int B, uint32_t* engine_ctrl) {
   const int b = threadIdx.x;
   if (b == 0 && engine_ctrl) {
-    engine_ctrl[0] += 1;
-    engine_ctrl[2] = 0;
-    engine_ctrl[5] += 1;  // decode steps started on this workspace (index + 1 into the greedy history ring)
+    engine_ctrl[CTRL_EPOCH] += 1;
+    engine_ctrl[CTRL_ABORT] = 0;
+    engine_ctrl[CTRL_STEPS] += 1;  // decode steps started on this workspace (index + 1 into the greedy history ring)
   }
   if (b < B) {
     const int p = (int)kv_seqlens[b];
@@ -141,9 +141,9 @@ __global__ __launch_bounds__(256) void decode_prep_embedding_kernel(int64_t* kv_
   const int t = blockIdx.x;
   if (threadIdx.x == 0) {
     if (t == 0 && engine_ctrl) {
-      engine_ctrl[0] += 1;
-      engine_ctrl[2] = 0;
-      engine_ctrl[5] += 1;
+      engine_ctrl[CTRL_EPOCH] += 1;
+      engine_ctrl[CTRL_ABORT] = 0;
+      engine_ctrl[CTRL_STEPS] += 1;
     }
     const int p = (int)kv_seqlens[t];
     kv_before[t] = p;
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void decode_prep_embedding_kernel(int64_t* kv_
     kv_seqlens[t] = p + 1;
     if (t == 0) q_start[B] = B;
   }
-  const long id = checked_id(ids[t], vocab, t, engine_ctrl ? engine_ctrl + 3 : nullptr);
+  const long id = checked_id(ids[t], vocab, t, engine_ctrl ? engine_ctrl + CTRL_BAD_ID : nullptr);
   const bf16_t* src = table + (size_t)id * D;
   bf16_t* dst = out + (size_t)t * D;
   for (int p = threadIdx.x; p < (D >> 3); p += 256) st16(dst + p * 8, ld16(src + p * 8));
@@ -236,7 +236,7 @@ __global__ __launch_bounds__(1024) void greedy_rows_kernel(const float* logits, 
     tok[b] = I;
     lp[b] = l;
     if (hist_tok && hist_len > 0) {
-      const uint32_t step = (ctrl[5] - 1u) % (uint32_t)hist_len;
+      const uint32_t step = (ctrl[CTRL_STEPS] - 1u) % (uint32_t)hist_len;
       hist_tok[(size_t)step * B + b] = I;
       hist_lp[(size_t)step * B + b] = l;
     }
@@ -244,10 +244,10 @@ __global__ __launch_bounds__(1024) void greedy_rows_kernel(const float* logits, 
 }
 
 __global__ void engine_ctrl_reset_kernel(uint32_t* ctrl) {
-  ctrl[0] += 16;  // tags of the failed step (epoch + 1) can never match again
-  ctrl[1] = 0;
-  ctrl[2] = 0;
-  ctrl[6] = 0;
+  ctrl[CTRL_EPOCH] += 16;  // tags of the failed step (epoch + 1) can never match again
+  ctrl[CTRL_STATUS] = 0;
+  ctrl[CTRL_ABORT] = 0;
+  ctrl[CTRL_ARRIVE] = 0;
 }
 
 // out = bf16(a + b) (transformer_layers.py:168 for the MoE prefill path)

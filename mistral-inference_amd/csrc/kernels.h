@@ -163,6 +163,23 @@ inline int device_cus() {
   return cus;
 }
 
+// ---------------------------------------------------------------------------------------------- workspace control words
+// The first 32-bit words of a workspace (mi_forward's and the generic path's alike), shared by the launch path's kernels, the
+// persistent decode engine and the host (mi_decode_engine_status copies the eight words below CTRL_CENSUS0).  mistral_inference/_hip.py names them in
+// the same order (CTRL_WORDS; tests/test_ctrl_words.py holds the two together).
+enum : int {
+  CTRL_EPOCH = 0,     // step epoch of the persistent decode engine (granule tags), bumped by the step's first kernel
+  CTRL_STATUS = 1,    // sticky engine status: the code of the first timed-out wait (mi_decode_engine_reset clears it)
+  CTRL_ABORT = 2,     // per-step abort broadcast
+  CTRL_BAD_ID = 3,    // 1 + the index of an out-of-range token id (atomic max)
+  CTRL_LAUNCHES = 4,  // engine launches completed
+  CTRL_STEPS = 5,     // decode steps committed (index + 1 into the greedy history ring)
+  CTRL_ARRIVE = 6,    // workgroup arrivals of the running engine launch
+  CTRL_SABOTAGE = 7,  // test hook: engine launches that shall fail their residency gate (mi_debug_engine_sabotage)
+  CTRL_CENSUS0 = 8,   // two spare words that the engine's residency census borrows
+  CTRL_CENSUS1 = 9
+};
+
 // ---------------------------------------------------------------------------------------------- elementwise
 hipError_t launch_gelu(void* x, int ldx, int T, int N, hipStream_t s);
 // log-softmax gather: out[m] = x_t - logsumexp(row m), from per-tile (max, sum-exp) partials or from a full logits row
@@ -176,8 +193,8 @@ hipError_t launch_rope(void* qkv, int ld, int T, int H, int Hkv, int Dh, const f
                        hipStream_t s);
 hipError_t launch_kv_write(void* ck, void* cv, int W, const void* k, const void* v, int ld, int T, int kv_dim,
                            const int32_t* tok_seq, const int32_t* tok_pos, const int32_t* q_start, int kv_layout, int Dh, hipStream_t s);
-// engine_ctrl (nullable): control words of the workspace - [0] step epoch of the persistent decode engine (incremented
-// here), [2] its per-step abort broadcast (cleared here), [3] out-of-range token id flag (launch_embedding)
+// engine_ctrl (nullable): control words of the workspace - CTRL_EPOCH and CTRL_STEPS are incremented here, CTRL_ABORT is cleared
+// here, CTRL_BAD_ID receives the out-of-range token id flag (launch_embedding)
 hipError_t launch_decode_prep(int64_t* kv_seqlens, int32_t* q_start, int32_t* kv_before, int32_t* tok_seq,
                               int32_t* tok_pos, int B, uint32_t* engine_ctrl, hipStream_t s);
 hipError_t launch_decode_prep_embedding(int64_t* kv_seqlens, int32_t* q_start, int32_t* kv_before, int32_t* tok_seq,
@@ -185,13 +202,13 @@ hipError_t launch_decode_prep_embedding(int64_t* kv_seqlens, int32_t* q_start, i
                                         int vocab, uint32_t* engine_ctrl, hipStream_t s);
 hipError_t launch_add_rows(void* out, const void* a, const void* b, size_t n, hipStream_t s);
 // Greedy sampling of B logits rows (generate.py:124-136 at temperature 0): tok[b] = first index of the row maximum
-// (torch.argmax), lp[b] = log_softmax(row)[tok[b]]; also stored at entry (ctrl[5] - 1) % hist_len of the [hist_len, B]
-// history rings when given (ctrl[5] = decode steps started on this workspace, advanced by decode_prep).
+// (torch.argmax), lp[b] = log_softmax(row)[tok[b]]; also stored at entry (ctrl[CTRL_STEPS] - 1) % hist_len of the
+// [hist_len, B] history rings when given (CTRL_STEPS = decode steps started on this workspace, advanced by decode_prep).
 hipError_t launch_greedy_rows(const float* logits, int ld, int B, int V, int64_t* tok, float* lp, int64_t* hist_tok,
                               float* hist_lp, int hist_len, const uint32_t* ctrl, hipStream_t s);
 // Nucleus sampling of B logits rows (generate.py:151-170 + the logprob of :134-136), csrc/sampling.hip: tok[b] drawn from
 // softmax(row / temperature) restricted to the top-p prefix; uniforms (nullable): u[b] in [0, 1) instead of the Philox draw
-// keyed by (seed; offset + ctrl[5], b); history rings as launch_greedy_rows.
+// keyed by (seed; offset + ctrl[CTRL_STEPS], b); history rings as launch_greedy_rows.
 hipError_t launch_sample_top_p(const float* logits, int ld, int B, int V, float temperature, float top_p, uint64_t seed,
                                uint64_t offset, const float* uniforms, int64_t* tok, float* lp, int64_t* hist_tok, float* hist_lp,
                                int hist_len, const uint32_t* ctrl, hipStream_t s);
@@ -239,14 +256,14 @@ struct EngArgs {
   int32_t *q_start, *kv_before, *tok_seq, *tok_pos;  // the step's metadata words, written at commit for callers (launch-path layout)
   int64_t* greedy_tok;    // [1] argmax of the logits (first maximal index), or nullptr
   float* greedy_lp;       // [1] log_softmax(logits)[argmax]
-  int64_t* hist_tok;      // [hist_len] ring indexed by the step counter (ctrl[5]) or nullptr
+  int64_t* hist_tok;      // [hist_len] ring indexed by the step counter (CTRL_STEPS) or nullptr
   float* hist_lp;
   const float* rope_cs;
   const bf16_t* final_norm;
   const bf16_t* output;
   float* logits;
   uint64_t* gran;         // granule regions
-  uint32_t* ctrl;         // [0] epoch, [1] sticky status, [2] per-step abort
+  uint32_t* ctrl;         // the workspace control words (CTRL_*)
   uint32_t g_h, g_qkv, g_att, g_h1, g_hid, g_hid2, g_part, g_amax;
   int E;                  // experts (0: dense).  MoE layers: EngLayer.w1 = gate [E, D], .w2 = device table [E][3] of (w1, w2, w3)
   unsigned long long* trace;  // optional timeline buffer (debug)

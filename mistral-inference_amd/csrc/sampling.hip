@@ -259,7 +259,7 @@ __global__ __launch_bounds__(ST) void sample_top_p_kernel(const float* logits, i
   // step count - and poisons the workspace until the host has re-run the step on the launch path (GreedySession._recover).
   // Drawing from whatever the logits buffer holds would overwrite `tok`, which is the NEXT step's input id and the id the
   // recovery re-runs from.  (The stand-alone mi_sample_top_p passes no control block.)
-  if (ctrl && ctrl[1] != 0) return;
+  if (ctrl && ctrl[CTRL_STATUS] != 0) return;
   const int b = blockIdx.x;
   Row r;
   r.x = logits + (size_t)b * ld;
@@ -312,7 +312,7 @@ __global__ __launch_bounds__(ST) void sample_top_p_kernel(const float* logits, i
     u = (double)uniforms[b];
   } else {
     uint32_t rnd[4];
-    const unsigned long long step = ctrl ? (unsigned long long)ctrl[5] : 0ull;
+    const unsigned long long step = ctrl ? (unsigned long long)ctrl[CTRL_STEPS] : 0ull;
     Philox::draw(seed, offset + step, (uint32_t)b, rnd);
     u = ((double)rnd[0] * 4294967296.0 + (double)rnd[1]) * (1.0 / 18446744073709551616.0);
   }
@@ -352,7 +352,7 @@ __global__ __launch_bounds__(ST) void sample_top_p_kernel(const float* logits, i
           tok[b] = i;
           lp[b] = l;
           if (hist_tok && hist_len > 0 && ctrl) {
-            const uint32_t step = (ctrl[5] - 1u) % (uint32_t)hist_len;
+            const uint32_t step = (ctrl[CTRL_STEPS] - 1u) % (uint32_t)hist_len;
             hist_tok[(size_t)step * B + b] = i;
             hist_lp[(size_t)step * B + b] = l;
           }

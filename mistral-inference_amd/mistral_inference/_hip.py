@@ -540,12 +540,31 @@ def set_decode_engine(enabled: bool) -> bool:
     return bool(lib().mi_set_decode_engine(1 if enabled else 0))
 
 
+# The workspace's control words in order: word i is csrc/kernels.h's CTRL_<NAME> = i (tests/test_ctrl_words.py holds the two together).
+CTRL_WORDS = ("epoch", "status", "abort", "bad_id", "launches", "steps", "arrive", "sabotage", "census0", "census1")
+_STATUS_KEYS = {"launches": "engine_launches", "arrive": "arrivals"}  # decode_engine_status reports these two under older names
+
+
 def decode_engine_status(workspace: torch.Tensor) -> dict:
     """Control words of the persistent decode engine in `workspace` (synchronises the current stream)."""
     st = (C.c_uint32 * 8)()
     check(lib().mi_decode_engine_status(workspace.data_ptr(), stream_ptr(workspace.device), st), "mi_decode_engine_status")
-    return {"epoch": int(st[0]), "status": int(st[1]), "abort": int(st[2]), "bad_id": int(st[3]), "engine_launches": int(st[4]),
-            "steps": int(st[5]), "arrivals": int(st[6])}
+    return {_STATUS_KEYS.get(name, name): int(st[i]) for i, name in enumerate(CTRL_WORDS[:CTRL_WORDS.index("sabotage")])}
+
+
+def _ctrl_word(workspace: torch.Tensor, name: str) -> torch.Tensor:
+    i = CTRL_WORDS.index(name)
+    return workspace[4 * i:4 * i + 4]
+
+
+def ctrl_clear(workspace: torch.Tensor, name: str) -> None:
+    """Zero one control word of a (uint8) workspace tensor, on the current stream."""
+    _ctrl_word(workspace, name).zero_()
+
+
+def ctrl_set(workspace: torch.Tensor, name: str, value: int) -> None:
+    """Set one control word of a (uint8) workspace tensor to `value` (31 bits), on the current stream."""
+    _ctrl_word(workspace, name).view(torch.int32).fill_(int(value) & 0x7FFFFFFF)
 
 
 def debug_engine_sabotage(workspace: torch.Tensor, launches: int) -> None:

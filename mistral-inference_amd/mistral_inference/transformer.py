@@ -211,7 +211,7 @@ class HipStackBackend:
             return
         st = _hip.decode_engine_status(self._workspace)
         if st["bad_id"]:
-            self._workspace[12:16].zero_()
+            _hip.ctrl_clear(self._workspace, "bad_id")
             raise IndexError(f"index out of range in self (token {st['bad_id'] - 1} of a forward call)")
         if st["status"]:
             # the raised word makes every later engine launch on this workspace leave at once: clear it now that it is reported
@@ -240,10 +240,10 @@ class HipStackBackend:
         self._get_workspace(model, self.plan(model), B, B, max(cache.cache_sizes))  # (a decode step has T == B rows)
 
     def session_rewind(self, steps: int) -> None:
-        """Set the workspace's decode-step counter (status word 5: the row of the greedy history ring and the Philox offset of the
-        NEXT step) - GreedySession's lock-step rollback re-runs steps whose samples must land where the first attempt's would."""
+        """Set the workspace's decode-step counter (control word `steps`: the row of the greedy history ring and the Philox offset
+        of the NEXT step) - GreedySession's lock-step rollback re-runs steps whose samples must land where the first attempt's would."""
         assert self._workspace is not None
-        self._workspace[20:24].view(torch.int32).fill_(int(steps) & 0x7FFFFFFF)
+        _hip.ctrl_set(self._workspace, "steps", steps)
 
     def session_disable_engine(self) -> None:
         """After a raised engine status: clear the word (it poisons the workspace) and take the launch path for the rest of this

@@ -15,14 +15,12 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "mistral-i
 sys.path.insert(0, ROOT)
 import build_native as b  # noqa: E402
 
+# Every -D macro named in the three tables below is one that its source file reads (tests/test_variant_flags.py): a switch that
+# leaves the source takes its entries with it (scripts/probes/*.patch keep such experiments).
 VARIANTS = {
-    "asm_dma1": ("-DENG_ASM_DMA=1",),             # the loader's DMA through the builtin (hipcc then decides where vmcnt waits go)
     "trace0": ("-DENG_TRACE=0",),                 # no stamp sites: measured 17 % SLOWER (they pin the compiler's scheduling)
     "trace2": ("-DENG_TRACE=2",),                 # stamp sites replaced by bare compiler / scheduling barriers
     "all4_0": ("-DENG_ALL4=0",),                  # the generic-group path compiled into every instantiation (round-2 form)
-    "cbar_flags": ("-DENG_CBAR_FLAGS=1",),        # consumer barrier on per-wave flag words (measured +10..20 us per step)
-    "sparse_poll": ("-DENG_SPARSE_POLL=1",),      # re-poll only the granules that were missing (+25 us)
-    "lean_barriers": ("-DENG_LEAN_BARRIERS=1",),  # attn sweep starts while wave 0 still merges (+45 us)
     "holders0": ("-DENG_HOLDERS=0",),             # no holder waves (5-wave workgroups)
     # compiler-flag lottery (the kernel's speed is a chaotic function of its code: profiles/EXPERIMENTS.md)
     # (the shipped engine build uses -amdgpu-sched-strategy=max-memory-clause: build_native.PER_FILE_FLAGS; set
@@ -64,13 +62,6 @@ FILE_VARIANTS = {
     # the stamp sites again, as a one-object variant (round 4: PMC counters of both builds, scripts/engine_pmc.sh)
     "e_trace0": ("decode_engine.hip", ("-DENG_TRACE=0",)),
     "e_trace2": ("decode_engine.hip", ("-DENG_TRACE=2",)),
-    # which stamp sites matter (consumer events 0-17, loader events 18-25; bit set = site compiled in)
-    "e_mask_loader": ("decode_engine.hip", ("-DENG_TRACE_MASK=0x03fc0000u",)),
-    "e_mask_cons": ("decode_engine.hip", ("-DENG_TRACE_MASK=0x0003ffffu",)),
-    "e_mask_cons_lo": ("decode_engine.hip", ("-DENG_TRACE_MASK=0x000001ffu",)),
-    "e_mask_cons_hi": ("decode_engine.hip", ("-DENG_TRACE_MASK=0x0003fe00u",)),
-    "e_mask_even": ("decode_engine.hip", ("-DENG_TRACE_MASK=0x01555555u",)),
-    "e_mask_odd": ("decode_engine.hip", ("-DENG_TRACE_MASK=0x02aaaaaau",)),
     # launch path (Nemo dims, batch > 1): the same strategy for the GEMV / decode-attention sources
     "l_gemv_mmc": ("gemv.hip", ("-mllvm", "-amdgpu-sched-strategy=max-memory-clause")),
     "l_attn_mmc": ("attn_decode.hip", ("-mllvm", "-amdgpu-sched-strategy=max-memory-clause")),
@@ -128,13 +119,11 @@ ENGINE_SLOTS = {
     "hid_prio2": ("-DENG_ABORT_RARE=1", "-DENG_CONS_PRIO=2", "-DENG_HOLD_STAGE=2", "-DENG_SADDR=2", "-DENG_TRACE=0", "-DENG_NOSTOP=32"),
     "ns_ce_hid": _NS + _CE + ("-DENG_NOSTOP=32",),                  # the shipped flags WITH stamp sites, clean by the static check: timelines
     "nst_hid_stage3": _AP + ("-DENG_SADDR=2", "-DENG_TRACE=0", "-DENG_NOSTOP=32"),
-    "nst_hid_hold4": _NS + ("-DENG_TRACE=0", "-DENG_NOSTOP=32", "-DENG_SLP_HOLD=4"),
     # round 6 (the K/V-phase experiments of this round - asm K/V pieces, fine / tight publication, a reordered stream - are kept as
     # scripts/probes/decode_engine_round6_kv_experiments.patch; what shipped is the head-major ring layout)
     "ce": _N0 + _CE,                                                # + a modelled wait at the loader's entry
     "ce_hid": _N0 + _CE + ("-DENG_NOSTOP=32",),
     "ns_ce": _NS + _CE,                                             # (with the stamp sites: timelines)
-    "ns_hid": _NS + ("-DENG_NOSTOP=32",),
     # round 7: the holders' fetch tied to the loader's ring-full waits (ENG_HOLD_GATE; the fourth held unit, ENG_HOLD_SPLIT, is kept as
     # scripts/probes/decode_engine_round7_hold_split.patch); the t_* slots keep the stamp sites and time the loader's ring-full waits
     "r7_ce": _N0 + _CE + ("-DENG_NOSTOP=32",),
@@ -199,7 +188,7 @@ if __name__ == "__main__":
         print(build_engine_slots(sys.argv[sys.argv.index("engine_slots") + 1:]), flush=True)
         sys.exit(0)
     for name, (src, flags) in FILE_VARIANTS.items():
-        if name in sys.argv[1:] or "gemm" in sys.argv[1:] and name.startswith("g_") or "attn" in sys.argv[1:] and name.startswith("a_") or "engine_flags" in sys.argv[1:] and name.startswith("e_") and not name.startswith("e_mask") or "engine_masks" in sys.argv[1:] and name.startswith("e_mask") or "launch_flags" in sys.argv[1:] and name.startswith("l_"):
+        if name in sys.argv[1:] or "gemm" in sys.argv[1:] and name.startswith("g_") or "attn" in sys.argv[1:] and name.startswith("a_") or "engine_flags" in sys.argv[1:] and name.startswith("e_") or "launch_flags" in sys.argv[1:] and name.startswith("l_"):
             print(name, build_file_variant(name, src, flags), flush=True)
     for name, flags in VARIANTS.items():
         if name not in sys.argv[1:] and "engine" not in sys.argv[1:]:
