@@ -335,6 +335,56 @@ size_t mi_workspace_bytes(const mi_model_t* model, int T, int B, int max_cache_s
  * decode engine - step epoch, status - and the engine's hand-off granules carry tags that must never match garbage). */
 int mi_forward(const mi_model_t* model, const mi_batch_t* batch, mi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Weight-only FP8 (OCP e4m3, what torch.float8_e4m3fn and safetensors F8_E4M3 store) on dense bf16 models.  Additive to ABI
+ * v9: no struct above changes and no entry point above changes meaning; the presence of these symbols is the feature test.
+ * The reference has no quantised linear: a quantised linear here stands for the nn.Linear of transformer_layers.py:51-54,
+ * 101-103 on the real-valued weight  W[r, k] = scale[r] * e4m3(w[r, k])  (w: bytes [out, in]; scale: fp32 [out], positive, finite).
+ *   M <= 8:  acc[r] = sum_k e4m3(w[r, k]) * x[k] in fp32, y = acc * scale[r] in fp32, and y enters the epilogues of mi_linear /
+ *            mi_qkv_rope_kvwrite exactly where acc enters them there (csrc/gemv_w8.hip; activations, norms and rings stay bf16);
+ *   M  > 8:  W' = bf16(scale[r] * e4m3(w[r, k])) is written into a scratch and mi_linear's MFMA GEMM runs on W'.
+ * With power-of-two scales W' is exact and both forms are the bf16 model on the dequantised weights up to fp32 summation order;
+ * with other scales the two forms differ by one bf16 rounding of each weight.  K must be a multiple of 16 (MI_ERR_SHAPE).
+ * Embeddings, norms, the LM head, the MoE gate and the K/V rings stay bf16.
+ * ---------------------------------------------------------------------------------------------- */
+#define MI_W8_FP8_E4M3 1
+
+/* mi_linear (nn.Linear, transformer_layers.py:66,93,105-106) with w[i] read as e4m3 bytes [n_rows[i], K] and scale[i] their fp32
+ * row scales [n_rows[i]].  MI_EPI_STORE / MI_EPI_RESIDUAL / MI_EPI_SWIGLU (MI_EPI_LOGITS: MI_ERR_UNSUPPORTED - the LM head is
+ * not quantised).  M > 8 needs `scratch` of at least mi_linear_w8_scratch_bytes(M, K, n_rows, epilogue) bytes (0 for M <= 8,
+ * where scratch may be NULL); norm_w as mi_linear (M <= 8 only). */
+size_t mi_linear_w8_scratch_bytes(int M, int K, const int n_rows[3], int epilogue);
+int mi_linear_w8(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
+                 int epilogue, const void* residual, const void* norm_w, float eps, const float* const scale[3], void* scratch,
+                 size_t scratch_bytes, mi_stream_t stream);
+
+/* mi_qkv_rope_kvwrite (transformer_layers.py:66-70,165 + rope.py:13-23 + cache.py:83-92, T <= 8) with wq / wk / wv read as e4m3
+ * bytes and sq / sk / sv their fp32 row scales. */
+int mi_qkv_rope_kvwrite_w8(void* qkv, int ldo, const void* x, int ldx, int T, int D, const void* wq, const void* wk,
+                           const void* wv, const float* sq, const float* sk, const float* sv, int n_heads, int n_kv_heads,
+                           int head_dim, const void* norm_w, float eps, const float* rope_cs, int rope_len,
+                           const int32_t* tok_pos, const int32_t* tok_seq, void* cache_k, void* cache_v, int W, int kv_layout,
+                           mi_stream_t stream);
+
+/* Row scales of the seven linears of one layer (transformer_layers.py:51-54,101-103): DEVICE fp32 [rows of that linear]. */
+typedef struct mi_w8_layer {
+  const float *wq, *wk, *wv, *wo, *w1, *w2, *w3;
+} mi_w8_layer_t;
+/* The quantisation of a model's layers: beside an mi_model_t whose seven linear pointers per layer then point to e4m3 bytes. */
+typedef struct mi_w8_model {
+  int32_t format;               /* MI_W8_FP8_E4M3 */
+  const mi_w8_layer_t* layers;  /* host array [n_layers] */
+} mi_w8_model_t;
+
+/* mi_workspace_bytes / mi_forward (Transformer.forward_partial, transformer.py:163-219, + the LM head, :229-242) on a model
+ * whose linears are quantised as `w8` describes.  w8 == NULL: exactly mi_workspace_bytes / mi_forward.  T <= 8: the six launches
+ * per layer of mi_forward on the e4m3 GEMV kernels.  T > 8: per linear group (q|k|v, wo, w1|w3, w2) one dequantisation launch
+ * into a scratch carved behind everything else in the workspace (the largest group, only for such a model and such a T), then
+ * mi_forward's GEMM launch.  Always the launch path: the persistent engine declines.  Dense models without un-merged LoRA only
+ * (num_experts > 0 or lora_rank > 0: MI_ERR_UNSUPPORTED); dim, hidden_dim and n_heads * head_dim multiples of 16. */
+size_t mi_workspace_bytes_w8(const mi_model_t* model, const mi_w8_model_t* w8, int T, int B, int max_cache_size);
+int mi_forward_w8(const mi_model_t* model, const mi_w8_model_t* w8, const mi_batch_t* batch, mi_stream_t stream);
+
 /* ABI v6 - storage dtypes other than bf16 (reference transformer.py:303,338: `from_folder(dtype=...)` keeps the dtype the
  * caller asks for; the reference's own tests build fp32 models, tests/test_generate.py:51,100) and bf16 models of a shape
  * mi_forward declines with MI_ERR_SHAPE (head_dim != 128, more than 16 experts, top_k = 3).  Same structs, same metadata

@@ -95,6 +95,7 @@ template <class Try>
 bool engine_route(int variant, bool nemo_opt_in, const EngineBuild* slot, const EngProblem& pr, Try&& try_build) {
   const bool moe = pr.E > 0;
   if (pr.lora_rank > 0) return false;  // un-merged LoRA adapters: no engine build carries them, the launch path does (lora.hip)
+  if (pr.w8) return false;             // e4m3 weight bytes: no engine build reads them, the launch path does (gemv_w8.hip)
   auto takes = [&](int b) { return kBuilds[b]->applicable(pr, nullptr, 0); };
   if (slot && slot->applicable(pr, nullptr, 0) && try_build(*slot)) return true;
   // the dense GQA-4 headline shapes: the `next` compile (build_native.ENGINE_NEXT_FLAGS)
@@ -153,10 +154,18 @@ struct Workspace {
   int max_tiles;
   bf16_t* lora_t;    // un-merged LoRA (lora_rank > 0 only, behind everything else): t = bf16(A x)   [T, 3 * rank]
   void* lora_base;   // ... and the base products of q|k|v and w1|w3  [T, max(qkv cols, 2 F)]: fp32 holding bf16 values for T <= 8
-  size_t total;      //     (the GEMV's LOGITS form, see lora_linear), bf16 above.  Wo's and W2's base product goes to xn.
-};
+  bf16_t* w8;        // weight-only FP8 at T > 8 (behind everything else, such models only): the dequantised weights of one linear
+  size_t total;      //     group (w8_scratch_elems).  (lora_base: the GEMV's LOGITS form, see lora_linear; bf16 above 8 rows.  Wo's
+};                   //     and W2's base product goes to xn.)
 
-Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base) {
+// bf16 elements of the largest linear group a prefill dequantises at once: q|k|v, wo, w1|w3, w2
+size_t w8_scratch_elems(const mi_model_t* m) {
+  const size_t D = m->dim, F = m->hidden_dim, nq = (size_t)m->n_heads * m->head_dim, nkv = (size_t)m->n_kv_heads * m->head_dim;
+  const size_t a = (nq + 2 * nkv) * D, b = 2 * F * D;
+  return a > b ? a : b;  // (wo: D * nq <= a; w2: D * F <= b)
+}
+
+Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool w8 = false) {
   Workspace w;
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -192,6 +201,7 @@ Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base) {
     w.lora_t = (bf16_t*)take((size_t)T * 3 * m->lora_rank * 2);
     w.lora_base = take((size_t)T * wide * (T <= GEMV_MAX_T ? 4 : 2));
   }
+  w.w8 = (w8 && T > GEMV_MAX_T) ? (bf16_t*)take(w8_scratch_elems(m) * 2) : nullptr;  // (a plain model: layout and total as ever)
   w.total = off;
   return w;
 }
@@ -249,9 +259,9 @@ struct GemvKernels {
 };
 constexpr GemvKernels kGemvBf16 = {gemv_max_tokens, launch_gemv}, kGemvF16 = {gemv_max_tokens_f16, launch_gemv_f16};
 
-// GEMV over T <= 8 tokens, in passes when T * K does not fit the LDS budget.
-int gemv_passes(const GemvKernels& k, GemvArgs a, int T, hipStream_t s, const char* what) {
-  const int cap = k.max_tokens(a.K);
+// GEMV over T <= 8 tokens, in passes of at most `cap` rows when T * K does not fit the LDS budget.
+template <class Launch>
+int gemv_pass_loop(int cap, const GemvArgs& a, int T, const char* what, Launch&& launch) {
   const size_t out_elt = (a.mode == GEMV_LOGITS) ? 4 : 2;
   for (int t0 = 0; t0 < T; t0 += cap) {
     GemvArgs p = a;
@@ -261,9 +271,41 @@ int gemv_passes(const GemvKernels& k, GemvArgs a, int T, hipStream_t s, const ch
     if (a.residual) p.residual = a.residual + (size_t)t0 * a.ldo;
     if (a.tok_pos) p.tok_pos = a.tok_pos + t0;
     if (a.tok_seq) p.tok_seq = a.tok_seq + t0;
-    MI_TRY(hip_rc(k.launch(p, s), what));
+    MI_TRY(hip_rc(launch(p), what));
   }
   return MI_OK;
+}
+int gemv_passes(const GemvKernels& k, const GemvArgs& a, int T, hipStream_t s, const char* what) {
+  return gemv_pass_loop(k.max_tokens(a.K), a, T, what, [&](const GemvArgs& p) { return k.launch(p, s); });
+}
+// The third table: gemv_w8.hip, the same launches with the weight pointers read as e4m3 bytes and the row scales beside the
+// arguments (activation rows are bf16 there too: the bf16 kernels' row budget).
+struct W8Scales {
+  const float* s[3];
+};
+int gemv_passes_w8(const GemvArgs& a, const W8Scales& sc, int T, hipStream_t s, const char* what) {
+  return gemv_pass_loop(gemv_max_tokens(a.K), a, T, what, [&](const GemvArgs& p) {
+    const GemvW8Args w = {p, {sc.s[0], sc.s[1], sc.s[2]}};
+    return launch_gemv_w8(w, s);
+  });
+}
+// Dequantise up to three e4m3 matrices of K columns side by side into `out` (dense [sum of rows, K] bf16); w[i] then points at
+// the bf16 rows of matrix i.
+int dequant_group(const void* w[3], const W8Scales& sc, const int n_rows[3], int K, bf16_t* out, hipStream_t s, const char* what) {
+  DequantW8Args d;
+  memset(&d, 0, sizeof(d));
+  int n = 0;
+  for (int i = 0; i < 3; ++i) {
+    const int rows = w[i] ? n_rows[i] : 0;
+    d.w[i] = (const uint8_t*)w[i]; d.scale[i] = sc.s[i];
+    if (i == 0) d.n0 = rows;
+    if (i == 1) d.n1 = d.n0 + rows;
+    w[i] = w[i] ? (const void*)(out + (size_t)n * K) : nullptr;
+    n += rows;
+  }
+  if (!d.w[1]) d.n1 = d.n0;
+  d.N = n; d.K = K; d.out = out;
+  return hip_rc(launch_dequant_w8(d, s), what);
 }
 
 // out[M, N] = epi(a[M, K] @ w0^T (, a @ w1^T)): the plain GEMM of one weight matrix, or of W1 and W3 for GEMM_SWIGLU
@@ -784,6 +826,73 @@ int mi_qkv_rope_kvwrite(void* qkv, int ldo, const void* x, int ldx, int T, int D
   return gemv_passes(kGemvBf16, a, T, (hipStream_t)stream, "qkv gemv");
 }
 
+/* weight-only FP8 leaves (include/mistral_hip.h: MI_W8_FP8_E4M3) */
+static size_t linear_w8_rows(const int n_rows[3], const void* const w[3], int epilogue) {
+  if (epilogue == MI_EPI_SWIGLU) return 2 * (size_t)n_rows[0];
+  size_t n = 0;
+  for (int i = 0; i < 3 && (i == 0 || !w || w[i]); ++i) n += n_rows[i] > 0 ? n_rows[i] : 0;
+  return n;
+}
+size_t mi_linear_w8_scratch_bytes(int M, int K, const int n_rows[3], int epilogue) {
+  if (M <= GEMV_MAX_T || K <= 0 || !n_rows) return 0;
+  return align_up(linear_w8_rows(n_rows, nullptr, epilogue) * (size_t)K * 2);
+}
+
+int mi_linear_w8(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
+                 int epilogue, const void* residual, const void* norm_w, float eps, const float* const scale[3], void* scratch,
+                 size_t scratch_bytes, mi_stream_t stream) {
+  if (!out || !x || !w || !n_rows || !scale || !w[0] || !scale[0] || M <= 0 || K <= 0 || n_rows[0] <= 0) return fail(MI_ERR_ARG, "mi_linear_w8");
+  for (int i = 1; i < 3; ++i)
+    if (w[i] && (!scale[i] || n_rows[i] <= 0 || !w[i - 1])) return fail(MI_ERR_ARG, "mi_linear_w8: segment %d needs rows, a scale and its predecessor", i);
+  if (K % 16) return fail(MI_ERR_SHAPE, "mi_linear_w8: K = %d must be a multiple of 16 (a 16-byte piece is 16 e4m3 weights)", K);
+  if (epilogue != MI_EPI_STORE && epilogue != MI_EPI_RESIDUAL && epilogue != MI_EPI_SWIGLU)
+    return fail(MI_ERR_UNSUPPORTED, "mi_linear_w8: epilogue %d (store, residual and swiglu; the LM head is not quantised)", epilogue);
+  if (epilogue == MI_EPI_RESIDUAL && !residual) return fail(MI_ERR_ARG, "mi_linear_w8: residual epilogue without residual");
+  if (epilogue == MI_EPI_SWIGLU && (!w[1] || n_rows[0] != n_rows[1])) return fail(MI_ERR_ARG, "mi_linear_w8: swiglu needs W1, W3");
+  hipStream_t s = (hipStream_t)stream;
+  const bool swiglu = epilogue == MI_EPI_SWIGLU;
+  const int n0 = n_rows[0], n1 = n0 + (w[1] ? n_rows[1] : 0), n2 = n1 + ((!swiglu && w[2]) ? n_rows[2] : 0);
+  const W8Scales sc = {{scale[0], w[1] ? scale[1] : nullptr, (!swiglu && w[2]) ? scale[2] : nullptr}};
+  if (M <= GEMV_MAX_T) {
+    GemvArgs a = gemv_common(x, ldx, K, 0, norm_w, eps, out, ldo);
+    a.w0 = (const bf16_t*)w[0]; a.w1 = (const bf16_t*)w[1]; a.w2 = swiglu ? nullptr : (const bf16_t*)w[2]; a.residual = (const bf16_t*)residual;
+    a.mode = swiglu ? GEMV_SWIGLU : epilogue == MI_EPI_STORE ? GEMV_STORE : GEMV_RESIDUAL;
+    if (swiglu) {
+      a.N = n0; a.n0 = a.n1 = n0;
+    } else {
+      a.N = n2; a.n0 = n0; a.n1 = n1;
+    }
+    return gemv_passes_w8(a, sc, M, s, "gemv (w8)");
+  }
+  if (norm_w) return fail(MI_ERR_UNSUPPORTED, "mi_linear_w8: fused RMSNorm only on the M <= 8 path");
+  const size_t need = align_up((size_t)(swiglu ? 2 * n0 : n2) * K * 2);
+  if (!scratch || scratch_bytes < need) return fail(MI_ERR_WORKSPACE, "mi_linear_w8: scratch %zu < required %zu", scratch ? scratch_bytes : (size_t)0, need);
+  const void* wd[3] = {w[0], w[1], swiglu ? nullptr : w[2]};
+  const int nr[3] = {n0, n1 - n0, n2 - n1};
+  MI_TRY(dequant_group(wd, sc, nr, K, (bf16_t*)scratch, s, "dequant (w8)"));
+  return mi_linear(out, ldo, x, ldx, M, K, wd, n_rows, epilogue, residual, nullptr, 0.f, stream);
+}
+
+int mi_qkv_rope_kvwrite_w8(void* qkv, int ldo, const void* x, int ldx, int T, int D, const void* wq, const void* wk,
+                           const void* wv, const float* sq, const float* sk, const float* sv, int n_heads, int n_kv_heads,
+                           int head_dim, const void* norm_w, float eps, const float* rope_cs, int rope_len,
+                           const int32_t* tok_pos, const int32_t* tok_seq, void* cache_k, void* cache_v, int W, int kv_layout,
+                           mi_stream_t stream) {
+  if (!qkv || !x || !wq || !wk || !wv || !sq || !sk || !sv || !rope_cs || !tok_pos || T <= 0 || D <= 0 || rope_len <= 0 ||
+      !kv_layout_ok(kv_layout))
+    return fail(MI_ERR_ARG, "mi_qkv_rope_kvwrite_w8");
+  if (D % 16) return fail(MI_ERR_SHAPE, "mi_qkv_rope_kvwrite_w8: D = %d must be a multiple of 16 (a 16-byte piece is 16 e4m3 weights)", D);
+  if (head_dim != 128) return fail(MI_ERR_SHAPE, "head_dim must be 128");
+  if ((cache_k == nullptr) != (cache_v == nullptr) || (cache_k && W <= 0)) return fail(MI_ERR_ARG, "mi_qkv_rope_kvwrite_w8: cache");
+  if (T > GEMV_MAX_T)
+    return fail(MI_ERR_UNSUPPORTED, "mi_qkv_rope_kvwrite_w8: T = %d > %d (the prefill path is mi_rmsnorm + mi_linear_w8 + "
+                "mi_rope_inplace + mi_kv_write)", T, GEMV_MAX_T);
+  const RingWrite ring = {cache_k, cache_v, W, kv_layout};
+  const GemvArgs a = gemv_qkv_rope(x, ldx, D, norm_w, eps, wq, wk, wv, n_heads * head_dim, n_kv_heads * head_dim, qkv, ldo, rope_cs,
+                                   tok_pos, tok_seq, head_dim, cache_k ? &ring : nullptr);
+  return gemv_passes_w8(a, W8Scales{{sq, sk, sv}}, T, (hipStream_t)stream, "qkv gemv (w8)");
+}
+
 int mi_moe_experts_decode(void* out, const void* residual, const void* x, int ldx, int T, int D, int F,
                           const void* const* expert_w_dev, const int32_t* sel_idx, const float* sel_w, int top_k,
                           const void* norm_w, float eps, void* hidden_scratch, mi_stream_t stream) {
@@ -916,15 +1025,33 @@ size_t mi_workspace_bytes(const mi_model_t* model, int T, int B, int max_cache_s
   return carve(model, T, B, max_cache_size > 0 ? max_cache_size : 1, nullptr).total;
 }
 
-int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
+size_t mi_workspace_bytes_w8(const mi_model_t* model, const mi_w8_model_t* w8, int T, int B, int max_cache_size) {
+  if (!model || T <= 0 || B <= 0) return 0;
+  return carve(model, T, B, max_cache_size > 0 ? max_cache_size : 1, nullptr, w8 != nullptr).total;
+}
+
+// what a quantised model must be, by name, before any launch
+static int check_w8(const char* entry, const mi_model_t* m, const mi_w8_model_t* w8) {
+  if (w8->format != MI_W8_FP8_E4M3) return fail(MI_ERR_UNSUPPORTED, "%s: weight format %d (MI_W8_FP8_E4M3 = 1 is the only one)", entry, w8->format);
+  if (!w8->layers) return fail(MI_ERR_ARG, "%s: w8 without layer scales", entry);
+  if (m->num_experts > 0) return fail(MI_ERR_UNSUPPORTED, "%s: FP8 weights on a MoE model are not implemented (the experts stay bf16)", entry);
+  if (m->lora_rank > 0) return fail(MI_ERR_UNSUPPORTED, "%s: un-merged LoRA on an FP8 base is not implemented; merge the adapter before quantising", entry);
+  if (m->dim % 16 || m->hidden_dim % 16 || (m->n_heads * m->head_dim) % 16)
+    return fail(MI_ERR_SHAPE, "%s: dim, hidden_dim and n_heads * head_dim must be multiples of 16 (a 16-byte piece is 16 e4m3 weights)", entry);
+  return MI_OK;
+}
+
+// mi_forward and mi_forward_w8.  w8 == nullptr: exactly the launches of mi_forward as they always were.
+static int forward_body(const char* entry, const mi_model_t* m, const mi_w8_model_t* w8, const mi_batch_t* bt, mi_stream_t stream) {
   MI_TRY(check_model(m));
+  if (w8) MI_TRY(check_w8(entry, m, w8));
   BatchInfo bi;
-  MI_TRY(check_batch("mi_forward", m, bt, true, &bi));
+  MI_TRY(check_batch(entry, m, bt, true, &bi));
   int maxW = 1;
   if (bi.has_cache)
     for (int l = 0; l < m->n_layers; ++l) maxW = bt->cache_sizes[l] > maxW ? bt->cache_sizes[l] : maxW;
-  const Workspace ws = carve(m, bi.T, bi.B, maxW, (char*)bt->workspace);
-  MI_TRY(check_workspace_and_sample("mi_forward", bt, ws.total, &bi));
+  const Workspace ws = carve(m, bi.T, bi.B, maxW, (char*)bt->workspace, w8 != nullptr);
+  MI_TRY(check_workspace_and_sample(entry, bt, ws.total, &bi));
   const int T = bi.T, B = bi.B, branch = bi.branch, kvl = bi.kv_layout;
   const bool has_cache = bi.has_cache, want_greedy = bi.want_sample, want_topp = bi.want_topp;
   hipStream_t s = (hipStream_t)stream;
@@ -956,7 +1083,7 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
       pr.hist_tok = bt->hist_token; pr.hist_lp = bt->hist_logprob; pr.hist_len = bt->hist_len;
     }
     pr.granules = ws.gran; pr.granule_bytes = ws.gran_bytes; pr.ctrl = engine_ctrl;
-    pr.E = m->num_experts; pr.top_k = m->top_k; pr.lora_rank = m->lora_rank;
+    pr.E = m->num_experts; pr.top_k = m->top_k; pr.lora_rank = m->lora_rank; pr.w8 = w8 != nullptr;
     pr.forced = engine_variant() == 1;
     bool dense_ok = true;
     for (int l = 0; l < m->n_layers; ++l)
@@ -1002,6 +1129,20 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
 
     // ---- un-merged LoRA (ABI v8): every linear is [base product] [lora_down] [lora_up] (lora_linear above); RoPE and the ring
     // write are the separate passes (bit-equal to the fused epilogues: same arithmetic on the same bf16 values)
+    // ---- weight-only FP8: `run` sends a GEMV to the e4m3 kernels with the linear's row scales; `deq` (T > 8) writes the bf16
+    // image of a linear group into the scratch and points w[] at it for the GEMM that follows.  Without w8 both pass through.
+    static const mi_w8_layer_t kNoScales = {};
+    const mi_w8_layer_t& Q = w8 ? w8->layers[l] : kNoScales;
+    auto run = [&](const GemvArgs& ga, const W8Scales& sc, const char* what) {
+      return w8 ? gemv_passes_w8(ga, sc, T, s, what) : gemv_passes(kGemvBf16, ga, T, s, what);
+    };
+    auto deq = [&](const void* (&w)[3], const W8Scales& sc, int r0, int r1, int r2, int K, const char* what) {
+      if (!w8) return (int)MI_OK;
+      if (!sc.s[0] || (w[1] && !sc.s[1]) || (w[2] && !sc.s[2])) return fail(MI_ERR_ARG, "%s: layer %d has a linear without row scales", entry, l);
+      const int nr[3] = {r0, r1, r2};
+      return dequant_group(w, sc, nr, K, ws.w8, s, what);
+    };
+    if (w8 && !(Q.wq && Q.wk && Q.wv && Q.wo && Q.w1 && Q.w2 && Q.w3)) return fail(MI_ERR_ARG, "%s: layer %d has a linear without row scales", entry, l);
     static const mi_lora_layer_t kNoAdapters = {};
     const mi_lora_layer_t& A = (lora && L.lora) ? *L.lora : kNoAdapters;
     const float ls = m->lora_scaling;
@@ -1021,15 +1162,17 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
       if (branch == MI_BRANCH_DECODE) MI_TRY(kv_write("kv_write (decode)"));
     } else if (gemv) {
       const RingWrite ring = {ck, cv, W, kvl};
-      MI_TRY(gemv_passes(kGemvBf16, gemv_qkv_rope(h, D, D, L.attention_norm, m->norm_eps, L.wq, L.wk, L.wv, nq, nkv, ws.qkv, qkv_cols,
-                                                  m->rope_cs, bt->tok_pos, bt->tok_seq, Dh, branch == MI_BRANCH_DECODE ? &ring : nullptr),
-                         T, s, "qkv gemv"));
+      MI_TRY(run(gemv_qkv_rope(h, D, D, L.attention_norm, m->norm_eps, L.wq, L.wk, L.wv, nq, nkv, ws.qkv, qkv_cols, m->rope_cs, bt->tok_pos,
+                               bt->tok_seq, Dh, branch == MI_BRANCH_DECODE ? &ring : nullptr),
+                 {{Q.wq, Q.wk, Q.wv}}, "qkv gemv"));
     } else {
       MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, L.attention_norm, T, D, m->norm_eps, s), "attention_norm"));
+      const void* wqkv[3] = {L.wq, L.wk, L.wv};
+      MI_TRY(deq(wqkv, {{Q.wq, Q.wk, Q.wv}}, nq, nkv, nkv, D, "dequant q|k|v"));
       GemmArgs g;
       memset(&g, 0, sizeof(g));
       g.epi = GEMM_STORE; g.M = T; g.N = qkv_cols; g.K = D; g.a = ws.xn; g.lda = D;
-      g.w0 = (const bf16_t*)L.wq; g.w1 = (const bf16_t*)L.wk; g.w2 = (const bf16_t*)L.wv; g.n0 = nq; g.n1 = nq + nkv;
+      g.w0 = (const bf16_t*)wqkv[0]; g.w1 = (const bf16_t*)wqkv[1]; g.w2 = (const bf16_t*)wqkv[2]; g.n0 = nq; g.n1 = nq + nkv;
       g.out = ws.qkv; g.ldo = qkv_cols;
       // RoPE rides on the GEMM's epilogue (same arithmetic as rope_kernel on the same bf16-rounded values; it was a
       // separate 20 us pass over q|k per layer at 4096 tokens).  Heads of a size the epilogues do not take: separate pass.
@@ -1057,10 +1200,13 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
     if (lora) {
       const LoraLinear wo = banked({{L.wo, nullptr, nullptr}, {A.wo_a, nullptr, nullptr}, {A.wo_b, nullptr, nullptr}, {D, 0, 0}, 1, MI_EPI_RESIDUAL});
       MI_TRY(lora_linear(h, D, ws.attn, nq, ws.attn, nq, T, nq, wo, h, nullptr, 0.f, m->lora_rank, ls, ws.xn, false, ws.lora_t, s));
-    } else if (gemv)
-      MI_TRY(gemv_passes(kGemvBf16, gemv_residual(ws.attn, nq, L.wo, h, D), T, s, "wo gemv"));
-    else
-      MI_TRY(hip_rc(launch_gemm(gemm_args(GEMM_RESIDUAL, ws.attn, T, nq, L.wo, nullptr, D, h, h), s), "wo gemm"));
+    } else if (gemv) {
+      MI_TRY(run(gemv_residual(ws.attn, nq, L.wo, h, D), {{Q.wo, nullptr, nullptr}}, "wo gemv"));
+    } else {
+      const void* wo[3] = {L.wo, nullptr, nullptr};
+      MI_TRY(deq(wo, {{Q.wo, nullptr, nullptr}}, D, 0, 0, nq, "dequant wo"));
+      MI_TRY(hip_rc(launch_gemm(gemm_args(GEMM_RESIDUAL, ws.attn, T, nq, wo[0], nullptr, D, h, h), s), "wo gemm"));
+    }
 
     // ---- h = h + FFN(ffn_norm(h))
     if (lora) {
@@ -1072,12 +1218,16 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
       MI_TRY(lora_linear(h, D, ws.hid, F, ws.hid, F, T, F, w2, h, nullptr, 0.f, m->lora_rank, ls, ws.xn, false, ws.lora_t, s));
     } else if (m->num_experts == 0) {
       if (gemv) {
-        MI_TRY(gemv_passes(kGemvBf16, gemv_swiglu(h, D, L.ffn_norm, m->norm_eps, L.w1, L.w3, ws.hid, F), T, s, "w13 gemv"));
-        MI_TRY(gemv_passes(kGemvBf16, gemv_residual(ws.hid, F, L.w2, h, D), T, s, "w2 gemv"));
+        MI_TRY(run(gemv_swiglu(h, D, L.ffn_norm, m->norm_eps, L.w1, L.w3, ws.hid, F), {{Q.w1, Q.w3, nullptr}}, "w13 gemv"));
+        MI_TRY(run(gemv_residual(ws.hid, F, L.w2, h, D), {{Q.w2, nullptr, nullptr}}, "w2 gemv"));
       } else {
         MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, L.ffn_norm, T, D, m->norm_eps, s), "ffn_norm"));
-        MI_TRY(hip_rc(launch_gemm(gemm_args(GEMM_SWIGLU, ws.xn, T, D, L.w1, L.w3, F, ws.hid, nullptr), s), "w13 gemm"));
-        MI_TRY(hip_rc(launch_gemm(gemm_args(GEMM_RESIDUAL, ws.hid, T, F, L.w2, nullptr, D, h, h), s), "w2 gemm"));
+        const void* w13[3] = {L.w1, L.w3, nullptr};
+        MI_TRY(deq(w13, {{Q.w1, Q.w3, nullptr}}, F, F, 0, D, "dequant w1|w3"));
+        MI_TRY(hip_rc(launch_gemm(gemm_args(GEMM_SWIGLU, ws.xn, T, D, w13[0], w13[1], F, ws.hid, nullptr), s), "w13 gemm"));
+        const void* w2[3] = {L.w2, nullptr, nullptr};
+        MI_TRY(deq(w2, {{Q.w2, nullptr, nullptr}}, D, 0, 0, F, "dequant w2"));
+        MI_TRY(hip_rc(launch_gemm(gemm_args(GEMM_RESIDUAL, ws.hid, T, F, w2[0], nullptr, D, h, h), s), "w2 gemm"));
       }
     } else {
       const int E = m->num_experts, k = m->top_k;
@@ -1108,6 +1258,12 @@ int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) {
     if (want_greedy) MI_TRY(sample_step(bt, m, want_topp, engine_ctrl, s));
   }
   return MI_OK;
+}
+
+int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) { return forward_body("mi_forward", m, nullptr, bt, stream); }
+
+int mi_forward_w8(const mi_model_t* m, const mi_w8_model_t* w8, const mi_batch_t* bt, mi_stream_t stream) {
+  return forward_body(w8 ? "mi_forward_w8" : "mi_forward", m, w8, bt, stream);
 }
 
 }  // extern "C"

@@ -64,6 +64,24 @@ hipError_t launch_gemv(const GemvArgs& a, hipStream_t s);
 int gemv_max_tokens_f16(int K);
 hipError_t launch_gemv_f16(const GemvArgs& a, hipStream_t s);
 
+// gemv_w8.hip: the same launches on weight rows of OCP e4m3 bytes with fp32 row scales (weight-only FP8).  GemvArgs is the bf16
+// kernels' kernarg and stays as it is: the scales ride beside it.  w0 / w1 / w2 point to bytes, K % 16 == 0, modes STORE /
+// RESIDUAL / SWIGLU / QKV_ROPE; scale[i] holds one fp32 per row of segment i (SWIGLU: scale[0] = W1's, scale[1] = W3's).
+struct GemvW8Args {
+  GemvArgs g;
+  const float* scale[3];
+};
+hipError_t launch_gemv_w8(const GemvW8Args& a, hipStream_t s);
+// out[r, k] = bf16(scale[r] * e4m3(W[r, k])) for the N rows of up to three matrices side by side (segment ends n0, n1 as in
+// GemvArgs), dense [N, K] bf16: the weight image the MFMA GEMMs read at more than 8 rows
+struct DequantW8Args {
+  const uint8_t* w[3];
+  const float* scale[3];
+  int n0, n1, N, K;
+  bf16_t* out;
+};
+hipError_t launch_dequant_w8(const DequantW8Args& a, hipStream_t s);
+
 // ---------------------------------------------------------------------------------------------- GEMM
 enum GemmEpi { GEMM_STORE = 0, GEMM_RESIDUAL = 1, GEMM_SWIGLU = 2, GEMM_LOGITS = 3, GEMM_LOGPROB = 4 };
 
@@ -298,6 +316,7 @@ struct EngProblem {
   uint32_t* ctrl;
   int forced;                // mi_debug_set_engine_variant(1): take shapes that measured slower than the launch path too (traces, tests)
   int lora_rank;             // > 0: the model carries un-merged LoRA adapters - no engine build takes it (api.hip engine_route)
+  int w8;                    // != 0: the layers' linears are e4m3 bytes (mi_forward_w8) - no engine build reads them
 };
 static_assert(sizeof(EngArgs) <= 4096, "EngArgs must fit the kernel-argument segment");
 size_t decode_engine_granule_bytes(int D, int H, int Hkv, int F, int maxW);  // the same for every build (default object only)

@@ -68,6 +68,18 @@ class MiBatch(C.Structure):
     ]
 
 
+class MiW8Layer(C.Structure):
+    """`mi_w8_layer_t`: device fp32 row scales of the seven quantised linears of a layer (weight-only FP8)."""
+    _fields_ = [(n, _vp) for n in ("wq", "wk", "wv", "wo", "w1", "w2", "w3")]
+
+
+class MiW8Model(C.Structure):
+    """`mi_w8_model_t`: the quantisation beside an MiModel whose linear pointers are e4m3 bytes."""
+    _fields_ = [("format", C.c_int32), ("layers", C.POINTER(MiW8Layer))]
+
+
+MI_W8_FP8_E4M3 = 1  # include/mistral_hip.h
+
 _lib: Optional[C.CDLL] = None
 
 _SIGS = {
@@ -105,6 +117,14 @@ _SIGS = {
                                       C.c_size_t, _vp]),
     "mi_workspace_bytes": (C.c_size_t, [C.POINTER(MiModel), C.c_int, C.c_int, C.c_int]),
     "mi_forward": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiBatch), _vp]),
+    # weight-only FP8 (additive to ABI v9: the presence of these symbols is the feature test)
+    "mi_linear_w8_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "mi_linear_w8": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp), C.POINTER(C.c_int), C.c_int,
+                               _vp, _vp, C.c_float, C.POINTER(_vp), _vp, C.c_size_t, _vp]),
+    "mi_qkv_rope_kvwrite_w8": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int,
+                                         C.c_int, _vp, C.c_float, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
+    "mi_workspace_bytes_w8": (C.c_size_t, [C.POINTER(MiModel), C.POINTER(MiW8Model), C.c_int, C.c_int, C.c_int]),
+    "mi_forward_w8": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiW8Model), C.POINTER(MiBatch), _vp]),
     "mi_workspace_bytes_generic": (C.c_size_t, [C.POINTER(MiModel), C.c_int, C.c_int]),  # ABI v6
     "mi_forward_generic": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiBatch), C.c_int, _vp]),
     "mi_embedding_generic": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
@@ -249,6 +269,37 @@ def linear(x: torch.Tensor, weights: Sequence[torch.Tensor], epilogue: int = EPI
     nr = (C.c_int * 3)(*n_rows, *([0] * (3 - len(weights))))
     check(lib().mi_linear(dev_ptr(out, odt), out.stride(0), dev_ptr(x), x.stride(0), M, K, wp, nr, epilogue,
                           dev_ptr(residual), dev_ptr(norm_w), float(eps), stream_ptr(x.device)), "mi_linear")
+    return out
+
+
+def linear_w8(x: torch.Tensor, weights: Sequence[torch.Tensor], scales: Sequence[torch.Tensor], epilogue: int = EPI_STORE,
+              residual: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`linear` on weight-only FP8 matrices (mi_linear_w8): weights[i] e4m3 bytes [n_i, K] (uint8 or float8_e4m3fn), scales[i]
+    fp32 [n_i]; STORE / RESIDUAL / SWIGLU.  M <= 8: the e4m3 GEMV; above: dequantise into a per-call scratch + the bf16 GEMM."""
+    assert 1 <= len(weights) <= 3 and len(scales) == len(weights) and x.dim() == 2
+    if x.dtype != torch.bfloat16:
+        raise NotImplementedError("FP8 weight-only linears take bfloat16 activations (fp16 / fp32 storage is not implemented)")
+    M, K = x.shape
+    n_rows = [w.shape[0] for w in weights]
+    wb = []
+    for w, sc in zip(weights, scales):
+        assert w.shape[1] == K and w.is_contiguous() and w.dtype in (torch.uint8, torch.float8_e4m3fn)
+        assert sc.dtype == torch.float32 and tuple(sc.shape) == (w.shape[0],) and sc.is_contiguous()
+        wb.append(w.view(torch.uint8) if w.dtype != torch.uint8 else w)
+    N = n_rows[0] if epilogue == EPI_SWIGLU else sum(n_rows)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    pad = [None] * (3 - len(weights))
+    wp = (_vp * 3)(*[dev_ptr(w, torch.uint8) for w in wb], *pad)
+    sp = (_vp * 3)(*[dev_ptr(sc, torch.float32) for sc in scales], *pad)
+    nr = (C.c_int * 3)(*n_rows, *([0] * (3 - len(weights))))
+    L = lib()
+    need = L.mi_linear_w8_scratch_bytes(M, K, nr, epilogue)
+    scratch = torch.empty(need, dtype=torch.uint8, device=x.device) if need else None  # per call, from the caching allocator
+    check(L.mi_linear_w8(dev_ptr(out), out.stride(0), dev_ptr(x), x.stride(0), M, K, wp, nr, epilogue, dev_ptr(residual),
+                         dev_ptr(norm_w), float(eps), sp, scratch.data_ptr() if need else None, need, stream_ptr(x.device)),
+          "mi_linear_w8")
     return out
 
 
@@ -503,6 +554,29 @@ def qkv_rope_kvwrite(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: to
                                     dev_ptr(tok_seq, torch.int32), dev_ptr(cache_k), dev_ptr(cache_v), W,
                                     _kv_layout2(cache_k, cache_v) if cache_k is not None else KV_SLOT_MAJOR,
                                     stream_ptr(x.device)), "mi_qkv_rope_kvwrite")
+    return out
+
+
+def qkv_rope_kvwrite_w8(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor, sq: torch.Tensor, sk: torch.Tensor,
+                        sv: torch.Tensor, head_dim: int, rope_cs: torch.Tensor, tok_pos: torch.Tensor,
+                        norm_w: Optional[torch.Tensor] = None, eps: float = 0.0, cache_k: Optional[torch.Tensor] = None,
+                        cache_v: Optional[torch.Tensor] = None, tok_seq: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`qkv_rope_kvwrite` on weight-only FP8 matrices (mi_qkv_rope_kvwrite_w8): wq / wk / wv e4m3 bytes, sq / sk / sv fp32 row scales."""
+    T, D = x.shape
+    nq, nkv = wq.shape[0], wk.shape[0]
+    assert wv.shape[0] == nkv and rope_cs.dtype == torch.float32 and rope_cs.is_contiguous() and tok_pos.dtype == torch.int32
+    ws = [w.view(torch.uint8) if w.dtype != torch.uint8 else w for w in (wq, wk, wv)]
+    for w, sc in zip(ws, (sq, sk, sv)):
+        assert w.is_contiguous() and w.shape[1] == D and sc.dtype == torch.float32 and tuple(sc.shape) == (w.shape[0],)
+    out = torch.empty((T, nq + 2 * nkv), dtype=x.dtype, device=x.device)
+    W = cache_k.shape[1] if cache_k is not None else 0
+    u8, f32 = torch.uint8, torch.float32
+    check(lib().mi_qkv_rope_kvwrite_w8(dev_ptr(out), out.stride(0), dev_ptr(x), x.stride(0), T, D, dev_ptr(ws[0], u8), dev_ptr(ws[1], u8),
+                                       dev_ptr(ws[2], u8), dev_ptr(sq, f32), dev_ptr(sk, f32), dev_ptr(sv, f32), nq // head_dim,
+                                       nkv // head_dim, head_dim, dev_ptr(norm_w), float(eps), dev_ptr(rope_cs, f32), rope_cs.shape[0],
+                                       dev_ptr(tok_pos, torch.int32), dev_ptr(tok_seq, torch.int32), dev_ptr(cache_k), dev_ptr(cache_v), W,
+                                       _kv_layout2(cache_k, cache_v) if cache_k is not None else KV_SLOT_MAJOR, stream_ptr(x.device)),
+          "mi_qkv_rope_kvwrite_w8")
     return out
 
 

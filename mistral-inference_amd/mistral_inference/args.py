@@ -47,6 +47,20 @@ class LoraArgs(_FromDict):
         assert self.scaling > 0.0
 
 
+QFORMAT_FP8_E4M3 = "fp8_e4m3"
+
+
+@dataclass
+class QuantizationArgs(_FromDict):
+    """`quantization` block of params.json: weight-only quantisation of the seven linears of every layer (quant.py)."""
+    qformat_weight: str         # "fp8_e4m3": OCP e4m3 bytes + one fp32 scale per output row
+
+    def __post_init__(self) -> None:
+        if self.qformat_weight != QFORMAT_FP8_E4M3:
+            raise NotImplementedError(f"quantization.qformat_weight {self.qformat_weight!r} is not implemented "
+                                      f"({QFORMAT_FP8_E4M3!r} is the only weight format)")
+
+
 @dataclass
 class VisionEncoderArgs(_FromDict):
     """`vision_encoder` block of params.json (Pixtral-12B, Mistral-Small-3.1)."""
@@ -82,6 +96,7 @@ class TransformerArgs(_FromDict):
     rope_theta: Optional[float] = None          # None -> 1e6 (reference transformer.py:115)
     moe: Optional[MoeArgs] = None               # sparse FFN: experts and experts per token
     lora: Optional[LoraArgs] = None             # un-merged LoRA layers (lora.py; dense bf16 models); without it load_lora() merges
+    quantization: Optional[QuantizationArgs] = None  # weight-only FP8 linears (quant.py; dense bf16 models without `lora`)
     sliding_window: Union[None, int, List[Optional[int]]] = None   # one window, or one per layer (cycled)
     _sliding_window: Union[None, int, List[Optional[int]]] = None  # legacy spelling of the same key
     model_type: str = "transformer"
@@ -97,5 +112,6 @@ class TransformerArgs(_FromDict):
 _NESTED = {
     ("TransformerArgs", "moe"): MoeArgs,
     ("TransformerArgs", "lora"): LoraArgs,
+    ("TransformerArgs", "quantization"): QuantizationArgs,
     ("TransformerArgs", "vision_encoder"): VisionEncoderArgs,
 }

@@ -76,13 +76,15 @@ def get_model_cls(model_path: str) -> Type[Transformer]:
 
 
 def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7, num_pipeline_ranks: int = 1,
-                instruct: bool = False, lora_path: Optional[str] = None) -> None:
+                instruct: bool = False, lora_path: Optional[str] = None, quantize: Optional[str] = None) -> None:
+    """quantize="fp8_e4m3": quantise a bf16 checkpoint to weight-only FP8 while it loads (a folder that quant.quantize_checkpoint
+    wrote needs no flag)."""
     num_pipeline_ranks = init_pipeline() if is_torchrun() else num_pipeline_ranks
     should_print = _should_print()
     mistral_tokenizer = load_tokenizer(Path(model_path))
     tokenizer = mistral_tokenizer.instruct_tokenizer.tokenizer
     model = get_model_cls(model_path).from_folder(Path(model_path), max_batch_size=3,
-                                                  num_pipeline_ranks=num_pipeline_ranks, dtype=torch.bfloat16)
+                                                  num_pipeline_ranks=num_pipeline_ranks, dtype=torch.bfloat16, quantize=quantize)
     if lora_path is not None:  # reference main.py:131-132
         model.load_lora(Path(lora_path))
     messages: List = []
@@ -113,11 +115,13 @@ def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7,
             messages += [msg.AssistantMessage(content=answer)]
 
 
-def demo(model_path: str, max_tokens: int = 35, temperature: float = 0, lora_path: Optional[str] = None) -> None:
+def demo(model_path: str, max_tokens: int = 35, temperature: float = 0, lora_path: Optional[str] = None,
+         quantize: Optional[str] = None) -> None:
+    """quantize: as `interactive`."""
     num_pipeline_ranks = init_pipeline()
     should_print = _should_print()
     model = get_model_cls(model_path).from_folder(Path(model_path), max_batch_size=3,
-                                                  num_pipeline_ranks=num_pipeline_ranks, dtype=torch.bfloat16)
+                                                  num_pipeline_ranks=num_pipeline_ranks, dtype=torch.bfloat16, quantize=quantize)
     if lora_path is not None:  # reference main.py:224-225
         model.load_lora(Path(lora_path))
     tokenizer = load_tokenizer(Path(model_path)).instruct_tokenizer.tokenizer

@@ -1,0 +1,192 @@
+"""Weight-only FP8 (OCP e4m3) linears over the HIP operators, and the quantiser that writes such checkpoints.
+
+A quantised linear stores `weight` as e4m3fn bytes [out, in] and `qscale_weight` as fp32 [out]; the real-valued weight is
+`qscale_weight[r] * e4m3(weight[r, k])`.  The reference has no quantised layer: `Fp8Linear` stands where its `nn.Linear` stands
+(reference transformer_layers.py:51-54,101-103) and its `forward` is one `mi_linear_w8` call (csrc/gemv_w8.hip):
+
+    T <= 8:  acc = sum_k e4m3(W[r, k]) x[k] in fp32;  y = bf16(acc * qscale_weight[r])
+    T  > 8:  W' = bf16(qscale_weight[r] * e4m3(W[r, k])) into a scratch, then the bf16 MFMA GEMM on W'
+
+`quantize_rows` produces power-of-two row scales only; W' is then exact in bf16 and both forms compute the bf16 model on the
+dequantised weights, up to fp32 summation order.  Other positive finite scales (checkpoints made elsewhere) are accepted; the
+two forms then differ by one bf16 rounding of each weight.  Embeddings, norms, the LM head, the MoE gate, the vision tower and
+the K/V rings stay bf16.  Dense bf16 models without un-merged LoRA only.
+
+Checkpoint layout: `<linear>.weight` with dtype F8_E4M3, `<linear>.qscale_weight` fp32 [out] (a scalar or [1] is broadcast at
+load), `params.json` with `"quantization": {"qformat_weight": "fp8_e4m3"}`.  Compatibility is claimed only with checkpoints
+that `quantize_checkpoint` wrote."""
+import json
+import re
+from pathlib import Path
+from typing import Dict, Optional, Sequence, Tuple, Union
+
+import torch
+from torch import nn
+
+from . import _hip
+from .args import QFORMAT_FP8_E4M3, QuantizationArgs  # noqa: F401
+
+QSCALE_KEY = "qscale_weight"   # `<linear>.qscale_weight`: the one place that names the checkpoint key of a row scale
+QSCALE_ACT_KEY = "qscale_act"  # per-tensor activation scales of FP8-activation checkpoints: not implemented, a foreign key here
+E4M3_MAX = 448.0
+# the linears that are quantised: the seven of every dense layer, nothing else
+_QUANT_KEY = re.compile(r"^layers\.\d+\.(attention\.w[qkvo]|feed_forward\.w[123])\.weight$")
+
+FP8_LORA_REFUSAL = ("un-merged LoRA on an FP8-quantised base is not implemented; merge the adapter into the bf16 weights "
+                    "(Transformer.load_lora on a bf16 model) and quantise the result")
+FP8_MOE_REFUSAL = "FP8 weight-only quantisation of a MoE model is not implemented (the expert kernels read bf16 weights)"
+FP8_MERGE_REFUSAL = ("load_lora: merging an adapter into FP8-quantised weights is not implemented (the merge needs the bf16 "
+                     "weights); merge into the bf16 checkpoint and quantise the result")
+
+
+def check_quantize_arg(quantize: Optional[str]) -> None:
+    if quantize is not None and quantize != QFORMAT_FP8_E4M3:
+        raise NotImplementedError(f"quantize={quantize!r} is not implemented ({QFORMAT_FP8_E4M3!r} is the only weight format)")
+
+
+def refuse_fp8_combinations(args, dtype: Optional[torch.dtype]) -> None:
+    """What a quantised model cannot be combined with, by name, before anything is read from disk."""
+    if args.quantization is None:
+        return
+    if args.lora is not None:
+        raise NotImplementedError(FP8_LORA_REFUSAL)
+    if args.moe is not None:
+        raise NotImplementedError(FP8_MOE_REFUSAL)
+    if dtype is not None and dtype != torch.bfloat16:
+        raise NotImplementedError(f"FP8 weight-only quantisation with fp16 / fp32 storage ({dtype}) is not implemented: the "
+                                  "activations, norms and the LM head of a quantised model are bfloat16")
+
+
+def is_quantized_linear_key(key: str) -> bool:
+    return _QUANT_KEY.match(key) is not None
+
+
+def quantize_rows(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[out, in] (bf16 / fp32) -> (q float8_e4m3fn [out, in], scale fp32 [out]) with the power-of-two row scale
+    2^ceil(log2(amax / 448)): for a nonzero row amax / scale lies in (224, 448].  An all-zero row gets scale 1.  The cast
+    saturates (at +-448, and below the largest bf16 after scaling) and never produces the NaN codes 0x7F / 0xFF.  Integer
+    exponent arithmetic (frexp / ldexp), so the CPU and the device give the same bytes."""
+    assert w.dim() == 2 and w.is_floating_point()
+    wf = w.float()
+    amax = wf.abs().amax(dim=1)
+    if not bool(torch.isfinite(amax).all()):
+        raise ValueError("quantize_rows: the weight holds inf or NaN")
+    mant, ex = torch.frexp(amax)                     # amax = mant * 2^ex, mant in [0.5, 1)
+    # amax / 448 = (2 mant / 1.75) * 2^(ex - 9): the ceil of its log2 is ex - 9, one more when 2 mant > 1.75
+    e = ex - 9 + (mant > 0.875).to(ex.dtype)
+    e = torch.where(amax > 0, e, torch.zeros_like(e))
+    scale = torch.ldexp(torch.ones_like(amax), e)
+    q = (wf / scale[:, None]).clamp_(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn)
+    # a row whose amax sits in bf16's top binade can round UP past the largest bf16 (255 -> 256 at scale 2^120): such a code
+    # steps down to the next smaller magnitude, so that the dequantised weight saturates instead of becoming inf
+    over = (q.float().abs() * scale[:, None]) > torch.finfo(torch.bfloat16).max
+    if bool(over.any()):
+        codes = q.view(torch.uint8)
+        q = torch.where(over, codes - 1, codes).view(torch.float8_e4m3fn)
+    return q, scale
+
+
+def dequantize(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """bf16(scale[r] * e4m3(q[r, k])); exact for power-of-two scales.  q: float8_e4m3fn or its bytes as uint8."""
+    if q.dtype == torch.uint8:
+        q = q.view(torch.float8_e4m3fn)
+    return (q.float() * scale.float().reshape(-1, 1)).to(torch.bfloat16)
+
+
+def expand_scale(scale: torch.Tensor, out_features: int) -> torch.Tensor:
+    """A checkpoint's row scale as fp32 [out]: a scalar or [1] is broadcast."""
+    s = scale.float().reshape(-1)
+    if s.numel() == 1:
+        s = s.expand(out_features)
+    if s.numel() != out_features:
+        raise ValueError(f"{QSCALE_KEY} has {s.numel()} entries for {out_features} output rows")
+    return s.contiguous()
+
+
+class Fp8Linear(nn.Module):
+    """`nn.Linear(bias=False)` on e4m3 weight bytes and fp32 row scales.  The bytes are held as a uint8 parameter and the scales
+    stay fp32 whatever dtype the model is cast to: `model.to(dtype=...)` would otherwise convert a float8 parameter silently, and
+    without its scale."""
+
+    def __init__(self, in_features: int, out_features: int, bias: bool = False):
+        super().__init__()
+        assert not bias
+        self.in_features, self.out_features = in_features, out_features
+        self.weight = nn.Parameter(torch.zeros((out_features, in_features), dtype=torch.uint8), requires_grad=False)
+        self.qscale_weight = nn.Parameter(torch.ones(out_features, dtype=torch.float32), requires_grad=False)
+
+    def _apply(self, fn, recurse: bool = True):
+        def keep_dtype(t: torch.Tensor) -> torch.Tensor:  # device moves pass; a dtype cast touches neither bytes nor scales
+            out = fn(t)
+            return out if out.dtype == t.dtype else t.to(device=out.device)
+        return super()._apply(keep_dtype, recurse)
+
+    @torch.no_grad()
+    def load_quantized(self, q: torch.Tensor, scale: torch.Tensor) -> None:
+        """Bind e4m3 weights (float8_e4m3fn or uint8 bytes) and their row scales (fp32 [out], scalar or [1])."""
+        assert tuple(q.shape) == (self.out_features, self.in_features), (tuple(q.shape), self.out_features, self.in_features)
+        self.weight = nn.Parameter(weight_bytes(q), requires_grad=False)
+        self.qscale_weight = nn.Parameter(expand_scale(scale, self.out_features).to(q.device), requires_grad=False)
+
+    def dequantized(self) -> torch.Tensor:
+        return dequantize(self.weight, self.qscale_weight)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        shape = x.shape
+        out = linear_fp8(x.reshape(-1, shape[-1]), (self,), _hip.EPI_STORE)
+        return out.view(*shape[:-1], self.out_features)
+
+
+def weight_bytes(q: torch.Tensor) -> torch.Tensor:
+    if q.dtype == torch.float8_e4m3fn:
+        return q.contiguous().view(torch.uint8)
+    if q.dtype != torch.uint8:
+        raise ValueError(f"a quantised weight is F8_E4M3 (torch.float8_e4m3fn), got {q.dtype}")
+    return q.contiguous()
+
+
+def linear_fp8(x: torch.Tensor, mods: Sequence[Fp8Linear], epilogue: int = _hip.EPI_STORE, residual: Optional[torch.Tensor] = None,
+               norm_w: Optional[torch.Tensor] = None, eps: float = 0.0) -> torch.Tensor:
+    """`_hip.linear` over up to three Fp8Linear modules that share an input (q|k|v; SWIGLU: w1, w3)."""
+    return _hip.linear_w8(x, [m.weight for m in mods], [m.qscale_weight for m in mods], epilogue, residual, norm_w, eps)
+
+
+def quantize_state_tensor(key: str, t: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """One checkpoint tensor -> the tensors that replace it: a quantised linear becomes its bytes and its row scales, anything
+    else stays as it is."""
+    if not is_quantized_linear_key(key):
+        return {key: t}
+    if t.dtype != torch.bfloat16:
+        raise NotImplementedError(f"{key}: FP8 quantisation starts from a bfloat16 checkpoint, got {t.dtype}")
+    q, scale = quantize_rows(t)
+    return {key: q, key[:-len("weight")] + QSCALE_KEY: scale}
+
+
+def quantize_checkpoint(src_folder: Union[Path, str], dst_folder: Union[Path, str]) -> Path:
+    """bf16 folder (params.json + consolidated.safetensors) -> FP8 weight-only folder, tensor by tensor on the CPU: the seven
+    linears of every layer become `<linear>.weight` (F8_E4M3) + `<linear>.qscale_weight` (fp32 [out]); everything else is
+    copied.  Other files of the folder (tokenizer) are the caller's to copy."""
+    import safetensors
+    from safetensors.torch import save_file
+    from .args import TransformerArgs
+
+    src, dst = Path(src_folder), Path(dst_folder)
+    with open(src / "params.json", "r") as f:
+        params = json.load(f)
+    args = TransformerArgs.from_dict(params)
+    if args.quantization is not None:
+        raise ValueError(f"{src} is already quantised ({args.quantization.qformat_weight})")
+    args.quantization = QuantizationArgs(QFORMAT_FP8_E4M3)
+    refuse_fp8_combinations(args, None)
+    st_file = src / "consolidated.safetensors"
+    assert st_file.exists(), f"{st_file} does not exist (quantize_checkpoint reads safetensors)"
+    out: Dict[str, torch.Tensor] = {}
+    with safetensors.safe_open(str(st_file), framework="pt", device="cpu") as f:
+        for k in f.keys():
+            out.update(quantize_state_tensor(k, f.get_tensor(k)))
+    dst.mkdir(parents=True, exist_ok=True)
+    save_file(out, str(dst / "consolidated.safetensors"))
+    params["quantization"] = {"qformat_weight": QFORMAT_FP8_E4M3}
+    with open(dst / "params.json", "w") as f:
+        json.dump(params, f)
+    return dst

@@ -29,10 +29,12 @@ import torch
 from torch import nn
 
 from . import _hip
-from .args import TransformerArgs
+from .args import QFORMAT_FP8_E4M3, QuantizationArgs, TransformerArgs
 from .cache import BatchMetadata, BufferCache
 from .lora import LoRALinear, check_rank
 from .model import ModelBase
+from .quant import (FP8_MERGE_REFUSAL, QSCALE_ACT_KEY, QSCALE_KEY, Fp8Linear, check_quantize_arg, expand_scale, quantize_state_tensor,
+                    refuse_fp8_combinations, weight_bytes)
 from .rope import precompute_freqs_cis
 from .transformer_layers import LORA_MOE_REFUSAL, RMSNorm, TransformerBlock
 from .vision_encoder import PATCH_MERGE, PatchMerger, VisionLanguageAdapter, VisionTransformer
@@ -97,6 +99,7 @@ class HipStackBackend:
         # persistent tensor.
         self._seq_adapter: Optional[torch.Tensor] = None
         self._seq_adapter_now: Optional[torch.Tensor] = None
+        self._w8: Optional[Any] = None  # set by _build_plan: the mi_w8_model_t of a weight-only FP8 model (then mi_forward_w8 runs it)
 
     # -- one-time: pointer tables of the weights -------------------------------------------------
     def _build_plan(self, model: "Transformer"):
@@ -120,6 +123,15 @@ class HipStackBackend:
         self.dtype_code = _hip.DTYPE_CODES[dt]
         keep = []  # python objects that own memory referenced by raw pointers
         p = lambda t, d=dt: _hip.dev_ptr(t, d)  # noqa: E731
+        fp8 = a.quantization is not None
+        if fp8:
+            refuse_fp8_combinations(a, dt)
+            if self.generic:  # bf16, but a shape mi_forward declines: the generic kernels read no e4m3 weights
+                raise NotImplementedError("FP8 weight-only quantisation on a model shape outside the tuned bf16 kernels (head_dim "
+                                          "128, dim / hidden_dim multiples of 16) is not implemented")
+        # weight-only FP8: the seven linear pointers of a layer are e4m3 bytes, their fp32 row scales ride in a table beside it
+        scales = (_hip.MiW8Layer * max(1, model.n_local_layers))() if fp8 else None
+        wp = (lambda mod: _hip.dev_ptr(mod.weight, torch.uint8)) if fp8 else (lambda mod: p(mod.weight))
         E = a.moe.num_experts if a.moe is not None else 0
         layers = (_hip.MiLayer * max(1, model.n_local_layers))()
         adapters = (_hip.MiLoraLayer * max(1, model.n_local_layers))() if a.lora is not None else None
@@ -139,7 +151,7 @@ class HipStackBackend:
                     setattr(adapters[j], name + "_b", p(mod.lora_B.weight))
                 L.lora = C.pointer(adapters[j])
             L.attention_norm, L.ffn_norm = p(blk.attention_norm.weight), p(blk.ffn_norm.weight)
-            L.wq, L.wk, L.wv, L.wo = p(at.wq.weight), p(at.wk.weight), p(at.wv.weight), p(at.wo.weight)
+            L.wq, L.wk, L.wv, L.wo = wp(at.wq), wp(at.wk), wp(at.wv), wp(at.wo)
             if E:
                 ff = blk.feed_forward
                 L.gate = p(ff.gate.weight)
@@ -153,7 +165,11 @@ class HipStackBackend:
                 L.expert_w_dev = devtab.data_ptr()
             else:
                 ff = blk.feed_forward
-                L.w1, L.w2, L.w3 = p(ff.w1.weight), p(ff.w2.weight), p(ff.w3.weight)
+                L.w1, L.w2, L.w3 = wp(ff.w1), wp(ff.w2), wp(ff.w3)
+            if scales is not None:
+                for name, mod in (("wq", at.wq), ("wk", at.wk), ("wv", at.wv), ("wo", at.wo), ("w1", ff.w1), ("w2", ff.w2), ("w3", ff.w3)):
+                    assert isinstance(mod, Fp8Linear) and tuple(mod.qscale_weight.shape) == (mod.out_features,)
+                    setattr(scales[j], name, _hip.dev_ptr(mod.qscale_weight, torch.float32))
         rope = torch.view_as_real(model.freqs_cis).contiguous()
         keep += [layers, rope]
         m = _hip.MiModel()
@@ -169,6 +185,11 @@ class HipStackBackend:
         if a.lora is not None:
             m.lora_rank, m.lora_scaling = int(a.lora.rank), float(a.lora.scaling)
             m.lora_slots = int(model.lora_slots)
+        self._w8 = None
+        if scales is not None:
+            self._w8 = _hip.MiW8Model()
+            self._w8.format, self._w8.layers = _hip.MI_W8_FP8_E4M3, C.cast(scales, C.POINTER(_hip.MiW8Layer))
+            keep.append(scales)
         return m, keep
 
     @property
@@ -201,6 +222,7 @@ class HipStackBackend:
 
     def invalidate(self) -> None:
         self._plan = None
+        self._w8 = None
         self._workspace = None
 
     def raise_if_flagged(self) -> None:
@@ -255,6 +277,8 @@ class HipStackBackend:
     def _get_workspace(self, model: "Transformer", m, T: int, B: int, max_w: int) -> torch.Tensor:
         if self.generic:
             need = _hip.lib().mi_workspace_bytes_generic(C.byref(m), T, self.dtype_code)
+        elif self._w8 is not None:
+            need = _hip.lib().mi_workspace_bytes_w8(C.byref(m), C.byref(self._w8), T, B, max_w)
         else:
             need = _hip.lib().mi_workspace_bytes(C.byref(m), T, B, max_w)
         ws = self._workspace
@@ -305,6 +329,8 @@ class HipStackBackend:
         if self.generic:
             _hip.check(_hip.lib().mi_forward_generic(C.byref(m), C.byref(bt), self.dtype_code, _hip.stream_ptr(h.device)),
                        "mi_forward_generic")
+        elif self._w8 is not None:
+            _hip.check(_hip.lib().mi_forward_w8(C.byref(m), C.byref(self._w8), C.byref(bt), _hip.stream_ptr(h.device)), "mi_forward_w8")
         else:
             _hip.check(_hip.lib().mi_forward(C.byref(m), C.byref(bt), _hip.stream_ptr(h.device)), "mi_forward")
 
@@ -328,6 +354,7 @@ class Transformer(ModelBase):
             if args.moe is not None:
                 raise NotImplementedError(LORA_MOE_REFUSAL)
             check_rank(args.lora.rank)
+        refuse_fp8_combinations(args, None)  # weight-only FP8 (quant.py): dense models without un-merged LoRA
 
         # Rank-specific modules (reference transformer.py:52-79)
         self.tok_embeddings: Optional[nn.Embedding] = None
@@ -357,7 +384,7 @@ class Transformer(ModelBase):
         self.layers = nn.ModuleDict({
             str(i): TransformerBlock(dim=args.dim, hidden_dim=args.hidden_dim, n_heads=args.n_heads,
                                      n_kv_heads=args.n_kv_heads, head_dim=args.head_dim, norm_eps=args.norm_eps,
-                                     lora=args.lora, moe=args.moe)
+                                     lora=args.lora, moe=args.moe, quantization=args.quantization)
             for i in range(first, last)})
         self.n_local_layers = len(self.layers)
         self._backend = backend if backend is not None else HipStackBackend()
@@ -369,7 +396,11 @@ class Transformer(ModelBase):
     # ---- properties ----------------------------------------------------------------------------
     @property
     def dtype(self) -> torch.dtype:
-        return next(self.parameters()).dtype
+        """Storage dtype of activations, norms, embeddings and the K/V rings.  A weight-only FP8 model's is bfloat16: the e4m3
+        bytes and fp32 row scales of its Fp8Linear layers (the FIRST parameters of a pipeline rank > 0) do not count."""
+        if self.args.quantization is None:
+            return next(self.parameters()).dtype
+        return next(p for n, p in self.named_parameters() if p.dtype != torch.uint8 and not n.endswith(QSCALE_KEY)).dtype
 
     @property
     def device(self) -> torch.device:
@@ -712,6 +743,8 @@ class Transformer(ModelBase):
         reference, lora.py:140-155); the base weights are not touched, so a second call swaps the fine-tune.
         slot: which adapter set of the bank (set_lora_slots) is replaced; the other slots keep serving."""
         self._check_slot(slot)
+        if self.args.quantization is not None:  # before anything is read from disk
+            raise NotImplementedError(FP8_MERGE_REFUSAL)
         lora_path = Path(lora_path)
         assert lora_path.is_file(), f"{lora_path} does not exist or is not a file"
         self._load_lora_state_dict(safetensors.torch.load_file(str(lora_path)), scaling=scaling, slot=slot)
@@ -733,6 +766,8 @@ class Transformer(ModelBase):
         assert all("lora" in key for key in lora_state_dict.keys())
         if self.args.lora is not None:
             return self._assign_lora(lora_state_dict, slot)
+        if self.args.quantization is not None:
+            raise NotImplementedError(FP8_MERGE_REFUSAL)
         if self.dtype != torch.bfloat16 or self.device.type != "cuda":
             raise RuntimeError("load_lora: the merge runs on the GPU in bf16 (model must be on the device)")
         logging.info("Loading and merging LoRA weights...")
@@ -783,16 +818,25 @@ class Transformer(ModelBase):
     @staticmethod
     def from_folder(folder: Union[Path, str], max_batch_size: int = 1, num_pipeline_ranks: int = 1,
                     device: Union[torch.device, str] = "cuda", dtype: Optional[torch.dtype] = None,
-                    softmax_fp32: bool = True, backend: Optional[Any] = None) -> "Transformer":
+                    softmax_fp32: bool = True, backend: Optional[Any] = None, quantize: Optional[str] = None) -> "Transformer":
         """params.json + exactly one of consolidated.00.pth / consolidated.safetensors (reference
         transformer.py:297-338).  With safetensors only this rank's tensors are read, straight to `device`
-        (the reference loads the whole file to the host on every rank)."""
+        (the reference loads the whole file to the host on every rank).
+
+        A folder whose params.json has a `quantization` block (quant.quantize_checkpoint) builds Fp8Linear layers and binds the
+        e4m3 bytes and row scales as they are.  quantize="fp8_e4m3" does the same to a bf16 safetensors folder while it loads:
+        each linear is quantised on the device as it arrives, so the bf16 model is never resident."""
         folder = Path(folder)
+        check_quantize_arg(quantize)
         with open(folder / "params.json", "r") as f:
             model_args = TransformerArgs.from_dict(json.load(f))
         model_args.max_batch_size = max_batch_size
         if model_args.lora is not None:
             refuse_lora_storage(dtype)   # before anything is read from disk
+        on_load = quantize is not None and model_args.quantization is None  # (an already quantised folder loads as it is)
+        if on_load:
+            model_args.quantization = QuantizationArgs(QFORMAT_FP8_E4M3)
+        refuse_fp8_combinations(model_args, dtype)  # before anything is read from disk
         pipeline_rank = torch.distributed.get_rank() if num_pipeline_ranks > 1 else 0
         with torch.device("meta"):
             model = Transformer(model_args, pipeline_rank=pipeline_rank, num_pipeline_ranks=num_pipeline_ranks,
@@ -802,6 +846,8 @@ class Transformer(ModelBase):
         assert pt_file.exists() or st_file.exists(), f"Make sure either {pt_file} or {st_file} exists"
         assert not (pt_file.exists() and st_file.exists()), f"Both {pt_file} and {st_file} cannot exist"
         if pt_file.exists():
+            if model_args.quantization is not None:
+                raise NotImplementedError("FP8 weight-only models load from consolidated.safetensors (a .pth checkpoint is not implemented)")
             loaded = torch.load(str(pt_file), mmap=True)
             model.load_state_dict(loaded, assign=True, strict=True)
             return model.to(device=device, dtype=dtype)
@@ -812,10 +858,22 @@ class Transformer(ModelBase):
         loaded = {}
         with safetensors.safe_open(str(st_file), framework="pt", device=str(device)) as f:
             for k in f.keys():
+                if k.endswith(QSCALE_ACT_KEY):
+                    raise ValueError(f"Unexpected key {k} (per-tensor activation scales: FP8 activations are not implemented)")
                 if k in wanted or k in plain:
-                    loaded[k] = f.get_tensor(k)
+                    if on_load:  # one tensor at a time: a linear becomes its e4m3 bytes and row scales, the rest passes
+                        loaded.update(quantize_state_tensor(k, f.get_tensor(k)))
+                    else:
+                        loaded[k] = f.get_tensor(k)
                 else:
                     model._check_foreign_key(k)
+        if model_args.quantization is not None:
+            # bytes as uint8 (no dtype cast can touch them) and fp32 [out] row scales (a scalar or [1] is broadcast)
+            for name, mod in model.named_modules():
+                if isinstance(mod, Fp8Linear) and name + ".weight" in loaded:
+                    assert name + "." + QSCALE_KEY in loaded, f"checkpoint is missing {name}.{QSCALE_KEY}"
+                    loaded[name + ".weight"] = weight_bytes(loaded[name + ".weight"])
+                    loaded[name + "." + QSCALE_KEY] = expand_scale(loaded[name + "." + QSCALE_KEY], mod.out_features)
         have = set(loaded) | {k.replace(".weight", ".linear.weight") for k in loaded if k in plain}
         missing = {k for k in wanted - have if ".lora_A." not in k and ".lora_B." not in k}  # absent adapters are not "missing"
         assert not missing, f"checkpoint is missing {sorted(missing)[:4]}..."

@@ -10,10 +10,11 @@ import torch
 from torch import nn
 
 from . import _hip
-from .args import LoraArgs, MoeArgs
+from .args import LoraArgs, MoeArgs, QuantizationArgs
 from .cache import CacheView
 from .lora import LoRALinear, maybe_lora
 from .moe import MoeLayer
+from .quant import FP8_LORA_REFUSAL, FP8_MOE_REFUSAL, Fp8Linear, linear_fp8
 
 LORA_MOE_REFUSAL = ("un-merged LoRA on a MoE model (adapters inside the experts) is not implemented; merge the adapter into the "
                     "checkpoint first (what the reference's default CLI path does, lora.py:118-139)")
@@ -24,6 +25,15 @@ def _no_lora(lora: Optional[LoraArgs], moe: Optional[MoeArgs]) -> None:
     forward, `_hip.lora_linear` / `HipStackBackend`)."""
     if lora is not None and moe is not None:
         raise NotImplementedError(LORA_MOE_REFUSAL)
+
+
+def _linear_cls(lora: Optional[LoraArgs], quantization: Optional[QuantizationArgs]):
+    """nn.Linear, LoRALinear (un-merged adapters) or Fp8Linear (weight-only FP8); the two do not combine."""
+    if quantization is not None:
+        if lora is not None:
+            raise NotImplementedError(FP8_LORA_REFUSAL)
+        return Fp8Linear
+    return maybe_lora(lora)
 
 
 def _adapters(*mods):
@@ -47,9 +57,10 @@ class FeedForward(nn.Module):
     """w2( silu(w1 x) * w3 x ) with bf16 rounding after every step (reference transformer_layers.py:96-106):
     gate/up projections + SiLU*mul are one kernel, the down projection another."""
 
-    def __init__(self, dim: int, hidden_dim: int, lora: Optional[LoraArgs] = None):
+    def __init__(self, dim: int, hidden_dim: int, lora: Optional[LoraArgs] = None,
+                 quantization: Optional[QuantizationArgs] = None):
         super().__init__()
-        linear = maybe_lora(lora)
+        linear = _linear_cls(lora, quantization)
         self.w1 = linear(dim, hidden_dim, bias=False)
         self.w2 = linear(hidden_dim, dim, bias=False)
         self.w3 = linear(dim, hidden_dim, bias=False)
@@ -59,6 +70,8 @@ class FeedForward(nn.Module):
             a, b = _adapters(self.w1, self.w3)
             hid = _hip.lora_linear(x, (self.w1.weight, self.w3.weight), a, b, self.w1.scaling, _hip.EPI_SWIGLU)
             return self.w2(hid)
+        if isinstance(self.w1, Fp8Linear):  # the same two launches on e4m3 weights (csrc/gemv_w8.hip)
+            return self.w2(linear_fp8(x, (self.w1, self.w3), _hip.EPI_SWIGLU))
         hid = _hip.linear(x, (self.w1.weight, self.w3.weight), _hip.EPI_SWIGLU)
         return _hip.linear(hid, (self.w2.weight,), _hip.EPI_STORE)
 
@@ -68,12 +81,13 @@ class Attention(nn.Module):
     matrices, GQA is resolved inside the attention kernels (no repeat_kv), and the three xformers masks
     are the kernels' position test."""
 
-    def __init__(self, dim: int, n_heads: int, head_dim: int, n_kv_heads: int, lora: Optional[LoraArgs] = None):
+    def __init__(self, dim: int, n_heads: int, head_dim: int, n_kv_heads: int, lora: Optional[LoraArgs] = None,
+                 quantization: Optional[QuantizationArgs] = None):
         super().__init__()
         self.n_heads, self.head_dim, self.n_kv_heads = n_heads, head_dim, n_kv_heads
         self.repeats = n_heads // n_kv_heads
         self.scale = head_dim ** -0.5
-        linear = maybe_lora(lora)
+        linear = _linear_cls(lora, quantization)
         self.wq = linear(dim, n_heads * head_dim, bias=False)
         self.wk = linear(dim, n_kv_heads * head_dim, bias=False)
         self.wv = linear(dim, n_kv_heads * head_dim, bias=False)
@@ -88,7 +102,14 @@ class Attention(nn.Module):
         cs = torch.view_as_real(freqs_cis).contiguous()  # rows already gathered by position (transformer.py:199)
         rows = torch.arange(T, dtype=torch.int32, device=x.device)
         lora = isinstance(self.wq, LoRALinear)
-        if lora:  # q | k | v with their three adapters: base product, lora_down, lora_up; RoPE as its own pass
+        fp8 = isinstance(self.wq, Fp8Linear)
+        if fp8 and T <= _hip.GEMV_MAX_T:  # the plain model's launches on e4m3 weights (csrc/gemv_w8.hip)
+            qkv = _hip.qkv_rope_kvwrite_w8(x, self.wq.weight, self.wk.weight, self.wv.weight, self.wq.qscale_weight,
+                                           self.wk.qscale_weight, self.wv.qscale_weight, Dh, cs, rows)
+        elif fp8:
+            qkv = linear_fp8(x, (self.wq, self.wk, self.wv), _hip.EPI_STORE)
+            _hip.rope_inplace(qkv, H, Hkv, Dh, cs, rows)
+        elif lora:  # q | k | v with their three adapters: base product, lora_down, lora_up; RoPE as its own pass
             a, b = _adapters(self.wq, self.wk, self.wv)
             qkv = _hip.lora_linear(x, (self.wq.weight, self.wk.weight, self.wv.weight), a, b, self.wq.scaling, _hip.EPI_STORE)
             _hip.rope_inplace(qkv, H, Hkv, Dh, cs, rows)
@@ -110,7 +131,7 @@ class Attention(nn.Module):
             else:
                 cache.update(qkv[:, nq:nq + nkv], qkv[:, nq + nkv:])
                 out = _hip.attn_decode(qkv, cache.cache_k, cache.cache_v, H, b.tok_pos)
-        if lora:
+        if lora or fp8:
             return self.wo(out)
         return _hip.linear(out, (self.wo.weight,), _hip.EPI_STORE)
 
@@ -119,12 +140,16 @@ class TransformerBlock(nn.Module):
     """Pre-norm residual block (reference transformer_layers.py:123-169)."""
 
     def __init__(self, dim: int, hidden_dim: int, n_heads: int, n_kv_heads: int, head_dim: int, norm_eps: float,
-                 lora: Optional[LoraArgs] = None, moe: Optional[MoeArgs] = None):
+                 lora: Optional[LoraArgs] = None, moe: Optional[MoeArgs] = None,
+                 quantization: Optional[QuantizationArgs] = None):
         super().__init__()
         _no_lora(lora, moe)
+        if quantization is not None and moe is not None:
+            raise NotImplementedError(FP8_MOE_REFUSAL)
         self.n_heads = n_heads
         self.dim = dim
-        self.attention = Attention(dim=dim, n_heads=n_heads, head_dim=head_dim, n_kv_heads=n_kv_heads, lora=lora)
+        self.attention = Attention(dim=dim, n_heads=n_heads, head_dim=head_dim, n_kv_heads=n_kv_heads, lora=lora,
+                                   quantization=quantization)
         self.attention_norm = RMSNorm(dim, eps=norm_eps)
         self.ffn_norm = RMSNorm(dim, eps=norm_eps)
         self.feed_forward: nn.Module
@@ -133,7 +158,7 @@ class TransformerBlock(nn.Module):
                 experts=[FeedForward(dim=dim, hidden_dim=hidden_dim, lora=lora) for _ in range(moe.num_experts)],
                 gate=nn.Linear(dim, moe.num_experts, bias=False), moe_args=moe)
         else:
-            self.feed_forward = FeedForward(dim=dim, hidden_dim=hidden_dim, lora=lora)
+            self.feed_forward = FeedForward(dim=dim, hidden_dim=hidden_dim, lora=lora, quantization=quantization)
 
     def forward(self, x: torch.Tensor, freqs_cis: torch.Tensor, cache: Optional[CacheView] = None,
                 mask=None) -> torch.Tensor:
