@@ -1,25 +1,18 @@
-// Weight-streaming GEMV kernels for M <= 8 tokens (decode): HBM-bound, one pass over the weights.
+// Weight-streaming GEMV launches for M <= 8 tokens (decode) on bf16 weight rows, and the MoE down-projection kernel.
 //
 // Replaces, per decode token and layer, the reference's separate launches for RMSNorm
 // (transformer_layers.py:115-120), the q/k/v/o and w1/w2/w3 nn.Linear GEMVs (:66,:93,:105-106), RoPE
 // (rope.py:13-23), the ring write (cache.py:83-92), the residual adds (:166,:168) and silu*mul.
 //
-// Structure (cdna_hip_programming.md "GEMV / M<=16 decode weights"): weights go straight HBM -> VGPR
-// with 16-byte non-temporal loads in batches of 8 per lane; a wave always has two batches (16 KiB) in
-// flight, across the prologue and across unit boundaries (the load cursor runs over the flattened
-// (unit, batch) sequence, two batches ahead of the FMAs).  The (optionally RMS-normalised) activation
-// vector lives in LDS; its loads are issued before the first weight batch so the prologue finishes under
-// the HBM latency of the weights.  A wave owns "units" (a pair of weight rows, or one row for small N)
-// strided over the whole grid, so at any instant the chip streams one contiguous weight region.
+// The kernels are gemv_core::gemv_body on the W16 format; the design notes are in gemv_core.cuh.
 #include <cstdlib>
 
 #include "common.cuh"
 
 // A second compile with -DGEMV_F16=1 (build_native.py: gemv_f16.o) is the same weight-streaming kernel for fp16 storage:
 // v_dot2_f32_f16 for v_dot2c_f32_bf16 and half conversions / rounding points, under launch_gemv_f16 (api.hip: decode steps of
-// fp16 models in mi_forward_generic).  Every 16-bit access of gemv_core.cuh goes through the helpers renamed here; the default
-// compile is untouched by this block (ISA hash checked) and gemv_core.cuh itself - shared with the frozen decode engine - is
-// not edited.
+// fp16 models in mi_forward_generic).  Every 16-bit access of gemv_core.cuh goes through the helpers renamed here (its e4m3 code is
+// parsed but not instantiated in that compile); the default compile is untouched by this block.
 #ifndef GEMV_F16
 #define GEMV_F16 0
 #endif
@@ -60,11 +53,12 @@ namespace {
 
 using namespace gemv_core;
 
-// DMA: the activation rows go to LDS by LDS-DMA (gemv_core.cuh; instantiated for 2..8 tokens, picked when they do not fit the registers)
+// ROWS: rows per unit, always 2; DMA: the activation rows go to LDS by LDS-DMA (instantiated for 2..8 tokens, picked when they do
+// not fit the registers)
 template <int TT, int MODE, int ROWS, bool DMA>
 __global__ __launch_bounds__(256, (TT == 1 ? 4 : (TT <= 3 ? 3 : 2))) void gemv_kernel(GemvArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  gemv_body<TT, MODE, ROWS, DMA>(a, smem, blockIdx.x, gridDim.x, blockIdx.y);
+  gemv_body<W16, TT, MODE, ROWS, DMA>(a, nullptr, smem, blockIdx.x, gridDim.x, blockIdx.y);
 }
 
 // Blocks of 5 .. 7 waves for the plain modes at one token (gemv_core.cuh NWV): row counts that 4-wave blocks cannot split evenly
@@ -72,7 +66,7 @@ __global__ __launch_bounds__(256, (TT == 1 ? 4 : (TT <= 3 ? 3 : 2))) void gemv_k
 template <int MODE, int NWV>
 __global__ __launch_bounds__(NWV * 64, 4) void gemv_kernel_nw(GemvArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  gemv_body<1, MODE, 2, false, NWV>(a, smem, blockIdx.x, gridDim.x, blockIdx.y);
+  gemv_body<W16, 1, MODE, 2, false, NWV>(a, nullptr, smem, blockIdx.x, gridDim.x, blockIdx.y);
 }
 
 // MoE down-projection + combine for one token per blockIdx.y (moe.py:28-32 at decode):
@@ -88,7 +82,7 @@ __global__ __launch_bounds__(256) void moe_w2_kernel(GemvArgs a) {
   const int nwaves = gridDim.x * 4;
   const int units = (a.N + 1) >> 1;
   constexpr int U = BATCH / 2;
-  const int nch = (a.K + 511) >> 9;
+  const int nch = (a.K + (1 << W16::SHIFT) - 1) >> W16::SHIFT;
   const int nb = (nch + U - 1) / U;
 
   int eid[TOPK];
@@ -128,10 +122,10 @@ __global__ __launch_bounds__(256) void moe_w2_kernel(GemvArgs a) {
 #pragma unroll
     for (int k = 1; k < TOPK; ++k) base = (kl == k) ? w2[k] : base;
     const int ue = live ? ul : 0;
-    RowPair r;
-    r.a = live ? base + (size_t)(2 * ue) * a.K : a.x;
-    r.b = live ? ((2 * ue + 1 < a.N) ? base + (size_t)(2 * ue + 1) * a.K : r.a) : a.x;
-    load_batch<2>(r, live ? jl * U : 0, live ? a.K : 8, live ? lane : 0, buf);
+    Rows<W16, 2> r;
+    r.p[0] = live ? base + (size_t)(2 * ue) * a.K : a.x;
+    r.p[1] = live ? ((2 * ue + 1 < a.N) ? base + (size_t)(2 * ue + 1) * a.K : r.p[0]) : a.x;
+    load_batch<W16, 2>(r, live ? jl * U : 0, live ? a.K : 8, live ? lane : 0, buf);
     if (live && ++jl == nb) {
       jl = 0;
       if (++kl == TOPK) {
@@ -151,17 +145,16 @@ __global__ __launch_bounds__(256) void moe_w2_kernel(GemvArgs a) {
   asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
   __syncthreads();
 
-  Acc<1> acc;
-  acc.v[0][0] = acc.v[1][0] = 0.f;
+  float acc[2][1] = {{0.f}, {0.f}};
   int jc = 0, kc = 0;
   float r0 = 0.f, r1 = 0.f;
   auto step = [&](u32x4 (&buf)[BATCH]) {
-    fma_batch<1, 2>(buf, jc * U, xs + (size_t)kc * a.K, a.K, lane, acc);
+    fma_batch<W16, 1, 2>(buf, jc * U, xs + (size_t)kc * a.K, a.K, lane, acc);
     issue(buf);
     if (++jc == nb) {
       jc = 0;
-      const float y0 = wave_sum(acc.v[0][0]), y1 = wave_sum(acc.v[1][0]);
-      acc.v[0][0] = acc.v[1][0] = 0.f;
+      const float y0 = wave_sum(acc[0][0]), y1 = wave_sum(acc[1][0]);
+      acc[0][0] = acc[1][0] = 0.f;
       float w = ew[0];
 #pragma unroll
       for (int k = 1; k < TOPK; ++k) w = (kc == k) ? ew[k] : w;
@@ -189,42 +182,15 @@ __global__ __launch_bounds__(256) void moe_w2_kernel(GemvArgs a) {
   }
 }
 
-template <int TT, int MODE, int ROWS, bool DMA>
-hipError_t launch_tt(const GemvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-  if (lds > 64 * 1024) {  // more than the default dynamic-LDS limit: an opt-in per function AND per device
-    static bool attr_set[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_kernel<TT, MODE, ROWS, DMA>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)GEMV_LDS_BUDGET + 1024);
-      if (e != hipSuccess) return e;
-      if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
-  }
-  hipLaunchKernelGGL((gemv_kernel<TT, MODE, ROWS, DMA>), grid, dim3(256), lds, s, a);
-  return hipGetLastError();
-}
-// Rows that fit the prologue's register set (gemv_core.cuh: 4 x 256 pieces with a fused RMSNorm, 8 x 256 without) are staged
-// through registers; 2..8 rows that do not, by LDS-DMA.
-template <int TT, int MODE, int ROWS>
-hipError_t launch_stage(const GemvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-  if constexpr (TT > 1) {
-    constexpr bool norm_mode = MODE == GEMV_QKV_ROPE || MODE == GEMV_SWIGLU || MODE == GEMV_LOGITS || MODE == GEMV_MOE_W13;  // (gemv_body's kNormMode)
-    if ((size_t)TT * (a.K >> 3) > (norm_mode ? 4u : 8u) * 256u) return launch_tt<TT, MODE, ROWS, true>(a, grid, lds, s);
-  }
-  return launch_tt<TT, MODE, ROWS, false>(a, grid, lds, s);
-}
-template <int MODE, int ROWS>
+template <int MODE>
 hipError_t launch_mode(const GemvArgs& a, int TT, dim3 grid, size_t lds, hipStream_t s) {
-  switch (TT) {
-    case 1: return launch_stage<1, MODE, ROWS>(a, grid, lds, s);
-    case 2: return launch_stage<2, MODE, ROWS>(a, grid, lds, s);
-    case 3: return launch_stage<3, MODE, ROWS>(a, grid, lds, s);
-    case 4: return launch_stage<4, MODE, ROWS>(a, grid, lds, s);
-    case 6: return launch_stage<6, MODE, ROWS>(a, grid, lds, s);
-    default: return launch_stage<8, MODE, ROWS>(a, grid, lds, s);
-  }
+  return for_tt(TT, [&](auto tt) {
+    constexpr int T = decltype(tt)::value;
+    if constexpr (T > 1) {
+      if (stage_by_dma(MODE, T, a.K)) return launch_lds<gemv_kernel<T, MODE, 2, true>>(a, grid, lds, s);
+    }
+    return launch_lds<gemv_kernel<T, MODE, 2, false>>(a, grid, lds, s);
+  });
 }
 
 template <int MODE>
@@ -238,8 +204,6 @@ hipError_t launch_nw(const GemvArgs& a, int nw, dim3 grid, size_t lds, hipStream
   return hipGetLastError();
 }
 
-int g_gemv_max_blocks = 0;
-
 }  // namespace
 
 int gemv_max_tokens(int K) {
@@ -250,34 +214,13 @@ int gemv_max_tokens(int K) {
 
 // One launch; a.T must be <= gemv_max_tokens(K).
 hipError_t launch_gemv(const GemvArgs& a, hipStream_t s) {
-  if (g_gemv_max_blocks == 0) {
-    const char* e = getenv("MI_GEMV_MAX_BLOCKS");
-    g_gemv_max_blocks = e ? atoi(e) : 2 * device_cus();  // 2 blocks per CU measured best on MI355X
-    if (g_gemv_max_blocks <= 0) g_gemv_max_blocks = 2 * device_cus();
-  }
   const bool pair_mode = !(a.mode == GEMV_SWIGLU || a.mode == GEMV_MOE_W13);
-  // single-row units when row pairs would leave CUs without a full set of waves (256 CUs x 4 blocks x 4 waves)
-  static int single_below = -1;  // MI_GEMV_SINGLE_BELOW: row-pair count under which units become single rows
-  if (single_below < 0) {
-    const char* e = getenv("MI_GEMV_SINGLE_BELOW");
-    single_below = e ? atoi(e) : 0;  // measured: row pairs are at least as fast on MI355X
-  }
-  const bool single = pair_mode && a.mode != GEMV_QKV_ROPE && a.mode != GEMV_MOE_W2 && (a.N + 1) / 2 < single_below;
-  const int units = pair_mode ? (single ? a.N : (a.N + 1) / 2) : a.N;
-  // Persistent-style grid: every wave gets the same number k of units (no partially filled last round of blocks; the
-  // two-batch load pipeline runs across a wave's units).  Preferred: the smallest k for which the block count is a
-  // multiple of the 256 CUs (even load per CU), at most 4 per CU, and divides the units exactly - e.g. W1|W3: 14336
-  // units -> 512 blocks x 4 waves x 7 units; q|k|v: 3072 units -> 768 blocks x 1.  Otherwise the smallest k that fits
-  // g_gemv_max_blocks (512 = 2 blocks per CU measured best on MI355X).
+  const int units = pair_mode ? (a.N + 1) / 2 : a.N;
   const int cus = device_cus();
-  int blocks = 0;
-  for (int k = 1; k <= 64 && !blocks; ++k) {
-    const int b = (units + 4 * k - 1) / (4 * k);
-    if (b <= 4 * cus && b % cus == 0 && b * 4 * k == units && (b <= g_gemv_max_blocks || k == 1)) blocks = b;
-  }
+  int blocks = even_blocks(units, cus);
   int nw = 4;  // waves per block
   if (!blocks) {
-    // No even split over 4-wave blocks (Mistral-Nemo's Wo / W2: 5120 rows = 2560 pairs = 256 CUs x 10).  The fallback below
+    // No even split over 4-wave blocks (Mistral-Nemo's Wo / W2: 5120 rows = 2560 pairs = 256 CUs x 10).  spread_blocks
     // gives 320 blocks - 64 CUs with two blocks, 192 with one - and the doubly loaded CUs set the kernel's time at their own
     // ingest rate (W2: 30 us for 147 MB).  One token, plain modes: blocks of 5 .. 7 waves that DO split evenly, all resident.
     static int nw_ok = -1;  // MI_GEMV_NW=0: 4-wave blocks only (A/B testing)
@@ -285,7 +228,7 @@ hipError_t launch_gemv(const GemvArgs& a, hipStream_t s) {
       const char* e = getenv("MI_GEMV_NW");
       nw_ok = e ? atoi(e) : 1;
     }
-    const bool plain1 = nw_ok && a.T == 1 && (a.mode == GEMV_STORE || a.mode == GEMV_RESIDUAL) && !single && a.norm_w == nullptr &&
+    const bool plain1 = nw_ok && a.T == 1 && (a.mode == GEMV_STORE || a.mode == GEMV_RESIDUAL) && a.norm_w == nullptr &&
                         (size_t)a.K * 2 <= 48 * 1024;
     for (int w = 5; plain1 && w <= 7 && nw == 4; ++w)
       for (int k = 1; k <= 16 && nw == 4; ++k) {
@@ -296,11 +239,7 @@ hipError_t launch_gemv(const GemvArgs& a, hipStream_t s) {
         }
       }
   }
-  if (!blocks) {
-    const int k = (units + 4 * g_gemv_max_blocks - 1) / (4 * g_gemv_max_blocks);
-    blocks = (units + 4 * k - 1) / (4 * k);
-  }
-  if (blocks < 1) blocks = 1;
+  if (!blocks) blocks = spread_blocks(units, max_blocks(cus));
   if (a.mode == GEMV_MOE_W2) {
     const size_t lds = (size_t)a.top_k * a.K * 2;
     dim3 grid(blocks, a.T);
@@ -312,28 +251,17 @@ hipError_t launch_gemv(const GemvArgs& a, hipStream_t s) {
     }
     return hipGetLastError();
   }
-  int TT = a.T;
-  if (a.mode == GEMV_MOE_W13) TT = 1;
-  if (TT == 5) TT = 6;
-  if (TT == 7) TT = 8;
-  // [TT][K] activations, 4 x TT partial sums, and (norm modes at TT > 1: the DMA staging path of gemv_core.cuh) K norm weights
-  const size_t lds = (size_t)TT * a.K * 2 + 4 * TT * sizeof(float) + ((TT > 1 && a.norm_w) ? (size_t)a.K * 2 : 0);
-  if (lds > 80 * 1024 && blocks > cus) {  // one such block fits a CU: one block per CU, every wave the same number of units
-    const int k = (units + 4 * cus - 1) / (4 * cus);
-    blocks = (units + 4 * k - 1) / (4 * k);
-  }
-  dim3 grid(blocks, a.mode == GEMV_MOE_W13 ? a.T * a.top_k : 1);
+  const int TT = a.mode == GEMV_MOE_W13 ? 1 : round_tt(a.T);
+  const size_t lds = lds_bytes(TT, a.K, a.norm_w != nullptr);
+  dim3 grid(blocks_for_lds(blocks, units, cus, lds), a.mode == GEMV_MOE_W13 ? a.T * a.top_k : 1);
   if (nw != 4) return a.mode == GEMV_STORE ? launch_nw<GEMV_STORE>(a, nw, grid, lds, s) : launch_nw<GEMV_RESIDUAL>(a, nw, grid, lds, s);
   switch (a.mode) {
-    case GEMV_STORE:
-      return single ? launch_mode<GEMV_STORE, 1>(a, TT, grid, lds, s) : launch_mode<GEMV_STORE, 2>(a, TT, grid, lds, s);
-    case GEMV_RESIDUAL:
-      return single ? launch_mode<GEMV_RESIDUAL, 1>(a, TT, grid, lds, s) : launch_mode<GEMV_RESIDUAL, 2>(a, TT, grid, lds, s);
-    case GEMV_LOGITS:
-      return single ? launch_mode<GEMV_LOGITS, 1>(a, TT, grid, lds, s) : launch_mode<GEMV_LOGITS, 2>(a, TT, grid, lds, s);
-    case GEMV_SWIGLU: return launch_mode<GEMV_SWIGLU, 2>(a, TT, grid, lds, s);
-    case GEMV_QKV_ROPE: return launch_mode<GEMV_QKV_ROPE, 2>(a, TT, grid, lds, s);
-    case GEMV_MOE_W13: return launch_mode<GEMV_MOE_W13, 2>(a, 1, grid, lds, s);
+    case GEMV_STORE: return launch_mode<GEMV_STORE>(a, TT, grid, lds, s);
+    case GEMV_RESIDUAL: return launch_mode<GEMV_RESIDUAL>(a, TT, grid, lds, s);
+    case GEMV_LOGITS: return launch_mode<GEMV_LOGITS>(a, TT, grid, lds, s);
+    case GEMV_SWIGLU: return launch_mode<GEMV_SWIGLU>(a, TT, grid, lds, s);
+    case GEMV_QKV_ROPE: return launch_mode<GEMV_QKV_ROPE>(a, TT, grid, lds, s);
+    case GEMV_MOE_W13: return launch_mode<GEMV_MOE_W13>(a, 1, grid, lds, s);
     default: return hipErrorInvalidValue;
   }
 }

@@ -1,53 +1,110 @@
-// Core of the weight-streaming GEMV (see gemv.hip for the design notes): batch loads, FMA, activation staging and the
-// per-wave unit loop.
+// Core of the weight-streaming GEMV for M <= 8 tokens (decode): HBM-bound, one pass over the weights.  One unit loop
+// (gemv_body) for 16-bit weight rows (gemv.hip: bf16, and fp16 in its -DGEMV_F16=1 compile) and for e4m3 rows with fp32 row
+// scales (gemv_w8.hip); the MoE down-projection (gemv.hip) uses the same batch loads and FMAs.  Host side: the launch plan.
+//
+// Structure (cdna_hip_programming.md "GEMV / M<=16 decode weights"): weights go straight HBM -> VGPR with 16-byte
+// non-temporal loads in batches of 8 per lane; a wave always has two batches (16 KiB) in flight, across the prologue and
+// across unit boundaries (the load cursor runs over the flattened (unit, batch) sequence, two batches ahead of the FMAs).
+// The (optionally RMS-normalised) activation rows live in LDS; their loads are issued before the first weight batch so the
+// prologue finishes under the HBM latency of the weights.  A wave owns "units" (one or two pairs of weight rows) strided over
+// the whole grid, so at any instant the chip streams one contiguous weight region.
 #pragma once
+#include <cstdlib>
+#include <type_traits>
+
 #include "common.cuh"
 #include "kernels.h"
 
 namespace gemv_core {
 
-constexpr int BATCH = 8;  // 16-byte loads per lane per batch (ROWS rows x BATCH/ROWS chunks); two batches in flight
+constexpr int BATCH = 8;  // 16-byte loads per lane per batch (NR rows x BATCH/NR chunks); two batches in flight
 
-template <int TT>
-struct Acc {
-  float v[2][TT];
+// ---- weight formats.  PIECE: weights per 16-byte piece; a chunk is one wave instruction = 64 pieces = 1 << SHIFT weights.
+struct W16 {  // bf16 rows (fp16 in the GEMV_F16 compile)
+  typedef bf16_t elem;
+  static constexpr int PIECE = 8, SHIFT = 9;
+  static constexpr bool SCALED = false;
+};
+// OCP e4m3 bytes; the real-valued weight is scale[r] * e4m3(W[r, k]).  Per output row acc = sum_k e4m3(W[r, k]) * x[k] in fp32
+// and y = acc * scale[r] in fp32 enters the epilogue where acc enters it for 16-bit rows.  K % 16 == 0.
+struct WE4m3 {
+  typedef uint8_t elem;
+  static constexpr int PIECE = 16, SHIFT = 10;
+  static constexpr bool SCALED = true;
 };
 
-struct RowPair {
-  const bf16_t* a;
-  const bf16_t* b;  // nullptr when the unit has one row
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+
+// four e4m3 bytes (k .. k + 3) -> fp32 (k, k + 1) and (k + 2, k + 3): v_cvt_pk_f32_fp8 on either half of the dword
+__device__ __forceinline__ void cvt4_e4m3_f32(uint32_t w, f32x2_t& lo, f32x2_t& hi) {
+  lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+  hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+}
+// ... -> the bf16 pairs (k, k + 1) and (k + 2, k + 3).  Every finite e4m3 value is exact in bf16, so the high halves of the two
+// fp32 results, packed by v_perm_b32, are an exact bf16 pair for v_dot2c_f32_bf16.  Per dword of weights: 2 converts + 2 perms
+// (shared by all tokens) + 2 dot2 per token, against 4 unpacks + 4 FMAs per token for the plain-fp32 form.
+__device__ __forceinline__ void cvt4_e4m3(uint32_t w, uint32_t& p01, uint32_t& p23) {
+  f32x2_t lo, hi;
+  cvt4_e4m3_f32(w, lo, hi);
+  // bytes 2, 3 of the first operand's partner (S1) below bytes 2, 3 of S0: (S1 >> 16) | (S0 & 0xffff0000)
+  p01 = __builtin_amdgcn_perm(__float_as_uint(lo[1]), __float_as_uint(lo[0]), 0x07060302u);
+  p23 = __builtin_amdgcn_perm(__float_as_uint(hi[1]), __float_as_uint(hi[0]), 0x07060302u);
+}
+
+template <class F, int NR>
+struct Rows {
+  const typename F::elem* p[NR];
 };
 
-// One batch = chunks [c0, c0 + BATCH/ROWS) of each of the unit's ROWS rows: always exactly BATCH unconditional loads.
-// Chunk offsets past K are clamped to the row's last 16 bytes (fma_batch skips them) and a missing second row aliases
-// the first (the epilogue drops it).  Never a `cond ? load : 0`: that makes hipcc branch around each load and wait
+// One batch = chunks [c0, c0 + BATCH/NR) of each of the unit's NR rows: always exactly BATCH unconditional loads.
+// Chunk offsets past K are clamped to the row's last 16 bytes (fma_batch skips them) and a missing last row aliases
+// its partner (the epilogue drops it).  Never a `cond ? load : 0`: that makes hipcc branch around each load and wait
 // vmcnt(0) after it (cdna_hip_programming.md, ".s-level traps" (c)).
-template <int ROWS>
-__device__ __forceinline__ void load_batch(const RowPair& r, int c0, int K, int lane, u32x4 (&buf)[BATCH]) {
-  constexpr int U = BATCH / ROWS;
+template <class F, int NR>
+__device__ __forceinline__ void load_batch(const Rows<F, NR>& r, int c0, int K, int lane, u32x4 (&buf)[BATCH]) {
+  constexpr int U = BATCH / NR;
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    const int e = min(((c0 + u) * 64 + lane) * 8, K - 8);
-    buf[u] = ld16_nt(r.a + e);
-    if (ROWS == 2) buf[U + u] = ld16_nt(r.b + e);
+    const int e = min(((c0 + u) * 64 + lane) * F::PIECE, K - F::PIECE);
+#pragma unroll
+    for (int i = 0; i < NR; ++i) buf[i * U + u] = ld16_nt(r.p[i] + e);
   }
 }
 
-template <int TT, int ROWS>
-__device__ __forceinline__ void fma_batch(const u32x4 (&buf)[BATCH], int c0, const bf16_t* xs, int K, int lane,
-                                          Acc<TT>& acc) {
-  constexpr int U = BATCH / ROWS;
+// xs: the activation rows in LDS, [TT][K] 16-bit
+template <class F, int TT, int NR>
+__device__ __forceinline__ void fma_batch(const u32x4 (&buf)[BATCH], int c0, const bf16_t* xs, int K, int lane, float (&acc)[NR][TT]) {
+  constexpr int U = BATCH / NR;
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    const int e = ((c0 + u) * 64 + lane) * 8;
+    const int e = ((c0 + u) * 64 + lane) * F::PIECE;
     if (e < K) {
+      if constexpr (F::PIECE == 8) {
 #pragma unroll
-      for (int t = 0; t < TT; ++t) {
-        const u32x4 xv = *reinterpret_cast<const u32x4*>(xs + (size_t)t * K + e);
+        for (int t = 0; t < TT; ++t) {
+          const u32x4 xv = *reinterpret_cast<const u32x4*>(xs + (size_t)t * K + e);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          acc.v[0][t] = dot2_bf16(buf[u][i], xv[i], acc.v[0][t]);
-          if (ROWS == 2) acc.v[1][t] = dot2_bf16(buf[U + u][i], xv[i], acc.v[1][t]);
+          for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int i = 0; i < NR; ++i) acc[i][t] = dot2_bf16(buf[i * U + u][c], xv[c], acc[i][t]);
+        }
+      } else {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {  // halves of the piece: 8 weights = 2 dwords against one 16-byte piece of x
+          uint32_t p[NR][4];
+#pragma unroll
+          for (int i = 0; i < NR; ++i) {
+            cvt4_e4m3(buf[i * U + u][2 * h], p[i][0], p[i][1]);
+            cvt4_e4m3(buf[i * U + u][2 * h + 1], p[i][2], p[i][3]);
+          }
+#pragma unroll
+          for (int t = 0; t < TT; ++t) {
+            const u32x4 xv = *reinterpret_cast<const u32x4*>(xs + (size_t)t * K + e + 8 * h);
+#pragma unroll
+            for (int i = 0; i < NR; ++i)
+#pragma unroll
+              for (int c = 0; c < 4; ++c) acc[i][t] = dot2_bf16(p[i][c], xv[c], acc[i][t]);
+          }
         }
       }
     }
@@ -154,7 +211,7 @@ __device__ __forceinline__ void x_finish(bool in_regs, XRegs<NX, NW>& xr, bf16_t
     }
   } else if constexpr (DMA) {
     // the rows (and norm weights) were sent to LDS by x_issue's DMAs.  vmcnt retires in order and EXACTLY the two weight batches
-    // (2 x BATCH unconditional loads: gemv_body) were issued behind them: vmcnt(2 * BATCH) = the DMAs have landed, the weights
+    // (2 x BATCH unconditional loads: gemv_body, moe_w2_kernel) were issued behind them: vmcnt(2 * BATCH) = the DMAs have landed, the weights
     // stay in flight under the passes below, which read LDS only.
     static_assert(BATCH == 8, "the wait below counts the two weight batches");
     asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
@@ -243,66 +300,60 @@ __device__ __forceinline__ void x_finish(bool in_regs, XRegs<NX, NW>& xr, bf16_t
   __syncthreads();
 }
 
-__device__ __forceinline__ const bf16_t* seg_row(const GemvArgs& a, int r) {
-  if (r < a.n0) return a.w0 + (size_t)r * a.K;
-  if (r < a.n1) return a.w1 + (size_t)(r - a.n0) * a.K;
-  return a.w2 + (size_t)(r - a.n1) * a.K;
+// Row r of up to three matrices side by side (segment ends n0, n1) picks the expression of its own matrix.  A macro, so that
+// only the picked expression is evaluated: the e4m3 kernels then keep scalar branches around the three forms; a function
+// taking the three pointers by value makes s_cselect chains there and a slower Wo kernel (profiles/EXPERIMENTS.md).
+#define GEMV_SEG_PICK(r, n0, n1, e0, e1, e2) ((r) < (n0) ? (e0) : ((r) < (n1) ? (e1) : (e2)))
+
+template <class E>
+__device__ __forceinline__ const E* seg_row(const GemvArgs& a, int r) {
+  return GEMV_SEG_PICK(r, a.n0, a.n1, reinterpret_cast<const E*>(a.w0) + (size_t)r * a.K,
+                       reinterpret_cast<const E*>(a.w1) + (size_t)(r - a.n0) * a.K, reinterpret_cast<const E*>(a.w2) + (size_t)(r - a.n1) * a.K);
 }
 
-template <int MODE, int ROWS>
-__device__ __forceinline__ RowPair unit_rows(const GemvArgs& a, int u, const bf16_t* e1, const bf16_t* e3) {
-  RowPair r;
-  if (MODE == GEMV_SWIGLU) {
-    r.a = a.w0 + (size_t)u * a.K;
-    r.b = a.w1 + (size_t)u * a.K;
-  } else if (MODE == GEMV_MOE_W13) {
-    r.a = e1 + (size_t)u * a.K;
-    r.b = e3 + (size_t)u * a.K;
-  } else if (ROWS == 1) {
-    r.a = seg_row(a, u);
-    r.b = r.a;
-  } else {
-    r.a = seg_row(a, 2 * u);
-    r.b = (2 * u + 1 < a.N) ? seg_row(a, 2 * u + 1) : r.a;  // odd N: alias, result dropped in the epilogue
-  }
-  return r;
-}
+// the modes that fuse the RMSNorm into the prologue
+constexpr bool norm_mode(int mode) { return mode == GEMV_QKV_ROPE || mode == GEMV_SWIGLU || mode == GEMV_LOGITS || mode == GEMV_MOE_W13; }
 
-// ROWS = rows per unit (2 everywhere except the plain/residual/logits modes on small N, where single-row units
-// double the number of waves so that a 4096-row matrix still fills 256 CUs x 16 waves).
+// F: weight format; TT: token rows staged in LDS; NR = rows per unit: one row pair, or two for e4m3 rows, which are half the
+// bytes, so that the fixed cost of a unit (wave reductions, epilogue, loop bookkeeping) weighs twice as much (launch_gemv_w8).
+// Row pair q: SWIGLU / MOE_W13 = (W1 row q, W3 row q), else output rows (2 q, 2 q + 1).
+// scale: the fp32 row scales of the (up to) three matrices, read by the SCALED formats only.
 // Order: activation loads first (L2 hits), then two weight batches, and the prologue finishes under them.
 // NWV = waves per block: 4; 5 .. 8 for the plain modes (no fused RMSNorm: its passes are written for 256 threads) when the row
 // count has no even split over 4-wave blocks - Mistral-Nemo's 5120 rows are 2560 pairs = 256 CUs x 10 (launch_gemv).
-template <int TT, int MODE, int ROWS, bool DMA, int NWV = 4>
-__device__ __forceinline__ void gemv_body(const GemvArgs& a, char* smem, int block_id, int n_blocks, int problem) {
+template <class F, int TT, int MODE, int NR, bool DMA, int NWV = 4>
+__device__ __forceinline__ void gemv_body(const GemvArgs& a, const float* const* scale, char* smem, int block_id, int n_blocks,
+                                          int problem) {
+  typedef typename F::elem E;
+  constexpr int RP = NR / 2, U = BATCH / NR;
   bf16_t* xs = reinterpret_cast<bf16_t*>(smem);
   float* red = reinterpret_cast<float*>(smem + (size_t)TT * a.K * 2);
-  bf16_t* ws = reinterpret_cast<bf16_t*>(smem + (size_t)TT * a.K * 2 + 16 * TT);  // (launch_gemv reserves it for TT > 1)
+  bf16_t* ws = reinterpret_cast<bf16_t*>(smem + (size_t)TT * a.K * 2 + 16 * TT);  // (lds_bytes reserves it for TT > 1)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably wave-uniform: unit loops become scalar
   const int nwaves = n_blocks * NWV;
   constexpr bool kPairOut = !(MODE == GEMV_SWIGLU || MODE == GEMV_MOE_W13);
-  const int units = kPairOut ? (ROWS == 2 ? (a.N + 1) >> 1 : a.N) : a.N;
-  constexpr int U = BATCH / ROWS;
-  const int nch = (a.K + 511) >> 9;
+  const int npairs = kPairOut ? (a.N + 1) >> 1 : a.N;
+  const int units = (npairs + RP - 1) / RP;
+  const int nch = (a.K + (1 << F::SHIFT) - 1) >> F::SHIFT;
   const int nb = (nch + U - 1) / U;  // batches per unit
 
   // MoE: blockIdx.y is the problem (token, slot); pick this problem's expert and input row
   const bf16_t* x = a.x;
-  const bf16_t *e1 = nullptr, *e3 = nullptr;
+  const E *e1 = nullptr, *e3 = nullptr;
   char* outp = reinterpret_cast<char*>(a.out);
   if (MODE == GEMV_MOE_W13) {
     const int prob = problem;
     const int e = a.sel_idx[prob];
-    e1 = reinterpret_cast<const bf16_t*>(a.expert_tab[e * 3 + 0]);
-    e3 = reinterpret_cast<const bf16_t*>(a.expert_tab[e * 3 + 2]);
+    e1 = reinterpret_cast<const E*>(a.expert_tab[e * 3 + 0]);
+    e3 = reinterpret_cast<const E*>(a.expert_tab[e * 3 + 2]);
     x = a.x + (size_t)(prob / a.top_k) * a.ldx;
     outp += (size_t)prob * a.ldo * 2;
   }
   const int T = (MODE == GEMV_MOE_W13) ? 1 : a.T;
 
   // 1. activation (and norm weight) loads first, 2. two weight batches, 3. finish the prologue under them
-  constexpr bool kNormMode = MODE == GEMV_QKV_ROPE || MODE == GEMV_SWIGLU || MODE == GEMV_LOGITS || MODE == GEMV_MOE_W13;
+  constexpr bool kNormMode = norm_mode(MODE);
   constexpr int NX = kNormMode ? 4 : 8, NW = kNormMode ? 4 : 0;
   static_assert(NWV == 4 || (!kNormMode && !DMA), "other block sizes: plain modes on the register staging path");
   XRegs<NX, NW> xr;
@@ -320,121 +371,179 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, char* smem, int blo
   }
   in_regs = x_issue<TT, NX, NW, DMA, NWV * 64>(xr, x, a.ldx, T, a.K, a.norm_w, xs, ws);
 
+  auto unit_rows = [&](int uu) {
+    Rows<F, NR> r;
+#pragma unroll
+    for (int p = 0; p < RP; ++p) {
+      // a unit's missing second pair repeats the last one.  Two-row e4m3 units keep the clamp although it changes nothing: without
+      // it hipcc lays the Wo kernel out 120 ns slower per call (profiles/EXPERIMENTS.md); the 16-bit rows never had it.
+      const int q = (RP == 1 && !F::SCALED) ? uu : min(uu * RP + p, npairs - 1);
+      if (MODE == GEMV_SWIGLU) {
+        r.p[2 * p] = reinterpret_cast<const E*>(a.w0) + (size_t)q * a.K;
+        r.p[2 * p + 1] = reinterpret_cast<const E*>(a.w1) + (size_t)q * a.K;
+      } else if (MODE == GEMV_MOE_W13) {
+        r.p[2 * p] = e1 + (size_t)q * a.K;
+        r.p[2 * p + 1] = e3 + (size_t)q * a.K;
+      } else {
+        r.p[2 * p] = seg_row<E>(a, 2 * q);
+        r.p[2 * p + 1] = (2 * q + 1 < a.N) ? seg_row<E>(a, 2 * q + 1) : r.p[2 * p];  // odd N: alias, result dropped in the epilogue
+      }
+    }
+    return r;
+  };
+
   // load cursor over the flattened (unit, batch) sequence of this wave: always two batches ahead of the math
   int u = block_id * NWV + wid;
   int ul = u, jl = 0;
-  RowPair rpl = unit_rows<MODE, ROWS>(a, min(ul, units - 1), e1, e3);
+  Rows<F, NR> rpl = unit_rows(min(ul, units - 1));
   u32x4 bufA[BATCH], bufB[BATCH];
   // Past the wave's last unit `issue` loads BATCH times one L2-resident line instead of branching around the loads:
   // the row pointers and chunk offset are SELECTED (real rows, or one dummy line) and the BATCH loads are issued
   // unconditionally, which keeps the loop body one basic block and the compiler's wait for one buffer at
   // "the other buffer's BATCH loads may stay in flight".  The trailing loads are never consumed.
-  const RowPair dummy = {x, x};
+  const E* dummy = reinterpret_cast<const E*>(x);
   auto issue = [&](u32x4 (&buf)[BATCH]) {
     const bool live = ul < units;
-    RowPair r;
-    r.a = live ? rpl.a : dummy.a;
-    r.b = live ? rpl.b : dummy.b;
-    load_batch<ROWS>(r, live ? jl * U : 0, live ? a.K : 8, live ? lane : 0, buf);
+    Rows<F, NR> r;
+#pragma unroll
+    for (int i = 0; i < NR; ++i) r.p[i] = live ? rpl.p[i] : dummy;
+    load_batch<F, NR>(r, live ? jl * U : 0, live ? a.K : F::PIECE, live ? lane : 0, buf);
     if (live && ++jl == nb) {
       jl = 0;
       ul += nwaves;
-      if (ul < units) rpl = unit_rows<MODE, ROWS>(a, ul, e1, e3);
+      if (ul < units) rpl = unit_rows(ul);
     }
   };
   issue(bufA);
   issue(bufB);
   x_finish<TT, NX, NW, DMA, NWV * 64>(in_regs, xr, xs, red, ws, x, a.ldx, T, a.K, a.norm_w, a.eps);
 
-  Acc<TT> acc;
+  float acc[NR][TT];
 #pragma unroll
-  for (int t = 0; t < TT; ++t) acc.v[0][t] = acc.v[1][t] = 0.f;
+  for (int i = 0; i < NR; ++i)
+#pragma unroll
+    for (int t = 0; t < TT; ++t) acc[i][t] = 0.f;
   int jc = 0;
 
-  // Epilogue operands are fetched EARLY (token position once, the unit's RoPE entry / residual pair when the unit
-  // starts) so that the end of a unit is arithmetic + one store instead of a chain of dependent loads.
-  float2 ep_cs = make_float2(1.f, 0.f);
-  uint32_t ep_res = 0;
+  // Epilogue operands are fetched EARLY (token position once; the unit's row scales, RoPE entries / residual pairs when the
+  // unit starts) so that the end of a unit is arithmetic + one store instead of a chain of dependent loads.
+  float ep_s[NR];
+  float2 ep_cs[RP];
+  uint32_t ep_res[RP];
+#pragma unroll
+  for (int p = 0; p < RP; ++p) {
+    ep_s[2 * p] = ep_s[2 * p + 1] = 1.f;
+    ep_cs[p] = make_float2(1.f, 0.f);
+    ep_res[p] = 0;
+  }
+  auto seg_scale = [&](int r) { return GEMV_SEG_PICK(r, a.n0, a.n1, scale[0][r], scale[1][r - a.n0], scale[2][r - a.n1]); };
   auto prefetch_epilogue = [&](int uu) {
-    const int r0 = (ROWS == 2) ? 2 * uu : uu;
-    if (MODE == GEMV_QKV_ROPE && r0 < a.n1) {
-      const int i = (r0 % a.head_dim) >> 1;
-      ep_cs = *reinterpret_cast<const float2*>(a.rope_cs + ((size_t)ep_pos * (a.head_dim >> 1) + i) * 2);
-    }
-    if (MODE == GEMV_RESIDUAL) {
-      const bf16_t* rs = a.residual + (size_t)tl * a.ldo + r0;
-      if (ROWS == 2 && r0 + 1 < a.N) ep_res = *reinterpret_cast<const uint32_t*>(rs);
-      else ep_res = rs[0];
+#pragma unroll
+    for (int p = 0; p < RP; ++p) {
+      const int q = (RP == 1 && !F::SCALED) ? uu : min(uu * RP + p, npairs - 1);  // (as unit_rows)
+      const int r0 = 2 * q;
+      const bool two = r0 + 1 < a.N;
+      if constexpr (F::SCALED) {
+        if (!kPairOut) {
+          ep_s[2 * p] = scale[0][q];
+          ep_s[2 * p + 1] = scale[1][q];
+        } else {
+          ep_s[2 * p] = seg_scale(r0);
+          ep_s[2 * p + 1] = seg_scale(two ? r0 + 1 : r0);
+        }
+      }
+      if (MODE == GEMV_QKV_ROPE && r0 < a.n1) {
+        const int i = (r0 % a.head_dim) >> 1;
+        ep_cs[p] = *reinterpret_cast<const float2*>(a.rope_cs + ((size_t)ep_pos * (a.head_dim >> 1) + i) * 2);
+      }
+      if (MODE == GEMV_RESIDUAL) {
+        const bf16_t* rs = a.residual + (size_t)tl * a.ldo + r0;
+        if (two) ep_res[p] = *reinterpret_cast<const uint32_t*>(rs);
+        else ep_res[p] = rs[0];
+      }
     }
   };
   if (u < units) prefetch_epilogue(u);
 
   auto finish_unit = [&]() {
 #pragma unroll
-    for (int t = 0; t < TT; ++t) {
-      acc.v[0][t] = wave_sum(acc.v[0][t]);
-      if (ROWS == 2) acc.v[1][t] = wave_sum(acc.v[1][t]);
-    }
+    for (int t = 0; t < TT; ++t)
+#pragma unroll
+      for (int i = 0; i < NR; ++i) acc[i][t] = wave_sum(acc[i][t]);
     // ---- epilogue: lane t finishes token t
-    float v0 = 0.f, v1 = 0.f;
+    float v[NR];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) v[i] = 0.f;
 #pragma unroll
     for (int t = 0; t < TT; ++t) {
       if (lane == t) {
-        v0 = acc.v[0][t];
-        v1 = acc.v[1][t];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) v[i] = acc[i][t];
       }
     }
     if (lane < T) {
       const int t = lane;
-      if (MODE == GEMV_SWIGLU || MODE == GEMV_MOE_W13) {
-        bf16_t* o = reinterpret_cast<bf16_t*>(outp) + (size_t)t * a.ldo + u;
-        *o = f_to_bf(swiglu_bf(v0, v1));
-      } else {
-        const int r0 = (ROWS == 2) ? 2 * u : u;
-        const bool two = (ROWS == 2) && (r0 + 1 < a.N);
-        if (MODE == GEMV_LOGITS) {
-          float* o = reinterpret_cast<float*>(outp) + (size_t)t * a.ldo + r0;
-          o[0] = bf_round(v0);
-          if (two) o[1] = bf_round(v1);
-        } else {
-          float y0 = bf_round(v0), y1 = bf_round(v1);
-          bf16_t* o = reinterpret_cast<bf16_t*>(outp) + (size_t)t * a.ldo + r0;
-          if (MODE == GEMV_RESIDUAL) {
-            y0 = bf_lo(ep_res) + y0;
-            if (two) y1 = bf_hi(ep_res) + y1;
+#pragma unroll
+      for (int p = 0; p < RP; ++p) {
+        const int q = u * RP + p;
+        if (RP == 1 || q < npairs) {
+          float v0 = v[2 * p], v1 = v[2 * p + 1];
+          if constexpr (F::SCALED) {  // y = acc * scale, fp32, before the first rounding
+            v0 *= ep_s[2 * p];
+            v1 *= ep_s[2 * p + 1];
           }
-          if (MODE == GEMV_QKV_ROPE) {
-            const int pos = ep_pos;
-            if (r0 < a.n1) {  // q or k rows: rotate the adjacent pair (rope.py:13-23)
-              const float2 cs = ep_cs;
-              float re, im;
-              rope_pair(y0, y1, cs.x, cs.y, re, im);
-              y0 = re;
-              y1 = im;
-            }
-            if (a.write_kv && r0 >= a.n0) {  // cache.py:83-92: ring slot pos % W of this sequence's row
-              const int kv_dim = a.n1 - a.n0;
-              const size_t off = kv_offset(a.kv_layout, a.W, kv_dim, a.head_dim, (size_t)ep_seq, pos % a.W, (r0 < a.n1) ? r0 - a.n0 : r0 - a.n1);
-              bf16_t* ring = ((r0 < a.n1) ? reinterpret_cast<bf16_t*>(a.cache_k) : reinterpret_cast<bf16_t*>(a.cache_v)) + off;
-              *reinterpret_cast<uint32_t*>(ring) = pack_bf2(y0, y1);
-            }
-          }
-          if (two) {
-            *reinterpret_cast<uint32_t*>(o) = pack_bf2(y0, y1);
+          if (!kPairOut) {
+            bf16_t* o = reinterpret_cast<bf16_t*>(outp) + (size_t)t * a.ldo + q;
+            *o = f_to_bf(swiglu_bf(v0, v1));
           } else {
-            o[0] = f_to_bf(y0);
+            const int r0 = 2 * q;
+            const bool two = r0 + 1 < a.N;
+            if (MODE == GEMV_LOGITS) {
+              float* o = reinterpret_cast<float*>(outp) + (size_t)t * a.ldo + r0;
+              o[0] = bf_round(v0);
+              if (two) o[1] = bf_round(v1);
+            } else {
+              float y0 = bf_round(v0), y1 = bf_round(v1);
+              bf16_t* o = reinterpret_cast<bf16_t*>(outp) + (size_t)t * a.ldo + r0;
+              if (MODE == GEMV_RESIDUAL) {
+                y0 = bf_lo(ep_res[p]) + y0;
+                if (two) y1 = bf_hi(ep_res[p]) + y1;
+              }
+              if (MODE == GEMV_QKV_ROPE) {
+                if (r0 < a.n1) {  // q or k rows: rotate the adjacent pair (rope.py:13-23)
+                  float re, im;
+                  rope_pair(y0, y1, ep_cs[p].x, ep_cs[p].y, re, im);
+                  y0 = re;
+                  y1 = im;
+                }
+                if (a.write_kv && r0 >= a.n0) {  // cache.py:83-92: ring slot pos % W of this sequence's row
+                  const int kv_dim = a.n1 - a.n0;
+                  const size_t off = kv_offset(a.kv_layout, a.W, kv_dim, a.head_dim, (size_t)ep_seq, ep_pos % a.W,
+                                               (r0 < a.n1) ? r0 - a.n0 : r0 - a.n1);
+                  bf16_t* ring = ((r0 < a.n1) ? reinterpret_cast<bf16_t*>(a.cache_k) : reinterpret_cast<bf16_t*>(a.cache_v)) + off;
+                  *reinterpret_cast<uint32_t*>(ring) = pack_bf2(y0, y1);
+                }
+              }
+              if (two) {
+                *reinterpret_cast<uint32_t*>(o) = pack_bf2(y0, y1);
+              } else {
+                o[0] = f_to_bf(y0);
+              }
+            }
           }
         }
       }
     }
 #pragma unroll
-    for (int t = 0; t < TT; ++t) acc.v[0][t] = acc.v[1][t] = 0.f;
+    for (int i = 0; i < NR; ++i)
+#pragma unroll
+      for (int t = 0; t < TT; ++t) acc[i][t] = 0.f;
   };
 
   // One step = consume the oldest batch, refill the same registers with the batch two ahead (ping-pong between
   // bufA and bufB: no register copies, so the compiler's wait for bufA leaves bufB's eight loads in flight).
   auto step = [&](u32x4 (&buf)[BATCH]) {
-    fma_batch<TT, ROWS>(buf, jc * U, xs, a.K, lane, acc);
+    fma_batch<F, TT, NR>(buf, jc * U, xs, a.K, lane, acc);
     issue(buf);
     if (++jc == nb) {
       jc = 0;
@@ -452,6 +561,81 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, char* smem, int blo
       step(bufA);
       step(bufB);
     } while (u < units);
+  }
+}
+
+// ---- the launch plan (host), shared by launch_gemv and launch_gemv_w8
+
+// 5 and 7 rows run on the 6- and 8-row instantiations, which stage 6 / 8 rows in LDS
+inline int round_tt(int T) { return T == 5 ? 6 : (T == 7 ? 8 : T); }
+
+// [TT][K] activations, 4 x TT partial sums, and (norm modes at TT > 1: the DMA staging path) K norm weights
+inline size_t lds_bytes(int TT, int K, bool norm) { return (size_t)TT * K * 2 + 4 * TT * sizeof(float) + ((TT > 1 && norm) ? (size_t)K * 2 : 0); }
+
+// Rows that fit the prologue's register set (4 x 256 pieces with a fused RMSNorm, 8 x 256 without) are staged through registers;
+// 2..8 rows that do not, by LDS-DMA.
+inline bool stage_by_dma(int mode, int TT, int K) { return TT > 1 && (size_t)TT * (K >> 3) > (norm_mode(mode) ? 4u : 8u) * 256u; }
+
+// MI_GEMV_MAX_BLOCKS; default 2 blocks per CU (of the first caller's device), measured best on MI355X.  Read once per copy of this
+// namespace: the fp16 compile of gemv.hip has its own.
+inline int max_blocks(int cus) {
+  static int v = 0;
+  if (v == 0) {
+    const char* e = getenv("MI_GEMV_MAX_BLOCKS");
+    v = e ? atoi(e) : 2 * cus;
+    if (v <= 0) v = 2 * cus;
+  }
+  return v;
+}
+
+// Persistent-style grid: every wave gets the same number k of units (no partially filled last round of blocks; the two-batch
+// load pipeline runs across a wave's units).  even_blocks: the smallest k for which the block count is a multiple of the CUs
+// (even load per CU), at most 4 per CU, and divides the units exactly - e.g. W1|W3: 14336 units -> 512 blocks x 4 waves x 7
+// units; q|k|v: 3072 units -> 768 blocks x 1; 0 when there is none.  spread_blocks: the smallest k that fits `cap` blocks.
+inline int even_blocks(int units, int cus) {
+  for (int k = 1; k <= 64; ++k) {
+    const int b = (units + 4 * k - 1) / (4 * k);
+    if (b <= 4 * cus && b % cus == 0 && b * 4 * k == units && (b <= max_blocks(cus) || k == 1)) return b;
+  }
+  return 0;
+}
+inline int spread_blocks(int units, int cap) {
+  const int k = (units + 4 * cap - 1) / (4 * cap);
+  const int b = (units + 4 * k - 1) / (4 * k);
+  return b < 1 ? 1 : b;
+}
+// above 80 KiB of LDS one block fits a CU: one block per CU, every wave the same number of units
+inline int blocks_for_lds(int blocks, int units, int cus, size_t lds) { return (lds > 80 * 1024 && blocks > cus) ? spread_blocks(units, cus) : blocks; }
+
+// Launch of a 256-thread kernel with `lds` bytes of dynamic LDS; more than the default limit of 64 KiB is an opt-in per function
+// AND per device.
+template <auto KERNEL, class Args>
+hipError_t launch_lds(const Args& a, dim3 grid, size_t lds, hipStream_t s) {
+  if (lds > 64 * 1024) {
+    static bool attr_set[64] = {};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)GEMV_LDS_BUDGET + 1024);
+      if (e != hipSuccess) return e;
+      if (dev >= 0 && dev < 64) attr_set[dev] = true;
+    }
+  }
+  hipLaunchKernelGGL(KERNEL, grid, dim3(256), lds, s, a);
+  return hipGetLastError();
+}
+
+// f(std::integral_constant<int, TT>) for the instantiated row counts
+template <class Fn>
+hipError_t for_tt(int TT, Fn&& f) {
+  switch (TT) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    default: return f(std::integral_constant<int, 8>{});
   }
 }
 
