@@ -385,6 +385,60 @@ typedef struct mi_w8_model {
 size_t mi_workspace_bytes_w8(const mi_model_t* model, const mi_w8_model_t* w8, int T, int B, int max_cache_size);
 int mi_forward_w8(const mi_model_t* model, const mi_w8_model_t* w8, const mi_batch_t* batch, mi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Weight-only MXFP4 (OCP microscaling: e2m1 codes in blocks of 32 along K, one e8m0 scale byte per block; 4.25 bits per
+ * weight) on dense bf16 models.  Additive to ABI v9 like the FP8 block above: the presence of these symbols is the feature test;
+ * mi_forward_w8 keeps refusing every format value other than MI_W8_FP8_E4M3.
+ * The reference has no quantised linear: a quantised linear here stands for the nn.Linear of transformer_layers.py:51-54,
+ * 101-103 on the real-valued weight  W[r, k] = 2^(s[r, k / 32] - 127) * e2m1(c[r, k])  where
+ *   c: bytes [out, in / 2], two codes per byte, the LOW nibble at the even k; code & 7 indexes {0, .5, 1, 1.5, 2, 3, 4, 6}, code & 8
+ *      is the sign;   s: bytes [out, in / 32], e8m0 (255, its NaN, must not occur).
+ * Every such W is exact in bf16.  Numerics contract: at any M the result is what mi_linear / mi_qkv_rope_kvwrite compute on the
+ * bf16 matrix W, up to the order of the fp32 summation -
+ *   M <= 8:  each code pair becomes a scaled bf16 pair in registers (v_cvt_scalef32_pk_bf16_fp4) and enters the bf16 kernels' dot
+ *            products and epilogues (csrc/gemv_w4.hip; activations, norms and rings stay bf16);
+ *   M  > 8:  W is written into a scratch as bf16 and mi_linear's MFMA GEMM runs on it.
+ * K must be a multiple of 32 (MI_ERR_SHAPE).  Scale bytes below 3 give bf16 subnormals, which the dot product may flush to zero.
+ * Embeddings, norms, the LM head, the MoE gate and the K/V rings stay bf16.
+ * ---------------------------------------------------------------------------------------------- */
+#define MI_W4_MXFP4 2
+
+/* mi_linear (nn.Linear, transformer_layers.py:66,93,105-106) with w[i] read as MXFP4 code bytes [n_rows[i], K / 2] and scale[i]
+ * their e8m0 block scales [n_rows[i], K / 32], row-major.  MI_EPI_STORE / MI_EPI_RESIDUAL / MI_EPI_SWIGLU (MI_EPI_LOGITS:
+ * MI_ERR_UNSUPPORTED - the LM head is not quantised).  M > 8 needs `scratch` of at least mi_linear_w4_scratch_bytes(M, K, n_rows,
+ * epilogue) bytes (0 for M <= 8, where scratch may be NULL); norm_w as mi_linear (M <= 8 only). */
+size_t mi_linear_w4_scratch_bytes(int M, int K, const int n_rows[3], int epilogue);
+int mi_linear_w4(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
+                 int epilogue, const void* residual, const void* norm_w, float eps, const uint8_t* const scale[3], void* scratch,
+                 size_t scratch_bytes, mi_stream_t stream);
+
+/* mi_qkv_rope_kvwrite (transformer_layers.py:66-70,165 + rope.py:13-23 + cache.py:83-92, T <= 8) with wq / wk / wv read as MXFP4
+ * code bytes and sq / sk / sv their e8m0 block scales. */
+int mi_qkv_rope_kvwrite_w4(void* qkv, int ldo, const void* x, int ldx, int T, int D, const void* wq, const void* wk,
+                           const void* wv, const uint8_t* sq, const uint8_t* sk, const uint8_t* sv, int n_heads, int n_kv_heads,
+                           int head_dim, const void* norm_w, float eps, const float* rope_cs, int rope_len,
+                           const int32_t* tok_pos, const int32_t* tok_seq, void* cache_k, void* cache_v, int W, int kv_layout,
+                           mi_stream_t stream);
+
+/* Block scales of the seven linears of one layer (transformer_layers.py:51-54,101-103): DEVICE bytes [rows, K / 32], row-major. */
+typedef struct mi_w4_layer {
+  const uint8_t *wq, *wk, *wv, *wo, *w1, *w2, *w3;
+} mi_w4_layer_t;
+/* The quantisation of a model's layers: beside an mi_model_t whose seven linear pointers per layer then point to MXFP4 code bytes. */
+typedef struct mi_w4_model {
+  int32_t format;               /* MI_W4_MXFP4 */
+  const mi_w4_layer_t* layers;  /* host array [n_layers] */
+} mi_w4_model_t;
+
+/* mi_workspace_bytes / mi_forward (Transformer.forward_partial, transformer.py:163-219, + the LM head, :229-242) on a model
+ * whose linears are quantised as `w4` describes; w4 == NULL: exactly mi_workspace_bytes / mi_forward.  Launches, scratch and
+ * refusals as mi_forward_w8: T <= 8 the six launches per layer on the MXFP4 GEMV kernels; T > 8 one dequantisation launch per linear
+ * group into the scratch behind everything else in the workspace, then mi_forward's GEMM launch.  Always the launch path: the
+ * persistent engine declines.  Dense models without un-merged LoRA only (num_experts > 0 or lora_rank > 0: MI_ERR_UNSUPPORTED,
+ * naming MXFP4); dim, hidden_dim and n_heads * head_dim multiples of 32. */
+size_t mi_workspace_bytes_w4(const mi_model_t* model, const mi_w4_model_t* w4, int T, int B, int max_cache_size);
+int mi_forward_w4(const mi_model_t* model, const mi_w4_model_t* w4, const mi_batch_t* batch, mi_stream_t stream);
+
 /* ABI v6 - storage dtypes other than bf16 (reference transformer.py:303,338: `from_folder(dtype=...)` keeps the dtype the
  * caller asks for; the reference's own tests build fp32 models, tests/test_generate.py:51,100) and bf16 models of a shape
  * mi_forward declines with MI_ERR_SHAPE (head_dim != 128, more than 16 experts, top_k = 3).  Same structs, same metadata

@@ -53,6 +53,9 @@ int mi_debug_engine_sabotage(void* workspace, int launches, mi_stream_t stream);
  * partly filled round of a 256x256-tile GEMM on the 128x128 kernel, 2 = as 128x256 tiles of the 256 kernel (default,
  * bit-identical to 0; MI_GEMM_TAIL). */
 int mi_debug_set_prefill_kernels(int attn_waves, int gemm_tail);
+/* The row pairs per unit that the MXFP4 GEMV launcher picks at one token for a matrix of `n_pairs` row pairs on a device of
+ * `n_cus` compute units (csrc/gemv_w4.hip; MI_GEMV_W4_RP unset): tests size their matrices to both sides of its threshold. */
+int mi_debug_gemv_w4_row_pairs(int n_pairs, int n_cus);
 
 #ifdef __cplusplus
 }

@@ -96,6 +96,7 @@ bool engine_route(int variant, bool nemo_opt_in, const EngineBuild* slot, const 
   const bool moe = pr.E > 0;
   if (pr.lora_rank > 0) return false;  // un-merged LoRA adapters: no engine build carries them, the launch path does (lora.hip)
   if (pr.w8) return false;             // e4m3 weight bytes: no engine build reads them, the launch path does (gemv_w8.hip)
+  if (pr.w4) return false;             // MXFP4 weights: likewise (gemv_w4.hip)
   auto takes = [&](int b) { return kBuilds[b]->applicable(pr, nullptr, 0); };
   if (slot && slot->applicable(pr, nullptr, 0) && try_build(*slot)) return true;
   // the dense GQA-4 headline shapes: the `next` compile (build_native.ENGINE_NEXT_FLAGS)
@@ -165,6 +166,7 @@ size_t w8_scratch_elems(const mi_model_t* m) {
   return a > b ? a : b;  // (wo: D * nq <= a; w2: D * F <= b)
 }
 
+// w8: the linears are quantised (e4m3 or MXFP4: the same scratch of one dequantised linear group)
 Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool w8 = false) {
   Workspace w;
   size_t off = 0;
@@ -306,6 +308,39 @@ int dequant_group(const void* w[3], const W8Scales& sc, const int n_rows[3], int
   if (!d.w[1]) d.n1 = d.n0;
   d.N = n; d.K = K; d.out = out;
   return hip_rc(launch_dequant_w8(d, s), what);
+}
+// The fourth table: gemv_w4.hip, MXFP4 code bytes behind the weight pointers and the e8m0 block-scale rows beside the arguments.
+struct W4Scales {
+  const uint8_t* s[3];
+};
+// the (up to three) linears of a layer that a launch of forward_body reads, in the field order of mi_w8_layer_t / mi_w4_layer_t; -1: none
+enum { LIN_WQ = 0, LIN_WK, LIN_WV, LIN_WO, LIN_W1, LIN_W2, LIN_W3 };
+struct Lins {
+  int i[3];
+};
+int gemv_passes_w4(const GemvArgs& a, const W4Scales& sc, int T, hipStream_t s, const char* what) {
+  return gemv_pass_loop(gemv_max_tokens(a.K), a, T, what, [&](const GemvArgs& p) {
+    const GemvW4Args w = {p, {sc.s[0], sc.s[1], sc.s[2]}};
+    return launch_gemv_w4(w, s);
+  });
+}
+// Dequantise up to three MXFP4 matrices of K columns side by side into `out` (dense [sum of rows, K] bf16); w[i] then points at
+// the bf16 rows of matrix i.
+int dequant_group_w4(const void* w[3], const W4Scales& sc, const int n_rows[3], int K, bf16_t* out, hipStream_t s, const char* what) {
+  DequantW4Args d;
+  memset(&d, 0, sizeof(d));
+  int n = 0;
+  for (int i = 0; i < 3; ++i) {
+    const int rows = w[i] ? n_rows[i] : 0;
+    d.w[i] = (const uint8_t*)w[i]; d.scale[i] = sc.s[i];
+    if (i == 0) d.n0 = rows;
+    if (i == 1) d.n1 = d.n0 + rows;
+    w[i] = w[i] ? (const void*)(out + (size_t)n * K) : nullptr;
+    n += rows;
+  }
+  if (!d.w[1]) d.n1 = d.n0;
+  d.N = n; d.K = K; d.out = out;
+  return hip_rc(launch_dequant_w4(d, s), what);
 }
 
 // out[M, N] = epi(a[M, K] @ w0^T (, a @ w1^T)): the plain GEMM of one weight matrix, or of W1 and W3 for GEMM_SWIGLU
@@ -838,21 +873,52 @@ size_t mi_linear_w8_scratch_bytes(int M, int K, const int n_rows[3], int epilogu
   return align_up(linear_w8_rows(n_rows, nullptr, epilogue) * (size_t)K * 2);
 }
 
-int mi_linear_w8(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
-                 int epilogue, const void* residual, const void* norm_w, float eps, const float* const scale[3], void* scratch,
-                 size_t scratch_bytes, mi_stream_t stream) {
-  if (!out || !x || !w || !n_rows || !scale || !w[0] || !scale[0] || M <= 0 || K <= 0 || n_rows[0] <= 0) return fail(MI_ERR_ARG, "mi_linear_w8");
+}  // extern "C"
+
+// What differs between the two weight-only forms at the leaves: the scale element, the K modulus and its reason, the launches.
+struct QuantW8 {
+  typedef float scale_t;
+  typedef W8Scales Scales;
+  static constexpr int kMod = 16;
+  static constexpr const char* kWhy = "a 16-byte piece is 16 e4m3 weights";
+  static constexpr const char *kLinear = "mi_linear_w8", *kQkv = "mi_qkv_rope_kvwrite_w8", *kGemv = "gemv (w8)", *kDequant = "dequant (w8)",
+                              *kQkvGemv = "qkv gemv (w8)";
+  static int passes(const GemvArgs& a, const Scales& sc, int T, hipStream_t s, const char* what) { return gemv_passes_w8(a, sc, T, s, what); }
+  static int dequant(const void* w[3], const Scales& sc, const int nr[3], int K, bf16_t* out, hipStream_t s, const char* what) {
+    return dequant_group(w, sc, nr, K, out, s, what);
+  }
+};
+struct QuantW4 {
+  typedef uint8_t scale_t;
+  typedef W4Scales Scales;
+  static constexpr int kMod = 32;
+  static constexpr const char* kWhy = "one e8m0 scale per block of 32 MXFP4 weights";
+  static constexpr const char *kLinear = "mi_linear_w4", *kQkv = "mi_qkv_rope_kvwrite_w4", *kGemv = "gemv (w4)", *kDequant = "dequant (w4)",
+                              *kQkvGemv = "qkv gemv (w4)";
+  static int passes(const GemvArgs& a, const Scales& sc, int T, hipStream_t s, const char* what) { return gemv_passes_w4(a, sc, T, s, what); }
+  static int dequant(const void* w[3], const Scales& sc, const int nr[3], int K, bf16_t* out, hipStream_t s, const char* what) {
+    return dequant_group_w4(w, sc, nr, K, out, s, what);
+  }
+};
+
+// mi_linear_w8 / mi_linear_w4
+template <class Q>
+static int linear_quant(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3], int epilogue,
+                        const void* residual, const void* norm_w, float eps, const typename Q::scale_t* const scale[3], void* scratch,
+                        size_t scratch_bytes, mi_stream_t stream) {
+  const char* me = Q::kLinear;
+  if (!out || !x || !w || !n_rows || !scale || !w[0] || !scale[0] || M <= 0 || K <= 0 || n_rows[0] <= 0) return fail(MI_ERR_ARG, "%s", me);
   for (int i = 1; i < 3; ++i)
-    if (w[i] && (!scale[i] || n_rows[i] <= 0 || !w[i - 1])) return fail(MI_ERR_ARG, "mi_linear_w8: segment %d needs rows, a scale and its predecessor", i);
-  if (K % 16) return fail(MI_ERR_SHAPE, "mi_linear_w8: K = %d must be a multiple of 16 (a 16-byte piece is 16 e4m3 weights)", K);
+    if (w[i] && (!scale[i] || n_rows[i] <= 0 || !w[i - 1])) return fail(MI_ERR_ARG, "%s: segment %d needs rows, a scale and its predecessor", me, i);
+  if (K % Q::kMod) return fail(MI_ERR_SHAPE, "%s: K = %d must be a multiple of %d (%s)", me, K, Q::kMod, Q::kWhy);
   if (epilogue != MI_EPI_STORE && epilogue != MI_EPI_RESIDUAL && epilogue != MI_EPI_SWIGLU)
-    return fail(MI_ERR_UNSUPPORTED, "mi_linear_w8: epilogue %d (store, residual and swiglu; the LM head is not quantised)", epilogue);
-  if (epilogue == MI_EPI_RESIDUAL && !residual) return fail(MI_ERR_ARG, "mi_linear_w8: residual epilogue without residual");
-  if (epilogue == MI_EPI_SWIGLU && (!w[1] || n_rows[0] != n_rows[1])) return fail(MI_ERR_ARG, "mi_linear_w8: swiglu needs W1, W3");
+    return fail(MI_ERR_UNSUPPORTED, "%s: epilogue %d (store, residual and swiglu; the LM head is not quantised)", me, epilogue);
+  if (epilogue == MI_EPI_RESIDUAL && !residual) return fail(MI_ERR_ARG, "%s: residual epilogue without residual", me);
+  if (epilogue == MI_EPI_SWIGLU && (!w[1] || n_rows[0] != n_rows[1])) return fail(MI_ERR_ARG, "%s: swiglu needs W1, W3", me);
   hipStream_t s = (hipStream_t)stream;
   const bool swiglu = epilogue == MI_EPI_SWIGLU;
   const int n0 = n_rows[0], n1 = n0 + (w[1] ? n_rows[1] : 0), n2 = n1 + ((!swiglu && w[2]) ? n_rows[2] : 0);
-  const W8Scales sc = {{scale[0], w[1] ? scale[1] : nullptr, (!swiglu && w[2]) ? scale[2] : nullptr}};
+  const typename Q::Scales sc = {{scale[0], w[1] ? scale[1] : nullptr, (!swiglu && w[2]) ? scale[2] : nullptr}};
   if (M <= GEMV_MAX_T) {
     GemvArgs a = gemv_common(x, ldx, K, 0, norm_w, eps, out, ldo);
     a.w0 = (const bf16_t*)w[0]; a.w1 = (const bf16_t*)w[1]; a.w2 = swiglu ? nullptr : (const bf16_t*)w[2]; a.residual = (const bf16_t*)residual;
@@ -862,15 +928,46 @@ int mi_linear_w8(void* out, int ldo, const void* x, int ldx, int M, int K, const
     } else {
       a.N = n2; a.n0 = n0; a.n1 = n1;
     }
-    return gemv_passes_w8(a, sc, M, s, "gemv (w8)");
+    return Q::passes(a, sc, M, s, Q::kGemv);
   }
-  if (norm_w) return fail(MI_ERR_UNSUPPORTED, "mi_linear_w8: fused RMSNorm only on the M <= 8 path");
+  if (norm_w) return fail(MI_ERR_UNSUPPORTED, "%s: fused RMSNorm only on the M <= 8 path", me);
   const size_t need = align_up((size_t)(swiglu ? 2 * n0 : n2) * K * 2);
-  if (!scratch || scratch_bytes < need) return fail(MI_ERR_WORKSPACE, "mi_linear_w8: scratch %zu < required %zu", scratch ? scratch_bytes : (size_t)0, need);
+  if (!scratch || scratch_bytes < need) return fail(MI_ERR_WORKSPACE, "%s: scratch %zu < required %zu", me, scratch ? scratch_bytes : (size_t)0, need);
   const void* wd[3] = {w[0], w[1], swiglu ? nullptr : w[2]};
   const int nr[3] = {n0, n1 - n0, n2 - n1};
-  MI_TRY(dequant_group(wd, sc, nr, K, (bf16_t*)scratch, s, "dequant (w8)"));
+  MI_TRY(Q::dequant(wd, sc, nr, K, (bf16_t*)scratch, s, Q::kDequant));
   return mi_linear(out, ldo, x, ldx, M, K, wd, n_rows, epilogue, residual, nullptr, 0.f, stream);
+}
+
+// mi_qkv_rope_kvwrite_w8 / mi_qkv_rope_kvwrite_w4
+template <class Q>
+static int qkv_rope_kvwrite_quant(void* qkv, int ldo, const void* x, int ldx, int T, int D, const void* wq, const void* wk, const void* wv,
+                                  const typename Q::scale_t* sq, const typename Q::scale_t* sk, const typename Q::scale_t* sv, int n_heads,
+                                  int n_kv_heads, int head_dim, const void* norm_w, float eps, const float* rope_cs, int rope_len,
+                                  const int32_t* tok_pos, const int32_t* tok_seq, void* cache_k, void* cache_v, int W, int kv_layout,
+                                  mi_stream_t stream) {
+  const char* me = Q::kQkv;
+  if (!qkv || !x || !wq || !wk || !wv || !sq || !sk || !sv || !rope_cs || !tok_pos || T <= 0 || D <= 0 || rope_len <= 0 ||
+      !kv_layout_ok(kv_layout))
+    return fail(MI_ERR_ARG, "%s", me);
+  if (D % Q::kMod) return fail(MI_ERR_SHAPE, "%s: D = %d must be a multiple of %d (%s)", me, D, Q::kMod, Q::kWhy);
+  if (head_dim != 128) return fail(MI_ERR_SHAPE, "head_dim must be 128");
+  if ((cache_k == nullptr) != (cache_v == nullptr) || (cache_k && W <= 0)) return fail(MI_ERR_ARG, "%s: cache", me);
+  if (T > GEMV_MAX_T)
+    return fail(MI_ERR_UNSUPPORTED, "%s: T = %d > %d (the prefill path is mi_rmsnorm + %s + mi_rope_inplace + mi_kv_write)", me, T, GEMV_MAX_T,
+                Q::kLinear);
+  const RingWrite ring = {cache_k, cache_v, W, kv_layout};
+  const GemvArgs a = gemv_qkv_rope(x, ldx, D, norm_w, eps, wq, wk, wv, n_heads * head_dim, n_kv_heads * head_dim, qkv, ldo, rope_cs,
+                                   tok_pos, tok_seq, head_dim, cache_k ? &ring : nullptr);
+  return Q::passes(a, typename Q::Scales{{sq, sk, sv}}, T, (hipStream_t)stream, Q::kQkvGemv);
+}
+
+extern "C" {
+
+int mi_linear_w8(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
+                 int epilogue, const void* residual, const void* norm_w, float eps, const float* const scale[3], void* scratch,
+                 size_t scratch_bytes, mi_stream_t stream) {
+  return linear_quant<QuantW8>(out, ldo, x, ldx, M, K, w, n_rows, epilogue, residual, norm_w, eps, scale, scratch, scratch_bytes, stream);
 }
 
 int mi_qkv_rope_kvwrite_w8(void* qkv, int ldo, const void* x, int ldx, int T, int D, const void* wq, const void* wk,
@@ -878,19 +975,26 @@ int mi_qkv_rope_kvwrite_w8(void* qkv, int ldo, const void* x, int ldx, int T, in
                            int head_dim, const void* norm_w, float eps, const float* rope_cs, int rope_len,
                            const int32_t* tok_pos, const int32_t* tok_seq, void* cache_k, void* cache_v, int W, int kv_layout,
                            mi_stream_t stream) {
-  if (!qkv || !x || !wq || !wk || !wv || !sq || !sk || !sv || !rope_cs || !tok_pos || T <= 0 || D <= 0 || rope_len <= 0 ||
-      !kv_layout_ok(kv_layout))
-    return fail(MI_ERR_ARG, "mi_qkv_rope_kvwrite_w8");
-  if (D % 16) return fail(MI_ERR_SHAPE, "mi_qkv_rope_kvwrite_w8: D = %d must be a multiple of 16 (a 16-byte piece is 16 e4m3 weights)", D);
-  if (head_dim != 128) return fail(MI_ERR_SHAPE, "head_dim must be 128");
-  if ((cache_k == nullptr) != (cache_v == nullptr) || (cache_k && W <= 0)) return fail(MI_ERR_ARG, "mi_qkv_rope_kvwrite_w8: cache");
-  if (T > GEMV_MAX_T)
-    return fail(MI_ERR_UNSUPPORTED, "mi_qkv_rope_kvwrite_w8: T = %d > %d (the prefill path is mi_rmsnorm + mi_linear_w8 + "
-                "mi_rope_inplace + mi_kv_write)", T, GEMV_MAX_T);
-  const RingWrite ring = {cache_k, cache_v, W, kv_layout};
-  const GemvArgs a = gemv_qkv_rope(x, ldx, D, norm_w, eps, wq, wk, wv, n_heads * head_dim, n_kv_heads * head_dim, qkv, ldo, rope_cs,
-                                   tok_pos, tok_seq, head_dim, cache_k ? &ring : nullptr);
-  return gemv_passes_w8(a, W8Scales{{sq, sk, sv}}, T, (hipStream_t)stream, "qkv gemv (w8)");
+  return qkv_rope_kvwrite_quant<QuantW8>(qkv, ldo, x, ldx, T, D, wq, wk, wv, sq, sk, sv, n_heads, n_kv_heads, head_dim, norm_w, eps, rope_cs,
+                                         rope_len, tok_pos, tok_seq, cache_k, cache_v, W, kv_layout, stream);
+}
+
+/* weight-only MXFP4 leaves (include/mistral_hip.h: MI_W4_MXFP4) */
+size_t mi_linear_w4_scratch_bytes(int M, int K, const int n_rows[3], int epilogue) { return mi_linear_w8_scratch_bytes(M, K, n_rows, epilogue); }
+
+int mi_linear_w4(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
+                 int epilogue, const void* residual, const void* norm_w, float eps, const uint8_t* const scale[3], void* scratch,
+                 size_t scratch_bytes, mi_stream_t stream) {
+  return linear_quant<QuantW4>(out, ldo, x, ldx, M, K, w, n_rows, epilogue, residual, norm_w, eps, scale, scratch, scratch_bytes, stream);
+}
+
+int mi_qkv_rope_kvwrite_w4(void* qkv, int ldo, const void* x, int ldx, int T, int D, const void* wq, const void* wk,
+                           const void* wv, const uint8_t* sq, const uint8_t* sk, const uint8_t* sv, int n_heads, int n_kv_heads,
+                           int head_dim, const void* norm_w, float eps, const float* rope_cs, int rope_len,
+                           const int32_t* tok_pos, const int32_t* tok_seq, void* cache_k, void* cache_v, int W, int kv_layout,
+                           mi_stream_t stream) {
+  return qkv_rope_kvwrite_quant<QuantW4>(qkv, ldo, x, ldx, T, D, wq, wk, wv, sq, sk, sv, n_heads, n_kv_heads, head_dim, norm_w, eps, rope_cs,
+                                         rope_len, tok_pos, tok_seq, cache_k, cache_v, W, kv_layout, stream);
 }
 
 int mi_moe_experts_decode(void* out, const void* residual, const void* x, int ldx, int T, int D, int F,
@@ -1010,6 +1114,7 @@ extern "C" int mi_debug_set_engine_slot(int slot) {  // -1: the library's own ro
   return N_SLOTS;
 }
 #endif
+int mi_debug_gemv_w4_row_pairs(int n_pairs, int n_cus) { return gemv_w4_row_pairs(n_pairs, n_cus); }
 int mi_debug_set_prefill_kernels(int attn_waves, int gemm_tail) {
   attn_prefill_set_mode(attn_waves);
   if (gemm_tail >= 0) gemm_set_tail_mode(gemm_tail);
@@ -1041,16 +1146,33 @@ static int check_w8(const char* entry, const mi_model_t* m, const mi_w8_model_t*
   return MI_OK;
 }
 
-// mi_forward and mi_forward_w8.  w8 == nullptr: exactly the launches of mi_forward as they always were.
-static int forward_body(const char* entry, const mi_model_t* m, const mi_w8_model_t* w8, const mi_batch_t* bt, mi_stream_t stream) {
+size_t mi_workspace_bytes_w4(const mi_model_t* model, const mi_w4_model_t* w4, int T, int B, int max_cache_size) {
+  if (!model || T <= 0 || B <= 0) return 0;
+  return carve(model, T, B, max_cache_size > 0 ? max_cache_size : 1, nullptr, w4 != nullptr).total;
+}
+
+static int check_w4(const char* entry, const mi_model_t* m, const mi_w4_model_t* w4) {
+  if (w4->format != MI_W4_MXFP4) return fail(MI_ERR_UNSUPPORTED, "%s: weight format %d (MI_W4_MXFP4 = 2 is the only one)", entry, w4->format);
+  if (!w4->layers) return fail(MI_ERR_ARG, "%s: w4 without layer scales", entry);
+  if (m->num_experts > 0) return fail(MI_ERR_UNSUPPORTED, "%s: MXFP4 weights on a MoE model are not implemented (the experts stay bf16)", entry);
+  if (m->lora_rank > 0) return fail(MI_ERR_UNSUPPORTED, "%s: un-merged LoRA on an MXFP4 base is not implemented; merge the adapter before quantising", entry);
+  if (m->dim % 32 || m->hidden_dim % 32 || (m->n_heads * m->head_dim) % 32)
+    return fail(MI_ERR_SHAPE, "%s: dim, hidden_dim and n_heads * head_dim must be multiples of 32 (one e8m0 scale per block of 32 MXFP4 weights)", entry);
+  return MI_OK;
+}
+
+// mi_forward, mi_forward_w8 and mi_forward_w4 (at most one of w8 / w4).  Neither: exactly the launches of mi_forward as they always were.
+static int forward_body(const char* entry, const mi_model_t* m, const mi_w8_model_t* w8, const mi_w4_model_t* w4, const mi_batch_t* bt,
+                        mi_stream_t stream) {
   MI_TRY(check_model(m));
   if (w8) MI_TRY(check_w8(entry, m, w8));
+  if (w4) MI_TRY(check_w4(entry, m, w4));
   BatchInfo bi;
   MI_TRY(check_batch(entry, m, bt, true, &bi));
   int maxW = 1;
   if (bi.has_cache)
     for (int l = 0; l < m->n_layers; ++l) maxW = bt->cache_sizes[l] > maxW ? bt->cache_sizes[l] : maxW;
-  const Workspace ws = carve(m, bi.T, bi.B, maxW, (char*)bt->workspace, w8 != nullptr);
+  const Workspace ws = carve(m, bi.T, bi.B, maxW, (char*)bt->workspace, w8 != nullptr || w4 != nullptr);
   MI_TRY(check_workspace_and_sample(entry, bt, ws.total, &bi));
   const int T = bi.T, B = bi.B, branch = bi.branch, kvl = bi.kv_layout;
   const bool has_cache = bi.has_cache, want_greedy = bi.want_sample, want_topp = bi.want_topp;
@@ -1083,7 +1205,7 @@ static int forward_body(const char* entry, const mi_model_t* m, const mi_w8_mode
       pr.hist_tok = bt->hist_token; pr.hist_lp = bt->hist_logprob; pr.hist_len = bt->hist_len;
     }
     pr.granules = ws.gran; pr.granule_bytes = ws.gran_bytes; pr.ctrl = engine_ctrl;
-    pr.E = m->num_experts; pr.top_k = m->top_k; pr.lora_rank = m->lora_rank; pr.w8 = w8 != nullptr;
+    pr.E = m->num_experts; pr.top_k = m->top_k; pr.lora_rank = m->lora_rank; pr.w8 = w8 != nullptr; pr.w4 = w4 != nullptr;
     pr.forced = engine_variant() == 1;
     bool dense_ok = true;
     for (int l = 0; l < m->n_layers; ++l)
@@ -1133,16 +1255,31 @@ static int forward_body(const char* entry, const mi_model_t* m, const mi_w8_mode
     // image of a linear group into the scratch and points w[] at it for the GEMM that follows.  Without w8 both pass through.
     static const mi_w8_layer_t kNoScales = {};
     const mi_w8_layer_t& Q = w8 ? w8->layers[l] : kNoScales;
-    auto run = [&](const GemvArgs& ga, const W8Scales& sc, const char* what) {
-      return w8 ? gemv_passes_w8(ga, sc, T, s, what) : gemv_passes(kGemvBf16, ga, T, s, what);
+    // MXFP4 (w4): the same two hooks on the e8m0 block-scale rows.  A call names its (up to three) linears; the scales of either
+    // form are looked up here.
+    static const mi_w4_layer_t kNoBlockScales = {};
+    const mi_w4_layer_t& Q4 = w4 ? w4->layers[l] : kNoBlockScales;
+    const float* const q8[7] = {Q.wq, Q.wk, Q.wv, Q.wo, Q.w1, Q.w2, Q.w3};
+    const uint8_t* const q4[7] = {Q4.wq, Q4.wk, Q4.wv, Q4.wo, Q4.w1, Q4.w2, Q4.w3};
+    auto sc8 = [&](const Lins& n) { return W8Scales{{n.i[0] < 0 ? nullptr : q8[n.i[0]], n.i[1] < 0 ? nullptr : q8[n.i[1]], n.i[2] < 0 ? nullptr : q8[n.i[2]]}}; };
+    auto sc4 = [&](const Lins& n) { return W4Scales{{n.i[0] < 0 ? nullptr : q4[n.i[0]], n.i[1] < 0 ? nullptr : q4[n.i[1]], n.i[2] < 0 ? nullptr : q4[n.i[2]]}}; };
+    auto run = [&](const GemvArgs& ga, const Lins& n, const char* what) {
+      if (w4) return gemv_passes_w4(ga, sc4(n), T, s, what);
+      return w8 ? gemv_passes_w8(ga, sc8(n), T, s, what) : gemv_passes(kGemvBf16, ga, T, s, what);
     };
-    auto deq = [&](const void* (&w)[3], const W8Scales& sc, int r0, int r1, int r2, int K, const char* what) {
+    auto deq = [&](const void* (&w)[3], const Lins& n, int r0, int r1, int r2, int K, const char* what) {
+      if (w4) {
+        const int nr[3] = {r0, r1, r2};
+        return dequant_group_w4(w, sc4(n), nr, K, ws.w8, s, what);
+      }
+      const W8Scales sc = sc8(n);
       if (!w8) return (int)MI_OK;
       if (!sc.s[0] || (w[1] && !sc.s[1]) || (w[2] && !sc.s[2])) return fail(MI_ERR_ARG, "%s: layer %d has a linear without row scales", entry, l);
       const int nr[3] = {r0, r1, r2};
       return dequant_group(w, sc, nr, K, ws.w8, s, what);
     };
     if (w8 && !(Q.wq && Q.wk && Q.wv && Q.wo && Q.w1 && Q.w2 && Q.w3)) return fail(MI_ERR_ARG, "%s: layer %d has a linear without row scales", entry, l);
+    if (w4 && !(Q4.wq && Q4.wk && Q4.wv && Q4.wo && Q4.w1 && Q4.w2 && Q4.w3)) return fail(MI_ERR_ARG, "%s: layer %d has a linear without block scales", entry, l);
     static const mi_lora_layer_t kNoAdapters = {};
     const mi_lora_layer_t& A = (lora && L.lora) ? *L.lora : kNoAdapters;
     const float ls = m->lora_scaling;
@@ -1164,11 +1301,11 @@ static int forward_body(const char* entry, const mi_model_t* m, const mi_w8_mode
       const RingWrite ring = {ck, cv, W, kvl};
       MI_TRY(run(gemv_qkv_rope(h, D, D, L.attention_norm, m->norm_eps, L.wq, L.wk, L.wv, nq, nkv, ws.qkv, qkv_cols, m->rope_cs, bt->tok_pos,
                                bt->tok_seq, Dh, branch == MI_BRANCH_DECODE ? &ring : nullptr),
-                 {{Q.wq, Q.wk, Q.wv}}, "qkv gemv"));
+                 Lins{{LIN_WQ, LIN_WK, LIN_WV}}, "qkv gemv"));
     } else {
       MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, L.attention_norm, T, D, m->norm_eps, s), "attention_norm"));
       const void* wqkv[3] = {L.wq, L.wk, L.wv};
-      MI_TRY(deq(wqkv, {{Q.wq, Q.wk, Q.wv}}, nq, nkv, nkv, D, "dequant q|k|v"));
+      MI_TRY(deq(wqkv, Lins{{LIN_WQ, LIN_WK, LIN_WV}}, nq, nkv, nkv, D, "dequant q|k|v"));
       GemmArgs g;
       memset(&g, 0, sizeof(g));
       g.epi = GEMM_STORE; g.M = T; g.N = qkv_cols; g.K = D; g.a = ws.xn; g.lda = D;
@@ -1201,10 +1338,10 @@ static int forward_body(const char* entry, const mi_model_t* m, const mi_w8_mode
       const LoraLinear wo = banked({{L.wo, nullptr, nullptr}, {A.wo_a, nullptr, nullptr}, {A.wo_b, nullptr, nullptr}, {D, 0, 0}, 1, MI_EPI_RESIDUAL});
       MI_TRY(lora_linear(h, D, ws.attn, nq, ws.attn, nq, T, nq, wo, h, nullptr, 0.f, m->lora_rank, ls, ws.xn, false, ws.lora_t, s));
     } else if (gemv) {
-      MI_TRY(run(gemv_residual(ws.attn, nq, L.wo, h, D), {{Q.wo, nullptr, nullptr}}, "wo gemv"));
+      MI_TRY(run(gemv_residual(ws.attn, nq, L.wo, h, D), Lins{{LIN_WO, -1, -1}}, "wo gemv"));
     } else {
       const void* wo[3] = {L.wo, nullptr, nullptr};
-      MI_TRY(deq(wo, {{Q.wo, nullptr, nullptr}}, D, 0, 0, nq, "dequant wo"));
+      MI_TRY(deq(wo, Lins{{LIN_WO, -1, -1}}, D, 0, 0, nq, "dequant wo"));
       MI_TRY(hip_rc(launch_gemm(gemm_args(GEMM_RESIDUAL, ws.attn, T, nq, wo[0], nullptr, D, h, h), s), "wo gemm"));
     }
 
@@ -1218,15 +1355,15 @@ static int forward_body(const char* entry, const mi_model_t* m, const mi_w8_mode
       MI_TRY(lora_linear(h, D, ws.hid, F, ws.hid, F, T, F, w2, h, nullptr, 0.f, m->lora_rank, ls, ws.xn, false, ws.lora_t, s));
     } else if (m->num_experts == 0) {
       if (gemv) {
-        MI_TRY(run(gemv_swiglu(h, D, L.ffn_norm, m->norm_eps, L.w1, L.w3, ws.hid, F), {{Q.w1, Q.w3, nullptr}}, "w13 gemv"));
-        MI_TRY(run(gemv_residual(ws.hid, F, L.w2, h, D), {{Q.w2, nullptr, nullptr}}, "w2 gemv"));
+        MI_TRY(run(gemv_swiglu(h, D, L.ffn_norm, m->norm_eps, L.w1, L.w3, ws.hid, F), Lins{{LIN_W1, LIN_W3, -1}}, "w13 gemv"));
+        MI_TRY(run(gemv_residual(ws.hid, F, L.w2, h, D), Lins{{LIN_W2, -1, -1}}, "w2 gemv"));
       } else {
         MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, L.ffn_norm, T, D, m->norm_eps, s), "ffn_norm"));
         const void* w13[3] = {L.w1, L.w3, nullptr};
-        MI_TRY(deq(w13, {{Q.w1, Q.w3, nullptr}}, F, F, 0, D, "dequant w1|w3"));
+        MI_TRY(deq(w13, Lins{{LIN_W1, LIN_W3, -1}}, F, F, 0, D, "dequant w1|w3"));
         MI_TRY(hip_rc(launch_gemm(gemm_args(GEMM_SWIGLU, ws.xn, T, D, w13[0], w13[1], F, ws.hid, nullptr), s), "w13 gemm"));
         const void* w2[3] = {L.w2, nullptr, nullptr};
-        MI_TRY(deq(w2, {{Q.w2, nullptr, nullptr}}, D, 0, 0, F, "dequant w2"));
+        MI_TRY(deq(w2, Lins{{LIN_W2, -1, -1}}, D, 0, 0, F, "dequant w2"));
         MI_TRY(hip_rc(launch_gemm(gemm_args(GEMM_RESIDUAL, ws.hid, T, F, w2[0], nullptr, D, h, h), s), "w2 gemm"));
       }
     } else {
@@ -1260,10 +1397,14 @@ static int forward_body(const char* entry, const mi_model_t* m, const mi_w8_mode
   return MI_OK;
 }
 
-int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) { return forward_body("mi_forward", m, nullptr, bt, stream); }
+int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) { return forward_body("mi_forward", m, nullptr, nullptr, bt, stream); }
 
 int mi_forward_w8(const mi_model_t* m, const mi_w8_model_t* w8, const mi_batch_t* bt, mi_stream_t stream) {
-  return forward_body(w8 ? "mi_forward_w8" : "mi_forward", m, w8, bt, stream);
+  return forward_body(w8 ? "mi_forward_w8" : "mi_forward", m, w8, nullptr, bt, stream);
+}
+
+int mi_forward_w4(const mi_model_t* m, const mi_w4_model_t* w4, const mi_batch_t* bt, mi_stream_t stream) {
+  return forward_body(w4 ? "mi_forward_w4" : "mi_forward", m, nullptr, w4, bt, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // Core of the weight-streaming GEMV for M <= 8 tokens (decode): HBM-bound, one pass over the weights.  One unit loop
 // (gemv_body) for 16-bit weight rows (gemv.hip: bf16, and fp16 in its -DGEMV_F16=1 compile) and for e4m3 rows with fp32 row
-// scales (gemv_w8.hip); the MoE down-projection (gemv.hip) uses the same batch loads and FMAs.  Host side: the launch plan.
+// scales (gemv_w8.hip) and for MXFP4 rows, e2m1 codes with one e8m0 scale byte per block of 32 (gemv_w4.hip); the MoE
+// down-projection (gemv.hip) uses the same batch loads and FMAs.  Host side: the launch plan.
 //
 // Structure (cdna_hip_programming.md "GEMV / M<=16 decode weights"): weights go straight HBM -> VGPR with 16-byte
 // non-temporal loads in batches of 8 per lane; a wave always has two batches (16 KiB) in flight, across the prologue and
@@ -20,18 +21,41 @@ namespace gemv_core {
 constexpr int BATCH = 8;  // 16-byte loads per lane per batch (NR rows x BATCH/NR chunks); two batches in flight
 
 // ---- weight formats.  PIECE: weights per 16-byte piece; a chunk is one wave instruction = 64 pieces = 1 << SHIFT weights.
+// VLOADS: vector loads per batch (x_finish counts two batches of them behind the LDS-DMAs); BLOCK: block-scaled (below).
 struct W16 {  // bf16 rows (fp16 in the GEMV_F16 compile)
   typedef bf16_t elem;
+  typedef float scale_t;
   static constexpr int PIECE = 8, SHIFT = 9;
-  static constexpr bool SCALED = false;
+  static constexpr bool SCALED = false, BLOCK = false;
+  static constexpr int VLOADS = 8;
 };
 // OCP e4m3 bytes; the real-valued weight is scale[r] * e4m3(W[r, k]).  Per output row acc = sum_k e4m3(W[r, k]) * x[k] in fp32
 // and y = acc * scale[r] in fp32 enters the epilogue where acc enters it for 16-bit rows.  K % 16 == 0.
 struct WE4m3 {
   typedef uint8_t elem;
+  typedef float scale_t;
   static constexpr int PIECE = 16, SHIFT = 10;
-  static constexpr bool SCALED = true;
+  static constexpr bool SCALED = true, BLOCK = false;
+  static constexpr int VLOADS = 8;
 };
+// OCP MXFP4: e2m1 codes, two per byte with the low nibble at the even k, and one e8m0 scale byte per block of 32 along K (scale
+// rows [rows, K / 32] beside the weight rows); the weight entering the dot product is 2^(b - 127) * e2m1(code), exact in bf16.  A
+// 16-byte piece is 32 weights = exactly one scale block: every piece load of a batch has one scale-byte load beside it (block-
+// scaled, as opposed to SCALED per row: nothing is applied in the epilogue).  K % 32 == 0.  Element offsets k of this format are
+// byte offsets k / 2 (wofs).
+struct WMxfp4 {
+  typedef uint8_t elem;
+  typedef uint8_t scale_t;
+  static constexpr int PIECE = 32, SHIFT = 11;
+  static constexpr bool SCALED = false, BLOCK = true;
+  static constexpr int VLOADS = 16;
+};
+// offset of weight k of a row, in F::elem
+template <class F>
+__device__ __forceinline__ size_t wofs(size_t k) {
+  if constexpr (F::BLOCK) return k >> 1;
+  else return k;
+}
 
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
@@ -51,10 +75,29 @@ __device__ __forceinline__ void cvt4_e4m3(uint32_t w, uint32_t& p01, uint32_t& p
   p23 = __builtin_amdgcn_perm(__float_as_uint(hi[1]), __float_as_uint(hi[0]), 0x07060302u);
 }
 
-template <class F, int NR>
+template <class F, int NR, bool BLK = F::BLOCK>
 struct Rows {
   const typename F::elem* p[NR];
 };
+template <class F, int NR>
+struct Rows<F, NR, true> {
+  const typename F::elem* p[NR];
+  const uint8_t* s[NR];  // the rows of block scales, [K / 32] bytes each
+};
+// the scale bytes of a batch beside its pieces (block-scaled formats; nothing otherwise)
+template <class F>
+struct ScaleBuf {};
+template <>
+struct ScaleBuf<WMxfp4> {
+  uint32_t b[BATCH];
+};
+
+// byte SEL of w = two e2m1 codes (k, k + 1), the low nibble first -> the bf16 pair scaled by 2^(b - 127), sc = the float b << 23:
+// one v_cvt_scalef32_pk_bf16_fp4 (op_sel picks the byte).  Exact: 8 magnitudes x a power of two.
+template <int SEL>
+__device__ __forceinline__ uint32_t cvt2_e2m1(uint32_t w, float sc) {
+  return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, SEL));
+}
 
 // One batch = chunks [c0, c0 + BATCH/NR) of each of the unit's NR rows: always exactly BATCH unconditional loads.
 // Chunk offsets past K are clamped to the row's last 16 bytes (fma_batch skips them) and a missing last row aliases
@@ -67,7 +110,18 @@ __device__ __forceinline__ void load_batch(const Rows<F, NR>& r, int c0, int K, 
   for (int u = 0; u < U; ++u) {
     const int e = min(((c0 + u) * 64 + lane) * F::PIECE, K - F::PIECE);
 #pragma unroll
-    for (int i = 0; i < NR; ++i) buf[i * U + u] = ld16_nt(r.p[i] + e);
+    for (int i = 0; i < NR; ++i) buf[i * U + u] = ld16_nt(r.p[i] + wofs<F>(e));
+  }
+}
+// ... and the scale bytes of the same (clamped) pieces: BATCH more unconditional loads, 64 consecutive bytes per wave instruction
+template <class F, int NR>
+__device__ __forceinline__ void load_scales(const Rows<F, NR>& r, int c0, int K, int lane, ScaleBuf<F>& sb) {
+  constexpr int U = BATCH / NR;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int e = min(((c0 + u) * 64 + lane) * F::PIECE, K - F::PIECE);
+#pragma unroll
+    for (int i = 0; i < NR; ++i) sb.b[i * U + u] = r.s[i][e >> 5];
   }
 }
 
@@ -105,6 +159,43 @@ __device__ __forceinline__ void fma_batch(const u32x4 (&buf)[BATCH], int c0, con
 #pragma unroll
               for (int c = 0; c < 4; ++c) acc[i][t] = dot2_bf16(p[i][c], xv[c], acc[i][t]);
           }
+        }
+      }
+    }
+  }
+}
+
+// MXFP4: a piece is 32 weights against 64 bytes of x.  Per quarter of the piece (one dword = 8 weights): 4 converts per row, shared
+// by all tokens, then 4 dot2 per row and token.
+template <int TT, int NR>
+__device__ __forceinline__ void fma_batch_w4(const u32x4 (&buf)[BATCH], const ScaleBuf<WMxfp4>& sb, int c0, const bf16_t* xs, int K,
+                                             int lane, float (&acc)[NR][TT]) {
+  constexpr int U = BATCH / NR;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int e = ((c0 + u) * 64 + lane) * 32;
+    if (e < K) {
+      float sc[NR];
+#pragma unroll
+      for (int i = 0; i < NR; ++i) sc[i] = __uint_as_float(sb.b[i * U + u] << 23);
+#pragma unroll
+      for (int h = 0; h < 4; ++h) {
+        uint32_t p[NR][4];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+          const uint32_t w = buf[i * U + u][h];
+          p[i][0] = cvt2_e2m1<0>(w, sc[i]);
+          p[i][1] = cvt2_e2m1<1>(w, sc[i]);
+          p[i][2] = cvt2_e2m1<2>(w, sc[i]);
+          p[i][3] = cvt2_e2m1<3>(w, sc[i]);
+        }
+#pragma unroll
+        for (int t = 0; t < TT; ++t) {
+          const u32x4 xv = *reinterpret_cast<const u32x4*>(xs + (size_t)t * K + e + 8 * h);
+#pragma unroll
+          for (int i = 0; i < NR; ++i)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) acc[i][t] = dot2_bf16(p[i][c], xv[c], acc[i][t]);
         }
       }
     }
@@ -181,7 +272,8 @@ __device__ __forceinline__ bool x_issue(XRegs<NX, NW>& xr, const bf16_t* x, int 
   return fits;
 }
 
-template <int TT, int NX, int NW, bool DMA, int NT = 256>
+// VMW: the vector loads issued behind the DMAs = two weight batches of the format (F::VLOADS each).
+template <int TT, int NX, int NW, bool DMA, int NT = 256, int VMW = 2 * BATCH>
 __device__ __forceinline__ void x_finish(bool in_regs, XRegs<NX, NW>& xr, bf16_t* xs, float* red, const bf16_t* ws,
                                          const bf16_t* x, int ldx, int T, int K, const bf16_t* norm_w, float eps) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -211,10 +303,11 @@ __device__ __forceinline__ void x_finish(bool in_regs, XRegs<NX, NW>& xr, bf16_t
     }
   } else if constexpr (DMA) {
     // the rows (and norm weights) were sent to LDS by x_issue's DMAs.  vmcnt retires in order and EXACTLY the two weight batches
-    // (2 x BATCH unconditional loads: gemv_body, moe_w2_kernel) were issued behind them: vmcnt(2 * BATCH) = the DMAs have landed, the weights
-    // stay in flight under the passes below, which read LDS only.
-    static_assert(BATCH == 8, "the wait below counts the two weight batches");
-    asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+    // (2 x BATCH unconditional loads: gemv_body, moe_w2_kernel; a block-scaled format has as many scale-byte loads again) were issued
+    // behind them: vmcnt(VMW) = the DMAs have landed, the weights stay in flight under the passes below, which read LDS only.
+    static_assert(BATCH == 8 && (VMW == 16 || VMW == 32), "the wait below counts the two weight batches");
+    if constexpr (VMW == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
     __syncthreads();
     if (norm_w != nullptr) {
       for (int p = tid; p < npieces; p += 256) {
@@ -310,6 +403,16 @@ __device__ __forceinline__ const E* seg_row(const GemvArgs& a, int r) {
   return GEMV_SEG_PICK(r, a.n0, a.n1, reinterpret_cast<const E*>(a.w0) + (size_t)r * a.K,
                        reinterpret_cast<const E*>(a.w1) + (size_t)(r - a.n0) * a.K, reinterpret_cast<const E*>(a.w2) + (size_t)(r - a.n1) * a.K);
 }
+// ... of MXFP4 rows (K / 2 bytes each), and the row's block scales (K / 32 bytes)
+__device__ __forceinline__ const uint8_t* seg_row_w4(const GemvArgs& a, int r) {
+  const size_t rb = (size_t)(a.K >> 1);
+  return GEMV_SEG_PICK(r, a.n0, a.n1, reinterpret_cast<const uint8_t*>(a.w0) + (size_t)r * rb,
+                       reinterpret_cast<const uint8_t*>(a.w1) + (size_t)(r - a.n0) * rb, reinterpret_cast<const uint8_t*>(a.w2) + (size_t)(r - a.n1) * rb);
+}
+__device__ __forceinline__ const uint8_t* seg_scale_row_w4(const GemvArgs& a, const uint8_t* const* scale, int r) {
+  const size_t rb = (size_t)(a.K >> 5);
+  return GEMV_SEG_PICK(r, a.n0, a.n1, scale[0] + (size_t)r * rb, scale[1] + (size_t)(r - a.n0) * rb, scale[2] + (size_t)(r - a.n1) * rb);
+}
 
 // the modes that fuse the RMSNorm into the prologue
 constexpr bool norm_mode(int mode) { return mode == GEMV_QKV_ROPE || mode == GEMV_SWIGLU || mode == GEMV_LOGITS || mode == GEMV_MOE_W13; }
@@ -317,12 +420,12 @@ constexpr bool norm_mode(int mode) { return mode == GEMV_QKV_ROPE || mode == GEM
 // F: weight format; TT: token rows staged in LDS; NR = rows per unit: one row pair, or two for e4m3 rows, which are half the
 // bytes, so that the fixed cost of a unit (wave reductions, epilogue, loop bookkeeping) weighs twice as much (launch_gemv_w8).
 // Row pair q: SWIGLU / MOE_W13 = (W1 row q, W3 row q), else output rows (2 q, 2 q + 1).
-// scale: the fp32 row scales of the (up to) three matrices, read by the SCALED formats only.
+// scale: the fp32 row scales of the (up to) three matrices, read by the SCALED formats only; the block-scale rows of the BLOCK ones.
 // Order: activation loads first (L2 hits), then two weight batches, and the prologue finishes under them.
 // NWV = waves per block: 4; 5 .. 8 for the plain modes (no fused RMSNorm: its passes are written for 256 threads) when the row
 // count has no even split over 4-wave blocks - Mistral-Nemo's 5120 rows are 2560 pairs = 256 CUs x 10 (launch_gemv).
 template <class F, int TT, int MODE, int NR, bool DMA, int NWV = 4>
-__device__ __forceinline__ void gemv_body(const GemvArgs& a, const float* const* scale, char* smem, int block_id, int n_blocks,
+__device__ __forceinline__ void gemv_body(const GemvArgs& a, const typename F::scale_t* const* scale, char* smem, int block_id, int n_blocks,
                                           int problem) {
   typedef typename F::elem E;
   constexpr int RP = NR / 2, U = BATCH / NR;
@@ -378,7 +481,20 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, const float* const*
       // a unit's missing second pair repeats the last one.  Two-row e4m3 units keep the clamp although it changes nothing: without
       // it hipcc lays the Wo kernel out 120 ns slower per call (profiles/EXPERIMENTS.md); the 16-bit rows never had it.
       const int q = (RP == 1 && !F::SCALED) ? uu : min(uu * RP + p, npairs - 1);
-      if (MODE == GEMV_SWIGLU) {
+      if constexpr (F::BLOCK) {  // (STORE / RESIDUAL / SWIGLU / QKV_ROPE)
+        if (MODE == GEMV_SWIGLU) {
+          r.p[2 * p] = reinterpret_cast<const E*>(a.w0) + (size_t)q * (a.K >> 1);
+          r.p[2 * p + 1] = reinterpret_cast<const E*>(a.w1) + (size_t)q * (a.K >> 1);
+          r.s[2 * p] = scale[0] + (size_t)q * (a.K >> 5);
+          r.s[2 * p + 1] = scale[1] + (size_t)q * (a.K >> 5);
+        } else {
+          const int r1 = (2 * q + 1 < a.N) ? 2 * q + 1 : 2 * q;  // odd N: alias, result dropped in the epilogue
+          r.p[2 * p] = seg_row_w4(a, 2 * q);
+          r.p[2 * p + 1] = seg_row_w4(a, r1);
+          r.s[2 * p] = seg_scale_row_w4(a, scale, 2 * q);
+          r.s[2 * p + 1] = seg_scale_row_w4(a, scale, r1);
+        }
+      } else if (MODE == GEMV_SWIGLU) {
         r.p[2 * p] = reinterpret_cast<const E*>(a.w0) + (size_t)q * a.K;
         r.p[2 * p + 1] = reinterpret_cast<const E*>(a.w1) + (size_t)q * a.K;
       } else if (MODE == GEMV_MOE_W13) {
@@ -397,26 +513,32 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, const float* const*
   int ul = u, jl = 0;
   Rows<F, NR> rpl = unit_rows(min(ul, units - 1));
   u32x4 bufA[BATCH], bufB[BATCH];
+  ScaleBuf<F> sbA, sbB;  // (block-scaled formats: the scale bytes of the two batches)
   // Past the wave's last unit `issue` loads BATCH times one L2-resident line instead of branching around the loads:
   // the row pointers and chunk offset are SELECTED (real rows, or one dummy line) and the BATCH loads are issued
   // unconditionally, which keeps the loop body one basic block and the compiler's wait for one buffer at
   // "the other buffer's BATCH loads may stay in flight".  The trailing loads are never consumed.
   const E* dummy = reinterpret_cast<const E*>(x);
-  auto issue = [&](u32x4 (&buf)[BATCH]) {
+  auto issue = [&](u32x4 (&buf)[BATCH], ScaleBuf<F>& sb) {
     const bool live = ul < units;
     Rows<F, NR> r;
 #pragma unroll
     for (int i = 0; i < NR; ++i) r.p[i] = live ? rpl.p[i] : dummy;
     load_batch<F, NR>(r, live ? jl * U : 0, live ? a.K : F::PIECE, live ? lane : 0, buf);
+    if constexpr (F::BLOCK) {
+#pragma unroll
+      for (int i = 0; i < NR; ++i) r.s[i] = live ? rpl.s[i] : reinterpret_cast<const uint8_t*>(dummy);
+      load_scales<F, NR>(r, live ? jl * U : 0, live ? a.K : F::PIECE, live ? lane : 0, sb);
+    }
     if (live && ++jl == nb) {
       jl = 0;
       ul += nwaves;
       if (ul < units) rpl = unit_rows(ul);
     }
   };
-  issue(bufA);
-  issue(bufB);
-  x_finish<TT, NX, NW, DMA, NWV * 64>(in_regs, xr, xs, red, ws, x, a.ldx, T, a.K, a.norm_w, a.eps);
+  issue(bufA, sbA);
+  issue(bufB, sbB);
+  x_finish<TT, NX, NW, DMA, NWV * 64, 2 * F::VLOADS>(in_regs, xr, xs, red, ws, x, a.ldx, T, a.K, a.norm_w, a.eps);
 
   float acc[NR][TT];
 #pragma unroll
@@ -542,9 +664,10 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, const float* const*
 
   // One step = consume the oldest batch, refill the same registers with the batch two ahead (ping-pong between
   // bufA and bufB: no register copies, so the compiler's wait for bufA leaves bufB's eight loads in flight).
-  auto step = [&](u32x4 (&buf)[BATCH]) {
-    fma_batch<F, TT, NR>(buf, jc * U, xs, a.K, lane, acc);
-    issue(buf);
+  auto step = [&](u32x4 (&buf)[BATCH], ScaleBuf<F>& sb) {
+    if constexpr (F::BLOCK) fma_batch_w4<TT, NR>(buf, sb, jc * U, xs, a.K, lane, acc);
+    else fma_batch<F, TT, NR>(buf, jc * U, xs, a.K, lane, acc);
+    issue(buf, sb);
     if (++jc == nb) {
       jc = 0;
       if (u < units) finish_unit();
@@ -558,13 +681,13 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, const float* const*
   // and the "two batches in flight" of the design was one.
   if (u < units) {
     do {
-      step(bufA);
-      step(bufB);
+      step(bufA, sbA);
+      step(bufB, sbB);
     } while (u < units);
   }
 }
 
-// ---- the launch plan (host), shared by launch_gemv and launch_gemv_w8
+// ---- the launch plan (host), shared by launch_gemv, launch_gemv_w8 and launch_gemv_w4
 
 // 5 and 7 rows run on the 6- and 8-row instantiations, which stage 6 / 8 rows in LDS
 inline int round_tt(int T) { return T == 5 ? 6 : (T == 7 ? 8 : T); }

@@ -80,6 +80,19 @@ class MiW8Model(C.Structure):
 
 MI_W8_FP8_E4M3 = 1  # include/mistral_hip.h
 
+
+class MiW4Layer(C.Structure):
+    """`mi_w4_layer_t`: device e8m0 block scales [rows, K / 32] of the seven quantised linears of a layer (weight-only MXFP4)."""
+    _fields_ = [(n, _vp) for n in ("wq", "wk", "wv", "wo", "w1", "w2", "w3")]
+
+
+class MiW4Model(C.Structure):
+    """`mi_w4_model_t`: the quantisation beside an MiModel whose linear pointers are MXFP4 code bytes."""
+    _fields_ = [("format", C.c_int32), ("layers", C.POINTER(MiW4Layer))]
+
+
+MI_W4_MXFP4 = 2  # include/mistral_hip.h
+
 _lib: Optional[C.CDLL] = None
 
 _SIGS = {
@@ -125,6 +138,14 @@ _SIGS = {
                                          C.c_int, _vp, C.c_float, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "mi_workspace_bytes_w8": (C.c_size_t, [C.POINTER(MiModel), C.POINTER(MiW8Model), C.c_int, C.c_int, C.c_int]),
     "mi_forward_w8": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiW8Model), C.POINTER(MiBatch), _vp]),
+    # weight-only MXFP4 (additive likewise)
+    "mi_linear_w4_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "mi_linear_w4": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp), C.POINTER(C.c_int), C.c_int,
+                               _vp, _vp, C.c_float, C.POINTER(_vp), _vp, C.c_size_t, _vp]),
+    "mi_qkv_rope_kvwrite_w4": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int,
+                                         C.c_int, _vp, C.c_float, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
+    "mi_workspace_bytes_w4": (C.c_size_t, [C.POINTER(MiModel), C.POINTER(MiW4Model), C.c_int, C.c_int, C.c_int]),
+    "mi_forward_w4": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiW4Model), C.POINTER(MiBatch), _vp]),
     "mi_workspace_bytes_generic": (C.c_size_t, [C.POINTER(MiModel), C.c_int, C.c_int]),  # ABI v6
     "mi_forward_generic": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiBatch), C.c_int, _vp]),
     "mi_embedding_generic": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
@@ -156,6 +177,7 @@ _SIGS = {
     "mi_debug_set_engine_variant": (C.c_int, [C.c_int]),
     "mi_debug_engine_route": (C.c_int, [C.c_int] * 12 + [C.c_char_p, C.c_size_t]),
     "mi_debug_set_prefill_kernels": (C.c_int, [C.c_int, C.c_int]),
+    "mi_debug_gemv_w4_row_pairs": (C.c_int, [C.c_int, C.c_int]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -300,6 +322,41 @@ def linear_w8(x: torch.Tensor, weights: Sequence[torch.Tensor], scales: Sequence
     check(L.mi_linear_w8(dev_ptr(out), out.stride(0), dev_ptr(x), x.stride(0), M, K, wp, nr, epilogue, dev_ptr(residual),
                          dev_ptr(norm_w), float(eps), sp, scratch.data_ptr() if need else None, need, stream_ptr(x.device)),
           "mi_linear_w8")
+    return out
+
+
+def _check_w4(w: torch.Tensor, sc: torch.Tensor, K: int) -> None:
+    assert K % 32 == 0, f"MXFP4: K = {K} must be a multiple of 32"
+    assert w.dtype == torch.uint8 and w.is_contiguous() and w.shape[1] == K // 2
+    assert sc.dtype == torch.uint8 and sc.is_contiguous() and tuple(sc.shape) == (w.shape[0], K // 32)
+
+
+def linear_w4(x: torch.Tensor, weights: Sequence[torch.Tensor], scales: Sequence[torch.Tensor], epilogue: int = EPI_STORE,
+              residual: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`linear` on weight-only MXFP4 matrices (mi_linear_w4): weights[i] uint8 code bytes [n_i, K / 2] (low nibble = even k),
+    scales[i] uint8 e8m0 block scales [n_i, K / 32]; STORE / RESIDUAL / SWIGLU.  M <= 8: the MXFP4 GEMV; above: dequantise into a
+    per-call scratch + the bf16 GEMM."""
+    assert 1 <= len(weights) <= 3 and len(scales) == len(weights) and x.dim() == 2
+    if x.dtype != torch.bfloat16:
+        raise NotImplementedError("MXFP4 weight-only linears take bfloat16 activations (fp16 / fp32 storage is not implemented)")
+    M, K = x.shape
+    n_rows = [w.shape[0] for w in weights]
+    for w, sc in zip(weights, scales):
+        _check_w4(w, sc, K)
+    N = n_rows[0] if epilogue == EPI_SWIGLU else sum(n_rows)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    pad = [None] * (3 - len(weights))
+    wp = (_vp * 3)(*[dev_ptr(w, torch.uint8) for w in weights], *pad)
+    sp = (_vp * 3)(*[dev_ptr(sc, torch.uint8) for sc in scales], *pad)
+    nr = (C.c_int * 3)(*n_rows, *([0] * (3 - len(weights))))
+    L = lib()
+    need = L.mi_linear_w4_scratch_bytes(M, K, nr, epilogue)
+    scratch = torch.empty(need, dtype=torch.uint8, device=x.device) if need else None  # per call, from the caching allocator
+    check(L.mi_linear_w4(dev_ptr(out), out.stride(0), dev_ptr(x), x.stride(0), M, K, wp, nr, epilogue, dev_ptr(residual),
+                         dev_ptr(norm_w), float(eps), sp, scratch.data_ptr() if need else None, need, stream_ptr(x.device)),
+          "mi_linear_w4")
     return out
 
 
@@ -577,6 +634,29 @@ def qkv_rope_kvwrite_w8(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv:
                                        dev_ptr(tok_pos, torch.int32), dev_ptr(tok_seq, torch.int32), dev_ptr(cache_k), dev_ptr(cache_v), W,
                                        _kv_layout2(cache_k, cache_v) if cache_k is not None else KV_SLOT_MAJOR, stream_ptr(x.device)),
           "mi_qkv_rope_kvwrite_w8")
+    return out
+
+
+def qkv_rope_kvwrite_w4(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor, sq: torch.Tensor, sk: torch.Tensor,
+                        sv: torch.Tensor, head_dim: int, rope_cs: torch.Tensor, tok_pos: torch.Tensor,
+                        norm_w: Optional[torch.Tensor] = None, eps: float = 0.0, cache_k: Optional[torch.Tensor] = None,
+                        cache_v: Optional[torch.Tensor] = None, tok_seq: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`qkv_rope_kvwrite` on weight-only MXFP4 matrices (mi_qkv_rope_kvwrite_w4): wq / wk / wv code bytes [n, D / 2], sq / sk / sv
+    e8m0 block scales [n, D / 32]."""
+    T, D = x.shape
+    nq, nkv = wq.shape[0], wk.shape[0]
+    assert wv.shape[0] == nkv and rope_cs.dtype == torch.float32 and rope_cs.is_contiguous() and tok_pos.dtype == torch.int32
+    for w, sc in zip((wq, wk, wv), (sq, sk, sv)):
+        _check_w4(w, sc, D)
+    out = torch.empty((T, nq + 2 * nkv), dtype=x.dtype, device=x.device)
+    W = cache_k.shape[1] if cache_k is not None else 0
+    u8, f32 = torch.uint8, torch.float32
+    check(lib().mi_qkv_rope_kvwrite_w4(dev_ptr(out), out.stride(0), dev_ptr(x), x.stride(0), T, D, dev_ptr(wq, u8), dev_ptr(wk, u8),
+                                       dev_ptr(wv, u8), dev_ptr(sq, u8), dev_ptr(sk, u8), dev_ptr(sv, u8), nq // head_dim,
+                                       nkv // head_dim, head_dim, dev_ptr(norm_w), float(eps), dev_ptr(rope_cs, f32), rope_cs.shape[0],
+                                       dev_ptr(tok_pos, torch.int32), dev_ptr(tok_seq, torch.int32), dev_ptr(cache_k), dev_ptr(cache_v), W,
+                                       _kv_layout2(cache_k, cache_v) if cache_k is not None else KV_SLOT_MAJOR, stream_ptr(x.device)),
+          "mi_qkv_rope_kvwrite_w4")
     return out
 
 

@@ -48,17 +48,20 @@ class LoraArgs(_FromDict):
 
 
 QFORMAT_FP8_E4M3 = "fp8_e4m3"
+QFORMAT_MXFP4 = "mxfp4"
+QFORMATS = (QFORMAT_FP8_E4M3, QFORMAT_MXFP4)
 
 
 @dataclass
 class QuantizationArgs(_FromDict):
     """`quantization` block of params.json: weight-only quantisation of the seven linears of every layer (quant.py)."""
-    qformat_weight: str         # "fp8_e4m3": OCP e4m3 bytes + one fp32 scale per output row
+    qformat_weight: str         # "fp8_e4m3": OCP e4m3 bytes + one fp32 scale per output row; "mxfp4": OCP MXFP4, e2m1 codes in
+                                # blocks of 32 along `in` + one e8m0 scale byte per block
 
     def __post_init__(self) -> None:
-        if self.qformat_weight != QFORMAT_FP8_E4M3:
+        if self.qformat_weight not in QFORMATS:
             raise NotImplementedError(f"quantization.qformat_weight {self.qformat_weight!r} is not implemented "
-                                      f"({QFORMAT_FP8_E4M3!r} is the only weight format)")
+                                      f"(the weight formats are {', '.join(repr(q) for q in QFORMATS)})")
 
 
 @dataclass
@@ -96,7 +99,7 @@ class TransformerArgs(_FromDict):
     rope_theta: Optional[float] = None          # None -> 1e6 (reference transformer.py:115)
     moe: Optional[MoeArgs] = None               # sparse FFN: experts and experts per token
     lora: Optional[LoraArgs] = None             # un-merged LoRA layers (lora.py; dense bf16 models); without it load_lora() merges
-    quantization: Optional[QuantizationArgs] = None  # weight-only FP8 linears (quant.py; dense bf16 models without `lora`)
+    quantization: Optional[QuantizationArgs] = None  # weight-only FP8 / MXFP4 linears (quant.py; dense bf16 models without `lora`)
     sliding_window: Union[None, int, List[Optional[int]]] = None   # one window, or one per layer (cycled)
     _sliding_window: Union[None, int, List[Optional[int]]] = None  # legacy spelling of the same key
     model_type: str = "transformer"

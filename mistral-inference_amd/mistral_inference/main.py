@@ -77,8 +77,8 @@ def get_model_cls(model_path: str) -> Type[Transformer]:
 
 def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7, num_pipeline_ranks: int = 1,
                 instruct: bool = False, lora_path: Optional[str] = None, quantize: Optional[str] = None) -> None:
-    """quantize="fp8_e4m3": quantise a bf16 checkpoint to weight-only FP8 while it loads (a folder that quant.quantize_checkpoint
-    wrote needs no flag)."""
+    """quantize="fp8_e4m3" / "mxfp4": quantise a bf16 checkpoint to weight-only FP8 / MXFP4 while it loads (a folder that
+    quant.quantize_checkpoint wrote needs no flag)."""
     num_pipeline_ranks = init_pipeline() if is_torchrun() else num_pipeline_ranks
     should_print = _should_print()
     mistral_tokenizer = load_tokenizer(Path(model_path))

@@ -14,7 +14,13 @@ the K/V rings stay bf16.  Dense bf16 models without un-merged LoRA only.
 
 Checkpoint layout: `<linear>.weight` with dtype F8_E4M3, `<linear>.qscale_weight` fp32 [out] (a scalar or [1] is broadcast at
 load), `params.json` with `"quantization": {"qformat_weight": "fp8_e4m3"}`.  Compatibility is claimed only with checkpoints
-that `quantize_checkpoint` wrote."""
+that `quantize_checkpoint` wrote.
+
+MXFP4 (`qformat_weight` "mxfp4", OCP microscaling): e2m1 codes in blocks of 32 along `in`, one e8m0 scale byte per block, 4.25 bits
+per weight.  `<linear>.weight` is U8 [out, in / 2], two codes per byte with the LOW nibble at the even k; `<linear>.qscale_weight`
+is U8 [out, in / 32], byte b meaning 2^(b - 127) (255, the e8m0 NaN, is refused).  The real-valued weight is
+`2^(b - 127) * e2m1(code)`, exact in bf16, so `Mxfp4Linear` (one `mi_linear_w4` call, csrc/gemv_w4.hip) computes the bf16 model on
+the dequantised weights up to fp32 summation order, at any number of rows.  `in` must be a multiple of 32."""
 import json
 import re
 from pathlib import Path
@@ -24,7 +30,7 @@ import torch
 from torch import nn
 
 from . import _hip
-from .args import QFORMAT_FP8_E4M3, QuantizationArgs  # noqa: F401
+from .args import QFORMAT_FP8_E4M3, QFORMAT_MXFP4, QFORMATS, QuantizationArgs  # noqa: F401
 
 QSCALE_KEY = "qscale_weight"   # `<linear>.qscale_weight`: the one place that names the checkpoint key of a row scale
 QSCALE_ACT_KEY = "qscale_act"  # per-tensor activation scales of FP8-activation checkpoints: not implemented, a foreign key here
@@ -37,11 +43,35 @@ FP8_LORA_REFUSAL = ("un-merged LoRA on an FP8-quantised base is not implemented;
 FP8_MOE_REFUSAL = "FP8 weight-only quantisation of a MoE model is not implemented (the expert kernels read bf16 weights)"
 FP8_MERGE_REFUSAL = ("load_lora: merging an adapter into FP8-quantised weights is not implemented (the merge needs the bf16 "
                      "weights); merge into the bf16 checkpoint and quantise the result")
+MXFP4_LORA_REFUSAL = ("un-merged LoRA on an MXFP4-quantised base is not implemented; merge the adapter into the bf16 weights "
+                      "(Transformer.load_lora on a bf16 model) and quantise the result")
+MXFP4_MOE_REFUSAL = "MXFP4 weight-only quantisation of a MoE model is not implemented (the expert kernels read bf16 weights)"
+MXFP4_MERGE_REFUSAL = ("load_lora: merging an adapter into MXFP4-quantised weights is not implemented (the merge needs the bf16 "
+                       "weights); merge into the bf16 checkpoint and quantise the result")
+MXFP4_BLOCK = 32
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # magnitude of code & 7; code & 8 is the sign
+
+
+def is_mxfp4(quantization: Optional[QuantizationArgs]) -> bool:
+    return quantization is not None and quantization.qformat_weight == QFORMAT_MXFP4
+
+
+def lora_refusal(quantization: Optional[QuantizationArgs]) -> str:
+    return MXFP4_LORA_REFUSAL if is_mxfp4(quantization) else FP8_LORA_REFUSAL
+
+
+def moe_refusal(quantization: Optional[QuantizationArgs]) -> str:
+    return MXFP4_MOE_REFUSAL if is_mxfp4(quantization) else FP8_MOE_REFUSAL
+
+
+def merge_refusal(quantization: Optional[QuantizationArgs]) -> str:
+    return MXFP4_MERGE_REFUSAL if is_mxfp4(quantization) else FP8_MERGE_REFUSAL
 
 
 def check_quantize_arg(quantize: Optional[str]) -> None:
-    if quantize is not None and quantize != QFORMAT_FP8_E4M3:
-        raise NotImplementedError(f"quantize={quantize!r} is not implemented ({QFORMAT_FP8_E4M3!r} is the only weight format)")
+    if quantize is not None and quantize not in QFORMATS:
+        raise NotImplementedError(f"quantize={quantize!r} is not implemented "
+                                  f"(the weight formats are {', '.join(repr(q) for q in QFORMATS)})")
 
 
 def refuse_fp8_combinations(args, dtype: Optional[torch.dtype]) -> None:
@@ -49,10 +79,13 @@ def refuse_fp8_combinations(args, dtype: Optional[torch.dtype]) -> None:
     if args.quantization is None:
         return
     if args.lora is not None:
-        raise NotImplementedError(FP8_LORA_REFUSAL)
+        raise NotImplementedError(lora_refusal(args.quantization))
     if args.moe is not None:
-        raise NotImplementedError(FP8_MOE_REFUSAL)
+        raise NotImplementedError(moe_refusal(args.quantization))
     if dtype is not None and dtype != torch.bfloat16:
+        if is_mxfp4(args.quantization):
+            raise NotImplementedError(f"MXFP4 weight-only quantisation with fp16 / fp32 storage ({dtype}) is not implemented: the "
+                                      "activations, norms and the LM head of a quantised model are bfloat16")
         raise NotImplementedError(f"FP8 weight-only quantisation with fp16 / fp32 storage ({dtype}) is not implemented: the "
                                   "activations, norms and the LM head of a quantised model are bfloat16")
 
@@ -119,7 +152,7 @@ class Fp8Linear(nn.Module):
         def keep_dtype(t: torch.Tensor) -> torch.Tensor:  # device moves pass; a dtype cast touches neither bytes nor scales
             out = fn(t)
             return out if out.dtype == t.dtype else t.to(device=out.device)
-        return super()._apply(keep_dtype, recurse)
+        return nn.Module._apply(self, keep_dtype, recurse)
 
     @torch.no_grad()
     def load_quantized(self, q: torch.Tensor, scale: torch.Tensor) -> None:
@@ -151,42 +184,140 @@ def linear_fp8(x: torch.Tensor, mods: Sequence[Fp8Linear], epilogue: int = _hip.
     return _hip.linear_w8(x, [m.weight for m in mods], [m.qscale_weight for m in mods], epilogue, residual, norm_w, eps)
 
 
-def quantize_state_tensor(key: str, t: torch.Tensor) -> Dict[str, torch.Tensor]:
-    """One checkpoint tensor -> the tensors that replace it: a quantised linear becomes its bytes and its row scales, anything
-    else stays as it is."""
+def quantize_blocks(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[out, in] (bf16 / fp32), in % 32 == 0 -> (packed uint8 [out, in / 2], scale uint8 [out, in / 32]): OCP MXFP4.  Per block
+    of 32 the scale is 2^e with e = ceil(log2(amax / 6)), so amax / scale lies in (3, 6]; an all-zero block gets e = 0 (byte
+    127); e is clamped to [-127, 127].  Codes are round-to-nearest, ties to the even code, onto +-{0, .5, 1, 1.5, 2, 3, 4, 6},
+    saturating at +-6; a code whose dequantised value would pass the largest bf16 (a block holding bf16 max) steps down.  Two
+    codes per byte, the low nibble at the even k.  Integer exponent arithmetic and comparisons only, so the CPU and the device
+    give the same bytes."""
+    assert w.dim() == 2 and w.is_floating_point()
+    out, K = w.shape
+    if K % MXFP4_BLOCK:
+        raise ValueError(f"quantize_blocks: in = {K} must be a multiple of {MXFP4_BLOCK} (one e8m0 scale per block of 32)")
+    wf = w.float().reshape(out, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = wf.abs().amax(dim=2)
+    if not bool(torch.isfinite(amax).all()):
+        raise ValueError("quantize_blocks: the weight holds inf or NaN")
+    mant, ex = torch.frexp(amax)                     # amax = mant * 2^ex, mant in [0.5, 1)
+    # amax / 6 = (mant / 0.75) * 2^(ex - 3): the ceil of its log2 is ex - 3, one more when mant > 0.75
+    e = ex - 3 + (mant > 0.75).to(ex.dtype)
+    e = torch.where(amax > 0, e, torch.zeros_like(e)).clamp_(-127, 127)
+    scale = torch.ldexp(torch.ones_like(amax), e)
+    v = wf / scale[:, :, None]                       # exact: a power of two
+    a = v.abs()
+    idx = ((a > 0.25).to(torch.uint8) + (a >= 0.75).to(torch.uint8) + (a > 1.25).to(torch.uint8) + (a >= 1.75).to(torch.uint8)
+           + (a > 2.5).to(torch.uint8) + (a >= 3.5).to(torch.uint8) + (a > 5.0).to(torch.uint8))
+    tab = torch.tensor(E2M1_VALUES, dtype=torch.float32, device=w.device)
+    over = tab[idx.long()] * scale[:, :, None] > torch.finfo(torch.bfloat16).max
+    idx = torch.where(over, idx - 1, idx)
+    codes = torch.where((v < 0) & (idx > 0), idx | 8, idx).reshape(out, K)
+    packed = codes[:, 0::2] | (codes[:, 1::2] << 4)
+    return packed.contiguous(), (e + 127).to(torch.uint8).contiguous()
+
+
+def check_mxfp4_tensors(packed: torch.Tensor, scale: torch.Tensor, out_features: int, in_features: int, what: str = "MXFP4") -> None:
+    """What the tensors of an MXFP4 linear must be (ValueError otherwise); nothing here reads the device unless they live there."""
+    if in_features % MXFP4_BLOCK:
+        raise ValueError(f"{what}: in = {in_features} must be a multiple of {MXFP4_BLOCK} (one e8m0 scale per block of 32)")
+    if packed.dtype != torch.uint8 or scale.dtype != torch.uint8:
+        raise ValueError(f"{what}: an MXFP4 linear is U8 codes and U8 e8m0 scales, got {packed.dtype} and {scale.dtype}")
+    if tuple(packed.shape) != (out_features, in_features // 2) or tuple(scale.shape) != (out_features, in_features // MXFP4_BLOCK):
+        raise ValueError(f"{what}: MXFP4 codes {tuple(packed.shape)} / scales {tuple(scale.shape)} do not fit a linear "
+                         f"[{out_features}, {in_features}] (codes [out, in / 2], scales [out, in / 32])")
+    if not scale.is_meta and bool((scale == 255).any()):
+        raise ValueError(f"{what}: scale byte 255 (the e8m0 NaN)")
+
+
+def dequantize_mxfp4(packed: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """bf16 [out, in] of 2^(scale - 127) * e2m1(code): exact."""
+    out, half = packed.shape
+    tab = torch.tensor(E2M1_VALUES + tuple(-x for x in E2M1_VALUES), dtype=torch.float32, device=packed.device)
+    vals = torch.stack((tab[(packed & 15).long()], tab[(packed >> 4).long()]), dim=2).reshape(out, half * 2 // MXFP4_BLOCK, MXFP4_BLOCK)
+    sc = torch.ldexp(torch.ones(scale.shape, dtype=torch.float32, device=scale.device), scale.to(torch.int32) - 127)
+    return (vals * sc[:, :, None]).reshape(out, half * 2).to(torch.bfloat16)
+
+
+class Mxfp4Linear(nn.Module):
+    """`nn.Linear(bias=False)` on MXFP4 weights: e2m1 codes [out, in / 2] and e8m0 block scales [out, in / 32], both uint8
+    parameters that no dtype cast touches."""
+
+    def __init__(self, in_features: int, out_features: int, bias: bool = False):
+        super().__init__()
+        assert not bias
+        if in_features % MXFP4_BLOCK:
+            raise ValueError(f"Mxfp4Linear: in = {in_features} must be a multiple of {MXFP4_BLOCK} (one e8m0 scale per block of 32)")
+        self.in_features, self.out_features = in_features, out_features
+        self.weight = nn.Parameter(torch.zeros((out_features, in_features // 2), dtype=torch.uint8), requires_grad=False)
+        self.qscale_weight = nn.Parameter(torch.full((out_features, in_features // MXFP4_BLOCK), 127, dtype=torch.uint8), requires_grad=False)
+
+    _apply = Fp8Linear._apply
+
+    @torch.no_grad()
+    def load_quantized(self, packed: torch.Tensor, scale: torch.Tensor) -> None:
+        check_mxfp4_tensors(packed, scale, self.out_features, self.in_features, "Mxfp4Linear.load_quantized")
+        self.weight = nn.Parameter(packed.contiguous(), requires_grad=False)
+        self.qscale_weight = nn.Parameter(scale.contiguous().to(packed.device), requires_grad=False)
+
+    def dequantized(self) -> torch.Tensor:
+        return dequantize_mxfp4(self.weight, self.qscale_weight)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        shape = x.shape
+        out = linear_mxfp4(x.reshape(-1, shape[-1]), (self,), _hip.EPI_STORE)
+        return out.view(*shape[:-1], self.out_features)
+
+
+def linear_mxfp4(x: torch.Tensor, mods: Sequence[Mxfp4Linear], epilogue: int = _hip.EPI_STORE, residual: Optional[torch.Tensor] = None,
+                 norm_w: Optional[torch.Tensor] = None, eps: float = 0.0) -> torch.Tensor:
+    """`_hip.linear` over up to three Mxfp4Linear modules that share an input (q|k|v; SWIGLU: w1, w3)."""
+    return _hip.linear_w4(x, [m.weight for m in mods], [m.qscale_weight for m in mods], epilogue, residual, norm_w, eps)
+
+
+def quantized_linear_cls(quantization: QuantizationArgs):
+    return Mxfp4Linear if is_mxfp4(quantization) else Fp8Linear
+
+
+def quantize_state_tensor(key: str, t: torch.Tensor, qformat: str = QFORMAT_FP8_E4M3) -> Dict[str, torch.Tensor]:
+    """One checkpoint tensor -> the tensors that replace it: a quantised linear becomes its bytes and its row (MXFP4: block)
+    scales, anything else stays as it is."""
+    check_quantize_arg(qformat)
     if not is_quantized_linear_key(key):
         return {key: t}
     if t.dtype != torch.bfloat16:
-        raise NotImplementedError(f"{key}: FP8 quantisation starts from a bfloat16 checkpoint, got {t.dtype}")
-    q, scale = quantize_rows(t)
+        name = "MXFP4" if qformat == QFORMAT_MXFP4 else "FP8"
+        raise NotImplementedError(f"{key}: {name} quantisation starts from a bfloat16 checkpoint, got {t.dtype}")
+    q, scale = quantize_blocks(t) if qformat == QFORMAT_MXFP4 else quantize_rows(t)
     return {key: q, key[:-len("weight")] + QSCALE_KEY: scale}
 
 
-def quantize_checkpoint(src_folder: Union[Path, str], dst_folder: Union[Path, str]) -> Path:
-    """bf16 folder (params.json + consolidated.safetensors) -> FP8 weight-only folder, tensor by tensor on the CPU: the seven
-    linears of every layer become `<linear>.weight` (F8_E4M3) + `<linear>.qscale_weight` (fp32 [out]); everything else is
-    copied.  Other files of the folder (tokenizer) are the caller's to copy."""
+def quantize_checkpoint(src_folder: Union[Path, str], dst_folder: Union[Path, str], qformat: str = QFORMAT_FP8_E4M3) -> Path:
+    """bf16 folder (params.json + consolidated.safetensors) -> weight-only quantised folder, tensor by tensor on the CPU: the
+    seven linears of every layer become `<linear>.weight` (F8_E4M3) + `<linear>.qscale_weight` (fp32 [out]), or with
+    qformat="mxfp4" U8 [out, in / 2] + U8 [out, in / 32]; everything else is copied.  Other files of the folder (tokenizer) are
+    the caller's to copy."""
     import safetensors
     from safetensors.torch import save_file
     from .args import TransformerArgs
 
+    check_quantize_arg(qformat)
     src, dst = Path(src_folder), Path(dst_folder)
     with open(src / "params.json", "r") as f:
         params = json.load(f)
     args = TransformerArgs.from_dict(params)
     if args.quantization is not None:
         raise ValueError(f"{src} is already quantised ({args.quantization.qformat_weight})")
-    args.quantization = QuantizationArgs(QFORMAT_FP8_E4M3)
+    args.quantization = QuantizationArgs(qformat)
     refuse_fp8_combinations(args, None)
     st_file = src / "consolidated.safetensors"
     assert st_file.exists(), f"{st_file} does not exist (quantize_checkpoint reads safetensors)"
     out: Dict[str, torch.Tensor] = {}
     with safetensors.safe_open(str(st_file), framework="pt", device="cpu") as f:
         for k in f.keys():
-            out.update(quantize_state_tensor(k, f.get_tensor(k)))
+            out.update(quantize_state_tensor(k, f.get_tensor(k), qformat))
     dst.mkdir(parents=True, exist_ok=True)
     save_file(out, str(dst / "consolidated.safetensors"))
-    params["quantization"] = {"qformat_weight": QFORMAT_FP8_E4M3}
+    params["quantization"] = {"qformat_weight": qformat}
     with open(dst / "params.json", "w") as f:
         json.dump(params, f)
     return dst

@@ -14,7 +14,7 @@ from .args import LoraArgs, MoeArgs, QuantizationArgs
 from .cache import CacheView
 from .lora import LoRALinear, maybe_lora
 from .moe import MoeLayer
-from .quant import FP8_LORA_REFUSAL, FP8_MOE_REFUSAL, Fp8Linear, linear_fp8
+from .quant import Fp8Linear, Mxfp4Linear, linear_fp8, linear_mxfp4, lora_refusal, moe_refusal, quantized_linear_cls
 
 LORA_MOE_REFUSAL = ("un-merged LoRA on a MoE model (adapters inside the experts) is not implemented; merge the adapter into the "
                     "checkpoint first (what the reference's default CLI path does, lora.py:118-139)")
@@ -28,11 +28,12 @@ def _no_lora(lora: Optional[LoraArgs], moe: Optional[MoeArgs]) -> None:
 
 
 def _linear_cls(lora: Optional[LoraArgs], quantization: Optional[QuantizationArgs]):
-    """nn.Linear, LoRALinear (un-merged adapters) or Fp8Linear (weight-only FP8); the two do not combine."""
+    """nn.Linear, LoRALinear (un-merged adapters), or Fp8Linear / Mxfp4Linear (weight-only FP8 / MXFP4, by format); adapters and
+    quantisation do not combine."""
     if quantization is not None:
         if lora is not None:
-            raise NotImplementedError(FP8_LORA_REFUSAL)
-        return Fp8Linear
+            raise NotImplementedError(lora_refusal(quantization))
+        return quantized_linear_cls(quantization)
     return maybe_lora(lora)
 
 
@@ -72,6 +73,8 @@ class FeedForward(nn.Module):
             return self.w2(hid)
         if isinstance(self.w1, Fp8Linear):  # the same two launches on e4m3 weights (csrc/gemv_w8.hip)
             return self.w2(linear_fp8(x, (self.w1, self.w3), _hip.EPI_SWIGLU))
+        if isinstance(self.w1, Mxfp4Linear):  # ... on MXFP4 weights (csrc/gemv_w4.hip)
+            return self.w2(linear_mxfp4(x, (self.w1, self.w3), _hip.EPI_SWIGLU))
         hid = _hip.linear(x, (self.w1.weight, self.w3.weight), _hip.EPI_SWIGLU)
         return _hip.linear(hid, (self.w2.weight,), _hip.EPI_STORE)
 
@@ -103,7 +106,14 @@ class Attention(nn.Module):
         rows = torch.arange(T, dtype=torch.int32, device=x.device)
         lora = isinstance(self.wq, LoRALinear)
         fp8 = isinstance(self.wq, Fp8Linear)
-        if fp8 and T <= _hip.GEMV_MAX_T:  # the plain model's launches on e4m3 weights (csrc/gemv_w8.hip)
+        fp4 = isinstance(self.wq, Mxfp4Linear)
+        if fp4 and T <= _hip.GEMV_MAX_T:  # the plain model's launches on MXFP4 weights (csrc/gemv_w4.hip)
+            qkv = _hip.qkv_rope_kvwrite_w4(x, self.wq.weight, self.wk.weight, self.wv.weight, self.wq.qscale_weight,
+                                           self.wk.qscale_weight, self.wv.qscale_weight, Dh, cs, rows)
+        elif fp4:
+            qkv = linear_mxfp4(x, (self.wq, self.wk, self.wv), _hip.EPI_STORE)
+            _hip.rope_inplace(qkv, H, Hkv, Dh, cs, rows)
+        elif fp8 and T <= _hip.GEMV_MAX_T:  # the plain model's launches on e4m3 weights (csrc/gemv_w8.hip)
             qkv = _hip.qkv_rope_kvwrite_w8(x, self.wq.weight, self.wk.weight, self.wv.weight, self.wq.qscale_weight,
                                            self.wk.qscale_weight, self.wv.qscale_weight, Dh, cs, rows)
         elif fp8:
@@ -131,7 +141,7 @@ class Attention(nn.Module):
             else:
                 cache.update(qkv[:, nq:nq + nkv], qkv[:, nq + nkv:])
                 out = _hip.attn_decode(qkv, cache.cache_k, cache.cache_v, H, b.tok_pos)
-        if lora or fp8:
+        if lora or fp8 or fp4:
             return self.wo(out)
         return _hip.linear(out, (self.wo.weight,), _hip.EPI_STORE)
 
@@ -145,7 +155,7 @@ class TransformerBlock(nn.Module):
         super().__init__()
         _no_lora(lora, moe)
         if quantization is not None and moe is not None:
-            raise NotImplementedError(FP8_MOE_REFUSAL)
+            raise NotImplementedError(moe_refusal(quantization))
         self.n_heads = n_heads
         self.dim = dim
         self.attention = Attention(dim=dim, n_heads=n_heads, head_dim=head_dim, n_kv_heads=n_kv_heads, lora=lora,
