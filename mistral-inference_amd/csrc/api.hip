@@ -95,8 +95,7 @@ template <class Try>
 bool engine_route(int variant, bool nemo_opt_in, const EngineBuild* slot, const EngProblem& pr, Try&& try_build) {
   const bool moe = pr.E > 0;
   if (pr.lora_rank > 0) return false;  // un-merged LoRA adapters: no engine build carries them, the launch path does (lora.hip)
-  if (pr.w8) return false;             // e4m3 weight bytes: no engine build reads them, the launch path does (gemv_w8.hip)
-  if (pr.w4) return false;             // MXFP4 weights: likewise (gemv_w4.hip)
+  if (pr.quant) return false;          // quantised weight bytes: no engine build reads them, the launch path does (gemv_w8.hip, gemv_w4.hip)
   auto takes = [&](int b) { return kBuilds[b]->applicable(pr, nullptr, 0); };
   if (slot && slot->applicable(pr, nullptr, 0) && try_build(*slot)) return true;
   // the dense GQA-4 headline shapes: the `next` compile (build_native.ENGINE_NEXT_FLAGS)
@@ -155,19 +154,19 @@ struct Workspace {
   int max_tiles;
   bf16_t* lora_t;    // un-merged LoRA (lora_rank > 0 only, behind everything else): t = bf16(A x)   [T, 3 * rank]
   void* lora_base;   // ... and the base products of q|k|v and w1|w3  [T, max(qkv cols, 2 F)]: fp32 holding bf16 values for T <= 8
-  bf16_t* w8;        // weight-only FP8 at T > 8 (behind everything else, such models only): the dequantised weights of one linear
-  size_t total;      //     group (w8_scratch_elems).  (lora_base: the GEMV's LOGITS form, see lora_linear; bf16 above 8 rows.  Wo's
+  bf16_t* deq;       // quantised models at T > 8 (behind everything else, such models only): the dequantised weights of one linear
+  size_t total;      //     group (deq_scratch_elems).  (lora_base: the GEMV's LOGITS form, see lora_linear; bf16 above 8 rows.  Wo's
 };                   //     and W2's base product goes to xn.)
 
 // bf16 elements of the largest linear group a prefill dequantises at once: q|k|v, wo, w1|w3, w2
-size_t w8_scratch_elems(const mi_model_t* m) {
+size_t deq_scratch_elems(const mi_model_t* m) {
   const size_t D = m->dim, F = m->hidden_dim, nq = (size_t)m->n_heads * m->head_dim, nkv = (size_t)m->n_kv_heads * m->head_dim;
   const size_t a = (nq + 2 * nkv) * D, b = 2 * F * D;
   return a > b ? a : b;  // (wo: D * nq <= a; w2: D * F <= b)
 }
 
-// w8: the linears are quantised (e4m3 or MXFP4: the same scratch of one dequantised linear group)
-Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool w8 = false) {
+// quant: the linears are quantised (any format: the same scratch of one dequantised linear group)
+Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool quant = false) {
   Workspace w;
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -203,7 +202,7 @@ Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool w8
     w.lora_t = (bf16_t*)take((size_t)T * 3 * m->lora_rank * 2);
     w.lora_base = take((size_t)T * wide * (T <= GEMV_MAX_T ? 4 : 2));
   }
-  w.w8 = (w8 && T > GEMV_MAX_T) ? (bf16_t*)take(w8_scratch_elems(m) * 2) : nullptr;  // (a plain model: layout and total as ever)
+  w.deq = (quant && T > GEMV_MAX_T) ? (bf16_t*)take(deq_scratch_elems(m) * 2) : nullptr;  // (a plain model: layout and total as ever)
   w.total = off;
   return w;
 }
@@ -280,21 +279,45 @@ int gemv_pass_loop(int cap, const GemvArgs& a, int T, const char* what, Launch&&
 int gemv_passes(const GemvKernels& k, const GemvArgs& a, int T, hipStream_t s, const char* what) {
   return gemv_pass_loop(k.max_tokens(a.K), a, T, what, [&](const GemvArgs& p) { return k.launch(p, s); });
 }
-// The third table: gemv_w8.hip, the same launches with the weight pointers read as e4m3 bytes and the row scales beside the
-// arguments (activation rows are bf16 there too: the bf16 kernels' row budget).
-struct W8Scales {
-  const float* s[3];
+// The weight-only formats: the same launches with the weight pointers read as quantised bytes and the scales beside the arguments
+// (activation rows are bf16 there too: the bf16 kernels' row budget).  A format is one trait: its scale element, K modulus, names
+// and the two launchers of its file.
+template <class scale_t>
+struct Scales {
+  const scale_t* s[3];
 };
-int gemv_passes_w8(const GemvArgs& a, const W8Scales& sc, int T, hipStream_t s, const char* what) {
+struct QuantW8 {  // gemv_w8.hip: e4m3 bytes, one fp32 scale per row
+  typedef float scale_t;
+  static constexpr int kFormat = MI_W8_FP8_E4M3, kMod = 16;
+  static constexpr const char *kFormatName = "MI_W8_FP8_E4M3 = 1", *kArg = "w8", *kName = "FP8", *kScales = "row scales";
+  static constexpr const char* kWhy = "a 16-byte piece is 16 e4m3 weights";
+  static constexpr const char *kLinear = "mi_linear_w8", *kQkv = "mi_qkv_rope_kvwrite_w8", *kGemv = "gemv (w8)", *kDequant = "dequant (w8)",
+                              *kQkvGemv = "qkv gemv (w8)";
+  static constexpr auto launch_gemv = launch_gemv_w8;
+  static constexpr auto launch_dequant = launch_dequant_w8;
+};
+struct QuantW4 {  // gemv_w4.hip: MXFP4 code bytes, one e8m0 scale byte per block of 32
+  typedef uint8_t scale_t;
+  static constexpr int kFormat = MI_W4_MXFP4, kMod = 32;
+  static constexpr const char *kFormatName = "MI_W4_MXFP4 = 2", *kArg = "w4", *kName = "MXFP4", *kScales = "block scales";
+  static constexpr const char* kWhy = "one e8m0 scale per block of 32 MXFP4 weights";
+  static constexpr const char *kLinear = "mi_linear_w4", *kQkv = "mi_qkv_rope_kvwrite_w4", *kGemv = "gemv (w4)", *kDequant = "dequant (w4)",
+                              *kQkvGemv = "qkv gemv (w4)";
+  static constexpr auto launch_gemv = launch_gemv_w4;
+  static constexpr auto launch_dequant = launch_dequant_w4;
+};
+template <class Q>
+int gemv_passes_quant(const GemvArgs& a, const Scales<typename Q::scale_t>& sc, int T, hipStream_t s, const char* what) {
   return gemv_pass_loop(gemv_max_tokens(a.K), a, T, what, [&](const GemvArgs& p) {
-    const GemvW8Args w = {p, {sc.s[0], sc.s[1], sc.s[2]}};
-    return launch_gemv_w8(w, s);
+    const GemvScaledArgs<typename Q::scale_t> w = {p, {sc.s[0], sc.s[1], sc.s[2]}};
+    return Q::launch_gemv(w, s);
   });
 }
-// Dequantise up to three e4m3 matrices of K columns side by side into `out` (dense [sum of rows, K] bf16); w[i] then points at
-// the bf16 rows of matrix i.
-int dequant_group(const void* w[3], const W8Scales& sc, const int n_rows[3], int K, bf16_t* out, hipStream_t s, const char* what) {
-  DequantW8Args d;
+// Dequantise up to three matrices of K columns side by side into `out` (dense [sum of rows, K] bf16); w[i] then points at the
+// bf16 rows of matrix i.
+template <class Q>
+int dequant_group(const void* w[3], const Scales<typename Q::scale_t>& sc, const int n_rows[3], int K, bf16_t* out, hipStream_t s, const char* what) {
+  DequantArgs<typename Q::scale_t> d;
   memset(&d, 0, sizeof(d));
   int n = 0;
   for (int i = 0; i < 3; ++i) {
@@ -307,41 +330,25 @@ int dequant_group(const void* w[3], const W8Scales& sc, const int n_rows[3], int
   }
   if (!d.w[1]) d.n1 = d.n0;
   d.N = n; d.K = K; d.out = out;
-  return hip_rc(launch_dequant_w8(d, s), what);
+  return hip_rc(Q::launch_dequant(d, s), what);
 }
-// The fourth table: gemv_w4.hip, MXFP4 code bytes behind the weight pointers and the e8m0 block-scale rows beside the arguments.
-struct W4Scales {
-  const uint8_t* s[3];
-};
 // the (up to three) linears of a layer that a launch of forward_body reads, in the field order of mi_w8_layer_t / mi_w4_layer_t; -1: none
 enum { LIN_WQ = 0, LIN_WK, LIN_WV, LIN_WO, LIN_W1, LIN_W2, LIN_W3 };
 struct Lins {
   int i[3];
 };
-int gemv_passes_w4(const GemvArgs& a, const W4Scales& sc, int T, hipStream_t s, const char* what) {
-  return gemv_pass_loop(gemv_max_tokens(a.K), a, T, what, [&](const GemvArgs& p) {
-    const GemvW4Args w = {p, {sc.s[0], sc.s[1], sc.s[2]}};
-    return launch_gemv_w4(w, s);
-  });
-}
-// Dequantise up to three MXFP4 matrices of K columns side by side into `out` (dense [sum of rows, K] bf16); w[i] then points at
-// the bf16 rows of matrix i.
-int dequant_group_w4(const void* w[3], const W4Scales& sc, const int n_rows[3], int K, bf16_t* out, hipStream_t s, const char* what) {
-  DequantW4Args d;
-  memset(&d, 0, sizeof(d));
-  int n = 0;
-  for (int i = 0; i < 3; ++i) {
-    const int rows = w[i] ? n_rows[i] : 0;
-    d.w[i] = (const uint8_t*)w[i]; d.scale[i] = sc.s[i];
-    if (i == 0) d.n0 = rows;
-    if (i == 1) d.n1 = d.n0 + rows;
-    w[i] = w[i] ? (const void*)(out + (size_t)n * K) : nullptr;
-    n += rows;
-  }
-  if (!d.w[1]) d.n1 = d.n0;
-  d.N = n; d.K = K; d.out = out;
-  return hip_rc(launch_dequant_w4(d, s), what);
-}
+// The quantisation that forward_body runs a model under: what mi_forward_w8 / mi_forward_w4 were handed, as one argument.
+struct QuantModel {
+  int entry_format;  // the format of the entry point that was called: MI_W8_FP8_E4M3 / MI_W4_MXFP4
+  int format;        // the format the caller's struct names (check_quant: must be the entry's)
+  const mi_w8_layer_t* l8;  // host [n_layers]; the table of entry_format, the other one nullptr
+  const mi_w4_layer_t* l4;
+};
+// f(trait of the format)
+template <class Fn>
+int with_format(int format, Fn&& f) { return format == MI_W4_MXFP4 ? f(QuantW4{}) : f(QuantW8{}); }
+inline const mi_w8_layer_t* layers_of(const QuantModel& q, QuantW8) { return q.l8; }
+inline const mi_w4_layer_t* layers_of(const QuantModel& q, QuantW4) { return q.l4; }
 
 // out[M, N] = epi(a[M, K] @ w0^T (, a @ w1^T)): the plain GEMM of one weight matrix, or of W1 and W3 for GEMM_SWIGLU
 GemmArgs gemm_args(int epi, const bf16_t* a, int M, int K, const void* w0, const void* w1, int N, void* out, const bf16_t* residual) {
@@ -875,32 +882,6 @@ size_t mi_linear_w8_scratch_bytes(int M, int K, const int n_rows[3], int epilogu
 
 }  // extern "C"
 
-// What differs between the two weight-only forms at the leaves: the scale element, the K modulus and its reason, the launches.
-struct QuantW8 {
-  typedef float scale_t;
-  typedef W8Scales Scales;
-  static constexpr int kMod = 16;
-  static constexpr const char* kWhy = "a 16-byte piece is 16 e4m3 weights";
-  static constexpr const char *kLinear = "mi_linear_w8", *kQkv = "mi_qkv_rope_kvwrite_w8", *kGemv = "gemv (w8)", *kDequant = "dequant (w8)",
-                              *kQkvGemv = "qkv gemv (w8)";
-  static int passes(const GemvArgs& a, const Scales& sc, int T, hipStream_t s, const char* what) { return gemv_passes_w8(a, sc, T, s, what); }
-  static int dequant(const void* w[3], const Scales& sc, const int nr[3], int K, bf16_t* out, hipStream_t s, const char* what) {
-    return dequant_group(w, sc, nr, K, out, s, what);
-  }
-};
-struct QuantW4 {
-  typedef uint8_t scale_t;
-  typedef W4Scales Scales;
-  static constexpr int kMod = 32;
-  static constexpr const char* kWhy = "one e8m0 scale per block of 32 MXFP4 weights";
-  static constexpr const char *kLinear = "mi_linear_w4", *kQkv = "mi_qkv_rope_kvwrite_w4", *kGemv = "gemv (w4)", *kDequant = "dequant (w4)",
-                              *kQkvGemv = "qkv gemv (w4)";
-  static int passes(const GemvArgs& a, const Scales& sc, int T, hipStream_t s, const char* what) { return gemv_passes_w4(a, sc, T, s, what); }
-  static int dequant(const void* w[3], const Scales& sc, const int nr[3], int K, bf16_t* out, hipStream_t s, const char* what) {
-    return dequant_group_w4(w, sc, nr, K, out, s, what);
-  }
-};
-
 // mi_linear_w8 / mi_linear_w4
 template <class Q>
 static int linear_quant(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3], int epilogue,
@@ -918,7 +899,7 @@ static int linear_quant(void* out, int ldo, const void* x, int ldx, int M, int K
   hipStream_t s = (hipStream_t)stream;
   const bool swiglu = epilogue == MI_EPI_SWIGLU;
   const int n0 = n_rows[0], n1 = n0 + (w[1] ? n_rows[1] : 0), n2 = n1 + ((!swiglu && w[2]) ? n_rows[2] : 0);
-  const typename Q::Scales sc = {{scale[0], w[1] ? scale[1] : nullptr, (!swiglu && w[2]) ? scale[2] : nullptr}};
+  const Scales<typename Q::scale_t> sc = {{scale[0], w[1] ? scale[1] : nullptr, (!swiglu && w[2]) ? scale[2] : nullptr}};
   if (M <= GEMV_MAX_T) {
     GemvArgs a = gemv_common(x, ldx, K, 0, norm_w, eps, out, ldo);
     a.w0 = (const bf16_t*)w[0]; a.w1 = (const bf16_t*)w[1]; a.w2 = swiglu ? nullptr : (const bf16_t*)w[2]; a.residual = (const bf16_t*)residual;
@@ -928,14 +909,14 @@ static int linear_quant(void* out, int ldo, const void* x, int ldx, int M, int K
     } else {
       a.N = n2; a.n0 = n0; a.n1 = n1;
     }
-    return Q::passes(a, sc, M, s, Q::kGemv);
+    return gemv_passes_quant<Q>(a, sc, M, s, Q::kGemv);
   }
   if (norm_w) return fail(MI_ERR_UNSUPPORTED, "%s: fused RMSNorm only on the M <= 8 path", me);
   const size_t need = align_up((size_t)(swiglu ? 2 * n0 : n2) * K * 2);
   if (!scratch || scratch_bytes < need) return fail(MI_ERR_WORKSPACE, "%s: scratch %zu < required %zu", me, scratch ? scratch_bytes : (size_t)0, need);
   const void* wd[3] = {w[0], w[1], swiglu ? nullptr : w[2]};
   const int nr[3] = {n0, n1 - n0, n2 - n1};
-  MI_TRY(Q::dequant(wd, sc, nr, K, (bf16_t*)scratch, s, Q::kDequant));
+  MI_TRY(dequant_group<Q>(wd, sc, nr, K, (bf16_t*)scratch, s, Q::kDequant));
   return mi_linear(out, ldo, x, ldx, M, K, wd, n_rows, epilogue, residual, nullptr, 0.f, stream);
 }
 
@@ -959,7 +940,7 @@ static int qkv_rope_kvwrite_quant(void* qkv, int ldo, const void* x, int ldx, in
   const RingWrite ring = {cache_k, cache_v, W, kv_layout};
   const GemvArgs a = gemv_qkv_rope(x, ldx, D, norm_w, eps, wq, wk, wv, n_heads * head_dim, n_kv_heads * head_dim, qkv, ldo, rope_cs,
                                    tok_pos, tok_seq, head_dim, cache_k ? &ring : nullptr);
-  return Q::passes(a, typename Q::Scales{{sq, sk, sv}}, T, (hipStream_t)stream, Q::kQkvGemv);
+  return gemv_passes_quant<Q>(a, Scales<typename Q::scale_t>{{sq, sk, sv}}, T, (hipStream_t)stream, Q::kQkvGemv);
 }
 
 extern "C" {
@@ -1130,49 +1111,42 @@ size_t mi_workspace_bytes(const mi_model_t* model, int T, int B, int max_cache_s
   return carve(model, T, B, max_cache_size > 0 ? max_cache_size : 1, nullptr).total;
 }
 
-size_t mi_workspace_bytes_w8(const mi_model_t* model, const mi_w8_model_t* w8, int T, int B, int max_cache_size) {
+static size_t workspace_bytes_quant(const mi_model_t* model, bool quant, int T, int B, int max_cache_size) {
   if (!model || T <= 0 || B <= 0) return 0;
-  return carve(model, T, B, max_cache_size > 0 ? max_cache_size : 1, nullptr, w8 != nullptr).total;
+  return carve(model, T, B, max_cache_size > 0 ? max_cache_size : 1, nullptr, quant).total;
+}
+size_t mi_workspace_bytes_w8(const mi_model_t* model, const mi_w8_model_t* w8, int T, int B, int max_cache_size) {
+  return workspace_bytes_quant(model, w8 != nullptr, T, B, max_cache_size);
+}
+size_t mi_workspace_bytes_w4(const mi_model_t* model, const mi_w4_model_t* w4, int T, int B, int max_cache_size) {
+  return workspace_bytes_quant(model, w4 != nullptr, T, B, max_cache_size);
 }
 
 // what a quantised model must be, by name, before any launch
-static int check_w8(const char* entry, const mi_model_t* m, const mi_w8_model_t* w8) {
-  if (w8->format != MI_W8_FP8_E4M3) return fail(MI_ERR_UNSUPPORTED, "%s: weight format %d (MI_W8_FP8_E4M3 = 1 is the only one)", entry, w8->format);
-  if (!w8->layers) return fail(MI_ERR_ARG, "%s: w8 without layer scales", entry);
-  if (m->num_experts > 0) return fail(MI_ERR_UNSUPPORTED, "%s: FP8 weights on a MoE model are not implemented (the experts stay bf16)", entry);
-  if (m->lora_rank > 0) return fail(MI_ERR_UNSUPPORTED, "%s: un-merged LoRA on an FP8 base is not implemented; merge the adapter before quantising", entry);
-  if (m->dim % 16 || m->hidden_dim % 16 || (m->n_heads * m->head_dim) % 16)
-    return fail(MI_ERR_SHAPE, "%s: dim, hidden_dim and n_heads * head_dim must be multiples of 16 (a 16-byte piece is 16 e4m3 weights)", entry);
-  return MI_OK;
+static int check_quant(const char* entry, const mi_model_t* m, const QuantModel& q) {
+  return with_format(q.entry_format, [&](auto Q) {
+    typedef decltype(Q) F;
+    if (q.format != F::kFormat) return fail(MI_ERR_UNSUPPORTED, "%s: weight format %d (%s is the only one)", entry, q.format, F::kFormatName);
+    if (!layers_of(q, Q)) return fail(MI_ERR_ARG, "%s: %s without layer scales", entry, F::kArg);
+    if (m->num_experts > 0) return fail(MI_ERR_UNSUPPORTED, "%s: %s weights on a MoE model are not implemented (the experts stay bf16)", entry, F::kName);
+    if (m->lora_rank > 0)
+      return fail(MI_ERR_UNSUPPORTED, "%s: un-merged LoRA on an %s base is not implemented; merge the adapter before quantising", entry, F::kName);
+    if (m->dim % F::kMod || m->hidden_dim % F::kMod || (m->n_heads * m->head_dim) % F::kMod)
+      return fail(MI_ERR_SHAPE, "%s: dim, hidden_dim and n_heads * head_dim must be multiples of %d (%s)", entry, F::kMod, F::kWhy);
+    return (int)MI_OK;
+  });
 }
 
-size_t mi_workspace_bytes_w4(const mi_model_t* model, const mi_w4_model_t* w4, int T, int B, int max_cache_size) {
-  if (!model || T <= 0 || B <= 0) return 0;
-  return carve(model, T, B, max_cache_size > 0 ? max_cache_size : 1, nullptr, w4 != nullptr).total;
-}
-
-static int check_w4(const char* entry, const mi_model_t* m, const mi_w4_model_t* w4) {
-  if (w4->format != MI_W4_MXFP4) return fail(MI_ERR_UNSUPPORTED, "%s: weight format %d (MI_W4_MXFP4 = 2 is the only one)", entry, w4->format);
-  if (!w4->layers) return fail(MI_ERR_ARG, "%s: w4 without layer scales", entry);
-  if (m->num_experts > 0) return fail(MI_ERR_UNSUPPORTED, "%s: MXFP4 weights on a MoE model are not implemented (the experts stay bf16)", entry);
-  if (m->lora_rank > 0) return fail(MI_ERR_UNSUPPORTED, "%s: un-merged LoRA on an MXFP4 base is not implemented; merge the adapter before quantising", entry);
-  if (m->dim % 32 || m->hidden_dim % 32 || (m->n_heads * m->head_dim) % 32)
-    return fail(MI_ERR_SHAPE, "%s: dim, hidden_dim and n_heads * head_dim must be multiples of 32 (one e8m0 scale per block of 32 MXFP4 weights)", entry);
-  return MI_OK;
-}
-
-// mi_forward, mi_forward_w8 and mi_forward_w4 (at most one of w8 / w4).  Neither: exactly the launches of mi_forward as they always were.
-static int forward_body(const char* entry, const mi_model_t* m, const mi_w8_model_t* w8, const mi_w4_model_t* w4, const mi_batch_t* bt,
-                        mi_stream_t stream) {
+// mi_forward, mi_forward_w8 and mi_forward_w4.  q == nullptr: exactly the launches of mi_forward as they always were.
+static int forward_body(const char* entry, const mi_model_t* m, const QuantModel* q, const mi_batch_t* bt, mi_stream_t stream) {
   MI_TRY(check_model(m));
-  if (w8) MI_TRY(check_w8(entry, m, w8));
-  if (w4) MI_TRY(check_w4(entry, m, w4));
+  if (q) MI_TRY(check_quant(entry, m, *q));
   BatchInfo bi;
   MI_TRY(check_batch(entry, m, bt, true, &bi));
   int maxW = 1;
   if (bi.has_cache)
     for (int l = 0; l < m->n_layers; ++l) maxW = bt->cache_sizes[l] > maxW ? bt->cache_sizes[l] : maxW;
-  const Workspace ws = carve(m, bi.T, bi.B, maxW, (char*)bt->workspace, w8 != nullptr || w4 != nullptr);
+  const Workspace ws = carve(m, bi.T, bi.B, maxW, (char*)bt->workspace, q != nullptr);
   MI_TRY(check_workspace_and_sample(entry, bt, ws.total, &bi));
   const int T = bi.T, B = bi.B, branch = bi.branch, kvl = bi.kv_layout;
   const bool has_cache = bi.has_cache, want_greedy = bi.want_sample, want_topp = bi.want_topp;
@@ -1205,7 +1179,7 @@ static int forward_body(const char* entry, const mi_model_t* m, const mi_w8_mode
       pr.hist_tok = bt->hist_token; pr.hist_lp = bt->hist_logprob; pr.hist_len = bt->hist_len;
     }
     pr.granules = ws.gran; pr.granule_bytes = ws.gran_bytes; pr.ctrl = engine_ctrl;
-    pr.E = m->num_experts; pr.top_k = m->top_k; pr.lora_rank = m->lora_rank; pr.w8 = w8 != nullptr; pr.w4 = w4 != nullptr;
+    pr.E = m->num_experts; pr.top_k = m->top_k; pr.lora_rank = m->lora_rank; pr.quant = q != nullptr;
     pr.forced = engine_variant() == 1;
     bool dense_ok = true;
     for (int l = 0; l < m->n_layers; ++l)
@@ -1251,35 +1225,34 @@ static int forward_body(const char* entry, const mi_model_t* m, const mi_w8_mode
 
     // ---- un-merged LoRA (ABI v8): every linear is [base product] [lora_down] [lora_up] (lora_linear above); RoPE and the ring
     // write are the separate passes (bit-equal to the fused epilogues: same arithmetic on the same bf16 values)
-    // ---- weight-only FP8: `run` sends a GEMV to the e4m3 kernels with the linear's row scales; `deq` (T > 8) writes the bf16
-    // image of a linear group into the scratch and points w[] at it for the GEMM that follows.  Without w8 both pass through.
-    static const mi_w8_layer_t kNoScales = {};
-    const mi_w8_layer_t& Q = w8 ? w8->layers[l] : kNoScales;
-    // MXFP4 (w4): the same two hooks on the e8m0 block-scale rows.  A call names its (up to three) linears; the scales of either
-    // form are looked up here.
-    static const mi_w4_layer_t kNoBlockScales = {};
-    const mi_w4_layer_t& Q4 = w4 ? w4->layers[l] : kNoBlockScales;
-    const float* const q8[7] = {Q.wq, Q.wk, Q.wv, Q.wo, Q.w1, Q.w2, Q.w3};
-    const uint8_t* const q4[7] = {Q4.wq, Q4.wk, Q4.wv, Q4.wo, Q4.w1, Q4.w2, Q4.w3};
-    auto sc8 = [&](const Lins& n) { return W8Scales{{n.i[0] < 0 ? nullptr : q8[n.i[0]], n.i[1] < 0 ? nullptr : q8[n.i[1]], n.i[2] < 0 ? nullptr : q8[n.i[2]]}}; };
-    auto sc4 = [&](const Lins& n) { return W4Scales{{n.i[0] < 0 ? nullptr : q4[n.i[0]], n.i[1] < 0 ? nullptr : q4[n.i[1]], n.i[2] < 0 ? nullptr : q4[n.i[2]]}}; };
+    // ---- weight-only formats: `run` sends a GEMV to the format's kernels with the scales of the (up to three) linears it names;
+    // `deq` (T > 8) writes the bf16 image of a linear group into the scratch and points w[] at it for the GEMM that follows.
+    // Without q both pass through.  qs: the layer's seven scale pointers, read through the format's own layer struct.
+    const void* qs[7] = {};
+    if (q) {
+      MI_TRY(with_format(q->entry_format, [&](auto Q) {
+        const auto& S = layers_of(*q, Q)[l];
+        if (!(S.wq && S.wk && S.wv && S.wo && S.w1 && S.w2 && S.w3))
+          return fail(MI_ERR_ARG, "%s: layer %d has a linear without %s", entry, l, decltype(Q)::kScales);
+        const void* const all[7] = {S.wq, S.wk, S.wv, S.wo, S.w1, S.w2, S.w3};
+        memcpy(qs, all, sizeof(qs));
+        return (int)MI_OK;
+      }));
+    }
+    auto scales = [&](auto Q, const Lins& n) {
+      typedef const typename decltype(Q)::scale_t* ptr;  // (what qs[] held before it became void*)
+      return Scales<typename decltype(Q)::scale_t>{{n.i[0] < 0 ? nullptr : static_cast<ptr>(qs[n.i[0]]), n.i[1] < 0 ? nullptr : static_cast<ptr>(qs[n.i[1]]),
+                                                    n.i[2] < 0 ? nullptr : static_cast<ptr>(qs[n.i[2]])}};
+    };
     auto run = [&](const GemvArgs& ga, const Lins& n, const char* what) {
-      if (w4) return gemv_passes_w4(ga, sc4(n), T, s, what);
-      return w8 ? gemv_passes_w8(ga, sc8(n), T, s, what) : gemv_passes(kGemvBf16, ga, T, s, what);
+      if (!q) return gemv_passes(kGemvBf16, ga, T, s, what);
+      return with_format(q->entry_format, [&](auto Q) { return gemv_passes_quant<decltype(Q)>(ga, scales(Q, n), T, s, what); });
     };
     auto deq = [&](const void* (&w)[3], const Lins& n, int r0, int r1, int r2, int K, const char* what) {
-      if (w4) {
-        const int nr[3] = {r0, r1, r2};
-        return dequant_group_w4(w, sc4(n), nr, K, ws.w8, s, what);
-      }
-      const W8Scales sc = sc8(n);
-      if (!w8) return (int)MI_OK;
-      if (!sc.s[0] || (w[1] && !sc.s[1]) || (w[2] && !sc.s[2])) return fail(MI_ERR_ARG, "%s: layer %d has a linear without row scales", entry, l);
+      if (!q) return (int)MI_OK;
       const int nr[3] = {r0, r1, r2};
-      return dequant_group(w, sc, nr, K, ws.w8, s, what);
+      return with_format(q->entry_format, [&](auto Q) { return dequant_group<decltype(Q)>(w, scales(Q, n), nr, K, ws.deq, s, what); });
     };
-    if (w8 && !(Q.wq && Q.wk && Q.wv && Q.wo && Q.w1 && Q.w2 && Q.w3)) return fail(MI_ERR_ARG, "%s: layer %d has a linear without row scales", entry, l);
-    if (w4 && !(Q4.wq && Q4.wk && Q4.wv && Q4.wo && Q4.w1 && Q4.w2 && Q4.w3)) return fail(MI_ERR_ARG, "%s: layer %d has a linear without block scales", entry, l);
     static const mi_lora_layer_t kNoAdapters = {};
     const mi_lora_layer_t& A = (lora && L.lora) ? *L.lora : kNoAdapters;
     const float ls = m->lora_scaling;
@@ -1397,14 +1370,18 @@ static int forward_body(const char* entry, const mi_model_t* m, const mi_w8_mode
   return MI_OK;
 }
 
-int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) { return forward_body("mi_forward", m, nullptr, nullptr, bt, stream); }
+int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) { return forward_body("mi_forward", m, nullptr, bt, stream); }
 
 int mi_forward_w8(const mi_model_t* m, const mi_w8_model_t* w8, const mi_batch_t* bt, mi_stream_t stream) {
-  return forward_body(w8 ? "mi_forward_w8" : "mi_forward", m, w8, nullptr, bt, stream);
+  if (!w8) return forward_body("mi_forward", m, nullptr, bt, stream);
+  const QuantModel q = {MI_W8_FP8_E4M3, w8->format, w8->layers, nullptr};
+  return forward_body("mi_forward_w8", m, &q, bt, stream);
 }
 
 int mi_forward_w4(const mi_model_t* m, const mi_w4_model_t* w4, const mi_batch_t* bt, mi_stream_t stream) {
-  return forward_body(w4 ? "mi_forward_w4" : "mi_forward", m, nullptr, w4, bt, stream);
+  if (!w4) return forward_body("mi_forward", m, nullptr, bt, stream);
+  const QuantModel q = {MI_W4_MXFP4, w4->format, nullptr, w4->layers};
+  return forward_body("mi_forward_w4", m, &q, bt, stream);
 }
 
 }  // extern "C"

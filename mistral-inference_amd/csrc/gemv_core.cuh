@@ -687,7 +687,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, const typename F::s
   }
 }
 
-// ---- the launch plan (host), shared by launch_gemv, launch_gemv_w8 and launch_gemv_w4
+// ---- the launch plan (host), shared by launch_gemv and launch_gemv_scaled (gemv_w8.hip, gemv_w4.hip)
 
 // 5 and 7 rows run on the 6- and 8-row instantiations, which stage 6 / 8 rows in LDS
 inline int round_tt(int T) { return T == 5 ? 6 : (T == 7 ? 8 : T); }
@@ -759,6 +759,51 @@ hipError_t for_tt(int TT, Fn&& f) {
     case 4: return f(std::integral_constant<int, 4>{});
     case 6: return f(std::integral_constant<int, 6>{});
     default: return f(std::integral_constant<int, 8>{});
+  }
+}
+
+// ---- the launch of a GEMV on scaled weight rows (host), once for every weight format.  F names what a format's file owns:
+//   F::kernel<TT, MODE, RP, DMA>   its __global__ kernel (gemv_body on its WFormat, under its own launch bounds)
+//   F::row_pairs(npairs, cus)      its rule for the row pairs per unit at one token
+//   F::kRpEnv                      the environment variable that overrides the rule (A/B): 1 / 2; 0 or unset: the rule
+template <class F, int MODE, class Args>
+hipError_t launch_mode(const Args& a, int TT, int rp, dim3 grid, size_t lds, hipStream_t s) {
+  return for_tt(TT, [&](auto tt) {
+    constexpr int T = decltype(tt)::value;
+    if constexpr (T == 1) {
+      return rp == 2 ? launch_lds<F::template kernel<1, MODE, 2, false>>(a, grid, lds, s) : launch_lds<F::template kernel<1, MODE, 1, false>>(a, grid, lds, s);
+    } else {
+      return stage_by_dma(MODE, T, a.g.K) ? launch_lds<F::template kernel<T, MODE, 1, true>>(a, grid, lds, s)
+                                          : launch_lds<F::template kernel<T, MODE, 1, false>>(a, grid, lds, s);
+    }
+  });
+}
+
+// One launch; a.g.T must be <= gemv_max_tokens(K) (the activation rows are bf16 as in gemv.hip: the same LDS budget).
+template <class F, class Args>
+hipError_t launch_gemv_scaled(const Args& a, hipStream_t s) {
+  const GemvArgs& g = a.g;
+  static int rp_env = -1;  // (one per format: a static of this instantiation)
+  const int cus = device_cus();
+  if (rp_env < 0) {
+    const char* e = getenv(F::kRpEnv);
+    rp_env = e ? atoi(e) : 0;
+  }
+  const int npairs = g.mode == GEMV_SWIGLU ? g.N : (g.N + 1) / 2;
+  int rp = g.T == 1 ? F::row_pairs(npairs, cus) : 1;
+  if (g.T == 1 && (rp_env == 1 || rp_env == 2)) rp = rp_env;
+  const int units = (npairs + rp - 1) / rp;
+  int blocks = even_blocks(units, cus);
+  if (!blocks) blocks = spread_blocks(units, max_blocks(cus));
+  const int TT = round_tt(g.T);
+  const size_t lds = lds_bytes(TT, g.K, g.norm_w != nullptr);
+  const dim3 grid(blocks_for_lds(blocks, units, cus, lds));
+  switch (g.mode) {
+    case GEMV_STORE: return launch_mode<F, GEMV_STORE>(a, TT, rp, grid, lds, s);
+    case GEMV_RESIDUAL: return launch_mode<F, GEMV_RESIDUAL>(a, TT, rp, grid, lds, s);
+    case GEMV_SWIGLU: return launch_mode<F, GEMV_SWIGLU>(a, TT, rp, grid, lds, s);
+    case GEMV_QKV_ROPE: return launch_mode<F, GEMV_QKV_ROPE>(a, TT, rp, grid, lds, s);
+    default: return hipErrorInvalidValue;
   }
 }
 

@@ -28,19 +28,6 @@ __global__ __launch_bounds__(256, (TT <= 3 ? 3 : 2)) void gemv_w4_kernel(GemvW4A
   gemv_body<WMxfp4, TT, MODE, 2 * RP, DMA>(a.g, a.scale, smem, blockIdx.x, gridDim.x, 0);
 }
 
-template <int MODE>
-hipError_t launch_mode(const GemvW4Args& a, int TT, int rp, dim3 grid, size_t lds, hipStream_t s) {
-  return for_tt(TT, [&](auto tt) {
-    constexpr int T = decltype(tt)::value;
-    if constexpr (T == 1) {
-      return rp == 2 ? launch_lds<gemv_w4_kernel<1, MODE, 2, false>>(a, grid, lds, s) : launch_lds<gemv_w4_kernel<1, MODE, 1, false>>(a, grid, lds, s);
-    } else {
-      return stage_by_dma(MODE, T, a.g.K) ? launch_lds<gemv_w4_kernel<T, MODE, 1, true>>(a, grid, lds, s)
-                                          : launch_lds<gemv_w4_kernel<T, MODE, 1, false>>(a, grid, lds, s);
-    }
-  });
-}
-
 // ---- rows of MXFP4 -> bf16 rows: out[r, k] = 2^(scale[r, k / 32] - 127) * e2m1(code[r, k]), exact.  One 16-byte load, one scale
 // byte and four 16-byte stores per lane; up to three matrices side by side (q | k | v, W1 | W3) in one launch.
 __global__ __launch_bounds__(256) void dequant_w4_kernel(DequantW4Args a) {
@@ -79,29 +66,12 @@ hipError_t launch_dequant_w4(const DequantW4Args& a, hipStream_t s) {
 // 1966 (eight-row units, which are not built); below that, where nothing was measured, a wave keeps the two-row unit (profiles/EXPERIMENTS.md)
 int gemv_w4_row_pairs(int npairs, int cus) { return npairs >= 8 * cus ? 2 : 1; }
 
-// One launch; a.g.T must be <= gemv_max_tokens(K) (the activation rows are bf16 as in gemv.hip: the same LDS budget).
-hipError_t launch_gemv_w4(const GemvW4Args& a, hipStream_t s) {
-  const GemvArgs& g = a.g;
-  static int rp_env = -1;
-  const int cus = device_cus();
-  if (rp_env < 0) {
-    const char* e = getenv("MI_GEMV_W4_RP");  // 1 / 2: row pairs per unit at one token (A/B); 0: the rule above
-    rp_env = e ? atoi(e) : 0;
-  }
-  const int npairs = g.mode == GEMV_SWIGLU ? g.N : (g.N + 1) / 2;
-  int rp = g.T == 1 ? gemv_w4_row_pairs(npairs, cus) : 1;
-  if (g.T == 1 && (rp_env == 1 || rp_env == 2)) rp = rp_env;
-  const int units = (npairs + rp - 1) / rp;
-  int blocks = even_blocks(units, cus);
-  if (!blocks) blocks = spread_blocks(units, max_blocks(cus));
-  const int TT = round_tt(g.T);
-  const size_t lds = lds_bytes(TT, g.K, g.norm_w != nullptr);
-  const dim3 grid(blocks_for_lds(blocks, units, cus, lds));
-  switch (g.mode) {
-    case GEMV_STORE: return launch_mode<GEMV_STORE>(a, TT, rp, grid, lds, s);
-    case GEMV_RESIDUAL: return launch_mode<GEMV_RESIDUAL>(a, TT, rp, grid, lds, s);
-    case GEMV_SWIGLU: return launch_mode<GEMV_SWIGLU>(a, TT, rp, grid, lds, s);
-    case GEMV_QKV_ROPE: return launch_mode<GEMV_QKV_ROPE>(a, TT, rp, grid, lds, s);
-    default: return hipErrorInvalidValue;
-  }
-}
+namespace {
+struct W4 {  // what launch_gemv_scaled (gemv_core.cuh) asks of a weight format
+  template <int TT, int MODE, int RP, bool DMA>
+  static constexpr auto kernel = gemv_w4_kernel<TT, MODE, RP, DMA>;
+  static constexpr const char* kRpEnv = "MI_GEMV_W4_RP";
+  static int row_pairs(int npairs, int cus) { return gemv_w4_row_pairs(npairs, cus); }
+};
+}  // namespace
+hipError_t launch_gemv_w4(const GemvW4Args& a, hipStream_t s) { return launch_gemv_scaled<W4>(a, s); }

@@ -6,7 +6,7 @@
 //
 // A row is half the bytes of a bf16 row, so the fixed cost of a unit (wave reductions, epilogue, loop bookkeeping) weighs twice
 // as much.  Units are therefore RP row pairs: RP = 2 (four rows) where the matrix has enough row pairs that every wave of the grid
-// still gets at least two units (W1|W3), else RP = 1 (launch_gemv_w8).
+// still gets at least two units (W1|W3), else RP = 1 (W8::row_pairs; MI_GEMV_W8_RP: its A/B switch).
 #include <cstdlib>
 
 #include "common.cuh"
@@ -22,19 +22,6 @@ template <int TT, int MODE, int RP, bool DMA>
 __global__ __launch_bounds__(256, (TT == 1 ? 4 : (TT <= 3 ? 3 : 2))) void gemv_w8_kernel(GemvW8Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   gemv_body<WE4m3, TT, MODE, 2 * RP, DMA>(a.g, a.scale, smem, blockIdx.x, gridDim.x, 0);
-}
-
-template <int MODE>
-hipError_t launch_mode(const GemvW8Args& a, int TT, int rp, dim3 grid, size_t lds, hipStream_t s) {
-  return for_tt(TT, [&](auto tt) {
-    constexpr int T = decltype(tt)::value;
-    if constexpr (T == 1) {
-      return rp == 2 ? launch_lds<gemv_w8_kernel<1, MODE, 2, false>>(a, grid, lds, s) : launch_lds<gemv_w8_kernel<1, MODE, 1, false>>(a, grid, lds, s);
-    } else {
-      return stage_by_dma(MODE, T, a.g.K) ? launch_lds<gemv_w8_kernel<T, MODE, 1, true>>(a, grid, lds, s)
-                                          : launch_lds<gemv_w8_kernel<T, MODE, 1, false>>(a, grid, lds, s);
-    }
-  });
 }
 
 // ---- rows of e4m3 + row scales -> bf16 rows: out[r, k] = bf16(scale[r] * e4m3(W[r, k])).  One 16-byte load and two 16-byte
@@ -69,30 +56,13 @@ hipError_t launch_dequant_w8(const DequantW8Args& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-// One launch; a.g.T must be <= gemv_max_tokens(K) (the activation rows are bf16 as in gemv.hip: the same LDS budget).
-hipError_t launch_gemv_w8(const GemvW8Args& a, hipStream_t s) {
-  const GemvArgs& g = a.g;
-  static int rp_env = -1;
-  const int cus = device_cus();
-  if (rp_env < 0) {
-    const char* e = getenv("MI_GEMV_W8_RP");  // 1 / 2: row pairs per unit at one token (A/B); 0: the rule below
-    rp_env = e ? atoi(e) : 0;
-  }
-  const int npairs = g.mode == GEMV_SWIGLU ? g.N : (g.N + 1) / 2;
+namespace {
+struct W8 {  // what launch_gemv_scaled (gemv_core.cuh) asks of a weight format
+  template <int TT, int MODE, int RP, bool DMA>
+  static constexpr auto kernel = gemv_w8_kernel<TT, MODE, RP, DMA>;
+  static constexpr const char* kRpEnv = "MI_GEMV_W8_RP";
   // four-row units only where every wave of a full grid (2 blocks of 4 waves per CU) still gets two of them
-  int rp = (g.T == 1 && npairs >= 2 * 2 * 8 * cus) ? 2 : 1;
-  if (g.T == 1 && (rp_env == 1 || rp_env == 2)) rp = rp_env;
-  const int units = (npairs + rp - 1) / rp;
-  int blocks = even_blocks(units, cus);
-  if (!blocks) blocks = spread_blocks(units, max_blocks(cus));
-  const int TT = round_tt(g.T);
-  const size_t lds = lds_bytes(TT, g.K, g.norm_w != nullptr);
-  const dim3 grid(blocks_for_lds(blocks, units, cus, lds));
-  switch (g.mode) {
-    case GEMV_STORE: return launch_mode<GEMV_STORE>(a, TT, rp, grid, lds, s);
-    case GEMV_RESIDUAL: return launch_mode<GEMV_RESIDUAL>(a, TT, rp, grid, lds, s);
-    case GEMV_SWIGLU: return launch_mode<GEMV_SWIGLU>(a, TT, rp, grid, lds, s);
-    case GEMV_QKV_ROPE: return launch_mode<GEMV_QKV_ROPE>(a, TT, rp, grid, lds, s);
-    default: return hipErrorInvalidValue;
-  }
-}
+  static int row_pairs(int npairs, int cus) { return npairs >= 2 * 2 * 8 * cus ? 2 : 1; }
+};
+}  // namespace
+hipError_t launch_gemv_w8(const GemvW8Args& a, hipStream_t s) { return launch_gemv_scaled<W8>(a, s); }

@@ -64,42 +64,36 @@ hipError_t launch_gemv(const GemvArgs& a, hipStream_t s);
 int gemv_max_tokens_f16(int K);
 hipError_t launch_gemv_f16(const GemvArgs& a, hipStream_t s);
 
-// gemv_w8.hip: the same launches on weight rows of OCP e4m3 bytes with fp32 row scales (weight-only FP8).  GemvArgs is the bf16
-// kernels' kernarg and stays as it is: the scales ride beside it.  w0 / w1 / w2 point to bytes, K % 16 == 0, modes STORE /
-// RESIDUAL / SWIGLU / QKV_ROPE; scale[i] holds one fp32 per row of segment i (SWIGLU: scale[0] = W1's, scale[1] = W3's).
-struct GemvW8Args {
+// The same launches on quantised weight rows with their scales (weight-only formats).  GemvArgs is the bf16 kernels' kernarg and
+// stays as it is: the scales ride beside it.  w0 / w1 / w2 point to bytes, modes STORE / RESIDUAL / SWIGLU / QKV_ROPE; scale[i]
+// belongs to segment i (SWIGLU: scale[0] = W1's, scale[1] = W3's).
+template <class scale_t>
+struct GemvScaledArgs {
   GemvArgs g;
-  const float* scale[3];
+  const scale_t* scale[3];
 };
+// The dequantised image of the N rows of up to three matrices side by side (segment ends n0, n1 as in GemvArgs), dense [N, K]
+// bf16: what the MFMA GEMMs read at more than 8 rows
+template <class scale_t>
+struct DequantArgs {
+  const uint8_t* w[3];
+  const scale_t* scale[3];
+  int n0, n1, N, K;
+  bf16_t* out;
+};
+// gemv_w8.hip: OCP e4m3 bytes [rows, K], K % 16 == 0; scale[i] holds one fp32 per row.  out[r, k] = bf16(scale[r] * e4m3(W[r, k]))
+typedef GemvScaledArgs<float> GemvW8Args;
+typedef DequantArgs<float> DequantW8Args;
 hipError_t launch_gemv_w8(const GemvW8Args& a, hipStream_t s);
-// out[r, k] = bf16(scale[r] * e4m3(W[r, k])) for the N rows of up to three matrices side by side (segment ends n0, n1 as in
-// GemvArgs), dense [N, K] bf16: the weight image the MFMA GEMMs read at more than 8 rows
-struct DequantW8Args {
-  const uint8_t* w[3];
-  const float* scale[3];
-  int n0, n1, N, K;
-  bf16_t* out;
-};
 hipError_t launch_dequant_w8(const DequantW8Args& a, hipStream_t s);
-
-// gemv_w4.hip: the same launches on OCP MXFP4 weight rows: w0 / w1 / w2 point to e2m1 code bytes [rows, K / 2] (two codes per byte,
-// the low nibble at the even k), scale[i] to the e8m0 block scales [rows, K / 32] of segment i (byte b: 2^(b - 127)); K % 32 == 0,
-// modes STORE / RESIDUAL / SWIGLU / QKV_ROPE (SWIGLU: scale[0] = W1's, scale[1] = W3's).
-struct GemvW4Args {
-  GemvArgs g;
-  const uint8_t* scale[3];
-};
+// gemv_w4.hip: OCP MXFP4, e2m1 code bytes [rows, K / 2] (two codes per byte, the low nibble at the even k), K % 32 == 0; scale[i]
+// holds the e8m0 block scales [rows, K / 32] (byte b: 2^(b - 127)).  out[r, k] = 2^(scale[r, k / 32] - 127) * e2m1(code[r, k]),
+// exact in bf16
+typedef GemvScaledArgs<uint8_t> GemvW4Args;
+typedef DequantArgs<uint8_t> DequantW4Args;
 hipError_t launch_gemv_w4(const GemvW4Args& a, hipStream_t s);
-int gemv_w4_row_pairs(int npairs, int cus);  // row pairs per unit the launcher picks at one token
-// out[r, k] = 2^(scale[r, k / 32] - 127) * e2m1(code[r, k]) (exact in bf16) for the N rows of up to three matrices side by side,
-// dense [N, K] bf16: the weight image the MFMA GEMMs read at more than 8 rows
-struct DequantW4Args {
-  const uint8_t* w[3];
-  const uint8_t* scale[3];
-  int n0, n1, N, K;
-  bf16_t* out;
-};
 hipError_t launch_dequant_w4(const DequantW4Args& a, hipStream_t s);
+int gemv_w4_row_pairs(int npairs, int cus);  // row pairs per unit the launcher picks at one token
 
 // ---------------------------------------------------------------------------------------------- GEMM
 enum GemmEpi { GEMM_STORE = 0, GEMM_RESIDUAL = 1, GEMM_SWIGLU = 2, GEMM_LOGITS = 3, GEMM_LOGPROB = 4 };
@@ -335,8 +329,7 @@ struct EngProblem {
   uint32_t* ctrl;
   int forced;                // mi_debug_set_engine_variant(1): take shapes that measured slower than the launch path too (traces, tests)
   int lora_rank;             // > 0: the model carries un-merged LoRA adapters - no engine build takes it (api.hip engine_route)
-  int w8;                    // != 0: the layers' linears are e4m3 bytes (mi_forward_w8) - no engine build reads them
-  int w4;                    // != 0: the layers' linears are MXFP4 (mi_forward_w4) - no engine build reads them
+  int quant;                 // != 0: the layers' linears are quantised (mi_forward_w8 / _w4) - no engine build reads them
 };
 static_assert(sizeof(EngArgs) <= 4096, "EngArgs must fit the kernel-argument segment");
 size_t decode_engine_granule_bytes(int D, int H, int Hkv, int F, int maxW);  // the same for every build (default object only)

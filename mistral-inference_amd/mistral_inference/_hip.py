@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import List, Optional, Sequence
+from typing import Callable, List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -294,41 +294,66 @@ def linear(x: torch.Tensor, weights: Sequence[torch.Tensor], epilogue: int = EPI
     return out
 
 
-def linear_w8(x: torch.Tensor, weights: Sequence[torch.Tensor], scales: Sequence[torch.Tensor], epilogue: int = EPI_STORE,
-              residual: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0,
-              out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """`linear` on weight-only FP8 matrices (mi_linear_w8): weights[i] e4m3 bytes [n_i, K] (uint8 or float8_e4m3fn), scales[i]
-    fp32 [n_i]; STORE / RESIDUAL / SWIGLU.  M <= 8: the e4m3 GEMV; above: dequantise into a per-call scratch + the bf16 GEMM."""
+def _prep_w8(w: torch.Tensor, sc: torch.Tensor, K: int) -> torch.Tensor:
+    assert w.shape[1] == K and w.is_contiguous() and w.dtype in (torch.uint8, torch.float8_e4m3fn)
+    assert sc.dtype == torch.float32 and tuple(sc.shape) == (w.shape[0],) and sc.is_contiguous()
+    return w.view(torch.uint8) if w.dtype != torch.uint8 else w
+
+
+def _prep_w4(w: torch.Tensor, sc: torch.Tensor, K: int) -> torch.Tensor:
+    assert K % 32 == 0, f"MXFP4: K = {K} must be a multiple of 32"
+    assert w.dtype == torch.uint8 and w.is_contiguous() and w.shape[1] == K // 2
+    assert sc.dtype == torch.uint8 and sc.is_contiguous() and tuple(sc.shape) == (w.shape[0], K // 32)
+    return w
+
+
+class QuantFormat(NamedTuple):
+    """A weight-only format as this module sees it: `suffix` names its entry points (mi_linear_<suffix>, mi_forward_<suffix>, ...),
+    `prep(w, scale, K)` validates one linear's tensors and returns the weight as uint8 bytes; the rest mirrors the header."""
+    name: str
+    suffix: str
+    scale_dtype: torch.dtype
+    prep: Callable[[torch.Tensor, torch.Tensor, int], torch.Tensor]
+    format: int
+    model_t: type
+    layer_t: type
+
+
+W8 = QuantFormat("FP8", "w8", torch.float32, _prep_w8, MI_W8_FP8_E4M3, MiW8Model, MiW8Layer)
+W4 = QuantFormat("MXFP4", "w4", torch.uint8, _prep_w4, MI_W4_MXFP4, MiW4Model, MiW4Layer)
+
+
+def linear_quant(q: QuantFormat, x: torch.Tensor, weights: Sequence[torch.Tensor], scales: Sequence[torch.Tensor],
+                 epilogue: int = EPI_STORE, residual: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None,
+                 eps: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`linear` on up to three weight-only quantised matrices of format `q` with their scales (mi_linear_w8 / mi_linear_w4)."""
     assert 1 <= len(weights) <= 3 and len(scales) == len(weights) and x.dim() == 2
     if x.dtype != torch.bfloat16:
-        raise NotImplementedError("FP8 weight-only linears take bfloat16 activations (fp16 / fp32 storage is not implemented)")
+        raise NotImplementedError(f"{q.name} weight-only linears take bfloat16 activations (fp16 / fp32 storage is not implemented)")
     M, K = x.shape
     n_rows = [w.shape[0] for w in weights]
-    wb = []
-    for w, sc in zip(weights, scales):
-        assert w.shape[1] == K and w.is_contiguous() and w.dtype in (torch.uint8, torch.float8_e4m3fn)
-        assert sc.dtype == torch.float32 and tuple(sc.shape) == (w.shape[0],) and sc.is_contiguous()
-        wb.append(w.view(torch.uint8) if w.dtype != torch.uint8 else w)
+    wb = [q.prep(w, sc, K) for w, sc in zip(weights, scales)]
     N = n_rows[0] if epilogue == EPI_SWIGLU else sum(n_rows)
     if out is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
     pad = [None] * (3 - len(weights))
     wp = (_vp * 3)(*[dev_ptr(w, torch.uint8) for w in wb], *pad)
-    sp = (_vp * 3)(*[dev_ptr(sc, torch.float32) for sc in scales], *pad)
+    sp = (_vp * 3)(*[dev_ptr(sc, q.scale_dtype) for sc in scales], *pad)
     nr = (C.c_int * 3)(*n_rows, *([0] * (3 - len(weights))))
-    L = lib()
-    need = L.mi_linear_w8_scratch_bytes(M, K, nr, epilogue)
+    L, entry = lib(), f"mi_linear_{q.suffix}"
+    need = getattr(L, entry + "_scratch_bytes")(M, K, nr, epilogue)
     scratch = torch.empty(need, dtype=torch.uint8, device=x.device) if need else None  # per call, from the caching allocator
-    check(L.mi_linear_w8(dev_ptr(out), out.stride(0), dev_ptr(x), x.stride(0), M, K, wp, nr, epilogue, dev_ptr(residual),
-                         dev_ptr(norm_w), float(eps), sp, scratch.data_ptr() if need else None, need, stream_ptr(x.device)),
-          "mi_linear_w8")
+    check(getattr(L, entry)(dev_ptr(out), out.stride(0), dev_ptr(x), x.stride(0), M, K, wp, nr, epilogue, dev_ptr(residual),
+                            dev_ptr(norm_w), float(eps), sp, scratch.data_ptr() if need else None, need, stream_ptr(x.device)), entry)
     return out
 
 
-def _check_w4(w: torch.Tensor, sc: torch.Tensor, K: int) -> None:
-    assert K % 32 == 0, f"MXFP4: K = {K} must be a multiple of 32"
-    assert w.dtype == torch.uint8 and w.is_contiguous() and w.shape[1] == K // 2
-    assert sc.dtype == torch.uint8 and sc.is_contiguous() and tuple(sc.shape) == (w.shape[0], K // 32)
+def linear_w8(x: torch.Tensor, weights: Sequence[torch.Tensor], scales: Sequence[torch.Tensor], epilogue: int = EPI_STORE,
+              residual: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`linear` on weight-only FP8 matrices (mi_linear_w8): weights[i] e4m3 bytes [n_i, K] (uint8 or float8_e4m3fn), scales[i]
+    fp32 [n_i]; STORE / RESIDUAL / SWIGLU.  M <= 8: the e4m3 GEMV; above: dequantise into a per-call scratch + the bf16 GEMM."""
+    return linear_quant(W8, x, weights, scales, epilogue, residual, norm_w, eps, out)
 
 
 def linear_w4(x: torch.Tensor, weights: Sequence[torch.Tensor], scales: Sequence[torch.Tensor], epilogue: int = EPI_STORE,
@@ -337,27 +362,7 @@ def linear_w4(x: torch.Tensor, weights: Sequence[torch.Tensor], scales: Sequence
     """`linear` on weight-only MXFP4 matrices (mi_linear_w4): weights[i] uint8 code bytes [n_i, K / 2] (low nibble = even k),
     scales[i] uint8 e8m0 block scales [n_i, K / 32]; STORE / RESIDUAL / SWIGLU.  M <= 8: the MXFP4 GEMV; above: dequantise into a
     per-call scratch + the bf16 GEMM."""
-    assert 1 <= len(weights) <= 3 and len(scales) == len(weights) and x.dim() == 2
-    if x.dtype != torch.bfloat16:
-        raise NotImplementedError("MXFP4 weight-only linears take bfloat16 activations (fp16 / fp32 storage is not implemented)")
-    M, K = x.shape
-    n_rows = [w.shape[0] for w in weights]
-    for w, sc in zip(weights, scales):
-        _check_w4(w, sc, K)
-    N = n_rows[0] if epilogue == EPI_SWIGLU else sum(n_rows)
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-    pad = [None] * (3 - len(weights))
-    wp = (_vp * 3)(*[dev_ptr(w, torch.uint8) for w in weights], *pad)
-    sp = (_vp * 3)(*[dev_ptr(sc, torch.uint8) for sc in scales], *pad)
-    nr = (C.c_int * 3)(*n_rows, *([0] * (3 - len(weights))))
-    L = lib()
-    need = L.mi_linear_w4_scratch_bytes(M, K, nr, epilogue)
-    scratch = torch.empty(need, dtype=torch.uint8, device=x.device) if need else None  # per call, from the caching allocator
-    check(L.mi_linear_w4(dev_ptr(out), out.stride(0), dev_ptr(x), x.stride(0), M, K, wp, nr, epilogue, dev_ptr(residual),
-                         dev_ptr(norm_w), float(eps), sp, scratch.data_ptr() if need else None, need, stream_ptr(x.device)),
-          "mi_linear_w4")
-    return out
+    return linear_quant(W4, x, weights, scales, epilogue, residual, norm_w, eps, out)
 
 
 def lora_linear(x: torch.Tensor, weights: Sequence[torch.Tensor], lora_a: Sequence[Optional[torch.Tensor]],
@@ -614,27 +619,31 @@ def qkv_rope_kvwrite(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: to
     return out
 
 
+def qkv_rope_kvwrite_quant(q: QuantFormat, x, wq, wk, wv, sq, sk, sv, head_dim, rope_cs, tok_pos, norm_w=None, eps=0.0, cache_k=None,
+                           cache_v=None, tok_seq=None) -> torch.Tensor:
+    """`qkv_rope_kvwrite` on weight-only quantised matrices of format `q` (mi_qkv_rope_kvwrite_w8 / _w4)."""
+    T, D = x.shape
+    nq, nkv = wq.shape[0], wk.shape[0]
+    assert wv.shape[0] == nkv and rope_cs.dtype == torch.float32 and rope_cs.is_contiguous() and tok_pos.dtype == torch.int32
+    ws = [q.prep(w, sc, D) for w, sc in zip((wq, wk, wv), (sq, sk, sv))]
+    out = torch.empty((T, nq + 2 * nkv), dtype=x.dtype, device=x.device)
+    W = cache_k.shape[1] if cache_k is not None else 0
+    u8, f32, entry = torch.uint8, torch.float32, f"mi_qkv_rope_kvwrite_{q.suffix}"
+    check(getattr(lib(), entry)(dev_ptr(out), out.stride(0), dev_ptr(x), x.stride(0), T, D, dev_ptr(ws[0], u8), dev_ptr(ws[1], u8),
+                                dev_ptr(ws[2], u8), dev_ptr(sq, q.scale_dtype), dev_ptr(sk, q.scale_dtype), dev_ptr(sv, q.scale_dtype),
+                                nq // head_dim, nkv // head_dim, head_dim, dev_ptr(norm_w), float(eps), dev_ptr(rope_cs, f32),
+                                rope_cs.shape[0], dev_ptr(tok_pos, torch.int32), dev_ptr(tok_seq, torch.int32), dev_ptr(cache_k),
+                                dev_ptr(cache_v), W, _kv_layout2(cache_k, cache_v) if cache_k is not None else KV_SLOT_MAJOR,
+                                stream_ptr(x.device)), entry)
+    return out
+
+
 def qkv_rope_kvwrite_w8(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor, sq: torch.Tensor, sk: torch.Tensor,
                         sv: torch.Tensor, head_dim: int, rope_cs: torch.Tensor, tok_pos: torch.Tensor,
                         norm_w: Optional[torch.Tensor] = None, eps: float = 0.0, cache_k: Optional[torch.Tensor] = None,
                         cache_v: Optional[torch.Tensor] = None, tok_seq: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`qkv_rope_kvwrite` on weight-only FP8 matrices (mi_qkv_rope_kvwrite_w8): wq / wk / wv e4m3 bytes, sq / sk / sv fp32 row scales."""
-    T, D = x.shape
-    nq, nkv = wq.shape[0], wk.shape[0]
-    assert wv.shape[0] == nkv and rope_cs.dtype == torch.float32 and rope_cs.is_contiguous() and tok_pos.dtype == torch.int32
-    ws = [w.view(torch.uint8) if w.dtype != torch.uint8 else w for w in (wq, wk, wv)]
-    for w, sc in zip(ws, (sq, sk, sv)):
-        assert w.is_contiguous() and w.shape[1] == D and sc.dtype == torch.float32 and tuple(sc.shape) == (w.shape[0],)
-    out = torch.empty((T, nq + 2 * nkv), dtype=x.dtype, device=x.device)
-    W = cache_k.shape[1] if cache_k is not None else 0
-    u8, f32 = torch.uint8, torch.float32
-    check(lib().mi_qkv_rope_kvwrite_w8(dev_ptr(out), out.stride(0), dev_ptr(x), x.stride(0), T, D, dev_ptr(ws[0], u8), dev_ptr(ws[1], u8),
-                                       dev_ptr(ws[2], u8), dev_ptr(sq, f32), dev_ptr(sk, f32), dev_ptr(sv, f32), nq // head_dim,
-                                       nkv // head_dim, head_dim, dev_ptr(norm_w), float(eps), dev_ptr(rope_cs, f32), rope_cs.shape[0],
-                                       dev_ptr(tok_pos, torch.int32), dev_ptr(tok_seq, torch.int32), dev_ptr(cache_k), dev_ptr(cache_v), W,
-                                       _kv_layout2(cache_k, cache_v) if cache_k is not None else KV_SLOT_MAJOR, stream_ptr(x.device)),
-          "mi_qkv_rope_kvwrite_w8")
-    return out
+    return qkv_rope_kvwrite_quant(W8, x, wq, wk, wv, sq, sk, sv, head_dim, rope_cs, tok_pos, norm_w, eps, cache_k, cache_v, tok_seq)
 
 
 def qkv_rope_kvwrite_w4(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor, sq: torch.Tensor, sk: torch.Tensor,
@@ -643,21 +652,7 @@ def qkv_rope_kvwrite_w4(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv:
                         cache_v: Optional[torch.Tensor] = None, tok_seq: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`qkv_rope_kvwrite` on weight-only MXFP4 matrices (mi_qkv_rope_kvwrite_w4): wq / wk / wv code bytes [n, D / 2], sq / sk / sv
     e8m0 block scales [n, D / 32]."""
-    T, D = x.shape
-    nq, nkv = wq.shape[0], wk.shape[0]
-    assert wv.shape[0] == nkv and rope_cs.dtype == torch.float32 and rope_cs.is_contiguous() and tok_pos.dtype == torch.int32
-    for w, sc in zip((wq, wk, wv), (sq, sk, sv)):
-        _check_w4(w, sc, D)
-    out = torch.empty((T, nq + 2 * nkv), dtype=x.dtype, device=x.device)
-    W = cache_k.shape[1] if cache_k is not None else 0
-    u8, f32 = torch.uint8, torch.float32
-    check(lib().mi_qkv_rope_kvwrite_w4(dev_ptr(out), out.stride(0), dev_ptr(x), x.stride(0), T, D, dev_ptr(wq, u8), dev_ptr(wk, u8),
-                                       dev_ptr(wv, u8), dev_ptr(sq, u8), dev_ptr(sk, u8), dev_ptr(sv, u8), nq // head_dim,
-                                       nkv // head_dim, head_dim, dev_ptr(norm_w), float(eps), dev_ptr(rope_cs, f32), rope_cs.shape[0],
-                                       dev_ptr(tok_pos, torch.int32), dev_ptr(tok_seq, torch.int32), dev_ptr(cache_k), dev_ptr(cache_v), W,
-                                       _kv_layout2(cache_k, cache_v) if cache_k is not None else KV_SLOT_MAJOR, stream_ptr(x.device)),
-          "mi_qkv_rope_kvwrite_w4")
-    return out
+    return qkv_rope_kvwrite_quant(W4, x, wq, wk, wv, sq, sk, sv, head_dim, rope_cs, tok_pos, norm_w, eps, cache_k, cache_v, tok_seq)
 
 
 def moe_experts(x: torch.Tensor, expert_tab: torch.Tensor, n_experts: int, hidden_dim: int, sel_idx: torch.Tensor,

@@ -1,8 +1,9 @@
 """Weight-only FP8 (OCP e4m3) linears over the HIP operators, and the quantiser that writes such checkpoints.
 
 A quantised linear stores `weight` as e4m3fn bytes [out, in] and `qscale_weight` as fp32 [out]; the real-valued weight is
-`qscale_weight[r] * e4m3(weight[r, k])`.  The reference has no quantised layer: `Fp8Linear` stands where its `nn.Linear` stands
-(reference transformer_layers.py:51-54,101-103) and its `forward` is one `mi_linear_w8` call (csrc/gemv_w8.hip):
+`qscale_weight[r] * e4m3(weight[r, k])`.  The reference has no quantised layer: `Fp8Linear` (a `QuantLinear`, which carries what every weight format
+shares) stands where its `nn.Linear` stands (reference transformer_layers.py:51-54,101-103) and its `forward` is one
+`mi_linear_w8` call (csrc/gemv_w8.hip):
 
     T <= 8:  acc = sum_k e4m3(W[r, k]) x[k] in fp32;  y = bf16(acc * qscale_weight[r])
     T  > 8:  W' = bf16(qscale_weight[r] * e4m3(W[r, k])) into a scratch, then the bf16 MFMA GEMM on W'
@@ -38,34 +39,26 @@ E4M3_MAX = 448.0
 # the linears that are quantised: the seven of every dense layer, nothing else
 _QUANT_KEY = re.compile(r"^layers\.\d+\.(attention\.w[qkvo]|feed_forward\.w[123])\.weight$")
 
-FP8_LORA_REFUSAL = ("un-merged LoRA on an FP8-quantised base is not implemented; merge the adapter into the bf16 weights "
-                    "(Transformer.load_lora on a bf16 model) and quantise the result")
-FP8_MOE_REFUSAL = "FP8 weight-only quantisation of a MoE model is not implemented (the expert kernels read bf16 weights)"
-FP8_MERGE_REFUSAL = ("load_lora: merging an adapter into FP8-quantised weights is not implemented (the merge needs the bf16 "
-                     "weights); merge into the bf16 checkpoint and quantise the result")
-MXFP4_LORA_REFUSAL = ("un-merged LoRA on an MXFP4-quantised base is not implemented; merge the adapter into the bf16 weights "
-                      "(Transformer.load_lora on a bf16 model) and quantise the result")
-MXFP4_MOE_REFUSAL = "MXFP4 weight-only quantisation of a MoE model is not implemented (the expert kernels read bf16 weights)"
-MXFP4_MERGE_REFUSAL = ("load_lora: merging an adapter into MXFP4-quantised weights is not implemented (the merge needs the bf16 "
-                       "weights); merge into the bf16 checkpoint and quantise the result")
+# What a quantised model cannot be combined with: one text per kind, the format's name filled in (refusal()).
+_REFUSALS = {
+    "lora": ("un-merged LoRA on an {name}-quantised base is not implemented; merge the adapter into the bf16 weights "
+             "(Transformer.load_lora on a bf16 model) and quantise the result"),
+    "moe": "{name} weight-only quantisation of a MoE model is not implemented (the expert kernels read bf16 weights)",
+    "merge": ("load_lora: merging an adapter into {name}-quantised weights is not implemented (the merge needs the bf16 "
+              "weights); merge into the bf16 checkpoint and quantise the result"),
+    "storage": ("{name} weight-only quantisation with fp16 / fp32 storage ({dtype}) is not implemented: the "
+                "activations, norms and the LM head of a quantised model are bfloat16"),
+    "shape": ("{name} weight-only quantisation on a model shape outside the tuned bf16 kernels (head_dim "
+              "128, dim / hidden_dim multiples of {k_multiple}) is not implemented"),
+    "pth": "{name} weight-only models load from consolidated.safetensors (a .pth checkpoint is not implemented)",
+}
 MXFP4_BLOCK = 32
 E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # magnitude of code & 7; code & 8 is the sign
 
 
-def is_mxfp4(quantization: Optional[QuantizationArgs]) -> bool:
-    return quantization is not None and quantization.qformat_weight == QFORMAT_MXFP4
-
-
-def lora_refusal(quantization: Optional[QuantizationArgs]) -> str:
-    return MXFP4_LORA_REFUSAL if is_mxfp4(quantization) else FP8_LORA_REFUSAL
-
-
-def moe_refusal(quantization: Optional[QuantizationArgs]) -> str:
-    return MXFP4_MOE_REFUSAL if is_mxfp4(quantization) else FP8_MOE_REFUSAL
-
-
-def merge_refusal(quantization: Optional[QuantizationArgs]) -> str:
-    return MXFP4_MERGE_REFUSAL if is_mxfp4(quantization) else FP8_MERGE_REFUSAL
+def refusal(kind: str, quantization: QuantizationArgs, **kw) -> str:
+    cls = quantized_linear_cls(quantization)
+    return _REFUSALS[kind].format(name=cls.name, k_multiple=cls.k_multiple, **kw)
 
 
 def check_quantize_arg(quantize: Optional[str]) -> None:
@@ -74,20 +67,16 @@ def check_quantize_arg(quantize: Optional[str]) -> None:
                                   f"(the weight formats are {', '.join(repr(q) for q in QFORMATS)})")
 
 
-def refuse_fp8_combinations(args, dtype: Optional[torch.dtype]) -> None:
+def refuse_quant_combinations(args, dtype: Optional[torch.dtype]) -> None:
     """What a quantised model cannot be combined with, by name, before anything is read from disk."""
     if args.quantization is None:
         return
     if args.lora is not None:
-        raise NotImplementedError(lora_refusal(args.quantization))
+        raise NotImplementedError(refusal("lora", args.quantization))
     if args.moe is not None:
-        raise NotImplementedError(moe_refusal(args.quantization))
+        raise NotImplementedError(refusal("moe", args.quantization))
     if dtype is not None and dtype != torch.bfloat16:
-        if is_mxfp4(args.quantization):
-            raise NotImplementedError(f"MXFP4 weight-only quantisation with fp16 / fp32 storage ({dtype}) is not implemented: the "
-                                      "activations, norms and the LM head of a quantised model are bfloat16")
-        raise NotImplementedError(f"FP8 weight-only quantisation with fp16 / fp32 storage ({dtype}) is not implemented: the "
-                                  "activations, norms and the LM head of a quantised model are bfloat16")
+        raise NotImplementedError(refusal("storage", args.quantization, dtype=dtype))
 
 
 def is_quantized_linear_key(key: str) -> bool:
@@ -136,17 +125,26 @@ def expand_scale(scale: torch.Tensor, out_features: int) -> torch.Tensor:
     return s.contiguous()
 
 
-class Fp8Linear(nn.Module):
-    """`nn.Linear(bias=False)` on e4m3 weight bytes and fp32 row scales.  The bytes are held as a uint8 parameter and the scales
-    stay fp32 whatever dtype the model is cast to: `model.to(dtype=...)` would otherwise convert a float8 parameter silently, and
-    without its scale."""
+class QuantLinear(nn.Module):
+    """`nn.Linear(bias=False)` on quantised weight bytes and their scales: what every weight-only format shares.  Both are
+    parameters whose dtype no cast touches (uint8 bytes; uint8 or fp32 scales): `model.to(dtype=...)` would otherwise convert a
+    float8 parameter silently, and without its scale.  A format supplies the class attributes below, `empty`, `load_quantized`,
+    `from_checkpoint`, `check_bound` and `dequantized`."""
+    name: str                 # in messages: "FP8"
+    qformat: str              # params.json `quantization.qformat_weight`
+    k_multiple: int           # what in_features (and the model's dim / hidden_dim) must be a multiple of
+    hip: _hip.QuantFormat     # the format's entry points of the library
+    quantize = None           # staticmethod: bf16 [out, in] -> (weight, scale) as a checkpoint stores them
 
     def __init__(self, in_features: int, out_features: int, bias: bool = False):
         super().__init__()
         assert not bias
         self.in_features, self.out_features = in_features, out_features
-        self.weight = nn.Parameter(torch.zeros((out_features, in_features), dtype=torch.uint8), requires_grad=False)
-        self.qscale_weight = nn.Parameter(torch.ones(out_features, dtype=torch.float32), requires_grad=False)
+        self._bind(*self.empty(in_features, out_features))
+
+    def _bind(self, weight: torch.Tensor, scale: torch.Tensor) -> None:
+        self.weight = nn.Parameter(weight, requires_grad=False)
+        self.qscale_weight = nn.Parameter(scale, requires_grad=False)
 
     def _apply(self, fn, recurse: bool = True):
         def keep_dtype(t: torch.Tensor) -> torch.Tensor:  # device moves pass; a dtype cast touches neither bytes nor scales
@@ -154,20 +152,44 @@ class Fp8Linear(nn.Module):
             return out if out.dtype == t.dtype else t.to(device=out.device)
         return nn.Module._apply(self, keep_dtype, recurse)
 
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        shape = x.shape
+        out = linear_quant(x.reshape(-1, shape[-1]), (self,), _hip.EPI_STORE)
+        return out.view(*shape[:-1], self.out_features)
+
+
+def linear_quant(x: torch.Tensor, mods: Sequence[QuantLinear], epilogue: int = _hip.EPI_STORE, residual: Optional[torch.Tensor] = None,
+                 norm_w: Optional[torch.Tensor] = None, eps: float = 0.0) -> torch.Tensor:
+    """`_hip.linear` over up to three quantised linears of one format that share an input (q|k|v; SWIGLU: w1, w3)."""
+    return _hip.linear_quant(mods[0].hip, x, [m.weight for m in mods], [m.qscale_weight for m in mods], epilogue, residual, norm_w, eps)
+
+
+class Fp8Linear(QuantLinear):
+    """e4m3 weight bytes [out, in] (a uint8 parameter) and fp32 row scales [out]."""
+    name, qformat, k_multiple, hip = "FP8", QFORMAT_FP8_E4M3, 16, _hip.W8
+    quantize = staticmethod(quantize_rows)
+
+    @staticmethod
+    def empty(in_features: int, out_features: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        return torch.zeros((out_features, in_features), dtype=torch.uint8), torch.ones(out_features, dtype=torch.float32)
+
     @torch.no_grad()
     def load_quantized(self, q: torch.Tensor, scale: torch.Tensor) -> None:
         """Bind e4m3 weights (float8_e4m3fn or uint8 bytes) and their row scales (fp32 [out], scalar or [1])."""
         assert tuple(q.shape) == (self.out_features, self.in_features), (tuple(q.shape), self.out_features, self.in_features)
-        self.weight = nn.Parameter(weight_bytes(q), requires_grad=False)
-        self.qscale_weight = nn.Parameter(expand_scale(scale, self.out_features).to(q.device), requires_grad=False)
+        self._bind(weight_bytes(q), expand_scale(scale, self.out_features).to(q.device))
+
+    def from_checkpoint(self, name: str, w: torch.Tensor, scale: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """A checkpoint's tensors as the parameters hold them: bytes as uint8, fp32 [out] row scales (a scalar or [1] is broadcast)."""
+        if not scale.is_floating_point() or tuple(w.shape) != (self.out_features, self.in_features):
+            raise ValueError(f"{name}: not an FP8 linear (weight {tuple(w.shape)} {w.dtype}, scale {scale.dtype})")
+        return weight_bytes(w), expand_scale(scale, self.out_features)
+
+    def check_bound(self, name: str) -> None:
+        assert tuple(self.qscale_weight.shape) == (self.out_features,)
 
     def dequantized(self) -> torch.Tensor:
         return dequantize(self.weight, self.qscale_weight)
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        shape = x.shape
-        out = linear_fp8(x.reshape(-1, shape[-1]), (self,), _hip.EPI_STORE)
-        return out.view(*shape[:-1], self.out_features)
 
 
 def weight_bytes(q: torch.Tensor) -> torch.Tensor:
@@ -176,12 +198,6 @@ def weight_bytes(q: torch.Tensor) -> torch.Tensor:
     if q.dtype != torch.uint8:
         raise ValueError(f"a quantised weight is F8_E4M3 (torch.float8_e4m3fn), got {q.dtype}")
     return q.contiguous()
-
-
-def linear_fp8(x: torch.Tensor, mods: Sequence[Fp8Linear], epilogue: int = _hip.EPI_STORE, residual: Optional[torch.Tensor] = None,
-               norm_w: Optional[torch.Tensor] = None, eps: float = 0.0) -> torch.Tensor:
-    """`_hip.linear` over up to three Fp8Linear modules that share an input (q|k|v; SWIGLU: w1, w3)."""
-    return _hip.linear_w8(x, [m.weight for m in mods], [m.qscale_weight for m in mods], epilogue, residual, norm_w, eps)
 
 
 def quantize_blocks(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -238,44 +254,39 @@ def dequantize_mxfp4(packed: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return (vals * sc[:, :, None]).reshape(out, half * 2).to(torch.bfloat16)
 
 
-class Mxfp4Linear(nn.Module):
-    """`nn.Linear(bias=False)` on MXFP4 weights: e2m1 codes [out, in / 2] and e8m0 block scales [out, in / 32], both uint8
-    parameters that no dtype cast touches."""
+class Mxfp4Linear(QuantLinear):
+    """MXFP4 weights: e2m1 codes [out, in / 2] and e8m0 block scales [out, in / 32], both uint8 parameters."""
+    name, qformat, k_multiple, hip = "MXFP4", QFORMAT_MXFP4, MXFP4_BLOCK, _hip.W4
+    quantize = staticmethod(quantize_blocks)
 
-    def __init__(self, in_features: int, out_features: int, bias: bool = False):
-        super().__init__()
-        assert not bias
+    @staticmethod
+    def empty(in_features: int, out_features: int) -> Tuple[torch.Tensor, torch.Tensor]:
         if in_features % MXFP4_BLOCK:
             raise ValueError(f"Mxfp4Linear: in = {in_features} must be a multiple of {MXFP4_BLOCK} (one e8m0 scale per block of 32)")
-        self.in_features, self.out_features = in_features, out_features
-        self.weight = nn.Parameter(torch.zeros((out_features, in_features // 2), dtype=torch.uint8), requires_grad=False)
-        self.qscale_weight = nn.Parameter(torch.full((out_features, in_features // MXFP4_BLOCK), 127, dtype=torch.uint8), requires_grad=False)
-
-    _apply = Fp8Linear._apply
+        return (torch.zeros((out_features, in_features // 2), dtype=torch.uint8),
+                torch.full((out_features, in_features // MXFP4_BLOCK), 127, dtype=torch.uint8))
 
     @torch.no_grad()
     def load_quantized(self, packed: torch.Tensor, scale: torch.Tensor) -> None:
         check_mxfp4_tensors(packed, scale, self.out_features, self.in_features, "Mxfp4Linear.load_quantized")
-        self.weight = nn.Parameter(packed.contiguous(), requires_grad=False)
-        self.qscale_weight = nn.Parameter(scale.contiguous().to(packed.device), requires_grad=False)
+        self._bind(packed.contiguous(), scale.contiguous().to(packed.device))
+
+    def from_checkpoint(self, name: str, w: torch.Tensor, scale: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        check_mxfp4_tensors(w, scale, self.out_features, self.in_features, name)
+        return w, scale
+
+    def check_bound(self, name: str) -> None:
+        check_mxfp4_tensors(self.weight, self.qscale_weight, self.out_features, self.in_features, name)
 
     def dequantized(self) -> torch.Tensor:
         return dequantize_mxfp4(self.weight, self.qscale_weight)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        shape = x.shape
-        out = linear_mxfp4(x.reshape(-1, shape[-1]), (self,), _hip.EPI_STORE)
-        return out.view(*shape[:-1], self.out_features)
 
-
-def linear_mxfp4(x: torch.Tensor, mods: Sequence[Mxfp4Linear], epilogue: int = _hip.EPI_STORE, residual: Optional[torch.Tensor] = None,
-                 norm_w: Optional[torch.Tensor] = None, eps: float = 0.0) -> torch.Tensor:
-    """`_hip.linear` over up to three Mxfp4Linear modules that share an input (q|k|v; SWIGLU: w1, w3)."""
-    return _hip.linear_w4(x, [m.weight for m in mods], [m.qscale_weight for m in mods], epilogue, residual, norm_w, eps)
+QUANT_LINEARS = {cls.qformat: cls for cls in (Fp8Linear, Mxfp4Linear)}
 
 
 def quantized_linear_cls(quantization: QuantizationArgs):
-    return Mxfp4Linear if is_mxfp4(quantization) else Fp8Linear
+    return QUANT_LINEARS[quantization.qformat_weight]
 
 
 def quantize_state_tensor(key: str, t: torch.Tensor, qformat: str = QFORMAT_FP8_E4M3) -> Dict[str, torch.Tensor]:
@@ -284,10 +295,10 @@ def quantize_state_tensor(key: str, t: torch.Tensor, qformat: str = QFORMAT_FP8_
     check_quantize_arg(qformat)
     if not is_quantized_linear_key(key):
         return {key: t}
+    cls = QUANT_LINEARS[qformat]
     if t.dtype != torch.bfloat16:
-        name = "MXFP4" if qformat == QFORMAT_MXFP4 else "FP8"
-        raise NotImplementedError(f"{key}: {name} quantisation starts from a bfloat16 checkpoint, got {t.dtype}")
-    q, scale = quantize_blocks(t) if qformat == QFORMAT_MXFP4 else quantize_rows(t)
+        raise NotImplementedError(f"{key}: {cls.name} quantisation starts from a bfloat16 checkpoint, got {t.dtype}")
+    q, scale = cls.quantize(t)
     return {key: q, key[:-len("weight")] + QSCALE_KEY: scale}
 
 
@@ -308,7 +319,7 @@ def quantize_checkpoint(src_folder: Union[Path, str], dst_folder: Union[Path, st
     if args.quantization is not None:
         raise ValueError(f"{src} is already quantised ({args.quantization.qformat_weight})")
     args.quantization = QuantizationArgs(qformat)
-    refuse_fp8_combinations(args, None)
+    refuse_quant_combinations(args, None)
     st_file = src / "consolidated.safetensors"
     assert st_file.exists(), f"{st_file} does not exist (quantize_checkpoint reads safetensors)"
     out: Dict[str, torch.Tensor] = {}

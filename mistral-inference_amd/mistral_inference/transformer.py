@@ -22,7 +22,7 @@ import math
 import os
 from dataclasses import dataclass
 from pathlib import Path
-from typing import Any, List, Mapping, Optional, Union
+from typing import Any, List, Mapping, Optional, Tuple, Union
 
 import safetensors.torch
 import torch
@@ -33,8 +33,8 @@ from .args import QuantizationArgs, TransformerArgs
 from .cache import BatchMetadata, BufferCache
 from .lora import LoRALinear, check_rank
 from .model import ModelBase
-from .quant import (QSCALE_ACT_KEY, QSCALE_KEY, Fp8Linear, Mxfp4Linear, check_mxfp4_tensors, check_quantize_arg, expand_scale, is_mxfp4,
-                    merge_refusal, quantize_state_tensor, refuse_fp8_combinations, weight_bytes)
+from .quant import (QSCALE_ACT_KEY, QSCALE_KEY, QuantLinear, check_quantize_arg, quantize_state_tensor, quantized_linear_cls,
+                    refusal, refuse_quant_combinations)
 from .rope import precompute_freqs_cis
 from .transformer_layers import LORA_MOE_REFUSAL, RMSNorm, TransformerBlock
 from .vision_encoder import PATCH_MERGE, PatchMerger, VisionLanguageAdapter, VisionTransformer
@@ -99,8 +99,9 @@ class HipStackBackend:
         # persistent tensor.
         self._seq_adapter: Optional[torch.Tensor] = None
         self._seq_adapter_now: Optional[torch.Tensor] = None
-        self._w8: Optional[Any] = None  # set by _build_plan: the mi_w8_model_t of a weight-only FP8 model (then mi_forward_w8 runs it)
-        self._w4: Optional[Any] = None  # ... the mi_w4_model_t of a weight-only MXFP4 model (mi_forward_w4)
+        # set by _build_plan for a weight-only quantised model: (its mi_w8_model_t / mi_w4_model_t, the format's workspace query,
+        # the format's forward, that forward's name)
+        self._quant: Optional[Tuple[Any, Any, Any, str]] = None
 
     # -- one-time: pointer tables of the weights -------------------------------------------------
     def _build_plan(self, model: "Transformer"):
@@ -124,21 +125,15 @@ class HipStackBackend:
         self.dtype_code = _hip.DTYPE_CODES[dt]
         keep = []  # python objects that own memory referenced by raw pointers
         p = lambda t, d=dt: _hip.dev_ptr(t, d)  # noqa: E731
-        fp4 = is_mxfp4(a.quantization)
-        fp8 = a.quantization is not None and not fp4
-        if fp8 or fp4:
-            refuse_fp8_combinations(a, dt)
+        qf = quantized_linear_cls(a.quantization).hip if a.quantization is not None else None
+        if qf is not None:
+            refuse_quant_combinations(a, dt)
             if self.generic:  # bf16, but a shape mi_forward declines: the generic kernels read no quantised weights
-                if fp4:
-                    raise NotImplementedError("MXFP4 weight-only quantisation on a model shape outside the tuned bf16 kernels (head_dim "
-                                              "128, dim / hidden_dim multiples of 32) is not implemented")
-                raise NotImplementedError("FP8 weight-only quantisation on a model shape outside the tuned bf16 kernels (head_dim "
-                                          "128, dim / hidden_dim multiples of 16) is not implemented")
-        # weight-only FP8: the seven linear pointers of a layer are e4m3 bytes, their fp32 row scales ride in a table beside it;
-        # MXFP4: e2m1 code bytes, and the table holds their e8m0 block-scale rows
-        scales = (_hip.MiW8Layer * max(1, model.n_local_layers))() if fp8 else None
-        scales4 = (_hip.MiW4Layer * max(1, model.n_local_layers))() if fp4 else None
-        wp = (lambda mod: _hip.dev_ptr(mod.weight, torch.uint8)) if (fp8 or fp4) else (lambda mod: p(mod.weight))
+                raise NotImplementedError(refusal("shape", a.quantization))
+        # weight-only formats: the seven linear pointers of a layer are quantised bytes, their scales (FP8: fp32 row scales; MXFP4:
+        # e8m0 block-scale rows) ride in a table beside it
+        scales = (qf.layer_t * max(1, model.n_local_layers))() if qf is not None else None
+        wp = (lambda mod: _hip.dev_ptr(mod.weight, torch.uint8)) if qf is not None else (lambda mod: p(mod.weight))
         E = a.moe.num_experts if a.moe is not None else 0
         layers = (_hip.MiLayer * max(1, model.n_local_layers))()
         adapters = (_hip.MiLoraLayer * max(1, model.n_local_layers))() if a.lora is not None else None
@@ -175,13 +170,9 @@ class HipStackBackend:
                 L.w1, L.w2, L.w3 = wp(ff.w1), wp(ff.w2), wp(ff.w3)
             if scales is not None:
                 for name, mod in (("wq", at.wq), ("wk", at.wk), ("wv", at.wv), ("wo", at.wo), ("w1", ff.w1), ("w2", ff.w2), ("w3", ff.w3)):
-                    assert isinstance(mod, Fp8Linear) and tuple(mod.qscale_weight.shape) == (mod.out_features,)
-                    setattr(scales[j], name, _hip.dev_ptr(mod.qscale_weight, torch.float32))
-            if scales4 is not None:
-                for name, mod in (("wq", at.wq), ("wk", at.wk), ("wv", at.wv), ("wo", at.wo), ("w1", ff.w1), ("w2", ff.w2), ("w3", ff.w3)):
-                    assert isinstance(mod, Mxfp4Linear)
-                    check_mxfp4_tensors(mod.weight, mod.qscale_weight, mod.out_features, mod.in_features, name)
-                    setattr(scales4[j], name, _hip.dev_ptr(mod.qscale_weight, torch.uint8))
+                    assert isinstance(mod, QuantLinear) and mod.hip is qf
+                    mod.check_bound(name)
+                    setattr(scales[j], name, _hip.dev_ptr(mod.qscale_weight, qf.scale_dtype))
         rope = torch.view_as_real(model.freqs_cis).contiguous()
         keep += [layers, rope]
         m = _hip.MiModel()
@@ -197,16 +188,13 @@ class HipStackBackend:
         if a.lora is not None:
             m.lora_rank, m.lora_scaling = int(a.lora.rank), float(a.lora.scaling)
             m.lora_slots = int(model.lora_slots)
-        self._w8 = None
-        if scales is not None:
-            self._w8 = _hip.MiW8Model()
-            self._w8.format, self._w8.layers = _hip.MI_W8_FP8_E4M3, C.cast(scales, C.POINTER(_hip.MiW8Layer))
+        self._quant = None
+        if qf is not None:
+            qm = qf.model_t()
+            qm.format, qm.layers = qf.format, C.cast(scales, C.POINTER(qf.layer_t))
+            fwd = "mi_forward_" + qf.suffix
+            self._quant = (qm, getattr(_hip.lib(), "mi_workspace_bytes_" + qf.suffix), getattr(_hip.lib(), fwd), fwd)
             keep.append(scales)
-        self._w4 = None
-        if scales4 is not None:
-            self._w4 = _hip.MiW4Model()
-            self._w4.format, self._w4.layers = _hip.MI_W4_MXFP4, C.cast(scales4, C.POINTER(_hip.MiW4Layer))
-            keep.append(scales4)
         return m, keep
 
     @property
@@ -239,8 +227,7 @@ class HipStackBackend:
 
     def invalidate(self) -> None:
         self._plan = None
-        self._w8 = None
-        self._w4 = None
+        self._quant = None
         self._workspace = None
 
     def raise_if_flagged(self) -> None:
@@ -295,10 +282,8 @@ class HipStackBackend:
     def _get_workspace(self, model: "Transformer", m, T: int, B: int, max_w: int) -> torch.Tensor:
         if self.generic:
             need = _hip.lib().mi_workspace_bytes_generic(C.byref(m), T, self.dtype_code)
-        elif self._w8 is not None:
-            need = _hip.lib().mi_workspace_bytes_w8(C.byref(m), C.byref(self._w8), T, B, max_w)
-        elif self._w4 is not None:
-            need = _hip.lib().mi_workspace_bytes_w4(C.byref(m), C.byref(self._w4), T, B, max_w)
+        elif self._quant is not None:
+            need = self._quant[1](C.byref(m), C.byref(self._quant[0]), T, B, max_w)
         else:
             need = _hip.lib().mi_workspace_bytes(C.byref(m), T, B, max_w)
         ws = self._workspace
@@ -349,10 +334,9 @@ class HipStackBackend:
         if self.generic:
             _hip.check(_hip.lib().mi_forward_generic(C.byref(m), C.byref(bt), self.dtype_code, _hip.stream_ptr(h.device)),
                        "mi_forward_generic")
-        elif self._w8 is not None:
-            _hip.check(_hip.lib().mi_forward_w8(C.byref(m), C.byref(self._w8), C.byref(bt), _hip.stream_ptr(h.device)), "mi_forward_w8")
-        elif self._w4 is not None:
-            _hip.check(_hip.lib().mi_forward_w4(C.byref(m), C.byref(self._w4), C.byref(bt), _hip.stream_ptr(h.device)), "mi_forward_w4")
+        elif self._quant is not None:
+            qm, _, forward, name = self._quant
+            _hip.check(forward(C.byref(m), C.byref(qm), C.byref(bt), _hip.stream_ptr(h.device)), name)
         else:
             _hip.check(_hip.lib().mi_forward(C.byref(m), C.byref(bt), _hip.stream_ptr(h.device)), "mi_forward")
 
@@ -376,7 +360,7 @@ class Transformer(ModelBase):
             if args.moe is not None:
                 raise NotImplementedError(LORA_MOE_REFUSAL)
             check_rank(args.lora.rank)
-        refuse_fp8_combinations(args, None)  # weight-only FP8 (quant.py): dense models without un-merged LoRA
+        refuse_quant_combinations(args, None)  # weight-only formats (quant.py): dense models without un-merged LoRA
 
         # Rank-specific modules (reference transformer.py:52-79)
         self.tok_embeddings: Optional[nn.Embedding] = None
@@ -766,7 +750,7 @@ class Transformer(ModelBase):
         slot: which adapter set of the bank (set_lora_slots) is replaced; the other slots keep serving."""
         self._check_slot(slot)
         if self.args.quantization is not None:  # before anything is read from disk
-            raise NotImplementedError(merge_refusal(self.args.quantization))
+            raise NotImplementedError(refusal("merge", self.args.quantization))
         lora_path = Path(lora_path)
         assert lora_path.is_file(), f"{lora_path} does not exist or is not a file"
         self._load_lora_state_dict(safetensors.torch.load_file(str(lora_path)), scaling=scaling, slot=slot)
@@ -789,7 +773,7 @@ class Transformer(ModelBase):
         if self.args.lora is not None:
             return self._assign_lora(lora_state_dict, slot)
         if self.args.quantization is not None:
-            raise NotImplementedError(merge_refusal(self.args.quantization))
+            raise NotImplementedError(refusal("merge", self.args.quantization))
         if self.dtype != torch.bfloat16 or self.device.type != "cuda":
             raise RuntimeError("load_lora: the merge runs on the GPU in bf16 (model must be on the device)")
         logging.info("Loading and merging LoRA weights...")
@@ -859,7 +843,7 @@ class Transformer(ModelBase):
         on_load = quantize is not None and model_args.quantization is None  # (an already quantised folder loads as it is)
         if on_load:
             model_args.quantization = QuantizationArgs(quantize)
-        refuse_fp8_combinations(model_args, dtype)  # before anything is read from disk
+        refuse_quant_combinations(model_args, dtype)  # before anything is read from disk
         pipeline_rank = torch.distributed.get_rank() if num_pipeline_ranks > 1 else 0
         with torch.device("meta"):
             model = Transformer(model_args, pipeline_rank=pipeline_rank, num_pipeline_ranks=num_pipeline_ranks,
@@ -870,8 +854,7 @@ class Transformer(ModelBase):
         assert not (pt_file.exists() and st_file.exists()), f"Both {pt_file} and {st_file} cannot exist"
         if pt_file.exists():
             if model_args.quantization is not None:
-                raise NotImplementedError(("MXFP4" if is_mxfp4(model_args.quantization) else "FP8") +
-                                          " weight-only models load from consolidated.safetensors (a .pth checkpoint is not implemented)")
+                raise NotImplementedError(refusal("pth", model_args.quantization))
             loaded = torch.load(str(pt_file), mmap=True)
             model.load_state_dict(loaded, assign=True, strict=True)
             return model.to(device=device, dtype=dtype)
@@ -892,18 +875,11 @@ class Transformer(ModelBase):
                 else:
                     model._check_foreign_key(k)
         if model_args.quantization is not None:
-            # bytes as uint8 (no dtype cast can touch them) and fp32 [out] row scales (a scalar or [1] is broadcast)
-            for name, mod in model.named_modules():
-                if isinstance(mod, Mxfp4Linear) and name + ".weight" in loaded:
-                    assert name + "." + QSCALE_KEY in loaded, f"checkpoint is missing {name}.{QSCALE_KEY}"
-                    check_mxfp4_tensors(loaded[name + ".weight"], loaded[name + "." + QSCALE_KEY], mod.out_features, mod.in_features, name)
-                if isinstance(mod, Fp8Linear) and name + ".weight" in loaded:
-                    assert name + "." + QSCALE_KEY in loaded, f"checkpoint is missing {name}.{QSCALE_KEY}"
-                    if not loaded[name + "." + QSCALE_KEY].is_floating_point() or tuple(loaded[name + ".weight"].shape) != (mod.out_features, mod.in_features):
-                        raise ValueError(f"{name}: not an FP8 linear (weight {tuple(loaded[name + '.weight'].shape)} "
-                                         f"{loaded[name + '.weight'].dtype}, scale {loaded[name + '.' + QSCALE_KEY].dtype})")
-                    loaded[name + ".weight"] = weight_bytes(loaded[name + ".weight"])
-                    loaded[name + "." + QSCALE_KEY] = expand_scale(loaded[name + "." + QSCALE_KEY], mod.out_features)
+            for name, mod in model.named_modules():  # every quantised linear validates its tensors and takes them as its parameters hold them
+                if isinstance(mod, QuantLinear) and name + ".weight" in loaded:
+                    wk, sk = name + ".weight", name + "." + QSCALE_KEY
+                    assert sk in loaded, f"checkpoint is missing {sk}"
+                    loaded[wk], loaded[sk] = mod.from_checkpoint(name, loaded[wk], loaded[sk])
         have = set(loaded) | {k.replace(".weight", ".linear.weight") for k in loaded if k in plain}
         missing = {k for k in wanted - have if ".lora_A." not in k and ".lora_B." not in k}  # absent adapters are not "missing"
         assert not missing, f"checkpoint is missing {sorted(missing)[:4]}..."

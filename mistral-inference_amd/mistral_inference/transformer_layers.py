@@ -14,7 +14,7 @@ from .args import LoraArgs, MoeArgs, QuantizationArgs
 from .cache import CacheView
 from .lora import LoRALinear, maybe_lora
 from .moe import MoeLayer
-from .quant import Fp8Linear, Mxfp4Linear, linear_fp8, linear_mxfp4, lora_refusal, moe_refusal, quantized_linear_cls
+from .quant import QuantLinear, linear_quant, quantized_linear_cls, refusal
 
 LORA_MOE_REFUSAL = ("un-merged LoRA on a MoE model (adapters inside the experts) is not implemented; merge the adapter into the "
                     "checkpoint first (what the reference's default CLI path does, lora.py:118-139)")
@@ -32,7 +32,7 @@ def _linear_cls(lora: Optional[LoraArgs], quantization: Optional[QuantizationArg
     quantisation do not combine."""
     if quantization is not None:
         if lora is not None:
-            raise NotImplementedError(lora_refusal(quantization))
+            raise NotImplementedError(refusal("lora", quantization))
         return quantized_linear_cls(quantization)
     return maybe_lora(lora)
 
@@ -71,10 +71,8 @@ class FeedForward(nn.Module):
             a, b = _adapters(self.w1, self.w3)
             hid = _hip.lora_linear(x, (self.w1.weight, self.w3.weight), a, b, self.w1.scaling, _hip.EPI_SWIGLU)
             return self.w2(hid)
-        if isinstance(self.w1, Fp8Linear):  # the same two launches on e4m3 weights (csrc/gemv_w8.hip)
-            return self.w2(linear_fp8(x, (self.w1, self.w3), _hip.EPI_SWIGLU))
-        if isinstance(self.w1, Mxfp4Linear):  # ... on MXFP4 weights (csrc/gemv_w4.hip)
-            return self.w2(linear_mxfp4(x, (self.w1, self.w3), _hip.EPI_SWIGLU))
+        if isinstance(self.w1, QuantLinear):  # the same two launches on quantised weights (csrc/gemv_w8.hip, gemv_w4.hip)
+            return self.w2(linear_quant(x, (self.w1, self.w3), _hip.EPI_SWIGLU))
         hid = _hip.linear(x, (self.w1.weight, self.w3.weight), _hip.EPI_SWIGLU)
         return _hip.linear(hid, (self.w2.weight,), _hip.EPI_STORE)
 
@@ -105,19 +103,12 @@ class Attention(nn.Module):
         cs = torch.view_as_real(freqs_cis).contiguous()  # rows already gathered by position (transformer.py:199)
         rows = torch.arange(T, dtype=torch.int32, device=x.device)
         lora = isinstance(self.wq, LoRALinear)
-        fp8 = isinstance(self.wq, Fp8Linear)
-        fp4 = isinstance(self.wq, Mxfp4Linear)
-        if fp4 and T <= _hip.GEMV_MAX_T:  # the plain model's launches on MXFP4 weights (csrc/gemv_w4.hip)
-            qkv = _hip.qkv_rope_kvwrite_w4(x, self.wq.weight, self.wk.weight, self.wv.weight, self.wq.qscale_weight,
-                                           self.wk.qscale_weight, self.wv.qscale_weight, Dh, cs, rows)
-        elif fp4:
-            qkv = linear_mxfp4(x, (self.wq, self.wk, self.wv), _hip.EPI_STORE)
-            _hip.rope_inplace(qkv, H, Hkv, Dh, cs, rows)
-        elif fp8 and T <= _hip.GEMV_MAX_T:  # the plain model's launches on e4m3 weights (csrc/gemv_w8.hip)
-            qkv = _hip.qkv_rope_kvwrite_w8(x, self.wq.weight, self.wk.weight, self.wv.weight, self.wq.qscale_weight,
-                                           self.wk.qscale_weight, self.wv.qscale_weight, Dh, cs, rows)
-        elif fp8:
-            qkv = linear_fp8(x, (self.wq, self.wk, self.wv), _hip.EPI_STORE)
+        quant = isinstance(self.wq, QuantLinear)
+        if quant and T <= _hip.GEMV_MAX_T:  # the plain model's launches on quantised weights (csrc/gemv_w8.hip, gemv_w4.hip)
+            qkv = _hip.qkv_rope_kvwrite_quant(self.wq.hip, x, self.wq.weight, self.wk.weight, self.wv.weight, self.wq.qscale_weight,
+                                              self.wk.qscale_weight, self.wv.qscale_weight, Dh, cs, rows)
+        elif quant:
+            qkv = linear_quant(x, (self.wq, self.wk, self.wv), _hip.EPI_STORE)
             _hip.rope_inplace(qkv, H, Hkv, Dh, cs, rows)
         elif lora:  # q | k | v with their three adapters: base product, lora_down, lora_up; RoPE as its own pass
             a, b = _adapters(self.wq, self.wk, self.wv)
@@ -141,7 +132,7 @@ class Attention(nn.Module):
             else:
                 cache.update(qkv[:, nq:nq + nkv], qkv[:, nq + nkv:])
                 out = _hip.attn_decode(qkv, cache.cache_k, cache.cache_v, H, b.tok_pos)
-        if lora or fp8 or fp4:
+        if lora or quant:
             return self.wo(out)
         return _hip.linear(out, (self.wo.weight,), _hip.EPI_STORE)
 
@@ -155,7 +146,7 @@ class TransformerBlock(nn.Module):
         super().__init__()
         _no_lora(lora, moe)
         if quantization is not None and moe is not None:
-            raise NotImplementedError(moe_refusal(quantization))
+            raise NotImplementedError(refusal("moe", quantization))
         self.n_heads = n_heads
         self.dim = dim
         self.attention = Attention(dim=dim, n_heads=n_heads, head_dim=head_dim, n_kv_heads=n_kv_heads, lora=lora,

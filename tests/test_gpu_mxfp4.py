@@ -11,25 +11,14 @@ import torch
 import torch.nn.functional as F
 
 import mistral_oracle as mo
-from hip_util import write_checkpoint
+import quant_util as qu
 from mxfp4_cases import EXACT_SHAPES, UNIT, dequant_f64, exact_case, exact_reference, exact_sum_of_magnitudes_units
-from test_gpu_fp8 import LOGIT_ATOL, MODEL, N_DECODE, PROMPTS, _cache, _replay, _schedule, bf, deltas_of, inside_envelope, rnd, ulp_bf16
+from quant_util import BF, MODEL, _hip, _quant, bf, deltas_of, inside_envelope, rnd
 
 pytestmark = pytest.mark.gpu
 
-BF = torch.bfloat16
 MS = [1, 3, 8]
 E2M1 = [0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0]
-
-
-def _hip():
-    from mistral_inference import _hip
-    return _hip
-
-
-def _quant():
-    from mistral_inference import quant
-    return quant
 
 
 class QW:
@@ -284,51 +273,14 @@ def test_qkv_rope_kvwrite_w4_in_four_row_units(head_major):
 
 
 # ------------------------------------------------------------------------------------------------ 6-9. model level
-def _load(folder, B=3, **kw):
-    from mistral_inference.transformer import Transformer
-    return Transformer.from_folder(folder, max_batch_size=B, device="cuda", dtype=BF, **kw)
-
-
 @pytest.fixture(scope="module")
 def folders(tmp_path_factory):
-    """bf16 checkpoint -> quantize_checkpoint(qformat="mxfp4") -> (bf16 folder, MXFP4 folder, folder of the dequantised bf16
-    weights, those weights)."""
-    import safetensors
-    q = _quant()
-    d = tmp_path_factory.mktemp("mxfp4")
-    w = mo.synth_weights(MODEL, seed=21)
-    src = write_checkpoint(d / "bf16", MODEL, w)
-    dst = q.quantize_checkpoint(src, d / "mxfp4", qformat="mxfp4")
-    with safetensors.safe_open(str(dst / "consolidated.safetensors"), framework="pt", device="cpu") as f:
-        sd = {k: f.get_tensor(k) for k in f.keys()}
-    deq = {}
-    for k, v in sd.items():
-        if k.endswith(q.QSCALE_KEY):
-            continue
-        deq[k] = q.dequantize_mxfp4(v, sd[k[:-len("weight")] + q.QSCALE_KEY]) if v.dtype == torch.uint8 else v
-    assert set(deq) == set(w) and sum(v.dtype == torch.uint8 for v in sd.values()) == 2 * 7 * MODEL.n_layers
-    return src, str(dst), write_checkpoint(d / "deq", MODEL, deq), deq
+    return qu.make_folders(qu.MXFP4, tmp_path_factory)
 
 
 @pytest.fixture(scope="module")
 def oracle_runs(folders):
-    """The bf16 oracle on the dequantised weights, once per schedule: logits of every forward and the greedy tokens that every
-    model under test is then fed (teacher forcing)."""
-    om = mo.OracleModel(MODEL, folders[3])
-    runs = {}
-    for B, chunk in ((1, None), (1, 5), (3, None)):
-        oc = mo.OracleCache(MODEL.n_layers, B, 64, MODEL.n_kv_heads, MODEL.head_dim, MODEL.sliding_window, dtype=BF)
-        logits, fed = [], []
-        for ids, lens in _schedule(B, chunk):
-            logits.append(om.forward(torch.tensor(ids), lens, oc))
-        ends = torch.tensor(_schedule(B, chunk)[-1][1]).cumsum(0) - 1
-        tok = logits[-1][ends].argmax(-1)
-        for _ in range(N_DECODE if chunk is None else 3):
-            fed.append(tok)
-            logits.append(om.forward(tok, [1] * B, oc))
-            tok = logits[-1].argmax(-1)
-        runs[(B, chunk)] = (logits, fed)
-    return runs
+    return qu.make_oracle_runs(folders)
 
 
 def test_quantised_model_against_the_oracle_on_the_dequantised_weights(folders, oracle_runs):
@@ -336,39 +288,11 @@ def test_quantised_model_against_the_oracle_on_the_dequantised_weights(folders, 
     B = 1 and B = 3 across the ring wrap: the logits of every forward stay within the project's bf16 tolerance of the oracle on
     the dequantised weights - the quantised model IS that bf16 model up to summation order.  The bf16 HIP path on the dequantised
     weights is run beside it; both distances are printed."""
-    _, q_dir, deq_dir, _ = folders
-    fp4, plain = _load(q_dir), _load(deq_dir)
-    from mistral_inference.quant import Mxfp4Linear
-    assert isinstance(fp4.layers["0"].attention.wq, Mxfp4Linear) and fp4.dtype == BF
-    worst = {"mxfp4": 0.0, "bf16": 0.0}
-    for (B, chunk), (ref, fed) in oracle_runs.items():
-        for name, model in (("mxfp4", fp4), ("bf16", plain)):
-            got = _replay(model, B, chunk, fed)
-            assert len(got) == len(ref)
-            d = max(float((g - r).abs().max()) for g, r in zip(got, ref))
-            print(f"B={B} chunk={chunk}: {name}-HIP to oracle max |dlogit| = {d:.4e} over {len(ref)} forwards")
-            worst[name] = max(worst[name], d)
-    print(f"mxfp4-HIP to oracle {worst['mxfp4']:.4e}; bf16-HIP on dequantised weights to oracle {worst['bf16']:.4e}")
-    assert worst["mxfp4"] <= LOGIT_ATOL, worst
-    st = _hip().decode_engine_status(fp4._backend._workspace)
-    assert st["engine_launches"] == 0 and st["status"] == 0 and st["bad_id"] == 0, st
+    qu.check_model_against_the_oracle(qu.MXFP4, folders, oracle_runs)
 
 
 def test_quantise_while_loading_equals_the_quantised_checkpoint(folders):
-    src, q_dir, _, deq = folders
-    a, b = _load(q_dir), _load(src, quantize="mxfp4")
-    pa, pb = dict(a.named_parameters()), dict(b.named_parameters())
-    assert set(pa) == set(pb)
-    for k in pa:
-        assert pa[k].dtype == pb[k].dtype and torch.equal(pa[k], pb[k]), k
-    assert sum(p.dtype == torch.uint8 for p in pa.values()) == 2 * 7 * MODEL.n_layers
-    ids, lens = _schedule(3, None)[0]
-    ca, cb = _cache(3), _cache(3)
-    with torch.inference_mode():
-        la, lb = a.forward(torch.tensor(ids, device="cuda"), lens, ca), b.forward(torch.tensor(ids, device="cuda"), lens, cb)
-        assert torch.equal(la, lb) and bool(torch.isfinite(la).all())
-        tok = torch.tensor([5, 6, 7], device="cuda")
-        assert torch.equal(a.forward(tok, [1, 1, 1], ca), b.forward(tok, [1, 1, 1], cb))
+    qu.check_quantise_while_loading(qu.MXFP4, folders)
     # the quantiser on the device gives the CPU's bytes
     w = mo.synth_weights(MODEL, seed=21)["layers.1.feed_forward.w2.weight"]
     pc, sc = _quant().quantize_blocks(w)
@@ -383,27 +307,7 @@ def test_quantise_while_loading_equals_the_quantised_checkpoint(folders):
 def test_generate_on_the_quantised_model(folders):
     """24 greedy steps with the session and the graph on equal step-by-step forward + argmax on the same model - the same
     kernels, so tokens and log-probabilities are bit-equal; every step ran on the launch path."""
-    from mistral_inference.generate import generate
-    h = _hip()
-    model = _load(folders[1], B=1)
-    prompt = PROMPTS[1][0]
-    toks, lps = generate([prompt], model, max_tokens=N_DECODE, temperature=0.0)
-    st = h.decode_engine_status(model._backend._workspace)
-    assert st["engine_launches"] == 0 and st["steps"] >= N_DECODE - 1 and st["status"] == 0, st
-    assert len(toks[0]) == N_DECODE and len(lps[0]) == len(prompt) - 1 + N_DECODE
-    with torch.inference_mode():
-        cache = _cache(1)
-        ids = torch.tensor(prompt, device="cuda")
-        last = model.forward(ids, [len(prompt)], cache)[-1:]
-        tok = last.argmax(-1)
-        lp = torch.log_softmax(last, dim=-1).gather(1, tok[:, None])[:, 0]   # the first sample is drawn by torch in generate()
-        ref_t, ref_lp = [int(tok)], [float(lp)]
-        for _ in range(N_DECODE - 1):
-            tok, lp = h.greedy_sample(model.forward(tok, [1], cache))
-            ref_t.append(int(tok))
-            ref_lp.append(float(lp))
-    assert toks[0] == ref_t
-    assert lps[0][len(prompt) - 1:] == ref_lp
+    qu.check_generate(folders)
 
 
 @pytest.mark.parametrize("T", [4, 12])
@@ -413,24 +317,4 @@ def test_module_level_block_on_mxfp4_linears_against_the_runner(folders, tmp_pat
     bit.  4 rows: the runner's GEMV fuses the RMSNorm and sums its squares in another order, which can move a normalised element
     by one bf16 ulp (test_module_level_block_on_fp8_linears_against_the_runner): at most 2 bf16 ulps at the block output's largest
     magnitude."""
-    import json
-    import safetensors
-    from safetensors.torch import save_file
-    src = folders[1]
-    one = tmp_path / "one"
-    one.mkdir()
-    p = json.load(open(src + "/params.json"))
-    json.dump(dict(p, n_layers=1), open(one / "params.json", "w"))
-    with safetensors.safe_open(src + "/consolidated.safetensors", framework="pt", device="cpu") as f:
-        save_file({k: f.get_tensor(k) for k in f.keys() if not k.startswith("layers.1.")}, str(one / "consolidated.safetensors"))
-    model = _load(str(one), B=1)
-    ids = torch.tensor((PROMPTS[1][0] * 2)[:T], device="cuda")
-    with torch.inference_mode():
-        h, _ = model._run(ids, [T], None, want_logits=True)        # with logits requested, h stays the block stack's output
-        out = model.layers["0"](model.tok_embeddings.weight[ids], model.freqs_cis[torch.arange(T, device="cuda")])
-    assert not torch.equal(out, torch.zeros_like(out))
-    if T > 8:
-        assert torch.equal(out, h), float((out.float() - h.float()).abs().max())
-    else:
-        tol = 2.0 * float(ulp_bf16(h.float().abs().max().cpu()))
-        assert float((out.float() - h.float()).abs().max()) <= tol, (float((out.float() - h.float()).abs().max()), tol)
+    qu.check_module_level_block(folders, tmp_path, T)
