@@ -79,6 +79,22 @@ int mi_kv_write(void* cache_k, void* cache_v, int W, const void* k, const void* 
  * Every entry point that touches a ring takes the layout; all rings of one mi_forward call share it (mi_batch_t.kv_layout). */
 #define MI_KV_SLOT_MAJOR 0
 #define MI_KV_HEAD_MAJOR 1
+/* FP8 K/V rings (additive to ABI v9: the presence of mi_kv_dequant is the feature test).  OR-ed into a layout code: the rings hold
+ * OCP e4m3 bytes (torch.float8_e4m3fn) instead of bf16 elements, same shapes and layouts, no scales.
+ *   write rule  byte = e4m3_rne(clamp(float(x), -448, 448)) of every bf16 x: +-inf saturates to +-448, NaN stays an e4m3 NaN
+ *   read rule   bf16(e4m3(byte)), exact
+ * so that an attention result on an e4m3 ring is, bit for bit, the bf16 kernel's on a bf16 ring holding the dequantised values.
+ * The valid layout codes are 0, 1, 0x10 and 0x11.  With the flag: mi_kv_write takes bf16 rows and writes bytes; mi_attn_decode
+ * reads bytes (the same split geometry and visit order as on bf16 rings); mi_qkv_rope_kvwrite[_w8/_w4] run the GEMV without its
+ * fused ring write, then the e4m3 ring write; mi_attn_prefill returns MI_ERR_UNSUPPORTED (mi_kv_dequant the rings first);
+ * mi_forward / _w8 / _w4 run on such rings (below); mi_forward_generic refuses them.  Scales are not implemented. */
+#define MI_KV_E4M3 0x10
+
+/* e4m3 rings of B sequences -> bf16 rings of the same layout: dst[i] = bf16(e4m3(src[i])) over B * W * n_kv_heads * head_dim
+ * elements each of K and V.  kv_layout: with or without MI_KV_E4M3 (the source is e4m3 either way; an element-wise pass, so the
+ * layout does not enter).  The element count per ring must be a multiple of 16. */
+int mi_kv_dequant(void* dst_k, void* dst_v, const void* src_k, const void* src_v, int W, int B, int n_kv_heads, int head_dim,
+                  int kv_layout, mi_stream_t stream);
 
 /* Epilogues of the dense contractions */
 enum mi_epilogue {
@@ -446,6 +462,16 @@ int mi_forward_w4(const mi_model_t* model, const mi_w4_model_t* w4, const mi_bat
  * Rounding points are the reference's in that dtype (csrc/generic.hip); with MI_DTYPE_FP32 nothing is rounded.  Launch by
  * launch (capturable in a hipGraph by the caller), not tuned to the roofline: BASELINE's configurations are bf16. */
 enum mi_dtype { MI_DTYPE_BF16 = 0, MI_DTYPE_FP16 = 1, MI_DTYPE_FP32 = 2 };
+/* Workspace of mi_forward (quantised == 0) or of mi_forward_w8 / _w4 (quantised != 0) for rings of layout code `kv_layout`.  Without
+ * MI_KV_E4M3 exactly mi_workspace_bytes / mi_workspace_bytes_w8 / _w4.  With it, larger by the prefill scratch of one layer's
+ * dequantised rings - 2 * B * n_kv_heads * max_cache_size * head_dim bf16 elements, rounded up to 256 bytes, behind everything else
+ * - which a forward with MI_KV_E4M3 in mi_batch_t.kv_layout requires.  Such a forward runs, per layer: decode steps of T <= 8 the
+ * q|k|v GEMV without its ring write, mi_kv_write's e4m3 kernel and the decode attention on bytes (one launch more than on bf16
+ * rings); T > 8 the existing ring write call site; prefill with a cache one dequantisation of the layer's rings into the scratch,
+ * the bf16 prefill attention on the scratch, then the e4m3 ring write.  The chunk's own rows are read from the activations,
+ * unrounded; a decode step's own row goes through the ring, rounded (transformer_layers.py:72-81).  The persistent engine declines. */
+size_t mi_workspace_bytes_kv(const mi_model_t* model, int quantised, int T, int B, int max_cache_size, int kv_layout);
+
 size_t mi_workspace_bytes_generic(const mi_model_t* model, int T, int dtype);
 int mi_forward_generic(const mi_model_t* model, const mi_batch_t* batch, int dtype, mi_stream_t stream);
 /* Leaf operators in any storage dtype - what module-level callers of an fp16 / fp32 model bind (the Pixtral tower of

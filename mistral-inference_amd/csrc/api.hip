@@ -5,6 +5,8 @@
 // forward (transformer.py:163-242).  Per decode token and dense layer that is 6 launches:
 //   [RMSNorm + Wq|Wk|Wv GEMV + RoPE + ring write] [split-KV GQA attention] [split combine] [Wo GEMV + residual]
 //   [RMSNorm + W1|W3 GEMV + SiLU*mul] [W2 GEMV + residual]
+// (rings of e4m3 bytes, MI_KV_E4M3: the GEMV without its ring write + the e4m3 ring write = 7 launches, and at prefill one
+// dequantisation of the layer's rings into a scratch in front of the attention)
 // with no host synchronisation and no per-step host metadata (positions come from the device-resident
 // kv_seqlens), so a decode step can also be captured in a hipGraph by the caller.
 #include <hip/hip_runtime.h>
@@ -28,7 +30,9 @@ namespace {
 
 thread_local char g_detail[512] = "";
 
-bool kv_layout_ok(int layout) { return layout == MI_KV_SLOT_MAJOR || layout == MI_KV_HEAD_MAJOR; }
+// a layout code: MI_KV_SLOT_MAJOR / MI_KV_HEAD_MAJOR, alone or with MI_KV_E4M3 (rings of e4m3 bytes)
+bool kv_layout_ok(int layout) { return (layout & ~MI_KV_E4M3) == MI_KV_SLOT_MAJOR || (layout & ~MI_KV_E4M3) == MI_KV_HEAD_MAJOR; }
+bool kv_e4m3(int layout) { return (layout & MI_KV_E4M3) != 0; }
 int fail(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
@@ -96,6 +100,7 @@ bool engine_route(int variant, bool nemo_opt_in, const EngineBuild* slot, const 
   const bool moe = pr.E > 0;
   if (pr.lora_rank > 0) return false;  // un-merged LoRA adapters: no engine build carries them, the launch path does (lora.hip)
   if (pr.quant) return false;          // quantised weight bytes: no engine build reads them, the launch path does (gemv_w8.hip, gemv_w4.hip)
+  if (kv_e4m3(pr.kv_layout)) return false;  // K/V rings of e4m3 bytes: no engine build reads them, the launch path does (attn_decode.hip)
   auto takes = [&](int b) { return kBuilds[b]->applicable(pr, nullptr, 0); };
   if (slot && slot->applicable(pr, nullptr, 0) && try_build(*slot)) return true;
   // the dense GQA-4 headline shapes: the `next` compile (build_native.ENGINE_NEXT_FLAGS)
@@ -155,8 +160,9 @@ struct Workspace {
   bf16_t* lora_t;    // un-merged LoRA (lora_rank > 0 only, behind everything else): t = bf16(A x)   [T, 3 * rank]
   void* lora_base;   // ... and the base products of q|k|v and w1|w3  [T, max(qkv cols, 2 F)]: fp32 holding bf16 values for T <= 8
   bf16_t* deq;       // quantised models at T > 8 (behind everything else, such models only): the dequantised weights of one linear
-  size_t total;      //     group (deq_scratch_elems).  (lora_base: the GEMV's LOGITS form, see lora_linear; bf16 above 8 rows.  Wo's
-};                   //     and W2's base product goes to xn.)
+  bf16_t* kv_deq;    // e4m3 K/V rings (behind everything else, such forwards only): one layer's rings of the batch as bf16, K then V,
+  size_t total;      //     for the prefill attention (kv_scratch_elems).  (deq: deq_scratch_elems.  lora_base: the GEMV's LOGITS form, see
+};                   //     lora_linear; bf16 above 8 rows.  Wo's and W2's base product goes to xn.)
 
 // bf16 elements of the largest linear group a prefill dequantises at once: q|k|v, wo, w1|w3, w2
 size_t deq_scratch_elems(const mi_model_t* m) {
@@ -165,8 +171,11 @@ size_t deq_scratch_elems(const mi_model_t* m) {
   return a > b ? a : b;  // (wo: D * nq <= a; w2: D * F <= b)
 }
 
-// quant: the linears are quantised (any format: the same scratch of one dequantised linear group)
-Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool quant = false) {
+// bf16 elements of ONE dequantised ring (K or V) of B sequences of a layer
+size_t kv_scratch_elems(const mi_model_t* m, int B, int maxW) { return (size_t)B * m->n_kv_heads * maxW * m->head_dim; }
+
+// quant: the linears are quantised (any format: the same scratch of one dequantised linear group); kv8: the rings hold e4m3 bytes
+Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool quant = false, bool kv8 = false) {
   Workspace w;
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -203,6 +212,7 @@ Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool qu
     w.lora_base = take((size_t)T * wide * (T <= GEMV_MAX_T ? 4 : 2));
   }
   w.deq = (quant && T > GEMV_MAX_T) ? (bf16_t*)take(deq_scratch_elems(m) * 2) : nullptr;  // (a plain model: layout and total as ever)
+  w.kv_deq = kv8 ? (bf16_t*)take(2 * kv_scratch_elems(m, B, maxW) * 2) : nullptr;          // (bf16 rings: layout and total as ever)
   w.total = off;
   return w;
 }
@@ -529,6 +539,16 @@ AttnPrefillArgs attn_prefill_args(void* out, const void* qkv, int ld, const void
   return a;
 }
 
+// The ring write of the q|k|v leaves on rings of e4m3 bytes: an e4m3 store in the GEMV epilogue would change every GEMV kernel, so
+// the GEMV runs without its fused write and the k | v columns of its output go through the e4m3 ring-write kernel - every row to
+// slot tok_pos % W of sequence tok_seq (nullptr: the row index), as the fused write does (q_start == nullptr: no window drop).
+int qkv_ring_write_e4m3(const RingWrite& ring, const void* qkv, int ldo, int T, int n_heads, int n_kv_heads, int head_dim,
+                        const int32_t* tok_pos, const int32_t* tok_seq, hipStream_t s) {
+  const bf16_t* k = (const bf16_t*)qkv + (size_t)n_heads * head_dim;
+  return hip_rc(launch_kv_write(ring.k, ring.v, ring.W, k, k + (size_t)n_kv_heads * head_dim, ldo, T, n_kv_heads * head_dim, tok_seq, tok_pos,
+                                nullptr, ring.layout, head_dim, s), "kv_write (e4m3)");
+}
+
 // ---- what mi_forward and mi_forward_generic check of a batch, in the order the checks fire
 struct BatchInfo {
   int T, B, branch, kv_layout;
@@ -643,6 +663,15 @@ int mi_kv_write(void* cache_k, void* cache_v, int W, const void* k, const void* 
   if (!kv_layout_ok(kv_layout) || head_dim <= 0 || head_dim % 8 || kv_dim % head_dim) return fail(MI_ERR_ARG, "mi_kv_write: layout / head_dim");
   return hip_rc(launch_kv_write(cache_k, cache_v, W, k, v, ld, T, kv_dim, tok_seq, tok_pos, q_start, kv_layout, head_dim,
                                 (hipStream_t)stream), "kv_write");
+}
+
+int mi_kv_dequant(void* dst_k, void* dst_v, const void* src_k, const void* src_v, int W, int B, int n_kv_heads, int head_dim,
+                  int kv_layout, mi_stream_t stream) {
+  if (!dst_k || !dst_v || !src_k || !src_v || W <= 0 || B <= 0 || n_kv_heads <= 0 || head_dim <= 0 || !kv_layout_ok(kv_layout))
+    return fail(MI_ERR_ARG, "mi_kv_dequant");
+  const size_t n = (size_t)B * W * n_kv_heads * head_dim;
+  if (n % 16) return fail(MI_ERR_SHAPE, "mi_kv_dequant: %zu elements per ring, not a multiple of 16", n);
+  return hip_rc(launch_kv_dequant(dst_k, dst_v, src_k, src_v, n, (hipStream_t)stream), "kv_dequant");
 }
 
 int mi_linear(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
@@ -830,6 +859,8 @@ int mi_attn_prefill(void* out, const void* qkv, int ld, const void* cache_k, con
                     const int32_t* kv_before, int causal, float softmax_scale, int kv_layout, mi_stream_t stream) {
   if (!out || !qkv || B <= 0 || max_q_len <= 0 || W <= 0 || !kv_layout_ok(kv_layout)) return fail(MI_ERR_ARG, "mi_attn_prefill");
   if (causal && (!q_start || !kv_before)) return fail(MI_ERR_ARG, "mi_attn_prefill: metadata");
+  if (kv_e4m3(kv_layout))
+    return fail(MI_ERR_UNSUPPORTED, "mi_attn_prefill: rings of e4m3 bytes (MI_KV_E4M3) are not read here; mi_kv_dequant them into bf16 rings first");
   if (head_dim != 128) return fail(MI_ERR_SHAPE, "head_dim must be 128");
   // the kernel forms 32-bit element offsets inside one ring (W * kv_dim) and inside the activation matrix (rows * ld)
   if ((size_t)W * n_kv_heads * head_dim >= (1ull << 31) || (size_t)B * max_q_len * (size_t)ld >= (1ull << 31))
@@ -863,9 +894,11 @@ int mi_qkv_rope_kvwrite(void* qkv, int ldo, const void* x, int ldx, int T, int D
     return fail(MI_ERR_UNSUPPORTED, "mi_qkv_rope_kvwrite: T = %d > %d (the prefill path is mi_rmsnorm + mi_linear + "
                 "mi_rope_inplace + mi_kv_write)", T, GEMV_MAX_T);
   const RingWrite ring = {cache_k, cache_v, W, kv_layout};
+  const bool fused_write = cache_k && !kv_e4m3(kv_layout);
   const GemvArgs a = gemv_qkv_rope(x, ldx, D, norm_w, eps, wq, wk, wv, n_heads * head_dim, n_kv_heads * head_dim, qkv, ldo, rope_cs,
-                                   tok_pos, tok_seq, head_dim, cache_k ? &ring : nullptr);
-  return gemv_passes(kGemvBf16, a, T, (hipStream_t)stream, "qkv gemv");
+                                   tok_pos, tok_seq, head_dim, fused_write ? &ring : nullptr);
+  MI_TRY(gemv_passes(kGemvBf16, a, T, (hipStream_t)stream, "qkv gemv"));
+  return (cache_k && !fused_write) ? qkv_ring_write_e4m3(ring, qkv, ldo, T, n_heads, n_kv_heads, head_dim, tok_pos, tok_seq, (hipStream_t)stream) : MI_OK;
 }
 
 /* weight-only FP8 leaves (include/mistral_hip.h: MI_W8_FP8_E4M3) */
@@ -938,9 +971,11 @@ static int qkv_rope_kvwrite_quant(void* qkv, int ldo, const void* x, int ldx, in
     return fail(MI_ERR_UNSUPPORTED, "%s: T = %d > %d (the prefill path is mi_rmsnorm + %s + mi_rope_inplace + mi_kv_write)", me, T, GEMV_MAX_T,
                 Q::kLinear);
   const RingWrite ring = {cache_k, cache_v, W, kv_layout};
+  const bool fused_write = cache_k && !kv_e4m3(kv_layout);
   const GemvArgs a = gemv_qkv_rope(x, ldx, D, norm_w, eps, wq, wk, wv, n_heads * head_dim, n_kv_heads * head_dim, qkv, ldo, rope_cs,
-                                   tok_pos, tok_seq, head_dim, cache_k ? &ring : nullptr);
-  return gemv_passes_quant<Q>(a, Scales<typename Q::scale_t>{{sq, sk, sv}}, T, (hipStream_t)stream, Q::kQkvGemv);
+                                   tok_pos, tok_seq, head_dim, fused_write ? &ring : nullptr);
+  MI_TRY(gemv_passes_quant<Q>(a, Scales<typename Q::scale_t>{{sq, sk, sv}}, T, (hipStream_t)stream, Q::kQkvGemv));
+  return (cache_k && !fused_write) ? qkv_ring_write_e4m3(ring, qkv, ldo, T, n_heads, n_kv_heads, head_dim, tok_pos, tok_seq, (hipStream_t)stream) : MI_OK;
 }
 
 extern "C" {
@@ -1122,6 +1157,11 @@ size_t mi_workspace_bytes_w4(const mi_model_t* model, const mi_w4_model_t* w4, i
   return workspace_bytes_quant(model, w4 != nullptr, T, B, max_cache_size);
 }
 
+size_t mi_workspace_bytes_kv(const mi_model_t* model, int quantised, int T, int B, int max_cache_size, int kv_layout) {
+  if (!model || T <= 0 || B <= 0 || !kv_layout_ok(kv_layout)) return 0;
+  return carve(model, T, B, max_cache_size > 0 ? max_cache_size : 1, nullptr, quantised != 0, kv_e4m3(kv_layout)).total;
+}
+
 // what a quantised model must be, by name, before any launch
 static int check_quant(const char* entry, const mi_model_t* m, const QuantModel& q) {
   return with_format(q.entry_format, [&](auto Q) {
@@ -1146,9 +1186,10 @@ static int forward_body(const char* entry, const mi_model_t* m, const QuantModel
   int maxW = 1;
   if (bi.has_cache)
     for (int l = 0; l < m->n_layers; ++l) maxW = bt->cache_sizes[l] > maxW ? bt->cache_sizes[l] : maxW;
-  const Workspace ws = carve(m, bi.T, bi.B, maxW, (char*)bt->workspace, q != nullptr);
+  const bool kv8 = bi.has_cache && kv_e4m3(bi.kv_layout);  // rings of e4m3 bytes: written by the e4m3 ring-write kernel only
+  const Workspace ws = carve(m, bi.T, bi.B, maxW, (char*)bt->workspace, q != nullptr, kv8);
   MI_TRY(check_workspace_and_sample(entry, bt, ws.total, &bi));
-  const int T = bi.T, B = bi.B, branch = bi.branch, kvl = bi.kv_layout;
+  const int T = bi.T, B = bi.B, branch = bi.branch, kvl = bi.kv_layout;  // (kvl keeps MI_KV_E4M3: the ring write and the decode attention pick their e4m3 kernels by it)
   const bool has_cache = bi.has_cache, want_greedy = bi.want_sample, want_topp = bi.want_topp;
   hipStream_t s = (hipStream_t)stream;
 
@@ -1273,8 +1314,10 @@ static int forward_body(const char* entry, const mi_model_t* m, const QuantModel
     } else if (gemv) {
       const RingWrite ring = {ck, cv, W, kvl};
       MI_TRY(run(gemv_qkv_rope(h, D, D, L.attention_norm, m->norm_eps, L.wq, L.wk, L.wv, nq, nkv, ws.qkv, qkv_cols, m->rope_cs, bt->tok_pos,
-                               bt->tok_seq, Dh, branch == MI_BRANCH_DECODE ? &ring : nullptr),
+                               bt->tok_seq, Dh, (branch == MI_BRANCH_DECODE && !kv8) ? &ring : nullptr),
                  Lins{{LIN_WQ, LIN_WK, LIN_WV}}, "qkv gemv"));
+      // e4m3 rings: the GEMV epilogue stores bf16 only - the step's rows go through the ring-write kernel (one launch more per layer)
+      if (branch == MI_BRANCH_DECODE && kv8) MI_TRY(kv_write("kv_write (decode, e4m3)"));
     } else {
       MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, L.attention_norm, T, D, m->norm_eps, s), "attention_norm"));
       const void* wqkv[3] = {L.wq, L.wk, L.wv};
@@ -1300,7 +1343,15 @@ static int forward_body(const char* entry, const mi_model_t* m, const QuantModel
       const AttnDecodeArgs a = attn_decode_args(ws.attn, ws.qkv, qkv_cols, ck, cv, kvl, W, B, H, Hkv, Dh, bt->tok_pos, ws.tickets, ws.partial);
       MI_TRY(hip_rc(launch_attn_decode(a, s), "attn_decode"));
     } else {
-      const AttnPrefillArgs a = attn_prefill_args(ws.attn, ws.qkv, qkv_cols, ck, cv, kvl, has_cache ? W : T, B, has_cache ? bt->max_q_len : T,
+      // e4m3 rings: the keys older than this forward are read from the bf16 image of the layer's rings in the scratch (exact); the
+      // chunk's own rows come from the activations, unrounded, as ever (transformer_layers.py:72-76)
+      const void *pk = ck, *pv = cv;
+      if (kv8) {
+        const size_t n = (size_t)B * Hkv * W * Dh;
+        pk = ws.kv_deq; pv = ws.kv_deq + n;
+        MI_TRY(hip_rc(launch_kv_dequant(ws.kv_deq, ws.kv_deq + n, ck, cv, n, s), "kv_dequant"));
+      }
+      const AttnPrefillArgs a = attn_prefill_args(ws.attn, ws.qkv, qkv_cols, pk, pv, kvl & 1, has_cache ? W : T, B, has_cache ? bt->max_q_len : T,
                                                   H, Hkv, Dh, bt->q_start, bt->kv_before, has_cache ? 1 : 0, 0.f);
       MI_TRY(hip_rc(launch_attn_prefill(a, s), "attn_prefill"));
       if (has_cache) MI_TRY(kv_write("kv_write"));
@@ -1537,6 +1588,9 @@ int mi_forward_generic(const mi_model_t* m, const mi_batch_t* bt, int dtype, mi_
   const size_t es = g_elem_bytes(dt);
   BatchInfo bi;
   MI_TRY(check_batch("mi_forward_generic", m, bt, false, &bi));
+  if (kv_e4m3(bi.kv_layout))
+    return fail(MI_ERR_UNSUPPORTED, "mi_forward_generic: K/V rings of e4m3 bytes (MI_KV_E4M3) are not implemented for fp16 / fp32 storage or "
+                "on the generic route; use rings of the model's dtype");
   const GWorkspace ws = carve_generic(m, bi.T, es, (char*)bt->workspace);
   MI_TRY(check_workspace_and_sample("mi_forward_generic", bt, ws.total, &bi));
   const int T = bi.T, B = bi.B, branch = bi.branch, kvl = bi.kv_layout;

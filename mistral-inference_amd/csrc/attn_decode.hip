@@ -15,11 +15,43 @@
 #include <cstdlib>
 
 #include "attn_decode_core.cuh"
+#include "gemv_core.cuh"  // cvt4_e4m3: e4m3 bytes -> exact bf16 pairs
 #include "kernels.h"
 
 namespace {
 
 using namespace attn_core;
+
+// The ring element (MI_KV_E4M3, include/mistral_hip.h): this file is compiled twice (build_native.py) - for bf16 rings, and with
+// -DATTN_KV_E4M3=1 (attn_decode_e4m3.o) for rings of e4m3 bytes, which exports launch_attn_decode_e4m3 and nothing else; the bf16
+// compile keeps the code objects it had before the second one existed.  A lane's piece of a ring row is its 8 head dims: 16 bytes
+// of a bf16 ring, 8 bytes of an e4m3 ring, which expand - exactly, every e4m3 value is a bf16 value - to the four bf16 pair words
+// that reduce_slot takes.  Everything else (split geometry, slot-to-lane-group mapping, ascending visit order, the arithmetic) is shared, so the
+// result on an e4m3 ring is bit for bit the result on a bf16 ring holding the dequantised values.
+#ifndef ATTN_KV_E4M3
+#define ATTN_KV_E4M3 0
+#endif
+#if !ATTN_KV_E4M3
+typedef bf16_t ring_t;
+struct Row {
+  typedef u32x4 raw;
+  static __device__ __forceinline__ raw load(const bf16_t* p) { return ld16_nt(p); }
+  static __device__ __forceinline__ u32x4 pairs(raw r) { return r; }
+};
+#else
+typedef uint8_t ring_t;
+struct Row {
+  typedef u32x2 raw;
+  static __device__ __forceinline__ raw load(const uint8_t* p) { return __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p)); }
+  static __device__ __forceinline__ u32x4 pairs(raw r) {
+    uint32_t p[4];
+    gemv_core::cvt4_e4m3(r[0], p[0], p[1]);
+    gemv_core::cvt4_e4m3(r[1], p[2], p[3]);
+    return u32x4{p[0], p[1], p[2], p[3]};
+  }
+};
+#endif
+typedef Row::raw raw_t;
 
 // SMALL (round 5, batches of >= 3 sequences - mistral-demo decodes three): the kernel sits at 170 VGPRs = 2 blocks per CU, so
 // 3 x 256 blocks ran as 1.5 rounds of the grid (20.7 us per layer against 9.0 at batch 1).  With half-size load sets (UK = 2:
@@ -61,8 +93,8 @@ __global__ __launch_bounds__(256, SMALL ? 3 : 1) void attn_decode_kernel(AttnDec
   const int hkv_real = a.Hkv / a.kv_groups;
   const size_t row_stride = a.kv_layout ? (size_t)DH : (size_t)hkv_real * DH;
   const size_t ring0 = kv_offset(a.kv_layout, a.W, hkv_real * DH, DH, (size_t)b, 0, kv_real * DH) + dl * 8;
-  const bf16_t* kbase = a.cache_k + ring0;
-  const bf16_t* vbase = a.cache_v + ring0;
+  const ring_t* kbase = reinterpret_cast<const ring_t*>(a.cache_k) + ring0;
+  const ring_t* vbase = reinterpret_cast<const ring_t*>(a.cache_v) + ring0;
 
   // Each lane group walks slots s_begin + wid*4 + g + 16*j, UK slots (K and V rows = 2*UK loads) per step, two
   // steps in flight (ping-pong register sets A/B refilled in place, 16 KiB per wave outstanding): the kernel is pure
@@ -71,22 +103,22 @@ __global__ __launch_bounds__(256, SMALL ? 3 : 1) void attn_decode_kernel(AttnDec
   const int s_first = s_begin + wid * 4 + g;
   const int s_clamp = max(kv_len - 1, 0);
   const int n_steps = (s_end > s_begin) ? (s_end - s_begin + 16 * UK - 1) / (16 * UK) : 0;  // block-uniform
-  u32x4 setA[2 * UK], setB[2 * UK];  // [0, UK): K rows, [UK, 2UK): V rows
+  raw_t setA[2 * UK], setB[2 * UK];  // [0, UK): K rows, [UK, 2UK): V rows
   // ALWAYS exactly 2*UK unconditional loads (slots past the block's range are clamped to a valid slot and masked in
   // reduce_step): no branch around a load, so hipcc's wait for one set leaves the other set's loads in flight.
-  auto load_step = [&](int it, u32x4 (&kv)[2 * UK]) {
+  auto load_step = [&](int it, raw_t (&kv)[2 * UK]) {
     const int s0 = s_first + it * 16 * UK;
 #pragma unroll
     for (int u = 0; u < UK; ++u) {
       const int sl = min(s0 + 16 * u, s_clamp);
-      kv[u] = ld16_nt(kbase + (size_t)sl * row_stride);
-      kv[UK + u] = ld16_nt(vbase + (size_t)sl * row_stride);
+      kv[u] = Row::load(kbase + (size_t)sl * row_stride);
+      kv[UK + u] = Row::load(vbase + (size_t)sl * row_stride);
     }
   };
-  auto reduce_step = [&](int it, const u32x4 (&kv)[2 * UK]) {
+  auto reduce_step = [&](int it, const raw_t (&kv)[2 * UK]) {
     const int s0 = s_first + it * 16 * UK;
 #pragma unroll
-    for (int u = 0; u < UK; ++u) reduce_slot<R>(st, qf, kv[u], kv[UK + u], (s0 + 16 * u) < s_end);
+    for (int u = 0; u < UK; ++u) reduce_slot<R>(st, qf, Row::pairs(kv[u]), Row::pairs(kv[UK + u]), (s0 + 16 * u) < s_end);
   };
   // Two sets in flight.  Steps beyond n_steps reduce nothing (every slot is masked).
   load_step(0, setA);
@@ -148,16 +180,16 @@ __global__ __launch_bounds__(256, 3) void attn_decode_allin_kernel(AttnDecodeArg
   const int hkv_real = a.Hkv / a.kv_groups;
   const size_t row_stride = a.kv_layout ? (size_t)DH : (size_t)hkv_real * DH;
   const size_t ring0 = kv_offset(a.kv_layout, a.W, hkv_real * DH, DH, (size_t)b, 0, kv_real * DH) + dl * 8;
-  const bf16_t* kbase = a.cache_k + ring0;
-  const bf16_t* vbase = a.cache_v + ring0;
+  const ring_t* kbase = reinterpret_cast<const ring_t*>(a.cache_k) + ring0;
+  const ring_t* vbase = reinterpret_cast<const ring_t*>(a.cache_v) + ring0;
   const int s_first = s_begin + wid * 4 + g;
   const int s_clamp = max(kv_len - 1, 0);
-  u32x4 kk[NS], vv[NS];  // ALWAYS 2 * NS unconditional loads (slots past the block's range: clamped, masked below)
+  raw_t kk[NS], vv[NS];  // ALWAYS 2 * NS unconditional loads (slots past the block's range: clamped, masked below)
 #pragma unroll
   for (int j = 0; j < NS; ++j) {
     const int sl = min(s_first + 16 * j, s_clamp);
-    kk[j] = ld16_nt(kbase + (size_t)sl * row_stride);
-    vv[j] = ld16_nt(vbase + (size_t)sl * row_stride);
+    kk[j] = Row::load(kbase + (size_t)sl * row_stride);
+    vv[j] = Row::load(vbase + (size_t)sl * row_stride);
   }
 #pragma unroll
   for (int rp = 0; rp < R; rp += 2) {
@@ -172,7 +204,7 @@ __global__ __launch_bounds__(256, 3) void attn_decode_allin_kernel(AttnDecodeArg
     State<2> st;
     init_state<2>(st);
 #pragma unroll
-    for (int j = 0; j < NS; ++j) reduce_slot<2>(st, qf, kk[j], vv[j], (s_first + 16 * j) < s_end);
+    for (int j = 0; j < NS; ++j) reduce_slot<2>(st, qf, Row::pairs(kk[j]), Row::pairs(vv[j]), (s_first + 16 * j) < s_end);
     wave_state_to_lds_heads<2, R>(st, wid, lane, rp, sm_m, sm_l, sm_acc);
   }
   __syncthreads();
@@ -237,6 +269,7 @@ combine:
 
 }  // namespace
 
+#if !ATTN_KV_E4M3
 int attn_decode_splits(int W) {
   static int slots = 0;  // minimum ring slots per block; MI_ATTN_SPLIT_SLOTS overrides (tuning)
   if (slots == 0) {
@@ -264,12 +297,21 @@ int attn_decode_group(int R) {
   return 1;
 }
 
+#endif  // !ATTN_KV_E4M3
+
+// kv_layout with MI_KV_E4M3: the e4m3 compile's launcher (the same choice of form on the same geometry)
+#if ATTN_KV_E4M3
+hipError_t launch_attn_decode_e4m3(const AttnDecodeArgs& a_in, hipStream_t s) {
+#else
 hipError_t launch_attn_decode(const AttnDecodeArgs& a_in, hipStream_t s) {
+  if (a_in.kv_layout & MI_KV_E4M3) return launch_attn_decode_e4m3(a_in, s);
+#endif
   if (a_in.Dh != DH || a_in.H % a_in.Hkv != 0) return hipErrorInvalidValue;
   AttnDecodeArgs a = a_in;
   const int R = attn_decode_group(a.H / a.Hkv);
   a.kv_groups = (a.H / a.Hkv) / R;
   a.Hkv = a_in.Hkv * a.kv_groups;
+  a.kv_layout = a_in.kv_layout & 1;  // the kernels index with the layout bit
   switch (R) {
     case 1: launch_r<1>(a, s); break;
     case 2: launch_r<2>(a, s); break;

@@ -46,6 +46,11 @@ __device__ __forceinline__ float dot2_bf16(uint32_t a, uint32_t b, float acc) {
 #define MI_KV_SLOT_MAJOR 0
 #define MI_KV_HEAD_MAJOR 1
 #endif
+// OR-ed into a layout code: the rings hold OCP e4m3 bytes, no scales (include/mistral_hip.h).  Every kernel indexes with
+// `layout & 1`; the flag picks the kernel on the host.
+#ifndef MI_KV_E4M3
+#define MI_KV_E4M3 0x10
+#endif
 // element offset of (sequence, slot, column c = kv_head * head_dim + d) inside a ring of W slots
 __host__ __device__ __forceinline__ size_t kv_offset(int layout, int W, int kv_dim, int Dh, size_t seq, int slot, int c) {
   return layout ? ((seq * (size_t)(kv_dim / Dh) + (size_t)(c / Dh)) * (size_t)W + (size_t)slot) * (size_t)Dh + (size_t)(c % Dh)

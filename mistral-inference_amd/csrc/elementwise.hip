@@ -1,5 +1,6 @@
 // Memory-bound elementwise / row kernels of the hot path.  All bf16 traffic is 16 bytes per lane.
 #include "common.cuh"
+#include "gemv_core.cuh"  // cvt4_e4m3: e4m3 bytes -> exact bf16 pairs
 #include "kernels.h"
 
 namespace {
@@ -109,6 +110,68 @@ __global__ __launch_bounds__(256) void kv_write_kernel(bf16_t* ck, bf16_t* cv, i
   const size_t off = kv_offset(layout, W, kv_dim, Dh, (size_t)b, tok_pos[t] % W, p * 8);  // (Dh % 8 == 0: a piece stays inside a head)
   st16(ck + off, ld16(k + (size_t)t * ld + p * 8));
   st16(cv + off, ld16(v + (size_t)t * ld + p * 8));
+}
+
+// ---- FP8 K/V rings (include/mistral_hip.h: MI_KV_E4M3).  Write rule: byte = e4m3_rne(clamp(float(x), -448, 448)), a NaN stays a
+// NaN - in torch x.float().clamp(-448, 448).to(torch.float8_e4m3fn), mistral_inference.cache.kv_quantize.
+// v_max / v_min drop a NaN operand (IEEE maxNum), so the NaN code (0x7f under the input's sign, what torch's cast gives) is set
+// on the converted bytes.
+__device__ __forceinline__ float kv8_clamp(float x) { return fminf(fmaxf(x, -448.f), 448.f); }
+__device__ __forceinline__ uint32_t kv8_nan_fix(uint32_t w, uint32_t pair, int byte) {
+  const uint32_t lo = pair << 16, hi = pair & 0xffff0000u;  // the two bf16 values as fp32 bits
+  if ((lo & 0x7fffffffu) > 0x7f800000u) w = (w & ~(0xffu << (8 * byte))) | ((0x7fu | (lo >> 24 & 0x80u)) << (8 * byte));
+  if ((hi & 0x7fffffffu) > 0x7f800000u) w = (w & ~(0xff00u << (8 * byte))) | ((0x7f00u | (hi >> 16 & 0x8000u)) << (8 * byte));
+  return w;
+}
+// eight bf16 (four pair words) -> eight e4m3 bytes
+__device__ __forceinline__ u32x2 kv8_pack(u32x4 v) {
+  u32x2 o;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const uint32_t p0 = v[2 * i], p1 = v[2 * i + 1];
+    int w = __builtin_amdgcn_cvt_pk_fp8_f32(kv8_clamp(bf_lo(p0)), kv8_clamp(bf_hi(p0)), 0, false);
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(kv8_clamp(bf_lo(p1)), kv8_clamp(bf_hi(p1)), w, true);
+    o[i] = kv8_nan_fix(kv8_nan_fix((uint32_t)w, p0, 0), p1, 2);
+  }
+  return o;
+}
+// kv_write_kernel with e4m3 rings: 16 bytes in, 8 bytes out per lane; the same window-drop rule
+__global__ __launch_bounds__(256) void kv_write_e4m3_kernel(uint8_t* ck, uint8_t* cv, int W, const bf16_t* k, const bf16_t* v,
+                                                            int ld, int T, int kv_dim, const int32_t* tok_seq,
+                                                            const int32_t* tok_pos, const int32_t* q_start, int layout, int Dh) {
+  const int pieces = kv_dim >> 3;
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (long)T * pieces) return;
+  const int t = (int)(gid / pieces), p = (int)(gid % pieces);
+  const int b = tok_seq ? tok_seq[t] : t;
+  if (q_start) {  // (nullptr: every row is stored - the q|k|v leaves, whose fused write has no window rule either)
+    const int i = t - q_start[b];
+    const int s = q_start[b + 1] - q_start[b];
+    if (i < s - W) return;  // to_cache_mask: only the last W tokens of the chunk are stored
+  }
+  const size_t off = kv_offset(layout, W, kv_dim, Dh, (size_t)b, tok_pos[t] % W, p * 8);  // in elements = bytes; a multiple of 8
+  *reinterpret_cast<u32x2*>(ck + off) = kv8_pack(ld16(k + (size_t)t * ld + p * 8));
+  *reinterpret_cast<u32x2*>(cv + off) = kv8_pack(ld16(v + (size_t)t * ld + p * 8));
+}
+
+// e4m3 rings -> bf16 rings, element by element (the layout does not enter): one 16-byte load and two 16-byte stores per lane
+// and ring; blockIdx.y picks K or V.  n16: 16-element pieces per ring.
+__global__ __launch_bounds__(256) void kv_dequant_kernel(bf16_t* dk, bf16_t* dv, const uint8_t* sk, const uint8_t* sv, size_t n16) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n16) return;
+  const uint8_t* src = (blockIdx.y ? sv : sk) + idx * 16;
+  bf16_t* dst = (blockIdx.y ? dv : dk) + idx * 16;
+  const u32x4 w = ld16_nt(src);
+  u32x4 o[2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    uint32_t p01, p23;
+    gemv_core::cvt4_e4m3(w[i], p01, p23);
+    o[i >> 1][2 * (i & 1)] = p01;
+    o[i >> 1][2 * (i & 1) + 1] = p23;
+  }
+  st16(dst, o[0]);
+  st16(dst + 8, o[1]);
 }
 
 // Decode step metadata from the device-resident kv_seqlens (no host round trip), then
@@ -498,8 +561,21 @@ hipError_t launch_kv_write(void* ck, void* cv, int W, const void* k, const void*
                            const int32_t* tok_seq, const int32_t* tok_pos, const int32_t* q_start, int kv_layout, int Dh, hipStream_t s) {
   if (Dh <= 0 || Dh % 8 || kv_dim % Dh) return hipErrorInvalidValue;
   const long n = (long)T * (kv_dim >> 3);
+  if (kv_layout & MI_KV_E4M3) {
+    hipLaunchKernelGGL(kv_write_e4m3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (uint8_t*)ck, (uint8_t*)cv, W,
+                       (const bf16_t*)k, (const bf16_t*)v, ld, T, kv_dim, tok_seq, tok_pos, q_start, kv_layout & 1, Dh);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(kv_write_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (bf16_t*)ck, (bf16_t*)cv, W,
                      (const bf16_t*)k, (const bf16_t*)v, ld, T, kv_dim, tok_seq, tok_pos, q_start, kv_layout, Dh);
+  return hipGetLastError();
+}
+hipError_t launch_kv_dequant(void* dk, void* dv, const void* sk, const void* sv, size_t n_elems, hipStream_t s) {
+  if (n_elems % 16) return hipErrorInvalidValue;
+  const size_t n16 = n_elems / 16;
+  if (n16 == 0) return hipSuccess;
+  hipLaunchKernelGGL(kv_dequant_kernel, dim3((unsigned)((n16 + 255) / 256), 2), dim3(256), 0, s, (bf16_t*)dk, (bf16_t*)dv,
+                     (const uint8_t*)sk, (const uint8_t*)sv, n16);
   return hipGetLastError();
 }
 hipError_t launch_decode_prep(int64_t* kv_seqlens, int32_t* q_start, int32_t* kv_before, int32_t* tok_seq,

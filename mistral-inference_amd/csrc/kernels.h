@@ -149,7 +149,7 @@ struct AttnDecodeArgs {
   int ldq;
   const bf16_t* cache_k;  // [maxB, W, Hkv*Dh] (kv_layout 0) or [maxB, Hkv, W, Dh] (1)
   const bf16_t* cache_v;
-  int kv_layout;
+  int kv_layout;           // with MI_KV_E4M3: cache_k / cache_v point to e4m3 bytes (launch_attn_decode picks the instantiation)
   int W, B, H, Hkv, Dh;    // Hkv: kv heads AS SCHEDULED = real kv heads x kv_groups (launch_attn_decode sets both)
   int kv_groups;           // query-head groups per real kv head (1 unless the GQA ratio is split, see launch_attn_decode)
   const int32_t* tok_pos;  // [B]
@@ -161,6 +161,7 @@ int attn_decode_splits(int W);
 int attn_decode_group(int R);  // query heads served per block: the largest of {8, 6, 4, 2, 1} dividing the GQA ratio
 size_t attn_decode_partial_floats(int B, int H, int Hkv, int Dh, int W);
 hipError_t launch_attn_decode(const AttnDecodeArgs& a, hipStream_t s);
+hipError_t launch_attn_decode_e4m3(const AttnDecodeArgs& a, hipStream_t s);  // attn_decode.hip compiled with -DATTN_KV_E4M3=1
 
 struct AttnPrefillArgs {
   void* out;            // [T, H*Dh]
@@ -224,6 +225,9 @@ hipError_t launch_rope(void* qkv, int ld, int T, int H, int Hkv, int Dh, const f
                        hipStream_t s);
 hipError_t launch_kv_write(void* ck, void* cv, int W, const void* k, const void* v, int ld, int T, int kv_dim,
                            const int32_t* tok_seq, const int32_t* tok_pos, const int32_t* q_start, int kv_layout, int Dh, hipStream_t s);
+// kv_layout with MI_KV_E4M3 (launch_kv_write): bf16 rows in, e4m3 bytes to the ring.  launch_kv_dequant: n_elems e4m3 bytes of
+// each of sk / sv -> bf16 in dk / dv (n_elems % 16 == 0)
+hipError_t launch_kv_dequant(void* dk, void* dv, const void* sk, const void* sv, size_t n_elems, hipStream_t s);
 // engine_ctrl (nullable): control words of the workspace - CTRL_EPOCH and CTRL_STEPS are incremented here, CTRL_ABORT is cleared
 // here, CTRL_BAD_ID receives the out-of-range token id flag (launch_embedding)
 hipError_t launch_decode_prep(int64_t* kv_seqlens, int32_t* q_start, int32_t* kv_before, int32_t* tok_seq,

@@ -146,6 +146,9 @@ _SIGS = {
                                          C.c_int, _vp, C.c_float, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp]),
     "mi_workspace_bytes_w4": (C.c_size_t, [C.POINTER(MiModel), C.POINTER(MiW4Model), C.c_int, C.c_int, C.c_int]),
     "mi_forward_w4": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiW4Model), C.POINTER(MiBatch), _vp]),
+    # FP8 K/V rings (additive likewise): MI_KV_E4M3 in a layout code
+    "mi_kv_dequant": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "mi_workspace_bytes_kv": (C.c_size_t, [C.POINTER(MiModel), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "mi_workspace_bytes_generic": (C.c_size_t, [C.POINTER(MiModel), C.c_int, C.c_int]),  # ABI v6
     "mi_forward_generic": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiBatch), C.c_int, _vp]),
     "mi_embedding_generic": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
@@ -461,6 +464,8 @@ def rope_inplace(qkv: torch.Tensor, n_heads: int, n_kv_heads: int, head_dim: int
 
 
 KV_SLOT_MAJOR, KV_HEAD_MAJOR = 0, 1  # include/mistral_hip.h: MI_KV_SLOT_MAJOR / MI_KV_HEAD_MAJOR
+KV_E4M3 = 0x10                       # MI_KV_E4M3, OR-ed into a layout code: the rings hold e4m3 bytes (torch.float8_e4m3fn)
+KV_RING_DTYPES = (torch.bfloat16, torch.float8_e4m3fn)
 
 
 def kv_layout_of(ring: torch.Tensor) -> int:
@@ -478,9 +483,38 @@ def kv_layout_of(ring: torch.Tensor) -> int:
                      "permuted view of a contiguous [B, H, W, D] tensor")
 
 
+def kv_layout_code(ring: torch.Tensor) -> int:
+    """`kv_layout_of` plus KV_E4M3 for a ring of e4m3 bytes: the layout code the entry points take."""
+    return kv_layout_of(ring) | (KV_E4M3 if ring.dtype == torch.float8_e4m3fn else 0)
+
+
 def _kv_layout2(cache_k: torch.Tensor, cache_v: torch.Tensor) -> int:
     assert cache_k.shape == cache_v.shape and cache_k.stride() == cache_v.stride(), "cache_k and cache_v must share shape and layout"
-    return kv_layout_of(cache_k)
+    assert cache_k.dtype == cache_v.dtype, "cache_k and cache_v must share a dtype"
+    return kv_layout_code(cache_k)
+
+
+def ring_ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    """`dev_ptr` of a K/V ring: bf16 elements or e4m3 bytes (the one place an e4m3 tensor is taken for activations' company)."""
+    if t is not None and t.dtype not in KV_RING_DTYPES:
+        raise RuntimeError(f"K/V ring: expected {' or '.join(str(d) for d in KV_RING_DTYPES)}, got {t.dtype}")
+    return dev_ptr(t, None)
+
+
+def kv_dequant(cache_k: torch.Tensor, cache_v: torch.Tensor):
+    """bf16 rings of the same shape and layout holding the values of two e4m3 rings (mi_kv_dequant; exact)."""
+    assert cache_k.dtype == cache_v.dtype == torch.float8_e4m3fn
+    lay = _kv_layout2(cache_k, cache_v)
+    B, W, H, D = cache_k.shape
+
+    def like(t):
+        if lay & 1:
+            return torch.empty((B, H, W, D), dtype=torch.bfloat16, device=t.device).permute(0, 2, 1, 3)
+        return torch.empty((B, W, H, D), dtype=torch.bfloat16, device=t.device)
+    dk, dv = like(cache_k), like(cache_v)
+    check(lib().mi_kv_dequant(dev_ptr(dk), dev_ptr(dv), ring_ptr(cache_k), ring_ptr(cache_v), W, B, H, D, lay,
+                              stream_ptr(cache_k.device)), "mi_kv_dequant")
+    return dk, dv
 
 
 def kv_write(cache_k: torch.Tensor, cache_v: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tok_seq: torch.Tensor,
@@ -488,7 +522,7 @@ def kv_write(cache_k: torch.Tensor, cache_v: torch.Tensor, k: torch.Tensor, v: t
     W = cache_k.shape[1]
     kv_dim = cache_k.shape[2] * cache_k.shape[3]
     assert k.stride(0) == v.stride(0)
-    check(lib().mi_kv_write(dev_ptr(cache_k), dev_ptr(cache_v), W, dev_ptr(k), dev_ptr(v), k.stride(0), k.shape[0], kv_dim,
+    check(lib().mi_kv_write(ring_ptr(cache_k), ring_ptr(cache_v), W, dev_ptr(k), dev_ptr(v), k.stride(0), k.shape[0], kv_dim,
                             dev_ptr(tok_seq, torch.int32), dev_ptr(tok_pos, torch.int32), dev_ptr(q_start, torch.int32),
                             _kv_layout2(cache_k, cache_v), cache_k.shape[3], stream_ptr(k.device)), "mi_kv_write")
 
@@ -505,7 +539,7 @@ def attn_decode(q: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor, n
     if key not in _decode_scratch:
         _decode_scratch[key] = torch.zeros(need, dtype=torch.uint8, device=q.device)
     out = torch.empty((B, n_heads * Dh), dtype=q.dtype, device=q.device)
-    check(lib().mi_attn_decode(dev_ptr(out), dev_ptr(q), q.stride(0), dev_ptr(cache_k), dev_ptr(cache_v), W, B, n_heads, Hkv,
+    check(lib().mi_attn_decode(dev_ptr(out), dev_ptr(q), q.stride(0), ring_ptr(cache_k), ring_ptr(cache_v), W, B, n_heads, Hkv,
                                Dh, dev_ptr(tok_pos, torch.int32), dev_ptr(_decode_scratch[key], torch.uint8),
                                _kv_layout2(cache_k, cache_v), stream_ptr(q.device)), "mi_attn_decode")
     return out
@@ -526,6 +560,9 @@ def attn_prefill(qkv: torch.Tensor, n_heads: int, n_kv_heads: int, head_dim: int
                                                  head_dim, float(softmax_scale), _generic_code(qkv.dtype), stream_ptr(qkv.device)),
               "mi_attention_nocache_generic")
         return out
+    if cache_k is not None and cache_k.dtype == torch.float8_e4m3fn:
+        # mi_attn_prefill reads bf16 rings only: the e4m3 rings' exact bf16 image in temporaries (inside mi_forward: in the workspace)
+        cache_k, cache_v = kv_dequant(cache_k, cache_v)
     check(lib().mi_attn_prefill(dev_ptr(out), dev_ptr(qkv), qkv.stride(0), dev_ptr(cache_k), dev_ptr(cache_v), W, B,
                                 max_q_len, n_heads, n_kv_heads, head_dim, dev_ptr(q_start, torch.int32),
                                 dev_ptr(kv_before, torch.int32), 1 if causal else 0, float(softmax_scale),
@@ -613,7 +650,7 @@ def qkv_rope_kvwrite(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv: to
     check(lib().mi_qkv_rope_kvwrite(dev_ptr(out), out.stride(0), dev_ptr(x), x.stride(0), T, D, dev_ptr(wq), dev_ptr(wk),
                                     dev_ptr(wv), nq // head_dim, nkv // head_dim, head_dim, dev_ptr(norm_w), float(eps),
                                     dev_ptr(rope_cs, torch.float32), rope_cs.shape[0], dev_ptr(tok_pos, torch.int32),
-                                    dev_ptr(tok_seq, torch.int32), dev_ptr(cache_k), dev_ptr(cache_v), W,
+                                    dev_ptr(tok_seq, torch.int32), ring_ptr(cache_k), ring_ptr(cache_v), W,
                                     _kv_layout2(cache_k, cache_v) if cache_k is not None else KV_SLOT_MAJOR,
                                     stream_ptr(x.device)), "mi_qkv_rope_kvwrite")
     return out
@@ -632,8 +669,8 @@ def qkv_rope_kvwrite_quant(q: QuantFormat, x, wq, wk, wv, sq, sk, sv, head_dim, 
     check(getattr(lib(), entry)(dev_ptr(out), out.stride(0), dev_ptr(x), x.stride(0), T, D, dev_ptr(ws[0], u8), dev_ptr(ws[1], u8),
                                 dev_ptr(ws[2], u8), dev_ptr(sq, q.scale_dtype), dev_ptr(sk, q.scale_dtype), dev_ptr(sv, q.scale_dtype),
                                 nq // head_dim, nkv // head_dim, head_dim, dev_ptr(norm_w), float(eps), dev_ptr(rope_cs, f32),
-                                rope_cs.shape[0], dev_ptr(tok_pos, torch.int32), dev_ptr(tok_seq, torch.int32), dev_ptr(cache_k),
-                                dev_ptr(cache_v), W, _kv_layout2(cache_k, cache_v) if cache_k is not None else KV_SLOT_MAJOR,
+                                rope_cs.shape[0], dev_ptr(tok_pos, torch.int32), dev_ptr(tok_seq, torch.int32), ring_ptr(cache_k),
+                                ring_ptr(cache_v), W, _kv_layout2(cache_k, cache_v) if cache_k is not None else KV_SLOT_MAJOR,
                                 stream_ptr(x.device)), entry)
     return out
 

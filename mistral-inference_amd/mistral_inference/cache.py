@@ -26,6 +26,43 @@ from . import _hip
 
 SlidingWindow = Union[None, int, List[Optional[int]]]
 
+# ---- FP8 K/V rings (opt-in: BufferCache(..., dtype=torch.float8_e4m3fn); include/mistral_hip.h MI_KV_E4M3).  The two functions
+# below are the written definition of the rule; the ring-write kernel and the tests are held to them.  No scales.
+KV_FP8 = torch.float8_e4m3fn
+KV_FP8_MAX = 448.0
+KV_DTYPES = {"bf16": torch.bfloat16, "fp8_e4m3": KV_FP8}   # names of `--kv_dtype` (mistral-chat / mistral-demo)
+
+
+def kv_quantize(x: torch.Tensor) -> torch.Tensor:
+    """Write rule: byte = e4m3_rne(clamp(float(x), -448, 448)).  +-inf saturates to +-448, NaN stays an e4m3 NaN (torch's bare cast
+    would make NaN of everything beyond 448).  Every result of a finite input is exact in bf16."""
+    return x.float().clamp(-KV_FP8_MAX, KV_FP8_MAX).to(KV_FP8)
+
+
+def kv_dequantize(q: torch.Tensor, dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """Read rule: the value of the byte in `dtype` (exact in bf16, fp16 and fp32)."""
+    assert q.dtype == KV_FP8, q.dtype
+    return q.to(dtype)
+
+
+def kv_dtype_arg(name: Optional[str]) -> Optional[torch.dtype]:
+    """`--kv_dtype` of the command-line tools: None (the model's dtype) or a name of KV_DTYPES; anything else is refused by name."""
+    if name is None:
+        return None
+    if name not in KV_DTYPES:
+        raise NotImplementedError(f"kv_dtype={name!r} is not implemented (the K/V ring dtypes are {', '.join(repr(k) for k in KV_DTYPES)})")
+    return KV_DTYPES[name]
+
+
+def check_kv_dtype(kv_dtype: Optional[torch.dtype], model_dtype: torch.dtype) -> torch.dtype:
+    """`generate(kv_dtype=...)`: None or the model's dtype, or float8_e4m3fn; anything else is refused by name."""
+    if kv_dtype is None or kv_dtype == model_dtype:
+        return model_dtype
+    if kv_dtype != KV_FP8:
+        raise NotImplementedError(f"kv_dtype={kv_dtype} is not implemented (the K/V rings take the model's dtype {model_dtype} or "
+                                  f"{KV_FP8})")
+    return kv_dtype
+
 
 def get_cache_sizes(n_layers: int, max_seq_len: int, sliding_window: SlidingWindow) -> List[int]:
     """Per-layer ring length (reference cache.py:13-24)."""
@@ -120,7 +157,8 @@ class CacheView:
             index += list(range(B * W + row, B * W + row + n))         # then this sequence's new rows
             row += n
         idx = torch.tensor(index, dtype=torch.long, device=xk.device)
-        flat = lambda c, x: torch.cat([c.reshape(B * W, *c.shape[2:]), x], dim=0).index_select(0, idx)  # noqa: E731
+        ring = lambda c, x: kv_dequantize(c, x.dtype) if c.dtype == KV_FP8 else c  # noqa: E731  (e4m3 rings: their values in xk.dtype)
+        flat = lambda c, x: torch.cat([ring(c, x).reshape(B * W, *c.shape[2:]), x], dim=0).index_select(0, idx)  # noqa: E731
         return flat(self.cache_k, xk), flat(self.cache_v, xv)
 
     @property
@@ -177,18 +215,22 @@ class BufferCache:
         self._ptr_tables = None
 
     def _alloc(self, B: int, w: int, **kw) -> torch.Tensor:
-        if self.head_major:
-            return torch.empty((B, self.n_kv_heads, w, self.head_dim), **kw).permute(0, 2, 1, 3)
-        return torch.empty((B, w, self.n_kv_heads, self.head_dim), **kw)
+        # (e4m3 rings are zero-filled: a never-written byte is then the value 0, not a NaN code)
+        shape = (B, self.n_kv_heads, w, self.head_dim) if self.head_major else (B, w, self.n_kv_heads, self.head_dim)
+        t = torch.zeros(shape, **dict(kw, dtype=torch.uint8)).view(KV_FP8) if kw.get("dtype") == KV_FP8 else torch.empty(shape, **kw)
+        return t.permute(0, 2, 1, 3) if self.head_major else t
 
     @property
     def kv_layout(self) -> int:
-        """`_hip.KV_SLOT_MAJOR` / `_hip.KV_HEAD_MAJOR` of every ring (checked: a caller may have replaced tensors)."""
+        """`_hip.KV_SLOT_MAJOR` / `_hip.KV_HEAD_MAJOR` of every ring (checked: a caller may have replaced tensors), with
+        `_hip.KV_E4M3` when the rings hold e4m3 bytes."""
         if self.n_layers == 0:
             return _hip.KV_SLOT_MAJOR
         lay = {_hip.kv_layout_of(t) for d in (self.cache_k, self.cache_v) for i, t in d.items() if self.cache_sizes[i] > 1 and self.n_kv_heads > 1}
         assert len(lay) <= 1, "K/V rings of one cache in different layouts"
-        return lay.pop() if lay else _hip.KV_SLOT_MAJOR
+        dts = {t.dtype for d in (self.cache_k, self.cache_v) for t in d.values()}
+        assert len(dts) == 1, f"K/V rings of one cache in different dtypes: {dts}"
+        return (lay.pop() if lay else _hip.KV_SLOT_MAJOR) | (_hip.KV_E4M3 if dts.pop() == KV_FP8 else 0)
 
     # ---- reference API ----------------------------------------------------------------------
     def get_view(self, layer_id: int, metadata: CacheInputMetadata) -> CacheView:
@@ -208,10 +250,17 @@ class BufferCache:
         return self.cache_k[0].device
 
     def to(self, device: Union[str, torch.device], dtype: torch.dtype) -> "BufferCache":
+        def cast(t: torch.Tensor) -> torch.Tensor:  # (to and from e4m3 by the rule, not by torch's bare cast)
+            if dtype == KV_FP8 and t.dtype != KV_FP8:
+                return kv_quantize(t.to(device))
+            if t.dtype == KV_FP8 and dtype != KV_FP8:
+                return kv_dequantize(t.to(device), dtype)
+            return t.to(device=device, dtype=dtype)
+
         def move(t: torch.Tensor) -> torch.Tensor:  # (keeps the layout: a head-major ring stays a permuted view of dense storage)
             if _hip.kv_layout_of(t) == _hip.KV_HEAD_MAJOR:
-                return t.permute(0, 2, 1, 3).to(device=device, dtype=dtype).contiguous().permute(0, 2, 1, 3)
-            return t.to(device=device, dtype=dtype)
+                return cast(t.permute(0, 2, 1, 3)).contiguous().permute(0, 2, 1, 3)
+            return cast(t)
         for i in range(self.n_layers):
             self.cache_k[i] = move(self.cache_k[i])
             self.cache_v[i] = move(self.cache_v[i])
@@ -295,8 +344,9 @@ class BufferCache:
         if self._ptr_tables is None:
             import ctypes as C
             dt = self.cache_k[0].dtype  # (the model checks it against its own storage dtype: HipStackBackend.run_stack)
-            ks = _hip.ptr_array([_hip.dev_ptr(self.cache_k[i], dt) for i in range(self.n_layers)])
-            vs = _hip.ptr_array([_hip.dev_ptr(self.cache_v[i], dt) for i in range(self.n_layers)])
+            ptr = _hip.ring_ptr if dt == KV_FP8 else (lambda t: _hip.dev_ptr(t, dt))
+            ks = _hip.ptr_array([ptr(self.cache_k[i]) for i in range(self.n_layers)])
+            vs = _hip.ptr_array([ptr(self.cache_v[i]) for i in range(self.n_layers)])
             ws = (C.c_int32 * self.n_layers)(*self.cache_sizes)
             self._ptr_tables = (ks, vs, ws, self.kv_layout)  # (the layout is checked once per table build, not per forward)
         return self._ptr_tables

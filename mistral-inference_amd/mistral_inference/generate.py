@@ -17,7 +17,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from .cache import BufferCache
+from .cache import BufferCache, check_kv_dtype
 from .transformer import Transformer
 
 
@@ -46,7 +46,11 @@ def generate(
     chunk_size: Optional[int] = None,
     eos_id: Optional[int] = None,
     adapters: Optional[List[int]] = None,
+    kv_dtype: Optional[torch.dtype] = None,
 ) -> Tuple[List[List[int]], List[List[float]]]:
+    # kv_dtype: dtype of the K/V rings; None: the model's.  torch.float8_e4m3fn (bf16 models on the tuned path): rings of e4m3 bytes
+    # at half the size, written and read by the rule of cache.kv_quantize / kv_dequantize; such a generation takes the launch path.
+    kv_dtype = check_kv_dtype(kv_dtype, model.dtype)   # (before anything is pinned or allocated)
     # adapters (a model built with `lora`, Transformer.set_lora_slots): one adapter slot per prompt, -1 = the base model; written
     # to the device ONCE here, before the first prefill chunk - every forward, prompt_logprobs call and the decode session below
     # run with it.  None: slot 0 for every sequence.
@@ -68,7 +72,7 @@ def generate(
     # K/V rings, straight in device memory (reference generate.py:67-78)
     cache_window = max(seqlens) + max_tokens
     cache = BufferCache(model.n_local_layers, model.args.max_batch_size, cache_window, model.args.n_kv_heads,
-                        model.args.head_dim, model.args.sliding_window, device=dev, dtype=model.dtype)
+                        model.args.head_dim, model.args.sliding_window, device=dev, dtype=kv_dtype)
     cache.reset()
 
     # logprob pieces stay on the device; (sequence, tensor) in emission order

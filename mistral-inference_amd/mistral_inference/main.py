@@ -14,6 +14,7 @@ from typing import List, Optional, Type, Union
 
 import torch
 
+from .cache import kv_dtype_arg
 from .generate import generate  # noqa: F401  (the reference's tests import generate from main)
 from .transformer import Transformer
 
@@ -76,9 +77,11 @@ def get_model_cls(model_path: str) -> Type[Transformer]:
 
 
 def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7, num_pipeline_ranks: int = 1,
-                instruct: bool = False, lora_path: Optional[str] = None, quantize: Optional[str] = None) -> None:
+                instruct: bool = False, lora_path: Optional[str] = None, quantize: Optional[str] = None,
+                kv_dtype: Optional[str] = None) -> None:
     """quantize="fp8_e4m3" / "mxfp4": quantise a bf16 checkpoint to weight-only FP8 / MXFP4 while it loads (a folder that
-    quant.quantize_checkpoint wrote needs no flag)."""
+    quant.quantize_checkpoint wrote needs no flag).  kv_dtype="fp8_e4m3": K/V rings of e4m3 bytes (half the bytes; launch path)."""
+    kv = kv_dtype_arg(kv_dtype)  # (an unknown name is refused before anything is loaded)
     num_pipeline_ranks = init_pipeline() if is_torchrun() else num_pipeline_ranks
     should_print = _should_print()
     mistral_tokenizer = load_tokenizer(Path(model_path))
@@ -105,7 +108,7 @@ def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7,
             if not should_print:
                 tokens = n * [0]
         generated, _ = generate([tokens], model, max_tokens=max_tokens, temperature=temperature,
-                                eos_id=tokenizer.eos_id)
+                                eos_id=tokenizer.eos_id, kv_dtype=kv)
         answer = tokenizer.decode(generated[0])
         if should_print:
             print(answer)
@@ -116,8 +119,9 @@ def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7,
 
 
 def demo(model_path: str, max_tokens: int = 35, temperature: float = 0, lora_path: Optional[str] = None,
-         quantize: Optional[str] = None) -> None:
-    """quantize: as `interactive`."""
+         quantize: Optional[str] = None, kv_dtype: Optional[str] = None) -> None:
+    """quantize, kv_dtype: as `interactive`."""
+    kv = kv_dtype_arg(kv_dtype)
     num_pipeline_ranks = init_pipeline()
     should_print = _should_print()
     model = get_model_cls(model_path).from_folder(Path(model_path), max_batch_size=3,
@@ -128,7 +132,7 @@ def demo(model_path: str, max_tokens: int = 35, temperature: float = 0, lora_pat
     prompts = ["This is a test", "This is another great test", "This is a third test, mistral AI is very good at testing. "]
     encoded = [tokenizer.encode(p, bos=True, eos=False) for p in prompts]
     generated, logprobs = generate(encoded, model, max_tokens=max_tokens, temperature=temperature,
-                                   eos_id=tokenizer.eos_id)
+                                   eos_id=tokenizer.eos_id, kv_dtype=kv)
     if should_print:
         for p, g, lp in zip(prompts, generated, logprobs):
             print(p + tokenizer.decode(g))

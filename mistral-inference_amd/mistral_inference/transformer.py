@@ -264,7 +264,7 @@ class HipStackBackend:
             HipStackBackend._engine_suspended = False
             _hip.check(_hip.lib().mi_decode_engine_census(1), "mi_decode_engine_census")
             _hip.set_decode_engine(True)
-        self._get_workspace(model, self.plan(model), B, B, max(cache.cache_sizes))  # (a decode step has T == B rows)
+        self._get_workspace(model, self.plan(model), B, B, max(cache.cache_sizes), cache.kv_layout)  # (a decode step has T == B rows)
 
     def session_rewind(self, steps: int) -> None:
         """Set the workspace's decode-step counter (control word `steps`: the row of the greedy history ring and the Philox offset
@@ -279,13 +279,11 @@ class HipStackBackend:
         _hip.set_decode_engine(False)
         HipStackBackend._engine_suspended = True
 
-    def _get_workspace(self, model: "Transformer", m, T: int, B: int, max_w: int) -> torch.Tensor:
+    def _get_workspace(self, model: "Transformer", m, T: int, B: int, max_w: int, kv_layout: int = 0) -> torch.Tensor:
         if self.generic:
             need = _hip.lib().mi_workspace_bytes_generic(C.byref(m), T, self.dtype_code)
-        elif self._quant is not None:
-            need = self._quant[1](C.byref(m), C.byref(self._quant[0]), T, B, max_w)
-        else:
-            need = _hip.lib().mi_workspace_bytes(C.byref(m), T, B, max_w)
+        else:  # (rings of e4m3 bytes add the prefill scratch of one layer's dequantised rings; otherwise mi_workspace_bytes[_w8 / _w4])
+            need = _hip.lib().mi_workspace_bytes_kv(C.byref(m), 1 if self._quant is not None else 0, T, B, max_w, kv_layout)
         ws = self._workspace
         if ws is None or ws.numel() < need or ws.device != model.device:
             # grow geometrically; zero-filled because the first 4 KiB are split-KV arrival counters
@@ -309,7 +307,12 @@ class HipStackBackend:
         max_w = 1
         if cache is not None:
             if cache.n_layers and cache.cache_k[0].dtype != model.dtype:
-                raise RuntimeError(f"cache dtype {cache.cache_k[0].dtype} != model dtype {model.dtype} (BufferCache.to(device, dtype))")
+                if cache.cache_k[0].dtype != torch.float8_e4m3fn:
+                    raise RuntimeError(f"cache dtype {cache.cache_k[0].dtype} != model dtype {model.dtype} (BufferCache.to(device, dtype))")
+                if model.dtype != torch.bfloat16 or self.generic:  # e4m3 rings: a bf16 model on the tuned path only
+                    raise NotImplementedError(
+                        f"an FP8 K/V cache (torch.float8_e4m3fn) on {'the generic route' if model.dtype == torch.bfloat16 else f'{model.dtype} storage'} "
+                        "is not implemented: the e4m3 ring kernels serve bfloat16 models on the tuned path; use a cache of the model's dtype")
             ks, vs, ws, bt.kv_layout = cache.pointer_tables()
             bt.cache_k, bt.cache_v = C.cast(ks, C.POINTER(C.c_void_p)), C.cast(vs, C.POINTER(C.c_void_p))
             bt.cache_sizes = C.cast(ws, C.POINTER(C.c_int32))
@@ -329,7 +332,7 @@ class HipStackBackend:
         if seq_adapter is not None:  # ABI v9: one adapter slot per sequence (meta.tok_seq names a row's sequence on every branch)
             assert seq_adapter.numel() >= B
             bt.seq_adapter = _hip.dev_ptr(seq_adapter, i32)
-        wsb = self._get_workspace(model, m, T, B, max_w)
+        wsb = self._get_workspace(model, m, T, B, max_w, bt.kv_layout)
         bt.workspace, bt.workspace_bytes = wsb.data_ptr(), wsb.numel()
         if self.generic:
             _hip.check(_hip.lib().mi_forward_generic(C.byref(m), C.byref(bt), self.dtype_code, _hip.stream_ptr(h.device)),
