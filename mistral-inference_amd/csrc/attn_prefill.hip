@@ -27,27 +27,14 @@
 #include "common.cuh"
 #include "kernels.h"
 
-// A second compile with -DATTN_F16=1 (build_native.py: attn_prefill_f16.o) is the same kernel for fp16 storage: the MFMA
-// opcode (v_mfma_f32_32x32x16_f16), P rounded to fp16 instead of bf16 for P.V (what fp16 flash kernels do), fp16 output
-// packing; entry point launch_attn_prefill_f16 (generic.hip: prefills of fp16 models with 128-wide heads).  The default
-// compile is untouched by this block.
+// A second compile with -DATTN_F16=1 (build_native.py: attn_prefill_f16.o) is the same kernel for fp16 storage.  The element E
+// (common.cuh) carries what differs: the MFMA opcode, P rounded to fp16 instead of bf16 for P.V (what fp16 flash kernels do),
+// fp16 output packing.  That compile exports launch_attn_prefill_f16 and nothing else (generic.hip: prefills of fp16 models with
+// 128-wide heads); mi_debug_set_prefill_kernels pins the block shape of the default compile only.
 #ifndef ATTN_F16
 #define ATTN_F16 0
 #endif
-#if ATTN_F16
-typedef _Float16 attn_f16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ uint32_t attn_h_pack2(float lo, float hi) {
-  return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)lo) | ((uint32_t)__builtin_bit_cast(uint16_t, (_Float16)hi) << 16);
-}
-#define bf16x8 attn_f16x8
-#define cvt_pk_bf16 attn_h_pack2
-#define pack_bf2 attn_h_pack2
-#define ATTN_MFMA __builtin_amdgcn_mfma_f32_32x32x16_f16
-#define launch_attn_prefill launch_attn_prefill_f16
-#define attn_prefill_set_mode attn_prefill_set_mode_f16
-#else
-#define ATTN_MFMA __builtin_amdgcn_mfma_f32_32x32x16_bf16
-#endif
+using E = Elem16<ATTN_F16>;
 
 #ifndef ATT_FASTLOAD
 #define ATT_FASTLOAD 1  // 0 = every tile through the general (per-lane source selection) staging path: the round 1-5 form
@@ -137,11 +124,11 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_prefill_kernel(
   const int qp_w_hi = p_b + min(qt * QB + wid * 32 + 31, s_b - 1);
   const bool wave_active = (qt * QB + wid * 32) < s_b;
 
-  bf16x8 qf[8];
+  E::x8 qf[8];
   {
     const bf16_t* qrow = a.qkv + (size_t)(row0 + qi_c) * a.ld + (size_t)h * DH + hf * 8;
 #pragma unroll
-    for (int kk = 0; kk < 8; ++kk) qf[kk] = __builtin_bit_cast(bf16x8, ld16(qrow + kk * 16));
+    for (int kk = 0; kk < 8; ++kk) qf[kk] = __builtin_bit_cast(E::x8, ld16(qrow + kk * 16));
   }
 
   f32x16 acc[4];
@@ -299,14 +286,14 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_prefill_kernel(
         for (int r = 0; r < 16; ++r) st[mb][r] = 0.f;
 #pragma unroll
       for (int kh = 0; kh < 2; ++kh) {
-        bf16x8 kf[4][2];
+        E::x8 kf[4][2];
 #pragma unroll
         for (int k4 = 0; k4 < 4; ++k4)
 #pragma unroll
           for (int mb = 0; mb < 2; ++mb) {
             const int key = mb * 32 + ql, slot = (kh * 4 + k4) * 2 + hf;
             kf[k4][mb] = __builtin_bit_cast(
-                bf16x8, *reinterpret_cast<const u32x4*>(Ks + key * (DH * 2) + ((slot ^ (key & 15)) << 4)));
+                E::x8, *reinterpret_cast<const u32x4*>(Ks + key * (DH * 2) + ((slot ^ (key & 15)) << 4)));
           }
         __builtin_amdgcn_sched_barrier(0);  // keep the 8 reads ahead of the MFMAs (hipcc sinks them back otherwise)
         if (ATT_PRIO == 1) __builtin_amdgcn_s_setprio(1);
@@ -314,7 +301,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_prefill_kernel(
         for (int k4 = 0; k4 < 4; ++k4)
 #pragma unroll
           for (int mb = 0; mb < 2; ++mb)
-            st[mb] = ATTN_MFMA(kf[k4][mb], qf[kh * 4 + k4], st[mb], 0, 0, 0);
+            st[mb] = E::mfma32(kf[k4][mb], qf[kh * 4 + k4], st[mb]);
         if (ATT_PRIO == 1) __builtin_amdgcn_s_setprio(0);
       }
       ATT_STAMP(1)
@@ -367,7 +354,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_prefill_kernel(
         for (int r = 0; r < 16; r += 2) {
           const float p0 = fast_exp2(fmaf(st[mb][r], sc, nm)), p1 = fast_exp2(fmaf(st[mb][r + 1], sc, nm));
           psum += p0 + p1;
-          pb[mb][r >> 3][(r & 7) >> 1] = cvt_pk_bf16(p0, p1);
+          pb[mb][r >> 3][(r & 7) >> 1] = E::pack2_fast(p0, p1);
         }
       l_run = l_run * alpha + psum;
       if (ATT_PRIO == 1) __builtin_amdgcn_s_setprio(1);
@@ -378,7 +365,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_prefill_kernel(
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
           u32x4 pw = {pb[mb][kb][0], pb[mb][kb][1], pb[mb][kb][2], pb[mb][kb][3]};
-          const bf16x8 pf = __builtin_bit_cast(bf16x8, pw);
+          const E::x8 pf = __builtin_bit_cast(E::x8, pw);
 #pragma unroll
           for (int dt = 0; dt < 4; ++dt) {
 #if ATT_VB128
@@ -389,7 +376,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_prefill_kernel(
             const u32x2 v1 = *reinterpret_cast<const u32x2*>(vrow + 16);
             const u32x4 vw = {v0[0], v0[1], v1[0], v1[1]};
 #endif
-            acc[dt] = ATTN_MFMA(__builtin_bit_cast(bf16x8, vw), pf, acc[dt], 0, 0, 0);
+            acc[dt] = E::mfma32(__builtin_bit_cast(E::x8, vw), pf, acc[dt]);
           }
         }
       if (ATT_PRIO == 1) __builtin_amdgcn_s_setprio(0);
@@ -433,8 +420,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_prefill_kernel(
       for (int g = 0; g < 4; ++g) {
         const int d = dt * 32 + 8 * g + 4 * hf;
         u32x2 o;
-        o[0] = pack_bf2(acc[dt][4 * g] * inv, acc[dt][4 * g + 1] * inv);
-        o[1] = pack_bf2(acc[dt][4 * g + 2] * inv, acc[dt][4 * g + 3] * inv);
+        o[0] = E::pack2(acc[dt][4 * g] * inv, acc[dt][4 * g + 1] * inv);
+        o[1] = E::pack2(acc[dt][4 * g + 2] * inv, acc[dt][4 * g + 3] * inv);
         *reinterpret_cast<u32x2*>(orow + d) = o;
       }
   }
@@ -461,11 +448,15 @@ static hipError_t launch_nw(const AttnPrefillArgs& a, hipStream_t s) {
 }
 
 static int g_force_waves = -1;
+#if ATTN_F16
+hipError_t launch_attn_prefill_f16(const AttnPrefillArgs& a, hipStream_t s) {
+#else
 void attn_prefill_set_mode(int waves) {
   if (waves >= 0) g_force_waves = waves;
 }
 
 hipError_t launch_attn_prefill(const AttnPrefillArgs& a, hipStream_t s) {
+#endif
   if (a.Dh != DH || a.H % a.Hkv != 0) return hipErrorInvalidValue;
   int& force = g_force_waves;  // MI_ATTN_PREFILL_WAVES=4|8 / mi_debug_set_prefill_kernels pin the block shape (A/B testing)
   if (force < 0) {

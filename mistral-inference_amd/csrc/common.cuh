@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 typedef uint16_t bf16_t;  // raw bf16 payload
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -146,3 +147,54 @@ __device__ __forceinline__ float swiglu_bf_fast(float acc1, float acc3) {
   const float s = bf_round(a * __builtin_amdgcn_rcpf(1.0f + e));
   return s * b;
 }
+
+// ---- the 16-bit storage element of a kernel that is compiled once per element (gemm256.hip, attn_prefill.hip, gemv.hip with
+// gemv_core.cuh): such a file picks one of the two structs at file scope and names every conversion, rounding point, dot product
+// and MFMA through it.  The data movement of the two elements is identical.  ElemBf16 is the free functions above under the
+// trait's names (the bf16-only files call them directly); ElemF16 is the only place IEEE half is spelled out.  Elem16<F16> (below)
+// is the choice by a file's -D switch.
+struct ElemBf16 {
+  typedef bf16x2_t x2;
+  typedef bf16x8 x8;
+  static __device__ __forceinline__ float to_f(uint16_t h) { return bf_to_f(h); }
+  static __device__ __forceinline__ uint16_t from_f(float f) { return f_to_bf(f); }
+  static __device__ __forceinline__ float round(float f) { return bf_round(f); }
+  static __device__ __forceinline__ uint32_t pack2(float lo, float hi) { return pack_bf2(lo, hi); }
+  static __device__ __forceinline__ uint32_t pack2_fast(float lo, float hi) { return cvt_pk_bf16(lo, hi); }
+  static __device__ __forceinline__ float lo(uint32_t u) { return bf_lo(u); }
+  static __device__ __forceinline__ float hi(uint32_t u) { return bf_hi(u); }
+  static __device__ __forceinline__ float dot2(uint32_t a, uint32_t b, float acc) { return dot2_bf16(a, b, acc); }
+  static __device__ __forceinline__ float swiglu(float acc1, float acc3) { return swiglu_bf(acc1, acc3); }
+  static __device__ __forceinline__ float swiglu_fast(float acc1, float acc3) { return swiglu_bf_fast(acc1, acc3); }
+  static __device__ __forceinline__ f32x4 mfma16(x8 a, x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+  static __device__ __forceinline__ f32x16 mfma32(x8 a, x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+// IEEE half: v_dot2_f32_f16, v_mfma_*_f16, and (float)(_Float16)f as the rounding point wherever ElemBf16 has bf_round.
+struct ElemF16 {
+  typedef _Float16 x2 __attribute__((ext_vector_type(2)));
+  typedef _Float16 x8 __attribute__((ext_vector_type(8)));
+  static __device__ __forceinline__ float to_f(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
+  static __device__ __forceinline__ uint16_t from_f(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
+  static __device__ __forceinline__ float round(float f) { return (float)(_Float16)f; }
+  static __device__ __forceinline__ uint32_t pack2(float lo, float hi) { return (uint32_t)from_f(lo) | ((uint32_t)from_f(hi) << 16); }
+  static __device__ __forceinline__ uint32_t pack2_fast(float lo, float hi) { return pack2(lo, hi); }  // the plain pack
+  static __device__ __forceinline__ float lo(uint32_t u) { return to_f((uint16_t)(u & 0xffffu)); }
+  static __device__ __forceinline__ float hi(uint32_t u) { return to_f((uint16_t)(u >> 16)); }
+  static __device__ __forceinline__ float dot2(uint32_t a, uint32_t b, float acc) {
+    return __builtin_amdgcn_fdot2(__builtin_bit_cast(x2, a), __builtin_bit_cast(x2, b), acc, false);
+  }
+  static __device__ __forceinline__ float swiglu(float acc1, float acc3) {  // swiglu_bf's chain
+    const float a = round(acc1), b = round(acc3);
+    const float s = round(a / (1.0f + expf(-a)));
+    return s * b;
+  }
+  static __device__ __forceinline__ float swiglu_fast(float acc1, float acc3) {  // swiglu_bf_fast's chain
+    const float a = round(acc1), b = round(acc3);
+    const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * a);
+    const float s = round(a * __builtin_amdgcn_rcpf(1.0f + e));
+    return s * b;
+  }
+  static __device__ __forceinline__ f32x4 mfma16(x8 a, x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+  static __device__ __forceinline__ f32x16 mfma32(x8 a, x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
+template <bool F16> using Elem16 = std::conditional_t<F16, ElemF16, ElemBf16>;

@@ -24,12 +24,6 @@ constexpr int TILE_BYTES = BM * BK * 2;  // 16 KiB per operand per buffer
 
 __device__ __forceinline__ int lds_off(int row, int slot) { return row * (BK * 2) + ((slot ^ (row & 7)) << 4); }
 
-__device__ __forceinline__ const bf16_t* seg_row(const GemmArgs& g, int r) {
-  if (r < g.n0) return g.w0 + (size_t)r * g.K;
-  if (r < g.n1) return g.w1 + (size_t)(r - g.n0) * g.K;
-  return g.w2 + (size_t)(r - g.n1) * g.K;
-}
-
 template <int EPI, bool GLDS>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];

@@ -29,45 +29,13 @@
 #include "kernels.h"
 
 // A second compile of this file with -DG256_F16=1 (build_native.py: gemm256_f16.o) is the SAME kernel for fp16 storage - the
-// data movement of two 16-bit types is identical; what changes is the MFMA opcode (v_mfma_f32_16x16x32_f16) and the half
-// conversions / rounding points of the epilogues - under the entry points launch_gemm256_f16 & co., used by the generic
-// storage path (generic.hip) for prefills of fp16 models.  The default compile is untouched by this block (its ISA hash is
-// checked like the decode engine's).
+// data movement of two 16-bit types is identical; what changes is the element E (common.cuh): the MFMA opcode and the
+// conversions / rounding points of the epilogues.  That compile exports launch_gemm256_f16 and nothing else (generic.hip:
+// prefills of fp16 models); the default compile's code objects are checked against their ISA hash like the decode engine's.
 #ifndef G256_F16
 #define G256_F16 0
 #endif
-#if G256_F16
-typedef _Float16 g256_f16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ float g256_h_to_f(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
-__device__ __forceinline__ uint16_t g256_h_from_f(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
-__device__ __forceinline__ float g256_h_round(float f) { return (float)(_Float16)f; }
-__device__ __forceinline__ uint32_t g256_h_pack2(float lo, float hi) {
-  return (uint32_t)g256_h_from_f(lo) | ((uint32_t)g256_h_from_f(hi) << 16);
-}
-__device__ __forceinline__ float g256_h_lo(uint32_t u) { return g256_h_to_f((uint16_t)(u & 0xffffu)); }
-__device__ __forceinline__ float g256_h_hi(uint32_t u) { return g256_h_to_f((uint16_t)(u >> 16)); }
-__device__ __forceinline__ float g256_h_swiglu(float acc1, float acc3) {  // swiglu_bf_fast with fp16 rounding points
-  const float a = g256_h_round(acc1), b = g256_h_round(acc3);
-  const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * a);
-  const float s = g256_h_round(a * __builtin_amdgcn_rcpf(1.0f + e));
-  return s * b;
-}
-#define bf_round g256_h_round
-#define pack_bf2 g256_h_pack2
-#define f_to_bf g256_h_from_f
-#define bf_to_f g256_h_to_f
-#define bf_lo g256_h_lo
-#define bf_hi g256_h_hi
-#define swiglu_bf_fast g256_h_swiglu
-#define bf16x8 g256_f16x8
-#define G256_MFMA __builtin_amdgcn_mfma_f32_16x16x32_f16
-#define gemm256_applicable gemm256_applicable_f16
-#define gemm256_half_applicable gemm256_half_applicable_f16
-#define launch_gemm256_half launch_gemm256_half_f16
-#define launch_gemm256 launch_gemm256_f16
-#else
-#define G256_MFMA __builtin_amdgcn_mfma_f32_16x16x32_bf16
-#endif
+using E = Elem16<G256_F16>;
 
 // Build-time experiment switches (all off in the shipped build; the experimental main loops live OUTSIDE the product tree, in scripts/probes/gemm256_experiments.inc):
 #ifndef G256_PRIO
@@ -112,12 +80,6 @@ constexpr int LDS_BYTES = 2 * STAGE_BYTES;   // 128 KiB
 // at 1.5x the LDS bytes per flop of the square tile.  Same MFMA shape, same k order: bit-identical outputs.
 constexpr int STAGE_BYTES_H = 3 * HALF_BYTES;
 constexpr int LDS_BYTES_H = 3 * STAGE_BYTES_H;  // 144 KiB
-
-__device__ __forceinline__ const bf16_t* seg_row256(const GemmArgs& g, int r) {
-  if (r < g.n0) return g.w0 + (size_t)r * g.K;
-  if (r < g.n1) return g.w1 + (size_t)(r - g.n0) * g.K;
-  return g.w2 + (size_t)(r - g.n1) * g.K;
-}
 
 __device__ __forceinline__ void dma16(const bf16_t* src, char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
@@ -200,7 +162,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmArgs g) {
         src[MH + h][j] = (h == 0 ? w0 : w1) + (size_t)n * g.K + sslot * 8;
       } else {
         const int n = min(n_tile * 256 + h * 128 + r, g.N - 1);
-        src[MH + h][j] = (grouped ? w0 + (size_t)n * g.K : seg_row256(g, n)) + sslot * 8;
+        src[MH + h][j] = (grouped ? w0 + (size_t)n * g.K : seg_row(g, n)) + sslot * 8;
       }
     }
   char* const my_piece = smem + wid * 2048;  // this wave's two 1-KiB pieces inside any half tile
@@ -229,9 +191,9 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmArgs g) {
 #if G256_PIPE || G256_BAL || G256_SPLIT || G256_ABL || G256_PRIO || !G256_DMA_AFTER
 #include "../../scripts/probes/gemm256_experiments.inc"  // probe builds only (scripts/build_variants.py gemm): never part of the shipped library
 #else
-  bf16x8 af[2][4];             // [k step][row fragment] of the A half in use
-  bf16x8 b0x[2][2], b1[2][2];  // [k step][column fragment] of B half 0 / 1
-#define LDS_FRAG(ADDR) __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(ADDR))
+  E::x8 af[2][4];             // [k step][row fragment] of the A half in use
+  E::x8 b0x[2][2], b1[2][2];  // [k step][column fragment] of B half 0 / 1
+#define LDS_FRAG(ADDR) __builtin_bit_cast(E::x8, *reinterpret_cast<const u32x4*>(ADDR))
 #define READ_A(HA, SB)                                                               \
   _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                    \
     af[0][i] = LDS_FRAG((SB) + (HA) * HALF_BYTES + a_off + i * 2048 + sw0);          \
@@ -259,8 +221,8 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmArgs g) {
   _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                              \
   _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                 \
   _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                                 \
-    acc[HA][HB][i][j] = kSwap ? G256_MFMA(BF[ks][j], af[ks][i], acc[HA][HB][i][j], 0, 0, 0) \
-                              : G256_MFMA(af[ks][i], BF[ks][j], acc[HA][HB][i][j], 0, 0, 0);
+    acc[HA][HB][i][j] = kSwap ? E::mfma16(BF[ks][j], af[ks][i], acc[HA][HB][i][j]) \
+                              : E::mfma16(af[ks][i], BF[ks][j], acc[HA][HB][i][j]);
 
   const int nk = g.K / BK;
   if constexpr (MH == 1) {
@@ -404,7 +366,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmArgs g) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
               const int n = n_tile * 256 + hb * 128 + wc * 32 + j * 16 + (lane & 15);
-              v[hb][j] = (n < g.N) ? bf_round(acc[ha][hb][i][j][r]) : -INFINITY;
+              v[hb][j] = (n < g.N) ? E::round(acc[ha][hb][i][j][r]) : -INFINITY;
               mx = fmaxf(mx, v[hb][j]);
               if (n == g.lp_target[row] && row0 + rl < g.M) g.lp_tgt[row] = v[hb][j];
             }
@@ -446,7 +408,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmArgs g) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
               const int n = n_tile * 256 + hb * 128 + wc * 32 + j * 16 + (lane & 15);
-              if (n < g.N) o[n] = bf_round(acc[ha][hb][i][j][r]);
+              if (n < g.N) o[n] = E::round(acc[ha][hb][i][j][r]);
             }
         }
     return;
@@ -474,14 +436,14 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmArgs g) {
           const int n = n_tile * 128 + wc * 32 + j * 16 + cq;
           float y[4];
 #pragma unroll
-          for (int r = 0; r < 4; ++r) y[r] = swiglu_bf_fast(acc[ha][0][i][j][r], acc[ha][1][i][j][r]);
+          for (int r = 0; r < 4; ++r) y[r] = E::swiglu_fast(acc[ha][0][i][j][r], acc[ha][1][i][j][r]);
           bf16_t* o = reinterpret_cast<bf16_t*>(g.out) + ob + n;
           if (n + 3 < g.N && wide_ok) {
-            *reinterpret_cast<uint2*>(o) = make_uint2(pack_bf2(y[0], y[1]), pack_bf2(y[2], y[3]));
+            *reinterpret_cast<uint2*>(o) = make_uint2(E::pack2(y[0], y[1]), E::pack2(y[2], y[3]));
           } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-              if (n + r < g.N) o[r] = f_to_bf(y[r]);
+              if (n + r < g.N) o[r] = E::from_f(y[r]);
           }
         }
       } else {
@@ -494,7 +456,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmArgs g) {
             const bool full = (n + 3 < g.N) && wide_ok;
             float y[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) y[r] = bf_round(acc[ha][hb][i][j][r]);
+            for (int r = 0; r < 4; ++r) y[r] = E::round(acc[ha][hb][i][j][r]);
             if (EPI == GEMM_STORE && rope && n < g.rope_cols) {
               // rotary embedding on the bf16-rounded projection (transformer_layers.py:66-70): this lane's four columns
               // are two (re, im) pairs of one head; their (cos, sin) entries are 16 contiguous bytes of the table
@@ -502,9 +464,9 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmArgs g) {
               const f32x4 cs = *reinterpret_cast<const f32x4*>(g.rope_cs + ((size_t)tp * (g.rope_dh >> 1) + i0) * 2);
               float re, im;
               rope_pair(y[0], y[1], cs[0], cs[1], re, im);
-              y[0] = bf_round(re); y[1] = bf_round(im);
+              y[0] = E::round(re); y[1] = E::round(im);
               rope_pair(y[2], y[3], cs[2], cs[3], re, im);
-              y[2] = bf_round(re); y[3] = bf_round(im);
+              y[2] = E::round(re); y[3] = E::round(im);
             }
             if (EPI == GEMM_LOGITS) {
               float* o = reinterpret_cast<float*>(g.out) + ob + n;
@@ -520,13 +482,13 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmArgs g) {
               if (full) {
                 if (EPI == GEMM_RESIDUAL) {
                   const uint2 rs = *reinterpret_cast<const uint2*>(g.residual + ob + n);
-                  y[0] += bf_lo(rs.x); y[1] += bf_hi(rs.x); y[2] += bf_lo(rs.y); y[3] += bf_hi(rs.y);
+                  y[0] += E::lo(rs.x); y[1] += E::hi(rs.x); y[2] += E::lo(rs.y); y[3] += E::hi(rs.y);
                 }
-                *reinterpret_cast<uint2*>(o) = make_uint2(pack_bf2(y[0], y[1]), pack_bf2(y[2], y[3]));
+                *reinterpret_cast<uint2*>(o) = make_uint2(E::pack2(y[0], y[1]), E::pack2(y[2], y[3]));
               } else {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                  if (n + r < g.N) o[r] = f_to_bf(EPI == GEMM_RESIDUAL ? bf_to_f(g.residual[ob + n + r]) + y[r] : y[r]);
+                  if (n + r < g.N) o[r] = E::from_f(EPI == GEMM_RESIDUAL ? E::to_f(g.residual[ob + n + r]) + y[r] : y[r]);
               }
             }
           }
@@ -559,6 +521,7 @@ hipError_t launch_one(const GemmArgs& g, dim3 grid, hipStream_t s) {
 
 }  // namespace
 
+#if !G256_F16  // (host predicates and the half-height launcher do not depend on the element: the default compile has them)
 bool gemm256_applicable(const GemmArgs& g) {
   if (g.K % BK != 0 || g.K < 2 * BK) return false;
   if (g.tile_tab != nullptr) return g.tile_rows == 256;  // token-grouped form: the tile table decides
@@ -581,8 +544,13 @@ hipError_t launch_gemm256_half(const GemmArgs& g, hipStream_t s) {
     default: return hipErrorInvalidValue;
   }
 }
+#endif
 
+#if G256_F16
+hipError_t launch_gemm256_f16(const GemmArgs& g, hipStream_t s) {
+#else
 hipError_t launch_gemm256(const GemmArgs& g, hipStream_t s) {
+#endif
   const int nout = (g.epi == GEMM_SWIGLU) ? 128 : 256;
   const int m_tiles = g.tile_tab ? g.max_m_tiles : (g.M + 255) >> 8, n_tiles = (g.N + nout - 1) / nout;
   const int supertiles = ((m_tiles + 3) >> 2) * ((n_tiles + 7) >> 3);

@@ -8,57 +8,28 @@
 #include <cstdlib>
 
 #include "common.cuh"
+#include "gemv_core.cuh"
 
-// A second compile with -DGEMV_F16=1 (build_native.py: gemv_f16.o) is the same weight-streaming kernel for fp16 storage:
-// v_dot2_f32_f16 for v_dot2c_f32_bf16 and half conversions / rounding points, under launch_gemv_f16 (api.hip: decode steps of
-// fp16 models in mi_forward_generic).  Every 16-bit access of gemv_core.cuh goes through the helpers renamed here (its e4m3 code is
-// parsed but not instantiated in that compile); the default compile is untouched by this block.
+// A second compile with -DGEMV_F16=1 (build_native.py: gemv_f16.o) is the same weight-streaming kernel for fp16 storage: the
+// element E (common.cuh) is ElemF16 - v_dot2_f32_f16 for v_dot2c_f32_bf16, half conversions and rounding points - and the entry
+// points are launch_gemv_f16 / gemv_max_tokens_f16 (api.hip: decode steps of fp16 models in mi_forward_generic).  gemv_core.cuh
+// takes the element from the weight format W16<E>; nothing in it depends on this file's switch.
 #ifndef GEMV_F16
 #define GEMV_F16 0
 #endif
-#if GEMV_F16
-typedef _Float16 gemv_half2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float gemv_h_to_f(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
-__device__ __forceinline__ uint16_t gemv_h_from_f(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }
-__device__ __forceinline__ float gemv_h_round(float f) { return (float)(_Float16)f; }
-__device__ __forceinline__ uint32_t gemv_h_pack2(float lo, float hi) {
-  return (uint32_t)gemv_h_from_f(lo) | ((uint32_t)gemv_h_from_f(hi) << 16);
-}
-__device__ __forceinline__ float gemv_h_lo(uint32_t u) { return gemv_h_to_f((uint16_t)(u & 0xffffu)); }
-__device__ __forceinline__ float gemv_h_hi(uint32_t u) { return gemv_h_to_f((uint16_t)(u >> 16)); }
-__device__ __forceinline__ float gemv_h_dot2(uint32_t a, uint32_t b, float acc) {
-  return __builtin_amdgcn_fdot2(__builtin_bit_cast(gemv_half2, a), __builtin_bit_cast(gemv_half2, b), acc, false);
-}
-__device__ __forceinline__ float gemv_h_swiglu(float acc1, float acc3) {  // swiglu_bf with fp16 rounding points
-  const float a = gemv_h_round(acc1), b = gemv_h_round(acc3);
-  const float s = gemv_h_round(a / (1.0f + expf(-a)));
-  return s * b;
-}
-#define dot2_bf16 gemv_h_dot2
-#define bf_lo gemv_h_lo
-#define bf_hi gemv_h_hi
-#define pack_bf2 gemv_h_pack2
-#define bf_round gemv_h_round
-#define f_to_bf gemv_h_from_f
-#define bf_to_f gemv_h_to_f
-#define swiglu_bf gemv_h_swiglu
-#define gemv_core gemv_core_f16
-#define gemv_max_tokens gemv_max_tokens_f16
-#define launch_gemv launch_gemv_f16
-#endif
-
-#include "gemv_core.cuh"
+using E = Elem16<GEMV_F16>;
 
 namespace {
 
 using namespace gemv_core;
+typedef W16<E> W;  // the weight format: 16-bit rows of the activations' element
 
 // ROWS: rows per unit, always 2; DMA: the activation rows go to LDS by LDS-DMA (instantiated for 2..8 tokens, picked when they do
 // not fit the registers)
 template <int TT, int MODE, int ROWS, bool DMA>
 __global__ __launch_bounds__(256, (TT == 1 ? 4 : (TT <= 3 ? 3 : 2))) void gemv_kernel(GemvArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  gemv_body<W16, TT, MODE, ROWS, DMA>(a, nullptr, smem, blockIdx.x, gridDim.x, blockIdx.y);
+  gemv_body<W, TT, MODE, ROWS, DMA>(a, nullptr, smem, blockIdx.x, gridDim.x, blockIdx.y);
 }
 
 // Blocks of 5 .. 7 waves for the plain modes at one token (gemv_core.cuh NWV): row counts that 4-wave blocks cannot split evenly
@@ -66,7 +37,7 @@ __global__ __launch_bounds__(256, (TT == 1 ? 4 : (TT <= 3 ? 3 : 2))) void gemv_k
 template <int MODE, int NWV>
 __global__ __launch_bounds__(NWV * 64, 4) void gemv_kernel_nw(GemvArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  gemv_body<W16, 1, MODE, 2, false, NWV>(a, nullptr, smem, blockIdx.x, gridDim.x, blockIdx.y);
+  gemv_body<W, 1, MODE, 2, false, NWV>(a, nullptr, smem, blockIdx.x, gridDim.x, blockIdx.y);
 }
 
 // MoE down-projection + combine for one token per blockIdx.y (moe.py:28-32 at decode):
@@ -82,7 +53,7 @@ __global__ __launch_bounds__(256) void moe_w2_kernel(GemvArgs a) {
   const int nwaves = gridDim.x * 4;
   const int units = (a.N + 1) >> 1;
   constexpr int U = BATCH / 2;
-  const int nch = (a.K + (1 << W16::SHIFT) - 1) >> W16::SHIFT;
+  const int nch = (a.K + (1 << W::SHIFT) - 1) >> W::SHIFT;
   const int nb = (nch + U - 1) / U;
 
   int eid[TOPK];
@@ -122,10 +93,10 @@ __global__ __launch_bounds__(256) void moe_w2_kernel(GemvArgs a) {
 #pragma unroll
     for (int k = 1; k < TOPK; ++k) base = (kl == k) ? w2[k] : base;
     const int ue = live ? ul : 0;
-    Rows<W16, 2> r;
+    Rows<W, 2> r;
     r.p[0] = live ? base + (size_t)(2 * ue) * a.K : a.x;
     r.p[1] = live ? ((2 * ue + 1 < a.N) ? base + (size_t)(2 * ue + 1) * a.K : r.p[0]) : a.x;
-    load_batch<W16, 2>(r, live ? jl * U : 0, live ? a.K : 8, live ? lane : 0, buf);
+    load_batch<W, 2>(r, live ? jl * U : 0, live ? a.K : 8, live ? lane : 0, buf);
     if (live && ++jl == nb) {
       jl = 0;
       if (++kl == TOPK) {
@@ -149,7 +120,7 @@ __global__ __launch_bounds__(256) void moe_w2_kernel(GemvArgs a) {
   int jc = 0, kc = 0;
   float r0 = 0.f, r1 = 0.f;
   auto step = [&](u32x4 (&buf)[BATCH]) {
-    fma_batch<W16, 1, 2>(buf, jc * U, xs + (size_t)kc * a.K, a.K, lane, acc);
+    fma_batch<W, 1, 2>(buf, jc * U, xs + (size_t)kc * a.K, a.K, lane, acc);
     issue(buf);
     if (++jc == nb) {
       jc = 0;
@@ -158,16 +129,16 @@ __global__ __launch_bounds__(256) void moe_w2_kernel(GemvArgs a) {
       float w = ew[0];
 #pragma unroll
       for (int k = 1; k < TOPK; ++k) w = (kc == k) ? ew[k] : w;
-      r0 = bf_round(r0 + bf_round(w * bf_round(y0)));
-      r1 = bf_round(r1 + bf_round(w * bf_round(y1)));
+      r0 = E::round(r0 + E::round(w * E::round(y0)));
+      r1 = E::round(r1 + E::round(w * E::round(y1)));
       if (++kc == TOPK) {
         kc = 0;
         if (lane == 0 && u < units) {
           const int n = 2 * u;
           const bf16_t* rs = a.residual + (size_t)t * a.ldo + n;
           bf16_t* o = reinterpret_cast<bf16_t*>(a.out) + (size_t)t * a.ldo + n;
-          o[0] = f_to_bf(bf_to_f(rs[0]) + r0);
-          if (n + 1 < a.N) o[1] = f_to_bf(bf_to_f(rs[1]) + r1);
+          o[0] = E::from_f(E::to_f(rs[0]) + r0);
+          if (n + 1 < a.N) o[1] = E::from_f(E::to_f(rs[1]) + r1);
         }
         r0 = r1 = 0.f;
         u += nwaves;
@@ -206,14 +177,22 @@ hipError_t launch_nw(const GemvArgs& a, int nw, dim3 grid, size_t lds, hipStream
 
 }  // namespace
 
+#if GEMV_F16
+int gemv_max_tokens_f16(int K) {
+#else
 int gemv_max_tokens(int K) {
+#endif
   int t = (int)(GEMV_LDS_BUDGET / ((size_t)K * 2));
   if (t == 5 || t == 7) --t;  // (5 and 7 rows run on the 6- and 8-row instantiations, which stage 6 / 8 rows in LDS)
   return t < 1 ? 1 : (t > GEMV_MAX_T ? GEMV_MAX_T : t);
 }
 
 // One launch; a.T must be <= gemv_max_tokens(K).
+#if GEMV_F16
+hipError_t launch_gemv_f16(const GemvArgs& a, hipStream_t s) {
+#else
 hipError_t launch_gemv(const GemvArgs& a, hipStream_t s) {
+#endif
   const bool pair_mode = !(a.mode == GEMV_SWIGLU || a.mode == GEMV_MOE_W13);
   const int units = pair_mode ? (a.N + 1) / 2 : a.N;
   const int cus = device_cus();

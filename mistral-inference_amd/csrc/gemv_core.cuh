@@ -1,6 +1,6 @@
 // Core of the weight-streaming GEMV for M <= 8 tokens (decode): HBM-bound, one pass over the weights.  One unit loop
-// (gemv_body) for 16-bit weight rows (gemv.hip: bf16, and fp16 in its -DGEMV_F16=1 compile) and for e4m3 rows with fp32 row
-// scales (gemv_w8.hip) and for MXFP4 rows, e2m1 codes with one e8m0 scale byte per block of 32 (gemv_w4.hip); the MoE
+// (gemv_body) for 16-bit weight rows (gemv.hip: W16<ElemBf16>, and W16<ElemF16> in its -DGEMV_F16=1 compile) and for e4m3 rows
+// with fp32 row scales (gemv_w8.hip) and for MXFP4 rows, e2m1 codes with one e8m0 scale byte per block of 32 (gemv_w4.hip); the MoE
 // down-projection (gemv.hip) uses the same batch loads and FMAs.  Host side: the launch plan.
 //
 // Structure (cdna_hip_programming.md "GEMV / M<=16 decode weights"): weights go straight HBM -> VGPR with 16-byte
@@ -22,8 +22,11 @@ constexpr int BATCH = 8;  // 16-byte loads per lane per batch (NR rows x BATCH/N
 
 // ---- weight formats.  PIECE: weights per 16-byte piece; a chunk is one wave instruction = 64 pieces = 1 << SHIFT weights.
 // VLOADS: vector loads per batch (x_finish counts two batches of them behind the LDS-DMAs); BLOCK: block-scaled (below).
-struct W16 {  // bf16 rows (fp16 in the GEMV_F16 compile)
-  typedef bf16_t elem;
+// act: the element (common.cuh) of the activation rows, norm weights, residual and outputs: the prologue and the epilogue convert and round through it.
+template <class A>
+struct W16 {  // 16-bit rows of the activations' own element, which is also the dot product's
+  typedef A act;
+  typedef uint16_t elem;
   typedef float scale_t;
   static constexpr int PIECE = 8, SHIFT = 9;
   static constexpr bool SCALED = false, BLOCK = false;
@@ -32,6 +35,7 @@ struct W16 {  // bf16 rows (fp16 in the GEMV_F16 compile)
 // OCP e4m3 bytes; the real-valued weight is scale[r] * e4m3(W[r, k]).  Per output row acc = sum_k e4m3(W[r, k]) * x[k] in fp32
 // and y = acc * scale[r] in fp32 enters the epilogue where acc enters it for 16-bit rows.  K % 16 == 0.
 struct WE4m3 {
+  typedef ElemBf16 act;
   typedef uint8_t elem;
   typedef float scale_t;
   static constexpr int PIECE = 16, SHIFT = 10;
@@ -44,6 +48,7 @@ struct WE4m3 {
 // scaled, as opposed to SCALED per row: nothing is applied in the epilogue).  K % 32 == 0.  Element offsets k of this format are
 // byte offsets k / 2 (wofs).
 struct WMxfp4 {
+  typedef ElemBf16 act;
   typedef uint8_t elem;
   typedef uint8_t scale_t;
   static constexpr int PIECE = 32, SHIFT = 11;
@@ -140,9 +145,10 @@ __device__ __forceinline__ void fma_batch(const u32x4 (&buf)[BATCH], int c0, con
 #pragma unroll
           for (int c = 0; c < 4; ++c)
 #pragma unroll
-            for (int i = 0; i < NR; ++i) acc[i][t] = dot2_bf16(buf[i * U + u][c], xv[c], acc[i][t]);
+            for (int i = 0; i < NR; ++i) acc[i][t] = F::act::dot2(buf[i * U + u][c], xv[c], acc[i][t]);
         }
       } else {
+        static_assert(std::is_same<typename F::act, ElemBf16>::value, "cvt4_e4m3 makes bf16 pairs");
 #pragma unroll
         for (int h = 0; h < 2; ++h) {  // halves of the piece: 8 weights = 2 dwords against one 16-byte piece of x
           uint32_t p[NR][4];
@@ -157,7 +163,7 @@ __device__ __forceinline__ void fma_batch(const u32x4 (&buf)[BATCH], int c0, con
 #pragma unroll
             for (int i = 0; i < NR; ++i)
 #pragma unroll
-              for (int c = 0; c < 4; ++c) acc[i][t] = dot2_bf16(p[i][c], xv[c], acc[i][t]);
+              for (int c = 0; c < 4; ++c) acc[i][t] = ElemBf16::dot2(p[i][c], xv[c], acc[i][t]);
           }
         }
       }
@@ -195,7 +201,7 @@ __device__ __forceinline__ void fma_batch_w4(const u32x4 (&buf)[BATCH], const Sc
 #pragma unroll
           for (int i = 0; i < NR; ++i)
 #pragma unroll
-            for (int c = 0; c < 4; ++c) acc[i][t] = dot2_bf16(p[i][c], xv[c], acc[i][t]);
+            for (int c = 0; c < 4; ++c) acc[i][t] = ElemBf16::dot2(p[i][c], xv[c], acc[i][t]);
         }
       }
     }
@@ -272,8 +278,8 @@ __device__ __forceinline__ bool x_issue(XRegs<NX, NW>& xr, const bf16_t* x, int 
   return fits;
 }
 
-// VMW: the vector loads issued behind the DMAs = two weight batches of the format (F::VLOADS each).
-template <int TT, int NX, int NW, bool DMA, int NT = 256, int VMW = 2 * BATCH>
+// A: the rows' element (F::act); VMW: the vector loads issued behind the DMAs = two weight batches of the format (F::VLOADS each).
+template <class A, int TT, int NX, int NW, bool DMA, int NT = 256, int VMW = 2 * BATCH>
 __device__ __forceinline__ void x_finish(bool in_regs, XRegs<NX, NW>& xr, bf16_t* xs, float* red, const bf16_t* ws,
                                          const bf16_t* x, int ldx, int T, int K, const bf16_t* norm_w, float eps) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -292,7 +298,7 @@ __device__ __forceinline__ void x_finish(bool in_regs, XRegs<NX, NW>& xr, bf16_t
         float s = 0.f;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const float a = bf_lo(xr.x[i][c]), b = bf_hi(xr.x[i][c]);
+          const float a = A::lo(xr.x[i][c]), b = A::hi(xr.x[i][c]);
           s = fmaf(a, a, s);
           s = fmaf(b, b, s);
         }
@@ -316,7 +322,7 @@ __device__ __forceinline__ void x_finish(bool in_regs, XRegs<NX, NW>& xr, bf16_t
           const u32x4 v = *reinterpret_cast<const u32x4*>(xs + (size_t)t * K + p * 8);
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
-            const float a = bf_lo(v[c]), b = bf_hi(v[c]);
+            const float a = A::lo(v[c]), b = A::hi(v[c]);
             ss[t] = fmaf(a, a, ss[t]);
             ss[t] = fmaf(b, b, ss[t]);
           }
@@ -333,7 +339,7 @@ __device__ __forceinline__ void x_finish(bool in_regs, XRegs<NX, NW>& xr, bf16_t
         st16(xs + (size_t)t * K + p * 8, v);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const float a = bf_lo(v[c]), b = bf_hi(v[c]);
+          const float a = A::lo(v[c]), b = A::hi(v[c]);
           ss[t] = fmaf(a, a, ss[t]);
           ss[t] = fmaf(b, b, ss[t]);
         }
@@ -370,8 +376,8 @@ __device__ __forceinline__ void x_finish(bool in_regs, XRegs<NX, NW>& xr, bf16_t
           u32x4 o;
 #pragma unroll
           for (int c = 0; c < 4; ++c)
-            o[c] = pack_bf2(bf_round(bf_lo(xr.x[i][c]) * iv) * bf_lo(xr.w[i < NW ? i : 0][c]),
-                            bf_round(bf_hi(xr.x[i][c]) * iv) * bf_hi(xr.w[i < NW ? i : 0][c]));
+            o[c] = A::pack2(A::round(A::lo(xr.x[i][c]) * iv) * A::lo(xr.w[i < NW ? i : 0][c]),
+                            A::round(A::hi(xr.x[i][c]) * iv) * A::hi(xr.w[i < NW ? i : 0][c]));
           st16(xs + (size_t)q * 8, o);
         }
       }
@@ -385,7 +391,7 @@ __device__ __forceinline__ void x_finish(bool in_regs, XRegs<NX, NW>& xr, bf16_t
         u32x4 o;
 #pragma unroll
         for (int c = 0; c < 4; ++c)
-          o[c] = pack_bf2(bf_round(bf_lo(v[c]) * inv[t]) * bf_lo(wv[c]), bf_round(bf_hi(v[c]) * inv[t]) * bf_hi(wv[c]));
+          o[c] = A::pack2(A::round(A::lo(v[c]) * inv[t]) * A::lo(wv[c]), A::round(A::hi(v[c]) * inv[t]) * A::hi(wv[c]));
         st16(xs + (size_t)t * K + p * 8, o);
       }
     }
@@ -398,10 +404,10 @@ __device__ __forceinline__ void x_finish(bool in_regs, XRegs<NX, NW>& xr, bf16_t
 // taking the three pointers by value makes s_cselect chains there and a slower Wo kernel (profiles/EXPERIMENTS.md).
 #define GEMV_SEG_PICK(r, n0, n1, e0, e1, e2) ((r) < (n0) ? (e0) : ((r) < (n1) ? (e1) : (e2)))
 
-template <class E>
-__device__ __forceinline__ const E* seg_row(const GemvArgs& a, int r) {
-  return GEMV_SEG_PICK(r, a.n0, a.n1, reinterpret_cast<const E*>(a.w0) + (size_t)r * a.K,
-                       reinterpret_cast<const E*>(a.w1) + (size_t)(r - a.n0) * a.K, reinterpret_cast<const E*>(a.w2) + (size_t)(r - a.n1) * a.K);
+template <class Wt>
+__device__ __forceinline__ const Wt* seg_row(const GemvArgs& a, int r) {
+  return GEMV_SEG_PICK(r, a.n0, a.n1, reinterpret_cast<const Wt*>(a.w0) + (size_t)r * a.K,
+                       reinterpret_cast<const Wt*>(a.w1) + (size_t)(r - a.n0) * a.K, reinterpret_cast<const Wt*>(a.w2) + (size_t)(r - a.n1) * a.K);
 }
 // ... of MXFP4 rows (K / 2 bytes each), and the row's block scales (K / 32 bytes)
 __device__ __forceinline__ const uint8_t* seg_row_w4(const GemvArgs& a, int r) {
@@ -427,7 +433,8 @@ constexpr bool norm_mode(int mode) { return mode == GEMV_QKV_ROPE || mode == GEM
 template <class F, int TT, int MODE, int NR, bool DMA, int NWV = 4>
 __device__ __forceinline__ void gemv_body(const GemvArgs& a, const typename F::scale_t* const* scale, char* smem, int block_id, int n_blocks,
                                           int problem) {
-  typedef typename F::elem E;
+  typedef typename F::elem Wt;  // weight storage
+  typedef typename F::act A;    // activations and outputs
   constexpr int RP = NR / 2, U = BATCH / NR;
   bf16_t* xs = reinterpret_cast<bf16_t*>(smem);
   float* red = reinterpret_cast<float*>(smem + (size_t)TT * a.K * 2);
@@ -443,13 +450,13 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, const typename F::s
 
   // MoE: blockIdx.y is the problem (token, slot); pick this problem's expert and input row
   const bf16_t* x = a.x;
-  const E *e1 = nullptr, *e3 = nullptr;
+  const Wt *e1 = nullptr, *e3 = nullptr;
   char* outp = reinterpret_cast<char*>(a.out);
   if (MODE == GEMV_MOE_W13) {
     const int prob = problem;
     const int e = a.sel_idx[prob];
-    e1 = reinterpret_cast<const E*>(a.expert_tab[e * 3 + 0]);
-    e3 = reinterpret_cast<const E*>(a.expert_tab[e * 3 + 2]);
+    e1 = reinterpret_cast<const Wt*>(a.expert_tab[e * 3 + 0]);
+    e3 = reinterpret_cast<const Wt*>(a.expert_tab[e * 3 + 2]);
     x = a.x + (size_t)(prob / a.top_k) * a.ldx;
     outp += (size_t)prob * a.ldo * 2;
   }
@@ -483,8 +490,8 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, const typename F::s
       const int q = (RP == 1 && !F::SCALED) ? uu : min(uu * RP + p, npairs - 1);
       if constexpr (F::BLOCK) {  // (STORE / RESIDUAL / SWIGLU / QKV_ROPE)
         if (MODE == GEMV_SWIGLU) {
-          r.p[2 * p] = reinterpret_cast<const E*>(a.w0) + (size_t)q * (a.K >> 1);
-          r.p[2 * p + 1] = reinterpret_cast<const E*>(a.w1) + (size_t)q * (a.K >> 1);
+          r.p[2 * p] = reinterpret_cast<const Wt*>(a.w0) + (size_t)q * (a.K >> 1);
+          r.p[2 * p + 1] = reinterpret_cast<const Wt*>(a.w1) + (size_t)q * (a.K >> 1);
           r.s[2 * p] = scale[0] + (size_t)q * (a.K >> 5);
           r.s[2 * p + 1] = scale[1] + (size_t)q * (a.K >> 5);
         } else {
@@ -495,14 +502,14 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, const typename F::s
           r.s[2 * p + 1] = seg_scale_row_w4(a, scale, r1);
         }
       } else if (MODE == GEMV_SWIGLU) {
-        r.p[2 * p] = reinterpret_cast<const E*>(a.w0) + (size_t)q * a.K;
-        r.p[2 * p + 1] = reinterpret_cast<const E*>(a.w1) + (size_t)q * a.K;
+        r.p[2 * p] = reinterpret_cast<const Wt*>(a.w0) + (size_t)q * a.K;
+        r.p[2 * p + 1] = reinterpret_cast<const Wt*>(a.w1) + (size_t)q * a.K;
       } else if (MODE == GEMV_MOE_W13) {
         r.p[2 * p] = e1 + (size_t)q * a.K;
         r.p[2 * p + 1] = e3 + (size_t)q * a.K;
       } else {
-        r.p[2 * p] = seg_row<E>(a, 2 * q);
-        r.p[2 * p + 1] = (2 * q + 1 < a.N) ? seg_row<E>(a, 2 * q + 1) : r.p[2 * p];  // odd N: alias, result dropped in the epilogue
+        r.p[2 * p] = seg_row<Wt>(a, 2 * q);
+        r.p[2 * p + 1] = (2 * q + 1 < a.N) ? seg_row<Wt>(a, 2 * q + 1) : r.p[2 * p];  // odd N: alias, result dropped in the epilogue
       }
     }
     return r;
@@ -518,7 +525,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, const typename F::s
   // the row pointers and chunk offset are SELECTED (real rows, or one dummy line) and the BATCH loads are issued
   // unconditionally, which keeps the loop body one basic block and the compiler's wait for one buffer at
   // "the other buffer's BATCH loads may stay in flight".  The trailing loads are never consumed.
-  const E* dummy = reinterpret_cast<const E*>(x);
+  const Wt* dummy = reinterpret_cast<const Wt*>(x);
   auto issue = [&](u32x4 (&buf)[BATCH], ScaleBuf<F>& sb) {
     const bool live = ul < units;
     Rows<F, NR> r;
@@ -538,7 +545,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, const typename F::s
   };
   issue(bufA, sbA);
   issue(bufB, sbB);
-  x_finish<TT, NX, NW, DMA, NWV * 64, 2 * F::VLOADS>(in_regs, xr, xs, red, ws, x, a.ldx, T, a.K, a.norm_w, a.eps);
+  x_finish<A, TT, NX, NW, DMA, NWV * 64, 2 * F::VLOADS>(in_regs, xr, xs, red, ws, x, a.ldx, T, a.K, a.norm_w, a.eps);
 
   float acc[NR][TT];
 #pragma unroll
@@ -616,20 +623,20 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, const typename F::s
           }
           if (!kPairOut) {
             bf16_t* o = reinterpret_cast<bf16_t*>(outp) + (size_t)t * a.ldo + q;
-            *o = f_to_bf(swiglu_bf(v0, v1));
+            *o = A::from_f(A::swiglu(v0, v1));
           } else {
             const int r0 = 2 * q;
             const bool two = r0 + 1 < a.N;
             if (MODE == GEMV_LOGITS) {
               float* o = reinterpret_cast<float*>(outp) + (size_t)t * a.ldo + r0;
-              o[0] = bf_round(v0);
-              if (two) o[1] = bf_round(v1);
+              o[0] = A::round(v0);
+              if (two) o[1] = A::round(v1);
             } else {
-              float y0 = bf_round(v0), y1 = bf_round(v1);
+              float y0 = A::round(v0), y1 = A::round(v1);
               bf16_t* o = reinterpret_cast<bf16_t*>(outp) + (size_t)t * a.ldo + r0;
               if (MODE == GEMV_RESIDUAL) {
-                y0 = bf_lo(ep_res[p]) + y0;
-                if (two) y1 = bf_hi(ep_res[p]) + y1;
+                y0 = A::lo(ep_res[p]) + y0;
+                if (two) y1 = A::hi(ep_res[p]) + y1;
               }
               if (MODE == GEMV_QKV_ROPE) {
                 if (r0 < a.n1) {  // q or k rows: rotate the adjacent pair (rope.py:13-23)
@@ -643,13 +650,13 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, const typename F::s
                   const size_t off = kv_offset(a.kv_layout, a.W, kv_dim, a.head_dim, (size_t)ep_seq, ep_pos % a.W,
                                                (r0 < a.n1) ? r0 - a.n0 : r0 - a.n1);
                   bf16_t* ring = ((r0 < a.n1) ? reinterpret_cast<bf16_t*>(a.cache_k) : reinterpret_cast<bf16_t*>(a.cache_v)) + off;
-                  *reinterpret_cast<uint32_t*>(ring) = pack_bf2(y0, y1);
+                  *reinterpret_cast<uint32_t*>(ring) = A::pack2(y0, y1);
                 }
               }
               if (two) {
-                *reinterpret_cast<uint32_t*>(o) = pack_bf2(y0, y1);
+                *reinterpret_cast<uint32_t*>(o) = A::pack2(y0, y1);
               } else {
-                o[0] = f_to_bf(y0);
+                o[0] = A::from_f(y0);
               }
             }
           }
@@ -699,8 +706,7 @@ inline size_t lds_bytes(int TT, int K, bool norm) { return (size_t)TT * K * 2 + 
 // 2..8 rows that do not, by LDS-DMA.
 inline bool stage_by_dma(int mode, int TT, int K) { return TT > 1 && (size_t)TT * (K >> 3) > (norm_mode(mode) ? 4u : 8u) * 256u; }
 
-// MI_GEMV_MAX_BLOCKS; default 2 blocks per CU (of the first caller's device), measured best on MI355X.  Read once per copy of this
-// namespace: the fp16 compile of gemv.hip has its own.
+// MI_GEMV_MAX_BLOCKS; default 2 blocks per CU (of the first caller's device), measured best on MI355X.  Read once.
 inline int max_blocks(int cus) {
   static int v = 0;
   if (v == 0) {

@@ -953,7 +953,7 @@ static bool g256_f16_args(const GLinearArgs& g, GemmArgs& a) {
   } else {
     a.n0 = a.n1 = g.N;
   }
-  return gemm256_applicable_f16(a);
+  return gemm256_applicable(a);
 }
 
 bool g_linear_fused_ok(int dt, const GLinearArgs& g) {

@@ -60,7 +60,7 @@ struct GemvArgs {
 
 int gemv_max_tokens(int K);
 hipError_t launch_gemv(const GemvArgs& a, hipStream_t s);
-// gemv.hip compiled with -DGEMV_F16=1: the same kernels on fp16 payloads (mi_forward_generic: decode steps of fp16 models)
+// gemv.hip compiled with -DGEMV_F16=1 (element ElemF16, common.cuh): the same kernels on fp16 payloads (mi_forward_generic: decode steps of fp16 models)
 int gemv_max_tokens_f16(int K);
 hipError_t launch_gemv_f16(const GemvArgs& a, hipStream_t s);
 
@@ -132,14 +132,19 @@ struct GemmArgs {
   int rope_cols, rope_dh;         // rope_cols % rope_dh == 0, rope_dh % 4 == 0
   int rope_col0;                  // column of the whole problem at which this (column-sliced) launch starts (% rope_dh == 0)
 };
+// weight row r of up to three matrices side by side (the MFMA GEMMs' DMA sources)
+__device__ __forceinline__ const bf16_t* seg_row(const GemmArgs& g, int r) {
+  if (r < g.n0) return g.w0 + (size_t)r * g.K;
+  if (r < g.n1) return g.w1 + (size_t)(r - g.n0) * g.K;
+  return g.w2 + (size_t)(r - g.n1) * g.K;
+}
 hipError_t launch_gemm(const GemmArgs& a, hipStream_t s);
 bool gemm256_applicable(const GemmArgs& g);  // gemm256.hip: 256x256 tile for the large prefill shapes
 hipError_t launch_gemm256(const GemmArgs& g, hipStream_t s);
 bool gemm256_half_applicable(const GemmArgs& g);  // 128x256 tiles of the same kernel: the columns of a half-filled last round
 hipError_t launch_gemm256_half(const GemmArgs& g, hipStream_t s);
 void gemm_set_tail_mode(int mode);  // mi_debug_set_prefill_kernels
-// gemm256.hip compiled with -DG256_F16=1: the same kernel on fp16 payloads (generic.hip: prefills of fp16 models)
-bool gemm256_applicable_f16(const GemmArgs& g);
+// gemm256.hip compiled with -DG256_F16=1 (element ElemF16): the same kernel on fp16 payloads (generic.hip: prefills of fp16 models; gemm256_applicable is the predicate for both elements)
 hipError_t launch_gemm256_f16(const GemmArgs& g, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------- attention

@@ -22,8 +22,8 @@
   //   G3 = (1, 1): reads A(0, 0), B(0) of tile T + 1  | DMA pieces 0, 1, 2 of tile T + 2 (stage S is free: barrier)
   // RAW: tile T + 1 is read after the barrier that follows every wave's vmcnt(0).  WAR: stage S is overwritten after the
   // barrier that follows every wave's last read of it.
-  bf16x8 aF[2][4], bF[2][2][2];
-#define LDS_FRAG(ADDR) __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(ADDR))
+  E::x8 aF[2][4], bF[2][2][2];
+#define LDS_FRAG(ADDR) __builtin_bit_cast(E::x8, *reinterpret_cast<const u32x4*>(ADDR))
 #define RD_A(BUF, KS, HA, SB)                                                                     \
   _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                   \
     aF[BUF][i] = LDS_FRAG((SB) + (HA) * HALF_BYTES + a_off + i * 2048 + ((KS) ? sw1 : sw0));
@@ -35,8 +35,8 @@
   _Pragma("unroll") for (int hb = 0; hb < 2; ++hb)                                                \
   _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                   \
   _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                   \
-    acc[HA][hb][i][j] = kSwap ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(bF[BB][hb][j], aF[AB][i], acc[HA][hb][i][j], 0, 0, 0) \
-                              : __builtin_amdgcn_mfma_f32_16x16x32_bf16(aF[AB][i], bF[BB][hb][j], acc[HA][hb][i][j], 0, 0, 0);
+    acc[HA][hb][i][j] = kSwap ? E::mfma16(bF[BB][hb][j], aF[AB][i], acc[HA][hb][i][j]) \
+                              : E::mfma16(aF[AB][i], bF[BB][hb][j], acc[HA][hb][i][j]);
   // piece D (0..7) of a tile: half D >> 1 in the order A0 B0 B1 A1, 1-KiB piece D & 1
 #define PIECE(D, KT, STAGE)                                                                       \
   do {                                                                                            \
@@ -121,13 +121,13 @@
 #undef LDS_FRAG
 #undef STAGE_HALF
 #else
-  bf16x8 af[2][4];                  // [k step][row fragment] of the A half in use
-  bf16x8 b0x[2][2], b1[2][2];       // [k step][column fragment] of B half 0 / 1
+  E::x8 af[2][4];                  // [k step][row fragment] of the A half in use
+  E::x8 b0x[2][2], b1[2][2];       // [k step][column fragment] of B half 0 / 1
 #if G256_BAL
-  bf16x8 b0y[2][2];                 // B half 0 of the NEXT K tile (fetched while this tile's last quadrant still uses b0x)
+  E::x8 b0y[2][2];                 // B half 0 of the NEXT K tile (fetched while this tile's last quadrant still uses b0x)
 #endif
 
-#define LDS_FRAG(ADDR) __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(ADDR))
+#define LDS_FRAG(ADDR) __builtin_bit_cast(E::x8, *reinterpret_cast<const u32x4*>(ADDR))
 #define READ_A(HA, SB)                                                               \
   if (!((G256_ABL == 2 || (G256_ABL >= 4 && G256_ABL != 8)) && abl_skip)) {                                                \
     _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                  \
@@ -182,7 +182,7 @@
   _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                              \
   _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                                 \
   _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                                 \
-    acc32[HA][HB][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(BF[ks][j], af[ks][i * 2 + j], acc32[HA][HB][j], 0, 0, 0);
+    acc32[HA][HB][j] = E::mfma32(BF[ks][j], af[ks][i * 2 + j], acc32[HA][HB][j]);
 #elif G256_ABL == 6
   // the same with 8 independent accumulators per quadrant-time (what a 4 x 2 layout of 32x32 tiles per wave would give)
   f32x16 acc32[2][2][2];
@@ -198,15 +198,15 @@
   _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                              \
   _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                                 \
   _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                                 \
-    acc32[ks][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(BF[ks][j], af[ks][i * 2 + j], acc32[ks][i][j], 0, 0, 0);
+    acc32[ks][i][j] = E::mfma32(BF[ks][j], af[ks][i * 2 + j], acc32[ks][i][j]);
 #else
 #define MFMA_QUAD(HA, HB, BF)                                                                                   \
   if (!((G256_ABL == 3 || G256_ABL >= 7) && abl_skip)) {                                                                           \
   _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                              \
   _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                 \
   _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                                 \
-    acc[HA][HB][i][j] = kSwap ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(BF[ks][j], af[ks][i], acc[HA][HB][i][j], 0, 0, 0) \
-                              : __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ks][i], BF[ks][j], acc[HA][HB][i][j], 0, 0, 0); \
+    acc[HA][HB][i][j] = kSwap ? E::mfma16(BF[ks][j], af[ks][i], acc[HA][HB][i][j]) \
+                              : E::mfma16(af[ks][i], BF[ks][j], acc[HA][HB][i][j]); \
   }
 #endif
 
@@ -342,8 +342,8 @@
 #define MFMA_KS(HA, HB, BF, KS)                                                                                 \
   _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                 \
   _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                                 \
-    acc[HA][HB][i][j] = kSwap ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(BF[KS][j], af[KS][i], acc[HA][HB][i][j], 0, 0, 0) \
-                              : __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[KS][i], BF[KS][j], acc[HA][HB][i][j], 0, 0, 0);
+    acc[HA][HB][i][j] = kSwap ? E::mfma16(BF[KS][j], af[KS][i], acc[HA][HB][i][j]) \
+                              : E::mfma16(af[KS][i], BF[KS][j], acc[HA][HB][i][j]);
 #define PHASE(READS, COND, HALF, KT, STAGE, WAIT, HA, HB, BF)   \
   READS                                                         \
   if (COND) PIECE1(HALF, 0, KT, STAGE);                         \
