@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "lib", "libmistral_hip.so")
 SOURCES = ["api.hip", "gemv.hip", "gemm.hip", "gemm256.hip", "attn_decode.hip", "attn_prefill.hip", "elementwise.hip",
-           "decode_engine.hip", "sampling.hip", "rccl_api.hip", "generic.hip", "lora.hip", "gemv_w8.hip", "gemv_w4.hip"]
+           "decode_engine.hip", "decode_engine_host.hip", "sampling.hip", "rccl_api.hip", "generic.hip", "lora.hip", "gemv_w8.hip", "gemv_w4.hip"]
 # (this file is a dependency of every object: a change of flags must rebuild them - round 6: decode_engine_next.o was once shipped
 # without a flag that had just been added here)
 HEADERS = [os.path.abspath(__file__), os.path.join(CSRC, "common.cuh"), os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "gemv_core.cuh"),
@@ -23,6 +23,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # Per-file flags.  The persistent decode engine is built with the max-memory-clause scheduling strategy: measured 1.3-1.5 % faster
 # on a good lease and 3 % on a slow one than the default strategy (same-box A/B of five flag variants, profiles/EXPERIMENTS.md) -
 # the kernel's speed is a chaotic function of its code, so this is an observation, not a principle.  MI_ENGINE_FLAGS overrides.
+# (decode_engine.hip holds the kernels only; the engine's host side, decode_engine_host.hip, is compiled once with the plain FLAGS.)
 PER_FILE_FLAGS = {"decode_engine.hip": os.environ.get("MI_ENGINE_FLAGS", "-mllvm -amdgpu-sched-strategy=max-memory-clause").split()}
 
 

@@ -20,12 +20,6 @@
 #include "../../include/mistral_hip_debug.h"
 #include "kernels.h"
 
-#ifdef MI_SLOT_LIST  // experiment libraries: see kBuilds below
-#define X(n) const EngineBuild& decode_engine_build_x##n();
-MI_SLOT_LIST
-#undef X
-#endif
-
 namespace {
 
 thread_local char g_detail[512] = "";
@@ -60,68 +54,6 @@ constexpr size_t TICKET_BYTES = 4096;  // first words: control block of the pers
 // 1 (default): batch-1 decode steps of dense models run on the persistent engine (decode_engine.hip) when the shapes
 // allow it; 0: always the launch path.  MI_DECODE_ENGINE sets the initial value, mi_set_decode_engine changes it.
 int g_engine_mode = -1;
-bool nemo_engine_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("MI_ENGINE_NEMO");
-    on = e ? atoi(e) != 0 : 0;  // measured (round 6): 5.15-5.17 ms per step against 4.94-4.95 on the launch path at the Nemo-12B dims
-  }
-  return on != 0;
-}
-int g_engine_variant = -1;  // 0 (default): the shipped engine build first (MoE: the wide build first); 1: wide first; 2: shipped first
-int engine_variant() {
-  if (g_engine_variant < 0) {
-    const char* e = getenv("MI_ENGINE_VARIANT");
-    g_engine_variant = e ? atoi(e) : 0;
-  }
-  return g_engine_variant;
-}
-// Every compile of the engine source (kernels.h: EngineBuild).  Experiment libraries (scripts/build_variants.py engine_slots ->
-// -DMI_SLOT_LIST="X(0) X(1) ...") append further compiles under the names *_x<N>, selected at run time by mi_debug_set_engine_slot
-// (scripts/engine_ab.py: one process, one set of weights, every slot timed in turn on the same box).
-enum { B_DEFAULT, B_NEXT, B_NEMO, B_WIDE, B_MOE, N_SHIPPED };
-#ifdef MI_SLOT_LIST
-#define X(n) &decode_engine_build_x##n(),
-#define ENGINE_SLOTS MI_SLOT_LIST
-#else
-#define ENGINE_SLOTS
-#endif
-const EngineBuild* const kBuilds[] = {&decode_engine_build(), &decode_engine_build_next(), &decode_engine_build_nemo(),
-                                      &decode_engine_build_wide(), &decode_engine_build_moe(), ENGINE_SLOTS};
-constexpr int N_SLOTS = (int)(sizeof(kBuilds) / sizeof(kBuilds[0])) - N_SHIPPED;
-int g_slot = -1;  // experiment slot that mi_forward tries first (-1: none)
-
-// Which builds a batch-1 decode step tries, in order: calls try_build(build) for each applicable one until it returns true (the
-// step is finished, or failed); a build whose launch declined (residency census) returns false and the next stage is asked.
-// Lazy: on the headline model `next` is the only applicable() called per step.  variant: mi_debug_set_engine_variant;
-// pr.forced = (variant == 1) is the caller's.  Returns whether a try_build returned true (false: take the launch path).
-template <class Try>
-bool engine_route(int variant, bool nemo_opt_in, const EngineBuild* slot, const EngProblem& pr, Try&& try_build) {
-  const bool moe = pr.E > 0;
-  if (pr.lora_rank > 0) return false;  // un-merged LoRA adapters: no engine build carries them, the launch path does (lora.hip)
-  if (pr.quant) return false;          // quantised weight bytes: no engine build reads them, the launch path does (gemv_w8.hip, gemv_w4.hip)
-  if (kv_e4m3(pr.kv_layout)) return false;  // K/V rings of e4m3 bytes: no engine build reads them, the launch path does (attn_decode.hip)
-  auto takes = [&](int b) { return kBuilds[b]->applicable(pr, nullptr, 0); };
-  if (slot && slot->applicable(pr, nullptr, 0) && try_build(*slot)) return true;
-  // the dense GQA-4 headline shapes: the `next` compile (build_native.ENGINE_NEXT_FLAGS)
-  if (!moe && variant == 0 && takes(B_NEXT) && try_build(*kBuilds[B_NEXT])) return true;
-  // large dims whose rows are not multiples of 4 pieces (Mistral-Nemo): the `nemo` compile - bit-equal, in a clean regime
-  // (scripts/engine_loader_waits.py) and still 4 % slower than the launch path at those dims (contiguous 20- / 40-piece units:
-  // four consumer waves cannot all hold one in the 128-piece ring), so it is opt-in: MI_ENGINE_NEMO=1 or engine variant 3 (tests)
-  if (!moe && (variant == 3 || (variant == 0 && nemo_opt_in)) && takes(B_NEMO) && try_build(*kBuilds[B_NEMO])) return true;
-  // Exactly one of the rest.  MoE models: the 8-fill MoE build where the model fits it (Mixtral-8x7B), else the 7-fill wide build
-  // (Mixtral-8x22B) wherever it applies - both carry the round-4 router (two experts per wave, batched loads: -8..-11 us per
-  // layer), which the default object - frozen, see decode_engine.hip - does not.  Dense models: the default build, and the wide
-  // one for what it declines (GQA ratio 6; rows of 10 pieces when forced).  Variant 1 (tests) prefers the wide build wherever
-  // it applies, so that its code paths can be compared bit for bit at small sizes; variant 2 = default build first for every model.
-  const bool wide_first = variant == 1 || (variant == 0 && moe);
-  const int last = (moe && variant == 0 && takes(B_MOE)) ? B_MOE
-                   : (wide_first && takes(B_WIDE))       ? B_WIDE
-                   : takes(B_DEFAULT)                    ? B_DEFAULT
-                   : (!wide_first && takes(B_WIDE))      ? B_WIDE
-                                                         : -1;
-  return last >= 0 && try_build(*kBuilds[last]);
-}
 int engine_mode() {
   if (g_engine_mode < 0) {
     const char* e = getenv("MI_DECODE_ENGINE");
@@ -1081,8 +1013,7 @@ int mi_debug_engine_sabotage(void* workspace, int launches, mi_stream_t stream) 
 }
 
 int mi_decode_engine_census(int forget) {
-  if (forget)
-    for (const EngineBuild* b : kBuilds) b->forget_census();
+  if (forget) decode_engine_forget_census();
   return MI_OK;
 }
 
@@ -1094,42 +1025,21 @@ int mi_decode_engine_status(const void* workspace, mi_stream_t stream, uint32_t 
 
 size_t mi_debug_engine_trace_bytes(void) { return decode_engine_trace_bytes(device_cus()); }
 int mi_debug_set_engine_knobs(int thin, int depth) {
-  for (const EngineBuild* b : kBuilds) b->set_knobs(thin, depth);
+  decode_engine_set_knobs(thin, depth);
   return MI_OK;
 }
 int mi_debug_set_engine_holders(int on) {
-  for (const EngineBuild* b : kBuilds) b->set_holders(on);
+  decode_engine_set_holders(on);
   return MI_OK;
 }
-int mi_debug_set_engine_variant(int variant) {
-  const int prev = engine_variant();
-  g_engine_variant = variant < 0 || variant > 3 ? 0 : variant;
-  return prev;
-}
+int mi_debug_set_engine_variant(int variant) { return decode_engine_set_variant(variant); }
 int mi_debug_engine_route(int dim, int n_heads, int n_kv_heads, int hidden_dim, int vocab, int num_experts, int top_k, int n_layers,
                           int cache_size, int n_cus, int variant, int nemo_opt_in, char* out, size_t out_len) {
   if (!out || !out_len || n_layers <= 0 || n_layers > 4096 || n_cus <= 0) return fail(MI_ERR_ARG, "mi_debug_engine_route");
-  int32_t W[4096];
-  for (int l = 0; l < n_layers; ++l) W[l] = cache_size;
-  EngProblem pr;
-  memset(&pr, 0, sizeof(pr));
-  pr.D = dim; pr.H = n_heads; pr.Hkv = n_kv_heads; pr.F = hidden_dim; pr.V = vocab; pr.n_layers = n_layers; pr.NB = n_cus;
-  pr.E = num_experts; pr.top_k = top_k; pr.W = W;
-  pr.forced = variant == 1;
-  size_t n = 0;
-  out[0] = 0;
-  engine_route(variant, nemo_opt_in != 0, nullptr, pr, [&](const EngineBuild& b) {  // "declined": the whole chain is listed
-    if (n < out_len) n += snprintf(out + n, out_len - n, "%s%s", n ? "," : "", b.name);
-    return false;
-  });
+  const size_t n = decode_engine_route_names(dim, n_heads, n_kv_heads, hidden_dim, vocab, num_experts, top_k, n_layers, cache_size, n_cus,
+                                             variant, nemo_opt_in != 0, out, out_len);
   return n < out_len ? MI_OK : fail(MI_ERR_ARG, "mi_debug_engine_route: out_len %zu", out_len);
 }
-#ifdef MI_SLOT_LIST
-extern "C" int mi_debug_set_engine_slot(int slot) {  // -1: the library's own routing; returns the number of slots
-  g_slot = slot < 0 || slot >= N_SLOTS ? -1 : slot;
-  return N_SLOTS;
-}
-#endif
 int mi_debug_gemv_w4_row_pairs(int n_pairs, int n_cus) { return gemv_w4_row_pairs(n_pairs, n_cus); }
 int mi_debug_set_prefill_kernels(int attn_waves, int gemm_tail) {
   attn_prefill_set_mode(attn_waves);
@@ -1137,7 +1047,7 @@ int mi_debug_set_prefill_kernels(int attn_waves, int gemm_tail) {
   return MI_OK;
 }
 int mi_debug_set_engine_trace(void* dev_buffer) {
-  for (const EngineBuild* b : kBuilds) b->set_trace(dev_buffer);
+  decode_engine_set_trace(dev_buffer);
   return MI_OK;
 }
 
@@ -1221,25 +1131,14 @@ static int forward_body(const char* entry, const mi_model_t* m, const QuantModel
     }
     pr.granules = ws.gran; pr.granule_bytes = ws.gran_bytes; pr.ctrl = engine_ctrl;
     pr.E = m->num_experts; pr.top_k = m->top_k; pr.lora_rank = m->lora_rank; pr.quant = q != nullptr;
-    pr.forced = engine_variant() == 1;
-    bool dense_ok = true;
-    for (int l = 0; l < m->n_layers; ++l)
-      dense_ok = dense_ok && (m->num_experts ? (m->layers[l].gate && m->layers[l].expert_w_dev)
-                                             : (m->layers[l].w1 && m->layers[l].w2 && m->layers[l].w3));
-    const EngineBuild* slot = g_slot >= 0 ? kBuilds[N_SHIPPED + g_slot] : nullptr;
-    int rc = MI_OK;
-    auto try_build = [&](const EngineBuild& b) {  // true: the step is finished, rc says how; false: the build declined
-      bool declined = false;
-      rc = hip_rc(b.launch(pr, s, &declined), &b == slot ? "decode engine (experiment slot)" : "decode engine");
-      if (rc == MI_OK && declined) {
-        if (&b != slot) snprintf(g_detail, sizeof(g_detail), "decode engine declined: %s", b.census_detail());  // informational
-        return false;
-      }
+    const EngStep step = decode_engine_step(pr, s);  // the builds of the route in turn: the first that takes the step ran it
+    if (step.declined) snprintf(g_detail, sizeof(g_detail), "decode engine declined: %s", decode_engine_census_detail());  // informational
+    if (step.ran) {
+      int rc = hip_rc(step.err, step.what);
       if (rc == MI_OK && m->final_norm && !bt->logits) rc = hip_rc(launch_rmsnorm(h, h, m->final_norm, T, D, m->norm_eps, s), "final norm");
       if (rc == MI_OK && want_topp) rc = sample_step(bt, m, true, engine_ctrl, s);
-      return true;
-    };
-    if (dense_ok && engine_route(engine_variant(), nemo_engine_enabled(), slot, pr, try_build)) return rc;
+      return rc;
+    }
   }
 
   if (branch == MI_BRANCH_DECODE && embed) {

@@ -154,7 +154,7 @@
 #define ENG_STR_(x) #x
 #define ENG_STR(x) ENG_STR_(x)
 // What needs a linker name of its own per compile: the accessor to this build's descriptor (kernels.h: EngineBuild, at the end of
-// this file) and the census kernel.  Every other host function is local to the object.
+// this file).  Nothing else leaves the object.
 #if defined(ENG_SUFFIX)
 #define ENG_NAME(x) ENG_CAT(x, ENG_SUFFIX)
 #define ENG_BUILD_NAME (ENG_STR(ENG_SUFFIX) + 1)  // "_next" -> "next"
@@ -167,9 +167,7 @@
 #else
 #define ENG_NAME(x) x
 #define ENG_BUILD_NAME "default"
-#define ENG_DEFAULT_BUILD 1
 #endif
-#define engine_census_kernel ENG_NAME(engine_census_kernel)
 
 namespace {
 
@@ -228,13 +226,11 @@ enum : int {
   C_EXPERT = 20,    // MoE: ((layer + 1) << 16) | expert A | expert B << 8 (ascending ids) once the router has decided (consumers -> loader)
   C_RLOGIT = 24     // [16] MoE: bf16-rounded router logits of the layer (fp32 words)
 };
-constexpr uint32_t ARRIVE_POLLS = 1u << 16;  // ~50 ms: far beyond the ~1 us over which a resident grid starts
 
 // Optional timeline (mi_debug_set_engine_trace): trace[c][layer][event] = 100 MHz wall clock.  Consumer wave 0 writes
 // events [0, TR_CONS), the loader events [TR_CONS, TR_EVENTS).  The buffer is reached through an explicit
 // global-address-space pointer held in `Shared`: a store through a generic pointer loaded from the by-value argument
-// struct makes hipcc spill the whole struct to scratch.
-constexpr int TR_CONS = 18, TR_EVENTS = 26;
+// struct makes hipcc spill the whole struct to scratch.  (TR_CONS, TR_EVENTS: kernels.h)
 
 struct Shared {
   lvu32* ctl;
@@ -2237,304 +2233,38 @@ __global__ __launch_bounds__(NTHREADS, 1) void decode_engine_kernel(const EngArg
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ host side
-namespace {
-struct GranLayout {
-  uint32_t g_h, g_qkv, g_att, g_h1, g_hid, g_hid2, g_part, g_amax, total;
-};
-constexpr int AMAX_MAX_NB = 1024;  // workgroups the greedy-sampling edge is sized for (decode_engine_applicable: NB <= 1024)
-GranLayout gran_layout(int D, int H, int Hkv, int F, int max_splits) {
-  using attn_core::DH;
-  const int Rtot = H / Hkv, R = attn_decode_group(Rtot), Hs = Hkv * (Rtot / R);
-  GranLayout g;
-  uint32_t off = 0;
-  g.g_h = off;    off += D / 2;
-  g.g_qkv = off;  off += (H + 2 * Hkv) * DH / 2;
-  g.g_att = off;  off += H * DH / 2;
-  g.g_h1 = off;   off += D / 2;
-  g.g_hid = off;  off += F / 2;
-  g.g_hid2 = off; off += F / 2;  // MoE: hid of the second expert
-  g.g_part = off; off += (uint32_t)((size_t)Hs * max_splits * R * (DH + 2));
-  g.g_amax = off; off += 4 * AMAX_MAX_NB;  // (max logit, argmax, sum exp, pad) per workgroup
-  g.total = off;
-  return g;
-}
-}  // namespace
-
-#ifdef ENG_DEFAULT_BUILD  // the same for every build: compiled into the default object only
-size_t decode_engine_granule_bytes(int D, int H, int Hkv, int F, int maxW) {
-  if (Hkv <= 0 || H % Hkv) return 0;
-  (void)maxW;  // sized for the maximum of 32 splits so that the layout depends on the model only
-  return (size_t)gran_layout(D, H, Hkv, F, 32).total * 8;
-}
-size_t decode_engine_trace_bytes(int NB) { return (size_t)NB * ENG_MAXL * TR_EVENTS * sizeof(uint64_t); }
-#endif
-
-static bool decode_engine_applicable(const EngProblem& pr, char* why, size_t why_len) {
-  auto no = [&](const char* m) {
-    if (why) snprintf(why, why_len, "%s", m);
-    return false;
-  };
-  using attn_core::DH;
-  if (pr.D % 512 || pr.F % 512 || (pr.H * DH) % 512) return no("dim / hidden_dim / n_heads*128 not a multiple of 512");
-  if (pr.D > 8192) return no("dim > 8192 (fused RMSNorm holds 4 pieces per thread)");
-  // Large dims that are not a multiple of 2048 (Mistral-Nemo: 5120 = rows of 10 pieces, streamed in 2-piece groups, no holder
-  // waves): 7.6-8.0 ms per step on the engine against 5.0 ms on the launch path (profiles/EXPERIMENTS.md) - such models
-  // take the launch path.  Small dims (the parity tests) stay on the engine.
-#if !ENG_WIDE
-#if ENG_HEADLINE_ONLY != 2
-  if (pr.D > 3072 && ((pr.D >> 9) & 3) != 0) return no("dim > 3072 and not a multiple of 2048: the launch path is faster (Nemo dims)");
-#endif
-#else
-  // The wide build streams such rows as contiguous units (Loader::unit) - the third form tried for the Nemo dims, and still
-  // slower than the launch path there: 5.47 vs 4.94 ms per step at an 8192-token context (profiles/EXPERIMENTS.md round 4;
-  // 2-piece groups: 7.6-8.0 ms, 4 + 4 + 2 groups: 5.62 ms).  Declined unless the caller forces the wide build (traces, tests).
-#if ENG_HEADLINE_ONLY != 2  // (the `nemo` build exists for exactly these dims)
-  if (pr.D > 3072 && ((pr.D >> 9) & 3) != 0 && !pr.forced) return no("dim > 3072 and not a multiple of 2048: the launch path is faster (Nemo dims)");
-#endif
-  if (((pr.D >> 9) & 1) && pr.D > 3072) return no("odd number of 512-element pieces per row at a large dim");
-#endif
-  if (pr.V % 2) return no("odd vocab");
-#if ENG_HEADLINE_ONLY == 1
-  if (pr.E || pr.H != 4 * pr.Hkv || pr.D % 2048 || (pr.H * DH) % 2048 || pr.F % 2048)
-    return no("this build instantiates the dense GQA-4 kernel for rows of 4-piece groups only");
-#elif ENG_HEADLINE_ONLY == 2
-  if (pr.E || pr.H != 4 * pr.Hkv || !(pr.D % 2048 || (pr.H * DH) % 2048 || pr.F % 2048) || pr.D <= 3072)
-    return no("this build instantiates the dense GQA-4 kernel for large dims whose rows are not all 4-piece groups only (Mistral-Nemo)");
-#elif ENG_WIDE == 2
-  if (!pr.E) return no("the 8-fill MoE build takes MoE models only");
-#endif
-  const int kmax = pr.D > pr.F ? (pr.D > pr.H * DH ? pr.D : pr.H * DH) : (pr.F > pr.H * DH ? pr.F : pr.H * DH);
-  const size_t region = (size_t)LDS_TOTAL - RING_FILLS * FILL * PIECE - XS_OFF;  // activation vector / attention scratch
-  if ((size_t)kmax * 2 > region) return no("activation vector does not fit beside the 8-fill ring");
-  if (pr.E) {
-    if (pr.E > 16 || pr.top_k != 2) return no("MoE: at most 16 experts, top-2 routing");
-#if ENG_WIDE
-    if ((size_t)pr.D * 6 > region) return no("MoE: normalised + raw + router-normalised activation vector");
-#else
-    if ((size_t)pr.D * 4 > region) return no("MoE: normalised + raw activation vector");
-#endif
-    if ((size_t)pr.F * 2 + (size_t)((pr.D / 2 + pr.NB - 1) / pr.NB) * 8 > region) return no("MoE: hid vector + per-unit partial sums");
-  }
-  if ((size_t)pr.D * 2 + (size_t)((pr.V / 2 + pr.NB - 1) / pr.NB) * 8 + 16 + (size_t)pr.NB * 16 > region)
-    return no("LM-head logits stash + greedy reduction staging");
-  const int NB = pr.NB;
-  if (NB < 8 || NB > 1024) return no("CU count");
-  if (((pr.D / 2 + NB - 1) / NB) * 2 * 2 > RES_BYTES) return no("residual slab");
-  if (pr.Hkv <= 0 || pr.H % pr.Hkv) return no("heads");
-  const int Rtot = pr.H / pr.Hkv;
-  const int R = attn_decode_group(Rtot);
-#if ENG_WIDE == 2
-  if (R != 4) return no("GQA group size (the 8-fill MoE build instantiates 4)");
-#elif ENG_WIDE
-  if (R != 4 && R != 6) return no("GQA group size (the wide build instantiates 4 and 6)");
-#else
-  if (R != 1 && R != 2 && R != 4 && R != 8) return no("GQA group size");
-#endif
-  const int Hs = pr.Hkv * (Rtot / R);
-  const int ne_max = ((pr.H * DH / 2 + NB - 1) / NB) * 2;
-  if (ne_max > 64) return no("split-merge slab");
-#if ENG_WIDE
-  // q (R*64 words) | k, v of this step (128 words) | m, l (8R floats) | acc (4 R DH floats) | merge staging (3 * 32 * ne words)
-  if ((size_t)R * 256 + 512 + (size_t)R * 32 + (size_t)4 * R * DH * 4 + (size_t)3 * 32 * ne_max * 4 > region) return no("attention scratch");
-#else
-  if ((size_t)R * (256 + 2 * DH * 16 + 32) + 512 + (size_t)3 * 32 * ne_max * 4 > region) return no("attention scratch");
-#endif
-  for (int l = 0; l < pr.n_layers; ++l) {
-    const int ns = attn_decode_splits(pr.W[l]);
-    if (ns > 32 || Hs * ns > NB) return no("more attention work items than CUs");
-#if ENG_WIDE
-    // ratio 6 serves its heads in two passes over K/V pieces that must all sit in the LDS ring (run_consumer)
-    if (R == 6 && 2 * ((attn_core::split_chunk(pr.W[l], ns) + 3) >> 2) > (RING_FILLS - 2) * FILL) return no("GQA ratio 6: ring longer than 5120 slots");
-#endif
-  }
-  return true;
-}
-
-namespace {
-uint64_t* g_trace = nullptr;
-int g_thin = -1, g_depth = -1, g_holders = -1;
-void decode_engine_set_holders(int on) { g_holders = on; }
-void decode_engine_set_knobs(int thin, int depth) {
-  g_thin = thin;
-  g_depth = depth;
-}
-void decode_engine_set_trace(void* dev_buffer) { g_trace = (uint64_t*)dev_buffer; }
-}  // namespace
-
-// ---- residency census (once per device and process, outside any stream capture) ------------------------------------------
-// The engine's hand-offs need all NB workgroups resident at once.  hipOccupancy... answers for an empty device; a CU mask,
-// a partition mode or a co-tenant kernel changes the real answer, and a plain launch applies no check (MI355X_MICROARCH.md
-// "Residency and cooperative launch").  So before the engine is used on a device the first time, a probe kernel with the
-// engine's exact launch shape (512 threads, 160 KiB LDS) is run: every workgroup counts itself in and waits (bounded) for
-// the others.  A failed census disables the engine for this device - the launch path is bit-identical and needs nothing.
-// The per-step residency gate in the kernel covers what changes later (run_consumer).
-__global__ __launch_bounds__(NTHREADS, 1) void engine_census_kernel(uint32_t* words, int nb) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  (void)smem;
-  if (threadIdx.x != 0) return;
-  __hip_atomic_fetch_add(words, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  for (uint32_t polls = 0; polls < ARRIVE_POLLS; ++polls) {
-    if (__hip_atomic_load(words, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= (uint32_t)nb) return;
-    __builtin_amdgcn_s_sleep(8);
-  }
-  __hip_atomic_store(words + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // somebody never showed up
-}
-
-namespace {
-// 0 unknown, 1 passed, -1 failed; per device
-int g_census[64] = {};
-char g_census_why[160] = "";
-
-int engine_census(int dev, int nb, uint32_t* ctrl, hipStream_t s) {
-  if (dev < 0 || dev >= 64) return -1;
-  if (g_census[dev] != 0) return g_census[dev];
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return 0;  // cannot probe now
-  const void* fn = (const void*)engine_census_kernel;
-  int per_cu = 0;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, NTHREADS, LDS_TOTAL) != hipSuccess || per_cu < 1) {
-    snprintf(g_census_why, sizeof(g_census_why), "occupancy query: %d workgroups of %d threads + %d B LDS per CU", per_cu, NTHREADS, LDS_TOTAL);
-    return g_census[dev] = -1;
-  }
-  uint32_t* words = ctrl + CTRL_CENSUS0;  // two spare control words of the caller's workspace (the ABI never allocates)
-  uint32_t host[2] = {0, 0};
-  bool ok = hipMemsetAsync(words, 0, 8, s) == hipSuccess;
-  if (ok) {
-    void* params[] = {(void*)&words, (void*)&nb};
-    ok = hipLaunchKernel(fn, dim3(nb), dim3(NTHREADS), params, LDS_TOTAL, s) == hipSuccess &&
-         hipMemcpyAsync(host, words, 8, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-  }
-  if (!ok || host[1] != 0 || host[0] != (uint32_t)nb) {
-    snprintf(g_census_why, sizeof(g_census_why), "census: %u of %d workgroups resident together (CU mask / partition / co-tenant?)",
-             host[0], nb);
-    return g_census[dev] = -1;
-  }
-  return g_census[dev] = 1;
-}
-const char* decode_engine_census_detail() { return g_census_why; }
-void decode_engine_forget_census() { memset(g_census, 0, sizeof(g_census)); }
-}  // namespace
-
-static hipError_t launch_decode_engine(const EngProblem& pr, hipStream_t s, bool* declined) {
-  if (declined) *declined = false;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (engine_census(dev, pr.NB, pr.ctrl, s) < 0) {  // not all workgroups can be resident: the caller takes the launch path
-    if (declined) *declined = true;
-    return hipSuccess;
-  }
-  EngArgs a;
-  memset(&a, 0, sizeof(a));
-  a.trace = (unsigned long long*)g_trace;
-  if (g_thin < 0) {
-    const char* e = getenv("MI_ENGINE_THIN");
-    g_thin = e ? atoi(e) : 2;  // 0 stream through sweeps, 1 one fill in flight, 2 stop (measured best)
-  }
-  if (g_depth < 0) {
-    const char* e = getenv("MI_ENGINE_DEPTH");
-    g_depth = e ? atoi(e) : 2;  // measured: 2 fills in flight (plus the one being issued) beats 3
-  }
-  a.thin = g_thin;
-  a.depth = g_depth;
-  if (g_holders < 0) {
-    const char* e = getenv("MI_ENGINE_HOLDERS");
-    g_holders = e ? (atoi(e) != 0) : 1;
-  }
-  a.holders = g_holders;
-  a.D = pr.D; a.H = pr.H; a.Hkv = pr.Hkv; a.F = pr.F; a.V = pr.V; a.eps = pr.eps; a.NB = pr.NB;
-  const int Rtot = pr.H / pr.Hkv;
-  a.R = attn_decode_group(Rtot);
-  a.kv_groups = Rtot / a.R;
-  a.Hs = pr.Hkv * a.kv_groups;
-  a.ring_fills = RING_FILLS;
-  a.h = (bf16_t*)pr.h; a.rope_cs = pr.rope_cs;
-  a.kv_seqlens = pr.kv_seqlens; a.q_start = pr.q_start; a.kv_before = pr.kv_before; a.tok_seq = pr.tok_seq; a.tok_pos = pr.tok_pos;
-  a.final_norm = (const bf16_t*)pr.final_norm; a.output = (const bf16_t*)pr.output; a.logits = pr.logits;
-  a.gran = (uint64_t*)pr.granules; a.ctrl = pr.ctrl;
-  const GranLayout gl = gran_layout(pr.D, pr.H, pr.Hkv, pr.F, 32);
-  a.g_h = gl.g_h; a.g_qkv = gl.g_qkv; a.g_att = gl.g_att; a.g_h1 = gl.g_h1; a.g_hid = gl.g_hid; a.g_part = gl.g_part;
-  a.g_amax = gl.g_amax; a.g_hid2 = gl.g_hid2; a.E = pr.E;
-  if ((size_t)gl.total * 8 > pr.granule_bytes || !pr.kv_seqlens) return hipErrorInvalidValue;
-
-  for (int l0 = 0; l0 < pr.n_layers; l0 += ENG_MAXL) {
-    const int nl = pr.n_layers - l0 < ENG_MAXL ? pr.n_layers - l0 : ENG_MAXL;
-    const bool last = l0 + nl == pr.n_layers;
-    a.n_layers = nl;
-    a.seq_base = l0;
-    a.first = 1;  // every launch starts from the residual stream in global memory (the first one: or the embedding row)
-    a.emb = l0 == 0 ? (const bf16_t*)pr.emb : nullptr;
-    a.ids = pr.ids;
-    a.commit = last;
-    a.head = last && pr.logits != nullptr;
-    const bool greedy = a.head && pr.greedy_tok && pr.greedy_lp;
-    a.greedy_tok = greedy ? pr.greedy_tok : nullptr;
-    a.greedy_lp = greedy ? pr.greedy_lp : nullptr;
-    a.hist_tok = greedy && pr.hist_lp ? pr.hist_tok : nullptr;
-    a.hist_lp = greedy && pr.hist_tok ? pr.hist_lp : nullptr;
-    a.hist_len = pr.hist_len;
-    for (int l = 0; l < nl; ++l) {
-      const mi_layer_t& M = pr.layers[l0 + l];
-      EngLayer& L = a.L[l];
-      L.an = (const bf16_t*)M.attention_norm; L.wq = (const bf16_t*)M.wq; L.wk = (const bf16_t*)M.wk;
-      L.wv = (const bf16_t*)M.wv; L.wo = (const bf16_t*)M.wo; L.fn = (const bf16_t*)M.ffn_norm;
-      if (pr.E) {  // MoE layers: the gate in the w1 slot, the DEVICE table [E][3] of expert matrices in the w2 slot
-        L.w1 = (const bf16_t*)M.gate; L.w2 = (const bf16_t*)M.expert_w_dev; L.w3 = nullptr;
-      } else {
-        L.w1 = (const bf16_t*)M.w1; L.w2 = (const bf16_t*)M.w2; L.w3 = (const bf16_t*)M.w3;
-      }
-      L.ck = (bf16_t*)pr.cache_k[l0 + l]; L.cv = (bf16_t*)pr.cache_v[l0 + l];
-      L.W = pr.W[l0 + l];
-      L.kv_layout = pr.kv_layout;
-      L.n_splits = attn_decode_splits(L.W);
-      L.chunk = attn_core::split_chunk(L.W, L.n_splits);
-    }
-    const void* fn = nullptr;
-    const bool moe = pr.E > 0;
-    const bool all4 = ENG_ALL4 && pr.D % 2048 == 0 && (pr.H * attn_core::DH) % 2048 == 0 && pr.F % 2048 == 0;
+// All of it is decode_engine_host.hip, compiled once.  What stays is this compile's descriptor: its name, the constants above
+// that the host reads, and the one thing that must name instantiations - which kernel serves (R, MoE, rows of 4-piece groups).
+// A case that is not listed is not compiled.
+static const void* decode_engine_pick(int R, bool moe, bool all4) {
 #define ENG_PICK(RR)                                                                                                       \
   (moe ? (all4 ? (const void*)decode_engine_kernel<RR, true, true> : (const void*)decode_engine_kernel<RR, true, false>) \
        : (all4 ? (const void*)decode_engine_kernel<RR, false, true> : (const void*)decode_engine_kernel<RR, false, false>))
-    switch (a.R) {
+  switch (R) {
 #if ENG_HEADLINE_ONLY == 1
-      case 4: fn = (!moe && all4) ? (const void*)decode_engine_kernel<4, false, true> : nullptr; break;
+    case 4: return (!moe && all4) ? (const void*)decode_engine_kernel<4, false, true> : nullptr;
 #elif ENG_HEADLINE_ONLY == 2
-      case 4: fn = (!moe && !all4) ? (const void*)decode_engine_kernel<4, false, false> : nullptr; break;
+    case 4: return (!moe && !all4) ? (const void*)decode_engine_kernel<4, false, false> : nullptr;
 #elif ENG_WIDE == 2
-      case 4: fn = !moe ? nullptr : (all4 ? (const void*)decode_engine_kernel<4, true, true> : (const void*)decode_engine_kernel<4, true, false>); break;
+    case 4: return !moe ? nullptr : (all4 ? (const void*)decode_engine_kernel<4, true, true> : (const void*)decode_engine_kernel<4, true, false>);
 #elif ENG_WIDE
-      case 4: fn = ENG_PICK(4); break;
-      case 6: fn = ENG_PICK(6); break;
+    case 4: return ENG_PICK(4);
+    case 6: return ENG_PICK(6);
 #else
-      case 1: fn = ENG_PICK(1); break;
-      case 2: fn = ENG_PICK(2); break;
-      case 4: fn = ENG_PICK(4); break;
-      case 8: fn = ENG_PICK(8); break;
+    case 1: return ENG_PICK(1);
+    case 2: return ENG_PICK(2);
+    case 4: return ENG_PICK(4);
+    case 8: return ENG_PICK(8);
 #endif
-      default: return hipErrorInvalidValue;
-    }
-#undef ENG_PICK
-    if (!fn) return hipErrorInvalidValue;
-    // 160 KiB of dynamic LDS is an opt-in per function AND per device
-    static bool attr_set[64][36] = {};
-    const int slot = a.R + (moe ? 9 : 0) + (all4 ? 18 : 0);
-    if (dev < 0 || dev >= 64 || !attr_set[dev][slot]) {
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
-      if (e != hipSuccess) return e;
-      if (dev >= 0 && dev < 64) attr_set[dev][slot] = true;
-    }
-    void* params[] = {(void*)&a};
-    hipError_t e = hipLaunchKernel(fn, dim3(pr.NB), dim3(NTHREADS), params, LDS_TOTAL, s);
-    if (e != hipSuccess) return e;
+    default: return nullptr;
   }
-  return hipSuccess;
+#undef ENG_PICK
 }
 
-// This compile's descriptor.  (A function-local static: a namespace-scope object would also be emitted by the device pass, whose
-// link then misses the host functions it names.)
+// (A function-local static: a namespace-scope object would also be emitted by the device pass, whose link then misses the host
+// function it names.)
 const EngineBuild& ENG_NAME(decode_engine_build)() {
-  static const EngineBuild build = {ENG_BUILD_NAME, decode_engine_applicable, launch_decode_engine, decode_engine_census_detail,
-                                    decode_engine_forget_census, decode_engine_set_trace, decode_engine_set_knobs,
-                                    decode_engine_set_holders};
+  static const EngineBuild build = {ENG_BUILD_NAME, ENG_WIDE, ENG_HEADLINE_ONLY, ENG_ALL4, RING_FILLS, FILL, PIECE,
+                                    LDS_TOTAL, XS_OFF, RES_BYTES, NTHREADS, decode_engine_pick};
   return build;
 }

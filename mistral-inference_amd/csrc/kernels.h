@@ -336,25 +336,29 @@ struct EngProblem {
   void* granules;
   size_t granule_bytes;
   uint32_t* ctrl;
-  int forced;                // mi_debug_set_engine_variant(1): take shapes that measured slower than the launch path too (traces, tests)
-  int lora_rank;             // > 0: the model carries un-merged LoRA adapters - no engine build takes it (api.hip engine_route)
+  int forced;                // set by the routing (variant 1): take shapes that measured slower than the launch path too (traces, tests)
+  int lora_rank;             // > 0: the model carries un-merged LoRA adapters - no engine build takes it (engine_route)
   int quant;                 // != 0: the layers' linears are quantised (mi_forward_w8 / _w4) - no engine build reads them
 };
 static_assert(sizeof(EngArgs) <= 4096, "EngArgs must fit the kernel-argument segment");
-size_t decode_engine_granule_bytes(int D, int H, int Hkv, int F, int maxW);  // the same for every build (default object only)
-size_t decode_engine_trace_bytes(int NB);
-// decode_engine.hip is compiled once per build below (build_native.py: VARIANT_OBJECTS); every compile exports one accessor to
-// this descriptor and nothing else.  Same EngProblem, same granule layout, bit-identical results.
+// The same in every build, read by the kernels and by the host side alike:
+constexpr int TR_CONS = 18, TR_EVENTS = 26;  // timeline events per layer: consumer wave 0 writes [0, TR_CONS), the loader the rest
+constexpr uint32_t ARRIVE_POLLS = 1u << 16;  // ~50 ms: far beyond the ~1 us over which a resident grid starts
+constexpr int AMAX_MAX_NB = 1024;            // workgroups the greedy-sampling edge is sized for (decode_engine_applicable: NB <= 1024)
+
+// decode_engine.hip holds the kernels and is compiled once per build below (build_native.py: VARIANT_OBJECTS); every compile
+// exports one accessor to this descriptor and nothing else (tests/test_engine_objects.py).  The descriptor holds what only the
+// build's own compile knows: its name, the constants its kernels were compiled with, and which kernels it instantiates.
+// Everything else about the engine - granule layout, residency census, knobs, applicability, launch, routing - is
+// decode_engine_host.hip, compiled once.  Same EngProblem, same granule layout, bit-identical results in every build.
 struct EngineBuild {
   const char* name;  // "default", "next", "nemo", "wide", "moe"; "x<N>": a slot of an experiment library
-  bool (*applicable)(const EngProblem& pr, char* why, size_t why_len);
-  // *declined = true (and nothing enqueued): the residency census failed on this device - take the launch path
-  hipError_t (*launch)(const EngProblem& pr, hipStream_t s, bool* declined);
-  const char* (*census_detail)();
-  void (*forget_census)();                 // tests
-  void (*set_trace)(void* dev_buffer);     // debug: nullptr disables
-  void (*set_knobs)(int thin, int depth);  // debug / tuning
-  void (*set_holders)(int on);             // debug / A/B: -1 = environment default
+  int wide, headline_only, all4;       // ENG_WIDE, ENG_HEADLINE_ONLY, ENG_ALL4
+  int ring_fills, fill, piece;         // the LDS ring: fills, pieces per fill, bytes per piece
+  int lds_total, xs_off, res_bytes;    // dynamic LDS per workgroup; offset of the activation region; bytes of the residual slab
+  int nthreads;                        // threads per workgroup
+  // the instantiation for (query heads per scheduled kv head, MoE, every row a multiple of 4 pieces); nullptr: not instantiated
+  const void* (*kernel)(int R, bool moe, bool all4);
 };
 // frozen since round 3: every dense shape the others decline; MI_ENGINE_VARIANT=2 routes the headline to it for A/B
 const EngineBuild& decode_engine_build();
@@ -368,6 +372,28 @@ const EngineBuild& decode_engine_build_nemo();
 const EngineBuild& decode_engine_build_wide();
 // -DENG_WIDE=2: the wide build's additions on the 8-fill ring, for MoE models whose hid vector fits beside it (Mixtral-8x7B)
 const EngineBuild& decode_engine_build_moe();
+
+// ---- decode_engine_host.hip
+size_t decode_engine_granule_bytes(int D, int H, int Hkv, int F, int maxW);
+size_t decode_engine_trace_bytes(int NB);
+// A batch-1 decode step on the first build of the route (engine_route) that takes it.
+struct EngStep {
+  bool ran;          // the step's launches are enqueued, or one of them failed (err); false: take the launch path
+  hipError_t err;
+  const char* what;  // names the launch for an error message
+  bool declined;     // a shipped build was asked and its residency census had failed: decode_engine_census_detail() says why
+};
+EngStep decode_engine_step(const EngProblem& pr, hipStream_t s);
+// the whole chain of builds a step of this shape would try, as "name,name" (every ring of cache_size slots); returns the length
+// the list needs, out_len or more if it was cut
+size_t decode_engine_route_names(int D, int H, int Hkv, int F, int V, int E, int top_k, int n_layers, int cache_size, int NB,
+                                 int variant, bool nemo_opt_in, char* out, size_t out_len);
+const char* decode_engine_census_detail();
+void decode_engine_forget_census();               // tests: the next launch probes again
+void decode_engine_set_trace(void* dev_buffer);   // debug: nullptr disables
+void decode_engine_set_knobs(int thin, int depth);  // debug / tuning
+void decode_engine_set_holders(int on);           // debug / A/B: -1 = environment default
+int decode_engine_set_variant(int variant);       // mi_debug_set_engine_variant; returns the previous one
 
 // ---------------------------------------------------------------------------------------------- un-merged LoRA (lora.hip)
 // lora.py:71-74 around a base product that the tuned GEMV / GEMM has already written:  t = bf16(A x),

@@ -151,14 +151,15 @@ def build_engine_slots(names):
         objs.append(o)
         jobs.append([hipcc, *b.FLAGS, *b.PER_FILE_FLAGS.get("decode_engine.hip", []), f"-DENG_SUFFIX=_x{i}", "-DENG_HEADLINE_ONLY=1",
                      *flags, "-c", src, "-o", o])
-    api_o = os.path.join(obj_dir, "api.o")
+    # the engine's host side (compiled once, also here) holds the list of builds: this library's copy names the slots too
+    host_o = os.path.join(obj_dir, "decode_engine_host.o")
     slot_list = " ".join(f"X({i})" for i in range(len(names)))
-    jobs.append([hipcc, *b.FLAGS, f"-DMI_SLOT_LIST={slot_list}", "-c", os.path.join(b.CSRC, "api.hip"), "-o", api_o])
+    jobs.append([hipcc, *b.FLAGS, f"-DMI_SLOT_LIST={slot_list}", "-c", os.path.join(b.CSRC, "decode_engine_host.hip"), "-o", host_o])
     with ThreadPoolExecutor(max_workers=8) as ex:
         for r in ex.map(lambda c: subprocess.run(c, capture_output=True, text=True), jobs):
             if r.returncode != 0:
                 raise RuntimeError(r.stderr[-3000:])
-    main = [api_o if s_ == "api.hip" else os.path.join(b.OBJ, s_.replace(".hip", ".o")) for s_ in b.SOURCES]
+    main = [host_o if s_ == "decode_engine_host.hip" else os.path.join(b.OBJ, s_.replace(".hip", ".o")) for s_ in b.SOURCES]
     main += [os.path.join(b.OBJ, v) for v in b.VARIANT_OBJECTS]
     lib = os.path.join(ROOT, "lib", "variants", "libmistral_hip_slots.so")
     subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *main, *objs, "-ldl", "-o", lib], check=True)
