@@ -455,6 +455,53 @@ typedef struct mi_w4_model {
 size_t mi_workspace_bytes_w4(const mi_model_t* model, const mi_w4_model_t* w4, int T, int B, int max_cache_size);
 int mi_forward_w4(const mi_model_t* model, const mi_w4_model_t* w4, const mi_batch_t* batch, mi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Speculative greedy decoding: one verify step scores up to 8 consecutive rows of a sequence.  Additive to ABI v9 like the blocks
+ * above: no struct or entry point above changes, the presence of these symbols is the feature test.  The reference has no
+ * speculative decoding; what a verify step emits is what generate.py:120-137 emits at temperature 0, token by token.
+ *
+ * Sequence b has p_b = kv_seqlens[b] cached positions and brings m_b rows (1 <= m_b <= 8, T = sum m_b <= 8): row 0 is its last
+ * emitted token, not yet cached, rows 1 .. m_b - 1 are drafted tokens; row i sits at position p_b + i.  Per layer the step runs the
+ * launches of a T-row prefill chunk (the T <= 8 GEMV kernels, same bits) except that NO row enters the rings: the post-RoPE K | V
+ * rows go to a per-layer stash in the workspace, and the attention (mi_attn_verify) reads ring keys below p_b and the step's own
+ * rows j <= i.  Behind the LM head: g_i = first argmax of row i, lp_i its log-softmax; a_b = the largest a with
+ * ids[i] == g_(i-1) for all 1 <= i <= a; the emitted tokens of sequence b are g_0 .. g_(a_b).  The last launch of the call
+ * commits: stash rows 0 .. a_b go to ring slots (p_b + i) % W_l of every layer, kv_seqlens[b] += a_b + 1, no other ring byte
+ * changes - a rejected draft leaves no trace, also on a wrapped ring where its slot still holds a position that earlier rows see.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The attention of a verify step, a leaf like mi_attn_decode / mi_attn_prefill.  qkv: [T, ld] fused post-RoPE rows, sequence b's
+ * are q_start[b] .. q_start[b + 1]; kv_before[b] = p_b.  Key position kp is visible to row i iff p_b + i - W < kp <= p_b + i;
+ * kp < p_b is read from ring slot kp % W, kp >= p_b from the rows; the rings are not written.  Split geometry of the decode
+ * attention (blocks of 128 slots of one kv head, streamed once for all rows and query heads); bf16 rings of either layout, W up
+ * to 4096 (more, or MI_KV_E4M3: MI_ERR_UNSUPPORTED), T <= 8, B <= T.  scratch: mi_attn_verify_scratch_bytes, no initialisation.
+ * out: [T, H*Dh]. */
+size_t mi_attn_verify_scratch_bytes(int T, int n_heads, int head_dim, int W);
+int mi_attn_verify(void* out, const void* qkv, int ld, const void* cache_k, const void* cache_v, int W, int T, int B, int n_heads,
+                   int n_kv_heads, int head_dim, const int32_t* q_start, const int32_t* kv_before, void* scratch, int kv_layout,
+                   mi_stream_t stream);
+
+typedef struct mi_verify_out {
+  int64_t* tokens;    /* dev [T]  g_i of every row; the first n_accept[b] + 1 of sequence b's rows are its emitted tokens */
+  float* logprobs;    /* dev [T]  lp_i */
+  int32_t* n_accept;  /* dev [B]  a_b */
+} mi_verify_out_t;
+
+/* Workspace of mi_forward_verify: mi_workspace_bytes_kv(model, quantised, T, T, max_cache_size, kv_layout) - the split partials
+ * of the attention are per row, so T stands where the batch size stands - plus exactly the stash,
+ * n_layers * T * 2 * n_kv_heads * head_dim bf16, behind everything else.  0 for T > 8 or a layout with MI_KV_E4M3. */
+size_t mi_workspace_bytes_verify(const mi_model_t* model, int quantised, int T, int max_cache_size, int kv_layout);
+
+/* One verify step on `model` - with w8 or w4 (at most one; both NULL: a bf16 model) as mi_forward_w8 / mi_forward_w4.  batch: the
+ * PREFILL branch with a cache - q_start, kv_before, tok_seq, tok_pos written by the host, kv_before[b] == kv_seqlens[b],
+ * tok_pos = kv_before[tok_seq[t]] + (t - q_start[tok_seq[t]]) - input_ids, logits [T, vocab] (all T rows are written) and a
+ * workspace of mi_workspace_bytes_verify; greedy_token NULL.  Refused before any launch: lora_rank > 0 and MI_KV_E4M3 rings
+ * (MI_ERR_UNSUPPORTED), T > 8 (MI_ERR_UNSUPPORTED), B > T or a max_q_len that leaves some sequence without a row, no cache or
+ * kv_seqlens, no input_ids / logits (MI_ERR_ARG), a ring above 4096 slots (MI_ERR_UNSUPPORTED), and whatever mi_forward_w8 / _w4
+ * refuse of a quantised model.  Always the launch path. */
+int mi_forward_verify(const mi_model_t* model, const mi_w8_model_t* w8, const mi_w4_model_t* w4, const mi_batch_t* batch,
+                      const mi_verify_out_t* out, mi_stream_t stream);
+
 /* ABI v6 - storage dtypes other than bf16 (reference transformer.py:303,338: `from_folder(dtype=...)` keeps the dtype the
  * caller asks for; the reference's own tests build fp32 models, tests/test_generate.py:51,100) and bf16 models of a shape
  * mi_forward declines with MI_ERR_SHAPE (head_dim != 128, more than 16 experts, top_k = 3).  Same structs, same metadata

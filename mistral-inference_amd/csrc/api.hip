@@ -93,8 +93,11 @@ struct Workspace {
   void* lora_base;   // ... and the base products of q|k|v and w1|w3  [T, max(qkv cols, 2 F)]: fp32 holding bf16 values for T <= 8
   bf16_t* deq;       // quantised models at T > 8 (behind everything else, such models only): the dequantised weights of one linear
   bf16_t* kv_deq;    // e4m3 K/V rings (behind everything else, such forwards only): one layer's rings of the batch as bf16, K then V,
-  size_t total;      //     for the prefill attention (kv_scratch_elems).  (deq: deq_scratch_elems.  lora_base: the GEMV's LOGITS form, see
-};                   //     lora_linear; bf16 above 8 rows.  Wo's and W2's base product goes to xn.)
+                     //     for the prefill attention (kv_scratch_elems).  (deq: deq_scratch_elems.  lora_base: the GEMV's LOGITS form, see
+                     //     lora_linear; bf16 above 8 rows.  Wo's and W2's base product goes to xn.)
+  bf16_t* stash;     // verify steps (behind everything else, such steps only): the step's post-RoPE K | V rows of every layer
+  size_t total;      //     [n_layers, T, 2 * n_kv_heads * head_dim], which enter the rings once acceptance is known
+};
 
 // bf16 elements of the largest linear group a prefill dequantises at once: q|k|v, wo, w1|w3, w2
 size_t deq_scratch_elems(const mi_model_t* m) {
@@ -106,8 +109,12 @@ size_t deq_scratch_elems(const mi_model_t* m) {
 // bf16 elements of ONE dequantised ring (K or V) of B sequences of a layer
 size_t kv_scratch_elems(const mi_model_t* m, int B, int maxW) { return (size_t)B * m->n_kv_heads * maxW * m->head_dim; }
 
+// bytes of a verify step's stash: K | V rows of T tokens in every layer (a multiple of 256 at head_dim 128)
+size_t verify_stash_bytes(const mi_model_t* m, int T) { return (size_t)m->n_layers * T * 2 * m->n_kv_heads * m->head_dim * sizeof(bf16_t); }
+
 // quant: the linears are quantised (any format: the same scratch of one dequantised linear group); kv8: the rings hold e4m3 bytes
-Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool quant = false, bool kv8 = false) {
+// verify: a verify step (mi_forward_verify) - its attention keeps split partials per ROW, so the caller passes B = T, and the stash
+Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool quant = false, bool kv8 = false, bool verify = false) {
   Workspace w;
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -127,7 +134,12 @@ Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool qu
   w.qkv = (bf16_t*)take((size_t)T * qkv_cols * 2);
   w.attn = (bf16_t*)take((size_t)T * m->n_heads * m->head_dim * 2);
   w.hid = (bf16_t*)take((size_t)T * slots * m->hidden_dim * 2);
-  w.partial = (float*)take(attn_decode_partial_floats(B, m->n_heads, m->n_kv_heads, m->head_dim, maxW) * sizeof(float));
+  size_t partial_floats = attn_decode_partial_floats(B, m->n_heads, m->n_kv_heads, m->head_dim, maxW);
+  if (verify) {  // (the same figure while the decode attention's split geometry is its default one)
+    const size_t v = attn_verify_partial_floats(T, m->n_heads, m->head_dim, maxW);
+    partial_floats = v > partial_floats ? v : partial_floats;
+  }
+  w.partial = (float*)take(partial_floats * sizeof(float));
   w.sel_idx = (int32_t*)take((size_t)T * slots * 4);
   w.sel_w = (float*)take((size_t)T * slots * 4);
   w.max_tiles = (T * slots + 127) / 128 + (m->num_experts > 0 ? m->num_experts : 0);
@@ -145,6 +157,7 @@ Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool qu
   }
   w.deq = (quant && T > GEMV_MAX_T) ? (bf16_t*)take(deq_scratch_elems(m) * 2) : nullptr;  // (a plain model: layout and total as ever)
   w.kv_deq = kv8 ? (bf16_t*)take(2 * kv_scratch_elems(m, B, maxW) * 2) : nullptr;          // (bf16 rings: layout and total as ever)
+  w.stash = verify ? (bf16_t*)take(verify_stash_bytes(m, T)) : nullptr;                      // (any other forward: layout and total as ever)
   w.total = off;
   return w;
 }
@@ -802,6 +815,31 @@ int mi_attn_prefill(void* out, const void* qkv, int ld, const void* cache_k, con
   return hip_rc(launch_attn_prefill(a, (hipStream_t)stream), "attn_prefill");
 }
 
+size_t mi_attn_verify_scratch_bytes(int T, int n_heads, int head_dim, int W) {
+  if (T <= 0 || n_heads <= 0 || W <= 0) return 0;
+  return align_up(attn_verify_partial_floats(T, n_heads, head_dim, W) * sizeof(float));
+}
+
+int mi_attn_verify(void* out, const void* qkv, int ld, const void* cache_k, const void* cache_v, int W, int T, int B, int n_heads,
+                   int n_kv_heads, int head_dim, const int32_t* q_start, const int32_t* kv_before, void* scratch, int kv_layout,
+                   mi_stream_t stream) {
+  if (!out || !qkv || !cache_k || !cache_v || !q_start || !kv_before || !scratch || W <= 0 || T <= 0 || B <= 0 || n_heads <= 0 ||
+      n_kv_heads <= 0 || !kv_layout_ok(kv_layout))
+    return fail(MI_ERR_ARG, "mi_attn_verify");
+  if (kv_e4m3(kv_layout)) return fail(MI_ERR_UNSUPPORTED, "mi_attn_verify: rings of e4m3 bytes (MI_KV_E4M3) are not implemented");
+  if (head_dim != 128) return fail(MI_ERR_SHAPE, "mi_attn_verify: head_dim must be 128");
+  if (n_heads % n_kv_heads) return fail(MI_ERR_SHAPE, "mi_attn_verify: n_heads %% n_kv_heads != 0");
+  if (T > GEMV_MAX_T) return fail(MI_ERR_UNSUPPORTED, "mi_attn_verify: T = %d rows; a verify step takes at most %d", T, GEMV_MAX_T);
+  if (B > T) return fail(MI_ERR_ARG, "mi_attn_verify: every sequence brings m_b >= 1 rows (T %d, B %d)", T, B);
+  if (ld < (n_heads + 2 * n_kv_heads) * head_dim) return fail(MI_ERR_ARG, "mi_attn_verify: ld %d below the q | k | v columns", ld);
+  if (attn_verify_splits(W) > 32) return fail(MI_ERR_UNSUPPORTED, "mi_attn_verify: a ring of %d slots; the verify attention takes 1 .. 4096", W);
+  AttnVerifyArgs a = {};
+  a.out = out; a.qkv = (const bf16_t*)qkv; a.ld = ld; a.cache_k = (const bf16_t*)cache_k; a.cache_v = (const bf16_t*)cache_v;
+  a.kv_layout = kv_layout; a.W = W; a.T = T; a.B = B; a.H = n_heads; a.Hkv = n_kv_heads; a.Dh = head_dim;
+  a.q_start = q_start; a.kv_before = kv_before; a.partial = (float*)scratch; a.stash = nullptr;
+  return hip_rc(launch_attn_verify(a, (hipStream_t)stream), "attn_verify");
+}
+
 int mi_gelu(void* x, int ldx, int T, int N, mi_stream_t stream) {
   if (!x || T <= 0 || N <= 0 || ldx < N) return fail(MI_ERR_ARG, "mi_gelu");
   return hip_rc(launch_gelu(x, ldx, T, N, (hipStream_t)stream), "gelu");
@@ -1087,17 +1125,39 @@ static int check_quant(const char* entry, const mi_model_t* m, const QuantModel&
   });
 }
 
+// what a verify step must be, by name, before any launch (mi_forward_verify; the batch has passed check_batch)
+static int check_verify(const char* entry, const mi_model_t* m, const mi_batch_t* bt, const mi_verify_out_t* vo) {
+  if (!vo->tokens || !vo->logprobs || !vo->n_accept) return fail(MI_ERR_ARG, "%s: outputs (tokens, logprobs, n_accept)", entry);
+  if (m->lora_rank > 0) return fail(MI_ERR_UNSUPPORTED, "%s: un-merged LoRA (lora_rank %d) in a verify step is not implemented; merge the adapter", entry, m->lora_rank);
+  if (bt->branch != MI_BRANCH_PREFILL || !bt->kv_seqlens)
+    return fail(MI_ERR_ARG, "%s: a verify step needs a cache: the PREFILL branch with kv_seqlens (branch %d)", entry, bt->branch);
+  if (kv_e4m3(bt->kv_layout)) return fail(MI_ERR_UNSUPPORTED, "%s: rings of e4m3 bytes (MI_KV_E4M3) in a verify step are not implemented", entry);
+  if (bt->T > GEMV_MAX_T) return fail(MI_ERR_UNSUPPORTED, "%s: T = %d rows; a verify step takes at most %d", entry, bt->T, GEMV_MAX_T);
+  if (bt->B > bt->T || bt->max_q_len < 1 || bt->max_q_len > bt->T - bt->B + 1)
+    return fail(MI_ERR_ARG, "%s: every sequence brings m_b >= 1 rows (T %d, B %d, max_q_len %d)", entry, bt->T, bt->B, bt->max_q_len);
+  if (!bt->input_ids || !m->tok_embeddings || !bt->logits)
+    return fail(MI_ERR_ARG, "%s: input_ids, the embedding table and a logits buffer [T, vocab] are needed (one pipeline stage)", entry);
+  for (int l = 0; l < m->n_layers; ++l)
+    if (bt->cache_sizes[l] <= 0 || attn_verify_splits(bt->cache_sizes[l]) > 32)
+      return fail(MI_ERR_UNSUPPORTED, "%s: layer %d has a ring of %d slots; the verify attention takes 1 .. 4096", entry, l, bt->cache_sizes[l]);
+  return MI_OK;
+}
+
 // mi_forward, mi_forward_w8 and mi_forward_w4.  q == nullptr: exactly the launches of mi_forward as they always were.
-static int forward_body(const char* entry, const mi_model_t* m, const QuantModel* q, const mi_batch_t* bt, mi_stream_t stream) {
+// vo != nullptr: a verify step (mi_forward_verify) - the T <= 8 launches of a prefill chunk with the verify attention in place of
+// the prefill attention and NO ring write, then argmax, acceptance and the commit of the accepted rows.
+static int forward_body(const char* entry, const mi_model_t* m, const QuantModel* q, const mi_batch_t* bt, mi_stream_t stream,
+                        const mi_verify_out_t* vo = nullptr) {
   MI_TRY(check_model(m));
   if (q) MI_TRY(check_quant(entry, m, *q));
   BatchInfo bi;
   MI_TRY(check_batch(entry, m, bt, true, &bi));
+  if (vo) MI_TRY(check_verify(entry, m, bt, vo));
   int maxW = 1;
   if (bi.has_cache)
     for (int l = 0; l < m->n_layers; ++l) maxW = bt->cache_sizes[l] > maxW ? bt->cache_sizes[l] : maxW;
   const bool kv8 = bi.has_cache && kv_e4m3(bi.kv_layout);  // rings of e4m3 bytes: written by the e4m3 ring-write kernel only
-  const Workspace ws = carve(m, bi.T, bi.B, maxW, (char*)bt->workspace, q != nullptr, kv8);
+  const Workspace ws = carve(m, bi.T, vo ? bi.T : bi.B, maxW, (char*)bt->workspace, q != nullptr, kv8, vo != nullptr);
   MI_TRY(check_workspace_and_sample(entry, bt, ws.total, &bi));
   const int T = bi.T, B = bi.B, branch = bi.branch, kvl = bi.kv_layout;  // (kvl keeps MI_KV_E4M3: the ring write and the decode attention pick their e4m3 kernels by it)
   const bool has_cache = bi.has_cache, want_greedy = bi.want_sample, want_topp = bi.want_topp;
@@ -1241,6 +1301,13 @@ static int forward_body(const char* entry, const mi_model_t* m, const QuantModel
     if (branch == MI_BRANCH_DECODE) {
       const AttnDecodeArgs a = attn_decode_args(ws.attn, ws.qkv, qkv_cols, ck, cv, kvl, W, B, H, Hkv, Dh, bt->tok_pos, ws.tickets, ws.partial);
       MI_TRY(hip_rc(launch_attn_decode(a, s), "attn_decode"));
+    } else if (vo) {
+      // verify step: ring keys below kv_before, the step's own rows from ws.qkv (and into the layer's stash); no ring write
+      AttnVerifyArgs a = {};
+      a.out = ws.attn; a.qkv = ws.qkv; a.ld = qkv_cols; a.cache_k = (const bf16_t*)ck; a.cache_v = (const bf16_t*)cv; a.kv_layout = kvl;
+      a.W = W; a.T = T; a.B = B; a.H = H; a.Hkv = Hkv; a.Dh = Dh; a.q_start = bt->q_start; a.kv_before = bt->kv_before;
+      a.partial = ws.partial; a.stash = ws.stash + (size_t)l * T * 2 * nkv;
+      MI_TRY(hip_rc(launch_attn_verify(a, s), "attn_verify"));
     } else {
       // e4m3 rings: the keys older than this forward are read from the bf16 image of the layer's rings in the scratch (exact); the
       // chunk's own rows come from the activations, unrounded, as ever (transformer_layers.py:72-76)
@@ -1317,6 +1384,24 @@ static int forward_body(const char* entry, const mi_model_t* m, const QuantModel
     }
     if (want_greedy) MI_TRY(sample_step(bt, m, want_topp, engine_ctrl, s));
   }
+  if (vo) {
+    MI_TRY(hip_rc(launch_greedy_rows(bt->logits, m->vocab_size, T, m->vocab_size, vo->tokens, vo->logprobs, nullptr, nullptr, 0, nullptr, s),
+                  "verify argmax"));
+    MI_TRY(hip_rc(launch_verify_accept(bt->input_ids, vo->tokens, bt->q_start, B, vo->n_accept, s), "verify accept"));
+    for (int l0 = 0; l0 < m->n_layers; l0 += VERIFY_COMMIT_LAYERS) {  // (one launch up to 128 layers)
+      VerifyCommitArgs c;
+      memset(&c, 0, sizeof(c));
+      c.n_layers = m->n_layers - l0 < VERIFY_COMMIT_LAYERS ? m->n_layers - l0 : VERIFY_COMMIT_LAYERS;
+      for (int l = 0; l < c.n_layers; ++l) {
+        c.k[l] = (bf16_t*)bt->cache_k[l0 + l]; c.v[l] = (bf16_t*)bt->cache_v[l0 + l]; c.W[l] = bt->cache_sizes[l0 + l];
+      }
+      c.stash = ws.stash + (size_t)l0 * T * 2 * nkv;
+      c.T = T; c.B = B; c.kv_dim = nkv; c.Dh = Dh; c.kv_layout = kvl & 1;
+      c.q_start = bt->q_start; c.kv_before = bt->kv_before; c.tok_seq = bt->tok_seq; c.n_accept = vo->n_accept;
+      c.kv_seqlens = (l0 + VERIFY_COMMIT_LAYERS >= m->n_layers) ? bt->kv_seqlens : nullptr;
+      MI_TRY(hip_rc(launch_verify_commit(c, s), "verify commit"));
+    }
+  }
   return MI_OK;
 }
 
@@ -1332,6 +1417,26 @@ int mi_forward_w4(const mi_model_t* m, const mi_w4_model_t* w4, const mi_batch_t
   if (!w4) return forward_body("mi_forward", m, nullptr, bt, stream);
   const QuantModel q = {MI_W4_MXFP4, w4->format, nullptr, w4->layers};
   return forward_body("mi_forward_w4", m, &q, bt, stream);
+}
+
+size_t mi_workspace_bytes_verify(const mi_model_t* model, int quantised, int T, int max_cache_size, int kv_layout) {
+  if (!model || T <= 0 || T > GEMV_MAX_T || !kv_layout_ok(kv_layout) || kv_e4m3(kv_layout)) return 0;
+  return carve(model, T, T, max_cache_size > 0 ? max_cache_size : 1, nullptr, quantised != 0, false, true).total;
+}
+
+int mi_forward_verify(const mi_model_t* m, const mi_w8_model_t* w8, const mi_w4_model_t* w4, const mi_batch_t* bt,
+                      const mi_verify_out_t* out, mi_stream_t stream) {
+  if (!out) return fail(MI_ERR_ARG, "mi_forward_verify: outputs");
+  if (w8 && w4) return fail(MI_ERR_ARG, "mi_forward_verify: both w8 and w4 given; a model has at most one weight format");
+  if (w8) {
+    const QuantModel q = {MI_W8_FP8_E4M3, w8->format, w8->layers, nullptr};
+    return forward_body("mi_forward_verify", m, &q, bt, stream, out);
+  }
+  if (w4) {
+    const QuantModel q = {MI_W4_MXFP4, w4->format, nullptr, w4->layers};
+    return forward_body("mi_forward_verify", m, &q, bt, stream, out);
+  }
+  return forward_body("mi_forward_verify", m, nullptr, bt, stream, out);
 }
 
 }  // extern "C"

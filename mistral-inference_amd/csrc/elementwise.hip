@@ -306,6 +306,34 @@ __global__ __launch_bounds__(1024) void greedy_rows_kernel(const float* logits, 
   }
 }
 
+// Verify step: thread b counts the leading drafts of sequence b that the model's own argmaxes confirm.
+__global__ void verify_accept_kernel(const int64_t* ids, const int64_t* tok, const int32_t* q_start, int B, int32_t* n_accept) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int q0 = q_start[b], m = q_start[b + 1] - q0;
+  int a = 0;
+  while (a + 1 < m && ids[q0 + a + 1] == tok[q0 + a]) ++a;
+  n_accept[b] = a;
+}
+
+// Verify step: the accepted rows of the per-layer stash enter the rings - block (row t, layer l), one 16-byte piece of K and of V
+// per thread and trip; rejected rows are not read.  Block (0, 0) advances kv_seqlens when the launch carries it.
+__global__ __launch_bounds__(256) void verify_commit_kernel(VerifyCommitArgs a) {
+  const int t = blockIdx.x, l = blockIdx.y;
+  const int b = a.tok_seq[t];
+  const int i = t - a.q_start[b];
+  if (t == 0 && l == 0 && a.kv_seqlens)
+    for (int s = threadIdx.x; s < a.B; s += 256) a.kv_seqlens[s] += a.n_accept[s] + 1;
+  if (i > a.n_accept[b]) return;
+  const int W = a.W[l];
+  const bf16_t* src = a.stash + ((size_t)l * a.T + t) * 2 * a.kv_dim;
+  for (int p = threadIdx.x; p < (a.kv_dim >> 3); p += 256) {
+    const size_t off = kv_offset(a.kv_layout, W, a.kv_dim, a.Dh, (size_t)b, (a.kv_before[b] + i) % W, p * 8);
+    st16(a.k[l] + off, ld16(src + p * 8));
+    st16(a.v[l] + off, ld16(src + a.kv_dim + p * 8));
+  }
+}
+
 __global__ void engine_ctrl_reset_kernel(uint32_t* ctrl) {
   ctrl[CTRL_EPOCH] += 16;  // tags of the failed step (epoch + 1) can never match again
   ctrl[CTRL_STATUS] = 0;
@@ -595,6 +623,16 @@ hipError_t launch_decode_prep_embedding(int64_t* kv_seqlens, int32_t* q_start, i
 hipError_t launch_greedy_rows(const float* logits, int ld, int B, int V, int64_t* tok, float* lp, int64_t* hist_tok,
                               float* hist_lp, int hist_len, const uint32_t* ctrl, hipStream_t s) {
   hipLaunchKernelGGL(greedy_rows_kernel, dim3(B), dim3(1024), 0, s, logits, ld, B, V, tok, lp, hist_tok, hist_lp, hist_len, ctrl);
+  return hipGetLastError();
+}
+hipError_t launch_verify_accept(const int64_t* ids, const int64_t* tok, const int32_t* q_start, int B, int32_t* n_accept, hipStream_t s) {
+  hipLaunchKernelGGL(verify_accept_kernel, dim3((B + 63) / 64), dim3(64), 0, s, ids, tok, q_start, B, n_accept);
+  return hipGetLastError();
+}
+hipError_t launch_verify_commit(const VerifyCommitArgs& a, hipStream_t s) {
+  if (a.n_layers <= 0 || a.n_layers > VERIFY_COMMIT_LAYERS || a.T <= 0 || a.Dh <= 0 || a.Dh % 8 || a.kv_dim % a.Dh || (a.kv_layout & ~1))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(verify_commit_kernel, dim3(a.T, a.n_layers), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 hipError_t launch_engine_ctrl_reset(uint32_t* ctrl, hipStream_t s) {

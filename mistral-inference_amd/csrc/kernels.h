@@ -185,6 +185,43 @@ hipError_t launch_attn_prefill(const AttnPrefillArgs& a, hipStream_t s);
 void attn_prefill_set_mode(int waves);  // mi_debug_set_prefill_kernels (negative: keep)
 hipError_t launch_attn_prefill_f16(const AttnPrefillArgs& a, hipStream_t s);  // attn_prefill.hip compiled with -DATTN_F16=1
 
+// Verify step (attn_verify.hip): sequence b brings rows q_start[b] .. q_start[b + 1] (at most 8, at positions kv_before[b] + i)
+// that are NOT in its ring; mask of the prefill attention, split geometry of the decode attention.
+struct AttnVerifyArgs {
+  void* out;            // [T, H*Dh]
+  const bf16_t* qkv;    // [T, ld]  q | k | v (post-RoPE)
+  int ld;
+  const bf16_t* cache_k;  // bf16 rings in kv_layout
+  const bf16_t* cache_v;
+  int kv_layout;
+  int W, T, B, H, Hkv, Dh;
+  const int32_t* q_start;    // [B+1]
+  const int32_t* kv_before;  // [B]
+  float* partial;            // attn_verify_partial_floats(T, H, Dh, W) floats
+  bf16_t* stash;             // [T, 2 * Hkv * Dh] K | V of the step's rows, or nullptr
+  int n_splits;              // launch_attn_verify sets it
+};
+int attn_verify_splits(int W);  // blocks of 128 slots; more than 32 of them: launch_attn_verify declines (hipErrorInvalidValue)
+size_t attn_verify_partial_floats(int T, int H, int Dh, int W);
+hipError_t launch_attn_verify(const AttnVerifyArgs& a, hipStream_t s);
+
+// Verify step, behind the LM head (elementwise.hip).  accept: n_accept[b] = the number of leading drafts ids[q_start[b] + i]
+// (i >= 1) that equal the argmax tok[q_start[b] + i - 1] of the row before them.  commit: for every layer l, rows 0 .. n_accept[b]
+// of sequence b go from the stash [n_layers, T, 2 * kv_dim] (K | V) to slot (kv_before[b] + i) % W_l of its rings, then
+// kv_seqlens[b] += n_accept[b] + 1.  The ring table travels in the kernel arguments, VERIFY_COMMIT_LAYERS layers per launch.
+constexpr int VERIFY_COMMIT_LAYERS = 128;
+struct VerifyCommitArgs {
+  bf16_t* k[VERIFY_COMMIT_LAYERS];
+  bf16_t* v[VERIFY_COMMIT_LAYERS];
+  int32_t W[VERIFY_COMMIT_LAYERS];
+  const bf16_t* stash;  // of the first layer of this launch
+  int n_layers, T, B, kv_dim, Dh, kv_layout;
+  const int32_t *q_start, *kv_before, *tok_seq, *n_accept;
+  int64_t* kv_seqlens;  // advanced by this launch, or nullptr (every launch of a step but the last)
+};
+hipError_t launch_verify_accept(const int64_t* ids, const int64_t* tok, const int32_t* q_start, int B, int32_t* n_accept, hipStream_t s);
+hipError_t launch_verify_commit(const VerifyCommitArgs& a, hipStream_t s);
+
 // Compute units of the current device (256 on a full MI355X; fewer in partitioned modes).  Grid-shaping heuristics
 // (rounds of blocks, tail splitting) use it; results never depend on it.
 inline int device_cus() {

@@ -93,6 +93,12 @@ class MiW4Model(C.Structure):
 
 MI_W4_MXFP4 = 2  # include/mistral_hip.h
 
+
+class MiVerifyOut(C.Structure):
+    """`mi_verify_out_t`: what a verify step returns - the argmax and its log-prob of every row, the accepted drafts per sequence."""
+    _fields_ = [("tokens", _vp), ("logprobs", _vp), ("n_accept", _vp)]
+
+
 _lib: Optional[C.CDLL] = None
 
 _SIGS = {
@@ -149,6 +155,13 @@ _SIGS = {
     # FP8 K/V rings (additive likewise): MI_KV_E4M3 in a layout code
     "mi_kv_dequant": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "mi_workspace_bytes_kv": (C.c_size_t, [C.POINTER(MiModel), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    # speculative greedy decoding (additive likewise): verify steps
+    "mi_attn_verify_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mi_attn_verify": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp,
+                                 C.c_int, _vp]),
+    "mi_workspace_bytes_verify": (C.c_size_t, [C.POINTER(MiModel), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mi_forward_verify": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiW8Model), C.POINTER(MiW4Model), C.POINTER(MiBatch),
+                                    C.POINTER(MiVerifyOut), _vp]),
     "mi_workspace_bytes_generic": (C.c_size_t, [C.POINTER(MiModel), C.c_int, C.c_int]),  # ABI v6
     "mi_forward_generic": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiBatch), C.c_int, _vp]),
     "mi_embedding_generic": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
@@ -568,6 +581,20 @@ def attn_prefill(qkv: torch.Tensor, n_heads: int, n_kv_heads: int, head_dim: int
                                 dev_ptr(kv_before, torch.int32), 1 if causal else 0, float(softmax_scale),
                                 _kv_layout2(cache_k, cache_v) if cache_k is not None else KV_SLOT_MAJOR,
                                 stream_ptr(qkv.device)), "mi_attn_prefill")
+    return out
+
+
+def attn_verify(qkv: torch.Tensor, n_heads: int, cache_k: torch.Tensor, cache_v: torch.Tensor, q_start: torch.Tensor,
+                kv_before: torch.Tensor, B: int) -> torch.Tensor:
+    """mi_attn_verify: the attention of a verify step - sequence b's rows q_start[b] .. q_start[b + 1] sit at positions
+    kv_before[b] + i and are NOT in the rings, which are read below kv_before[b] and left as they are."""
+    T = qkv.shape[0]
+    _, W, Hkv, Dh = cache_k.shape
+    scratch = torch.empty(max(lib().mi_attn_verify_scratch_bytes(T, n_heads, Dh, W), 1), dtype=torch.uint8, device=qkv.device)
+    out = torch.empty((T, n_heads * Dh), dtype=qkv.dtype, device=qkv.device)
+    check(lib().mi_attn_verify(dev_ptr(out), dev_ptr(qkv), qkv.stride(0), ring_ptr(cache_k), ring_ptr(cache_v), W, T, B, n_heads, Hkv,
+                               Dh, dev_ptr(q_start, torch.int32), dev_ptr(kv_before, torch.int32), dev_ptr(scratch, torch.uint8),
+                               _kv_layout2(cache_k, cache_v), stream_ptr(qkv.device)), "mi_attn_verify")
     return out
 
 

@@ -325,6 +325,19 @@ class BufferCache:
             m = self._decode_meta
             return BatchMetadata(_hip.BRANCH_DECODE, seqlens, 1, m[: B + 1], m[B + 1: 2 * B + 1],
                                  m[2 * B + 1: 3 * B + 1], m[3 * B + 1: 4 * B + 1])
+        return self._host_metadata(seqlens)
+
+    def verify_metadata(self, seqlens: List[int]) -> BatchMetadata:
+        """Metadata of a verify step (`Transformer.verify_step`): the PREFILL-with-cache arrays written by the host whatever the
+        row counts - a step of one row per sequence is NOT the decode branch, whose first kernel advances kv_seqlens."""
+        assert self.kv_seqlens is not None and self._seen is not None, "a verify step continues a cache that holds a prompt"
+        assert len(seqlens) == len(self._seen), f"Batch size is {len(self._seen)}, got {len(seqlens)}"
+        return self._host_metadata(seqlens)
+
+    def _host_metadata(self, seqlens: List[int]) -> BatchMetadata:
+        seen = self._seen
+        assert seen is not None
+        B, T = len(seqlens), sum(seqlens)
         q_start = [0]
         for s in seqlens:
             q_start.append(q_start[-1] + s)

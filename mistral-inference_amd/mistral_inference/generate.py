@@ -13,12 +13,64 @@ is the EOS test, and only when `eos_id` is given.
 """
 import contextlib
 import functools
-from typing import List, Optional, Tuple
+from dataclasses import dataclass
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
 from .cache import BufferCache, check_kv_dtype
 from .transformer import Transformer
+
+
+@dataclass
+class SpeculativeArgs:
+    """Speculative greedy decoding for `generate(speculative=...)`: every step drafts up to `k` tokens on the host and the model
+    scores them in ONE pass over its weights (`Transformer.verify_step`), keeping the drafts its own argmaxes confirm - the
+    tokens are those of the plain greedy loop.  The default drafter is prompt lookup (`ngram_draft`); `drafter` replaces it with
+    any callable history -> drafts (history: prompt plus everything emitted so far; more than `k` drafts are cut)."""
+    k: int = 3
+    ngram_max: int = 3
+    ngram_min: int = 1
+    drafter: Optional[Callable[[List[int]], Sequence[int]]] = None
+
+    def __post_init__(self) -> None:
+        if not 1 <= self.k <= 7:
+            raise ValueError(f"SpeculativeArgs.k = {self.k}: a verify step takes the last token and 1 .. 7 drafts")
+        if not 1 <= self.ngram_min <= self.ngram_max:
+            raise ValueError(f"SpeculativeArgs: 1 <= ngram_min <= ngram_max, got {self.ngram_min} .. {self.ngram_max}")
+
+    def draft(self, history: List[int]) -> List[int]:
+        d = self.drafter(history) if self.drafter is not None else ngram_draft(history, self.k, self.ngram_max, self.ngram_min)
+        return [int(t) for t in list(d)[: self.k]]
+
+
+def ngram_draft(history: Sequence[int], k: int, ngram_max: int = 3, ngram_min: int = 1) -> List[int]:
+    """Prompt lookup: the longest suffix n-gram of `history` (n from ngram_max down to ngram_min) that occurs earlier in it; of
+    its earlier occurrences the most recent one; the (up to) k tokens that followed it there.  No match: []."""
+    h = list(history)
+    L = len(h)
+    for n in range(min(ngram_max, L - 1), ngram_min - 1, -1):
+        suffix = h[L - n:]
+        for start in range(L - n - 1, -1, -1):  # most recent earlier occurrence first
+            if h[start: start + n] == suffix:
+                return h[start + n: start + n + k]
+    return []
+
+
+def refuse_speculative(model, n_prompts: int, temperature: float, kv_dtype: Optional[torch.dtype]) -> None:
+    """What generate(speculative=...) does not take, by name, before anything runs."""
+    if temperature > 0:
+        raise NotImplementedError(f"speculative decoding at temperature {temperature} > 0 (sampling with rejection) is not implemented; "
+                                  "it is greedy: pass temperature=0")
+    if n_prompts != 1:
+        raise NotImplementedError(f"speculative decoding of {n_prompts} prompts is not implemented: one prompt per call")
+    if kv_dtype == torch.float8_e4m3fn:
+        raise NotImplementedError("speculative decoding on an FP8 K/V cache (kv_dtype=float8_e4m3fn) is not implemented; "
+                                  "use the model's own bf16 rings")
+    if not hasattr(model, "verify_step"):
+        raise NotImplementedError("speculative decoding: this model has no verify_step")
+    if hasattr(model, "refuse_verify"):
+        model.refuse_verify(None, model_only=True)  # (the model's own refusals but the cache's: pipeline ranks, storage dtype, un-merged LoRA)
 
 
 def _unpins_adapters(fn):
@@ -47,7 +99,12 @@ def generate(
     eos_id: Optional[int] = None,
     adapters: Optional[List[int]] = None,
     kv_dtype: Optional[torch.dtype] = None,
+    speculative: Optional[SpeculativeArgs] = None,
 ) -> Tuple[List[List[int]], List[List[float]]]:
+    # speculative (temperature 0, one prompt, bf16 rings, one stage): the decode loop runs verify steps - see SpeculativeArgs; the
+    # returned tokens, log-probs, max_tokens truncation and EOS stop are the plain loop's.  None: the plain loop.
+    if speculative is not None:
+        refuse_speculative(model, len(encoded_prompts), temperature, kv_dtype)
     # kv_dtype: dtype of the K/V rings; None: the model's.  torch.float8_e4m3fn (bf16 models on the tuned path): rings of e4m3 bytes
     # at half the size, written and read by the rule of cache.kv_quantize / kv_dequantize; such a generation takes the launch path.
     kv_dtype = check_kv_dtype(kv_dtype, model.dtype)   # (before anything is pinned or allocated)
@@ -141,6 +198,35 @@ def generate(
     gen_lp: List[torch.Tensor] = []
     is_finished = torch.zeros(B, dtype=torch.bool, device=dev)
     assert last_token_prelogits is not None
+    spec_out: Optional[Tuple[List[int], List[float]]] = None
+    if speculative is not None and max_tokens > 0:
+        # token 0 comes from the prompt's last logits as in the plain loop; every later step scores [last emitted token] + drafts
+        # and emits the argmaxes of the confirmed rows.  One synchronisation per step (n_accept), which also brings the tokens.
+        t0 = torch.argmax(last_token_prelogits, dim=-1)
+        lp0 = torch.log_softmax(last_token_prelogits, dim=-1).gather(1, t0[:, None])[:, 0]
+        toks, lps = [int(t0[0])], [float(lp0[0])]
+        history = list(encoded_prompts[0]) + toks
+        done = eos_id is not None and toks[0] == eos_id
+        if done:
+            toks, lps = [], []
+        while not done and len(toks) < max_tokens:
+            drafts = speculative.draft(history)[: max_tokens - len(toks) - 1]
+            if any(d < 0 or d >= V for d in drafts):
+                raise IndexError("index out of range in self (a drafted token)")
+            ids = torch.tensor([history[-1]] + drafts, device=dev, dtype=torch.long)
+            tok, lp, n_accept = model.verify_step(ids, [len(drafts) + 1], cache)
+            new_t, new_lp = tok[: n_accept[0] + 1].tolist(), lp[: n_accept[0] + 1].tolist()
+            for t, l in zip(new_t, new_lp):
+                if eos_id is not None and t == eos_id:  # generate.py:128-132: the EOS token itself is not returned
+                    done = True
+                    break
+                if len(toks) == max_tokens:
+                    break
+                toks.append(int(t))
+                lps.append(float(l))
+                history.append(int(t))
+        spec_out = (toks, lps)
+        max_tokens = 0  # the loops below are done
     fused_greedy = (max_tokens > 0 and hasattr(model, "greedy_session")
                     and (dev.type == "cuda" or (temperature == 0 and getattr(model, "greedy_session_any_device", False)))  # (CPU stand-ins: tests)
                     and (getattr(model, "num_pipeline_ranks", 1) == 1 or getattr(model, "greedy_session_pp", False))
@@ -238,6 +324,9 @@ def generate(
         lp = torch.stack(gen_lp, 1).tolist()
         for b in range(B):
             logprobs[b].extend(lp[b])
+    elif spec_out is not None and spec_out[0]:
+        generated_tokens = [spec_out[0]]
+        logprobs[0].extend(spec_out[1])
     else:
         generated_tokens = []
     # the copies above synchronised the stream: the place to turn device-side flags (an out-of-range token id seen by the

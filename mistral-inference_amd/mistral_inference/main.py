@@ -15,7 +15,7 @@ from typing import List, Optional, Type, Union
 import torch
 
 from .cache import kv_dtype_arg
-from .generate import generate  # noqa: F401  (the reference's tests import generate from main)
+from .generate import SpeculativeArgs, generate  # noqa: F401  (the reference's tests import generate from main)
 from .transformer import Transformer
 
 
@@ -43,6 +43,13 @@ def share_prompt_length(n_tokens: int) -> int:
         buf = buf.cuda()
     torch.distributed.broadcast(buf, src=0)
     return int(buf.item())
+
+
+def speculative_arg(k: Optional[int]) -> Optional[SpeculativeArgs]:
+    """`--speculative K` of the command-line tools: None or 0 (plain decoding), or 1 .. 7 drafts per step from prompt lookup."""
+    if k is None or int(k) == 0:
+        return None
+    return SpeculativeArgs(k=int(k))  # (any other K is refused by name)
 
 
 def _should_print() -> bool:
@@ -78,10 +85,13 @@ def get_model_cls(model_path: str) -> Type[Transformer]:
 
 def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7, num_pipeline_ranks: int = 1,
                 instruct: bool = False, lora_path: Optional[str] = None, quantize: Optional[str] = None,
-                kv_dtype: Optional[str] = None) -> None:
+                kv_dtype: Optional[str] = None, speculative: Optional[int] = None) -> None:
     """quantize="fp8_e4m3" / "mxfp4": quantise a bf16 checkpoint to weight-only FP8 / MXFP4 while it loads (a folder that
-    quant.quantize_checkpoint wrote needs no flag).  kv_dtype="fp8_e4m3": K/V rings of e4m3 bytes (half the bytes; launch path)."""
+    quant.quantize_checkpoint wrote needs no flag).  kv_dtype="fp8_e4m3": K/V rings of e4m3 bytes (half the bytes; launch path).
+    speculative=K: greedy decoding that drafts up to K tokens per step by prompt lookup and verifies them in one pass over the
+    weights (needs temperature 0; generate() names what else it does not take)."""
     kv = kv_dtype_arg(kv_dtype)  # (an unknown name is refused before anything is loaded)
+    spec = speculative_arg(speculative)
     num_pipeline_ranks = init_pipeline() if is_torchrun() else num_pipeline_ranks
     should_print = _should_print()
     mistral_tokenizer = load_tokenizer(Path(model_path))
@@ -108,7 +118,7 @@ def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7,
             if not should_print:
                 tokens = n * [0]
         generated, _ = generate([tokens], model, max_tokens=max_tokens, temperature=temperature,
-                                eos_id=tokenizer.eos_id, kv_dtype=kv)
+                                eos_id=tokenizer.eos_id, kv_dtype=kv, speculative=spec)
         answer = tokenizer.decode(generated[0])
         if should_print:
             print(answer)
@@ -119,9 +129,10 @@ def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7,
 
 
 def demo(model_path: str, max_tokens: int = 35, temperature: float = 0, lora_path: Optional[str] = None,
-         quantize: Optional[str] = None, kv_dtype: Optional[str] = None) -> None:
-    """quantize, kv_dtype: as `interactive`."""
+         quantize: Optional[str] = None, kv_dtype: Optional[str] = None, speculative: Optional[int] = None) -> None:
+    """quantize, kv_dtype, speculative: as `interactive` (a speculative generation takes one prompt: the three run one by one)."""
     kv = kv_dtype_arg(kv_dtype)
+    spec = speculative_arg(speculative)
     num_pipeline_ranks = init_pipeline()
     should_print = _should_print()
     model = get_model_cls(model_path).from_folder(Path(model_path), max_batch_size=3,
@@ -131,8 +142,16 @@ def demo(model_path: str, max_tokens: int = 35, temperature: float = 0, lora_pat
     tokenizer = load_tokenizer(Path(model_path)).instruct_tokenizer.tokenizer
     prompts = ["This is a test", "This is another great test", "This is a third test, mistral AI is very good at testing. "]
     encoded = [tokenizer.encode(p, bos=True, eos=False) for p in prompts]
-    generated, logprobs = generate(encoded, model, max_tokens=max_tokens, temperature=temperature,
-                                   eos_id=tokenizer.eos_id, kv_dtype=kv)
+    if spec is None:
+        generated, logprobs = generate(encoded, model, max_tokens=max_tokens, temperature=temperature,
+                                       eos_id=tokenizer.eos_id, kv_dtype=kv)
+    else:
+        generated, logprobs = [], []
+        for e in encoded:
+            g, lp = generate([e], model, max_tokens=max_tokens, temperature=temperature, eos_id=tokenizer.eos_id, kv_dtype=kv,
+                             speculative=spec)
+            generated += g if g else [[]]
+            logprobs += lp
     if should_print:
         for p, g, lp in zip(prompts, generated, logprobs):
             print(p + tokenizer.decode(g))

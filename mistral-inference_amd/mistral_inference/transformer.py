@@ -279,8 +279,10 @@ class HipStackBackend:
         _hip.set_decode_engine(False)
         HipStackBackend._engine_suspended = True
 
-    def _get_workspace(self, model: "Transformer", m, T: int, B: int, max_w: int, kv_layout: int = 0) -> torch.Tensor:
-        if self.generic:
+    def _get_workspace(self, model: "Transformer", m, T: int, B: int, max_w: int, kv_layout: int = 0, verify: bool = False) -> torch.Tensor:
+        if verify:  # (split partials per row and the K | V stash of every layer: mi_workspace_bytes_verify)
+            need = _hip.lib().mi_workspace_bytes_verify(C.byref(m), 1 if self._quant is not None else 0, T, max_w, kv_layout)
+        elif self.generic:
             need = _hip.lib().mi_workspace_bytes_generic(C.byref(m), T, self.dtype_code)
         else:  # (rings of e4m3 bytes add the prefill scratch of one layer's dequantised rings; otherwise mi_workspace_bytes[_w8 / _w4])
             need = _hip.lib().mi_workspace_bytes_kv(C.byref(m), 1 if self._quant is not None else 0, T, B, max_w, kv_layout)
@@ -294,8 +296,10 @@ class HipStackBackend:
     # -- per forward -------------------------------------------------------------------------------
     def run_stack(self, model: "Transformer", h: torch.Tensor, input_ids: Optional[torch.Tensor],
                   meta: BatchMetadata, cache: Optional[BufferCache], logits: Optional[torch.Tensor],
-                  greedy: Optional["GreedyBuffers"] = None, seq_adapter: Any = "now") -> None:
-        """seq_adapter: the [B] adapter-slot tensor this launch carries (None: NULL); "now": what set_adapters chose last."""
+                  greedy: Optional["GreedyBuffers"] = None, seq_adapter: Any = "now",
+                  verify: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None) -> None:
+        """seq_adapter: the [B] adapter-slot tensor this launch carries (None: NULL); "now": what set_adapters chose last.
+        verify: (tokens int64 [T], logprobs fp32 [T], n_accept int32 [B]) - the launch is a verify step (mi_forward_verify)."""
         m = self.plan(model)
         T, B = h.shape[0], len(meta.seqlens)
         bt = _hip.MiBatch()
@@ -332,9 +336,18 @@ class HipStackBackend:
         if seq_adapter is not None:  # ABI v9: one adapter slot per sequence (meta.tok_seq names a row's sequence on every branch)
             assert seq_adapter.numel() >= B
             bt.seq_adapter = _hip.dev_ptr(seq_adapter, i32)
-        wsb = self._get_workspace(model, m, T, B, max_w, bt.kv_layout)
+        wsb = self._get_workspace(model, m, T, B, max_w, bt.kv_layout, verify=verify is not None)
         bt.workspace, bt.workspace_bytes = wsb.data_ptr(), wsb.numel()
-        if self.generic:
+        if verify is not None:
+            vo = _hip.MiVerifyOut()
+            vo.tokens, vo.logprobs = _hip.dev_ptr(verify[0], torch.long), _hip.dev_ptr(verify[1], torch.float32)
+            vo.n_accept = _hip.dev_ptr(verify[2], i32)
+            qm = self._quant[0] if self._quant is not None else None
+            w8 = C.byref(qm) if isinstance(qm, _hip.MiW8Model) else None
+            w4 = C.byref(qm) if isinstance(qm, _hip.MiW4Model) else None
+            _hip.check(_hip.lib().mi_forward_verify(C.byref(m), w8, w4, C.byref(bt), C.byref(vo), _hip.stream_ptr(h.device)),
+                       "mi_forward_verify")
+        elif self.generic:
             _hip.check(_hip.lib().mi_forward_generic(C.byref(m), C.byref(bt), self.dtype_code, _hip.stream_ptr(h.device)),
                        "mi_forward_generic")
         elif self._quant is not None:
@@ -601,6 +614,59 @@ class Transformer(ModelBase):
         """Decode loop of `generate()` (reference generate.py:120-140) with nothing but the model's own launches per token:
         see GreedySession.  temperature 0: argmax; temperature > 0: the nucleus draw of generate.py:151-170 on the device."""
         return GreedySession(self, cache, first_tokens, graph, temperature=temperature, top_p=top_p, seed=seed)
+
+    def refuse_verify(self, cache: Optional[BufferCache], model_only: bool = False) -> None:
+        """What a verify step does not run on, by name (the library refuses the same before any launch).  model_only: the
+        refusals that do not depend on the cache (generate() has none yet when it asks)."""
+        if self.num_pipeline_ranks > 1:
+            raise NotImplementedError("speculative decoding across pipeline ranks (num_pipeline_ranks > 1) is not implemented; "
+                                      "run the model on a single stage")
+        if self.dtype != torch.bfloat16 or getattr(self._backend, "generic", False):
+            raise NotImplementedError(f"speculative decoding with fp16 / fp32 storage or a shape outside the tuned bf16 kernels "
+                                      f"({self.dtype}) is not implemented; load the model in bfloat16")
+        if self.args.lora is not None:
+            raise NotImplementedError("speculative decoding with un-merged LoRA is not implemented; merge the adapter into the weights")
+        if model_only:
+            return
+        if cache is None:
+            raise ValueError("a verify step needs a cache that holds the sequence so far (cache=None)")
+        if cache.n_layers and cache.cache_k[0].dtype == torch.float8_e4m3fn:
+            raise NotImplementedError("speculative decoding on an FP8 K/V cache (kv_dtype=float8_e4m3fn) is not implemented; "
+                                      "use the model's own bf16 rings")
+
+    def verify_step(self, ids: torch.Tensor, seqlens: List[int], cache: BufferCache, return_logits: bool = False):
+        """One verify step of speculative greedy decoding (include/mistral_hip.h `mi_forward_verify`): sequence b brings
+        seqlens[b] <= 8 rows - its last emitted token, not yet cached, then drafted tokens - at the positions behind its cache.
+        Returns (tokens int64 [T], logprobs fp32 [T], n_accept list [B]): the argmax of every row and its log-softmax; the
+        first n_accept[b] + 1 of sequence b's rows are the tokens it emits.  Exactly those rows' K/V entered the rings and
+        the cache advanced by n_accept[b] + 1; a rejected draft leaves no trace.  One synchronisation (reading n_accept).
+        return_logits: also the fp32 logits [T, vocab] of every row, as a fourth value."""
+        tok, lp, n_acc, logits = self._verify_launch(ids, seqlens, cache)
+        n_accept = [int(a) for a in n_acc.tolist()]  # the one synchronisation
+        cache.advance_host([a + 1 for a in n_accept])  # (the commit kernel advanced the device copy)
+        return (tok, lp, n_accept, logits) if return_logits else (tok, lp, n_accept)
+
+    def _verify_launch(self, ids: torch.Tensor, seqlens: List[int], cache: BufferCache):
+        """The launches of a verify step, nothing read back: (tokens, logprobs, n_accept, logits) on the device.  The device
+        kv_seqlens are advanced by the commit kernel; the host mirror is the caller's to advance (verify_step does)."""
+        self.refuse_verify(cache)
+        T, B = sum(seqlens), len(seqlens)
+        if any(s < 1 for s in seqlens) or T > _hip.GEMV_MAX_T:
+            raise ValueError(f"a verify step takes 1 .. {_hip.GEMV_MAX_T} rows in all and at least one per sequence, got {seqlens}")
+        assert ids.shape == (T,), (ids.shape, seqlens)
+        _hip.check_ids_on_host(ids, self.vocab_size)
+        meta = cache.verify_metadata(seqlens)
+        if max(p + s for p, s in zip(cache._seen, seqlens)) > ROPE_TABLE_LEN:
+            raise IndexError(f"a verify step beyond the {ROPE_TABLE_LEN}-entry rotary table (reference transformer.py:116)")
+        dev = self.device
+        h = torch.empty((T, self.args.dim), device=dev, dtype=self.dtype)
+        logits = torch.empty((T, self.vocab_size), device=dev, dtype=torch.float32)
+        tok = torch.empty(T, device=dev, dtype=torch.long)
+        lp = torch.empty(T, device=dev, dtype=torch.float32)
+        n_acc = torch.empty(B, device=dev, dtype=torch.int32)
+        self._backend.run_stack(self, h, ids.to(device=dev, dtype=torch.long), meta, cache, logits, seq_adapter=None,
+                                verify=(tok, lp, n_acc))
+        return tok, lp, n_acc, logits
 
     def _logits(self, input_ids: torch.Tensor, seqlens: List[int], cache: Optional[BufferCache],
                 images: Optional[List[torch.Tensor]] = None) -> torch.Tensor:
