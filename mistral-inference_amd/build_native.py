@@ -36,6 +36,10 @@ PER_FILE_FLAGS = {"decode_engine.hip": os.environ.get("MI_ENGINE_FLAGS", "-mllvm
 # round 6: + the loader is not stopped during the hid sweep (ENG_NOSTOP=32: the ring is empty there; +0.1..0.7 % on six boxes)
 # round 7: + the holders' loads wait for the loader's ring-full waits or its Wo rows (ENG_HOLD_GATE=1; -1.5 .. -1.9 % per step on
 # three boxes, profiles/EXPERIMENTS.md round 7; a fourth held unit is kept as scripts/probes/decode_engine_round7_hold_split.patch)
+# round 10: with the gate, two of the holder waves also keep four q|k|v units of the NEXT layer, fetched while the loader waits for
+# a ring slot in the FFN.  No flag is added for it: ENG_QKV_HOLD=3 with ENG_QKV_WAVES=2 is what csrc/decode_engine.hip defaults
+# to in a dense build that passes ENG_HOLD_GATE=1 (-DENG_QKV_HOLD=0 gives round 7's holders back; profiles/EXPERIMENTS.md round
+# 10: six units and a fetch that ignores the hid sweep were measured on the same boxes)
 ENGINE_NEXT_FLAGS = ["-DENG_SUFFIX=_next", "-DENG_HEADLINE_ONLY=1", "-DENG_ABORT_RARE=1", "-DENG_CONS_PRIO=1", "-DENG_HOLD_STAGE=2",
                      "-DENG_SADDR=2", "-DENG_TRACE=0", "-DENG_NOSTOP=32", "-DENG_HOLD_GATE=1"]
 # round 6: Mistral-Nemo dims (dim 5120: rows of 10 pieces, contiguous units) on the 8-fill ring with every DMA from inline asm

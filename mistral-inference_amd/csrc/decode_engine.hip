@@ -42,16 +42,17 @@
 //
 //   object (EngineBuild name)        WIDE HEADLINE_ONLY TRACE SADDR QKV_HOLD ABORT_RARE CONS_PRIO HOLD_STAGE NOSTOP HOLD_GATE CLEAN_ENTRY
 //   decode_engine.o       "default"    0        0         1     0      0         0          0         3        0        0          0
-//   decode_engine_next.o  "next"       0        1         0     2      0         1          1         2       32        1          0
+//   decode_engine_next.o  "next"       0        1         0     2      3         1          1         2       32        1          0
 //   decode_engine_nemo.o  "nemo"       2        2         0     2      0         1          1         3       32        0          1
 //   decode_engine_wide.o  "wide"       1        0         1     0      2         1          1         3        0        0          0
 //   decode_engine_moe.o   "moe"        2        0         1     0      2         0          0         3        0        0          0
-//   (all five: ENG_HOLDERS 3, ENG_ALL4 1, ENG_STALL_TRACE 0; `next` and `nemo` also pass ENG_SUFFIX)
+//   (all five: ENG_HOLDERS 3, ENG_ALL4 1, ENG_STALL_TRACE 0; `next` and `nemo` also pass ENG_SUFFIX; `next` has QKV_HOLD 3 and
+//   ENG_QKV_WAVES 2 as the defaults that come with ENG_HOLD_GATE, the other values are passed or are the plain defaults)
 //
 // Values that no build, test or named experiment passes are refused (the #error below the defaults), their code is gone:
 // ENG_SADDR = 1 (the SGPR-base form through hipcc's builtin), ENG_QKV_HOLD = 1 (holders released by the loader's Wo stage) and
 // ENG_HOLD_STAGE = 0.
-// The measurements behind every choice are in profiles/EXPERIMENTS.md (rounds 3-7) and DESIGN.md section 3.  Shape-specific code
+// The measurements behind every choice are in profiles/EXPERIMENTS.md (rounds 3-10) and DESIGN.md section 3.  Shape-specific code
 // sits behind these switches because this kernel's speed moves by several per cent with ANY change of its instruction stream, and
 // a build must not pay for shapes it never runs: scripts/engine_isa_hash.sh prints a hash of an object's ISA, and an edit that is
 // meant to leave the device code alone is held to it, object by object.
@@ -76,13 +77,23 @@
 //   64-bit VGPR addresses hipcc guards every rewrite of the address pair with `s_waitcnt vmcnt(0)` - it treats the pair as the
 //   destination of a load - which drains the DMA queue once per unit in some builds and not in others (up to 30 % per step: the
 //   "regimes" of rounds 3-5).  scripts/engine_loader_waits.py finds such waits statically; tests/test_engine_build.py.
-// ENG_QKV_HOLD (0, 2): MoE models, whose holder waves have no W1|W3 unit to keep (which experts stream is decided late).  2: the
+// ENG_QKV_HOLD (0, 2, 3): 2: MoE models, whose holder waves have no W1|W3 unit to keep (which experts stream is decided late).  2: the
 //   three holder waves keep the LAST SIX q|k|v row-pair units of the NEXT layer in registers (two units = 4 rows = 128 VGPRs
 //   each; the wide build's rows of 12 pieces: one unit each), fetched in the one window of a MoE layer in which HBM idles - the
 //   router bubble, from the moment this workgroup has gathered h1 (C_HGO).  When attention_norm(h) of that layer stands in LDS
 //   they reduce their rows from registers (the arithmetic of Cons::unit_dot<2>: bit-identical) and run the consumers' epilogue
 //   (RoPE, ring write, granule): 96 KiB per workgroup and layer that no longer pass through the ring in the loader-bound q|k|v
 //   phase.
+//   3 (dense models; needs ENG_HOLD_GATE): holder waves 0 .. ENG_QKV_WAVES - 1 carry BOTH duties in turn (run_holder_both; their
+//   128 registers hold one at a time): the W1|W3 unit of layer l, fetched from the K/V stage on and reduced at ffn_norm(h1), and
+//   then two q|k|v units each of layer l + 1, reduced at attention_norm(h) of that layer.  Those loads are issued 8 at a time
+//   only while the loader waits for a ring slot (C_LFULL), no sweep is in progress and (ENG_QKV_SWEEP = 0) the consumers are not
+//   sweeping the hid granules - the time in which this CU's HBM stream idles.  Escapes: once the loader has issued the layer's
+//   last W2 piece (C_LEND; still between sweeps) or the next layer's norm stands in LDS (C_XA; at once), so a ring that never
+//   fills costs time and never correctness.  Layer 0 of a launch is fetched at entry, the last layer fetches nothing.
+//   It is the default of a dense build with ENG_HOLD_GATE (the gate's C_LFULL is what places the loads); such a build passes
+//   ENG_QKV_HOLD=0 to get round 7's single-duty holders (run_holder_x).
+// ENG_QKV_WAVES (1 .. ENG_HOLDERS, default 2: four held units measured faster than six), ENG_QKV_SWEEP (0, 1): see ENG_QKV_HOLD = 3.
 // ENG_ALL4 (1, 0): 1 lets instantiations whose weight rows are all multiples of 4 pieces (dim, n_heads*128 and hidden_dim multiples
 //   of 2048 - every BASELINE model but Nemo) drop the generic-group path from the five row loops of the consumers.
 // ENG_ABORT_RARE (0, 1): 1 reads the abort word on every 1024th iteration of a spin only (one LDS read less per poll).
@@ -115,9 +126,6 @@
 #ifndef ENG_SADDR
 #define ENG_SADDR 0
 #endif
-#ifndef ENG_QKV_HOLD
-#define ENG_QKV_HOLD 0
-#endif
 #ifndef ENG_ALL4
 #define ENG_ALL4 1
 #endif
@@ -136,14 +144,32 @@
 #ifndef ENG_HOLD_GATE
 #define ENG_HOLD_GATE 0
 #endif
+#ifndef ENG_QKV_HOLD  // (the gate is what lets dense holders take the second duty: a gated dense build has it unless it says 0)
+#if ENG_HOLD_GATE && !ENG_WIDE
+#define ENG_QKV_HOLD 3
+#else
+#define ENG_QKV_HOLD 0
+#endif
+#endif
 #ifndef ENG_CLEAN_ENTRY
 #define ENG_CLEAN_ENTRY 0
 #endif
 #ifndef ENG_STALL_TRACE
 #define ENG_STALL_TRACE 0
 #endif
-#if (ENG_SADDR != 0 && ENG_SADDR != 2) || (ENG_QKV_HOLD != 0 && ENG_QKV_HOLD != 2) || ENG_HOLD_STAGE < 1 || ENG_HOLD_STAGE > 3
-#error "ENG_SADDR and ENG_QKV_HOLD take 0 or 2, ENG_HOLD_STAGE takes 1, 2 or 3: the values that are built"
+#if (ENG_SADDR != 0 && ENG_SADDR != 2) || (ENG_QKV_HOLD != 0 && ENG_QKV_HOLD != 2 && ENG_QKV_HOLD != 3) || ENG_HOLD_STAGE < 1 || ENG_HOLD_STAGE > 3
+#error "ENG_SADDR takes 0 or 2, ENG_QKV_HOLD 0, 2 or 3, ENG_HOLD_STAGE 1, 2 or 3: the values that are built"
+#endif
+#if ENG_QKV_HOLD == 3
+#ifndef ENG_QKV_WAVES
+#define ENG_QKV_WAVES 2
+#endif
+#ifndef ENG_QKV_SWEEP
+#define ENG_QKV_SWEEP 0
+#endif
+#if !ENG_HOLD_GATE || ENG_WIDE || ENG_QKV_WAVES < 1 || ENG_QKV_WAVES > ENG_HOLDERS
+#error "ENG_QKV_HOLD = 3 is the dense build's second holder duty: it needs ENG_HOLD_GATE, ENG_WIDE = 0 and 1 .. ENG_HOLDERS waves"
+#endif
 #endif
 #if ENG_STALL_TRACE && ENG_TRACE != 1
 #error "ENG_STALL_TRACE needs the stamp sites (ENG_TRACE = 1)"
@@ -219,6 +245,10 @@ enum : int {
 #if ENG_HOLD_GATE
   C_LFULL = 16,     // ENG_HOLD_GATE: 1 while the loader waits for a free ring slot (loader -> holders)
   C_LWO = 17,       // ENG_HOLD_GATE: (layer + 1) once this layer's Wo rows are issued (loader -> holders)
+#endif
+#if ENG_QKV_HOLD == 3
+  C_LEND = 18,      // ENG_QKV_HOLD = 3: (layer + 1) once the loader has issued the layer's last W2 piece (loader -> holders)
+  C_HIDSWEEP = 19,  // ENG_QKV_HOLD = 3: 1 while the consumers sweep the hid granules (ENG_NOSTOP may keep C_GATHERING down there)
 #endif
   C_XA = 21,        // ENG_QKV_HOLD: (layer + 1) once attention_norm(h) of that layer stands in the activation region (-> holders)
   C_HGO = 23,       // ENG_QKV_HOLD: (layer + 1) once this workgroup has h1 of that layer (the router runs next: no sweep for a while)
@@ -340,6 +370,9 @@ __device__ __forceinline__ int holder_units(const EngArgs& a, int n_f) {
   return (NHOLD > 0 && a.holders && a.E == 0 && unit_group(P) == 4 && (P >> 2) <= HOLD_GROUPS && n_f >= 2 * NCONS + NHOLD) ? NHOLD : 0;
 }
 
+#if ENG_QKV_HOLD == 3
+constexpr int QKV_WAVES = ENG_QKV_WAVES;  // holder waves that also keep two q|k|v units of the next layer
+#endif
 #if ENG_QKV_HOLD
 // q|k|v units (row pairs) of a workgroup that the holder waves keep in registers: the last 2 * NHOLD of the list q.., k.., v..
 __device__ __forceinline__ int qkv_held(const EngArgs& a, int n_u) {
@@ -347,6 +380,11 @@ __device__ __forceinline__ int qkv_held(const EngArgs& a, int n_u) {
 #if ENG_WIDE == 1
   // rows of 9-12 pieces (Mixtral-8x22B: dim 6144): a holder keeps ONE unit (2 rows x 12 pieces = 96 VGPRs): run_qkv_holder1
   if (NHOLD > 0 && a.holders && a.E > 0 && unit_group(P) == 4 && (P >> 2) == HOLD_GROUPS + 1 && n_u >= NCONS + NHOLD) return NHOLD;
+#endif
+#if ENG_QKV_HOLD == 3
+  // dense models: holder waves 0 .. QKV_WAVES - 1 carry BOTH duties (run_holder_both), two q|k|v units each.  Their registers are
+  // free from the W1|W3 rows of a layer to the K/V stage of the next one.
+  if (a.E == 0) return (NHOLD > 0 && a.holders && unit_group(P) == 4 && (P >> 2) <= HOLD_GROUPS && n_u >= NCONS + 2 * QKV_WAVES) ? 2 * QKV_WAVES : 0;
 #endif
   return (NHOLD > 0 && a.holders && a.E > 0 && unit_group(P) == 4 && (P >> 2) <= HOLD_GROUPS && n_u >= NCONS + 2 * NHOLD) ? 2 * NHOLD : 0;
 }
@@ -627,7 +665,15 @@ __device__ __forceinline__ void run_loader(const EngArgs& a, const Shared& sh, i
     plan_layer(a, L, c, pos, p);
     const bool tr = lane == 0;
     trace_ev(sh, c, l, TR_CONS + 0, tr);
-#if ENG_QKV_HOLD
+#if ENG_QKV_HOLD == 3
+    {  // the list q.., k.., v.. without its last qkv_held() units, as three row-pair loops (the shape of the loader without holders)
+      const int nq_u = p.q1 - p.q0, nk_u = p.k1 - p.k0;
+      const int n_s = nq_u + 2 * nk_u - qkv_held(a, nq_u + 2 * nk_u);
+      ld.pairs(L.wq, p.q0, p.q0 + min(nq_u, n_s), a.D);
+      ld.pairs(L.wk, p.k0, p.k0 + min(nk_u, max(n_s - nq_u, 0)), a.D);
+      ld.pairs(L.wv, p.v0, p.v0 + min(nk_u, max(n_s - nq_u - nk_u, 0)), a.D);
+    }
+#elif ENG_QKV_HOLD
     if (const int n_held = qkv_held(a, (p.q1 - p.q0) + 2 * (p.k1 - p.k0))) {  // the list without its last n_held units
       const int n_s = (p.q1 - p.q0) + 2 * (p.k1 - p.k0) - n_held;
       for (int k = 0; k < n_s; ++k) {
@@ -638,11 +684,13 @@ __device__ __forceinline__ void run_loader(const EngArgs& a, const Shared& sh, i
       }
     } else
 #endif
+#if ENG_QKV_HOLD != 3
     {
       ld.pairs(L.wq, p.q0, p.q1, a.D);
       ld.pairs(L.wk, p.k0, p.k1, a.D);
       ld.pairs(L.wv, p.v0, p.v1, a.D);
     }
+#endif
     trace_ev(sh, c, l, TR_CONS + 1, tr);
     if (NHOLD && ENG_HOLD_STAGE == 1) sh.ctl[C_LSTAGE] = (uint32_t)(l + 1);
     if (p.n_att) {  // K piece j, V piece j: 4 ring slots x 256 B each (slots past the ring end are clamped; masked later)
@@ -685,6 +733,9 @@ __device__ __forceinline__ void run_loader(const EngArgs& a, const Shared& sh, i
       }
       trace_ev(sh, c, l, TR_CONS + 4, tr);
       ld.pairs(L.w2, p.o0, p.o1, a.F);
+#if ENG_QKV_HOLD == 3
+      sh.ctl[C_LEND] = (uint32_t)(l + 1);  // the layer's stream is issued: no ring-full wait of this layer is left to wait for
+#endif
     } else {
       // MoE (moe.py:24-32): WHICH expert matrices stream next is decided by the router, i.e. by this layer's activations:
       // the one edge where the loader cannot run ahead.  Everything issued so far must be visible to the consumers (they
@@ -1433,7 +1484,11 @@ __device__ __forceinline__ void run_consumer(const EngArgs& a, const Shared& sh,
     cs.cbar();  // every wave is done with the normalised activations: the region becomes attention scratch
 #if ENG_QKV_HOLD
     if (qkv_held(a, (p.q1 - p.q0) + 2 * (p.k1 - p.k0))) {  // ... and so are the holder waves (they finished long ago: 4 rows each)
+#if ENG_QKV_HOLD == 3
+      hq_target += (uint32_t)QKV_WAVES;
+#else
       hq_target += (uint32_t)NHOLD;
+#endif
       uint32_t spins = 0;
       while (sh.ctl[C_HQDONE] < hq_target)
         if (!spin_ok(sh, spins, 0x500)) break;
@@ -1670,9 +1725,15 @@ __device__ __forceinline__ void run_consumer(const EngArgs& a, const Shared& sh,
           if (!spin_ok(sh, spins, 0x500)) break;
       }
       sh.ctl[C_GATHERING] = GATHER_FLAG(32);
+#if ENG_QKV_HOLD == 3 && !ENG_QKV_SWEEP
+      sh.ctl[C_HIDSWEEP] = 1;
+#endif
       cs.gather<14>(G + a.g_hid, a.F / 2, tag_of(l, 5), xs32);
       cs.cbar();
       sh.ctl[C_GATHERING] = 0;
+#if ENG_QKV_HOLD == 3 && !ENG_QKV_SWEEP
+      sh.ctl[C_HIDSWEEP] = 0;
+#endif
       trace_ev(sh, c, l, 15, trc);
       {
         const int n_u = p.o1 - p.o0;
@@ -2171,6 +2232,149 @@ __device__ __forceinline__ void run_holder_x(const EngArgs& a, const Shared& sh,
 }
 #endif
 
+#if ENG_QKV_HOLD == 3
+// Dense models, BOTH duties of a holder wave in one loop over the same 128 registers.  Per layer l: reduce and publish the two
+// q|k|v units of layer l (held since the previous trip; layer 0 of a launch: fetched at entry), fetch the W1|W3 unit of layer l
+// under run_holder_x's gate, reduce it when ffn_norm(h1) stands in LDS, then fetch the q|k|v units of layer l + 1 - while the
+// loader waits for a ring slot in the FFN of layer l, which is when this CU's HBM stream idles.  The last layer of a launch
+// fetches nothing.  Arithmetic and publication are those of run_qkv_holder / run_holder_x: bit-identical results.
+__device__ __forceinline__ bool hold_may_fetch_qkv(const Shared& sh, int l) {  // units of layer l + 1, asked in the FFN of layer l
+  if (sh.ctl[C_XA] >= (uint32_t)(l + 2)) return true;  // the next layer's norm stands: the rows are due, fetch whatever goes on
+  if (sh.ctl[C_GATHERING]) return false;
+  if (sh.ctl[C_LEND] >= (uint32_t)(l + 1)) return true;  // the layer's last W2 piece is issued: no ring-full wait left to wait for
+  return (ENG_QKV_SWEEP || !sh.ctl[C_HIDSWEEP]) && sh.ctl[C_LFULL];
+}
+
+__device__ __forceinline__ void run_holder_both(const EngArgs& a, const Shared& sh, int c, int hi, int lane, int pos, int seq, uint32_t epoch) {
+  gu64* G = (gu64*)a.gran;
+  const int PD = a.D >> 9;
+  const lchar* xl = sh.xs + lane * 16;
+  const int nq = a.H * DH, nkv = a.Hkv * DH;
+  bool hold_q;
+  {
+    LayerPlan p0;
+    plan_layer(a, a.L[0], c, pos, p0);
+    hold_q = hi < QKV_WAVES && qkv_held(a, (p0.q1 - p0.q0) + 2 * (p0.k1 - p0.k0)) != 0;  // (the same answer for every layer)
+  }
+  u32x4 hw[HOLD_GROUPS][4][4];  // [group][row][piece in group]: constant indices only -> registers; one duty at a time
+  auto fetch = [&](const bf16_t* const (&rows)[4], auto&& may) -> bool {
+#pragma unroll
+    for (int grp = 0; grp < HOLD_GROUPS; ++grp) {
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {  // 8 loads, then look again whether this CU's HBM stream has room for them
+        uint32_t spins = 0;
+        while (!may())
+          if (!spin_ok(sh, spins, 0x600)) return false;
+#pragma unroll
+        for (int r = 2 * half; r < 2 * half + 2; ++r)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) hw[grp][r][q] = ld16_nt(rows[r] + (size_t)min(grp * 4 + q, PD - 1) * 512);
+      }
+    }
+    return true;
+  };
+  auto reduce = [&](float (&v)[4]) {
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int grp = 0; grp < HOLD_GROUPS; ++grp)
+      if (grp * 4 < PD) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const u32x4 xv = lds16(xl + (grp * 4 + q) * PIECE);
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[r] = dot2_bf16(hw[grp][r][q][i], xv[i], acc[r]);
+        }
+      }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = wave_sum(acc[r]);
+  };
+  auto fetch_qkv = [&](int l, auto&& may) -> bool {
+    const EngLayer& L = a.L[l];
+    LayerPlan p;
+    plan_layer(a, L, c, pos, p);
+    const int n_u = (p.q1 - p.q0) + 2 * (p.k1 - p.k0);
+    int kind0, u0, kind1, u1;
+    qkv_unit(p, n_u - 2 * QKV_WAVES + 2 * hi, kind0, u0);
+    qkv_unit(p, n_u - 2 * QKV_WAVES + 2 * hi + 1, kind1, u1);
+    const bf16_t* b0 = (kind0 == 0 ? L.wq : (kind0 == 1 ? L.wk : L.wv)) + (size_t)(2 * u0) * a.D + lane * 8;
+    const bf16_t* b1 = (kind1 == 0 ? L.wq : (kind1 == 1 ? L.wk : L.wv)) + (size_t)(2 * u1) * a.D + lane * 8;
+    const bf16_t* rows[4] = {b0, b0 + a.D, b1, b1 + a.D};
+    return fetch(rows, may);
+  };
+  // Trip l = -1 only fetches: layer 0 of a launch has nothing prefetched, and hold_may_fetch_qkv(-1) says "at once, between
+  // sweeps" (a later launch of the step gathers h first).  Loads have no side effects; the ring rows and granules wait for C_XA,
+  // which the consumers raise behind the residency gate.  (One loop, one fetch site: with a second fetch site in front of the
+  // loop hipcc moves the LOADER's ring addresses into VGPRs, which its DMA statements cannot take.)
+  for (int l = -1; l < a.n_layers; ++l) {
+    const EngLayer& L = a.L[max(l, 0)];
+    LayerPlan p;
+    plan_layer(a, L, c, pos, p);
+    uint32_t spins = 0;
+    if (hold_q && l >= 0) {  // ---- the q|k|v units of this layer
+      const int n_u = (p.q1 - p.q0) + 2 * (p.k1 - p.k0);
+      int kind0, u0, kind1, u1;
+      qkv_unit(p, n_u - 2 * QKV_WAVES + 2 * hi, kind0, u0);
+      qkv_unit(p, n_u - 2 * QKV_WAVES + 2 * hi + 1, kind1, u1);
+      const float2 cs0 = *reinterpret_cast<const float2*>(a.rope_cs + ((size_t)pos * (DH >> 1) + (((2 * u0) % DH) >> 1)) * 2);
+      const float2 cs1 = *reinterpret_cast<const float2*>(a.rope_cs + ((size_t)pos * (DH >> 1) + (((2 * u1) % DH) >> 1)) * 2);
+      while (sh.ctl[C_XA] < (uint32_t)(l + 1))
+        if (!spin_ok(sh, spins, 0x600)) return;
+      float v[4];
+      reduce(v);
+      if (lane == 0) {
+        const uint32_t tag = (epoch << 12) | (uint32_t)((a.seq_base + l) * 8 + 1 + 1);
+        auto finish = [&](int kind, int u, float2 cs2, float d0, float d1) {
+          float y0 = bf_round(d0), y1 = bf_round(d1);
+          if (kind < 2) {  // rope.py:13-23 on the adjacent pair
+            float re, im;
+            rope_pair(y0, y1, cs2.x, cs2.y, re, im);
+            y0 = re;
+            y1 = im;
+          }
+          const uint32_t packed = pack_bf2(y0, y1);
+          if (kind > 0) {  // cache.py:83-92
+            bf16_t* ring = (kind == 1 ? L.ck : L.cv) + kv_offset(L.kv_layout, L.W, nkv, DH, (size_t)seq, p.cur_slot, 2 * u);
+            *reinterpret_cast<uint32_t*>(ring) = packed;
+          }
+          const int gi = (kind == 0 ? 0 : (kind == 1 ? nq / 2 : nq / 2 + nkv / 2)) + u;
+          __hip_atomic_store(G + a.g_qkv + gi, ((unsigned long long)tag << 32) | packed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        };
+        finish(kind0, u0, cs0, v[0], v[1]);
+        finish(kind1, u1, cs1, v[2], v[3]);
+        // the LDS reads of x above were consumed by the dots: the region may become attention scratch once every holder says so
+        __hip_atomic_fetch_add((lu32*)(sh.ctl + C_HQDONE), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+    }
+    // ---- the W1|W3 unit of this layer (run_holder_x)
+    const int n_hold = holder_units(a, p.f1 - p.f0);
+    if (hi < n_hold && l >= 0) {
+      const int j = p.f1 - n_hold + hi;
+      spins = 0;
+      while (sh.ctl[C_LSTAGE] < (uint32_t)(l + 1))  // not before the layer's q|k|v and K/V streams are on their way
+        if (!spin_ok(sh, spins, 0x600)) return;
+      const size_t r0 = (size_t)(2 * j) * a.D + lane * 8;
+      const bf16_t* rows[4] = {L.w1 + r0, L.w3 + r0, L.w1 + r0 + a.D, L.w3 + r0 + a.D};
+      if (!fetch(rows, [&] { return hold_may_fetch(sh, l); })) return;
+      spins = 0;
+      while (sh.ctl[C_XREADY] < (uint32_t)(l + 1))
+        if (!spin_ok(sh, spins, 0x600)) return;
+      float v[4];
+      reduce(v);
+      if (lane == 0) {
+        const uint32_t tag = (epoch << 12) | (uint32_t)((a.seq_base + l) * 8 + 5 + 1);
+        const uint32_t packed = (uint32_t)f_to_bf(swiglu_bf(v[0], v[1])) | ((uint32_t)f_to_bf(swiglu_bf(v[2], v[3])) << 16);
+        __hip_atomic_store(G + a.g_hid + j, ((unsigned long long)tag << 32) | packed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add((lu32*)(sh.ctl + C_HDONE), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+    }
+    // ---- the q|k|v units of the next layer: the registers are free (the W1|W3 unit is reduced), the loads wait for idle HBM time
+    if (hold_q && l + 1 < a.n_layers && !fetch_qkv(l + 1, [&] { return hold_may_fetch_qkv(sh, l); })) return;
+  }
+}
+#endif
+
 // MOE is a separate instantiation: the dense kernel must not pay registers for the router / two-expert code (it sits at
 // 247 of 256 VGPRs and spilled with the MoE path compiled in)
 template <int R, bool MOE, bool ALL4>
@@ -2206,6 +2410,9 @@ __global__ __launch_bounds__(NTHREADS, 1) void decode_engine_kernel(const EngArg
   else if (w > NCONS && MOE && ((a.D >> 9) >> 2) == HOLD_GROUPS + 1) run_qkv_holder1(a, sh, c, w - NCONS - 1, lane, pos, seq, epoch);
 #endif
   else if (w > NCONS && MOE) run_qkv_holder(a, sh, c, w - NCONS - 1, lane, pos, seq, epoch);
+#endif
+#if ENG_QKV_HOLD == 3
+  else if (w > NCONS && !MOE) run_holder_both(a, sh, c, w - NCONS - 1, lane, pos, seq, epoch);
 #endif
 #if ENG_HOLD_GATE
   else if (w > NCONS) run_holder_x(a, sh, c, w - NCONS - 1, lane, pos, epoch);

@@ -127,11 +127,27 @@ ENGINE_SLOTS = {
     # round 7: the holders' fetch tied to the loader's ring-full waits (ENG_HOLD_GATE; the fourth held unit, ENG_HOLD_SPLIT, is kept as
     # scripts/probes/decode_engine_round7_hold_split.patch); the t_* slots keep the stamp sites and time the loader's ring-full waits
     "r7_ce": _N0 + _CE + ("-DENG_NOSTOP=32",),
-    "r7_gate": _N0 + ("-DENG_NOSTOP=32", "-DENG_HOLD_GATE=1"),
+    "r7_gate": _N0 + ("-DENG_NOSTOP=32", "-DENG_HOLD_GATE=1"),   # (since round 10 these flags compile the holders' second duty too)
+    "r7_gate_only": _N0 + ("-DENG_NOSTOP=32", "-DENG_HOLD_GATE=1", "-DENG_QKV_HOLD=0"),   # round 7's code: single-duty holders
     # timelines of the round-6 and the shipped round-7 flags, built the same way: with the stamp sites and the clean entry (without
     # it both stamp builds carry 30 / 31 DMA-queue drains in the loader's loops - scripts/engine_loader_waits.py)
     "r7_t_base": _NS + _CE + ("-DENG_NOSTOP=32", "-DENG_STALL_TRACE=1"),
-    "r7_t_gate": _NS + _CE + ("-DENG_NOSTOP=32", "-DENG_STALL_TRACE=1", "-DENG_HOLD_GATE=1"),
+    "r7_t_gate": _NS + _CE + ("-DENG_NOSTOP=32", "-DENG_STALL_TRACE=1", "-DENG_HOLD_GATE=1", "-DENG_QKV_HOLD=0"),
+    # round 10: the holders' second duty (ENG_QKV_HOLD=3, run_holder_both) - the next layer's last six q|k|v units, fetched while the
+    # loader waits for a ring slot in the FFN and not during the hid sweep; the two rejected alternatives; timelines as in round 7
+    # (ENG_QKV_HOLD=3 with ENG_QKV_WAVES=2 became the source's default for a gated dense build when `r10_qh4` won: the slots spell
+    # both out, `r7_gate_only` is the parent of the round, and `shipped` = `r7_gate` = `r10_qh4` in code)
+    "r10_qh": _N0 + ("-DENG_NOSTOP=32", "-DENG_HOLD_GATE=1", "-DENG_QKV_HOLD=3", "-DENG_QKV_WAVES=3"),
+    "r10_qh_ce": _N0 + _CE + ("-DENG_NOSTOP=32", "-DENG_HOLD_GATE=1", "-DENG_QKV_HOLD=3", "-DENG_QKV_WAVES=3"),
+    "r10_qh_sweep": _N0 + ("-DENG_NOSTOP=32", "-DENG_HOLD_GATE=1", "-DENG_QKV_HOLD=3", "-DENG_QKV_WAVES=3", "-DENG_QKV_SWEEP=1"),   # ... also during the hid sweep
+    "r10_qh4": _N0 + ("-DENG_NOSTOP=32", "-DENG_HOLD_GATE=1", "-DENG_QKV_HOLD=3", "-DENG_QKV_WAVES=2"),       # four held units, not six
+    "r10_qh4_sweep": _N0 + ("-DENG_NOSTOP=32", "-DENG_HOLD_GATE=1", "-DENG_QKV_HOLD=3", "-DENG_QKV_WAVES=2", "-DENG_QKV_SWEEP=1"),
+    "r10_qh2": _N0 + ("-DENG_NOSTOP=32", "-DENG_HOLD_GATE=1", "-DENG_QKV_HOLD=3", "-DENG_QKV_WAVES=1"),       # two held units
+    "r10_qh2_sweep": _N0 + ("-DENG_NOSTOP=32", "-DENG_HOLD_GATE=1", "-DENG_QKV_HOLD=3", "-DENG_QKV_WAVES=1", "-DENG_QKV_SWEEP=1"),
+    "r10_t_qh": _NS + _CE + ("-DENG_NOSTOP=32", "-DENG_STALL_TRACE=1", "-DENG_HOLD_GATE=1", "-DENG_QKV_HOLD=3", "-DENG_QKV_WAVES=3"),
+    "r10_t_qh4": _NS + _CE + ("-DENG_NOSTOP=32", "-DENG_STALL_TRACE=1", "-DENG_HOLD_GATE=1", "-DENG_QKV_HOLD=3", "-DENG_QKV_WAVES=2"),
+    "r10_t_qh4_sweep": _NS + _CE + ("-DENG_NOSTOP=32", "-DENG_STALL_TRACE=1", "-DENG_HOLD_GATE=1", "-DENG_QKV_HOLD=3", "-DENG_QKV_WAVES=2",
+                                     "-DENG_QKV_SWEEP=1"),
 }
 
 
