@@ -94,7 +94,7 @@ struct Workspace {
   bf16_t* deq;       // quantised models at T > 8 (behind everything else, such models only): the dequantised weights of one linear
   bf16_t* kv_deq;    // e4m3 K/V rings (behind everything else, such forwards only): one layer's rings of the batch as bf16, K then V,
                      //     for the prefill attention (kv_scratch_elems).  (deq: deq_scratch_elems.  lora_base: the GEMV's LOGITS form, see
-                     //     lora_linear; bf16 above 8 rows.  Wo's and W2's base product goes to xn.)
+                     //     linear_group; bf16 above 8 rows.  Wo's and W2's base product goes to xn.)
   bf16_t* stash;     // verify steps (behind everything else, such steps only): the step's post-RoPE K | V rows of every layer
   size_t total;      //     [n_layers, T, 2 * n_kv_heads * head_dim], which enter the rings once acceptance is known
 };
@@ -162,8 +162,8 @@ Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool qu
   return w;
 }
 
-// ---- GemvArgs of the fused modes, one builder each: the only places in this file that name the mode (mi_linear maps the
-// public epilogue codes itself).  Pointers are to 2-byte elements of either compile of gemv.hip; T is set per pass below.
+// ---- GemvArgs of the fused modes, one builder each, for mi_forward_generic's fp16 rows (every bf16 / quantised linear goes
+// through linear_group below).  Pointers are to 2-byte elements of either compile of gemv.hip; T is set per pass below.
 GemvArgs gemv_common(const void* x, int ldx, int K, int N, const void* norm_w, float eps, void* out, int ldo) {
   GemvArgs a;
   memset(&a, 0, sizeof(a));
@@ -287,10 +287,10 @@ int dequant_group(const void* w[3], const Scales<typename Q::scale_t>& sc, const
   d.N = n; d.K = K; d.out = out;
   return hip_rc(Q::launch_dequant(d, s), what);
 }
-// the (up to three) linears of a layer that a launch of forward_body reads, in the field order of mi_w8_layer_t / mi_w4_layer_t; -1: none
-enum { LIN_WQ = 0, LIN_WK, LIN_WV, LIN_WO, LIN_W1, LIN_W2, LIN_W3 };
-struct Lins {
-  int i[3];
+struct PlainBf16 {  // no format: what the q|k|v leaf that the formats share reads of a trait, for bf16 weights (no scales)
+  typedef float scale_t;
+  static constexpr int kFormat = 0;
+  static constexpr const char *kLinear = "mi_linear", *kQkv = "mi_qkv_rope_kvwrite", *kQkvGemv = "qkv gemv";
 };
 // The quantisation that forward_body runs a model under: what mi_forward_w8 / mi_forward_w4 were handed, as one argument.
 struct QuantModel {
@@ -304,14 +304,10 @@ template <class Fn>
 int with_format(int format, Fn&& f) { return format == MI_W4_MXFP4 ? f(QuantW4{}) : f(QuantW8{}); }
 inline const mi_w8_layer_t* layers_of(const QuantModel& q, QuantW8) { return q.l8; }
 inline const mi_w4_layer_t* layers_of(const QuantModel& q, QuantW4) { return q.l4; }
-
-// out[M, N] = epi(a[M, K] @ w0^T (, a @ w1^T)): the plain GEMM of one weight matrix, or of W1 and W3 for GEMM_SWIGLU
-GemmArgs gemm_args(int epi, const bf16_t* a, int M, int K, const void* w0, const void* w1, int N, void* out, const bf16_t* residual) {
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.epi = epi; g.M = M; g.N = N; g.K = K; g.a = a; g.lda = K;
-  g.w0 = (const bf16_t*)w0; g.w1 = (const bf16_t*)w1; g.n0 = g.n1 = N; g.out = out; g.ldo = N; g.residual = residual;
-  return g;
+// of the one struct that an entry point was handed (neither: not read)
+QuantModel quant_model(const mi_w8_model_t* w8, const mi_w4_model_t* w4) {
+  if (w8) return {MI_W8_FP8_E4M3, w8->format, w8->layers, nullptr};
+  return w4 ? QuantModel{MI_W4_MXFP4, w4->format, nullptr, w4->layers} : QuantModel{};
 }
 
 // ---- MoE FFN of T <= 8 tokens: per (token, slot) gate | up + SwiGLU into hid [T * top_k, F], then per token the down
@@ -362,64 +358,7 @@ int moe_grouped(void* out, const void* residual, const void* x, int T, int D, in
   return hip_rc(launch_moe_combine(out, residual, w.y, sel_idx, sel_w, w.row_of, T, D, k, s), "moe combine");
 }
 
-// ---- un-merged LoRA linear (lora.py:71-74): the base product by the tuned GEMV / GEMM in its plain store form, then lora_down and
-// lora_up (lora.hip).  One description for the leaf (mi_lora_linear) and for the linears of mi_forward.
-struct LoraLinear {
-  const void* w[3];     // weight segments as mi_linear takes them (SWIGLU: W1, W3)
-  const void* A[3];     // [rank, K] per segment or nullptr
-  const void* B[3];     // [rows of the segment, rank] or nullptr
-  int n_rows[3];
-  int nseg;
-  int epilogue;         // MI_EPI_STORE / RESIDUAL / SWIGLU
-  // adapter bank (ABI v9; all zero: one adapter set, the kernels' single-adapter mode).  seq_slot != nullptr: A[i] / B[i] are the
-  // bases of [slots, rank, K] / [slots, n_rows[i], rank] arrays and row m runs through slot seq_slot[tok_seq[m]] (kernels.h)
-  LoraBank bank;
-};
-// x: the input of W as the base pass reads it (pre-norm when norm_w is given: the GEMV fuses the RMSNorm); xn: the normalised
-// input (== x without norm_w), which lora_down reads.  base: [M, sum of n_rows] scratch - bf16, or with base_f32 fp32 holding
-// bf16 values: the GEMV's LOGITS form, whose fused RMSNorm is the one of the fused q|k|v and W1|W3 modes (gemv_core.cuh
-// kNormMode: same staging, same order of the sum of squares), so that a model whose adapters are zero reproduces the plain
-// model bit for bit.  M <= 8 only; needs M <= gemv passes like every GEMV launch here.
-int lora_linear(void* out, int ldo, const void* x, int ldx, const void* xn, int ldxn, int M, int K, const LoraLinear& L, const void* residual,
-                const void* norm_w, float eps, int rank, float scaling, void* base, bool base_f32, bf16_t* t, hipStream_t s) {
-  const bool swiglu = L.epilogue == MI_EPI_SWIGLU;
-  int n_total = 0;
-  for (int i = 0; i < L.nseg; ++i) n_total += L.n_rows[i];
-  const int n0 = L.n_rows[0], n1 = L.nseg > 1 ? n0 + L.n_rows[1] : n_total;
-  if (M <= GEMV_MAX_T) {
-    GemvArgs a = gemv_common(x, ldx, K, n_total, norm_w, eps, base, n_total);
-    a.mode = base_f32 ? GEMV_LOGITS : GEMV_STORE;
-    a.w0 = (const bf16_t*)L.w[0]; a.w1 = (const bf16_t*)L.w[1]; a.w2 = (const bf16_t*)L.w[2]; a.n0 = n0; a.n1 = n1;
-    MI_TRY(gemv_passes(kGemvBf16, a, M, s, "lora base gemv"));
-  } else {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.epi = GEMM_STORE; g.M = M; g.N = n_total; g.K = K; g.a = (const bf16_t*)x; g.lda = ldx;
-    g.w0 = (const bf16_t*)L.w[0]; g.w1 = (const bf16_t*)L.w[1]; g.w2 = (const bf16_t*)L.w[2]; g.n0 = n0; g.n1 = n1;
-    g.out = base; g.ldo = n_total;
-    MI_TRY(hip_rc(launch_gemm(g, s), "lora base gemm"));
-  }
-  bool any = false;
-  for (int i = 0; i < L.nseg; ++i) any = any || (L.A[i] && L.B[i]);
-  if (any) {
-    LoraDownArgs d;
-    memset(&d, 0, sizeof(d));
-    d.x = (const bf16_t*)xn; d.ldx = ldxn; d.T = M; d.K = K; d.nseg = L.nseg; d.r = rank; d.t = t;
-    d.a_stride = (int64_t)rank * K; d.bank = L.bank;
-    for (int i = 0; i < L.nseg; ++i) d.A[i] = (L.A[i] && L.B[i]) ? (const bf16_t*)L.A[i] : nullptr;
-    MI_TRY(hip_rc(launch_lora_down(d, s), "lora_down"));
-  }
-  LoraUpArgs u;
-  memset(&u, 0, sizeof(u));
-  u.epi = L.epilogue; u.T = M; u.N = swiglu ? n0 : n_total; u.base = base; u.ldb = n_total; u.base_f32 = base_f32 ? 1 : 0;
-  u.t = t; u.n0 = n0; u.n1 = n1; u.nseg = L.nseg; u.r = rank; u.scaling = scaling;
-  u.bank = L.bank;
-  for (int i = 0; i < L.nseg; ++i) u.b_stride[i] = (int64_t)L.n_rows[i] * rank;
-  for (int i = 0; i < L.nseg; ++i) u.B[i] = (L.A[i] && L.B[i]) ? (const bf16_t*)L.B[i] : nullptr;
-  u.out = (bf16_t*)out; u.ldo = ldo; u.residual = (const bf16_t*)residual;
-  u.fast_silu = M > GEMV_MAX_T;  // (the SiLU of the path that a plain linear of this M takes: gemv_core.cuh / gemm.hip)
-  return hip_rc(launch_lora_up(u, s), "lora_up");
-}
+// ---- scratch of the un-merged LoRA leaf (mi_lora_linear; the launches: linear_group below)
 struct LoraScratch {
   void* base;
   bf16_t* t;
@@ -484,14 +423,177 @@ AttnPrefillArgs attn_prefill_args(void* out, const void* qkv, int ld, const void
   return a;
 }
 
-// The ring write of the q|k|v leaves on rings of e4m3 bytes: an e4m3 store in the GEMV epilogue would change every GEMV kernel, so
-// the GEMV runs without its fused write and the k | v columns of its output go through the e4m3 ring-write kernel - every row to
-// slot tok_pos % W of sequence tok_seq (nullptr: the row index), as the fused write does (q_start == nullptr: no window drop).
-int qkv_ring_write_e4m3(const RingWrite& ring, const void* qkv, int ldo, int T, int n_heads, int n_kv_heads, int head_dim,
-                        const int32_t* tok_pos, const int32_t* tok_seq, hipStream_t s) {
-  const bf16_t* k = (const bf16_t*)qkv + (size_t)n_heads * head_dim;
-  return hip_rc(launch_kv_write(ring.k, ring.v, ring.W, k, k + (size_t)n_kv_heads * head_dim, ldo, T, n_kv_heads * head_dim, tok_seq, tok_pos,
-                                nullptr, ring.layout, head_dim, s), "kv_write (e4m3)");
+// The ring write as a launch of its own: the k | v columns of qkv [T, ldo] (behind nq columns of q) go to slot tok_pos % W of
+// sequence tok_seq (nullptr: the row index) - of bf16 rings or, by the layout, of e4m3 rings.  q_start == nullptr: no window drop.
+int ring_write(const RingWrite& ring, const void* qkv, int ldo, int T, int nq, int nkv, int head_dim, const int32_t* tok_pos,
+               const int32_t* tok_seq, const int32_t* q_start, hipStream_t s, const char* what) {
+  const bf16_t* k = (const bf16_t*)qkv + nq;
+  return hip_rc(launch_kv_write(ring.k, ring.v, ring.W, k, k + nkv, ldo, T, nkv, tok_seq, tok_pos, q_start, ring.layout, head_dim, s), what);
+}
+
+// ---- One linear group: up to three weight matrices of K columns read side by side (q|k|v, wo, w1|w3, w2, the LM head) in one
+// weight format, with or without un-merged LoRA adapters (lora.py:71-74).  Every linear of the leaves and of forward_body is this
+// description, a LinearCall and linear_group(): the one place that picks and sequences the launches.
+struct LinearGroup {
+  const void* w[3];     // weight segments (SwiGLU: W1, W3); nullptr: no such segment
+  int n_rows[3];
+  int nseg, K;
+  int format;           // 0: bf16; MI_W8_FP8_E4M3 / MI_W4_MXFP4: w[] are quantised bytes with the scales of that format's type
+  Scales<float> s8;
+  Scales<uint8_t> s4;
+  // adapters (rank > 0): A[i] [rank, K] and B[i] [n_rows[i], rank] per segment, or both nullptr.  bank.seq_slot != nullptr (ABI v9):
+  // A[i] / B[i] are the bases of [slots, rank, K] / [slots, n_rows[i], rank] arrays and row m runs through slot
+  // seq_slot[tok_seq[m]] (kernels.h); all zero: one adapter set, the kernels' single-adapter mode
+  const void *A[3], *B[3];
+  int rank;
+  float scaling;
+  LoraBank bank;
+};
+LinearGroup group_of(int K, const void* w0, int r0, const void* w1 = nullptr, int r1 = 0, const void* w2 = nullptr, int r2 = 0) {
+  LinearGroup g;
+  memset(&g, 0, sizeof(g));
+  g.w[0] = w0; g.w[1] = w1; g.w[2] = w2; g.n_rows[0] = r0; g.n_rows[1] = r1; g.n_rows[2] = r2;
+  g.nseg = !w0 ? 0 : !w1 ? 1 : !w2 ? 2 : 3;
+  g.K = K;
+  return g;
+}
+inline void set_scales(LinearGroup& g, QuantW8, const float* s0, const float* s1 = nullptr, const float* s2 = nullptr) {
+  g.format = QuantW8::kFormat; g.s8 = {{s0, s1, s2}};
+}
+inline void set_scales(LinearGroup& g, QuantW4, const uint8_t* s0, const uint8_t* s1 = nullptr, const uint8_t* s2 = nullptr) {
+  g.format = QuantW4::kFormat; g.s4 = {{s0, s1, s2}};
+}
+inline const Scales<float>& scales_of(const LinearGroup& g, QuantW8) { return g.s8; }
+inline const Scales<uint8_t>& scales_of(const LinearGroup& g, QuantW4) { return g.s4; }
+inline void set_adapters(LinearGroup& g, int rank, float scaling, const LoraBank& bank, const void* a0, const void* b0,
+                         const void* a1 = nullptr, const void* b1 = nullptr, const void* a2 = nullptr, const void* b2 = nullptr) {
+  g.rank = rank; g.scaling = scaling; g.bank = bank; g.A[0] = a0; g.A[1] = a1; g.A[2] = a2; g.B[0] = b0; g.B[1] = b1; g.B[2] = b2;
+}
+
+constexpr int EPI_QKV_ROPE = 100;  // beside the public MI_EPI_* codes: the fused q|k|v + RoPE (+ ring write)
+struct LinearLabels {  // the `what` of each launch (error details name it); nullptr: the caller cannot reach that launch
+  const char *gemv, *gemm, *dequant, *norm;
+  // the separate ring write behind a GEMV that could not fuse it (e4m3 rings) / behind the GEMM or LoRA route: two labels because
+  // forward_body's error details have always told the two apart ("kv_write (decode, e4m3)" / "kv_write (decode)")
+  const char *ring_gemv, *ring;
+};
+struct LinearCall {
+  const void* x;         // [M, ldx]; pre-norm when norm_w is given
+  int ldx;
+  const void* norm_w;    // fused RMSNorm (eps) in front of the product, or nullptr
+  float eps;
+  void* out;             // [M, ldo] bf16 (fp32: EPI_LOGITS)
+  int ldo;
+  const void* residual;
+  int epi;               // MI_EPI_* (the leaves pass validated codes only) or EPI_QKV_ROPE
+  // EPI_QKV_ROPE: the segments are wq | wk | wv over heads of head_dim.  ring != nullptr: the k | v columns also go to the ring
+  // (a separate launch reads ring_q_start: nullptr, no window drop)
+  const float* rope_cs;
+  const int32_t *tok_pos, *tok_seq;
+  int head_dim;
+  const RingWrite* ring;
+  const int32_t* ring_q_start;
+  // scratch of the routes; nullptr: the route is not open to this caller
+  bf16_t* xn;            // [M, K]: the RMSNorm as a launch of its own (M > 8, and whatever lora_down reads)
+  bf16_t* deq;           // the bf16 image of the group's quantised weights (M > 8)
+  void* lora_base;       // [M, sum of n_rows]: the base product of a group with adapters - bf16, or with lora_base_f32 fp32 holding
+  bf16_t* lora_t;        //     bf16 values (below);  lora_t [M, nseg * rank]: t = bf16(A xn)
+  // the base GEMV (M <= 8) in its LOGITS form: its fused RMSNorm is the one of the fused q|k|v and W1|W3 modes (gemv_core.cuh
+  // kNormMode: same staging, same order of the sum of squares), so that a model whose adapters are zero reproduces the plain model
+  // bit for bit.  forward_body asks for it at q|k|v and W1|W3, the leaf only for a fused-norm SwiGLU (lora_shape)
+  bool lora_base_f32;
+  LinearLabels what;
+};
+
+// M <= GEMV_MAX_T rows: weight-streaming GEMV passes with the RMSNorm, RoPE and (bf16 rings) the ring write fused.  More rows: the
+// RMSNorm into xn, the bf16 image of quantised weights into deq, then the MFMA GEMM (RoPE in its epilogue when it takes the heads).
+// Adapters: the RMSNorm into xn at any M (lora_down reads it), the base product by the same two routes in plain store form,
+// lora_down, lora_up with the epilogue, then RoPE and the ring write as passes of their own (bit-equal to the fused epilogues:
+// same arithmetic on the same bf16 values).
+int linear_group(const LinearGroup& G, const LinearCall& C, int M, hipStream_t s) {
+  const bool gemv = M <= GEMV_MAX_T, swiglu = C.epi == MI_EPI_SWIGLU, qkv = C.epi == EPI_QKV_ROPE;
+  const int K = G.K, n0 = G.n_rows[0], n1 = n0 + (G.w[1] ? G.n_rows[1] : 0), n2 = n1 + (G.w[2] ? G.n_rows[2] : 0);
+  const bool fused_ring = C.ring && gemv && G.rank == 0 && !kv_e4m3(C.ring->layout);  // (the GEMV epilogue stores bf16 only)
+  // RoPE rides on the GEMV's epilogue, and on the GEMM's (same arithmetic as rope_kernel on the same bf16-rounded values; it was a
+  // separate 20 us pass over q|k per layer at 4096 tokens) unless the heads are of a size that epilogue does not take
+  const bool fused_rope = qkv && G.rank == 0 && (gemv || (fuse_rope_enabled() && C.head_dim % 16 == 0));
+  if (C.norm_w && !C.xn && (!gemv || G.rank > 0)) return fail(MI_ERR_UNSUPPORTED, "linear group: fused RMSNorm only on the M <= 8 path");
+  if (G.rank > 0) {
+    const void* xn = C.x;
+    int ldxn = C.ldx;
+    if (C.norm_w) {
+      MI_TRY(hip_rc(launch_rmsnorm(C.xn, C.x, C.norm_w, M, K, C.eps, s), C.what.norm));
+      xn = C.xn; ldxn = K;
+    }
+    LinearGroup base = G;
+    base.rank = 0;
+    LinearCall bc = C;
+    bc.epi = C.lora_base_f32 ? MI_EPI_LOGITS : MI_EPI_STORE; bc.out = C.lora_base; bc.ldo = n2; bc.residual = nullptr; bc.ring = nullptr;
+    bc.what.gemv = "lora base gemv"; bc.what.gemm = "lora base gemm";
+    if (!gemv) { bc.x = xn; bc.ldx = ldxn; bc.norm_w = nullptr; }  // (M <= 8: the GEMV fuses the norm on x itself)
+    MI_TRY(linear_group(base, bc, M, s));
+    bool any = false;
+    for (int i = 0; i < G.nseg; ++i) any = any || (G.A[i] && G.B[i]);
+    if (any) {
+      LoraDownArgs d;
+      memset(&d, 0, sizeof(d));
+      d.x = (const bf16_t*)xn; d.ldx = ldxn; d.T = M; d.K = K; d.nseg = G.nseg; d.r = G.rank; d.t = C.lora_t;
+      d.a_stride = (int64_t)G.rank * K; d.bank = G.bank;
+      for (int i = 0; i < G.nseg; ++i) d.A[i] = (G.A[i] && G.B[i]) ? (const bf16_t*)G.A[i] : nullptr;
+      MI_TRY(hip_rc(launch_lora_down(d, s), "lora_down"));
+    }
+    LoraUpArgs u;
+    memset(&u, 0, sizeof(u));
+    u.epi = qkv ? MI_EPI_STORE : C.epi;
+    u.T = M; u.N = swiglu ? n0 : n2; u.base = C.lora_base; u.ldb = n2; u.base_f32 = C.lora_base_f32 ? 1 : 0;
+    u.t = C.lora_t; u.n0 = n0; u.n1 = n1; u.nseg = G.nseg; u.r = G.rank; u.scaling = G.scaling;
+    u.bank = G.bank;
+    for (int i = 0; i < G.nseg; ++i) u.b_stride[i] = (int64_t)G.n_rows[i] * G.rank;
+    for (int i = 0; i < G.nseg; ++i) u.B[i] = (G.A[i] && G.B[i]) ? (const bf16_t*)G.B[i] : nullptr;
+    u.out = (bf16_t*)C.out; u.ldo = C.ldo; u.residual = (const bf16_t*)C.residual;
+    u.fast_silu = !gemv;  // (the SiLU of the path that a plain linear of this M takes: gemv_core.cuh / gemm.hip)
+    MI_TRY(hip_rc(launch_lora_up(u, s), "lora_up"));
+  } else if (gemv) {
+    GemvArgs a = gemv_common(C.x, C.ldx, K, swiglu ? n0 : n2, C.norm_w, C.eps, C.out, C.ldo);
+    a.mode = swiglu ? GEMV_SWIGLU : qkv ? GEMV_QKV_ROPE : C.epi == MI_EPI_STORE ? GEMV_STORE : C.epi == MI_EPI_RESIDUAL ? GEMV_RESIDUAL : GEMV_LOGITS;
+    a.w0 = (const bf16_t*)G.w[0]; a.w1 = (const bf16_t*)G.w[1]; a.w2 = (const bf16_t*)G.w[2]; a.n0 = n0; a.n1 = swiglu ? n0 : n1;
+    a.residual = (const bf16_t*)C.residual;
+    if (qkv) { a.rope_cs = C.rope_cs; a.tok_pos = C.tok_pos; a.tok_seq = C.tok_seq; a.head_dim = C.head_dim; }
+    // (without a fused write the four ring fields stay 0: the kernel reads them only under write_kv, so there is no pos % 0)
+    if (fused_ring) { a.write_kv = 1; a.cache_k = C.ring->k; a.cache_v = C.ring->v; a.W = C.ring->W; a.kv_layout = C.ring->layout; }
+    if (G.format)
+      MI_TRY(with_format(G.format, [&](auto Q) { return gemv_passes_quant<decltype(Q)>(a, scales_of(G, Q), M, s, C.what.gemv); }));
+    else
+      MI_TRY(gemv_passes(kGemvBf16, a, M, s, C.what.gemv));
+  } else {
+    const bf16_t* x = (const bf16_t*)C.x;
+    int ldx = C.ldx;
+    if (C.norm_w) {
+      MI_TRY(hip_rc(launch_rmsnorm(C.xn, C.x, C.norm_w, M, K, C.eps, s), C.what.norm));
+      x = C.xn; ldx = K;
+    }
+    const void* w[3] = {G.w[0], G.w[1], G.w[2]};
+    if (G.format) {
+      if (!C.deq) return fail(MI_ERR_WORKSPACE, "linear group: no scratch for the dequantised weights");
+      const int nr[3] = {n0, n1 - n0, n2 - n1};
+      MI_TRY(with_format(G.format, [&](auto Q) { return dequant_group<decltype(Q)>(w, scales_of(G, Q), nr, K, C.deq, s, C.what.dequant); }));
+    }
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.epi = swiglu ? GEMM_SWIGLU : (C.epi == MI_EPI_STORE || qkv) ? GEMM_STORE : C.epi == MI_EPI_RESIDUAL ? GEMM_RESIDUAL : GEMM_LOGITS;
+    g.M = M; g.N = swiglu ? n0 : n2; g.K = K; g.a = x; g.lda = ldx;
+    g.w0 = (const bf16_t*)w[0]; g.w1 = (const bf16_t*)w[1]; g.w2 = (const bf16_t*)w[2]; g.n0 = n0; g.n1 = swiglu ? n0 : n1;
+    g.out = C.out; g.ldo = C.ldo; g.residual = (const bf16_t*)C.residual;
+    if (fused_rope) { g.rope_cs = C.rope_cs; g.tok_pos = C.tok_pos; g.rope_cols = n1; g.rope_dh = C.head_dim; }
+    MI_TRY(hip_rc(launch_gemm(g, s), C.what.gemm));
+  }
+  if (qkv && !fused_rope)
+    MI_TRY(hip_rc(launch_rope(C.out, C.ldo, M, n0 / C.head_dim, (n1 - n0) / C.head_dim, C.head_dim, C.rope_cs, C.tok_pos, s), "rope"));
+  // the ring write must precede the attention (cache.py:83-92 `update` then read, transformer_layers.py:77-81)
+  if (C.ring && !fused_ring)
+    MI_TRY(ring_write(*C.ring, C.out, C.ldo, M, n0, n1 - n0, C.head_dim, C.tok_pos, C.tok_seq, C.ring_q_start, s,
+                      (gemv && G.rank == 0) ? C.what.ring_gemv : C.what.ring));
+  return MI_OK;
 }
 
 // ---- what mi_forward and mi_forward_generic check of a batch, in the order the checks fire
@@ -566,6 +668,35 @@ int check_model(const mi_model_t* m) {
 
 }  // namespace
 
+// mi_qkv_rope_kvwrite and its _w8 / _w4 forms (PlainBf16: no scales, D a multiple of 8)
+template <class Q>
+static int qkv_rope_kvwrite(void* qkv, int ldo, const void* x, int ldx, int T, int D, const void* wq, const void* wk, const void* wv,
+                            const typename Q::scale_t* sq, const typename Q::scale_t* sk, const typename Q::scale_t* sv, int n_heads,
+                            int n_kv_heads, int head_dim, const void* norm_w, float eps, const float* rope_cs, int rope_len,
+                            const int32_t* tok_pos, const int32_t* tok_seq, void* cache_k, void* cache_v, int W, int kv_layout,
+                            mi_stream_t stream) {
+  const char* me = Q::kQkv;
+  constexpr bool quant = Q::kFormat != 0;
+  if (!qkv || !x || !wq || !wk || !wv || (quant ? (!sq || !sk || !sv) : D % 8 != 0) || !rope_cs || !tok_pos || T <= 0 || D <= 0 ||
+      rope_len <= 0 || !kv_layout_ok(kv_layout))
+    return fail(MI_ERR_ARG, "%s", me);
+  if constexpr (quant)
+    if (D % Q::kMod) return fail(MI_ERR_SHAPE, "%s: D = %d must be a multiple of %d (%s)", me, D, Q::kMod, Q::kWhy);
+  if (head_dim != 128) return fail(MI_ERR_SHAPE, "head_dim must be 128");
+  if ((cache_k == nullptr) != (cache_v == nullptr) || (cache_k && W <= 0)) return fail(MI_ERR_ARG, "%s: cache", me);
+  if (T > GEMV_MAX_T)
+    return fail(MI_ERR_UNSUPPORTED, "%s: T = %d > %d (the prefill path is mi_rmsnorm + %s + mi_rope_inplace + mi_kv_write)", me, T, GEMV_MAX_T,
+                Q::kLinear);
+  // rings of e4m3 bytes: an e4m3 store in the GEMV epilogue would change every GEMV kernel, so the GEMV runs without its fused write
+  // and the k | v columns of its output go through the e4m3 ring-write kernel - every row to the slot the fused write picks
+  const RingWrite ring = {cache_k, cache_v, W, kv_layout};
+  LinearGroup g = group_of(D, wq, n_heads * head_dim, wk, n_kv_heads * head_dim, wv, n_kv_heads * head_dim);
+  if constexpr (quant) set_scales(g, Q{}, sq, sk, sv);
+  LinearCall c = {x, ldx, norm_w, eps, qkv, ldo, nullptr, EPI_QKV_ROPE, rope_cs, tok_pos, tok_seq, head_dim, cache_k ? &ring : nullptr};
+  c.what = {Q::kQkvGemv, nullptr, nullptr, nullptr, "kv_write (e4m3)"};
+  return linear_group(g, c, T, (hipStream_t)stream);
+}
+
 extern "C" {
 
 int mi_abi_version(void) { return MI_ABI_VERSION; }
@@ -624,34 +755,13 @@ int mi_linear(void* out, int ldo, const void* x, int ldx, int M, int K, const vo
   if (!out || !x || !w || !n_rows || !w[0] || M <= 0 || K <= 0 || K % 8) return fail(MI_ERR_ARG, "mi_linear");
   if (epilogue == MI_EPI_RESIDUAL && !residual) return fail(MI_ERR_ARG, "mi_linear: residual epilogue without residual");
   if (epilogue == MI_EPI_SWIGLU && (!w[1] || n_rows[0] != n_rows[1])) return fail(MI_ERR_ARG, "mi_linear: swiglu needs W1, W3");
-  hipStream_t s = (hipStream_t)stream;
-  const int n0 = n_rows[0], n1 = n0 + (w[1] ? n_rows[1] : 0), n2 = n1 + (w[2] ? n_rows[2] : 0);
-  if (M <= GEMV_MAX_T) {
-    GemvArgs a = gemv_common(x, ldx, K, 0, norm_w, eps, out, ldo);
-    a.w0 = (const bf16_t*)w[0]; a.w1 = (const bf16_t*)w[1]; a.w2 = (const bf16_t*)w[2]; a.residual = (const bf16_t*)residual;
-    a.mode = epilogue == MI_EPI_SWIGLU   ? GEMV_SWIGLU  // (the one other place that names a mode: the public epilogue codes)
-             : epilogue == MI_EPI_STORE  ? GEMV_STORE
-             : epilogue == MI_EPI_RESIDUAL ? GEMV_RESIDUAL : GEMV_LOGITS;
-    if (epilogue == MI_EPI_SWIGLU) {
-      a.N = n0; a.n0 = a.n1 = n0;
-    } else {
-      a.N = n2; a.n0 = n0; a.n1 = n1;
-    }
-    return gemv_passes(kGemvBf16, a, M, s, "gemv");
-  }
-  if (norm_w) return fail(MI_ERR_UNSUPPORTED, "mi_linear: fused RMSNorm only on the M <= 8 path");
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.M = M; g.K = K; g.a = (const bf16_t*)x; g.lda = ldx;
-  g.w0 = (const bf16_t*)w[0]; g.w1 = (const bf16_t*)w[1]; g.w2 = (const bf16_t*)w[2];
-  g.out = out; g.ldo = ldo; g.residual = (const bf16_t*)residual;
-  if (epilogue == MI_EPI_SWIGLU) {
-    g.epi = GEMM_SWIGLU; g.N = n0; g.n0 = g.n1 = n0;
-  } else {
-    g.epi = epilogue == MI_EPI_STORE ? GEMM_STORE : epilogue == MI_EPI_RESIDUAL ? GEMM_RESIDUAL : GEMM_LOGITS;
-    g.N = n2; g.n0 = n0; g.n1 = n1;
-  }
-  return hip_rc(launch_gemm(g, s), "gemm");
+  if (norm_w && M > GEMV_MAX_T) return fail(MI_ERR_UNSUPPORTED, "mi_linear: fused RMSNorm only on the M <= 8 path");
+  const LinearGroup g = group_of(K, w[0], n_rows[0], w[1], n_rows[1], w[2], n_rows[2]);
+  // (any code but the three: LOGITS, as ever - and the internal EPI_QKV_ROPE is out of a caller's reach)
+  const int epi = (epilogue == MI_EPI_STORE || epilogue == MI_EPI_RESIDUAL || epilogue == MI_EPI_SWIGLU) ? epilogue : MI_EPI_LOGITS;
+  LinearCall c = {x, ldx, norm_w, eps, out, ldo, residual, epi};
+  c.what = {"gemv", "gemm"};
+  return linear_group(g, c, M, (hipStream_t)stream);
 }
 
 /* lora.py:71-74 */
@@ -677,26 +787,20 @@ static int lora_linear_leaf(const char* entry, void* out, int ldo, const void* x
   if (!(scaling > 0.f)) return fail(MI_ERR_ARG, "%s: scaling %g must be > 0 (lora.py:19)", entry, (double)scaling);
   if (norm_w && M > GEMV_MAX_T) return fail(MI_ERR_UNSUPPORTED, "%s: fused RMSNorm only on the M <= 8 path", entry);
   const LoraShape sh = lora_shape(n_rows, epilogue, norm_w != nullptr);
-  LoraLinear L;
-  memset(&L, 0, sizeof(L));
-  L.nseg = sh.nseg; L.epilogue = epilogue;
+  LinearGroup g = group_of(K, nullptr, 0);  // filled by hand: each segment is checked before it is taken, and the messages are pinned
+  g.nseg = sh.nseg; g.rank = rank; g.scaling = scaling;
   if (slots < 1) return fail(MI_ERR_ARG, "%s: slots %d", entry, slots);
-  L.bank = lora_bank(slots, nullptr, row_slot);  // (tok_seq == nullptr: row m is its own sequence)
+  g.bank = lora_bank(slots, nullptr, row_slot);  // (tok_seq == nullptr: row m is its own sequence)
   for (int i = 0; i < sh.nseg; ++i) {
     if (!w[i]) return fail(MI_ERR_ARG, "%s: n_rows[%d] without a weight", entry, i);
     if ((A[i] == nullptr) != (B[i] == nullptr)) return fail(MI_ERR_ARG, "%s: adapter %d needs both A and B (or neither)", entry, i);
-    L.w[i] = w[i]; L.A[i] = A[i]; L.B[i] = B[i]; L.n_rows[i] = epilogue == MI_EPI_SWIGLU ? n_rows[0] : n_rows[i];
+    g.w[i] = w[i]; g.A[i] = A[i]; g.B[i] = B[i]; g.n_rows[i] = epilogue == MI_EPI_SWIGLU ? n_rows[0] : n_rows[i];
   }
   const LoraScratch sc = lora_carve(M, K, sh.n_total, sh.nseg, rank, sh.base_f32, norm_w != nullptr, (char*)scratch);
   if (sc.total > scratch_bytes) return fail(MI_ERR_WORKSPACE, "%s: scratch %zu < required %zu", entry, scratch_bytes, sc.total);
-  hipStream_t s = (hipStream_t)stream;
-  const void* xn = x;
-  int ldxn = ldx;
-  if (norm_w) {
-    MI_TRY(hip_rc(launch_rmsnorm(sc.xn, x, norm_w, M, K, eps, s), "lora rmsnorm"));
-    xn = sc.xn; ldxn = K;
-  }
-  return lora_linear(out, ldo, x, ldx, xn, ldxn, M, K, L, residual, norm_w, eps, rank, scaling, sc.base, sh.base_f32, sc.t, s);
+  LinearCall c = {x, ldx, norm_w, eps, out, ldo, residual, epilogue};
+  c.xn = sc.xn; c.lora_base = sc.base; c.lora_t = sc.t; c.lora_base_f32 = sh.base_f32; c.what.norm = "lora rmsnorm";
+  return linear_group(g, c, M, (hipStream_t)stream);
 }
 
 /* lora.py:71-74 */
@@ -856,19 +960,8 @@ int mi_qkv_rope_kvwrite(void* qkv, int ldo, const void* x, int ldx, int T, int D
                         const void* wv, int n_heads, int n_kv_heads, int head_dim, const void* norm_w, float eps,
                         const float* rope_cs, int rope_len, const int32_t* tok_pos, const int32_t* tok_seq, void* cache_k,
                         void* cache_v, int W, int kv_layout, mi_stream_t stream) {
-  if (!qkv || !x || !wq || !wk || !wv || !rope_cs || !tok_pos || T <= 0 || D <= 0 || D % 8 || rope_len <= 0 || !kv_layout_ok(kv_layout))
-    return fail(MI_ERR_ARG, "mi_qkv_rope_kvwrite");
-  if (head_dim != 128) return fail(MI_ERR_SHAPE, "head_dim must be 128");
-  if ((cache_k == nullptr) != (cache_v == nullptr) || (cache_k && W <= 0)) return fail(MI_ERR_ARG, "mi_qkv_rope_kvwrite: cache");
-  if (T > GEMV_MAX_T)
-    return fail(MI_ERR_UNSUPPORTED, "mi_qkv_rope_kvwrite: T = %d > %d (the prefill path is mi_rmsnorm + mi_linear + "
-                "mi_rope_inplace + mi_kv_write)", T, GEMV_MAX_T);
-  const RingWrite ring = {cache_k, cache_v, W, kv_layout};
-  const bool fused_write = cache_k && !kv_e4m3(kv_layout);
-  const GemvArgs a = gemv_qkv_rope(x, ldx, D, norm_w, eps, wq, wk, wv, n_heads * head_dim, n_kv_heads * head_dim, qkv, ldo, rope_cs,
-                                   tok_pos, tok_seq, head_dim, fused_write ? &ring : nullptr);
-  MI_TRY(gemv_passes(kGemvBf16, a, T, (hipStream_t)stream, "qkv gemv"));
-  return (cache_k && !fused_write) ? qkv_ring_write_e4m3(ring, qkv, ldo, T, n_heads, n_kv_heads, head_dim, tok_pos, tok_seq, (hipStream_t)stream) : MI_OK;
+  return qkv_rope_kvwrite<PlainBf16>(qkv, ldo, x, ldx, T, D, wq, wk, wv, nullptr, nullptr, nullptr, n_heads, n_kv_heads, head_dim, norm_w, eps,
+                                     rope_cs, rope_len, tok_pos, tok_seq, cache_k, cache_v, W, kv_layout, stream);
 }
 
 /* weight-only FP8 leaves (include/mistral_hip.h: MI_W8_FP8_E4M3) */
@@ -899,53 +992,18 @@ static int linear_quant(void* out, int ldo, const void* x, int ldx, int M, int K
     return fail(MI_ERR_UNSUPPORTED, "%s: epilogue %d (store, residual and swiglu; the LM head is not quantised)", me, epilogue);
   if (epilogue == MI_EPI_RESIDUAL && !residual) return fail(MI_ERR_ARG, "%s: residual epilogue without residual", me);
   if (epilogue == MI_EPI_SWIGLU && (!w[1] || n_rows[0] != n_rows[1])) return fail(MI_ERR_ARG, "%s: swiglu needs W1, W3", me);
-  hipStream_t s = (hipStream_t)stream;
-  const bool swiglu = epilogue == MI_EPI_SWIGLU;
-  const int n0 = n_rows[0], n1 = n0 + (w[1] ? n_rows[1] : 0), n2 = n1 + ((!swiglu && w[2]) ? n_rows[2] : 0);
-  const Scales<typename Q::scale_t> sc = {{scale[0], w[1] ? scale[1] : nullptr, (!swiglu && w[2]) ? scale[2] : nullptr}};
-  if (M <= GEMV_MAX_T) {
-    GemvArgs a = gemv_common(x, ldx, K, 0, norm_w, eps, out, ldo);
-    a.w0 = (const bf16_t*)w[0]; a.w1 = (const bf16_t*)w[1]; a.w2 = swiglu ? nullptr : (const bf16_t*)w[2]; a.residual = (const bf16_t*)residual;
-    a.mode = swiglu ? GEMV_SWIGLU : epilogue == MI_EPI_STORE ? GEMV_STORE : GEMV_RESIDUAL;
-    if (swiglu) {
-      a.N = n0; a.n0 = a.n1 = n0;
-    } else {
-      a.N = n2; a.n0 = n0; a.n1 = n1;
-    }
-    return gemv_passes_quant<Q>(a, sc, M, s, Q::kGemv);
+  const bool swiglu = epilogue == MI_EPI_SWIGLU;  // (W1 | W3: a third segment is not read)
+  LinearGroup g = group_of(K, w[0], n_rows[0], w[1], w[1] ? n_rows[1] : 0, swiglu ? nullptr : w[2], (!swiglu && w[2]) ? n_rows[2] : 0);
+  set_scales(g, Q{}, scale[0], w[1] ? scale[1] : nullptr, (!swiglu && w[2]) ? scale[2] : nullptr);
+  if (M > GEMV_MAX_T) {
+    if (norm_w) return fail(MI_ERR_UNSUPPORTED, "%s: fused RMSNorm only on the M <= 8 path", me);
+    const size_t need = align_up((size_t)(g.n_rows[0] + g.n_rows[1] + g.n_rows[2]) * K * 2);
+    if (!scratch || scratch_bytes < need) return fail(MI_ERR_WORKSPACE, "%s: scratch %zu < required %zu", me, scratch ? scratch_bytes : (size_t)0, need);
   }
-  if (norm_w) return fail(MI_ERR_UNSUPPORTED, "%s: fused RMSNorm only on the M <= 8 path", me);
-  const size_t need = align_up((size_t)(swiglu ? 2 * n0 : n2) * K * 2);
-  if (!scratch || scratch_bytes < need) return fail(MI_ERR_WORKSPACE, "%s: scratch %zu < required %zu", me, scratch ? scratch_bytes : (size_t)0, need);
-  const void* wd[3] = {w[0], w[1], swiglu ? nullptr : w[2]};
-  const int nr[3] = {n0, n1 - n0, n2 - n1};
-  MI_TRY(dequant_group<Q>(wd, sc, nr, K, (bf16_t*)scratch, s, Q::kDequant));
-  return mi_linear(out, ldo, x, ldx, M, K, wd, n_rows, epilogue, residual, nullptr, 0.f, stream);
-}
-
-// mi_qkv_rope_kvwrite_w8 / mi_qkv_rope_kvwrite_w4
-template <class Q>
-static int qkv_rope_kvwrite_quant(void* qkv, int ldo, const void* x, int ldx, int T, int D, const void* wq, const void* wk, const void* wv,
-                                  const typename Q::scale_t* sq, const typename Q::scale_t* sk, const typename Q::scale_t* sv, int n_heads,
-                                  int n_kv_heads, int head_dim, const void* norm_w, float eps, const float* rope_cs, int rope_len,
-                                  const int32_t* tok_pos, const int32_t* tok_seq, void* cache_k, void* cache_v, int W, int kv_layout,
-                                  mi_stream_t stream) {
-  const char* me = Q::kQkv;
-  if (!qkv || !x || !wq || !wk || !wv || !sq || !sk || !sv || !rope_cs || !tok_pos || T <= 0 || D <= 0 || rope_len <= 0 ||
-      !kv_layout_ok(kv_layout))
-    return fail(MI_ERR_ARG, "%s", me);
-  if (D % Q::kMod) return fail(MI_ERR_SHAPE, "%s: D = %d must be a multiple of %d (%s)", me, D, Q::kMod, Q::kWhy);
-  if (head_dim != 128) return fail(MI_ERR_SHAPE, "head_dim must be 128");
-  if ((cache_k == nullptr) != (cache_v == nullptr) || (cache_k && W <= 0)) return fail(MI_ERR_ARG, "%s: cache", me);
-  if (T > GEMV_MAX_T)
-    return fail(MI_ERR_UNSUPPORTED, "%s: T = %d > %d (the prefill path is mi_rmsnorm + %s + mi_rope_inplace + mi_kv_write)", me, T, GEMV_MAX_T,
-                Q::kLinear);
-  const RingWrite ring = {cache_k, cache_v, W, kv_layout};
-  const bool fused_write = cache_k && !kv_e4m3(kv_layout);
-  const GemvArgs a = gemv_qkv_rope(x, ldx, D, norm_w, eps, wq, wk, wv, n_heads * head_dim, n_kv_heads * head_dim, qkv, ldo, rope_cs,
-                                   tok_pos, tok_seq, head_dim, fused_write ? &ring : nullptr);
-  MI_TRY(gemv_passes_quant<Q>(a, Scales<typename Q::scale_t>{{sq, sk, sv}}, T, (hipStream_t)stream, Q::kQkvGemv));
-  return (cache_k && !fused_write) ? qkv_ring_write_e4m3(ring, qkv, ldo, T, n_heads, n_kv_heads, head_dim, tok_pos, tok_seq, (hipStream_t)stream) : MI_OK;
+  LinearCall c = {x, ldx, norm_w, eps, out, ldo, residual, epilogue};
+  c.deq = (bf16_t*)scratch;
+  c.what = {Q::kGemv, "gemm", Q::kDequant};
+  return linear_group(g, c, M, (hipStream_t)stream);
 }
 
 extern "C" {
@@ -961,8 +1019,8 @@ int mi_qkv_rope_kvwrite_w8(void* qkv, int ldo, const void* x, int ldx, int T, in
                            int head_dim, const void* norm_w, float eps, const float* rope_cs, int rope_len,
                            const int32_t* tok_pos, const int32_t* tok_seq, void* cache_k, void* cache_v, int W, int kv_layout,
                            mi_stream_t stream) {
-  return qkv_rope_kvwrite_quant<QuantW8>(qkv, ldo, x, ldx, T, D, wq, wk, wv, sq, sk, sv, n_heads, n_kv_heads, head_dim, norm_w, eps, rope_cs,
-                                         rope_len, tok_pos, tok_seq, cache_k, cache_v, W, kv_layout, stream);
+  return qkv_rope_kvwrite<QuantW8>(qkv, ldo, x, ldx, T, D, wq, wk, wv, sq, sk, sv, n_heads, n_kv_heads, head_dim, norm_w, eps, rope_cs,
+                                   rope_len, tok_pos, tok_seq, cache_k, cache_v, W, kv_layout, stream);
 }
 
 /* weight-only MXFP4 leaves (include/mistral_hip.h: MI_W4_MXFP4) */
@@ -979,8 +1037,8 @@ int mi_qkv_rope_kvwrite_w4(void* qkv, int ldo, const void* x, int ldx, int T, in
                            int head_dim, const void* norm_w, float eps, const float* rope_cs, int rope_len,
                            const int32_t* tok_pos, const int32_t* tok_seq, void* cache_k, void* cache_v, int W, int kv_layout,
                            mi_stream_t stream) {
-  return qkv_rope_kvwrite_quant<QuantW4>(qkv, ldo, x, ldx, T, D, wq, wk, wv, sq, sk, sv, n_heads, n_kv_heads, head_dim, norm_w, eps, rope_cs,
-                                         rope_len, tok_pos, tok_seq, cache_k, cache_v, W, kv_layout, stream);
+  return qkv_rope_kvwrite<QuantW4>(qkv, ldo, x, ldx, T, D, wq, wk, wv, sq, sk, sv, n_heads, n_kv_heads, head_dim, norm_w, eps, rope_cs,
+                                   rope_len, tok_pos, tok_seq, cache_k, cache_v, W, kv_layout, stream);
 }
 
 int mi_moe_experts_decode(void* out, const void* residual, const void* x, int ldx, int T, int D, int F,
@@ -1213,89 +1271,52 @@ static int forward_body(const char* entry, const mi_model_t* m, const QuantModel
       MI_TRY(hip_rc(launch_embedding(h, m->tok_embeddings, bt->input_ids, T, D, m->vocab_size, engine_ctrl + CTRL_BAD_ID, s), "embedding"));
   }
 
+  // what every linear group of the step shares: the scratch of its routes, and (un-merged LoRA, ABI v8 / v9) the adapter bank -
+  // the pointers of a layer's adapters are bank bases and bt->seq_adapter picks a slot per sequence; without it every row runs
+  // through slot 0 in the kernels' single-adapter mode
+  LinearCall call;
+  memset(&call, 0, sizeof(call));
+  call.xn = ws.xn; call.deq = ws.deq; call.lora_base = ws.lora_base; call.lora_t = ws.lora_t;
+  const LoraBank bank = lora_bank(m->lora_slots, bt->tok_seq, bt->seq_adapter);
+  static const mi_lora_layer_t kNoAdapters = {};
+
   for (int l = 0; l < m->n_layers; ++l) {
     const mi_layer_t& L = m->layers[l];
     const int W = has_cache ? bt->cache_sizes[l] : 1;
     void* ck = has_cache ? bt->cache_k[l] : nullptr;
     void* cv = has_cache ? bt->cache_v[l] : nullptr;
-    auto kv_write = [&](const char* what) {
-      return hip_rc(launch_kv_write(ck, cv, W, ws.qkv + nq, ws.qkv + nq + nkv, qkv_cols, T, nkv, bt->tok_seq, bt->tok_pos, bt->q_start,
-                                    kvl, Dh, s), what);
-    };
+    const RingWrite ring = {ck, cv, W, kvl};
 
-    // ---- un-merged LoRA (ABI v8): every linear is [base product] [lora_down] [lora_up] (lora_linear above); RoPE and the ring
-    // write are the separate passes (bit-equal to the fused epilogues: same arithmetic on the same bf16 values)
-    // ---- weight-only formats: `run` sends a GEMV to the format's kernels with the scales of the (up to three) linears it names;
-    // `deq` (T > 8) writes the bf16 image of a linear group into the scratch and points w[] at it for the GEMM that follows.
-    // Without q both pass through.  qs: the layer's seven scale pointers, read through the format's own layer struct.
-    const void* qs[7] = {};
+    // ---- the layer's four linear groups: weights, then the scales of a quantised model or the adapters of an un-merged LoRA
+    LinearGroup qkv = group_of(D, L.wq, nq, L.wk, nkv, L.wv, nkv), wo = group_of(nq, L.wo, D), w13 = group_of(D, L.w1, F, L.w3, F),
+                w2 = group_of(F, L.w2, D);
     if (q) {
       MI_TRY(with_format(q->entry_format, [&](auto Q) {
         const auto& S = layers_of(*q, Q)[l];
         if (!(S.wq && S.wk && S.wv && S.wo && S.w1 && S.w2 && S.w3))
           return fail(MI_ERR_ARG, "%s: layer %d has a linear without %s", entry, l, decltype(Q)::kScales);
-        const void* const all[7] = {S.wq, S.wk, S.wv, S.wo, S.w1, S.w2, S.w3};
-        memcpy(qs, all, sizeof(qs));
+        set_scales(qkv, Q, S.wq, S.wk, S.wv); set_scales(wo, Q, S.wo); set_scales(w13, Q, S.w1, S.w3); set_scales(w2, Q, S.w2);
         return (int)MI_OK;
       }));
     }
-    auto scales = [&](auto Q, const Lins& n) {
-      typedef const typename decltype(Q)::scale_t* ptr;  // (what qs[] held before it became void*)
-      return Scales<typename decltype(Q)::scale_t>{{n.i[0] < 0 ? nullptr : static_cast<ptr>(qs[n.i[0]]), n.i[1] < 0 ? nullptr : static_cast<ptr>(qs[n.i[1]]),
-                                                    n.i[2] < 0 ? nullptr : static_cast<ptr>(qs[n.i[2]])}};
-    };
-    auto run = [&](const GemvArgs& ga, const Lins& n, const char* what) {
-      if (!q) return gemv_passes(kGemvBf16, ga, T, s, what);
-      return with_format(q->entry_format, [&](auto Q) { return gemv_passes_quant<decltype(Q)>(ga, scales(Q, n), T, s, what); });
-    };
-    auto deq = [&](const void* (&w)[3], const Lins& n, int r0, int r1, int r2, int K, const char* what) {
-      if (!q) return (int)MI_OK;
-      const int nr[3] = {r0, r1, r2};
-      return with_format(q->entry_format, [&](auto Q) { return dequant_group<decltype(Q)>(w, scales(Q, n), nr, K, ws.deq, s, what); });
-    };
-    static const mi_lora_layer_t kNoAdapters = {};
-    const mi_lora_layer_t& A = (lora && L.lora) ? *L.lora : kNoAdapters;
-    const float ls = m->lora_scaling;
-    // adapter banks (ABI v9): the pointers of `A` are bank bases and bt->seq_adapter picks a slot per sequence; without it
-    // every row runs through slot 0 in the kernels' single-adapter mode
-    auto banked = [&](LoraLinear ll) {
-      ll.bank = lora_bank(m->lora_slots, bt->tok_seq, bt->seq_adapter);
-      return ll;
-    };
     if (lora) {
       if (!L.w1 || !L.w2 || !L.w3) return fail(MI_ERR_ARG, "mi_forward: dense layer without w1/w2/w3");
-      MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, L.attention_norm, T, D, m->norm_eps, s), "attention_norm"));
-      const LoraLinear qkv = banked({{L.wq, L.wk, L.wv}, {A.wq_a, A.wk_a, A.wv_a}, {A.wq_b, A.wk_b, A.wv_b}, {nq, nkv, nkv}, 3, MI_EPI_STORE});
-      MI_TRY(lora_linear(ws.qkv, qkv_cols, gemv ? (const void*)h : ws.xn, D, ws.xn, D, T, D, qkv, nullptr, gemv ? L.attention_norm : nullptr,
-                         m->norm_eps, m->lora_rank, ls, ws.lora_base, gemv, ws.lora_t, s));
-      MI_TRY(hip_rc(launch_rope(ws.qkv, qkv_cols, T, H, Hkv, Dh, m->rope_cs, bt->tok_pos, s), "rope"));
-      if (branch == MI_BRANCH_DECODE) MI_TRY(kv_write("kv_write (decode)"));
-    } else if (gemv) {
-      const RingWrite ring = {ck, cv, W, kvl};
-      MI_TRY(run(gemv_qkv_rope(h, D, D, L.attention_norm, m->norm_eps, L.wq, L.wk, L.wv, nq, nkv, ws.qkv, qkv_cols, m->rope_cs, bt->tok_pos,
-                               bt->tok_seq, Dh, (branch == MI_BRANCH_DECODE && !kv8) ? &ring : nullptr),
-                 Lins{{LIN_WQ, LIN_WK, LIN_WV}}, "qkv gemv"));
-      // e4m3 rings: the GEMV epilogue stores bf16 only - the step's rows go through the ring-write kernel (one launch more per layer)
-      if (branch == MI_BRANCH_DECODE && kv8) MI_TRY(kv_write("kv_write (decode, e4m3)"));
-    } else {
-      MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, L.attention_norm, T, D, m->norm_eps, s), "attention_norm"));
-      const void* wqkv[3] = {L.wq, L.wk, L.wv};
-      MI_TRY(deq(wqkv, Lins{{LIN_WQ, LIN_WK, LIN_WV}}, nq, nkv, nkv, D, "dequant q|k|v"));
-      GemmArgs g;
-      memset(&g, 0, sizeof(g));
-      g.epi = GEMM_STORE; g.M = T; g.N = qkv_cols; g.K = D; g.a = ws.xn; g.lda = D;
-      g.w0 = (const bf16_t*)wqkv[0]; g.w1 = (const bf16_t*)wqkv[1]; g.w2 = (const bf16_t*)wqkv[2]; g.n0 = nq; g.n1 = nq + nkv;
-      g.out = ws.qkv; g.ldo = qkv_cols;
-      // RoPE rides on the GEMM's epilogue (same arithmetic as rope_kernel on the same bf16-rounded values; it was a
-      // separate 20 us pass over q|k per layer at 4096 tokens).  Heads of a size the epilogues do not take: separate pass.
-      const bool fused_rope = fuse_rope_enabled() && Dh % 16 == 0;
-      if (fused_rope) { g.rope_cs = m->rope_cs; g.tok_pos = bt->tok_pos; g.rope_cols = nq + nkv; g.rope_dh = Dh; }
-      MI_TRY(hip_rc(launch_gemm(g, s), "qkv gemm"));
-      if (!fused_rope) MI_TRY(hip_rc(launch_rope(ws.qkv, qkv_cols, T, H, Hkv, Dh, m->rope_cs, bt->tok_pos, s), "rope"));
-      // decode branch with more than 8 sequences: the ring write that the GEMV epilogue does otherwise; it must
-      // precede the attention (cache.py:83-92 `update` then read, transformer_layers.py:77-81)
-      if (branch == MI_BRANCH_DECODE) MI_TRY(kv_write("kv_write (decode)"));
+      const mi_lora_layer_t& A = L.lora ? *L.lora : kNoAdapters;
+      const int r = m->lora_rank;
+      const float ls = m->lora_scaling;
+      set_adapters(qkv, r, ls, bank, A.wq_a, A.wq_b, A.wk_a, A.wk_b, A.wv_a, A.wv_b); set_adapters(wo, r, ls, bank, A.wo_a, A.wo_b);
+      set_adapters(w13, r, ls, bank, A.w1_a, A.w1_b, A.w3_a, A.w3_b); set_adapters(w2, r, ls, bank, A.w2_a, A.w2_b);
     }
+
+    // ---- qkv = rope(attention_norm(h) @ [Wq; Wk; Wv]^T); on the DECODE branch the k | v rows also enter the ring here (bf16
+    // rings at T <= 8: in the GEMV's epilogue; else one launch more per layer).  A verify step has no ring write at all.
+    LinearCall c = call;
+    c.x = h; c.ldx = D; c.norm_w = L.attention_norm; c.eps = m->norm_eps; c.out = ws.qkv; c.ldo = qkv_cols; c.epi = EPI_QKV_ROPE;
+    c.rope_cs = m->rope_cs; c.tok_pos = bt->tok_pos; c.tok_seq = bt->tok_seq; c.head_dim = Dh;
+    c.ring = branch == MI_BRANCH_DECODE ? &ring : nullptr; c.ring_q_start = bt->q_start;
+    c.lora_base_f32 = gemv;
+    c.what = {"qkv gemv", "qkv gemm", "dequant q|k|v", "attention_norm", "kv_write (decode, e4m3)", "kv_write (decode)"};
+    MI_TRY(linear_group(qkv, c, T, s));
 
     // ---- attention
     if (branch == MI_BRANCH_DECODE) {
@@ -1320,42 +1341,25 @@ static int forward_body(const char* entry, const mi_model_t* m, const QuantModel
       const AttnPrefillArgs a = attn_prefill_args(ws.attn, ws.qkv, qkv_cols, pk, pv, kvl & 1, has_cache ? W : T, B, has_cache ? bt->max_q_len : T,
                                                   H, Hkv, Dh, bt->q_start, bt->kv_before, has_cache ? 1 : 0, 0.f);
       MI_TRY(hip_rc(launch_attn_prefill(a, s), "attn_prefill"));
-      if (has_cache) MI_TRY(kv_write("kv_write"));
+      if (has_cache) MI_TRY(ring_write(ring, ws.qkv, qkv_cols, T, nq, nkv, Dh, bt->tok_pos, bt->tok_seq, bt->q_start, s, "kv_write"));
     }
 
-    // ---- h = h + attn @ Wo^T
-    if (lora) {
-      const LoraLinear wo = banked({{L.wo, nullptr, nullptr}, {A.wo_a, nullptr, nullptr}, {A.wo_b, nullptr, nullptr}, {D, 0, 0}, 1, MI_EPI_RESIDUAL});
-      MI_TRY(lora_linear(h, D, ws.attn, nq, ws.attn, nq, T, nq, wo, h, nullptr, 0.f, m->lora_rank, ls, ws.xn, false, ws.lora_t, s));
-    } else if (gemv) {
-      MI_TRY(run(gemv_residual(ws.attn, nq, L.wo, h, D), Lins{{LIN_WO, -1, -1}}, "wo gemv"));
-    } else {
-      const void* wo[3] = {L.wo, nullptr, nullptr};
-      MI_TRY(deq(wo, Lins{{LIN_WO, -1, -1}}, D, 0, 0, nq, "dequant wo"));
-      MI_TRY(hip_rc(launch_gemm(gemm_args(GEMM_RESIDUAL, ws.attn, T, nq, wo[0], nullptr, D, h, h), s), "wo gemm"));
-    }
+    // ---- h = h + attn @ Wo^T   (adapters: the base product goes to xn, which nothing holds here)
+    c = call;
+    c.x = ws.attn; c.ldx = nq; c.out = h; c.ldo = D; c.residual = h; c.epi = MI_EPI_RESIDUAL; c.lora_base = ws.xn;
+    c.what = {"wo gemv", "wo gemm", "dequant wo"};
+    MI_TRY(linear_group(wo, c, T, s));
 
     // ---- h = h + FFN(ffn_norm(h))
-    if (lora) {
-      MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, L.ffn_norm, T, D, m->norm_eps, s), "ffn_norm"));
-      const LoraLinear w13 = banked({{L.w1, L.w3, nullptr}, {A.w1_a, A.w3_a, nullptr}, {A.w1_b, A.w3_b, nullptr}, {F, F, 0}, 2, MI_EPI_SWIGLU});
-      MI_TRY(lora_linear(ws.hid, F, gemv ? (const void*)h : ws.xn, D, ws.xn, D, T, D, w13, nullptr, gemv ? L.ffn_norm : nullptr, m->norm_eps,
-                         m->lora_rank, ls, ws.lora_base, gemv, ws.lora_t, s));
-      const LoraLinear w2 = banked({{L.w2, nullptr, nullptr}, {A.w2_a, nullptr, nullptr}, {A.w2_b, nullptr, nullptr}, {D, 0, 0}, 1, MI_EPI_RESIDUAL});
-      MI_TRY(lora_linear(h, D, ws.hid, F, ws.hid, F, T, F, w2, h, nullptr, 0.f, m->lora_rank, ls, ws.xn, false, ws.lora_t, s));
-    } else if (m->num_experts == 0) {
-      if (gemv) {
-        MI_TRY(run(gemv_swiglu(h, D, L.ffn_norm, m->norm_eps, L.w1, L.w3, ws.hid, F), Lins{{LIN_W1, LIN_W3, -1}}, "w13 gemv"));
-        MI_TRY(run(gemv_residual(ws.hid, F, L.w2, h, D), Lins{{LIN_W2, -1, -1}}, "w2 gemv"));
-      } else {
-        MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, L.ffn_norm, T, D, m->norm_eps, s), "ffn_norm"));
-        const void* w13[3] = {L.w1, L.w3, nullptr};
-        MI_TRY(deq(w13, Lins{{LIN_W1, LIN_W3, -1}}, F, F, 0, D, "dequant w1|w3"));
-        MI_TRY(hip_rc(launch_gemm(gemm_args(GEMM_SWIGLU, ws.xn, T, D, w13[0], w13[1], F, ws.hid, nullptr), s), "w13 gemm"));
-        const void* w2[3] = {L.w2, nullptr, nullptr};
-        MI_TRY(deq(w2, Lins{{LIN_W2, -1, -1}}, D, 0, 0, F, "dequant w2"));
-        MI_TRY(hip_rc(launch_gemm(gemm_args(GEMM_RESIDUAL, ws.hid, T, F, w2[0], nullptr, D, h, h), s), "w2 gemm"));
-      }
+    if (m->num_experts == 0) {
+      c = call;
+      c.x = h; c.ldx = D; c.norm_w = L.ffn_norm; c.eps = m->norm_eps; c.out = ws.hid; c.ldo = F; c.epi = MI_EPI_SWIGLU; c.lora_base_f32 = gemv;
+      c.what = {"w13 gemv", "w13 gemm", "dequant w1|w3", "ffn_norm"};
+      MI_TRY(linear_group(w13, c, T, s));
+      c = call;
+      c.x = ws.hid; c.ldx = F; c.out = h; c.ldo = D; c.residual = h; c.epi = MI_EPI_RESIDUAL; c.lora_base = ws.xn;
+      c.what = {"w2 gemv", "w2 gemm", "dequant w2"};
+      MI_TRY(linear_group(w2, c, T, s));
     } else {
       const int E = m->num_experts, k = m->top_k;
       if (!L.gate || !L.expert_w_dev || !L.expert_w_host) return fail(MI_ERR_ARG, "mi_forward: MoE layer tables");
@@ -1375,13 +1379,11 @@ static int forward_body(const char* entry, const mi_model_t* m, const QuantModel
   if (m->final_norm && !bt->logits) {
     MI_TRY(hip_rc(launch_rmsnorm(h, h, m->final_norm, T, D, m->norm_eps, s), "final norm"));
   } else if (m->final_norm) {
-    const int V = m->vocab_size;
-    if (gemv) {
-      MI_TRY(gemv_passes(kGemvBf16, gemv_logits(h, D, m->final_norm, m->norm_eps, m->output, bt->logits, V), T, s, "lm head gemv"));
-    } else {
-      MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, m->final_norm, T, D, m->norm_eps, s), "final norm"));
-      MI_TRY(hip_rc(launch_gemm(gemm_args(GEMM_LOGITS, ws.xn, T, D, m->output, nullptr, V, bt->logits, nullptr), s), "lm head gemm"));
-    }
+    // the LM head is never quantised and carries no adapters
+    LinearCall c = call;
+    c.x = h; c.ldx = D; c.norm_w = m->final_norm; c.eps = m->norm_eps; c.out = bt->logits; c.ldo = m->vocab_size; c.epi = MI_EPI_LOGITS;
+    c.what = {"lm head gemv", "lm head gemm", nullptr, "final norm"};
+    MI_TRY(linear_group(group_of(D, m->output, m->vocab_size), c, T, s));
     if (want_greedy) MI_TRY(sample_step(bt, m, want_topp, engine_ctrl, s));
   }
   if (vo) {
@@ -1408,15 +1410,13 @@ static int forward_body(const char* entry, const mi_model_t* m, const QuantModel
 int mi_forward(const mi_model_t* m, const mi_batch_t* bt, mi_stream_t stream) { return forward_body("mi_forward", m, nullptr, bt, stream); }
 
 int mi_forward_w8(const mi_model_t* m, const mi_w8_model_t* w8, const mi_batch_t* bt, mi_stream_t stream) {
-  if (!w8) return forward_body("mi_forward", m, nullptr, bt, stream);
-  const QuantModel q = {MI_W8_FP8_E4M3, w8->format, w8->layers, nullptr};
-  return forward_body("mi_forward_w8", m, &q, bt, stream);
+  const QuantModel q = quant_model(w8, nullptr);
+  return forward_body(w8 ? "mi_forward_w8" : "mi_forward", m, w8 ? &q : nullptr, bt, stream);
 }
 
 int mi_forward_w4(const mi_model_t* m, const mi_w4_model_t* w4, const mi_batch_t* bt, mi_stream_t stream) {
-  if (!w4) return forward_body("mi_forward", m, nullptr, bt, stream);
-  const QuantModel q = {MI_W4_MXFP4, w4->format, nullptr, w4->layers};
-  return forward_body("mi_forward_w4", m, &q, bt, stream);
+  const QuantModel q = quant_model(nullptr, w4);
+  return forward_body(w4 ? "mi_forward_w4" : "mi_forward", m, w4 ? &q : nullptr, bt, stream);
 }
 
 size_t mi_workspace_bytes_verify(const mi_model_t* model, int quantised, int T, int max_cache_size, int kv_layout) {
@@ -1428,15 +1428,8 @@ int mi_forward_verify(const mi_model_t* m, const mi_w8_model_t* w8, const mi_w4_
                       const mi_verify_out_t* out, mi_stream_t stream) {
   if (!out) return fail(MI_ERR_ARG, "mi_forward_verify: outputs");
   if (w8 && w4) return fail(MI_ERR_ARG, "mi_forward_verify: both w8 and w4 given; a model has at most one weight format");
-  if (w8) {
-    const QuantModel q = {MI_W8_FP8_E4M3, w8->format, w8->layers, nullptr};
-    return forward_body("mi_forward_verify", m, &q, bt, stream, out);
-  }
-  if (w4) {
-    const QuantModel q = {MI_W4_MXFP4, w4->format, nullptr, w4->layers};
-    return forward_body("mi_forward_verify", m, &q, bt, stream, out);
-  }
-  return forward_body("mi_forward_verify", m, nullptr, bt, stream, out);
+  const QuantModel q = quant_model(w8, w4);
+  return forward_body("mi_forward_verify", m, (w8 || w4) ? &q : nullptr, bt, stream, out);
 }
 
 }  // extern "C"

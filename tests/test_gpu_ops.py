@@ -621,3 +621,17 @@ def test_fused_rope_epilogue_bit_equal_to_separate_pass(tmp_path):
     for k in a:
         assert torch.isfinite(a[k]).all(), k
         assert torch.equal(a[k], b[k]), (k, float((a[k] - b[k]).abs().max()))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("T", [4, 12])
+def test_module_level_block_on_bf16_linears_against_the_runner(tmp_path, T):
+    """TransformerBlock.forward on plain bf16 nn.Linear layers (module by module: mi_linear / mi_qkv_rope_kvwrite leaves) against the
+    same layer inside mi_forward - leaf and runner are one routing function (csrc/api.hip linear_group).  The model and the
+    assertions are those of the FP8 / MXFP4 / LoRA block tests: 12 rows take the RMSNorm kernel and the MFMA GEMM on both sides, so
+    the comparison is bit for bit; at 4 rows the runner's GEMV fuses the RMSNorm and sums its squares in another order, which can
+    move a normalised element by one bf16 ulp: at most 2 bf16 ulps at the block output's largest magnitude."""
+    import quant_util as qu
+    from hip_util import write_checkpoint
+    src = write_checkpoint(tmp_path / "bf16", qu.MODEL, mo.synth_weights(qu.MODEL, seed=21))
+    qu.check_module_level_block((None, src), tmp_path, T)
