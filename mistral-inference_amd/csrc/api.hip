@@ -227,6 +227,7 @@ int gemv_pass_loop(int cap, const GemvArgs& a, int T, const char* what, Launch&&
     if (a.residual) p.residual = a.residual + (size_t)t0 * a.ldo;
     if (a.tok_pos) p.tok_pos = a.tok_pos + t0;
     if (a.tok_seq) p.tok_seq = a.tok_seq + t0;
+    else p.seq0 = a.seq0 + t0;  // (no tok_seq: token t is sequence t, in every pass)
     MI_TRY(hip_rc(launch(p), what));
   }
   return MI_OK;

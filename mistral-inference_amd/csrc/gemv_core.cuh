@@ -477,7 +477,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, const typename F::s
   int ep_pos = 0, ep_seq = 0;
   if (MODE == GEMV_QKV_ROPE) {
     ep_pos = a.tok_pos[tl];
-    ep_seq = a.tok_seq ? a.tok_seq[tl] : tl;
+    ep_seq = a.tok_seq ? a.tok_seq[tl] : a.seq0 + tl;
   }
   in_regs = x_issue<TT, NX, NW, DMA, NWV * 64>(xr, x, a.ldx, T, a.K, a.norm_w, xs, ws);
 

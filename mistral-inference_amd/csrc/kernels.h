@@ -44,7 +44,7 @@ struct GemvArgs {
   // QKV_ROPE
   const float* rope_cs; // fp32 [rope_len, head_dim/2, 2]
   const int32_t* tok_pos;
-  const int32_t* tok_seq;  // nullptr: sequence id == token index
+  const int32_t* tok_seq;  // nullptr: sequence id == seq0 + token index
   int head_dim;
   int write_kv;
   void* cache_k;
@@ -56,6 +56,7 @@ struct GemvArgs {
   const int32_t* sel_idx;         // device [T*top_k]
   const float* sel_w;             // device [T*top_k]
   int top_k;
+  int seq0;  // QKV_ROPE without tok_seq: the sequence of this launch's token 0 (the first row of a later pass, gemv_pass_loop)
 };
 
 int gemv_max_tokens(int K);
