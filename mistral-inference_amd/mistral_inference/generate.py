@@ -122,25 +122,83 @@ def generate(
                         for images_for_sample in images]
     flattened_images: List[torch.Tensor] = sum(images_torch, [])
     model = model.eval()
-    B, V = len(encoded_prompts), model.args.vocab_size
-    seqlens = [len(x) for x in encoded_prompts]
-    dev = model.device
 
     # K/V rings, straight in device memory (reference generate.py:67-78)
-    cache_window = max(seqlens) + max_tokens
+    cache_window = max(len(x) for x in encoded_prompts) + max_tokens
     cache = BufferCache(model.n_local_layers, model.args.max_batch_size, cache_window, model.args.n_kv_heads,
-                        model.args.head_dim, model.args.sliding_window, device=dev, dtype=kv_dtype)
+                        model.args.head_dim, model.args.sliding_window, device=model.device, dtype=kv_dtype)
     cache.reset()
 
-    # logprob pieces stay on the device; (sequence, tensor) in emission order
+    last_token_prelogits, lp_chunks = _run_prompt(encoded_prompts, model, cache, chunk_size, flattened_images)
+
+    # ---- decode (reference generate.py:120-140): exactly one decoder runs, or none
+    generated: List[torch.Tensor] = []
+    gen_lp: List[torch.Tensor] = []
+    spec_out: Optional[Tuple[List[int], List[float]]] = None
+    decoder = _pick_decoder(model, model.device.type, temperature, max_tokens, speculative)
+    if decoder == "speculative":
+        spec_out = _decode_speculative(model, cache, last_token_prelogits, max_tokens, temperature, eos_id,
+                                       speculative, encoded_prompts[0])
+    elif decoder == "session":
+        generated, gen_lp = _decode_session(model, cache, last_token_prelogits, max_tokens, temperature, eos_id)
+    elif decoder == "loop":
+        generated, gen_lp = _decode_loop(model, cache, last_token_prelogits, max_tokens, temperature, eos_id)
+
+    result = _copy_back(len(encoded_prompts), lp_chunks, generated, gen_lp, spec_out)
+    _raise_if_flagged(model)
+    return result
+
+
+# ---- which decoder: every read of the model's decode capabilities is here
+def _pp_ranks(model) -> int:
+    return getattr(model, "num_pipeline_ranks", 1)
+
+
+def _pick_decoder(model, device_type: str, temperature: float, max_tokens: int, speculative: Optional[SpeculativeArgs]) -> str:
+    """Which decoder generate() runs: "none", "speculative" (_decode_speculative), "session" (_decode_session) or "loop"
+    (_decode_loop)."""
+    if max_tokens <= 0:
+        return "none"
+    if speculative is not None:
+        return "speculative"
+    if (hasattr(model, "greedy_session")
+            and (device_type == "cuda" or (temperature == 0 and getattr(model, "greedy_session_any_device", False)))  # (CPU stand-ins: tests)
+            and (_pp_ranks(model) == 1 or getattr(model, "greedy_session_pp", False))
+            and getattr(model, "softmax_fp32", True)
+            and getattr(model, "fused_greedy", True)):  # (model.fused_greedy = False: the host loop, for A/B)
+        return "session"
+    return "loop"
+
+
+def _loop_shares_seed(model, temperature: float) -> bool:
+    """_decode_loop under pipeline parallelism at temperature > 0: every stage samples the same broadcast logits and must draw
+    the same variate whatever state its own CPU generator is in - step i uses (the agreed seed, offset i)."""
+    return temperature > 0 and _pp_ranks(model) > 1 and hasattr(model, "pp_comm")
+
+
+def _graph_context(model, cache: BufferCache):
+    """Inside it decode steps replay a captured hipGraph (single rank; no-op otherwise)."""
+    return model.graphed_decode(cache) if hasattr(model, "graphed_decode") else contextlib.nullcontext()
+
+
+def _fused_prompt_logprobs(model) -> bool:
+    """The prompt route: True - `model.prompt_logprobs` reduces the logits to the wanted log-probabilities inside the LM head
+    GEMM; False - `forward` returns the [T, V] logits and generate() takes their log_softmax."""
+    return bool(getattr(model, "supports_prompt_logprobs", False) and getattr(model, "softmax_fp32", True)
+                and (model.device.type == "cuda" or getattr(model, "prompt_logprobs_any_device", False)))
+
+
+# ---- prompt, by chunks (reference generate.py:91-118)
+def _run_prompt(encoded_prompts: List[List[int]], model, cache: BufferCache, chunk_size: Optional[int],
+                images: List[torch.Tensor]) -> Tuple[torch.Tensor, List[Tuple[int, torch.Tensor]]]:
+    """(logits after every prompt's last token [B, V], the prompt's log-prob pieces).  The pieces stay on the device:
+    (sequence, tensor) in emission order."""
+    B, V, dev = len(encoded_prompts), model.args.vocab_size, model.device
     lp_chunks: List[Tuple[int, torch.Tensor]] = []
     last_token_prelogits: Optional[torch.Tensor] = None
-
-    max_prompt_len = max(seqlens)
+    max_prompt_len = max(len(x) for x in encoded_prompts)
     if chunk_size is None:
         chunk_size = max_prompt_len
-
-    # ---- prompt, by chunks (reference generate.py:91-118)
     for s in range(0, max_prompt_len, chunk_size):
         prompt_chunks = [p[s: s + chunk_size] for p in encoded_prompts]
         assert all(len(p) > 0 for p in prompt_chunks)
@@ -157,18 +215,15 @@ def generate(
             cols += seq[1:]
             owners.append((b, n))
             offset += len(seq)
-        fused = (getattr(model, "supports_prompt_logprobs", False) and getattr(model, "softmax_fp32", True)
-                 and (model.device.type == "cuda" or getattr(model, "prompt_logprobs_any_device", False)))
-        if fused:
+        if _fused_prompt_logprobs(model):
             # the [T, V] logits are never materialised: the LM head GEMM reduces them to the wanted log-probabilities
             tgt = torch.full((flat.numel(),), -1, dtype=torch.int32)
             if rows:
                 tgt[rows] = torch.tensor(cols, dtype=torch.int32)
-            lp_rows, last_rows = model.prompt_logprobs(flat, [len(p) for p in prompt_chunks], cache, tgt.to(dev),
-                                                       images=flattened_images)
+            lp_rows, last_rows = model.prompt_logprobs(flat, [len(p) for p in prompt_chunks], cache, tgt.to(dev), images=images)
             picked_rows = lp_rows[torch.tensor(rows, device=dev, dtype=torch.long)] if rows else None
         else:
-            prelogits = model.forward(flat, seqlens=[len(p) for p in prompt_chunks], cache=cache, images=flattened_images)
+            prelogits = model.forward(flat, seqlens=[len(p) for p in prompt_chunks], cache=cache, images=images)
             logits = torch.log_softmax(prelogits, dim=-1)
             picked_rows = None
             if rows:
@@ -179,9 +234,8 @@ def generate(
 
         if last_token_prelogits is not None:
             # first token of this chunk is scored by the previous chunk's last position
-            prev = torch.log_softmax(last_token_prelogits, dim=-1)
             firsts = torch.tensor([p[0] for p in prompt_chunks], device=dev, dtype=torch.long)
-            picked = prev.gather(1, firsts[:, None])[:, 0]
+            picked = _logprob_of(last_token_prelogits, firsts)
             for b in range(B):
                 lp_chunks.append((b, picked[b: b + 1]))
         if picked_rows is not None:
@@ -192,124 +246,142 @@ def generate(
                 o += n
         last_token_prelogits = last_rows
         assert last_token_prelogits.shape == (B, V)
+    assert last_token_prelogits is not None
+    return last_token_prelogits, lp_chunks
 
-    # ---- decode (reference generate.py:120-140)
+
+# ---- the pieces the decoders share
+def _logprob_of(prelogits: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
+    return torch.log_softmax(prelogits, dim=-1).gather(1, tokens[:, None])[:, 0]
+
+
+def _first_token(prelogits: torch.Tensor, temperature: float, seed: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The token after the prompt and its log-prob, [B] each, as a decoder that samples on the device itself draws it: the
+    argmax at temperature 0, else the native nucleus draw at an offset no decode step of the same seed reaches."""
+    if temperature > 0:
+        from . import _hip
+        return _hip.sample_top_p(prelogits.contiguous(), temperature, 0.8, seed=seed, offset=1 << 63)
+    token = sample(prelogits, temperature=0.0, top_p=0.8)
+    return token, _logprob_of(prelogits, token)
+
+
+def _agree_seed(model) -> int:
+    """ONE seed per generation, from torch's default generator (torch.manual_seed makes a generation reproducible).  The
+    reference's pipeline ranks stay in step only because they share torch's default seed (generate.py:126 on every rank); here
+    rank 0's seed is the generation's seed on every stage, agreed over `model.pp_comm` - where the model and its pipeline
+    communicator are known.  `sample()` itself issues no collective: a data-parallel job, or ranks that generate different
+    things, never meet in it (the reference's sample() has none either, generate.py:151-159)."""
+    seed_t = torch.randint(0, 2 ** 62, (1,))
+    if _pp_ranks(model) > 1:
+        seed_t = seed_t.to(model.device)
+        model.pp_comm.broadcast(seed_t, src=0)
+    return int(seed_t.item())
+
+
+# ---- the three decoders: (model, cache, last_token_prelogits, max_tokens > 0, temperature, eos_id, ...)
+def _decode_speculative(model, cache: BufferCache, last_token_prelogits: torch.Tensor, max_tokens: int, temperature: float,
+                        eos_id: Optional[int], speculative: SpeculativeArgs, prompt: List[int]) -> Tuple[List[int], List[float]]:
+    """One prompt, temperature 0: (tokens, logprobs) as host lists.  Token 0 comes from the prompt's last logits as in the
+    plain loop; every later step scores [last emitted token] + drafts and emits the argmaxes of the confirmed rows.  One
+    synchronisation per step (n_accept), which also brings the tokens."""
+    V, dev = model.args.vocab_size, model.device
+    t0, lp0 = _first_token(last_token_prelogits, temperature)
+    toks, lps = [int(t0[0])], [float(lp0[0])]
+    if eos_id is not None and toks[0] == eos_id:
+        return [], []
+    history = list(prompt) + toks
+    done = False
+    while not done and len(toks) < max_tokens:
+        drafts = speculative.draft(history)[: max_tokens - len(toks) - 1]
+        if any(d < 0 or d >= V for d in drafts):
+            raise IndexError("index out of range in self (a drafted token)")
+        ids = torch.tensor([history[-1]] + drafts, device=dev, dtype=torch.long)
+        tok, lp, n_accept = model.verify_step(ids, [len(drafts) + 1], cache)
+        new_t, new_lp = tok[: n_accept[0] + 1].tolist(), lp[: n_accept[0] + 1].tolist()
+        for t, l in zip(new_t, new_lp):
+            if eos_id is not None and t == eos_id:  # generate.py:128-132: the EOS token itself is not returned
+                done = True
+                break
+            if len(toks) == max_tokens:
+                break
+            toks.append(int(t))
+            lps.append(float(l))
+            history.append(int(t))
+    return toks, lps
+
+
+def _decode_session(model, cache: BufferCache, last_token_prelogits: torch.Tensor, max_tokens: int, temperature: float,
+                    eos_id: Optional[int]) -> Tuple[List[torch.Tensor], List[torch.Tensor]]:
+    """The sample rides on the LM head inside the step (GreedySession): argmax + log-softmax at temperature 0, the native
+    nucleus draw (csrc/sampling.hip, generate.py:151-170 in one kernel) otherwise.  It feeds the next step on the device, and
+    the tokens come back in one copy per chunk of steps.  The session is one HIP stage, or pipeline stages with a session
+    each; the sample then crosses from the last stage to the first as 8 bytes per sequence instead of the reference's
+    [B, vocab] logits broadcast.  Temperature 0: the same values as _decode_loop (token i+1 = first argmax of the logits after
+    token i; its logprob = log_softmax at it).  Temperature > 0: the same distribution as _decode_loop, drawn from a Philox
+    stream seeded from torch's default generator (torch.multinomial's own stream cannot be reproduced by any other sampler);
+    only the last stage draws."""
     generated: List[torch.Tensor] = []
     gen_lp: List[torch.Tensor] = []
-    is_finished = torch.zeros(B, dtype=torch.bool, device=dev)
-    assert last_token_prelogits is not None
-    spec_out: Optional[Tuple[List[int], List[float]]] = None
-    if speculative is not None and max_tokens > 0:
-        # token 0 comes from the prompt's last logits as in the plain loop; every later step scores [last emitted token] + drafts
-        # and emits the argmaxes of the confirmed rows.  One synchronisation per step (n_accept), which also brings the tokens.
-        t0 = torch.argmax(last_token_prelogits, dim=-1)
-        lp0 = torch.log_softmax(last_token_prelogits, dim=-1).gather(1, t0[:, None])[:, 0]
-        toks, lps = [int(t0[0])], [float(lp0[0])]
-        history = list(encoded_prompts[0]) + toks
-        done = eos_id is not None and toks[0] == eos_id
-        if done:
-            toks, lps = [], []
-        while not done and len(toks) < max_tokens:
-            drafts = speculative.draft(history)[: max_tokens - len(toks) - 1]
-            if any(d < 0 or d >= V for d in drafts):
-                raise IndexError("index out of range in self (a drafted token)")
-            ids = torch.tensor([history[-1]] + drafts, device=dev, dtype=torch.long)
-            tok, lp, n_accept = model.verify_step(ids, [len(drafts) + 1], cache)
-            new_t, new_lp = tok[: n_accept[0] + 1].tolist(), lp[: n_accept[0] + 1].tolist()
-            for t, l in zip(new_t, new_lp):
-                if eos_id is not None and t == eos_id:  # generate.py:128-132: the EOS token itself is not returned
-                    done = True
-                    break
-                if len(toks) == max_tokens:
-                    break
-                toks.append(int(t))
-                lps.append(float(l))
-                history.append(int(t))
-        spec_out = (toks, lps)
-        max_tokens = 0  # the loops below are done
-    fused_greedy = (max_tokens > 0 and hasattr(model, "greedy_session")
-                    and (dev.type == "cuda" or (temperature == 0 and getattr(model, "greedy_session_any_device", False)))  # (CPU stand-ins: tests)
-                    and (getattr(model, "num_pipeline_ranks", 1) == 1 or getattr(model, "greedy_session_pp", False))
-                    and getattr(model, "softmax_fp32", True)
-                    and getattr(model, "fused_greedy", True))  # (model.fused_greedy = False: the loop below, for A/B)
-    if fused_greedy:
-        # One HIP stage - or pipeline stages, each with its own session; the sample then crosses from the last stage to the
-        # first as 8 bytes per sequence instead of the reference's [B, vocab] logits broadcast (GreedySession) -: the sample
-        # rides on the LM head inside the step (GreedySession) - argmax + log-softmax at temperature
-        # 0, the native nucleus draw (csrc/sampling.hip, generate.py:151-170 in one kernel) otherwise - it feeds the next step
-        # on the device, and the tokens come back in one copy per CHUNK steps.  Temperature 0: same values as the loop below
-        # (token i+1 = first argmax of the logits after token i; its logprob = log_softmax at it).  Temperature > 0: the same
-        # distribution as the loop below, drawn from a Philox stream seeded from torch's default generator (torch.manual_seed
-        # makes a generation reproducible; torch.multinomial's own stream cannot be reproduced by any other sampler).
-        seed = 0
-        if temperature > 0:
-            from . import _hip
-            seed_t = torch.randint(0, 2 ** 62, (1,))
-            if getattr(model, "num_pipeline_ranks", 1) > 1:
-                # the reference's ranks stay in step only because they share torch's default seed (generate.py:126 on every
-                # rank); here only the last stage draws, and rank 0's seed is the generation's seed on every stage
-                seed_t = seed_t.to(dev)
-                model.pp_comm.broadcast(seed_t, src=0)
-            seed = int(seed_t.item())
-            next_token, first_lp = _hip.sample_top_p(last_token_prelogits.contiguous(), temperature, 0.8, seed=seed, offset=1 << 63)
-        else:
-            next_token = sample(last_token_prelogits, temperature=0.0, top_p=0.8)
-            lsm = torch.log_softmax(last_token_prelogits, dim=-1)
-            first_lp = lsm.gather(1, next_token[:, None])[:, 0]
-        if eos_id is not None:
-            is_finished = is_finished | (next_token == eos_id)
-        if not (eos_id is not None and bool(is_finished.all())):
-            generated.append(next_token)
-            gen_lp.append(first_lp)
-            sess = (model.greedy_session(cache, next_token, temperature=temperature, top_p=0.8, seed=seed) if temperature > 0
-                    else model.greedy_session(cache, next_token))
-            need = max_tokens - 1            # (the reference's last forward only feeds a sample nobody draws)
-            chunk = 32 if eos_id is not None else sess.HIST
-            stop = False
-            while need > 0 and not stop:
-                n = min(need, chunk)
-                sess.run(n)
-                toks, lps = sess.collect(n)  # [n, B] each; one synchronisation per chunk
-                keep = n
-                if eos_id is not None:       # generate.py:128-132: stop BEFORE the step at which every sequence has hit EOS
-                    fin = is_finished[None, :] | ((toks == eos_id).cumsum(0) > 0)
-                    all_fin = fin.all(dim=1)
-                    if bool(all_fin.any()):
-                        keep = int(torch.nonzero(all_fin)[0, 0])
-                        stop = True
-                    is_finished = fin[keep - 1] if keep > 0 else is_finished
-                for j in range(keep):
-                    generated.append(toks[j])
-                    gen_lp.append(lps[j])
-                need -= n
-        max_tokens = 0  # the loop below is done
-    # Unfused loop under pipeline parallelism at temperature > 0: every stage samples the same broadcast logits and must draw
-    # the same variate whatever state its own CPU generator is in.  ONE seed per generation, agreed here - where the model and
-    # its pipeline communicator are known - over `model.pp_comm`; step i then uses (seed, offset i).  `sample()` itself issues
-    # no collective: a data-parallel job, or ranks that generate different things, never meet in it (the reference's sample()
-    # has none either, generate.py:151-159).
-    pp_seed: Optional[int] = None
-    if max_tokens > 0 and temperature > 0 and getattr(model, "num_pipeline_ranks", 1) > 1 and hasattr(model, "pp_comm"):
-        seed_t = torch.randint(0, 2 ** 62, (1,)).to(dev)
-        model.pp_comm.broadcast(seed_t, src=0)
-        pp_seed = int(seed_t.item())
-    graphed = model.graphed_decode(cache) if hasattr(model, "graphed_decode") else contextlib.nullcontext()
-    with graphed:  # decode steps replay a captured hipGraph (single rank; no-op otherwise)
+    is_finished = torch.zeros(last_token_prelogits.shape[0], dtype=torch.bool, device=model.device)
+    seed = _agree_seed(model) if temperature > 0 else 0
+    next_token, first_lp = _first_token(last_token_prelogits, temperature, seed)
+    if eos_id is not None:
+        is_finished = is_finished | (next_token == eos_id)
+        if bool(is_finished.all()):
+            return generated, gen_lp
+    generated.append(next_token)
+    gen_lp.append(first_lp)
+    sess = (model.greedy_session(cache, next_token, temperature=temperature, top_p=0.8, seed=seed) if temperature > 0
+            else model.greedy_session(cache, next_token))
+    need = max_tokens - 1            # (the reference's last forward only feeds a sample nobody draws)
+    chunk = 32 if eos_id is not None else sess.HIST
+    stop = False
+    while need > 0 and not stop:
+        n = min(need, chunk)
+        sess.run(n)
+        toks, lps = sess.collect(n)  # [n, B] each; one synchronisation per chunk
+        keep = n
+        if eos_id is not None:       # generate.py:128-132: stop BEFORE the step at which every sequence has hit EOS
+            fin = is_finished[None, :] | ((toks == eos_id).cumsum(0) > 0)
+            all_fin = fin.all(dim=1)
+            if bool(all_fin.any()):
+                keep = int(torch.nonzero(all_fin)[0, 0])
+                stop = True
+            is_finished = fin[keep - 1] if keep > 0 else is_finished
+        for j in range(keep):
+            generated.append(toks[j])
+            gen_lp.append(lps[j])
+        need -= n
+    return generated, gen_lp
+
+
+def _decode_loop(model, cache: BufferCache, last_token_prelogits: torch.Tensor, max_tokens: int, temperature: float,
+                 eos_id: Optional[int]) -> Tuple[List[torch.Tensor], List[torch.Tensor]]:
+    """The reference's loop: sample on the host side of the logits, one `forward` per token."""
+    B, V = last_token_prelogits.shape
+    generated: List[torch.Tensor] = []
+    gen_lp: List[torch.Tensor] = []
+    is_finished = torch.zeros(B, dtype=torch.bool, device=model.device)
+    pp_seed = _agree_seed(model) if _loop_shares_seed(model, temperature) else None
+    with _graph_context(model, cache):  # (the only place the context is entered)
         for step in range(max_tokens):
             next_token = sample(last_token_prelogits, temperature=temperature, top_p=0.8, seed=pp_seed, offset=step)
             if eos_id is not None:
                 is_finished = is_finished | (next_token == eos_id)
                 if bool(is_finished.all()):  # the one remaining per-token sync, only with an eos_id
                     break
-            lsm = torch.log_softmax(last_token_prelogits, dim=-1)
-            gen_lp.append(lsm.gather(1, next_token[:, None])[:, 0])
+            gen_lp.append(_logprob_of(last_token_prelogits, next_token))
             generated.append(next_token)
             # under the graph the returned tensor is the graph's output buffer (overwritten by the next step);
             # everything derived from it (next token, logprob) is computed before that happens
             last_token_prelogits = model.forward(next_token, seqlens=[1] * B, cache=cache)
             assert last_token_prelogits.shape == (B, V)
+    return generated, gen_lp
 
-    # ---- one copy back
+
+# ---- one copy back
+def _copy_back(B: int, lp_chunks: List[Tuple[int, torch.Tensor]], generated: List[torch.Tensor], gen_lp: List[torch.Tensor],
+               spec_out: Optional[Tuple[List[int], List[float]]]) -> Tuple[List[List[int]], List[List[float]]]:
     logprobs: List[List[float]] = [[] for _ in range(B)]
     if lp_chunks:
         flat_lp = torch.cat([t for _, t in lp_chunks]).tolist()
@@ -318,7 +390,7 @@ def generate(
             n = t.numel()
             logprobs[b].extend(flat_lp[o: o + n])
             o += n
-    generated_tokens: List[List[int]]
+    generated_tokens: List[List[int]] = []
     if generated:
         generated_tokens = torch.stack(generated, 1).tolist()
         lp = torch.stack(gen_lp, 1).tolist()
@@ -327,14 +399,15 @@ def generate(
     elif spec_out is not None and spec_out[0]:
         generated_tokens = [spec_out[0]]
         logprobs[0].extend(spec_out[1])
-    else:
-        generated_tokens = []
-    # the copies above synchronised the stream: the place to turn device-side flags (an out-of-range token id seen by the
-    # embedding kernel, a timed-out wait of the decode engine) into the exceptions the reference would have raised
+    return generated_tokens, logprobs
+
+
+def _raise_if_flagged(model) -> None:
+    """The copies back synchronised the stream: the place to turn device-side flags (an out-of-range token id seen by the
+    embedding kernel, a timed-out wait of the decode engine) into the exceptions the reference would have raised."""
     backend = getattr(model, "_backend", None)
     if hasattr(backend, "raise_if_flagged"):
         backend.raise_if_flagged()
-    return generated_tokens, logprobs
 
 
 def sample(logits: torch.Tensor, temperature: float, top_p: float, seed: Optional[int] = None, offset: int = 0) -> torch.Tensor:

@@ -302,8 +302,11 @@ def test_sample_never_communicates_and_takes_an_agreed_seed():
     src = inspect.getsource(G.sample)
     assert "torch.distributed" not in src and ".broadcast(" not in src and "all_reduce" not in src and "dist." not in src
     assert {"seed", "offset"} <= set(inspect.signature(G.sample).parameters)
-    gsrc = inspect.getsource(G.generate)
+    # (generate()'s side of it is one helper, which both decoders that sample call)
+    gsrc = inspect.getsource(G._agree_seed) + inspect.getsource(G._pp_ranks)
     assert "model.pp_comm.broadcast" in gsrc and "num_pipeline_ranks" in gsrc
+    assert all("_agree_seed(model)" in inspect.getsource(f) and f.__name__ + "(" in inspect.getsource(G.generate)
+               for f in (G._decode_session, G._decode_loop))
     # greedy and the torch path keep the reference's behaviour on CPU
     logits = torch.tensor([[0.1, 2.0, -1.0], [3.0, 0.0, 0.5]])
     assert G.sample(logits, temperature=0.0, top_p=0.8).tolist() == [1, 0]
