@@ -519,6 +519,51 @@ enum mi_dtype { MI_DTYPE_BF16 = 0, MI_DTYPE_FP16 = 1, MI_DTYPE_FP32 = 2 };
  * unrounded; a decode step's own row goes through the ring, rounded (transformer_layers.py:72-81).  The persistent engine declines. */
 size_t mi_workspace_bytes_kv(const mi_model_t* model, int quantised, int T, int B, int max_cache_size, int kv_layout);
 
+/* ------------------------------------------------------------------------------------------------
+ * FP8 prefill GEMMs (W8A8) for models whose weights are MI_W8_FP8_E4M3: opt-in, additive to ABI v9 like the blocks above (the
+ * presence of these symbols is the feature test; nothing above changes meaning).  A linear group of M >= 256 rows and K % 128 == 0
+ * quantises its bf16 input rows per row (per token) to e4m3 and contracts bytes with bytes on the block-scaled FP8 MFMA
+ * (csrc/gemm256_w8a8.hip):
+ *     s_x[m] = 2^ceil(log2(amax_k |x[m, k]| / 448))  (an all-zero row: 1),   x_q[m, k] = e4m3_rne(clamp(x[m, k] / s_x[m], +-448)),
+ *     y[m, n] = (sum_k e4m3(x_q[m, k]) * e4m3(w[n, k])) * (s_x[m] * scale[n])   in fp32,
+ * and y enters the epilogues exactly where the fp32 accumulator of mi_linear's GEMM enters them (same rounding points).  There is
+ * no dequantisation launch and no bf16 image of the weights.  Activations keep three mantissa bits: on inputs that e4m3 holds
+ * exactly under the row's power-of-two scale the route is lossless, on anything else it is NOT the weight-only model, and no claim
+ * about model quality is made.  Anything else - M < 256, K % 128 != 0, K > 16384 (the quantiser holds a row in registers), a row
+ * stride of x that is no multiple of 8, x or a weight matrix not 16-byte aligned - is not an error: it takes mi_linear_w8's routes,
+ * bit for bit.
+ * ---------------------------------------------------------------------------------------------- */
+/* xq [M, K] e4m3 bytes and sx [M] fp32 from bf16 rows x [M, K] (row stride ldx elements) by the rule above - the rule of
+ * mistral_inference.quant.quantize_rows, the same bytes as the CPU gives; never a NaN code; a code whose dequantised value would
+ * pass the largest bf16 steps down.  norm_w != NULL: the rows quantised are bf16(mi_rmsnorm(x, norm_w, eps)), i.e. what mi_rmsnorm
+ * writes.  K and ldx multiples of 8, K <= 16384 (MI_ERR_SHAPE). */
+int mi_act_quant_e4m3(void* xq, float* sx, const void* x, int ldx, int M, int K, const void* norm_w, float eps, mi_stream_t stream);
+/* mi_linear_w8 with the W8A8 route where it applies (M >= 256 && K % 128 == 0 && K <= 16384, operands as above): `scratch` then holds
+ * x_q | s_x, and norm_w is taken where the route is (fused into the quantisation).  Outside that shape it IS mi_linear_w8, scratch size
+ * included; inside it mi_linear_w8a8_scratch_bytes is the larger of the two routes' needs (x_q | s_x, or mi_linear_w8's bf16 image),
+ * since operands that the 16-byte accesses cannot read still take mi_linear_w8's route.  MI_EPI_LOGITS: MI_ERR_UNSUPPORTED, as there. */
+size_t mi_linear_w8a8_scratch_bytes(int M, int K, const int n_rows[3], int epilogue);
+int mi_linear_w8a8(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
+                   int epilogue, const void* residual, const void* norm_w, float eps, const float* const scale[3], void* scratch,
+                   size_t scratch_bytes, mi_stream_t stream);
+/* The q|k|v group of a prefill as mi_forward_w8a8 runs it, as a leaf: qkv[T, ldo] = rope(bf16((x_q . [wq; wk; wv]^T) * s_x * s_w))
+ * with RoPE in the GEMM's epilogue on the q | k columns (rope.py:13-23 on the bf16-rounded projection, as mi_rope_inplace) and no
+ * ring write.  The route's shape and operands only (T >= 256, D % 128 == 0, D <= 16384, ldx % 8 == 0, x and the weights 16-byte
+ * aligned; MI_ERR_UNSUPPORTED otherwise: fewer rows are mi_qkv_rope_kvwrite_w8's); head_dim 128; scratch of
+ * mi_linear_w8a8_scratch_bytes(T, D, ...) bytes. */
+int mi_qkv_rope_w8a8(void* qkv, int ldo, const void* x, int ldx, int T, int D, const void* wq, const void* wk, const void* wv,
+                     const float* sq, const float* sk, const float* sv, int n_heads, int n_kv_heads, int head_dim, const void* norm_w,
+                     float eps, const float* rope_cs, int rope_len, const int32_t* tok_pos, void* scratch, size_t scratch_bytes,
+                     mi_stream_t stream);
+/* mi_workspace_bytes_kv(model, 1, ...) / mi_forward_w8 with the W8A8 route in the four linear groups of every layer (q|k|v and
+ * w1|w3 with the RMSNorm fused into the quantisation, q|k|v with RoPE in the GEMM's epilogue).  The workspace is larger by
+ * x_q (T * max(dim, n_heads * head_dim, hidden_dim) bytes) and s_x (T floats), each rounded up to 256 bytes, behind everything else.
+ * A group outside the route (hidden_dim > 16384: w2) runs as in mi_forward_w8.
+ * Same refusals as mi_forward_w8 (w8 == NULL: MI_ERR_ARG).  Every forward of T < 256 rows - decode steps, short chunks - is launch
+ * for launch mi_forward_w8; rings of e4m3 bytes (MI_KV_E4M3) are independent of it. */
+size_t mi_workspace_bytes_w8a8(const mi_model_t* model, const mi_w8_model_t* w8, int T, int B, int max_cache_size, int kv_layout);
+int mi_forward_w8a8(const mi_model_t* model, const mi_w8_model_t* w8, const mi_batch_t* batch, mi_stream_t stream);
+
 size_t mi_workspace_bytes_generic(const mi_model_t* model, int T, int dtype);
 int mi_forward_generic(const mi_model_t* model, const mi_batch_t* batch, int dtype, mi_stream_t stream);
 /* Leaf operators in any storage dtype - what module-level callers of an fp16 / fp32 model bind (the Pixtral tower of

@@ -68,6 +68,85 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(bf16_t* out, const bf16_t*
   }
 }
 
+// ---- per-token e4m3 quantisation of activation rows (W8A8 prefill, kernels.h launch_act_quant_e4m3): the rule of
+// mistral_inference.quant.quantize_rows in the same integer-exponent arithmetic, so the CPU and the device give the same bytes.
+// One wave per row as rmsnorm_kernel, the row in registers: one pass over the row, 16-byte loads, 8-byte stores.  NORM: the row
+// quantised is the bf16 row rmsnorm_kernel writes (the same operations in the same order, then pack_bf2's rounding).
+__device__ __forceinline__ float aq_clamp(float x) { return fminf(fmaxf(x, -448.f), 448.f); }
+__device__ __forceinline__ uint32_t aq_stepdown(uint32_t w) {  // codes of magnitude >= 256 step down (a scale of 2^120 only)
+#pragma unroll
+  for (int b = 0; b < 4; ++b)
+    if (((w >> (8 * b)) & 0x7fu) >= 0x78u) w -= 1u << (8 * b);
+  return w;
+}
+template <int NP, bool NORM>
+__global__ __launch_bounds__(256) void act_quant_e4m3_kernel(uint8_t* xq, float* sx, const bf16_t* x, int ldx, const bf16_t* w, int T,
+                                                             int D, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (t >= T) return;
+  const bf16_t* xr = x + (size_t)t * ldx;
+  const int np = D >> 3;
+  u32x4 v[NP];
+#pragma unroll
+  for (int j = 0; j < NP; ++j) v[j] = ld16(xr + min(lane + j * 64, np - 1) * 8);
+  if (NORM) {
+    float ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float a = bf_lo(v[j][i]), b = bf_hi(v[j][i]);
+        s = fmaf(a, a, s);
+        s = fmaf(b, b, s);
+      }
+      ss += (lane + j * 64 < np) ? s : 0.f;
+    }
+    ss = wave_sum(ss);
+    const float inv = 1.0f / sqrtf(ss / (float)D + eps);
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      const u32x4 wv = ld16(w + min(lane + j * 64, np - 1) * 8);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        v[j][i] = pack_bf2(bf_round(bf_lo(v[j][i]) * inv) * bf_lo(wv[i]), bf_round(bf_hi(v[j][i]) * inv) * bf_hi(wv[i]));
+    }
+  }
+  // amax over bf16 magnitudes is a maximum over their 15-bit patterns
+  uint32_t am = 0;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    uint32_t m = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) m = max(m, max(v[j][i] & 0x7fffu, (v[j][i] >> 16) & 0x7fffu));
+    am = max(am, (lane + j * 64 < np) ? m : 0u);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) am = max(am, (uint32_t)__shfl_xor((int)am, o, 64));
+  const float amax = __uint_as_float(am << 16);
+  // amax = mant * 2^ex, mant in [0.5, 1);  amax / 448 = (2 mant / 1.75) * 2^(ex - 9)
+  int ex = 0;
+  const float mant = frexpf(amax, &ex);
+  const int e = am == 0 ? 0 : ex - 9 + (mant > 0.875f ? 1 : 0);
+  if (lane == 0) sx[t] = ldexpf(1.0f, e);
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    const int p = lane + j * 64;
+    if (p < np) {
+      u32x2 o;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const uint32_t p0 = v[j][2 * i], p1 = v[j][2 * i + 1];
+        int c = __builtin_amdgcn_cvt_pk_fp8_f32(aq_clamp(ldexpf(bf_lo(p0), -e)), aq_clamp(ldexpf(bf_hi(p0), -e)), 0, false);
+        c = __builtin_amdgcn_cvt_pk_fp8_f32(aq_clamp(ldexpf(bf_lo(p1), -e)), aq_clamp(ldexpf(bf_hi(p1), -e)), c, true);
+        o[i] = e >= 120 ? aq_stepdown((uint32_t)c) : (uint32_t)c;
+      }
+      *reinterpret_cast<u32x2*>(xq + (size_t)t * D + p * 8) = o;
+    }
+  }
+}
+
 // rope.py:13-23, in place on the q|k columns of the fused buffer.  One thread rotates 4 adjacent pairs.
 __global__ __launch_bounds__(256) void rope_kernel(bf16_t* qkv, int ld, int T, int n_rot_cols, int Dh,
                                                    const float* rope_cs, const int32_t* tok_pos) {
@@ -576,6 +655,21 @@ hipError_t launch_rmsnorm(void* out, const void* x, const void* w, int T, int D,
   else if (D <= 8192) hipLaunchKernelGGL((rmsnorm_kernel<16>), grid, block, 0, s, o, xx, ww, T, D, eps);
   else hipLaunchKernelGGL((rmsnorm_kernel<32>), grid, block, 0, s, o, xx, ww, T, D, eps);
   return hipGetLastError();
+}
+template <bool NORM>
+static hipError_t launch_act_quant(uint8_t* q, float* sx, const bf16_t* x, int ldx, const bf16_t* w, int M, int K, float eps, hipStream_t s) {
+  const dim3 grid((M + 3) / 4), block(256);
+  if (K <= 4096) hipLaunchKernelGGL((act_quant_e4m3_kernel<8, NORM>), grid, block, 0, s, q, sx, x, ldx, w, M, K, eps);
+  else if (K <= 6144) hipLaunchKernelGGL((act_quant_e4m3_kernel<12, NORM>), grid, block, 0, s, q, sx, x, ldx, w, M, K, eps);
+  else if (K <= 8192) hipLaunchKernelGGL((act_quant_e4m3_kernel<16, NORM>), grid, block, 0, s, q, sx, x, ldx, w, M, K, eps);
+  else hipLaunchKernelGGL((act_quant_e4m3_kernel<32, NORM>), grid, block, 0, s, q, sx, x, ldx, w, M, K, eps);
+  return hipGetLastError();
+}
+hipError_t launch_act_quant_e4m3(void* xq, float* sx, const void* x, int ldx, int M, int K, const void* norm_w, float eps,
+                                 hipStream_t s) {
+  if (M <= 0 || K <= 0 || K % 8 || K > 16384 || ldx < K || ldx % 8) return hipErrorInvalidValue;
+  return norm_w ? launch_act_quant<true>((uint8_t*)xq, sx, (const bf16_t*)x, ldx, (const bf16_t*)norm_w, M, K, eps, s)
+                : launch_act_quant<false>((uint8_t*)xq, sx, (const bf16_t*)x, ldx, nullptr, M, K, eps, s);
 }
 hipError_t launch_rope(void* qkv, int ld, int T, int H, int Hkv, int Dh, const float* rope_cs, const int32_t* tok_pos,
                        hipStream_t s) {

@@ -148,6 +148,18 @@ void gemm_set_tail_mode(int mode);  // mi_debug_set_prefill_kernels
 // gemm256.hip compiled with -DG256_F16=1 (element ElemF16): the same kernel on fp16 payloads (generic.hip: prefills of fp16 models; gemm256_applicable is the predicate for both elements)
 hipError_t launch_gemm256_f16(const GemmArgs& g, hipStream_t s);
 
+// gemm256_w8a8.hip: gemm256's structure on e4m3 bytes for BOTH operands (prefills of FP8 models, opt-in):
+// out = epilogue((A_q . W_q^T)[m, n] * sx[m] * sw[n]).  g.a / g.w0 / g.w1 / g.w2 point to e4m3 bytes, g.lda is in bytes; sx [M] are
+// the activation rows' scales (launch_act_quant_e4m3), sw[i] the row scales of weight segment i (SWIGLU: sw[0] = W1's, sw[1] =
+// W3's).  Epilogues STORE (with RoPE) / RESIDUAL / SWIGLU; plain form only (no tile table, no gather).
+struct GemmW8A8Args {
+  GemmArgs g;
+  const float* sx;
+  const float* sw[3];
+};
+bool gemm256_w8a8_applicable(int M, int K);  // M >= 256 && K % 128 == 0 && K <= 16384 (the quantiser's limit): the route's one shape predicate
+hipError_t launch_gemm256_w8a8(const GemmW8A8Args& a, hipStream_t s);
+
 // ---------------------------------------------------------------------------------------------- attention
 struct AttnDecodeArgs {
   void* out;            // [B, H*Dh]
@@ -266,6 +278,12 @@ hipError_t launch_embedding(void* out, const void* table, const int64_t* ids, in
 hipError_t launch_rmsnorm(void* out, const void* x, const void* w, int T, int D, float eps, hipStream_t s);
 hipError_t launch_rope(void* qkv, int ld, int T, int H, int Hkv, int Dh, const float* rope_cs, const int32_t* tok_pos,
                        hipStream_t s);
+// Per-row (per-token) e4m3 quantisation of bf16 rows x [M, K] (row stride ldx elements): xq [M, K] bytes, sx [M] fp32, by the rule
+// of mistral_inference.quant.quantize_rows - sx = 2^ceil(log2(amax / 448)) (an all-zero row: 1), byte = e4m3_rne(clamp(x / sx,
+// +-448)), never a NaN code.  norm_w != nullptr: the row quantised is the bf16 row launch_rmsnorm would have written.
+// K % 8 == 0, K <= 16384, ldx % 8 == 0.
+hipError_t launch_act_quant_e4m3(void* xq, float* sx, const void* x, int ldx, int M, int K, const void* norm_w, float eps,
+                                 hipStream_t s);
 hipError_t launch_kv_write(void* ck, void* cv, int W, const void* k, const void* v, int ld, int T, int kv_dim,
                            const int32_t* tok_seq, const int32_t* tok_pos, const int32_t* q_start, int kv_layout, int Dh, hipStream_t s);
 // kv_layout with MI_KV_E4M3 (launch_kv_write): bf16 rows in, e4m3 bytes to the ring.  launch_kv_dequant: n_elems e4m3 bytes of

@@ -21,7 +21,19 @@ MXFP4 (`qformat_weight` "mxfp4", OCP microscaling): e2m1 codes in blocks of 32 a
 per weight.  `<linear>.weight` is U8 [out, in / 2], two codes per byte with the LOW nibble at the even k; `<linear>.qscale_weight`
 is U8 [out, in / 32], byte b meaning 2^(b - 127) (255, the e8m0 NaN, is refused).  The real-valued weight is
 `2^(b - 127) * e2m1(code)`, exact in bf16, so `Mxfp4Linear` (one `mi_linear_w4` call, csrc/gemv_w4.hip) computes the bf16 model on
-the dequantised weights up to fp32 summation order, at any number of rows.  `in` must be a multiple of 32."""
+the dequantised weights up to fp32 summation order, at any number of rows.  `in` must be a multiple of 32.
+
+FP8 prefill GEMMs (`prefill_fp8=True`, FP8 e4m3 weights only, opt-in): a linear of T >= 256 rows, `in` % 128 == 0 and `in` <= 16384 quantises its
+input rows too, per row (per token), by the rule of `quantize_rows` (`quantize_activations` names it):
+
+    s_x[t] = 2^ceil(log2(amax_k |x[t, k]| / 448))  (an all-zero row: 1),   x_q[t, k] = e4m3_rne(clamp(x[t, k] / s_x[t], +-448))
+    y[t, r] = bf16((sum_k e4m3(x_q[t, k]) e4m3(W[r, k])) * (s_x[t] * qscale_weight[r]))        (csrc/gemm256_w8a8.hip)
+
+with the sum in fp32 on the FP8 MFMA and no dequantisation pass.  In front of q|k|v and w1|w3 the row quantised is the bf16 output
+of the RMSNorm.  Activations keep three mantissa bits: on inputs that e4m3 holds exactly the route is lossless, on real activations
+it is a different (coarser) model than the weight-only one, and nobody claims model quality for it - it ships with its measured
+speed (README) and is off unless asked for.  Every other shape - decode steps, verify steps, short chunks - takes the weight-only
+routes above, bit for bit."""
 import json
 import re
 from pathlib import Path
@@ -51,6 +63,8 @@ _REFUSALS = {
     "shape": ("{name} weight-only quantisation on a model shape outside the tuned bf16 kernels (head_dim "
               "128, dim / hidden_dim multiples of {k_multiple}) is not implemented"),
     "pth": "{name} weight-only models load from consolidated.safetensors (a .pth checkpoint is not implemented)",
+    "prefill_fp8": ("prefill_fp8=True on {what} is not implemented: the FP8 prefill GEMMs read FP8 (e4m3) weights beside bfloat16 "
+                    "activations (quantize=\"fp8_e4m3\", or a folder that quantize_checkpoint wrote, with bfloat16 storage)"),
 }
 MXFP4_BLOCK = 32
 E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # magnitude of code & 7; code & 8 is the sign
@@ -77,6 +91,20 @@ def refuse_quant_combinations(args, dtype: Optional[torch.dtype]) -> None:
         raise NotImplementedError(refusal("moe", args.quantization))
     if dtype is not None and dtype != torch.bfloat16:
         raise NotImplementedError(refusal("storage", args.quantization, dtype=dtype))
+
+
+def refuse_prefill_fp8(args, dtype: Optional[torch.dtype]) -> None:
+    """`prefill_fp8=True` on a model whose weights are not FP8 e4m3 (bf16, MXFP4) or whose storage is not bfloat16, by name."""
+    qz = args.quantization
+    if qz is None:
+        what = "a model without FP8 weights" if dtype in (None, torch.bfloat16) else f"a model with {dtype} storage"
+    elif qz.qformat_weight != QFORMAT_FP8_E4M3:
+        what = f"{quantized_linear_cls(qz).name} weights"
+    elif dtype not in (None, torch.bfloat16):
+        what = f"{dtype} storage"
+    else:
+        return
+    raise NotImplementedError(_REFUSALS["prefill_fp8"].format(what=what))
 
 
 def is_quantized_linear_key(key: str) -> bool:
@@ -108,6 +136,12 @@ def quantize_rows(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return q, scale
 
 
+def quantize_activations(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[T, in] bf16 activation rows -> (x_q float8_e4m3fn [T, in], s_x fp32 [T]): `quantize_rows`, one power-of-two scale per row
+    (per token).  The host-side statement of what `_hip.act_quant_e4m3` computes, byte for byte."""
+    return quantize_rows(x)
+
+
 def dequantize(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     """bf16(scale[r] * e4m3(q[r, k])); exact for power-of-two scales.  q: float8_e4m3fn or its bytes as uint8."""
     if q.dtype == torch.uint8:
@@ -134,6 +168,7 @@ class QuantLinear(nn.Module):
     qformat: str              # params.json `quantization.qformat_weight`
     k_multiple: int           # what in_features (and the model's dim / hidden_dim) must be a multiple of
     hip: _hip.QuantFormat     # the format's entry points of the library
+    prefill_fp8 = False       # FP8 linears: Transformer.prefill_fp8 sets it on every linear of the model (mi_linear_w8a8)
     quantize = None           # staticmethod: bf16 [out, in] -> (weight, scale) as a checkpoint stores them
 
     def __init__(self, in_features: int, out_features: int, bias: bool = False):
@@ -161,7 +196,8 @@ class QuantLinear(nn.Module):
 def linear_quant(x: torch.Tensor, mods: Sequence[QuantLinear], epilogue: int = _hip.EPI_STORE, residual: Optional[torch.Tensor] = None,
                  norm_w: Optional[torch.Tensor] = None, eps: float = 0.0) -> torch.Tensor:
     """`_hip.linear` over up to three quantised linears of one format that share an input (q|k|v; SWIGLU: w1, w3)."""
-    return _hip.linear_quant(mods[0].hip, x, [m.weight for m in mods], [m.qscale_weight for m in mods], epilogue, residual, norm_w, eps)
+    return _hip.linear_quant(mods[0].hip, x, [m.weight for m in mods], [m.qscale_weight for m in mods], epilogue, residual, norm_w, eps,
+                             a8=bool(mods[0].prefill_fp8))
 
 
 class Fp8Linear(QuantLinear):
