@@ -564,6 +564,43 @@ int mi_qkv_rope_w8a8(void* qkv, int ldo, const void* x, int ldx, int T, int D, c
 size_t mi_workspace_bytes_w8a8(const mi_model_t* model, const mi_w8_model_t* w8, int T, int B, int max_cache_size, int kv_layout);
 int mi_forward_w8a8(const mi_model_t* model, const mi_w8_model_t* w8, const mi_batch_t* batch, mi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * MXFP4 x FP8 prefill GEMMs (W4A8) for models whose weights are MI_W4_MXFP4: opt-in, additive to ABI v9 like the block above.  A
+ * linear group of M >= 256 rows and K % 128 == 0 quantises its bf16 input rows per row (per token) to e4m3 - mi_act_quant_e4m3,
+ * the rule above - and contracts them with the e2m1 codes on the mixed form of the block-scaled MFMA, which applies the e8m0 block
+ * scale bytes itself (csrc/gemm256_w4a8.hip):
+ *     y[m, n] = (sum_k e4m3(x_q[m, k]) * e2m1(c[n, k]) * 2^(s[n, k / 32] - 127)) * s_x[m]   in fp32,
+ * and y enters the epilogues exactly where the fp32 accumulator of mi_linear's GEMM enters them (same rounding points).  There is
+ * no dequantisation launch and no bf16 image of the weights.  On inputs that e4m3 holds exactly under the row's power-of-two scale
+ * the route is the weight-only route up to fp32 summation order (lossless); on anything else it is NOT the weight-only model, and
+ * no claim about model quality is made.  For block scale bytes below 3 (weights under 2^-124) the weight-only route's bf16 image
+ * holds subnormals, which it may flush and this route does not.  Anything else - M < 256, K % 128 != 0, K > 16384, a row stride of
+ * x that is no multiple of 8, x or a code matrix not 16-byte aligned, a block scale matrix not 4-byte aligned (the GEMM stages the
+ * scale bytes of a K tile by 4-byte DMA) - is not an error: it takes mi_linear_w4's routes, bit for bit.
+ * ---------------------------------------------------------------------------------------------- */
+/* mi_linear_w4 with the W4A8 route where it applies: `scratch` then holds x_q | s_x, and norm_w is taken where the route is (fused
+ * into the quantisation).  Outside the route's shape it IS mi_linear_w4, scratch size included; inside it
+ * mi_linear_w4a8_scratch_bytes is the larger of the two routes' needs (x_q | s_x, or mi_linear_w4's bf16 image).  MI_EPI_LOGITS:
+ * MI_ERR_UNSUPPORTED, as there. */
+size_t mi_linear_w4a8_scratch_bytes(int M, int K, const int n_rows[3], int epilogue);
+int mi_linear_w4a8(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
+                   int epilogue, const void* residual, const void* norm_w, float eps, const uint8_t* const scale[3], void* scratch,
+                   size_t scratch_bytes, mi_stream_t stream);
+/* mi_qkv_rope_w8a8 on MXFP4 code matrices and their block scale bytes: the q|k|v group of a prefill as mi_forward_w4a8 runs it,
+ * RoPE in the GEMM's epilogue, no ring write.  The route's shape and operands only, the 4-byte alignment of sq / sk / sv included
+ * (MI_ERR_UNSUPPORTED otherwise: fewer rows are mi_qkv_rope_kvwrite_w4's); head_dim 128; scratch of mi_linear_w4a8_scratch_bytes(T, D, ...) bytes. */
+int mi_qkv_rope_w4a8(void* qkv, int ldo, const void* x, int ldx, int T, int D, const void* wq, const void* wk, const void* wv,
+                     const uint8_t* sq, const uint8_t* sk, const uint8_t* sv, int n_heads, int n_kv_heads, int head_dim,
+                     const void* norm_w, float eps, const float* rope_cs, int rope_len, const int32_t* tok_pos, void* scratch,
+                     size_t scratch_bytes, mi_stream_t stream);
+/* mi_workspace_bytes_kv(model, 1, ...) / mi_forward_w4 with the W4A8 route in the four linear groups of every layer (q|k|v and
+ * w1|w3 with the RMSNorm fused into the quantisation, q|k|v with RoPE in the GEMM's epilogue).  The workspace is larger by
+ * x_q (T * max(dim, n_heads * head_dim, hidden_dim) bytes) and s_x (T floats), each rounded up to 256 bytes, behind everything else.
+ * A group outside the route (hidden_dim > 16384: w2) runs as in mi_forward_w4.  Same refusals as mi_forward_w4 (w4 == NULL:
+ * MI_ERR_ARG).  Every forward of T < 256 rows - decode steps, short chunks - is launch for launch mi_forward_w4. */
+size_t mi_workspace_bytes_w4a8(const mi_model_t* model, const mi_w4_model_t* w4, int T, int B, int max_cache_size, int kv_layout);
+int mi_forward_w4a8(const mi_model_t* model, const mi_w4_model_t* w4, const mi_batch_t* batch, mi_stream_t stream);
+
 size_t mi_workspace_bytes_generic(const mi_model_t* model, int T, int dtype);
 int mi_forward_generic(const mi_model_t* model, const mi_batch_t* batch, int dtype, mi_stream_t stream);
 /* Leaf operators in any storage dtype - what module-level callers of an fp16 / fp32 model bind (the Pixtral tower of

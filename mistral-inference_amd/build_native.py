@@ -13,7 +13,8 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "lib", "libmistral_hip.so")
 SOURCES = ["api.hip", "gemv.hip", "gemm.hip", "gemm256.hip", "attn_decode.hip", "attn_prefill.hip", "attn_verify.hip", "elementwise.hip",
-           "decode_engine.hip", "decode_engine_host.hip", "sampling.hip", "rccl_api.hip", "generic.hip", "lora.hip", "gemv_w8.hip", "gemv_w4.hip", "gemm256_w8a8.hip"]
+           "decode_engine.hip", "decode_engine_host.hip", "sampling.hip", "rccl_api.hip", "generic.hip", "lora.hip", "gemv_w8.hip", "gemv_w4.hip", "gemm256_w8a8.hip",
+           "gemm256_w4a8.hip"]
 # (this file is a dependency of every object: a change of flags must rebuild them - round 6: decode_engine_next.o was once shipped
 # without a flag that had just been added here)
 HEADERS = [os.path.abspath(__file__), os.path.join(CSRC, "common.cuh"), os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "gemv_core.cuh"),

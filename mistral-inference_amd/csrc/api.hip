@@ -97,7 +97,7 @@ struct Workspace {
                      //     linear_group; bf16 above 8 rows.  Wo's and W2's base product goes to xn.)
   bf16_t* stash;     // verify steps (behind everything else, such steps only): the step's post-RoPE K | V rows of every layer
                      //     [n_layers, T, 2 * n_kv_heads * head_dim], which enter the rings once acceptance is known
-  uint8_t* x_q;      // FP8 prefill GEMMs (mi_forward_w8a8 only, behind everything else): the e4m3 rows of a linear group's input
+  uint8_t* x_q;      // FP8 prefill GEMMs (mi_forward_w8a8 / mi_forward_w4a8 only, behind everything else): the e4m3 rows of a linear group's input
   float* s_x;        //     [T, max(dim, n_heads * head_dim, hidden_dim)] and their scales [T]
   size_t total;
 };
@@ -117,7 +117,7 @@ size_t verify_stash_bytes(const mi_model_t* m, int T) { return (size_t)m->n_laye
 
 // quant: the linears are quantised (any format: the same scratch of one dequantised linear group); kv8: the rings hold e4m3 bytes
 // verify: a verify step (mi_forward_verify) - its attention keeps split partials per ROW, so the caller passes B = T, and the stash
-// a8: the entry is mi_forward_w8a8 - the activation rows of its FP8 GEMMs
+// a8: the entry is mi_forward_w8a8 / mi_forward_w4a8 - the activation rows of its FP8-activation GEMMs
 Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool quant = false, bool kv8 = false, bool verify = false,
                 bool a8 = false) {
   Workspace w;
@@ -260,7 +260,9 @@ struct QuantW8 {  // gemv_w8.hip: e4m3 bytes, one fp32 scale per row
   static constexpr const char *kFormatName = "MI_W8_FP8_E4M3 = 1", *kArg = "w8", *kName = "FP8", *kScales = "row scales";
   static constexpr const char* kWhy = "a 16-byte piece is 16 e4m3 weights";
   static constexpr const char *kLinear = "mi_linear_w8", *kQkv = "mi_qkv_rope_kvwrite_w8", *kGemv = "gemv (w8)", *kDequant = "dequant (w8)",
-                              *kQkvGemv = "qkv gemv (w8)";
+                              *kQkvGemv = "qkv gemv (w8)", *kLinearA8 = "mi_linear_w8a8", *kQkvA8 = "mi_qkv_rope_w8a8",
+                              *kPrior = "mi_qkv_rope_kvwrite_w8", *kGemmA8 = "FP8 prefill GEMM",
+                              *kOperandsA8 = "x and the weights 16-byte aligned";
   static constexpr auto launch_gemv = launch_gemv_w8;
   static constexpr auto launch_dequant = launch_dequant_w8;
 };
@@ -270,7 +272,9 @@ struct QuantW4 {  // gemv_w4.hip: MXFP4 code bytes, one e8m0 scale byte per bloc
   static constexpr const char *kFormatName = "MI_W4_MXFP4 = 2", *kArg = "w4", *kName = "MXFP4", *kScales = "block scales";
   static constexpr const char* kWhy = "one e8m0 scale per block of 32 MXFP4 weights";
   static constexpr const char *kLinear = "mi_linear_w4", *kQkv = "mi_qkv_rope_kvwrite_w4", *kGemv = "gemv (w4)", *kDequant = "dequant (w4)",
-                              *kQkvGemv = "qkv gemv (w4)";
+                              *kQkvGemv = "qkv gemv (w4)", *kLinearA8 = "mi_linear_w4a8", *kQkvA8 = "mi_qkv_rope_w4a8",
+                              *kPrior = "mi_qkv_rope_kvwrite_w4", *kGemmA8 = "MXFP4 x FP8 prefill GEMM",
+                              *kOperandsA8 = "x and the code matrices 16-byte aligned, the block scale matrices 4-byte aligned";
   static constexpr auto launch_gemv = launch_gemv_w4;
   static constexpr auto launch_dequant = launch_dequant_w4;
 };
@@ -490,6 +494,18 @@ inline bool w8a8_operands_ok(const void* x, int ldx, const void* const w[3]) {
                            reinterpret_cast<size_t>(w[2])) & 15) == 0;
 }
 
+// The route's one shape predicate, by the group's format (kernels.h): the runner, the leaves and the scratch queries all ask here
+inline bool a8_applicable(int format, int M, int K) {
+  return format == MI_W4_MXFP4 ? gemm256_w4a8_applicable(M, K) : gemm256_w8a8_applicable(M, K);
+}
+// The operands' needs for a group of either format: the W4A8 GEMM also stages the block scale bytes by 4-byte DMA (rows are K / 32 = 4 k bytes)
+inline bool a8_operands_ok(const LinearGroup& G, const void* x, int ldx) {
+  if (G.format == MI_W4_MXFP4 &&
+      ((reinterpret_cast<size_t>(G.s4.s[0]) | reinterpret_cast<size_t>(G.s4.s[1]) | reinterpret_cast<size_t>(G.s4.s[2])) & 3))
+    return false;
+  return w8a8_operands_ok(x, ldx, G.w);
+}
+
 constexpr int EPI_QKV_ROPE = 100;  // beside the public MI_EPI_* codes: the fused q|k|v + RoPE (+ ring write)
 struct LinearLabels {  // the `what` of each launch (error details name it); nullptr: the caller cannot reach that launch
   const char *gemv, *gemm, *dequant, *norm;
@@ -523,8 +539,9 @@ struct LinearCall {
   // bit for bit.  forward_body asks for it at q|k|v and W1|W3, the leaf only for a fused-norm SwiGLU (lora_shape)
   bool lora_base_f32;
   LinearLabels what;
-  // FP8 prefill GEMMs (opt-in: mi_linear_w8a8, mi_forward_w8a8): an FP8 group of M >= 256 rows and K % 128 == 0 quantises its input
-  // rows into x_q [M, K] e4m3 bytes / s_x [M] and runs the W8A8 GEMM on the weight bytes as they are
+  // FP8 prefill GEMMs (opt-in: mi_linear_w8a8, mi_forward_w8a8; on MXFP4 weights mi_linear_w4a8, mi_forward_w4a8): a quantised group
+  // of M >= 256 rows and K % 128 == 0 quantises its input rows into x_q [M, K] e4m3 bytes / s_x [M] and runs the W8A8 GEMM (the W4A8
+  // GEMM) on the weight bytes as they are
   bool a8;
   uint8_t* x_q;
   float* s_x;
@@ -532,8 +549,9 @@ struct LinearCall {
 
 // M <= GEMV_MAX_T rows: weight-streaming GEMV passes with the RMSNorm, RoPE and (bf16 rings) the ring write fused.  More rows: the
 // RMSNorm into xn, the bf16 image of quantised weights into deq, then the MFMA GEMM (RoPE in its epilogue when it takes the heads).
-// FP8 groups with C.a8 at M >= 256 rows and K % 128 == 0: the per-token e4m3 quantisation of the input rows (the RMSNorm fused into
-// it) and the W8A8 MFMA GEMM on the weight bytes - no xn, no deq, no dequantisation launch; any other shape takes the routes above.
+// Quantised groups with C.a8 at M >= 256 rows and K % 128 == 0: the per-token e4m3 quantisation of the input rows (the RMSNorm fused
+// into it) and the format's FP8-activation MFMA GEMM on the weight bytes (gemm256_w8a8.hip / gemm256_w4a8.hip) - no xn, no deq, no
+// dequantisation launch; any other shape takes the routes above.
 // Adapters: the RMSNorm into xn at any M (lora_down reads it), the base product by the same two routes in plain store form,
 // lora_down, lora_up with the epilogue, then RoPE and the ring write as passes of their own (bit-equal to the fused epilogues:
 // same arithmetic on the same bf16 values).
@@ -544,9 +562,9 @@ int linear_group(const LinearGroup& G, const LinearCall& C, int M, hipStream_t s
   // RoPE rides on the GEMV's epilogue, and on the GEMM's (same arithmetic as rope_kernel on the same bf16-rounded values; it was a
   // separate 20 us pass over q|k per layer at 4096 tokens) unless the heads are of a size that epilogue does not take
   const bool fused_rope = qkv && G.rank == 0 && (gemv || (fuse_rope_enabled() && C.head_dim % 16 == 0));  // (either GEMM's epilogue)
-  const bool w8a8 = C.a8 && C.x_q && C.s_x && G.format == MI_W8_FP8_E4M3 && G.rank == 0 && C.epi != MI_EPI_LOGITS &&
-                    gemm256_w8a8_applicable(M, K) && w8a8_operands_ok(C.x, C.ldx, G.w);
-  if (C.norm_w && !C.xn && !w8a8 && (!gemv || G.rank > 0)) return fail(MI_ERR_UNSUPPORTED, "linear group: fused RMSNorm only on the M <= 8 path");
+  const bool a8 = C.a8 && C.x_q && C.s_x && G.format != 0 && G.rank == 0 && C.epi != MI_EPI_LOGITS && a8_applicable(G.format, M, K) &&
+                  a8_operands_ok(G, C.x, C.ldx);
+  if (C.norm_w && !C.xn && !a8 && (!gemv || G.rank > 0)) return fail(MI_ERR_UNSUPPORTED, "linear group: fused RMSNorm only on the M <= 8 path");
   if (G.rank > 0) {
     const void* xn = C.x;
     int ldxn = C.ldx;
@@ -594,19 +612,22 @@ int linear_group(const LinearGroup& G, const LinearCall& C, int M, hipStream_t s
       MI_TRY(with_format(G.format, [&](auto Q) { return gemv_passes_quant<decltype(Q)>(a, scales_of(G, Q), M, s, C.what.gemv); }));
     else
       MI_TRY(gemv_passes(kGemvBf16, a, M, s, C.what.gemv));
-  } else if (w8a8) {
+  } else if (a8) {
     MI_TRY(hip_rc(launch_act_quant_e4m3(C.x_q, C.s_x, C.x, C.ldx, M, K, C.norm_w, C.eps, s), "act_quant_e4m3"));
-    GemmW8A8Args a;
-    memset(&a, 0, sizeof(a));
-    GemmArgs& g = a.g;
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
     g.epi = swiglu ? GEMM_SWIGLU : (C.epi == MI_EPI_STORE || qkv) ? GEMM_STORE : GEMM_RESIDUAL;
     g.M = M; g.N = swiglu ? n0 : n2; g.K = K; g.a = (const bf16_t*)C.x_q; g.lda = K;
     g.w0 = (const bf16_t*)G.w[0]; g.w1 = (const bf16_t*)G.w[1]; g.w2 = (const bf16_t*)G.w[2]; g.n0 = n0; g.n1 = swiglu ? n0 : n1;
     g.out = C.out; g.ldo = C.ldo; g.residual = (const bf16_t*)C.residual;
     if (fused_rope) { g.rope_cs = C.rope_cs; g.tok_pos = C.tok_pos; g.rope_cols = n1; g.rope_dh = C.head_dim; }
-    a.sx = C.s_x;
-    for (int i = 0; i < 3; ++i) a.sw[i] = G.s8.s[i];
-    MI_TRY(hip_rc(launch_gemm256_w8a8(a, s), "w8a8 gemm"));
+    if (G.format == MI_W4_MXFP4) {  // e2m1 codes x e4m3 bytes, the block scales inside the MFMA
+      const GemmW4A8Args a = {g, C.s_x, {G.s4.s[0], G.s4.s[1], G.s4.s[2]}};
+      MI_TRY(hip_rc(launch_gemm256_w4a8(a, s), "w4a8 gemm"));
+    } else {  // e4m3 bytes x e4m3 bytes, the row scales in the epilogue
+      const GemmW8A8Args a = {g, C.s_x, {G.s8.s[0], G.s8.s[1], G.s8.s[2]}};
+      MI_TRY(hip_rc(launch_gemm256_w8a8(a, s), "w8a8 gemm"));
+    }
   } else {
     const bf16_t* x = (const bf16_t*)C.x;
     int ldx = C.ldx;
@@ -1022,12 +1043,12 @@ size_t mi_linear_w8_scratch_bytes(int M, int K, const int n_rows[3], int epilogu
 
 static size_t w8a8_scratch_bytes(int M, int K) { return align_up((size_t)M * K) + align_up((size_t)M * sizeof(float)); }  // x_q | s_x
 
-// mi_linear_w8 / mi_linear_w4; a8 (mi_linear_w8a8): the FP8 prefill GEMM where it applies, whose scratch is x_q | s_x
+// mi_linear_w8 / mi_linear_w4; a8 (mi_linear_w8a8 / mi_linear_w4a8): the format's FP8-activation GEMM where it applies, whose scratch is x_q | s_x
 template <class Q>
 static int linear_quant(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3], int epilogue,
                         const void* residual, const void* norm_w, float eps, const typename Q::scale_t* const scale[3], void* scratch,
                         size_t scratch_bytes, mi_stream_t stream, bool a8 = false) {
-  const char* me = a8 ? "mi_linear_w8a8" : Q::kLinear;
+  const char* me = a8 ? Q::kLinearA8 : Q::kLinear;
   if (!out || !x || !w || !n_rows || !scale || !w[0] || !scale[0] || M <= 0 || K <= 0 || n_rows[0] <= 0) return fail(MI_ERR_ARG, "%s", me);
   for (int i = 1; i < 3; ++i)
     if (w[i] && (!scale[i] || n_rows[i] <= 0 || !w[i - 1])) return fail(MI_ERR_ARG, "%s: segment %d needs rows, a scale and its predecessor", me, i);
@@ -1041,9 +1062,9 @@ static int linear_quant(void* out, int ldo, const void* x, int ldx, int M, int K
   set_scales(g, Q{}, scale[0], w[1] ? scale[1] : nullptr, (!swiglu && w[2]) ? scale[2] : nullptr);
   // (outside the route's shape the leaf is mi_linear_w8; inside it linear_group still takes the weight-only route for operands the
   // 16-byte accesses cannot read, so the scratch is sized for either: mi_linear_w8a8_scratch_bytes)
-  a8 = a8 && gemm256_w8a8_applicable(M, K);
+  a8 = a8 && a8_applicable(Q::kFormat, M, K);
   if (M > GEMV_MAX_T) {
-    if (norm_w && !(a8 && w8a8_operands_ok(x, ldx, g.w))) return fail(MI_ERR_UNSUPPORTED, "%s: fused RMSNorm only on the M <= 8 path", me);
+    if (norm_w && !(a8 && a8_operands_ok(g, x, ldx))) return fail(MI_ERR_UNSUPPORTED, "%s: fused RMSNorm only on the M <= 8 path", me);
     size_t need = align_up((size_t)(g.n_rows[0] + g.n_rows[1] + g.n_rows[2]) * K * 2);
     if (a8 && need < w8a8_scratch_bytes(M, K)) need = w8a8_scratch_bytes(M, K);
     if (!scratch || scratch_bytes < need) return fail(MI_ERR_WORKSPACE, "%s: scratch %zu < required %zu", me, scratch ? scratch_bytes : (size_t)0, need);
@@ -1055,6 +1076,30 @@ static int linear_quant(void* out, int ldo, const void* x, int ldx, int M, int K
   c.deq = (bf16_t*)scratch;
   c.what = {Q::kGemv, "gemm", Q::kDequant};
   return linear_group(g, c, M, (hipStream_t)stream);
+}
+
+// mi_qkv_rope_w8a8 / mi_qkv_rope_w4a8
+template <class Q>
+static int qkv_rope_a8(void* qkv, int ldo, const void* x, int ldx, int T, int D, const void* wq, const void* wk, const void* wv,
+                       const typename Q::scale_t* sq, const typename Q::scale_t* sk, const typename Q::scale_t* sv, int n_heads,
+                       int n_kv_heads, int head_dim, const void* norm_w, float eps, const float* rope_cs, int rope_len,
+                       const int32_t* tok_pos, void* scratch, size_t scratch_bytes, mi_stream_t stream) {
+  const char* me = Q::kQkvA8;
+  if (!qkv || !x || !wq || !wk || !wv || !sq || !sk || !sv || !rope_cs || !tok_pos || T <= 0 || D <= 0 || rope_len <= 0 || n_heads <= 0 ||
+      n_kv_heads <= 0)
+    return fail(MI_ERR_ARG, "%s", me);
+  if (head_dim != 128) return fail(MI_ERR_SHAPE, "head_dim must be 128");
+  LinearGroup g = group_of(D, wq, n_heads * head_dim, wk, n_kv_heads * head_dim, wv, n_kv_heads * head_dim);
+  set_scales(g, Q{}, sq, sk, sv);
+  if (!a8_applicable(Q::kFormat, T, D) || !a8_operands_ok(g, x, ldx))
+    return fail(MI_ERR_UNSUPPORTED, "%s: T = %d, D = %d, ldx = %d (this leaf is the %s only: T >= 256, D %% 128 == 0, D <= 16384, "
+                "ldx %% 8 == 0, %s; fewer rows are %s's)", me, T, D, ldx, Q::kGemmA8, Q::kOperandsA8, Q::kPrior);
+  const size_t need = w8a8_scratch_bytes(T, D);
+  if (!scratch || scratch_bytes < need) return fail(MI_ERR_WORKSPACE, "%s: scratch %zu < required %zu", me, scratch ? scratch_bytes : (size_t)0, need);
+  LinearCall c = {x, ldx, norm_w, eps, qkv, ldo, nullptr, EPI_QKV_ROPE, rope_cs, tok_pos, nullptr, head_dim, nullptr};
+  c.a8 = true; c.x_q = (uint8_t*)scratch; c.s_x = (float*)((char*)scratch + align_up((size_t)T * D));
+  c.what = {Q::kQkvGemv, "qkv gemm", "dequant q|k|v", "attention_norm"};
+  return linear_group(g, c, T, (hipStream_t)stream);
 }
 
 extern "C" {
@@ -1085,7 +1130,7 @@ int mi_act_quant_e4m3(void* xq, float* sx, const void* x, int ldx, int M, int K,
 size_t mi_linear_w8a8_scratch_bytes(int M, int K, const int n_rows[3], int epilogue) {
   if (M <= 0 || K <= 0 || !n_rows) return 0;
   const size_t w8 = mi_linear_w8_scratch_bytes(M, K, n_rows, epilogue);
-  if (!gemm256_w8a8_applicable(M, K)) return w8;
+  if (!a8_applicable(MI_W8_FP8_E4M3, M, K)) return w8;
   return w8 > w8a8_scratch_bytes(M, K) ? w8 : w8a8_scratch_bytes(M, K);  // (either route of such a call: linear_quant)
 }
 
@@ -1099,23 +1144,30 @@ int mi_qkv_rope_w8a8(void* qkv, int ldo, const void* x, int ldx, int T, int D, c
                      const float* sq, const float* sk, const float* sv, int n_heads, int n_kv_heads, int head_dim, const void* norm_w,
                      float eps, const float* rope_cs, int rope_len, const int32_t* tok_pos, void* scratch, size_t scratch_bytes,
                      mi_stream_t stream) {
-  const char* me = "mi_qkv_rope_w8a8";
-  if (!qkv || !x || !wq || !wk || !wv || !sq || !sk || !sv || !rope_cs || !tok_pos || T <= 0 || D <= 0 || rope_len <= 0 || n_heads <= 0 ||
-      n_kv_heads <= 0)
-    return fail(MI_ERR_ARG, "%s", me);
-  if (head_dim != 128) return fail(MI_ERR_SHAPE, "head_dim must be 128");
-  const void* const w3[3] = {wq, wk, wv};
-  if (!gemm256_w8a8_applicable(T, D) || !w8a8_operands_ok(x, ldx, w3))
-    return fail(MI_ERR_UNSUPPORTED, "%s: T = %d, D = %d, ldx = %d (this leaf is the FP8 prefill GEMM only: T >= 256, D %% 128 == 0, D <= 16384, "
-                "ldx %% 8 == 0, x and the weights 16-byte aligned; fewer rows are mi_qkv_rope_kvwrite_w8's)", me, T, D, ldx);
-  const size_t need = w8a8_scratch_bytes(T, D);
-  if (!scratch || scratch_bytes < need) return fail(MI_ERR_WORKSPACE, "%s: scratch %zu < required %zu", me, scratch ? scratch_bytes : (size_t)0, need);
-  LinearGroup g = group_of(D, wq, n_heads * head_dim, wk, n_kv_heads * head_dim, wv, n_kv_heads * head_dim);
-  set_scales(g, QuantW8{}, sq, sk, sv);
-  LinearCall c = {x, ldx, norm_w, eps, qkv, ldo, nullptr, EPI_QKV_ROPE, rope_cs, tok_pos, nullptr, head_dim, nullptr};
-  c.a8 = true; c.x_q = (uint8_t*)scratch; c.s_x = (float*)((char*)scratch + align_up((size_t)T * D));
-  c.what = {"qkv gemv (w8)", "qkv gemm", "dequant q|k|v", "attention_norm"};
-  return linear_group(g, c, T, (hipStream_t)stream);
+  return qkv_rope_a8<QuantW8>(qkv, ldo, x, ldx, T, D, wq, wk, wv, sq, sk, sv, n_heads, n_kv_heads, head_dim, norm_w, eps, rope_cs, rope_len,
+                              tok_pos, scratch, scratch_bytes, stream);
+}
+
+/* MXFP4 x FP8 prefill GEMMs (include/mistral_hip.h: W4A8) */
+size_t mi_linear_w4a8_scratch_bytes(int M, int K, const int n_rows[3], int epilogue) {
+  if (M <= 0 || K <= 0 || !n_rows) return 0;
+  const size_t w4 = mi_linear_w4_scratch_bytes(M, K, n_rows, epilogue);
+  if (!a8_applicable(MI_W4_MXFP4, M, K)) return w4;
+  return w4 > w8a8_scratch_bytes(M, K) ? w4 : w8a8_scratch_bytes(M, K);  // (either route of such a call: linear_quant)
+}
+
+int mi_linear_w4a8(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
+                   int epilogue, const void* residual, const void* norm_w, float eps, const uint8_t* const scale[3], void* scratch,
+                   size_t scratch_bytes, mi_stream_t stream) {
+  return linear_quant<QuantW4>(out, ldo, x, ldx, M, K, w, n_rows, epilogue, residual, norm_w, eps, scale, scratch, scratch_bytes, stream, true);
+}
+
+int mi_qkv_rope_w4a8(void* qkv, int ldo, const void* x, int ldx, int T, int D, const void* wq, const void* wk, const void* wv,
+                     const uint8_t* sq, const uint8_t* sk, const uint8_t* sv, int n_heads, int n_kv_heads, int head_dim, const void* norm_w,
+                     float eps, const float* rope_cs, int rope_len, const int32_t* tok_pos, void* scratch, size_t scratch_bytes,
+                     mi_stream_t stream) {
+  return qkv_rope_a8<QuantW4>(qkv, ldo, x, ldx, T, D, wq, wk, wv, sq, sk, sv, n_heads, n_kv_heads, head_dim, norm_w, eps, rope_cs, rope_len,
+                              tok_pos, scratch, scratch_bytes, stream);
 }
 
 /* weight-only MXFP4 leaves (include/mistral_hip.h: MI_W4_MXFP4) */
@@ -1268,6 +1320,11 @@ size_t mi_workspace_bytes_w8a8(const mi_model_t* model, const mi_w8_model_t* w8,
   return carve(model, T, B, max_cache_size > 0 ? max_cache_size : 1, nullptr, true, kv_e4m3(kv_layout), false, true).total;
 }
 
+size_t mi_workspace_bytes_w4a8(const mi_model_t* model, const mi_w4_model_t* w4, int T, int B, int max_cache_size, int kv_layout) {
+  if (!model || !w4 || T <= 0 || B <= 0 || !kv_layout_ok(kv_layout)) return 0;
+  return carve(model, T, B, max_cache_size > 0 ? max_cache_size : 1, nullptr, true, kv_e4m3(kv_layout), false, true).total;
+}
+
 // what a quantised model must be, by name, before any launch
 static int check_quant(const char* entry, const mi_model_t* m, const QuantModel& q) {
   return with_format(q.entry_format, [&](auto Q) {
@@ -1304,7 +1361,8 @@ static int check_verify(const char* entry, const mi_model_t* m, const mi_batch_t
 // mi_forward, mi_forward_w8 and mi_forward_w4.  q == nullptr: exactly the launches of mi_forward as they always were.
 // vo != nullptr: a verify step (mi_forward_verify) - the T <= 8 launches of a prefill chunk with the verify attention in place of
 // the prefill attention and NO ring write, then argmax, acceptance and the commit of the accepted rows.
-// a8 (mi_forward_w8a8): x_q | s_x behind the workspace, and the FP8 groups of a forward of 256 rows or more take the W8A8 route.
+// a8 (mi_forward_w8a8, mi_forward_w4a8): x_q | s_x behind the workspace, and the quantised groups of a forward of 256 rows or more
+// take the format's FP8-activation route (W8A8 / W4A8).
 static int forward_body(const char* entry, const mi_model_t* m, const QuantModel* q, const mi_batch_t* bt, mi_stream_t stream,
                         const mi_verify_out_t* vo = nullptr, bool a8 = false) {
   MI_TRY(check_model(m));
@@ -1525,6 +1583,12 @@ int mi_forward_w8a8(const mi_model_t* m, const mi_w8_model_t* w8, const mi_batch
   if (!w8) return fail(MI_ERR_ARG, "mi_forward_w8a8: w8 (the FP8 prefill GEMMs read FP8 weights)");
   const QuantModel q = quant_model(w8, nullptr);
   return forward_body("mi_forward_w8a8", m, &q, bt, stream, nullptr, true);
+}
+
+int mi_forward_w4a8(const mi_model_t* m, const mi_w4_model_t* w4, const mi_batch_t* bt, mi_stream_t stream) {
+  if (!w4) return fail(MI_ERR_ARG, "mi_forward_w4a8: w4 (the MXFP4 x FP8 prefill GEMMs read MXFP4 weights)");
+  const QuantModel q = quant_model(nullptr, w4);
+  return forward_body("mi_forward_w4a8", m, &q, bt, stream, nullptr, true);
 }
 
 size_t mi_workspace_bytes_verify(const mi_model_t* model, int quantised, int T, int max_cache_size, int kv_layout) {

@@ -160,6 +160,19 @@ struct GemmW8A8Args {
 bool gemm256_w8a8_applicable(int M, int K);  // M >= 256 && K % 128 == 0 && K <= 16384 (the quantiser's limit): the route's one shape predicate
 hipError_t launch_gemm256_w8a8(const GemmW8A8Args& a, hipStream_t s);
 
+// gemm256_w4a8.hip: the same on MXFP4 weights (prefills of MXFP4 models, opt-in): e2m1 codes meet e4m3 activations on the mixed
+// form of the block-scaled MFMA, which applies the e8m0 block scales itself:
+// out = epilogue((sum_k A_q[m, k] * e2m1(C[n, k]) * 2^(S[n, k / 32] - 127)) * sx[m]).  g.a points to e4m3 bytes (g.lda in bytes),
+// g.w0 / g.w1 / g.w2 to code bytes [rows, K / 2]; sw[i] are the block scale bytes [rows, K / 32] of segment i (SWIGLU: sw[0] =
+// W1's, sw[1] = W3's).  Epilogues and form as above.
+struct GemmW4A8Args {
+  GemmArgs g;
+  const float* sx;
+  const uint8_t* sw[3];
+};
+bool gemm256_w4a8_applicable(int M, int K);  // gemm256_w8a8_applicable: one quantiser, one K tile
+hipError_t launch_gemm256_w4a8(const GemmW4A8Args& a, hipStream_t s);
+
 // ---------------------------------------------------------------------------------------------- attention
 struct AttnDecodeArgs {
   void* out;            // [B, H*Dh]

@@ -164,6 +164,14 @@ _SIGS = {
                                    _vp, C.c_float, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp]),
     "mi_workspace_bytes_w8a8": (C.c_size_t, [C.POINTER(MiModel), C.POINTER(MiW8Model), C.c_int, C.c_int, C.c_int, C.c_int]),
     "mi_forward_w8a8": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiW8Model), C.POINTER(MiBatch), _vp]),
+    # MXFP4 x FP8 prefill GEMMs, W4A8 (additive likewise): per-token e4m3 activations on MXFP4 weights, opt-in
+    "mi_linear_w4a8_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "mi_linear_w4a8": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp), C.POINTER(C.c_int), C.c_int,
+                                 _vp, _vp, C.c_float, C.POINTER(_vp), _vp, C.c_size_t, _vp]),
+    "mi_qkv_rope_w4a8": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int,
+                                   _vp, C.c_float, _vp, C.c_int, _vp, _vp, C.c_size_t, _vp]),
+    "mi_workspace_bytes_w4a8": (C.c_size_t, [C.POINTER(MiModel), C.POINTER(MiW4Model), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mi_forward_w4a8": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiW4Model), C.POINTER(MiBatch), _vp]),
     # speculative greedy decoding (additive likewise): verify steps
     "mi_attn_verify_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "mi_attn_verify": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp,
@@ -352,8 +360,8 @@ def linear_quant(q: QuantFormat, x: torch.Tensor, weights: Sequence[torch.Tensor
                  epilogue: int = EPI_STORE, residual: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None,
                  eps: float = 0.0, out: Optional[torch.Tensor] = None, a8: bool = False) -> torch.Tensor:
     """`linear` on up to three weight-only quantised matrices of format `q` with their scales (mi_linear_w8 / mi_linear_w4).
-    a8 (FP8 only): mi_linear_w8a8 - at M >= 256 rows and K % 128 == 0 the activations are quantised per row and the FP8 GEMM runs."""
-    assert not a8 or q.suffix == "w8", "FP8 activations run on FP8 (e4m3) weights only"
+    a8: mi_linear_w8a8 / mi_linear_w4a8 - at M >= 256 rows and K % 128 == 0 the activations are quantised per row to e4m3 and the
+    format's FP8-activation GEMM runs."""
     assert 1 <= len(weights) <= 3 and len(scales) == len(weights) and x.dim() == 2
     if x.dtype != torch.bfloat16:
         raise NotImplementedError(f"{q.name} weight-only linears take bfloat16 activations (fp16 / fp32 storage is not implemented)")
@@ -392,26 +400,34 @@ def linear_w8a8(x: torch.Tensor, weights: Sequence[torch.Tensor], scales: Sequen
     return linear_quant(W8, x, weights, scales, epilogue, residual, norm_w, eps, out, a8=True)
 
 
-def qkv_rope_w8a8(x: torch.Tensor, weights: Sequence[torch.Tensor], scales: Sequence[torch.Tensor], n_heads: int, n_kv_heads: int,
-                  rope_cs: torch.Tensor, tok_pos: torch.Tensor, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0,
-                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The q|k|v group of an FP8 prefill (mi_qkv_rope_w8a8): rope(bf16((x_q @ [wq; wk; wv]^T) * s_x * s_w)) with RoPE in the GEMM's
-    epilogue, no ring write; T >= 256 rows, K % 128 == 0, heads of 128."""
+def _qkv_rope_a8(q: QuantFormat, x: torch.Tensor, weights: Sequence[torch.Tensor], scales: Sequence[torch.Tensor], n_heads: int,
+                 n_kv_heads: int, rope_cs: torch.Tensor, tok_pos: torch.Tensor, norm_w: Optional[torch.Tensor], eps: float,
+                 out: Optional[torch.Tensor]) -> torch.Tensor:
+    """mi_qkv_rope_w8a8 / mi_qkv_rope_w4a8."""
     assert len(weights) == 3 and len(scales) == 3 and x.dim() == 2 and x.dtype == torch.bfloat16
     T, D = x.shape
-    wb = [_prep_w8(w, sc, D) for w, sc in zip(weights, scales)]
+    wb = [q.prep(w, sc, D) for w, sc in zip(weights, scales)]
     N = sum(w.shape[0] for w in wb)
     assert wb[0].shape[0] == n_heads * 128 and wb[1].shape[0] == n_kv_heads * 128 and wb[2].shape[0] == n_kv_heads * 128
     if out is None:
         out = torch.empty((T, N), dtype=torch.bfloat16, device=x.device)
     nr = (C.c_int * 3)(*[w.shape[0] for w in wb])
-    need = lib().mi_linear_w8a8_scratch_bytes(T, D, nr, EPI_STORE)
+    L, entry = lib(), f"mi_qkv_rope_{q.suffix}a8"
+    need = getattr(L, f"mi_linear_{q.suffix}a8_scratch_bytes")(T, D, nr, EPI_STORE)
     scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=x.device)
-    check(lib().mi_qkv_rope_w8a8(dev_ptr(out), out.stride(0), dev_ptr(x), x.stride(0), T, D, *[dev_ptr(w, torch.uint8) for w in wb],
-                                 *[dev_ptr(s, torch.float32) for s in scales], n_heads, n_kv_heads, 128, dev_ptr(norm_w), float(eps),
-                                 dev_ptr(rope_cs, torch.float32), rope_cs.shape[0], dev_ptr(tok_pos, torch.int32), scratch.data_ptr(), need,
-                                 stream_ptr(x.device)), "mi_qkv_rope_w8a8")
+    check(getattr(L, entry)(dev_ptr(out), out.stride(0), dev_ptr(x), x.stride(0), T, D, *[dev_ptr(w, torch.uint8) for w in wb],
+                            *[dev_ptr(s, q.scale_dtype) for s in scales], n_heads, n_kv_heads, 128, dev_ptr(norm_w), float(eps),
+                            dev_ptr(rope_cs, torch.float32), rope_cs.shape[0], dev_ptr(tok_pos, torch.int32), scratch.data_ptr(), need,
+                            stream_ptr(x.device)), entry)
     return out
+
+
+def qkv_rope_w8a8(x: torch.Tensor, weights: Sequence[torch.Tensor], scales: Sequence[torch.Tensor], n_heads: int, n_kv_heads: int,
+                  rope_cs: torch.Tensor, tok_pos: torch.Tensor, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The q|k|v group of an FP8 prefill (mi_qkv_rope_w8a8): rope(bf16((x_q @ [wq; wk; wv]^T) * s_x * s_w)) with RoPE in the GEMM's
+    epilogue, no ring write; T >= 256 rows, K % 128 == 0, heads of 128."""
+    return _qkv_rope_a8(W8, x, weights, scales, n_heads, n_kv_heads, rope_cs, tok_pos, norm_w, eps, out)
 
 
 def act_quant_e4m3(x: torch.Tensor, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0):
@@ -433,6 +449,23 @@ def linear_w4(x: torch.Tensor, weights: Sequence[torch.Tensor], scales: Sequence
     scales[i] uint8 e8m0 block scales [n_i, K / 32]; STORE / RESIDUAL / SWIGLU.  M <= 8: the MXFP4 GEMV; above: dequantise into a
     per-call scratch + the bf16 GEMM."""
     return linear_quant(W4, x, weights, scales, epilogue, residual, norm_w, eps, out)
+
+
+def linear_w4a8(x: torch.Tensor, weights: Sequence[torch.Tensor], scales: Sequence[torch.Tensor], epilogue: int = EPI_STORE,
+                residual: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`linear_w4` with FP8 activations where they apply (mi_linear_w4a8): at M >= 256 rows and K % 128 == 0 the rows of x (after
+    the RMSNorm, when norm_w is given) are quantised per row to e4m3 and contracted with the e2m1 codes on the mixed FP4 x FP8 MFMA,
+    which applies the block scale bytes itself; any other shape is `linear_w4`, bit for bit."""
+    return linear_quant(W4, x, weights, scales, epilogue, residual, norm_w, eps, out, a8=True)
+
+
+def qkv_rope_w4a8(x: torch.Tensor, weights: Sequence[torch.Tensor], scales: Sequence[torch.Tensor], n_heads: int, n_kv_heads: int,
+                  rope_cs: torch.Tensor, tok_pos: torch.Tensor, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The q|k|v group of an MXFP4 prefill with the flag (mi_qkv_rope_w4a8): rope(bf16((x_q @ deq([wq; wk; wv])^T) * s_x)) with RoPE
+    in the GEMM's epilogue, no ring write; T >= 256 rows, K % 128 == 0, heads of 128."""
+    return _qkv_rope_a8(W4, x, weights, scales, n_heads, n_kv_heads, rope_cs, tok_pos, norm_w, eps, out)
 
 
 def lora_linear(x: torch.Tensor, weights: Sequence[torch.Tensor], lora_a: Sequence[Optional[torch.Tensor]],

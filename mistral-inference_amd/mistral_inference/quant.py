@@ -33,7 +33,18 @@ with the sum in fp32 on the FP8 MFMA and no dequantisation pass.  In front of q|
 of the RMSNorm.  Activations keep three mantissa bits: on inputs that e4m3 holds exactly the route is lossless, on real activations
 it is a different (coarser) model than the weight-only one, and nobody claims model quality for it - it ships with its measured
 speed (README) and is off unless asked for.  Every other shape - decode steps, verify steps, short chunks - takes the weight-only
-routes above, bit for bit."""
+routes above, bit for bit.
+
+MXFP4 x FP8 prefill GEMMs (`prefill_w4a8=True`, MXFP4 weights only, opt-in): the same on an MXFP4 model.  A linear of the same
+shapes quantises its input rows by the same rule (s_x, x_q as above) and contracts them with the e2m1 codes on the mixed form of
+the block-scaled MFMA, which takes the checkpoint's e8m0 bytes as its block scales:
+
+    y[t, r] = bf16((sum_k e4m3(x_q[t, k]) * e2m1(c[r, k]) * 2^(qscale_weight[r, k / 32] - 127)) * s_x[t])   (csrc/gemm256_w4a8.hip)
+
+with the sum in fp32 and no dequantisation pass.  On activations that e4m3 holds exactly under the row scale this is the
+weight-only route up to fp32 summation order (lossless); on real activations it is a coarser model, nobody claims model quality for
+it, and it is off unless asked for.  For scale bytes below 3 the weight-only route's bf16 image holds subnormals, which it may
+flush and this route does not.  Every other shape takes the weight-only MXFP4 routes, bit for bit."""
 import json
 import re
 from pathlib import Path
@@ -65,6 +76,8 @@ _REFUSALS = {
     "pth": "{name} weight-only models load from consolidated.safetensors (a .pth checkpoint is not implemented)",
     "prefill_fp8": ("prefill_fp8=True on {what} is not implemented: the FP8 prefill GEMMs read FP8 (e4m3) weights beside bfloat16 "
                     "activations (quantize=\"fp8_e4m3\", or a folder that quantize_checkpoint wrote, with bfloat16 storage)"),
+    "prefill_w4a8": ("prefill_w4a8=True on {what} is not implemented: the MXFP4 x FP8 prefill GEMMs read MXFP4 weights beside bfloat16 "
+                     "activations (quantize=\"mxfp4\", or a folder that quantize_checkpoint wrote, with bfloat16 storage)"),
 }
 MXFP4_BLOCK = 32
 E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # magnitude of code & 7; code & 8 is the sign
@@ -105,6 +118,20 @@ def refuse_prefill_fp8(args, dtype: Optional[torch.dtype]) -> None:
     else:
         return
     raise NotImplementedError(_REFUSALS["prefill_fp8"].format(what=what))
+
+
+def refuse_prefill_w4a8(args, dtype: Optional[torch.dtype]) -> None:
+    """`prefill_w4a8=True` on a model whose weights are not MXFP4 (bf16, FP8) or whose storage is not bfloat16, by name."""
+    qz = args.quantization
+    if qz is None:
+        what = "a model without MXFP4 weights" if dtype in (None, torch.bfloat16) else f"a model with {dtype} storage"
+    elif qz.qformat_weight != QFORMAT_MXFP4:
+        what = f"{quantized_linear_cls(qz).name} weights"
+    elif dtype not in (None, torch.bfloat16):
+        what = f"{dtype} storage"
+    else:
+        return
+    raise NotImplementedError(_REFUSALS["prefill_w4a8"].format(what=what))
 
 
 def is_quantized_linear_key(key: str) -> bool:
@@ -169,6 +196,7 @@ class QuantLinear(nn.Module):
     k_multiple: int           # what in_features (and the model's dim / hidden_dim) must be a multiple of
     hip: _hip.QuantFormat     # the format's entry points of the library
     prefill_fp8 = False       # FP8 linears: Transformer.prefill_fp8 sets it on every linear of the model (mi_linear_w8a8)
+    prefill_w4a8 = False      # MXFP4 linears: Transformer.prefill_w4a8 likewise (mi_linear_w4a8)
     quantize = None           # staticmethod: bf16 [out, in] -> (weight, scale) as a checkpoint stores them
 
     def __init__(self, in_features: int, out_features: int, bias: bool = False):
@@ -197,7 +225,7 @@ def linear_quant(x: torch.Tensor, mods: Sequence[QuantLinear], epilogue: int = _
                  norm_w: Optional[torch.Tensor] = None, eps: float = 0.0) -> torch.Tensor:
     """`_hip.linear` over up to three quantised linears of one format that share an input (q|k|v; SWIGLU: w1, w3)."""
     return _hip.linear_quant(mods[0].hip, x, [m.weight for m in mods], [m.qscale_weight for m in mods], epilogue, residual, norm_w, eps,
-                             a8=bool(mods[0].prefill_fp8))
+                             a8=bool(mods[0].prefill_w4a8 if mods[0].hip.suffix == "w4" else mods[0].prefill_fp8))
 
 
 class Fp8Linear(QuantLinear):

@@ -34,7 +34,7 @@ from .cache import BatchMetadata, BufferCache
 from .lora import LoRALinear, check_rank
 from .model import ModelBase
 from .quant import (QSCALE_ACT_KEY, QSCALE_KEY, QuantLinear, check_quantize_arg, quantize_state_tensor, quantized_linear_cls,
-                    refusal, refuse_prefill_fp8, refuse_quant_combinations)
+                    refusal, refuse_prefill_fp8, refuse_prefill_w4a8, refuse_quant_combinations)
 from .rope import precompute_freqs_cis
 from .transformer_layers import LORA_MOE_REFUSAL, RMSNorm, TransformerBlock
 from .vision_encoder import PATCH_MERGE, PatchMerger, VisionLanguageAdapter, VisionTransformer
@@ -286,6 +286,8 @@ class HipStackBackend:
             need = _hip.lib().mi_workspace_bytes_generic(C.byref(m), T, self.dtype_code)
         elif self._quant is not None and model.prefill_fp8:  # (+ the e4m3 activation rows and their scales)
             need = _hip.lib().mi_workspace_bytes_w8a8(C.byref(m), C.byref(self._quant[0]), T, B, max_w, kv_layout)
+        elif self._quant is not None and model.prefill_w4a8:  # (MXFP4 weights: the same x_q | s_x)
+            need = _hip.lib().mi_workspace_bytes_w4a8(C.byref(m), C.byref(self._quant[0]), T, B, max_w, kv_layout)
         else:  # (rings of e4m3 bytes add the prefill scratch of one layer's dequantised rings; otherwise mi_workspace_bytes[_w8 / _w4])
             need = _hip.lib().mi_workspace_bytes_kv(C.byref(m), 1 if self._quant is not None else 0, T, B, max_w, kv_layout)
         ws = self._workspace
@@ -356,6 +358,8 @@ class HipStackBackend:
             qm, _, forward, name = self._quant
             if model.prefill_fp8:  # (FP8 weights: the setter has checked; T < 256 is launch for launch mi_forward_w8)
                 forward, name = _hip.lib().mi_forward_w8a8, "mi_forward_w8a8"
+            elif model.prefill_w4a8:  # (MXFP4 weights likewise; T < 256 is launch for launch mi_forward_w4)
+                forward, name = _hip.lib().mi_forward_w4a8, "mi_forward_w4a8"
             _hip.check(forward(C.byref(m), C.byref(qm), C.byref(bt), _hip.stream_ptr(h.device)), name)
         else:
             _hip.check(_hip.lib().mi_forward(C.byref(m), C.byref(bt), _hip.stream_ptr(h.device)), "mi_forward")
@@ -416,6 +420,7 @@ class Transformer(ModelBase):
         self._backend = backend if backend is not None else HipStackBackend()
         self._graphed: Optional[dict] = None  # state of an active graphed_decode() context
         self._prefill_fp8 = False
+        self._prefill_w4a8 = False
         self.lora_slots = 1                   # adapter sets per LoRA linear (set_lora_slots)
         self._adapters_pinned = False         # between pin_adapters() and unpin_adapters(): forward() leaves the slots alone
         self._pp_comm: Optional[Any] = None   # pipeline transport (distributed.pipeline_comm), created at first use
@@ -764,6 +769,24 @@ class Transformer(ModelBase):
                 mod.prefill_fp8 = on
 
     @property
+    def prefill_w4a8(self) -> bool:
+        """MXFP4 x FP8 prefill GEMMs (quant.py): `prefill_fp8` for a model with MXFP4 weights - forwards of 256 rows or more quantise
+        their activations per token and run the four linear groups of every layer on the mixed FP4 x FP8 MFMA, the block scales
+        applied by the instruction.  Settable between generations; MXFP4 weights only."""
+        return self._prefill_w4a8
+
+    @prefill_w4a8.setter
+    def prefill_w4a8(self, on: bool) -> None:
+        on = bool(on)
+        if on:
+            params = next(self.parameters(), None)
+            refuse_prefill_w4a8(self.args, self.dtype if params is not None and not params.is_meta else None)
+        self._prefill_w4a8 = on
+        for mod in self.modules():  # a block driven module by module takes the route the runner takes
+            if isinstance(mod, QuantLinear):
+                mod.prefill_w4a8 = on
+
+    @property
     def supports_prompt_logprobs(self) -> bool:
         """generate() reduces a prompt chunk's logits inside the LM head GEMM (prompt_logprobs) on the tuned bf16 path; models
         on the generic kernels return [T, vocab] logits from forward() and generate() takes its log-softmax."""
@@ -917,7 +940,7 @@ class Transformer(ModelBase):
     def from_folder(folder: Union[Path, str], max_batch_size: int = 1, num_pipeline_ranks: int = 1,
                     device: Union[torch.device, str] = "cuda", dtype: Optional[torch.dtype] = None,
                     softmax_fp32: bool = True, backend: Optional[Any] = None, quantize: Optional[str] = None,
-                    prefill_fp8: bool = False) -> "Transformer":
+                    prefill_fp8: bool = False, prefill_w4a8: bool = False) -> "Transformer":
         """params.json + exactly one of consolidated.00.pth / consolidated.safetensors (reference
         transformer.py:297-338).  With safetensors only this rank's tensors are read, straight to `device`
         (the reference loads the whole file to the host on every rank).
@@ -927,7 +950,8 @@ class Transformer(ModelBase):
         quantize="fp8_e4m3" / "mxfp4" does the same to a bf16 safetensors folder while it loads: each linear is quantised on the
         device as it arrives, so the bf16 model is never resident.
 
-        prefill_fp8=True (FP8 e4m3 weights only, whether quantised here or in the folder): `model.prefill_fp8`, the FP8 prefill GEMMs."""
+        prefill_fp8=True (FP8 e4m3 weights only, whether quantised here or in the folder): `model.prefill_fp8`, the FP8 prefill GEMMs.
+        prefill_w4a8=True (MXFP4 weights only, likewise): `model.prefill_w4a8`, the MXFP4 x FP8 prefill GEMMs."""
         folder = Path(folder)
         check_quantize_arg(quantize)
         with open(folder / "params.json", "r") as f:
@@ -940,6 +964,8 @@ class Transformer(ModelBase):
             model_args.quantization = QuantizationArgs(quantize)
         if prefill_fp8:
             refuse_prefill_fp8(model_args, dtype)
+        if prefill_w4a8:
+            refuse_prefill_w4a8(model_args, dtype)
         refuse_quant_combinations(model_args, dtype)  # before anything is read from disk
         pipeline_rank = torch.distributed.get_rank() if num_pipeline_ranks > 1 else 0
         with torch.device("meta"):
@@ -954,7 +980,7 @@ class Transformer(ModelBase):
                 raise NotImplementedError(refusal("pth", model_args.quantization))
             loaded = torch.load(str(pt_file), mmap=True)
             model.load_state_dict(loaded, assign=True, strict=True)
-            return model.to(device=device, dtype=dtype)  # (never an FP8 model: prefill_fp8 was refused above)
+            return model.to(device=device, dtype=dtype)  # (never a quantised model: prefill_fp8 / prefill_w4a8 were refused above)
         wanted = set(model.state_dict().keys())
         # a LoRA model takes both key forms (lora.py:76-89): `<name>.linear.weight` (+ optional `<name>.lora_A/B.weight`), or the
         # plain `<name>.weight` of a base checkpoint, which LoRALinear loads with zero adapters
@@ -990,6 +1016,7 @@ class Transformer(ModelBase):
         model._weights_changed()
         model = model.to(device=device, dtype=dtype)
         model.prefill_fp8 = prefill_fp8
+        model.prefill_w4a8 = prefill_w4a8
         return model
 
     def _weights_changed(self) -> None:
