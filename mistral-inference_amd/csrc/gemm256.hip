@@ -9,24 +9,17 @@
 //
 // Why a second tile shape: the 128x128 kernel moves 32 KiB of operands through LDS per 128x128x64 MACs and is bound by
 // LDS bandwidth (DMA writes ~64-85 B/clk + fragment reads 256 B/clk against 16 clk per MFMA): ~37 % of the MFMA peak.
-// 256x256 halves the LDS bytes per flop.  Structure (cdna_hip_programming.md section 5, "256^2 8-phase template",
-// written from its description):
-//   * 8 waves = 2 (M) x 4 (N); a wave owns 64 rows of each 128-row A half and 32 columns of each 128-column B half,
-//     i.e. four 64x32 quadrants (ha, hb), 16 MFMA 16x16x32 each per K tile;
-//   * LDS = 2 stages x {A0, A1, B0, B1} x 16 KiB half tiles (128 rows x 128 B, 16-byte slot XOR-swizzled by row & 7,
-//     the swizzle applied on the DMA's SOURCE address);
-//   * one K tile = 4 phases, one quadrant each.  A phase (a) reads the fragments it is missing, (b) re-stages ONE
-//     half tile whose last reader finished a phase earlier (2 `global_load_lds_dwordx4` per lane), (c) lgkmcnt(0) +
-//     raw s_barrier, (d) 16 MFMAs.  The DMAs are never drained inside the loop: the single `s_waitcnt vmcnt(6)` per
-//     K tile (phase 4) retires the NEXT tile's four halves and leaves the three halves issued after them in flight
-//     across the barrier.
-// Hazards, by construction:  RAW - tile t+1's halves are waited for (vmcnt) by every wave BEFORE phase 4's barrier and
-// first read AFTER it.  WAR - a half is re-staged in the phase after the one whose barrier followed its last reads
-// (lgkmcnt(0) precedes every barrier).
+// 256x256 halves the LDS bytes per flop.  The structure - wave layout, tile map, the four-phase K loop with its hazard
+// argument, the 16-bit-output epilogue - is gemm256_core.cuh's, shared with the two FP8-activation kernels.  This file's own:
+//   * the operands: 16-bit elements, K tile of 64, two MFMA 16x16x32 (k steps) per (row fragment, column fragment), 16 per
+//     quadrant and K tile; lane l holds row l & 15, k = (l >> 4) * 8 .. + 8 of each 32-wide k step;
+//   * the LDS image: 2 stages x {A0, A1, B0, B1} x 16 KiB half tiles (128 rows x 128 B, 16-byte slot XOR-swizzled by row & 7 on
+//     the DMA's SOURCE address), 2 `global_load_lds_dwordx4` per wave and half: the loop's counted wait is vmcnt(6);
+//   * the token-grouped MoE form, the half-height tile with its own loop (MH = 1, below), the LOGITS / LOGPROB epilogues, and
+//     the build-time experiment switches.
 #include <cstdlib>
 
-#include "common.cuh"
-#include "kernels.h"
+#include "gemm256_core.cuh"
 
 // A second compile of this file with -DG256_F16=1 (build_native.py: gemm256_f16.o) is the SAME kernel for fp16 storage - the
 // data movement of two 16-bit types is identical; what changes is the element E (common.cuh): the MFMA opcode and the
@@ -68,6 +61,7 @@ extern "C" int mi_debug_gemm_clock(unsigned long long* out2) {
 #endif
 
 namespace {
+using namespace gemm256_core;
 
 constexpr int BK = 64;
 constexpr int HALF_BYTES = 128 * BK * 2;     // 16 KiB: 128 rows x 128 B
@@ -81,32 +75,55 @@ constexpr int LDS_BYTES = 2 * STAGE_BYTES;   // 128 KiB
 constexpr int STAGE_BYTES_H = 3 * HALF_BYTES;
 constexpr int LDS_BYTES_H = 3 * STAGE_BYTES_H;  // 144 KiB
 
-__device__ __forceinline__ void dma16(const bf16_t* src, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
+// The operands of gemm256_core::k_loop (MH = 2) and of the half-height loop below (MH = 1, whose stage is A0 B0 B1: half
+// indices 0, 1, 2).  SWAP: MFMAs issued W-fragment x A-fragment (transposed 16x16 result tiles, see the shared epilogue).
+template <int MH, bool SWAP>
+struct Ops {
+  static constexpr int STG = (MH + 2) * HALF_BYTES;  // bytes per stage: the A halves, B0, B1
+  static constexpr int dmas(int) { return 2; }
+  const char* src[MH + 2][2];  // [half][piece]
+  char* my_piece;              // this wave's two 1-KiB pieces inside any half tile of stage 0
+  const char* smem;
+  int a_off, b_off, sw0, sw1;  // fragment addressing
+  f32x4 acc[MH][2][4][2];
+  typename E::x8 af[2][4];     // [k step][row fragment] of the A half in use
+  typename E::x8 bf[2][2][2];  // [B half][k step][column fragment]
 
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// s_barrier is not a memory operation for the compiler: the asm statements (memory clobber) on both sides keep every
-// LDS read and every DMA on its side of the barrier.
-__device__ __forceinline__ void raw_barrier() {
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ void lds_reads_done_then_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  raw_barrier();
-}
+  static __device__ __forceinline__ typename E::x8 frag(const char* p) { return __builtin_bit_cast(typename E::x8, *reinterpret_cast<const u32x4*>(p)); }
+  __device__ __forceinline__ void stage(int half, int kt, int st) {
+    char* dst = my_piece + st * STG + half * HALF_BYTES;
+    dma16(src[half][0] + (size_t)kt * (BK * 2), dst);
+    dma16(src[half][1] + (size_t)kt * (BK * 2), dst + 1024);
+  }
+  __device__ __forceinline__ void read_a(int ha, int st) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      af[0][i] = frag(smem + st * STG + ha * HALF_BYTES + a_off + i * 2048 + sw0);
+      af[1][i] = frag(smem + st * STG + ha * HALF_BYTES + a_off + i * 2048 + sw1);
+    }
+  }
+  __device__ __forceinline__ void read_b(int hb, int st) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      bf[hb][0][j] = frag(smem + st * STG + hb * HALF_BYTES + b_off + j * 2048 + sw0);
+      bf[hb][1][j] = frag(smem + st * STG + hb * HALF_BYTES + b_off + j * 2048 + sw1);
+    }
+  }
+  __device__ __forceinline__ void mfma_quad(int ha, int hb) {
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          acc[ha][hb][i][j] = SWAP ? E::mfma16(bf[hb][ks][j], af[ks][i], acc[ha][hb][i][j]) : E::mfma16(af[ks][i], bf[hb][ks][j], acc[ha][hb][i][j]);
+  }
+};
 
 template <int EPI, bool STAGGER, int MH = 2>
 __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int NOUT = (EPI == GEMM_SWIGLU) ? 128 : 256;  // output columns per block
-  constexpr int MROWS = MH * 128;                         // output rows per block
-  constexpr int STG = (MH + 2) * HALF_BYTES;              // bytes per stage: the A halves, B0, B1
+  constexpr int MROWS = MH * 128;  // output rows per block
   static_assert(MH == 2 || (EPI == GEMM_STORE || EPI == GEMM_RESIDUAL), "half-height tiles: store / residual epilogues");
   // bf16 outputs: MFMAs issued as W-fragment x A-fragment (transposed 16x16 result tiles, see the epilogue); fp32
   // logits: A x W, whose 4-byte stores already cover 64-byte row segments and measured faster than 16-byte ones.
@@ -119,16 +136,11 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmArgs g) {
   const unsigned long long clk_c0 = __builtin_readcyclecounter(), clk_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
 
-  // ---- block -> tile.  Block b runs on XCD b % 8; a 4 (m) x 8 (n) supertile = the 32 blocks one XCD runs at a time
-  // stays on one XCD so that its blocks share 4 A panels and 8 W panels in that XCD's L2 (guide T1; speed only).
+  // ---- block -> tile (gemm256_core)
   const bool grouped = g.tile_tab != nullptr;  // token-grouped MoE form: m-tiles come from the device tile table
-  const int m_tiles = grouped ? g.max_m_tiles : (g.M + MROWS - 1) / MROWS, n_tiles = (g.N + NOUT - 1) / NOUT;
-  const int MS = (m_tiles + 3) >> 2, NS = (n_tiles + 7) >> 3;
-  const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-  const int st = (q >> 5) * 8 + xcd, wi = q & 31;
-  if (st >= MS * NS) return;
-  const int m_tile = (st % MS) * 4 + (wi & 3), n_tile = (st / MS) * 8 + (wi >> 2);
-  if (m_tile >= m_tiles || n_tile >= n_tiles) return;
+  const int n_tiles = col_tiles(g.N, EPI);
+  int m_tile, n_tile;
+  if (!tile_of_block(grouped ? g.max_m_tiles : (g.M + MROWS - 1) / MROWS, n_tiles, m_tile, n_tile)) return;
   int row0, rows_valid;
   const bf16_t *w0 = g.w0, *w1 = g.w1;
   if (grouped) {  // one tile of one expert: {expert, first compact row, valid rows (<= 256)}
@@ -143,43 +155,33 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmArgs g) {
     rows_valid = min(MROWS, g.M - row0);
   }
 
-  // ---- DMA sources.  One instruction fills 8 consecutive 128-B rows of a half tile; wave w, piece j covers rows
-  // (2w + j) * 8 .. + 8; lane l lands at (row + (l >> 3), slot l & 7) and fetches global slot (l & 7) ^ (row & 7).
-  const int sslot = (lane & 7) ^ ((lane >> 3) & 7);
-  const bf16_t* src[MH + 2][2];  // halves of a stage: A0 (A1) B0 B1
+  // ---- DMA sources (gemm256_core: both operands are 16-KiB halves).  Rows at or past the tile's valid rows / N are clamped.
+  Ops<MH, kSwap> op;
 #pragma unroll
   for (int h = 0; h < 2; ++h)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      const int r = (wid * 2 + j) * 8 + (lane >> 3);
-      if (h < MH) {
-        int m = row0 + min(h * 128 + r, rows_valid - 1);
-        if (g.a_gather) m = g.a_gather[m];
-        src[h][j] = g.a + (size_t)m * g.lda + sslot * 8;
-      }
+      if (h < MH) op.src[h][j] = a_half_src<bf16_t, true>(g, row0, rows_valid, h, wid, j, lane);
+      const int r = piece_row(wid, j, lane);
+      const bf16_t* w;
       if (EPI == GEMM_SWIGLU) {
         const int n = min(n_tile * 128 + r, g.N - 1);
-        src[MH + h][j] = (h == 0 ? w0 : w1) + (size_t)n * g.K + sslot * 8;
+        w = (h == 0 ? w0 : w1) + (size_t)n * g.K;
       } else {
         const int n = min(n_tile * 256 + h * 128 + r, g.N - 1);
-        src[MH + h][j] = (grouped ? w0 + (size_t)n * g.K : seg_row(g, n)) + sslot * 8;
+        w = grouped ? w0 + (size_t)n * g.K : seg_row(g, n);
       }
+      op.src[MH + h][j] = reinterpret_cast<const char*>(w) + src_slot_bytes(lane);
     }
-  char* const my_piece = smem + wid * 2048;  // this wave's two 1-KiB pieces inside any half tile
-#define STAGE_HALF(HALF, KT, STAGE)                                                              \
-  do {                                                                                           \
-    char* dst_ = my_piece + (STAGE) * STG + (HALF) * HALF_BYTES;                                 \
-    dma16(src[HALF][0] + (size_t)(KT) * BK, dst_);                                               \
-    dma16(src[HALF][1] + (size_t)(KT) * BK, dst_ + 1024);                                        \
-  } while (0)
-
+  op.my_piece = smem + wid * 2048;
+  op.smem = smem;
   // ---- fragment addressing (MFMA 16x16x32: lane holds row lane & 15, k = (lane >> 4) * 8 .. + 8 of each 32-wide k step)
   const int fq = lane >> 4;
-  const int sw0 = ((fq) ^ (lane & 7)) << 4, sw1 = ((4 + fq) ^ (lane & 7)) << 4;
-  const int a_off = (wr * 64 + (lane & 15)) * 128;
-  const int b_off = MH * HALF_BYTES + (wc * 32 + (lane & 15)) * 128;
-
-  f32x4 acc[MH][2][4][2];
+  op.sw0 = ((fq) ^ (lane & 7)) << 4;
+  op.sw1 = ((4 + fq) ^ (lane & 7)) << 4;
+  op.a_off = (wr * 64 + (lane & 15)) * 128;
+  op.b_off = MH * HALF_BYTES + (wc * 32 + (lane & 15)) * 128;
+  f32x4 (&acc)[MH][2][4][2] = op.acc;
 #pragma unroll
   for (int a = 0; a < MH; ++a)
 #pragma unroll
@@ -191,52 +193,20 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmArgs g) {
 #if G256_PIPE || G256_BAL || G256_SPLIT || G256_ABL || G256_PRIO || !G256_DMA_AFTER
 #include "../../scripts/probes/gemm256_experiments.inc"  // probe builds only (scripts/build_variants.py gemm): never part of the shipped library
 #else
-  E::x8 af[2][4];             // [k step][row fragment] of the A half in use
-  E::x8 b0x[2][2], b1[2][2];  // [k step][column fragment] of B half 0 / 1
-#define LDS_FRAG(ADDR) __builtin_bit_cast(E::x8, *reinterpret_cast<const u32x4*>(ADDR))
-#define READ_A(HA, SB)                                                               \
-  _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                    \
-    af[0][i] = LDS_FRAG((SB) + (HA) * HALF_BYTES + a_off + i * 2048 + sw0);          \
-    af[1][i] = LDS_FRAG((SB) + (HA) * HALF_BYTES + a_off + i * 2048 + sw1);          \
-  }
-#define READ_B(DST, HB, SB)                                                          \
-  _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                    \
-    DST[0][j] = LDS_FRAG((SB) + (HB) * HALF_BYTES + b_off + j * 2048 + sw0);         \
-    DST[1][j] = LDS_FRAG((SB) + (HB) * HALF_BYTES + b_off + j * 2048 + sw1);         \
-  }
-#define SEGMENT_END()                          \
-  do {                                         \
-    lds_reads_done_then_barrier();             \
-    __builtin_amdgcn_sched_barrier(0);         \
-  } while (0)
-#define MFMA_END()                             \
-  do {                                         \
-    if (STAGGER) {                             \
-      __builtin_amdgcn_sched_barrier(0);       \
-      raw_barrier();                           \
-      __builtin_amdgcn_sched_barrier(0);       \
-    }                                          \
-  } while (0)
-#define MFMA_QUAD(HA, HB, BF)                                                                                   \
-  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                              \
-  _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                 \
-  _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                                 \
-    acc[HA][HB][i][j] = kSwap ? E::mfma16(BF[ks][j], af[ks][i], acc[HA][HB][i][j]) \
-                              : E::mfma16(af[ks][i], BF[ks][j], acc[HA][HB][i][j]);
-
   const int nk = g.K / BK;
   if constexpr (MH == 1) {
-    // ---- half-height tile: stage = {A0, B0, B1} (half indices 0, 1, 2), three stages, tile t in stage t % 3.  Tile
-    // t + 2 is staged during tile t into the stage tile t - 1 was read from (its last reads - by the group that runs one
-    // barrier behind - ended with the barrier before this tile's first read segment), and is waited for one tile later
-    // (vmcnt(6): everything but the six pieces issued since), two barriers before its first read.
-    STAGE_HALF(0, 0, 0);
-    STAGE_HALF(1, 0, 0);
-    STAGE_HALF(2, 0, 0);
+    // ---- half-height tile: stage = {A0, B0, B1} (half indices 0, 1, 2), three stages, tile t in stage t % 3, two phases per K
+    // tile with gemm256_core's segments and stagger.  Tile t + 2 is staged during tile t into the stage tile t - 1 was read from
+    // (its last reads - by the group that runs one barrier behind - ended with the barrier before this tile's first read
+    // segment), and is waited for one tile later (vmcnt(6): everything but the six pieces issued since), two barriers before its
+    // first read.
+    op.stage(0, 0, 0);
+    op.stage(1, 0, 0);
+    op.stage(2, 0, 0);
     if (nk > 1) {
-      STAGE_HALF(0, 1, 1);
-      STAGE_HALF(1, 1, 1);
-      STAGE_HALF(2, 1, 1);
+      op.stage(0, 1, 1);
+      op.stage(1, 1, 1);
+      op.stage(2, 1, 1);
       wait_vm<6>();
     } else {
       wait_vm<0>();
@@ -245,98 +215,33 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmArgs g) {
     if (STAGGER && wr == 1) raw_barrier();
     int s = 0, s2 = 2;  // stage of tile t, of tile t + 2
     for (int t = 0; t < nk; ++t) {
-      const char* sb = smem + s * STG;
       const bool more1 = t + 1 < nk, more2 = t + 2 < nk;
       // phase 1: quadrant (0, 0)
-      READ_B(b0x, 0, sb)
-      READ_A(0, sb)
-      if (more2) STAGE_HALF(0, t + 2, s2);
-      SEGMENT_END();
-      MFMA_QUAD(0, 0, b0x)
-      MFMA_END();
+      op.read_b(0, s);
+      op.read_a(0, s);
+      if (more2) op.stage(0, t + 2, s2);
+      segment_end();
+      op.mfma_quad(0, 0);
+      mfma_end<STAGGER>();
       // phase 2: quadrant (0, 1); retire tile t + 1
-      READ_B(b1, 1, sb)
+      op.read_b(1, s);
       if (more2) {
-        STAGE_HALF(1, t + 2, s2);
-        STAGE_HALF(2, t + 2, s2);
+        op.stage(1, t + 2, s2);
+        op.stage(2, t + 2, s2);
         wait_vm<6>();
       } else if (more1) {
         wait_vm<0>();
       }
-      SEGMENT_END();
-      MFMA_QUAD(0, 1, b1)
-      MFMA_END();
+      segment_end();
+      op.mfma_quad(0, 1);
+      mfma_end<STAGGER>();
       s = (s == 2) ? 0 : s + 1;
       s2 = (s2 == 2) ? 0 : s2 + 1;
     }
     if (STAGGER && wr == 0) raw_barrier();
   } else {
-  // ---- prologue: all of tile 0, then A0 B0 B1 of tile 1 (its A1 is staged by phase 1 of tile 0)
-  STAGE_HALF(0, 0, 0);
-  STAGE_HALF(2, 0, 0);
-  STAGE_HALF(3, 0, 0);
-  STAGE_HALF(1, 0, 0);
-  if (nk > 1) {
-    STAGE_HALF(0, 1, 1);
-    STAGE_HALF(2, 1, 1);
-    STAGE_HALF(3, 1, 1);
-    wait_vm<6>();
-  } else {
-    wait_vm<0>();
+    k_loop<STAGGER>(op, nk, wr);
   }
-  raw_barrier();
-  // Every phase is two segments, [fragment reads + one half tile's DMA] | barrier | [16 MFMAs] | barrier.  The wr = 1 waves
-  // run one barrier behind the wr = 0 waves (each SIMD hosts one wave of either group), so while one wave of a SIMD issues
-  // its MFMAs the other one does its LDS reads, and the matrix pipe never waits for a read segment.  The hazard rules of
-  // the header still hold with one barrier of slack less: a half tile is re-staged in the read segment after the one (two
-  // barriers earlier for the same wave, one for the other group) in which it was last read, and tile t + 1 is waited for
-  // in phase 4's first segment and read two barriers later.  Inside a read segment the fragment reads come FIRST: their
-  // latency then runs under the ~120 cycles that the DMA's issue takes (the group's four waves queue their 1-KiB pieces
-  // on the CU's one vector-memory path right after the barrier): -9 % cycles per K tile, profiles/EXPERIMENTS.md.
-  if (STAGGER && wr == 1) raw_barrier();
-  for (int t = 0; t < nk; ++t) {
-    const int s = t & 1;
-    const char* sb = smem + s * STAGE_BYTES;
-    const bool more1 = t + 1 < nk, more2 = t + 2 < nk;
-    // phase 1: quadrant (0, 0)
-    READ_B(b0x, 0, sb)
-    READ_A(0, sb)
-    if (more1) STAGE_HALF(1, t + 1, s ^ 1);  // A1 of the other stage: last read in phase 3 of tile t - 1
-    SEGMENT_END();
-    MFMA_QUAD(0, 0, b0x)
-    MFMA_END();
-    // phase 2: quadrant (0, 1)
-    READ_B(b1, 1, sb)
-    if (more2) STAGE_HALF(0, t + 2, s);  // A0: read in phase 1
-    SEGMENT_END();
-    MFMA_QUAD(0, 1, b1)
-    MFMA_END();
-    // phase 3: quadrant (1, 1)
-    READ_A(1, sb)
-    if (more2) STAGE_HALF(2, t + 2, s);  // B0: read in phase 1
-    SEGMENT_END();
-    MFMA_QUAD(1, 1, b1)
-    MFMA_END();
-    // phase 4: quadrant (1, 0); retire tile t + 1 (everything issued before the last three halves)
-    if (more2) {
-      STAGE_HALF(3, t + 2, s);  // B1: read in phase 2
-      wait_vm<6>();
-    } else {
-      wait_vm<0>();
-    }
-    SEGMENT_END();
-    MFMA_QUAD(1, 0, b0x)
-    MFMA_END();
-  }
-  if (STAGGER && wr == 0) raw_barrier();
-  }  // MH == 2
-#undef STAGE_HALF
-#undef READ_A
-#undef READ_B
-#undef LDS_FRAG
-#undef MFMA_QUAD
-#undef SEGMENT_END
-#undef MFMA_END
 #if G256_CLK
   if (blockIdx.x == 0 && tid == 0) {
     g256_clk[0] = __builtin_readcyclecounter() - clk_c0;
@@ -413,110 +318,18 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmArgs g) {
         }
     return;
   }
-  // ---- epilogue.  The MFMAs were issued as W-fragment x A-fragment, i.e. they produced the transposed 16x16 tiles:
-  // acc[ha][hb][i][j][r] is tile row ha*128 + wr*64 + i*16 + (lane & 15), tile column hb*128 + wc*32 + j*16 +
-  // (lane >> 4)*4 + r - four CONSECUTIVE output columns per lane, so results (and the residual) move as 8-byte
-  // (bf16) / 16-byte (fp32 logits) accesses instead of 2-byte ones.
-  const int cq = (lane >> 4) * 4;
-  const bool rope = EPI == GEMM_STORE && g.rope_cs != nullptr;
-  const bool wide_ok = (g.ldo & 3) == 0 && (reinterpret_cast<size_t>(g.out) & 15) == 0 &&
-                       (EPI != GEMM_RESIDUAL || (reinterpret_cast<size_t>(g.residual) & 7) == 0);
-#pragma unroll
-  for (int ha = 0; ha < MH; ++ha)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int rl = ha * 128 + wr * 64 + i * 16 + (lane & 15);
-      if (rl >= rows_valid) continue;
-      const int row = row0 + rl;
-      const size_t ob = (size_t)row * g.ldo;
-      const int tp = rope ? g.tok_pos[row] : 0;
-      if (EPI == GEMM_SWIGLU) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int n = n_tile * 128 + wc * 32 + j * 16 + cq;
-          float y[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) y[r] = E::swiglu_fast(acc[ha][0][i][j][r], acc[ha][1][i][j][r]);
-          bf16_t* o = reinterpret_cast<bf16_t*>(g.out) + ob + n;
-          if (n + 3 < g.N && wide_ok) {
-            *reinterpret_cast<uint2*>(o) = make_uint2(E::pack2(y[0], y[1]), E::pack2(y[2], y[3]));
-          } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (n + r < g.N) o[r] = E::from_f(y[r]);
-          }
-        }
-      } else {
-#pragma unroll
-        for (int hb = 0; hb < 2; ++hb)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            const int n = n_tile * 256 + hb * 128 + wc * 32 + j * 16 + cq;
-            if (n >= g.N) continue;
-            const bool full = (n + 3 < g.N) && wide_ok;
-            float y[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) y[r] = E::round(acc[ha][hb][i][j][r]);
-            if (EPI == GEMM_STORE && rope && n < g.rope_cols) {
-              // rotary embedding on the bf16-rounded projection (transformer_layers.py:66-70): this lane's four columns
-              // are two (re, im) pairs of one head; their (cos, sin) entries are 16 contiguous bytes of the table
-              const int i0 = ((n + g.rope_col0) % g.rope_dh) >> 1;
-              const f32x4 cs = *reinterpret_cast<const f32x4*>(g.rope_cs + ((size_t)tp * (g.rope_dh >> 1) + i0) * 2);
-              float re, im;
-              rope_pair(y[0], y[1], cs[0], cs[1], re, im);
-              y[0] = E::round(re); y[1] = E::round(im);
-              rope_pair(y[2], y[3], cs[2], cs[3], re, im);
-              y[2] = E::round(re); y[3] = E::round(im);
-            }
-            if (EPI == GEMM_LOGITS) {
-              float* o = reinterpret_cast<float*>(g.out) + ob + n;
-              if (full) {
-                *reinterpret_cast<float4*>(o) = make_float4(y[0], y[1], y[2], y[3]);
-              } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                  if (n + r < g.N) o[r] = y[r];
-              }
-            } else {
-              bf16_t* o = reinterpret_cast<bf16_t*>(g.out) + ob + n;
-              if (full) {
-                if (EPI == GEMM_RESIDUAL) {
-                  const uint2 rs = *reinterpret_cast<const uint2*>(g.residual + ob + n);
-                  y[0] += E::lo(rs.x); y[1] += E::hi(rs.x); y[2] += E::lo(rs.y); y[3] += E::hi(rs.y);
-                }
-                *reinterpret_cast<uint2*>(o) = make_uint2(E::pack2(y[0], y[1]), E::pack2(y[2], y[3]));
-              } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                  if (n + r < g.N) o[r] = E::from_f(EPI == GEMM_RESIDUAL ? E::to_f(g.residual[ob + n + r]) + y[r] : y[r]);
-              }
-            }
-          }
-      }
-    }
+  if constexpr (kSwap) epilogue16<E, EPI, MH>(g, acc, ScaleNone{}, row0, rows_valid, n_tile, wr, wc, lane);  // STORE / RESIDUAL / SWIGLU
 }
 
-template <int EPI, bool STAGGER, int MH = 2>
-hipError_t launch_var(const GemmArgs& g, dim3 grid, hipStream_t s) {
-  constexpr int lds = MH == 2 ? LDS_BYTES : LDS_BYTES_H;
-  static bool attr_set = false;  // > 64 KiB of dynamic LDS needs the opt-in once per kernel
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<EPI, STAGGER, MH>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((gemm256_kernel<EPI, STAGGER, MH>), grid, dim3(512), lds, s, g);
-  return hipGetLastError();
-}
 template <int EPI, int MH = 2>
-hipError_t launch_one(const GemmArgs& g, dim3 grid, hipStream_t s) {
+hipError_t launch_staggered(const GemmArgs& g, dim3 grid, hipStream_t s) {
+  constexpr int lds = MH == 2 ? LDS_BYTES : LDS_BYTES_H;
   static int stagger = -1;  // MI_GEMM_STAGGER=0: both wave groups in lockstep (A/B testing)
   if (stagger < 0) {
     const char* e = getenv("MI_GEMM_STAGGER");
     stagger = e ? atoi(e) : 1;
   }
-  return stagger ? launch_var<EPI, true, MH>(g, grid, s) : launch_var<EPI, false, MH>(g, grid, s);
+  return stagger ? launch_one<&gemm256_kernel<EPI, true, MH>, lds>(g, grid, s) : launch_one<&gemm256_kernel<EPI, false, MH>, lds>(g, grid, s);
 }
 
 }  // namespace
@@ -535,12 +348,10 @@ bool gemm256_half_applicable(const GemmArgs& g) {
 }
 
 hipError_t launch_gemm256_half(const GemmArgs& g, hipStream_t s) {
-  const int m_tiles = (g.M + 127) >> 7, n_tiles = (g.N + 255) >> 8;
-  const int supertiles = ((m_tiles + 3) >> 2) * ((n_tiles + 7) >> 3);
-  const dim3 grid((unsigned)(((supertiles + 7) / 8) * 8 * 32));
+  const dim3 grid = tile_grid((g.M + 127) >> 7, col_tiles(g.N, g.epi));
   switch (g.epi) {
-    case GEMM_STORE: return launch_one<GEMM_STORE, 1>(g, grid, s);
-    case GEMM_RESIDUAL: return launch_one<GEMM_RESIDUAL, 1>(g, grid, s);
+    case GEMM_STORE: return launch_staggered<GEMM_STORE, 1>(g, grid, s);
+    case GEMM_RESIDUAL: return launch_staggered<GEMM_RESIDUAL, 1>(g, grid, s);
     default: return hipErrorInvalidValue;
   }
 }
@@ -551,16 +362,13 @@ hipError_t launch_gemm256_f16(const GemmArgs& g, hipStream_t s) {
 #else
 hipError_t launch_gemm256(const GemmArgs& g, hipStream_t s) {
 #endif
-  const int nout = (g.epi == GEMM_SWIGLU) ? 128 : 256;
-  const int m_tiles = g.tile_tab ? g.max_m_tiles : (g.M + 255) >> 8, n_tiles = (g.N + nout - 1) / nout;
-  const int supertiles = ((m_tiles + 3) >> 2) * ((n_tiles + 7) >> 3);
-  const dim3 grid((unsigned)(((supertiles + 7) / 8) * 8 * 32));
+  const dim3 grid = tile_grid(g.tile_tab ? g.max_m_tiles : (g.M + 255) >> 8, col_tiles(g.N, g.epi));
   switch (g.epi) {
-    case GEMM_STORE: return launch_one<GEMM_STORE>(g, grid, s);
-    case GEMM_RESIDUAL: return launch_one<GEMM_RESIDUAL>(g, grid, s);
-    case GEMM_SWIGLU: return launch_one<GEMM_SWIGLU>(g, grid, s);
-    case GEMM_LOGITS: return launch_one<GEMM_LOGITS>(g, grid, s);
-    case GEMM_LOGPROB: return launch_one<GEMM_LOGPROB>(g, grid, s);
+    case GEMM_STORE: return launch_staggered<GEMM_STORE>(g, grid, s);
+    case GEMM_RESIDUAL: return launch_staggered<GEMM_RESIDUAL>(g, grid, s);
+    case GEMM_SWIGLU: return launch_staggered<GEMM_SWIGLU>(g, grid, s);
+    case GEMM_LOGITS: return launch_staggered<GEMM_LOGITS>(g, grid, s);
+    case GEMM_LOGPROB: return launch_staggered<GEMM_LOGPROB>(g, grid, s);
     default: return hipErrorInvalidValue;
   }
 }

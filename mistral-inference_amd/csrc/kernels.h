@@ -148,28 +148,28 @@ void gemm_set_tail_mode(int mode);  // mi_debug_set_prefill_kernels
 // gemm256.hip compiled with -DG256_F16=1 (element ElemF16): the same kernel on fp16 payloads (generic.hip: prefills of fp16 models; gemm256_applicable is the predicate for both elements)
 hipError_t launch_gemm256_f16(const GemmArgs& g, hipStream_t s);
 
-// gemm256_w8a8.hip: gemm256's structure on e4m3 bytes for BOTH operands (prefills of FP8 models, opt-in):
-// out = epilogue((A_q . W_q^T)[m, n] * sx[m] * sw[n]).  g.a / g.w0 / g.w1 / g.w2 point to e4m3 bytes, g.lda is in bytes; sx [M] are
-// the activation rows' scales (launch_act_quant_e4m3), sw[i] the row scales of weight segment i (SWIGLU: sw[0] = W1's, sw[1] =
-// W3's).  Epilogues STORE (with RoPE) / RESIDUAL / SWIGLU; plain form only (no tile table, no gather).
-struct GemmW8A8Args {
+// The 256-tile GEMM on e4m3 activation bytes (prefills of quantised models, opt-in).  gemm256.hip, gemm256_w8a8.hip and
+// gemm256_w4a8.hip share their tile map, K loop, epilogue and launcher pieces through gemm256_core.cuh; GemmArgs is the bf16
+// kernel's kernarg and stays as it is, the scales ride beside it (as GemvScaledArgs above).  g.a points to e4m3 bytes, g.lda is in
+// bytes; sx [M] are the activation rows' scales (launch_act_quant_e4m3), sw[i] the scales of weight segment i (SWIGLU: sw[0] =
+// W1's, sw[1] = W3's).  Epilogues STORE (with RoPE) / RESIDUAL / SWIGLU; plain form only (no tile table, no gather).
+template <class scale_t>
+struct GemmA8Args {
   GemmArgs g;
   const float* sx;
-  const float* sw[3];
+  const scale_t* sw[3];
 };
+// gemm256_w8a8.hip: e4m3 bytes for BOTH operands (FP8 models): out = epilogue((A_q . W_q^T)[m, n] * sx[m] * sw[n]).
+// g.w0 / g.w1 / g.w2 point to e4m3 bytes [rows, K], sw[i] holds one fp32 per weight row.
+typedef GemmA8Args<float> GemmW8A8Args;
 bool gemm256_w8a8_applicable(int M, int K);  // M >= 256 && K % 128 == 0 && K <= 16384 (the quantiser's limit): the route's one shape predicate
 hipError_t launch_gemm256_w8a8(const GemmW8A8Args& a, hipStream_t s);
 
-// gemm256_w4a8.hip: the same on MXFP4 weights (prefills of MXFP4 models, opt-in): e2m1 codes meet e4m3 activations on the mixed
-// form of the block-scaled MFMA, which applies the e8m0 block scales itself:
-// out = epilogue((sum_k A_q[m, k] * e2m1(C[n, k]) * 2^(S[n, k / 32] - 127)) * sx[m]).  g.a points to e4m3 bytes (g.lda in bytes),
-// g.w0 / g.w1 / g.w2 to code bytes [rows, K / 2]; sw[i] are the block scale bytes [rows, K / 32] of segment i (SWIGLU: sw[0] =
-// W1's, sw[1] = W3's).  Epilogues and form as above.
-struct GemmW4A8Args {
-  GemmArgs g;
-  const float* sx;
-  const uint8_t* sw[3];
-};
+// gemm256_w4a8.hip: the same on MXFP4 weights (MXFP4 models): e2m1 codes meet e4m3 activations on the mixed form of the
+// block-scaled MFMA, which applies the e8m0 block scales itself:
+// out = epilogue((sum_k A_q[m, k] * e2m1(C[n, k]) * 2^(S[n, k / 32] - 127)) * sx[m]).  g.w0 / g.w1 / g.w2 point to code bytes
+// [rows, K / 2]; sw[i] are the block scale bytes [rows, K / 32] of segment i, 4-byte aligned.
+typedef GemmA8Args<uint8_t> GemmW4A8Args;
 bool gemm256_w4a8_applicable(int M, int K);  // gemm256_w8a8_applicable: one quantiser, one K tile
 hipError_t launch_gemm256_w4a8(const GemmW4A8Args& a, hipStream_t s);
 

@@ -10,6 +10,16 @@
 //   G256_ABL=1..8  timing ablations (WRONG results): no DMA / no reads / no MFMA / MFMA only (16x16x32, 32x32x16) / DMA only /
 //                  reads only inside the main loop
 // Every schedule keeps the accumulation order of the shipped loop: outputs are bit-identical (checked by the probe).
+// The loops below were written against the kernel's local names of the time; the kernel now keeps them in its operand struct
+// `op` (gemm256.hip Ops), so they are bound here (`acc` is the kernel's own reference to op.acc).
+  const bf16_t* src[MH + 2][2];  // halves of a stage: A0 (A1) B0 B1
+#pragma unroll
+  for (int h = 0; h < MH + 2; ++h)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) src[h][j] = reinterpret_cast<const bf16_t*>(op.src[h][j]);
+  [[maybe_unused]] char* const my_piece = op.my_piece;  // (only the PIPE and SPLIT loops issue single pieces)
+  const int a_off = op.a_off, b_off = op.b_off, sw0 = op.sw0, sw1 = op.sw1;
+#define STAGE_HALF(HALF, KT, STAGE) op.stage(HALF, KT, STAGE)
 #if G256_PIPE
   // ---- Software-pipelined main loop, every wave in the same role, ONE barrier per K tile.
   // A K tile is four blocks of 16 MFMAs, G(ks, ha) = k step ks x A half ha x both B halves.  The fragments of the NEXT block
