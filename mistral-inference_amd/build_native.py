@@ -18,7 +18,7 @@ SOURCES = ["api.hip", "gemv.hip", "gemm.hip", "gemm256.hip", "attn_decode.hip", 
 # (this file is a dependency of every object: a change of flags must rebuild them - round 6: decode_engine_next.o was once shipped
 # without a flag that had just been added here)
 HEADERS = [os.path.abspath(__file__), os.path.join(CSRC, "common.cuh"), os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "gemv_core.cuh"),
-           os.path.join(CSRC, "attn_decode_core.cuh"), os.path.join(CSRC, "gemm256_core.cuh"), os.path.join(HERE, "..", "scripts", "probes", "gemm256_experiments.inc"),
+           os.path.join(CSRC, "attn_decode_core.cuh"), os.path.join(CSRC, "attn_split.cuh"), os.path.join(CSRC, "gemm256_core.cuh"), os.path.join(HERE, "..", "scripts", "probes", "gemm256_experiments.inc"),
            os.path.join(HERE, "..", "include", "mistral_hip.h"), os.path.join(HERE, "..", "include", "mistral_hip_debug.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # Per-file flags.  The persistent decode engine is built with the max-memory-clause scheduling strategy: measured 1.3-1.5 % faster
@@ -58,7 +58,6 @@ VARIANT_OBJECTS = {"decode_engine_next.o": ("decode_engine.hip", ENGINE_NEXT_FLA
                    "decode_engine_moe.o": ("decode_engine.hip", ["-DENG_WIDE=2", "-DENG_QKV_HOLD=2"]),
                    "gemm256_f16.o": ("gemm256.hip", ["-DG256_F16=1"]),                # the 256-tile GEMM on fp16 payloads (generic path)
                    "attn_prefill_f16.o": ("attn_prefill.hip", ["-DATTN_F16=1"]),      # the MFMA prefill attention on fp16 payloads
-                   "attn_decode_e4m3.o": ("attn_decode.hip", ["-DATTN_KV_E4M3=1"]),   # the decode attention on rings of e4m3 bytes
                    "gemv_f16.o": ("gemv.hip", ["-DGEMV_F16=1"])}                      # the weight-streaming GEMV kernels on fp16 payloads
 
 

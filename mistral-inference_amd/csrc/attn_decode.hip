@@ -12,113 +12,71 @@
 // and merged once at the end: lanes -> waves (LDS) -> splits (global fp32 partials, merged by a second, tiny
 // launch: the kernel boundary is the cross-XCD visibility point.  An in-kernel "last block combines" variant with an
 // agent-scope release/acquire ticket measured slower than that boundary and was dropped).
+//
+// The ring element is the kernels' first template argument (attn_split.cuh: RingBf16 / RingE4m3); the block coordinates, the ring
+// loads, the partial's store and the merge of the splits are attn_split.cuh's, shared with attn_verify.hip.
 #include <cstdlib>
 
-#include "attn_decode_core.cuh"
-#include "gemv_core.cuh"  // cvt4_e4m3: e4m3 bytes -> exact bf16 pairs
+#include "attn_split.cuh"
 #include "kernels.h"
 
 namespace {
 
-using namespace attn_core;
+using namespace attn_split;
 
-// The ring element (MI_KV_E4M3, include/mistral_hip.h): this file is compiled twice (build_native.py) - for bf16 rings, and with
-// -DATTN_KV_E4M3=1 (attn_decode_e4m3.o) for rings of e4m3 bytes, which exports launch_attn_decode_e4m3 and nothing else; the bf16
-// compile keeps the code objects it had before the second one existed.  A lane's piece of a ring row is its 8 head dims: 16 bytes
-// of a bf16 ring, 8 bytes of an e4m3 ring, which expand - exactly, every e4m3 value is a bf16 value - to the four bf16 pair words
-// that reduce_slot takes.  Everything else (split geometry, slot-to-lane-group mapping, ascending visit order, the arithmetic) is shared, so the
-// result on an e4m3 ring is bit for bit the result on a bf16 ring holding the dequantised values.
-#ifndef ATTN_KV_E4M3
-#define ATTN_KV_E4M3 0
-#endif
-#if !ATTN_KV_E4M3
-typedef bf16_t ring_t;
-struct Row {
-  typedef u32x4 raw;
-  static __device__ __forceinline__ raw load(const bf16_t* p) { return ld16_nt(p); }
-  static __device__ __forceinline__ u32x4 pairs(raw r) { return r; }
-};
-#else
-typedef uint8_t ring_t;
-struct Row {
-  typedef u32x2 raw;
-  static __device__ __forceinline__ raw load(const uint8_t* p) { return __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p)); }
-  static __device__ __forceinline__ u32x4 pairs(raw r) {
-    uint32_t p[4];
-    gemv_core::cvt4_e4m3(r[0], p[0], p[1]);
-    gemv_core::cvt4_e4m3(r[1], p[2], p[3]);
-    return u32x4{p[0], p[1], p[2], p[3]};
-  }
-};
-#endif
-typedef Row::raw raw_t;
+// The block's partial in the scratch: acc [b, kvh][split][R][Dh], then (m, l) [b, kvh][split][R][2]
+template <int R, class FP>
+__device__ __forceinline__ void store_block_partial(float* partial, int B, int Hkv, int n_splits, int b, int kvh, int split, int tid, FP sm_m,
+                                                    FP sm_l, FP sm_acc) {
+  const int bh = b * Hkv + kvh;
+  float* p_acc = partial + ((size_t)bh * n_splits + split) * R * DH;
+  float* p_ml = partial + (size_t)B * Hkv * n_splits * R * DH + ((size_t)bh * n_splits + split) * R * 2;
+  store_split_partial<R>(tid, sm_m, sm_l, sm_acc, p_acc, p_ml, R);
+}
 
 // SMALL (round 5, batches of >= 3 sequences - mistral-demo decodes three): the kernel sits at 170 VGPRs = 2 blocks per CU, so
 // 3 x 256 blocks ran as 1.5 rounds of the grid (20.7 us per layer against 9.0 at batch 1).  With half-size load sets (UK = 2:
 // 8 instead of 16 KiB in flight per wave) it fits 3 blocks per CU without spilling and the batch is ONE round.  A lane group
 // still visits its slots in ascending order: bit-identical results.
-template <int R, bool SMALL>
+template <class Ring, int R, bool SMALL>
 __global__ __launch_bounds__(256, SMALL ? 3 : 1) void attn_decode_kernel(AttnDecodeArgs a) {
+  typedef typename Ring::raw raw_t;
   __shared__ float sm_m[4 * R];
   __shared__ float sm_l[4 * R];
   __shared__ float sm_acc[4 * R * DH];
 
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably wave-uniform -> scalar control flow
-  const int g = lane >> 4, dl = lane & 15;
-  // Workgroup i runs on XCD i % 8: consecutive ids cycle through the kv heads, so (Hkv = 8) every split of a kv head
-  // - and the combine block that merges them - sits on ONE XCD and the fp32 partials are re-read from that XCD's L2.
-  const int kvh = blockIdx.x % a.Hkv, split = blockIdx.x / a.Hkv, b = blockIdx.y;
-  const int pos = a.tok_pos[b];
+  const Coords c(a.Hkv, a.W, a.n_splits);
+  const int pos = a.tok_pos[c.b];
   const int kv_len = min(pos + 1, a.W);
-  const int chunk = split_chunk(a.W, a.n_splits);
-  const int s_begin = split * chunk;
-  const int s_end = min(s_begin + chunk, kv_len);
+  const int s_end = min(c.s_begin + c.chunk, kv_len);
 
   float qf[R][8];
   {
     u32x4 qraw[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) qraw[r] = ld16(a.q + (size_t)b * a.ldq + (size_t)(kvh * R + r) * DH + dl * 8);
+    for (int r = 0; r < R; ++r) qraw[r] = ld16(a.q + (size_t)c.b * a.ldq + (size_t)(c.kvh * R + r) * DH + c.dl * 8);
     load_q<R>(qf, qraw);
   }
   State<R> st;
   init_state<R>(st);
 
-  // `kvh` is a SCHEDULED kv head: when a GQA ratio is split into groups, kv_groups consecutive scheduled heads read the
-  // same real head's K/V (the repeat hits the XCD's L2) and own consecutive slices of its query heads.
-  const int kv_real = kvh / a.kv_groups;
-  // elements between consecutive slots: a whole row of kv heads in the reference's layout, ONE head row in the head-major
-  // layout (common.cuh) - there the four lane groups of a wave read four consecutive slots = one contiguous KiB per load
-  const int hkv_real = a.Hkv / a.kv_groups;
-  const size_t row_stride = a.kv_layout ? (size_t)DH : (size_t)hkv_real * DH;
-  const size_t ring0 = kv_offset(a.kv_layout, a.W, hkv_real * DH, DH, (size_t)b, 0, kv_real * DH) + dl * 8;
-  const ring_t* kbase = reinterpret_cast<const ring_t*>(a.cache_k) + ring0;
-  const ring_t* vbase = reinterpret_cast<const ring_t*>(a.cache_v) + ring0;
+  const RingSlice<Ring> ring(a.cache_k, a.cache_v, a.kv_layout, a.W, a.Hkv, a.kv_groups, c.b, c.kvh, c.dl);
 
   // Each lane group walks slots s_begin + wid*4 + g + 16*j, UK slots (K and V rows = 2*UK loads) per step, two
   // steps in flight (ping-pong register sets A/B refilled in place, 16 KiB per wave outstanding): the kernel is pure
   // HBM latency/bandwidth, so depth is what matters.
   constexpr int UK = (R <= 4 && !SMALL) ? 4 : 2;  // R >= 6 needs the registers for its accumulators: half-size sets, no AGPR spills
-  const int s_first = s_begin + wid * 4 + g;
   const int s_clamp = max(kv_len - 1, 0);
-  const int n_steps = (s_end > s_begin) ? (s_end - s_begin + 16 * UK - 1) / (16 * UK) : 0;  // block-uniform
-  raw_t setA[2 * UK], setB[2 * UK];  // [0, UK): K rows, [UK, 2UK): V rows
-  // ALWAYS exactly 2*UK unconditional loads (slots past the block's range are clamped to a valid slot and masked in
-  // reduce_step): no branch around a load, so hipcc's wait for one set leaves the other set's loads in flight.
-  auto load_step = [&](int it, raw_t (&kv)[2 * UK]) {
-    const int s0 = s_first + it * 16 * UK;
-#pragma unroll
-    for (int u = 0; u < UK; ++u) {
-      const int sl = min(s0 + 16 * u, s_clamp);
-      kv[u] = Row::load(kbase + (size_t)sl * row_stride);
-      kv[UK + u] = Row::load(vbase + (size_t)sl * row_stride);
-    }
-  };
+  const int n_steps = (s_end > c.s_begin) ? (s_end - c.s_begin + 16 * UK - 1) / (16 * UK) : 0;  // block-uniform
+  // [0, UK): K rows, [UK, 2UK): V rows.  (ONE array per set: with the K and the V rows in arrays of their own, <4, true> came out
+  // at 168 VGPRs and 28 bytes of scratch instead of 148 and none.)
+  raw_t setA[2 * UK], setB[2 * UK];
+  // slots past the block's range are clamped to a valid slot (RingSlice::load) and masked in reduce_step
+  auto load_step = [&](int it, raw_t (&kv)[2 * UK]) { ring.template load<UK>(c.s_first + it * 16 * UK, s_clamp, kv, kv + UK); };
   auto reduce_step = [&](int it, const raw_t (&kv)[2 * UK]) {
-    const int s0 = s_first + it * 16 * UK;
+    const int s0 = c.s_first + it * 16 * UK;
 #pragma unroll
-    for (int u = 0; u < UK; ++u) reduce_slot<R>(st, qf, Row::pairs(kv[u]), Row::pairs(kv[UK + u]), (s0 + 16 * u) < s_end);
+    for (int u = 0; u < UK; ++u) reduce_slot<R>(st, qf, Ring::pairs(kv[u]), Ring::pairs(kv[UK + u]), (s0 + 16 * u) < s_end);
   };
   // Two sets in flight.  Steps beyond n_steps reduce nothing (every slot is masked).
   load_step(0, setA);
@@ -131,22 +89,11 @@ __global__ __launch_bounds__(256, SMALL ? 3 : 1) void attn_decode_kernel(AttnDec
   }
 
   // 4 lane groups -> wave -> LDS
-  wave_state_to_lds<R>(st, wid, lane, sm_m, sm_l, sm_acc);
+  wave_state_to_lds<R>(st, c.wid, c.lane, sm_m, sm_l, sm_acc);
   __syncthreads();
 
   // 4 waves -> block partial in global scratch
-  const int bh = b * a.Hkv + kvh;
-  float* p_acc = a.partial + ((size_t)bh * a.n_splits + split) * R * DH;
-  float* p_ml = a.partial + (size_t)a.B * a.Hkv * a.n_splits * R * DH + ((size_t)bh * a.n_splits + split) * R * 2;
-  for (int idx = tid; idx < R * DH; idx += 256) {
-    float A, M, L;
-    split_partial<R>(idx, sm_m, sm_l, sm_acc, A, M, L);
-    p_acc[idx] = A;
-    if (idx % DH == 0) {
-      p_ml[(idx / DH) * 2] = M;
-      p_ml[(idx / DH) * 2 + 1] = L;
-    }
-  }
+  store_block_partial<R>(a.partial, a.B, a.Hkv, a.n_splits, c.b, c.kvh, c.split, c.tid, sm_m, sm_l, sm_acc);
 }
 
 // ALL-IN form (round 6; batches of >= 3 sequences on rings of <= 4096 slots: 128 slots per block = 8 per lane group): the block's
@@ -154,7 +101,7 @@ __global__ __launch_bounds__(256, SMALL ? 3 : 1) void attn_decode_kernel(AttnDec
 // (heads do not interact in reduce_slot, a lane group still visits its slots in ascending order: bit-identical results).  The
 // SMALL form above walks the same slots in four dependent steps with two in flight: three memory round trips where this has
 // one (batch 3: 16.9 us per layer for 50 MB).  Fits 3 blocks per CU.
-template <int R>
+template <class Ring, int R>
 __global__ __launch_bounds__(256, 3) void attn_decode_allin_kernel(AttnDecodeArgs a) {
   static_assert(R == 2 || R == 4, "passes of two query heads");
   __shared__ float sm_m[4 * R];
@@ -162,35 +109,18 @@ __global__ __launch_bounds__(256, 3) void attn_decode_allin_kernel(AttnDecodeArg
   __shared__ float sm_acc[4 * R * DH];
   constexpr int NS = 8;  // slots per lane group: 4 waves x 4 groups x 8 = 128 slots per block
 
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int g = lane >> 4, dl = lane & 15;
-  const int kvh = blockIdx.x % a.Hkv, split = blockIdx.x / a.Hkv, b = blockIdx.y;
-  const int pos = a.tok_pos[b];
+  const Coords c(a.Hkv, a.W, a.n_splits);  // chunk <= 128 (decode_form)
+  const int pos = a.tok_pos[c.b];
   const int kv_len = min(pos + 1, a.W);
-  const int chunk = split_chunk(a.W, a.n_splits);  // <= 128 (launch_r)
-  const int s_begin = split * chunk;
-  const int s_end = min(s_begin + chunk, kv_len);
+  const int s_end = min(c.s_begin + c.chunk, kv_len);
 
   u32x4 qraw[R];
 #pragma unroll
-  for (int r = 0; r < R; ++r) qraw[r] = ld16(a.q + (size_t)b * a.ldq + (size_t)(kvh * R + r) * DH + dl * 8);
+  for (int r = 0; r < R; ++r) qraw[r] = ld16(a.q + (size_t)c.b * a.ldq + (size_t)(c.kvh * R + r) * DH + c.dl * 8);
 
-  const int kv_real = kvh / a.kv_groups;
-  const int hkv_real = a.Hkv / a.kv_groups;
-  const size_t row_stride = a.kv_layout ? (size_t)DH : (size_t)hkv_real * DH;
-  const size_t ring0 = kv_offset(a.kv_layout, a.W, hkv_real * DH, DH, (size_t)b, 0, kv_real * DH) + dl * 8;
-  const ring_t* kbase = reinterpret_cast<const ring_t*>(a.cache_k) + ring0;
-  const ring_t* vbase = reinterpret_cast<const ring_t*>(a.cache_v) + ring0;
-  const int s_first = s_begin + wid * 4 + g;
-  const int s_clamp = max(kv_len - 1, 0);
-  raw_t kk[NS], vv[NS];  // ALWAYS 2 * NS unconditional loads (slots past the block's range: clamped, masked below)
-#pragma unroll
-  for (int j = 0; j < NS; ++j) {
-    const int sl = min(s_first + 16 * j, s_clamp);
-    kk[j] = Row::load(kbase + (size_t)sl * row_stride);
-    vv[j] = Row::load(vbase + (size_t)sl * row_stride);
-  }
+  const RingSlice<Ring> ring(a.cache_k, a.cache_v, a.kv_layout, a.W, a.Hkv, a.kv_groups, c.b, c.kvh, c.dl);
+  typename Ring::raw kk[NS], vv[NS];  // (slots past the block's range: clamped, masked below)
+  ring.template load<NS>(c.s_first, max(kv_len - 1, 0), kk, vv);
 #pragma unroll
   for (int rp = 0; rp < R; rp += 2) {
     if (rp > 0) {  // the passes run one after the other on the RAW rows: shared, hipcc keeps every row's 16 converted floats live (145 spills)
@@ -204,28 +134,15 @@ __global__ __launch_bounds__(256, 3) void attn_decode_allin_kernel(AttnDecodeArg
     State<2> st;
     init_state<2>(st);
 #pragma unroll
-    for (int j = 0; j < NS; ++j) reduce_slot<2>(st, qf, Row::pairs(kk[j]), Row::pairs(vv[j]), (s_first + 16 * j) < s_end);
-    wave_state_to_lds_heads<2, R>(st, wid, lane, rp, sm_m, sm_l, sm_acc);
+    for (int j = 0; j < NS; ++j) reduce_slot<2>(st, qf, Ring::pairs(kk[j]), Ring::pairs(vv[j]), (c.s_first + 16 * j) < s_end);
+    wave_state_to_lds_heads<2, R>(st, c.wid, c.lane, rp, sm_m, sm_l, sm_acc);
   }
   __syncthreads();
 
-  const int bh = b * a.Hkv + kvh;
-  float* p_acc = a.partial + ((size_t)bh * a.n_splits + split) * R * DH;
-  float* p_ml = a.partial + (size_t)a.B * a.Hkv * a.n_splits * R * DH + ((size_t)bh * a.n_splits + split) * R * 2;
-  for (int idx = tid; idx < R * DH; idx += 256) {
-    float A, M, L;
-    split_partial<R>(idx, sm_m, sm_l, sm_acc, A, M, L);
-    p_acc[idx] = A;
-    if (idx % DH == 0) {
-      p_ml[(idx / DH) * 2] = M;
-      p_ml[(idx / DH) * 2 + 1] = L;
-    }
-  }
+  store_block_partial<R>(a.partial, a.B, a.Hkv, a.n_splits, c.b, c.kvh, c.split, c.tid, sm_m, sm_l, sm_acc);
 }
 
-// Second launch: one block per (sequence, q head), one thread per output element.  All of a
-// thread's loads (the head's (m, l) pairs - same address across the block, so one transaction each - and its own
-// accumulator column) are independent and issued together: one memory round trip instead of a chain.
+// Second launch: one block per (sequence, q head), one thread per output element (attn_split.cuh: combine_pair).
 template <int NS>  // upper bound on n_splits held in registers
 __global__ __launch_bounds__(128) void attn_decode_combine_kernel(AttnDecodeArgs a) {
   const int d = threadIdx.x, b = blockIdx.y;
@@ -233,43 +150,55 @@ __global__ __launch_bounds__(128) void attn_decode_combine_kernel(AttnDecodeArgs
   const int bh = b * a.Hkv + kvh;
   const float* all_acc = a.partial + (size_t)bh * a.n_splits * R * DH + (size_t)r * DH + d;
   const float* all_ml = a.partial + (size_t)a.B * a.Hkv * a.n_splits * R * DH + (size_t)bh * a.n_splits * R * 2 + r * 2;
-  float m[NS], l[NS], v[NS];
-#pragma unroll
-  for (int sp = 0; sp < NS; ++sp) {
-    const int s2 = min(sp, a.n_splits - 1);  // clamped, never a conditional load
-    const float2 ml = *reinterpret_cast<const float2*>(all_ml + (size_t)s2 * R * 2);
-    m[sp] = (sp < a.n_splits) ? ml.x : -1e30f;
-    l[sp] = (sp < a.n_splits) ? ml.y : 0.f;
-    v[sp] = all_acc[(size_t)s2 * R * DH];
-  }
-  const float o = combine_splits<NS>(m, l, v, a.n_splits);
+  const float o = combine_pair<NS>(all_acc, all_ml, R, a.n_splits);
   reinterpret_cast<bf16_t*>(a.out)[(size_t)b * a.H * DH + (size_t)h * DH + d] = f_to_bf(o);
 }
 
-template <int R>
+bool allin_enabled() {  // MI_ATTN_ALLIN=0: the stepping form for batches >= 3 (A/B testing)
+  static const bool on = [] {
+    const char* e = getenv("MI_ATTN_ALLIN");
+    return e ? atoi(e) != 0 : true;
+  }();
+  return on;
+}
+
+// Which kernel serves R query heads per block at batch B with `chunk` slots per block.
+enum class Form { STEP, STEP_SMALL, ALLIN };
+Form decode_form(int R, int B, int chunk) {
+  if (B < 3 || R > 4) return Form::STEP;  // (R >= 6 has no SMALL form: its load sets are half-size already)
+  if ((R == 2 || R == 4) && chunk <= 128 && allin_enabled()) return Form::ALLIN;
+  return Form::STEP_SMALL;
+}
+
+template <class Ring, int R>
 void launch_r(const AttnDecodeArgs& a, hipStream_t s) {
   dim3 grid(a.n_splits * a.Hkv, a.B), block(256);
-  static int allin = -1;  // MI_ATTN_ALLIN=0: the stepping form for batches >= 3 (A/B testing)
-  if (allin < 0) {
-    const char* e = getenv("MI_ATTN_ALLIN");
-    allin = e ? atoi(e) : 1;
+  switch (decode_form(R, a.B, split_chunk(a.W, a.n_splits))) {
+    case Form::ALLIN:
+      if constexpr (R == 2 || R == 4) hipLaunchKernelGGL((attn_decode_allin_kernel<Ring, R>), grid, block, 0, s, a);
+      break;
+    case Form::STEP_SMALL: hipLaunchKernelGGL((attn_decode_kernel<Ring, R, (R <= 4)>), grid, block, 0, s, a); break;
+    case Form::STEP: hipLaunchKernelGGL((attn_decode_kernel<Ring, R, false>), grid, block, 0, s, a); break;
   }
-  if constexpr (R == 2 || R == 4) {
-    if (a.B >= 3 && allin && attn_core::split_chunk(a.W, a.n_splits) <= 128) {
-      hipLaunchKernelGGL((attn_decode_allin_kernel<R>), grid, block, 0, s, a);
-      goto combine;
-    }
-  }
-  if (R <= 4 && a.B >= 3) hipLaunchKernelGGL((attn_decode_kernel<R, (R <= 4)>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((attn_decode_kernel<R, false>), grid, block, 0, s, a);
-combine:
   if (a.n_splits <= 16) hipLaunchKernelGGL((attn_decode_combine_kernel<16>), dim3(a.H, a.B), dim3(128), 0, s, a);
   else hipLaunchKernelGGL((attn_decode_combine_kernel<32>), dim3(a.H, a.B), dim3(128), 0, s, a);  // n_splits <= 32
 }
 
+template <class Ring>
+hipError_t launch_ring(const AttnDecodeArgs& a, int R, hipStream_t s) {
+  switch (R) {
+    case 1: launch_r<Ring, 1>(a, s); break;
+    case 2: launch_r<Ring, 2>(a, s); break;
+    case 4: launch_r<Ring, 4>(a, s); break;
+    case 6: launch_r<Ring, 6>(a, s); break;
+    case 8: launch_r<Ring, 8>(a, s); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
 }  // namespace
 
-#if !ATTN_KV_E4M3
 int attn_decode_splits(int W) {
   static int slots = 0;  // minimum ring slots per block; MI_ATTN_SPLIT_SLOTS overrides (tuning)
   if (slots == 0) {
@@ -297,28 +226,12 @@ int attn_decode_group(int R) {
   return 1;
 }
 
-#endif  // !ATTN_KV_E4M3
-
-// kv_layout with MI_KV_E4M3: the e4m3 compile's launcher (the same choice of form on the same geometry)
-#if ATTN_KV_E4M3
-hipError_t launch_attn_decode_e4m3(const AttnDecodeArgs& a_in, hipStream_t s) {
-#else
 hipError_t launch_attn_decode(const AttnDecodeArgs& a_in, hipStream_t s) {
-  if (a_in.kv_layout & MI_KV_E4M3) return launch_attn_decode_e4m3(a_in, s);
-#endif
   if (a_in.Dh != DH || a_in.H % a_in.Hkv != 0) return hipErrorInvalidValue;
   AttnDecodeArgs a = a_in;
   const int R = attn_decode_group(a.H / a.Hkv);
   a.kv_groups = (a.H / a.Hkv) / R;
   a.Hkv = a_in.Hkv * a.kv_groups;
-  a.kv_layout = a_in.kv_layout & 1;  // the kernels index with the layout bit
-  switch (R) {
-    case 1: launch_r<1>(a, s); break;
-    case 2: launch_r<2>(a, s); break;
-    case 4: launch_r<4>(a, s); break;
-    case 6: launch_r<6>(a, s); break;
-    case 8: launch_r<8>(a, s); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  a.kv_layout = a_in.kv_layout & 1;  // the kernels index with the layout bit; the element bit picks their ring
+  return (a_in.kv_layout & MI_KV_E4M3) ? launch_ring<RingE4m3>(a, R, s) : launch_ring<RingBf16>(a, R, s);
 }

@@ -14,12 +14,14 @@
 // partial (global fp32).
 // The last split also folds in the step's own rows (lane group f of the block takes row f) and copies them, K then V, into the
 // per-layer stash that the commit kernel (elementwise.hip) reads.  A second launch merges the splits as the decode combine does.
-#include "attn_decode_core.cuh"
+// The block coordinates, the ring loads (through the RingBf16 element: bf16 rings only), the partial's store and the merge of the
+// splits are attn_split.cuh's, shared with attn_decode.hip.
+#include "attn_split.cuh"
 #include "kernels.h"
 
 namespace {
 
-using namespace attn_core;
+using namespace attn_split;
 
 constexpr int NS = 8;  // ring slots per lane group: 4 waves x 4 groups x 8 = 128 slots per block (launch_attn_verify keeps chunks <= 128)
 constexpr int P = 4;   // pairs per pass
@@ -52,37 +54,22 @@ __global__ __launch_bounds__(256, 1) void attn_verify_kernel(AttnVerifyArgs a) {
   __shared__ float sm_l[2][4 * P];
   __shared__ float sm_acc[2][4 * P * DH];
 
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int g = lane >> 4, dl = lane & 15;
-  const int kvh = blockIdx.x % a.Hkv, split = blockIdx.x / a.Hkv, b = blockIdx.y;
+  const Coords c(a.Hkv, a.W, a.n_splits);  // chunk <= 128
   const int R = a.H / a.Hkv;
-  const int q0 = a.q_start[b], m = a.q_start[b + 1] - q0, p = a.kv_before[b];
+  const int q0 = a.q_start[c.b], m = a.q_start[c.b + 1] - q0, p = a.kv_before[c.b];
   const int n_pairs = R * m;
-  const int chunk = split_chunk(a.W, a.n_splits);  // <= 128
-  const int s_begin = split * chunk;
-  const int s_end = min(s_begin + chunk, a.W);
-  const bool fresh_split = split == a.n_splits - 1;
+  const int s_end = min(c.s_begin + c.chunk, a.W);
+  const bool fresh_split = c.split == a.n_splits - 1;
 
   // ---- the block's whole K/V share, then the step's own rows: every load is issued before the first use
-  const size_t row_stride = a.kv_layout ? (size_t)DH : (size_t)a.Hkv * DH;
-  const size_t ring0 = kv_offset(a.kv_layout, a.W, a.Hkv * DH, DH, (size_t)b, 0, kvh * DH) + dl * 8;
-  const bf16_t* kbase = a.cache_k + ring0;
-  const bf16_t* vbase = a.cache_v + ring0;
-  const int s_first = s_begin + wid * 4 + g;
-  const int s_clamp = a.W - 1;  // every slot of a ring is allocated; what a clamped or unfilled slot holds is masked below
-  u32x4 kk[NS], vv[NS];
-#pragma unroll
-  for (int j = 0; j < NS; ++j) {  // set A: j < 4, set B: j >= 4
-    const int sl = min(s_first + 16 * j, s_clamp);
-    kk[j] = ld16_nt(kbase + (size_t)sl * row_stride);
-    vv[j] = ld16_nt(vbase + (size_t)sl * row_stride);
-  }
-  const int f = wid * 4 + g;  // the step's own row this lane group takes (rows f >= m: clamped, masked)
-  const bf16_t* frow = a.qkv + (size_t)min(q0 + max(min(f, m - 1), 0), a.T - 1) * a.ld + (size_t)a.H * DH + (size_t)kvh * DH + dl * 8;
+  const RingSlice<RingBf16> ring(a.cache_k, a.cache_v, a.kv_layout, a.W, a.Hkv, 1, c.b, c.kvh, c.dl);
+  u32x4 kk[NS], vv[NS];  // set A: j < 4, set B: j >= 4
+  ring.load<NS>(c.s_first, a.W - 1, kk, vv);  // every slot of a ring is allocated; what a clamped or unfilled slot holds is masked below
+  const int f = c.wid * 4 + c.g;  // the step's own row this lane group takes (rows f >= m: clamped, masked)
+  const bf16_t* frow = a.qkv + (size_t)min(q0 + max(min(f, m - 1), 0), a.T - 1) * a.ld + (size_t)a.H * DH + (size_t)c.kvh * DH + c.dl * 8;
   u32x4 fk = ld16(frow), fv = ld16(frow + (size_t)a.Hkv * DH);
   if (fresh_split && f < m && a.stash) {  // K | V of the step's rows, [T, 2 * Hkv * Dh]
-    bf16_t* dst = a.stash + (size_t)(q0 + f) * 2 * a.Hkv * DH + (size_t)kvh * DH + dl * 8;
+    bf16_t* dst = a.stash + (size_t)(q0 + f) * 2 * a.Hkv * DH + (size_t)c.kvh * DH + c.dl * 8;
     st16(dst, fk);
     st16(dst + (size_t)a.Hkv * DH, fv);
   }
@@ -93,7 +80,7 @@ __global__ __launch_bounds__(256, 1) void attn_verify_kernel(AttnVerifyArgs a) {
   int kp[NS];
 #pragma unroll
   for (int j = 0; j < NS; ++j) {
-    const int sl = s_first + 16 * j;
+    const int sl = c.s_first + 16 * j;
     kp[j] = (sl < s_end && p > 0) ? ((sl <= last_slot) ? base_pos + sl : base_pos - a.W + sl) : -1;
     kk[j] = keep_if(kk[j], kp[j] >= 0);
     vv[j] = keep_if(vv[j], kp[j] >= 0);
@@ -107,7 +94,7 @@ __global__ __launch_bounds__(256, 1) void attn_verify_kernel(AttnVerifyArgs a) {
 #pragma unroll
     for (int r = 0; r < P; ++r) {
       const int pi = max(min(pp + r, n_pairs - 1), 0);
-      qraw[r] = ld16(a.qkv + (size_t)min(q0 + pi / R, a.T - 1) * a.ld + (size_t)(kvh * R + pi % R) * DH + dl * 8);
+      qraw[r] = ld16(a.qkv + (size_t)min(q0 + pi / R, a.T - 1) * a.ld + (size_t)(c.kvh * R + pi % R) * DH + c.dl * 8);
     }
   };
   u32x4 qnext[P];
@@ -115,8 +102,8 @@ __global__ __launch_bounds__(256, 1) void attn_verify_kernel(AttnVerifyArgs a) {
 
   const size_t pair0 = (size_t)q0 * R;  // first pair of the sequence among the T * R pairs of this kv head
   const size_t n_all = (size_t)a.T * R;
-  float* p_acc = a.partial + (((size_t)kvh * a.n_splits + split) * n_all + pair0) * DH;
-  float* p_ml = a.partial + (size_t)a.Hkv * a.n_splits * n_all * DH + (((size_t)kvh * a.n_splits + split) * n_all + pair0) * 2;
+  float* p_acc = a.partial + (((size_t)c.kvh * a.n_splits + c.split) * n_all + pair0) * DH;
+  float* p_ml = a.partial + (size_t)a.Hkv * a.n_splits * n_all * DH + (((size_t)c.kvh * a.n_splits + c.split) * n_all + pair0) * 2;
 
   int buf = 0;
   for (int pp = 0; pp < n_pairs; pp += P, buf ^= 1) {
@@ -192,40 +179,20 @@ __global__ __launch_bounds__(256, 1) void attn_verify_kernel(AttnVerifyArgs a) {
         st.acc[r][2 * i] = acc[r][i][0];
         st.acc[r][2 * i + 1] = acc[r][i][1];
       }
-    wave_state_to_lds<P>(st, wid, lane, sm_m[buf], sm_l[buf], sm_acc[buf]);
+    wave_state_to_lds<P>(st, c.wid, c.lane, sm_m[buf], sm_l[buf], sm_acc[buf]);
     __syncthreads();
-    for (int idx = tid; idx < P * DH; idx += 256) {
-      const int r = idx / DH;
-      if (pp + r >= n_pairs) continue;
-      float A, M, L;
-      split_partial<P>(idx, sm_m[buf], sm_l[buf], sm_acc[buf], A, M, L);
-      p_acc[(size_t)pp * DH + idx] = A;
-      if (idx % DH == 0) {
-        p_ml[(size_t)(pp + r) * 2] = M;
-        p_ml[(size_t)(pp + r) * 2 + 1] = L;
-      }
-    }
+    store_split_partial<P>(c.tid, sm_m[buf], sm_l[buf], sm_acc[buf], p_acc + (size_t)pp * DH, p_ml + (size_t)pp * 2, n_pairs - pp);
   }
 }
 
 // Second launch: one block per (row, q head), one thread per output element - the decode combine on the pair's partials.
 __global__ __launch_bounds__(128) void attn_verify_combine_kernel(AttnVerifyArgs a) {
-  constexpr int MAXS = 32;
   const int d = threadIdx.x, h = blockIdx.x, t = blockIdx.y;
   const int R = a.H / a.Hkv, kvh = h / R, r = h % R;
   const size_t n_all = (size_t)a.T * R, pair = (size_t)t * R + r;
   const float* all_acc = a.partial + ((size_t)kvh * a.n_splits * n_all + pair) * DH + d;
   const float* all_ml = a.partial + (size_t)a.Hkv * a.n_splits * n_all * DH + ((size_t)kvh * a.n_splits * n_all + pair) * 2;
-  float m[MAXS], l[MAXS], v[MAXS];
-#pragma unroll
-  for (int sp = 0; sp < MAXS; ++sp) {
-    const int s2 = min(sp, a.n_splits - 1);  // clamped, never a conditional load
-    const float2 ml = *reinterpret_cast<const float2*>(all_ml + (size_t)s2 * n_all * 2);
-    m[sp] = (sp < a.n_splits) ? ml.x : -1e30f;
-    l[sp] = (sp < a.n_splits) ? ml.y : 0.f;
-    v[sp] = all_acc[(size_t)s2 * n_all * DH];
-  }
-  const float o = combine_splits<MAXS>(m, l, v, a.n_splits);
+  const float o = combine_pair<32>(all_acc, all_ml, n_all, a.n_splits);  // launch_attn_verify: n_splits <= 32
   reinterpret_cast<bf16_t*>(a.out)[(size_t)t * a.H * DH + (size_t)h * DH + d] = f_to_bf(o);
 }
 

@@ -180,7 +180,7 @@ struct AttnDecodeArgs {
   int ldq;
   const bf16_t* cache_k;  // [maxB, W, Hkv*Dh] (kv_layout 0) or [maxB, Hkv, W, Dh] (1)
   const bf16_t* cache_v;
-  int kv_layout;           // with MI_KV_E4M3: cache_k / cache_v point to e4m3 bytes (launch_attn_decode picks the instantiation)
+  int kv_layout;           // with MI_KV_E4M3: cache_k / cache_v point to e4m3 bytes (launch_attn_decode picks the kernels' Ring argument)
   int W, B, H, Hkv, Dh;    // Hkv: kv heads AS SCHEDULED = real kv heads x kv_groups (launch_attn_decode sets both)
   int kv_groups;           // query-head groups per real kv head (1 unless the GQA ratio is split, see launch_attn_decode)
   const int32_t* tok_pos;  // [B]
@@ -192,7 +192,6 @@ int attn_decode_splits(int W);
 int attn_decode_group(int R);  // query heads served per block: the largest of {8, 6, 4, 2, 1} dividing the GQA ratio
 size_t attn_decode_partial_floats(int B, int H, int Hkv, int Dh, int W);
 hipError_t launch_attn_decode(const AttnDecodeArgs& a, hipStream_t s);
-hipError_t launch_attn_decode_e4m3(const AttnDecodeArgs& a, hipStream_t s);  // attn_decode.hip compiled with -DATTN_KV_E4M3=1
 
 struct AttnPrefillArgs {
   void* out;            // [T, H*Dh]
