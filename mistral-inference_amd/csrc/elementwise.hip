@@ -303,7 +303,8 @@ __global__ __launch_bounds__(256) void decode_prep_embedding_kernel(int64_t* kv_
 
 // Greedy sampling behind the LM head on the launch path (the persistent engine does the same in its own epilogue,
 // decode_engine.hip): block b reduces logits row b to (max, FIRST index of the max, sum exp(x - max)) - generate.py:124
-// `torch.argmax` and :134-136 `log_softmax(...)[token]`, which at the argmax is -log(sum).
+// `torch.argmax` and :134-136 `log_softmax(...)[token]`, which at the argmax is -log(sum).  Logits of -inf (a masked vocabulary
+// tail) add nothing to the sum, as in log_softmax; a row of nothing but -inf has no defined result.
 __global__ __launch_bounds__(1024) void greedy_rows_kernel(const float* logits, int ld, int B, int V, int64_t* tok, float* lp,
                                                            int64_t* hist_tok, float* hist_lp, int hist_len,
                                                            const uint32_t* ctrl) {
@@ -312,6 +313,9 @@ __global__ __launch_bounds__(1024) void greedy_rows_kernel(const float* logits, 
   const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const float* row = logits + (size_t)b * ld;
   float M = -INFINITY, S = 0.f;
+  // What the sum subtracts: M once the thread has met a finite logit, 0 until then - x - M would be -inf + inf = NaN for a thread that
+  // starts on -inf logits (a masked vocabulary tail), exp(-inf - 0) is the 0 such a logit adds.  Set where M is: no work per trip.
+  float Ms = 0.f;
   int I = 0x7fffffff;
   int i0 = threadIdx.x;
   if ((V & 3) == 0 && (reinterpret_cast<size_t>(row) & 15) == 0) {
@@ -336,14 +340,14 @@ __global__ __launch_bounds__(1024) void greedy_rows_kernel(const float* logits, 
       for (int e = 1; e < 16; ++e) cm = fmaxf(cm, x[e]);
       if (cm > M) {
         S *= __expf(M - cm);  // (M = -inf at the start: exp(-inf) = 0 and S = 0)
-        M = cm;
+        M = Ms = cm;
         int first = 15;
 #pragma unroll
         for (int e = 14; e >= 0; --e) first = (x[e] == cm) ? e : first;
         I = (q + (first >> 2) * 1024) * 4 + (first & 3);
       }
 #pragma unroll
-      for (int e = 0; e < 16; ++e) S += __expf(x[e] - M);
+      for (int e = 0; e < 16; ++e) S += __expf(x[e] - Ms);
     }
     i0 = V;  // nothing left for the scalar loop
   }
@@ -351,10 +355,10 @@ __global__ __launch_bounds__(1024) void greedy_rows_kernel(const float* logits, 
     const float x = row[i];
     if (x > M) {
       S = S * __expf(M - x) + 1.f;
-      M = x;
+      M = Ms = x;
       I = i;
     } else {
-      S += __expf(x - M);
+      S += __expf(x - Ms);
     }
   }
   auto merge = [&](float m2, int i2, float s2) {

@@ -105,6 +105,9 @@ def test_session_moe_and_batch3_launch_path(graph):
     assert float((ref_lp - got_lp).abs().max()) < 2e-5
 
 
+# V = 32768 + 5 is no multiple of 4: every row below takes greedy_rows_kernel's scalar loop.  The 16-logits-per-trip float4 loop that
+# every real vocabulary takes - the trip's maximum, the first slot holding it, the index formula, the tail mask - and rows with -inf
+# logits are pinned by test_gpu_rows_structured.py::test_greedy_rows (inputs: row_cases.py).
 def test_greedy_sample_leaf_ties_and_logprob():
     """First maximal index wins (torch.argmax), across threads, waves and the whole row; logprob = log_softmax at it."""
     from mistral_inference import _hip
