@@ -41,6 +41,7 @@ int main(int argc, char** argv) {
       fprintf(stderr, "missing symbol %s\n", v3[i]);
       return 3;
     }
+  printf("sampled verify steps (mi_verify_sample): %s\n", dlsym(h, "mi_verify_sample") ? "yes" : "no"); /* additive: presence is the feature test */
   if (abi() != MI_ABI_VERSION) {
     fprintf(stderr, "ABI %d, header %d\n", abi(), MI_ABI_VERSION);
     return 4;

@@ -502,6 +502,40 @@ size_t mi_workspace_bytes_verify(const mi_model_t* model, int quantised, int T, 
 int mi_forward_verify(const mi_model_t* model, const mi_w8_model_t* w8, const mi_w4_model_t* w4, const mi_batch_t* batch,
                       const mi_verify_out_t* out, mi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sampled verify steps: speculative decoding at temperature > 0.  Additive like the block above: one new symbol whose presence is
+ * the feature test, no struct changes.  THE RULE (this is its definition; DESIGN.md section 0 restates it):
+ *
+ * Drafts are deterministic, so the proposal for a position is a point mass on the drafted token.  One sequence brings rows
+ * 0 .. m-1: row 0 its last emitted token, rows 1 .. m-1 the drafts d_1 .. d_(m-1).  P_i is exactly the distribution mi_sample_top_p
+ * draws from on row i's logits: softmax(logits / temperature); kept set = the prefix of the descending order whose mass BEFORE the
+ * token is <= top_p, ties by ascending token id; renormalised; 40-bit fixed-point masses.  M_i is the kept mass, mass_i(d) the mass
+ * of d if d is kept and 0 otherwise - also for a token tied at the cut value that the ascending-id rule leaves out.
+ *   - for i = 0 .. m-2 in order: d_(i+1) is ACCEPTED iff u_acc[i] * M_i < mass_i(d_(i+1)); then token[i] = d_(i+1), the scan goes on;
+ *   - at the first rejection token[i] is drawn by inverse CDF with u_draw[i] from P_i with d_(i+1) removed and renormalised (same
+ *     order, same tie rule; the removed token's mass leaves the running sums), n_accept = i, and later rows emit nothing
+ *     (token -1, logprob 0);
+ *   - if every draft is accepted (n_accept = m-1, also m = 1), token[m-1] is the plain mi_sample_top_p draw from P_(m-1) with
+ *     u_draw[m-1];
+ *   - logprob[i] = log_softmax(UNSCALED logits_i)[token[i]] (generate.py:134-136), as mi_sample_top_p reports it;
+ *   - a sole-survivor nucleus has mass(d) == M and is always accepted (u < 1): the residual is never empty when drawn from.
+ * Accepting has probability P_i(d) and a rejection draws from P_i without d, so each emitted token is distributed as P_i: the
+ * generation has the plain sampler's distribution - not its tokens for a given seed.
+ * Variates: (w0, w1, w2, w3) = Philox4x32-10(seed; counter = offset, row t), t = the row's index in the step;
+ * u_draw = (w0 * 2^32 + w1) / 2^64 - the words mi_sample_top_p uses - and u_acc = (w2 * 2^32 + w3) / 2^64.
+ *
+ * mi_verify_sample applies the rule to T rows of fp32 logits [T, ld] in B sequences (rows q_start[b] .. q_start[b + 1], q_start
+ * device int32 [B + 1] with q_start[B] == T; ids device int64 [T]: the step's input ids, ids[t + 1] is row t's draft).  T is not
+ * limited to 8 here.  uniforms: device fp32 [T][2] = (u_acc, u_draw) per row in place of the Philox words, or NULL.  An id
+ * outside [0, vocab) has mass 0 (it is rejected; nothing is read for it).  Two launches, no scratch.  MI_ERR_ARG: a NULL
+ * pointer but uniforms, B > T, temperature <= 0, top_p outside [0, 1].
+ * mi_forward_verify with batch->sample_temperature > 0 runs it behind the LM head in place of argmax + acceptance, with
+ * sample_top_p (checked as mi_forward checks it), sample_seed and counter = sample_offset (the host passes the index of the verify
+ * step within the generation); the commit is unchanged.  sample_temperature == 0 is launch for launch the greedy step. */
+int mi_verify_sample(const float* logits, int ld, int T, int B, int vocab, const int64_t* ids, const int32_t* q_start,
+                     float temperature, float top_p, uint64_t seed, uint64_t offset, const float* uniforms, int64_t* tokens,
+                     float* logprobs, int32_t* n_accept, mi_stream_t stream);
+
 /* ABI v6 - storage dtypes other than bf16 (reference transformer.py:303,338: `from_folder(dtype=...)` keeps the dtype the
  * caller asks for; the reference's own tests build fp32 models, tests/test_generate.py:51,100) and bf16 models of a shape
  * mi_forward declines with MI_ERR_SHAPE (head_dim != 128, more than 16 experts, top_k = 3).  Same structs, same metadata

@@ -1247,6 +1247,19 @@ int mi_sample_top_p(const float* logits, int ld, int B, int vocab, float tempera
                 "top-p sample");
 }
 
+int mi_verify_sample(const float* logits, int ld, int T, int B, int vocab, const int64_t* ids, const int32_t* q_start,
+                     float temperature, float top_p, uint64_t seed, uint64_t offset, const float* uniforms, int64_t* tokens,
+                     float* logprobs, int32_t* n_accept, mi_stream_t stream) {
+  if (!logits || !ids || !q_start || !tokens || !logprobs || !n_accept || T <= 0 || B <= 0 || B > T || vocab <= 0 || ld < vocab)
+    return fail(MI_ERR_ARG, "mi_verify_sample: logits, ids, q_start and the three outputs; 1 <= B <= T (T %d, B %d), ld >= vocab > 0", T, B);
+  if (!(temperature > 0.f) || !(top_p >= 0.f && top_p <= 1.f))
+    return fail(MI_ERR_ARG, "mi_verify_sample: temperature %g must be > 0 and top_p %g in [0, 1] (generate.py:163)", (double)temperature,
+                (double)top_p);
+  return hip_rc(launch_verify_sample(logits, ld, T, B, vocab, ids, q_start, temperature, top_p, seed, offset, uniforms, tokens,
+                                     logprobs, n_accept, (hipStream_t)stream),
+                "verify sample");
+}
+
 int mi_debug_engine_sabotage(void* workspace, int launches, mi_stream_t stream) {
   if (!workspace || launches < 0) return fail(MI_ERR_ARG, "mi_debug_engine_sabotage");
   static thread_local uint32_t v;
@@ -1347,6 +1360,9 @@ static int check_verify(const char* entry, const mi_model_t* m, const mi_batch_t
   if (bt->branch != MI_BRANCH_PREFILL || !bt->kv_seqlens)
     return fail(MI_ERR_ARG, "%s: a verify step needs a cache: the PREFILL branch with kv_seqlens (branch %d)", entry, bt->branch);
   if (kv_e4m3(bt->kv_layout)) return fail(MI_ERR_UNSUPPORTED, "%s: rings of e4m3 bytes (MI_KV_E4M3) in a verify step are not implemented", entry);
+  // sample_temperature > 0: the step verifies by sampling (mi_verify_sample); top_p as mi_forward checks it
+  if (bt->sample_temperature > 0.f && !(bt->sample_top_p >= 0.f && bt->sample_top_p <= 1.f))
+    return fail(MI_ERR_ARG, "%s: sample_temperature %g / sample_top_p %g", entry, (double)bt->sample_temperature, (double)bt->sample_top_p);
   if (bt->T > GEMV_MAX_T) return fail(MI_ERR_UNSUPPORTED, "%s: T = %d rows; a verify step takes at most %d", entry, bt->T, GEMV_MAX_T);
   if (bt->B > bt->T || bt->max_q_len < 1 || bt->max_q_len > bt->T - bt->B + 1)
     return fail(MI_ERR_ARG, "%s: every sequence brings m_b >= 1 rows (T %d, B %d, max_q_len %d)", entry, bt->T, bt->B, bt->max_q_len);
@@ -1360,7 +1376,8 @@ static int check_verify(const char* entry, const mi_model_t* m, const mi_batch_t
 
 // mi_forward, mi_forward_w8 and mi_forward_w4.  q == nullptr: exactly the launches of mi_forward as they always were.
 // vo != nullptr: a verify step (mi_forward_verify) - the T <= 8 launches of a prefill chunk with the verify attention in place of
-// the prefill attention and NO ring write, then argmax, acceptance and the commit of the accepted rows.
+// the prefill attention and NO ring write, then argmax and acceptance (sample_temperature > 0: the sampled verification) and the
+// commit of the accepted rows.
 // a8 (mi_forward_w8a8, mi_forward_w4a8): x_q | s_x behind the workspace, and the quantised groups of a forward of 256 rows or more
 // take the format's FP8-activation route (W8A8 / W4A8).
 static int forward_body(const char* entry, const mi_model_t* m, const QuantModel* q, const mi_batch_t* bt, mi_stream_t stream,
@@ -1547,9 +1564,15 @@ static int forward_body(const char* entry, const mi_model_t* m, const QuantModel
     if (want_greedy) MI_TRY(sample_step(bt, m, want_topp, engine_ctrl, s));
   }
   if (vo) {
-    MI_TRY(hip_rc(launch_greedy_rows(bt->logits, m->vocab_size, T, m->vocab_size, vo->tokens, vo->logprobs, nullptr, nullptr, 0, nullptr, s),
-                  "verify argmax"));
-    MI_TRY(hip_rc(launch_verify_accept(bt->input_ids, vo->tokens, bt->q_start, B, vo->n_accept, s), "verify accept"));
+    if (bt->sample_temperature > 0.f) {  // sampled verification: accept / residual draw per row, then the scan (mi_verify_sample)
+      MI_TRY(hip_rc(launch_verify_sample(bt->logits, m->vocab_size, T, B, m->vocab_size, bt->input_ids, bt->q_start, bt->sample_temperature,
+                                         bt->sample_top_p, bt->sample_seed, bt->sample_offset, nullptr, vo->tokens, vo->logprobs,
+                                         vo->n_accept, s), "verify sample"));
+    } else {
+      MI_TRY(hip_rc(launch_greedy_rows(bt->logits, m->vocab_size, T, m->vocab_size, vo->tokens, vo->logprobs, nullptr, nullptr, 0, nullptr, s),
+                    "verify argmax"));
+      MI_TRY(hip_rc(launch_verify_accept(bt->input_ids, vo->tokens, bt->q_start, B, vo->n_accept, s), "verify accept"));
+    }
     for (int l0 = 0; l0 < m->n_layers; l0 += VERIFY_COMMIT_LAYERS) {  // (one launch up to 128 layers)
       VerifyCommitArgs c;
       memset(&c, 0, sizeof(c));

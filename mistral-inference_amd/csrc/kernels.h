@@ -320,6 +320,12 @@ hipError_t launch_greedy_rows(const float* logits, int ld, int B, int V, int64_t
 hipError_t launch_sample_top_p(const float* logits, int ld, int B, int V, float temperature, float top_p, uint64_t seed,
                                uint64_t offset, const float* uniforms, int64_t* tok, float* lp, int64_t* hist_tok, float* hist_lp,
                                int hist_len, const uint32_t* ctrl, hipStream_t s);
+// Sampled verification of T logits rows in B sequences (mi_verify_sample), csrc/sampling.hip: one block per row decides accept /
+// residual draw / plain draw against ids[t + 1], then one thread per sequence scans its rows - tok[T], lp[T], n_accept[B].
+// uniforms (nullable): (u_acc, u_draw)[t] instead of the Philox draw keyed by (seed; offset, t).  Two launches.
+hipError_t launch_verify_sample(const float* logits, int ld, int T, int B, int V, const int64_t* ids, const int32_t* q_start,
+                                float temperature, float top_p, uint64_t seed, uint64_t offset, const float* uniforms, int64_t* tok,
+                                float* lp, int32_t* n_accept, hipStream_t s);
 // control words of a workspace after a raised engine status: status / abort / arrivals cleared, epoch advanced
 hipError_t launch_engine_ctrl_reset(uint32_t* ctrl, hipStream_t s);
 

@@ -23,6 +23,10 @@
 //
 // The sample is written where the greedy sample goes (token buffer that the next step reads as its input ids, logprob,
 // history rings): the decode loop of generate() at temperature > 0 is then ONE native call per token as well.
+//
+// The same passes serve the verify step of speculative decoding at temperature > 0 (verify_sample_kernel below, the rule of
+// include/mistral_hip.h `mi_verify_sample`): the kernel body is three pieces - nucleus_of, mass_offset, token_at - and a row
+// that holds a draft adds only what it needs of that draft to the total-mass pass.
 #include "common.cuh"
 #include "kernels.h"
 
@@ -171,7 +175,7 @@ struct Sel {
 // spread over lane-dependent bins (no same-address contention), changed nothing, and fusing the total-mass pass into the
 // first histogram pass did not either).
 template <class F>
-__device__ __forceinline__ void for_logits(const Row& r, F&& f) {
+__device__ __forceinline__ void for_logits_at(const Row& r, F&& f) {  // f(value, token id)
   if ((r.V & 3) == 0 && (reinterpret_cast<size_t>(r.x) & 15) == 0) {
     const int V4 = r.V >> 2;
     for (int q = threadIdx.x; q < V4; q += 4 * ST) {
@@ -181,15 +185,20 @@ __device__ __forceinline__ void for_logits(const Row& r, F&& f) {
 #pragma unroll
       for (int k = 0; k < 4; ++k)
         if (q + k * ST < V4) {
-          f(v[k].x);
-          f(v[k].y);
-          f(v[k].z);
-          f(v[k].w);
+          const int i = (q + k * ST) * 4;
+          f(v[k].x, i);
+          f(v[k].y, i + 1);
+          f(v[k].z, i + 2);
+          f(v[k].w, i + 3);
         }
     }
   } else {
-    for (int i = threadIdx.x; i < r.V; i += ST) f(r.x[i]);
+    for (int i = threadIdx.x; i < r.V; i += ST) f(r.x[i], i);
   }
+}
+template <class F>
+__device__ __forceinline__ void for_logits(const Row& r, F&& f) {
+  for_logits_at(r, [&](float xv, int) { f(xv); });
 }
 
 __device__ Sel select_pos(const Row& r, uint32_t lo, uint32_t hi, unsigned long long target, uint32_t cnt0, Scratch& sc) {
@@ -250,21 +259,18 @@ __device__ Sel select_pos(const Row& r, uint32_t lo, uint32_t hi, unsigned long 
   return Sel{lo, cnt, above};
 }
 
-__global__ __launch_bounds__(ST) void sample_top_p_kernel(const float* logits, int ld, int B, int V, float temperature, float top_p,
-                                                         unsigned long long seed, unsigned long long offset,
-                                                         const float* uniforms, int64_t* tok, float* lp, int64_t* hist_tok,
-                                                         float* hist_lp, int hist_len, const uint32_t* ctrl) {
-  __shared__ Scratch sc;
-  // Behind the persistent decode engine: a launch that failed its residency gate (status 0x700) wrote nothing - no logits, no
-  // step count - and poisons the workspace until the host has re-run the step on the launch path (GreedySession._recover).
-  // Drawing from whatever the logits buffer holds would overwrite `tok`, which is the NEXT step's input id and the id the
-  // recovery re-runs from.  (The stand-alone mi_sample_top_p passes no control block.)
-  if (ctrl && ctrl[CTRL_STATUS] != 0) return;
-  const int b = blockIdx.x;
-  Row r;
-  r.x = logits + (size_t)b * ld;
-  r.V = V;
-  r.temperature = temperature;
+// What one row's nucleus is (block-uniform): M = max of the UNSCALED logits, S1 = sum exp(x - M) (generate.py:134), the cut
+// (key value v*, mass above it, tokens tied at it), n_keep = how many of the ties are kept (ascending id), kept = the kept mass.
+struct Nucleus {
+  float M, S1;
+  uint32_t khi;
+  Sel cut;
+  unsigned long long n_keep, kept;
+};
+// Passes 1 and 2 over the row and the select of the cut; false for a row of NaN (nothing to draw from).  `extra(value, id)`
+// rides on the total-mass pass (the verify kernel measures its draft there); it runs once per token, r.ms is set.
+template <class F>
+__device__ __forceinline__ bool nucleus_of(Row& r, float top_p, Scratch& sc, Nucleus& n, F&& extra) {
   // ---- pass 1: maxima and key range
   float M = -INFINITY;
   uint32_t klo = 0xffffffffu, khi = 0u;
@@ -278,51 +284,56 @@ __global__ __launch_bounds__(ST) void sample_top_p_kernel(const float* logits, i
   });
   M = block_max(M, sc);
   block_minmax_u32(klo, khi, sc);
-  if (klo > khi) {  // a row of NaN: nothing to draw from (torch.multinomial raises); token 0, logprob NaN
-    if (threadIdx.x == 0) {
-      tok[b] = 0;
-      lp[b] = __uint_as_float(0x7fc00000u);
-    }
-    return;
-  }
-  r.ms = M / temperature;
+  if (klo > khi) return false;
+  r.ms = M / r.temperature;
   // ---- pass 2: total mass (fixed point) and the log-sum-exp of the UNSCALED logits (generate.py:134)
   unsigned long long S = 0;
   float S1 = 0.f;
-  for_logits(r, [&](float xv) {
+  for_logits_at(r, [&](float xv, int i) {
     S += r.q(xv);
     if (xv == xv) S1 += expf(xv - M);
+    extra(xv, i);
   });
   S = block_sum_u64(S, sc);
   S1 = block_sum_f(S1, sc);
   // ---- the nucleus: last position with mass-before <= p * total (generate.py:166 `probs_sum - probs_sort > p` is dropped)
   const double pt = (double)top_p * (double)S;
   const unsigned long long target = pt >= (double)S ? S : (unsigned long long)pt;
-  const Sel cut = select_pos(r, klo, khi, target, (uint32_t)V, sc);
+  const Sel cut = select_pos(r, klo, khi, target, (uint32_t)r.V, sc);
   const unsigned long long qcut = r.q(float_of(cut.key));
   unsigned long long n_keep = cut.cnt;
   if (qcut > 0) {
     const unsigned long long fit = (target - cut.above) / qcut + 1ull;  // tied tokens whose mass-before is still <= target
     n_keep = fit < n_keep ? fit : n_keep;
   }
-  const unsigned long long kept = cut.above + n_keep * qcut;  // > 0: the mode alone has mass 2^40
-  // ---- the draw (generate.py:168 torch.multinomial on the renormalised kept masses): r uniform in [0, kept)
-  double u;
-  if (uniforms) {
-    u = (double)uniforms[b];
-  } else {
-    uint32_t rnd[4];
-    const unsigned long long step = ctrl ? (unsigned long long)ctrl[CTRL_STEPS] : 0ull;
-    Philox::draw(seed, offset + step, (uint32_t)b, rnd);
-    u = ((double)rnd[0] * 4294967296.0 + (double)rnd[1]) * (1.0 / 18446744073709551616.0);
-  }
+  n.M = M;
+  n.S1 = S1;
+  n.khi = khi;
+  n.cut = cut;
+  n.n_keep = n_keep;
+  n.kept = cut.above + n_keep * qcut;  // > 0: the mode alone has mass 2^40
+  return true;
+}
+
+// u in [0, 1) as a mass offset in [0, mass): the inverse CDF's argument (generate.py:168 torch.multinomial on the kept masses)
+__device__ __forceinline__ unsigned long long mass_offset(double u, unsigned long long mass) {
   u = u < 0.0 ? 0.0 : u;
-  unsigned long long rr = (unsigned long long)(u * (double)kept);
-  if (rr >= kept) rr = kept - 1;
-  const Sel pick = select_pos(r, cut.key, khi, rr, cut.cnt, sc);   // (never below the cut: rr < kept)
+  const unsigned long long rr = (unsigned long long)(u * (double)mass);
+  return rr >= mass ? mass - 1 : rr;
+}
+__device__ __forceinline__ double unit_of(uint32_t hi, uint32_t lo) {
+  return ((double)hi * 4294967296.0 + (double)lo) * (1.0 / 18446744073709551616.0);
+}
+
+// The kept token at mass offset rr < n.kept (descending value, ties by ascending id): the thread that owns it calls
+// emit(token id, log_softmax(logits)[token]) - exactly one thread of the block does.
+template <class E>
+__device__ __forceinline__ void token_at(const Row& r, const Nucleus& n, unsigned long long rr, Scratch& sc, E&& emit) {
+  const int V = r.V;
+  const Sel pick = select_pos(r, n.cut.key, n.khi, rr, n.cut.cnt, sc);   // (never below the cut: rr < kept)
   const unsigned long long qp = r.q(float_of(pick.key));
   unsigned long long rank = qp > 0 ? (rr - pick.above) / qp : 0ull;
-  const unsigned long long lim = (pick.key == cut.key ? n_keep : (unsigned long long)pick.cnt) - 1ull;
+  const unsigned long long lim = (pick.key == n.cut.key ? n.n_keep : (unsigned long long)pick.cnt) - 1ull;
   rank = rank > lim ? lim : rank;
   // ---- index of the rank-th token (ascending index) whose key is pick.key: thread t owns indices [t * per, t * per + per)
   const int per = (V + ST - 1) / ST;
@@ -348,20 +359,162 @@ __global__ __launch_bounds__(ST) void sample_top_p_kernel(const float* logits, i
     for (int i = i0; i < i1; ++i) {
       if (key_of(r.x[i]) == pick.key) {
         if (seen == rank) {
-          const float l = r.x[i] - M - logf(S1);  // log_softmax(logits)[token] (generate.py:134-136)
-          tok[b] = i;
-          lp[b] = l;
-          if (hist_tok && hist_len > 0 && ctrl) {
-            const uint32_t step = (ctrl[CTRL_STEPS] - 1u) % (uint32_t)hist_len;
-            hist_tok[(size_t)step * B + b] = i;
-            hist_lp[(size_t)step * B + b] = l;
-          }
+          emit(i, r.x[i] - n.M - logf(n.S1));  // log_softmax(logits)[token] (generate.py:134-136)
           break;
         }
         ++seen;
       }
     }
   }
+}
+
+__global__ __launch_bounds__(ST) void sample_top_p_kernel(const float* logits, int ld, int B, int V, float temperature, float top_p,
+                                                         unsigned long long seed, unsigned long long offset,
+                                                         const float* uniforms, int64_t* tok, float* lp, int64_t* hist_tok,
+                                                         float* hist_lp, int hist_len, const uint32_t* ctrl) {
+  __shared__ Scratch sc;
+  // Behind the persistent decode engine: a launch that failed its residency gate (status 0x700) wrote nothing - no logits, no
+  // step count - and poisons the workspace until the host has re-run the step on the launch path (GreedySession._recover).
+  // Drawing from whatever the logits buffer holds would overwrite `tok`, which is the NEXT step's input id and the id the
+  // recovery re-runs from.  (The stand-alone mi_sample_top_p passes no control block.)
+  if (ctrl && ctrl[CTRL_STATUS] != 0) return;
+  const int b = blockIdx.x;
+  Row r;
+  r.x = logits + (size_t)b * ld;
+  r.V = V;
+  r.temperature = temperature;
+  Nucleus n;
+  if (!nucleus_of(r, top_p, sc, n, [](float, int) {})) {  // a row of NaN (torch.multinomial raises); token 0, logprob NaN
+    if (threadIdx.x == 0) {
+      tok[b] = 0;
+      lp[b] = __uint_as_float(0x7fc00000u);
+    }
+    return;
+  }
+  // ---- the draw: r uniform in [0, kept)
+  double u;
+  if (uniforms) {
+    u = (double)uniforms[b];
+  } else {
+    uint32_t rnd[4];
+    const unsigned long long step = ctrl ? (unsigned long long)ctrl[CTRL_STEPS] : 0ull;
+    Philox::draw(seed, offset + step, (uint32_t)b, rnd);
+    u = unit_of(rnd[0], rnd[1]);
+  }
+  token_at(r, n, mass_offset(u, n.kept), sc, [&](int i, float l) {
+    tok[b] = i;
+    lp[b] = l;
+    if (hist_tok && hist_len > 0 && ctrl) {
+      const uint32_t step = (ctrl[CTRL_STEPS] - 1u) % (uint32_t)hist_len;
+      hist_tok[(size_t)step * B + b] = i;
+      hist_lp[(size_t)step * B + b] = l;
+    }
+  });
+}
+
+// Verify step at temperature > 0 (include/mistral_hip.h, mi_verify_sample): block t decides row t of the step on its own.
+// Row t of sequence b scores the token after ids[t]; when row t + 1 belongs to the same sequence, d = ids[t + 1] is the draft
+// for it.  With P = the nucleus distribution above, M = its kept mass and mass(d) = d's fixed-point mass if d is kept, else 0:
+//   * a drafted row ACCEPTS iff floor(u_acc * M) < mass(d) - it emits d; otherwise it emits the inverse-CDF draw with u_draw
+//     from P without d: the same select with d's mass taken out of the running sums, i.e. the offset in [0, M - mass(d))
+//     is moved past d when it reaches d's place in the order (mass above d's value + its rank among its ties * its mass);
+//   * the last row of a sequence has no draft and emits the plain draw with u_draw.
+// Only the draw the row can use is computed.  What a row needs of its draft - the mass above its value and its rank by id among
+// the tokens tied with it - rides on the total-mass pass.  No global scratch: a REJECTING row writes its token as ~token (< 0)
+// into tok[t], and the scan kernel below, which stops a sequence at its first negative entry, puts the token back.
+__global__ __launch_bounds__(ST) void verify_sample_kernel(const float* logits, int ld, int T, int B, int V, const int64_t* ids,
+                                                          const int32_t* q_start, float temperature, float top_p,
+                                                          unsigned long long seed, unsigned long long offset,
+                                                          const float* uniforms, int64_t* tok, float* lp) {
+  __shared__ Scratch sc;
+  const int t = blockIdx.x;
+  Row r;
+  r.x = logits + (size_t)t * ld;
+  r.V = V;
+  r.temperature = temperature;
+  // row t + 1 is a draft for this row unless it opens a sequence: the first boundary q_start[j] >= t + 1, 1 <= j <= B
+  bool drafted = false;
+  if (t + 1 < T) {
+    int lo = 1, hi = B;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (q_start[mid] >= t + 1) hi = mid; else lo = mid + 1;
+    }
+    drafted = q_start[lo] != t + 1;
+  }
+  // the draft: an id outside the vocabulary or a NaN logit has mass 0 (the host range-checks ids; nothing is read out of bounds)
+  const int64_t d64 = drafted ? ids[t + 1] : -1;
+  const bool d_in = d64 >= 0 && d64 < (int64_t)V;
+  const int d = d_in ? (int)d64 : -1;
+  const float xd = d_in ? r.x[d] : __uint_as_float(0x7fc00000u);
+  const bool d_num = xd == xd;
+  const uint32_t kd = d_num ? key_of(xd) : 0xffffffffu;  // (NaN bits: no logit's key - a number's never has all bits set)
+  unsigned long long above_d = 0, rank_d = 0;
+  Nucleus n;
+  const bool ok = nucleus_of(r, top_p, sc, n, [&](float xv, int i) {
+    const uint32_t k = key_of(xv);
+    if (k > kd) above_d += r.q(xv);
+    rank_d += (k == kd && i < d);
+  });
+  const float nan = __uint_as_float(0x7fc00000u);
+  if (!ok) {  // a row of NaN: token 0, logprob NaN as the plain sampler; a drafted row rejects
+    if (threadIdx.x == 0) {
+      tok[t] = drafted ? ~(int64_t)0 : 0;
+      lp[t] = nan;
+    }
+    return;
+  }
+  double u_acc, u_draw;
+  if (uniforms) {
+    u_acc = (double)uniforms[2 * t];
+    u_draw = (double)uniforms[2 * t + 1];
+  } else {
+    uint32_t rnd[4];
+    Philox::draw(seed, offset, (uint32_t)t, rnd);
+    u_draw = unit_of(rnd[0], rnd[1]);  // the words of the plain sampler's variate
+    u_acc = unit_of(rnd[2], rnd[3]);
+  }
+  unsigned long long rr;
+  if (drafted) {
+    above_d = block_sum_u64(above_d, sc);
+    rank_d = block_sum_u64(rank_d, sc);
+    const unsigned long long qd = d_num ? r.q(xd) : 0ull;
+    const bool d_kept = d_num && (kd > n.cut.key || (kd == n.cut.key && rank_d < n.n_keep));
+    const unsigned long long mass_d = d_kept ? qd : 0ull;
+    if (mass_offset(u_acc, n.kept) < mass_d) {  // accept: u_acc * M < mass(d)
+      if (threadIdx.x == 0) {
+        tok[t] = d;
+        lp[t] = xd - n.M - logf(n.S1);
+      }
+      return;
+    }
+    // reject (mass_d < kept: a sole survivor is always accepted): the residual draw
+    rr = mass_offset(u_draw, n.kept - mass_d);
+    if (mass_d > 0 && rr >= above_d + rank_d * qd) rr += mass_d;
+  } else {
+    rr = mass_offset(u_draw, n.kept);
+  }
+  token_at(r, n, rr, sc, [&](int i, float l) {
+    tok[t] = drafted ? ~(int64_t)i : (int64_t)i;
+    lp[t] = l;
+  });
+}
+
+// The sampling counterpart of verify_accept_kernel: thread b walks sequence b's rows as verify_sample_kernel left them -
+// n_accept[b] = the rows before its first rejecting (negative) entry or its last row; that row's token is restored, and the
+// rows behind it emit nothing (token -1, logprob 0).
+__global__ void verify_sample_scan_kernel(const int32_t* q_start, int B, int64_t* tok, float* lp, int32_t* n_accept) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int q0 = q_start[b], m = q_start[b + 1] - q0;
+  int a = 0;
+  while (a + 1 < m && tok[q0 + a] >= 0) ++a;
+  if (m > 0 && tok[q0 + a] < 0) tok[q0 + a] = ~tok[q0 + a];
+  for (int i = a + 1; i < m; ++i) {
+    tok[q0 + i] = -1;
+    lp[q0 + i] = 0.f;
+  }
+  n_accept[b] = a;
 }
 
 }  // namespace
@@ -371,5 +524,16 @@ hipError_t launch_sample_top_p(const float* logits, int ld, int B, int V, float 
                                int hist_len, const uint32_t* ctrl, hipStream_t s) {
   hipLaunchKernelGGL(sample_top_p_kernel, dim3(B), dim3(ST), 0, s, logits, ld, B, V, temperature, top_p,
                      (unsigned long long)seed, (unsigned long long)offset, uniforms, tok, lp, hist_tok, hist_lp, hist_len, ctrl);
+  return hipGetLastError();
+}
+
+hipError_t launch_verify_sample(const float* logits, int ld, int T, int B, int V, const int64_t* ids, const int32_t* q_start,
+                                float temperature, float top_p, uint64_t seed, uint64_t offset, const float* uniforms, int64_t* tok,
+                                float* lp, int32_t* n_accept, hipStream_t s) {
+  hipLaunchKernelGGL(verify_sample_kernel, dim3(T), dim3(ST), 0, s, logits, ld, T, B, V, ids, q_start, temperature, top_p,
+                     (unsigned long long)seed, (unsigned long long)offset, uniforms, tok, lp);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(verify_sample_scan_kernel, dim3((B + 63) / 64), dim3(64), 0, s, q_start, B, tok, lp, n_accept);
   return hipGetLastError();
 }

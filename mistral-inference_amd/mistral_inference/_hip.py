@@ -179,6 +179,8 @@ _SIGS = {
     "mi_workspace_bytes_verify": (C.c_size_t, [C.POINTER(MiModel), C.c_int, C.c_int, C.c_int, C.c_int]),
     "mi_forward_verify": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiW8Model), C.POINTER(MiW4Model), C.POINTER(MiBatch),
                                     C.POINTER(MiVerifyOut), _vp]),
+    "mi_verify_sample": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_float, C.c_float, C.c_uint64, C.c_uint64,
+                                   _vp, _vp, _vp, _vp, _vp]),
     "mi_workspace_bytes_generic": (C.c_size_t, [C.POINTER(MiModel), C.c_int, C.c_int]),  # ABI v6
     "mi_forward_generic": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiBatch), C.c_int, _vp]),
     "mi_embedding_generic": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
@@ -727,6 +729,31 @@ def sample_top_p(logits: torch.Tensor, temperature: float, top_p: float, seed: i
                                 int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), dev_ptr(uniforms, torch.float32),
                                 dev_ptr(tok, torch.long), dev_ptr(lp, torch.float32), stream_ptr(logits.device)), "mi_sample_top_p")
     return tok, lp
+
+
+def verify_sample(logits: torch.Tensor, ids: torch.Tensor, q_start: torch.Tensor, temperature: float, top_p: float, seed: int = 0,
+                  offset: int = 0, uniforms: Optional[torch.Tensor] = None):
+    """(tokens int64 [T], logprobs fp32 [T], n_accept int32 [B]) on the device: the sampled verification rule of
+    include/mistral_hip.h `mi_verify_sample` on T fp32 logits rows in B sequences (q_start int32 [B + 1], ids int64 [T]: the step's
+    input ids).  `uniforms` (fp32 [T, 2] = (u_acc, u_draw) in [0, 1)) replaces the Philox variates."""
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1
+    T, V = logits.shape
+    dev = logits.device
+    ids = torch.as_tensor(ids).to(device=dev, dtype=torch.long).contiguous()
+    q_start = torch.as_tensor(q_start).to(device=dev, dtype=torch.int32).contiguous()
+    B = q_start.numel() - 1
+    assert ids.numel() == T
+    tok = torch.empty(T, dtype=torch.long, device=dev)
+    lp = torch.empty(T, dtype=torch.float32, device=dev)
+    n_acc = torch.empty(max(B, 1), dtype=torch.int32, device=dev)
+    if uniforms is not None:
+        uniforms = uniforms.to(device=dev, dtype=torch.float32).contiguous()
+        assert uniforms.shape == (T, 2)
+    check(lib().mi_verify_sample(dev_ptr(logits, torch.float32), logits.stride(0), T, B, V, dev_ptr(ids, torch.long),
+                                 dev_ptr(q_start, torch.int32), float(temperature), float(top_p), int(seed) & (2 ** 64 - 1),
+                                 int(offset) & (2 ** 64 - 1), dev_ptr(uniforms, torch.float32), dev_ptr(tok, torch.long),
+                                 dev_ptr(lp, torch.float32), dev_ptr(n_acc, torch.int32), stream_ptr(dev)), "mi_verify_sample")
+    return tok, lp, n_acc[:B]
 
 
 def gelu_(x: torch.Tensor) -> torch.Tensor:

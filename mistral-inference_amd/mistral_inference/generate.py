@@ -24,14 +24,21 @@ from .transformer import Transformer
 
 @dataclass
 class SpeculativeArgs:
-    """Speculative greedy decoding for `generate(speculative=...)`: every step drafts up to `k` tokens on the host and the model
+    """Speculative decoding for `generate(speculative=...)`: every step drafts up to `k` tokens on the host and the model
     scores them in ONE pass over its weights (`Transformer.verify_step`), keeping the drafts its own argmaxes confirm - the
     tokens are those of the plain greedy loop.  The default drafter is prompt lookup (`ngram_draft`); `drafter` replaces it with
-    any callable history -> drafts (history: prompt plus everything emitted so far; more than `k` drafts are cut)."""
+    any callable history -> drafts (history: prompt plus everything emitted so far; more than `k` drafts are cut).
+
+    `sample=True` opts in to speculation at temperature > 0 (without it such a call is refused): a verify step then accepts a
+    draft with its probability under the nucleus distribution and draws a replacement from the rest of that distribution at the
+    first rejection (include/mistral_hip.h, `mi_verify_sample`).  What changes against the plain sampling loop: the generation
+    has the plain sampler's DISTRIBUTION and is reproducible per `torch.manual_seed`, but it is not the plain sampler's tokens
+    for a given seed.  At temperature 0 `sample` changes nothing: the greedy path."""
     k: int = 3
     ngram_max: int = 3
     ngram_min: int = 1
     drafter: Optional[Callable[[List[int]], Sequence[int]]] = None
+    sample: bool = False
 
     def __post_init__(self) -> None:
         if not 1 <= self.k <= 7:
@@ -57,11 +64,12 @@ def ngram_draft(history: Sequence[int], k: int, ngram_max: int = 3, ngram_min: i
     return []
 
 
-def refuse_speculative(model, n_prompts: int, temperature: float, kv_dtype: Optional[torch.dtype]) -> None:
+def refuse_speculative(model, n_prompts: int, temperature: float, kv_dtype: Optional[torch.dtype],
+                       speculative: Optional[SpeculativeArgs] = None) -> None:
     """What generate(speculative=...) does not take, by name, before anything runs."""
-    if temperature > 0:
-        raise NotImplementedError(f"speculative decoding at temperature {temperature} > 0 (sampling with rejection) is not implemented; "
-                                  "it is greedy: pass temperature=0")
+    if temperature > 0 and not (speculative is not None and speculative.sample):
+        raise NotImplementedError(f"speculative decoding at temperature {temperature} > 0 verifies by sampling, which changes the tokens "
+                                  "a seed gives (not their distribution): opt in with SpeculativeArgs(sample=True), or pass temperature=0")
     if n_prompts != 1:
         raise NotImplementedError(f"speculative decoding of {n_prompts} prompts is not implemented: one prompt per call")
     if kv_dtype == torch.float8_e4m3fn:
@@ -101,10 +109,11 @@ def generate(
     kv_dtype: Optional[torch.dtype] = None,
     speculative: Optional[SpeculativeArgs] = None,
 ) -> Tuple[List[List[int]], List[List[float]]]:
-    # speculative (temperature 0, one prompt, bf16 rings, one stage): the decode loop runs verify steps - see SpeculativeArgs; the
-    # returned tokens, log-probs, max_tokens truncation and EOS stop are the plain loop's.  None: the plain loop.
+    # speculative (one prompt, bf16 rings, one stage; temperature > 0 only with sample=True): the decode loop runs verify steps -
+    # see SpeculativeArgs; at temperature 0 the returned tokens and log-probs are the plain loop's, at temperature > 0 their
+    # distribution is; max_tokens truncation and EOS stop are the plain loop's.  None: the plain loop.
     if speculative is not None:
-        refuse_speculative(model, len(encoded_prompts), temperature, kv_dtype)
+        refuse_speculative(model, len(encoded_prompts), temperature, kv_dtype, speculative)
     # kv_dtype: dtype of the K/V rings; None: the model's.  torch.float8_e4m3fn (bf16 models on the tuned path): rings of e4m3 bytes
     # at half the size, written and read by the rule of cache.kv_quantize / kv_dequantize; such a generation takes the launch path.
     kv_dtype = check_kv_dtype(kv_dtype, model.dtype)   # (before anything is pinned or allocated)
@@ -281,22 +290,29 @@ def _agree_seed(model) -> int:
 # ---- the three decoders: (model, cache, last_token_prelogits, max_tokens > 0, temperature, eos_id, ...)
 def _decode_speculative(model, cache: BufferCache, last_token_prelogits: torch.Tensor, max_tokens: int, temperature: float,
                         eos_id: Optional[int], speculative: SpeculativeArgs, prompt: List[int]) -> Tuple[List[int], List[float]]:
-    """One prompt, temperature 0: (tokens, logprobs) as host lists.  Token 0 comes from the prompt's last logits as in the
-    plain loop; every later step scores [last emitted token] + drafts and emits the argmaxes of the confirmed rows.  One
-    synchronisation per step (n_accept), which also brings the tokens."""
+    """One prompt: (tokens, logprobs) as host lists.  Token 0 comes from the prompt's last logits as in the plain loop; every
+    later step scores [last emitted token] + drafts and emits the rows the step confirms - at temperature 0 the argmaxes, at
+    temperature > 0 (SpeculativeArgs.sample) the sampled verification with one seed per generation from torch's default
+    generator and the step's index as the Philox counter.  One synchronisation per step (n_accept), which also brings the tokens."""
     V, dev = model.args.vocab_size, model.device
-    t0, lp0 = _first_token(last_token_prelogits, temperature)
+    seed = _agree_seed(model) if temperature > 0 else 0
+    t0, lp0 = _first_token(last_token_prelogits, temperature, seed)
     toks, lps = [int(t0[0])], [float(lp0[0])]
     if eos_id is not None and toks[0] == eos_id:
         return [], []
     history = list(prompt) + toks
     done = False
+    step = 0
     while not done and len(toks) < max_tokens:
         drafts = speculative.draft(history)[: max_tokens - len(toks) - 1]
         if any(d < 0 or d >= V for d in drafts):
             raise IndexError("index out of range in self (a drafted token)")
         ids = torch.tensor([history[-1]] + drafts, device=dev, dtype=torch.long)
-        tok, lp, n_accept = model.verify_step(ids, [len(drafts) + 1], cache)
+        if temperature > 0:
+            tok, lp, n_accept = model.verify_step(ids, [len(drafts) + 1], cache, temperature=temperature, top_p=0.8, seed=seed, offset=step)
+        else:
+            tok, lp, n_accept = model.verify_step(ids, [len(drafts) + 1], cache)
+        step += 1
         new_t, new_lp = tok[: n_accept[0] + 1].tolist(), lp[: n_accept[0] + 1].tolist()
         for t, l in zip(new_t, new_lp):
             if eos_id is not None and t == eos_id:  # generate.py:128-132: the EOS token itself is not returned

@@ -6,6 +6,7 @@ gets the explicit backend "nccl" -- on ROCm that is RCCL, which runs the stage-t
 logits broadcast over xGMI.  Tokenisation is delegated to `mistral_common` exactly as in the reference and
 is imported lazily (it is CPU string processing outside the hot path; benchmarks feed token ids).
 """
+import dataclasses
 import json
 import logging
 import os
@@ -89,13 +90,16 @@ def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7,
                 prefill_w4a8: bool = False) -> None:
     """quantize="fp8_e4m3" / "mxfp4": quantise a bf16 checkpoint to weight-only FP8 / MXFP4 while it loads (a folder that
     quant.quantize_checkpoint wrote needs no flag).  kv_dtype="fp8_e4m3": K/V rings of e4m3 bytes (half the bytes; launch path).
-    speculative=K: greedy decoding that drafts up to K tokens per step by prompt lookup and verifies them in one pass over the
-    weights (needs temperature 0; generate() names what else it does not take).  prefill_fp8: FP8 (e4m3) weights only - prompt
+    speculative=K: decoding that drafts up to K tokens per step by prompt lookup and verifies them in one pass over the
+    weights (at temperature > 0 by sampling - SpeculativeArgs.sample: the sampler's distribution, not its tokens for a seed;
+    generate() names what it does not take).  prefill_fp8: FP8 (e4m3) weights only - prompt
     chunks of 256 tokens or more also quantise their activations per token and run on the FP8 MFMA (quant.py; a speed option, no
     claim about model quality).  prefill_w4a8: the same for MXFP4 weights - the e2m1 codes meet the e4m3 activations on the mixed
     FP4 x FP8 MFMA, block scales applied by the instruction."""
     kv = kv_dtype_arg(kv_dtype)  # (an unknown name is refused before anything is loaded)
     spec = speculative_arg(speculative)
+    if spec is not None and temperature > 0:  # (the tool's user asked for both: sampled verify steps)
+        spec = dataclasses.replace(spec, sample=True)
     num_pipeline_ranks = init_pipeline() if is_torchrun() else num_pipeline_ranks
     should_print = _should_print()
     mistral_tokenizer = load_tokenizer(Path(model_path))
@@ -139,6 +143,8 @@ def demo(model_path: str, max_tokens: int = 35, temperature: float = 0, lora_pat
     """quantize, kv_dtype, speculative, prefill_fp8, prefill_w4a8: as `interactive` (a speculative generation takes one prompt: the three run one by one)."""
     kv = kv_dtype_arg(kv_dtype)
     spec = speculative_arg(speculative)
+    if spec is not None and temperature > 0:  # (the tool's user asked for both: sampled verify steps)
+        spec = dataclasses.replace(spec, sample=True)
     num_pipeline_ranks = init_pipeline()
     should_print = _should_print()
     model = get_model_cls(model_path).from_folder(Path(model_path), max_batch_size=3,

@@ -301,9 +301,11 @@ class HipStackBackend:
     def run_stack(self, model: "Transformer", h: torch.Tensor, input_ids: Optional[torch.Tensor],
                   meta: BatchMetadata, cache: Optional[BufferCache], logits: Optional[torch.Tensor],
                   greedy: Optional["GreedyBuffers"] = None, seq_adapter: Any = "now",
-                  verify: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None) -> None:
+                  verify: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None, *, temperature: float = 0.0,
+                  top_p: float = 0.8, seed: int = 0, offset: int = 0) -> None:
         """seq_adapter: the [B] adapter-slot tensor this launch carries (None: NULL); "now": what set_adapters chose last.
-        verify: (tokens int64 [T], logprobs fp32 [T], n_accept int32 [B]) - the launch is a verify step (mi_forward_verify)."""
+        verify: (tokens int64 [T], logprobs fp32 [T], n_accept int32 [B]) - the launch is a verify step (mi_forward_verify);
+        temperature > 0 (a verify step only): it verifies by sampling with (top_p, seed, counter = offset) - mi_verify_sample."""
         m = self.plan(model)
         T, B = h.shape[0], len(meta.seqlens)
         bt = _hip.MiBatch()
@@ -343,6 +345,9 @@ class HipStackBackend:
         wsb = self._get_workspace(model, m, T, B, max_w, bt.kv_layout, verify=verify is not None)
         bt.workspace, bt.workspace_bytes = wsb.data_ptr(), wsb.numel()
         if verify is not None:
+            if temperature > 0:  # (the greedy buffers are NULL in a verify step: these fields mean the sampled verification)
+                bt.sample_temperature, bt.sample_top_p = float(temperature), float(top_p)
+                bt.sample_seed, bt.sample_offset = int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1)
             vo = _hip.MiVerifyOut()
             vo.tokens, vo.logprobs = _hip.dev_ptr(verify[0], torch.long), _hip.dev_ptr(verify[1], torch.float32)
             vo.n_accept = _hip.dev_ptr(verify[2], i32)
@@ -644,22 +649,30 @@ class Transformer(ModelBase):
             raise NotImplementedError("speculative decoding on an FP8 K/V cache (kv_dtype=float8_e4m3fn) is not implemented; "
                                       "use the model's own bf16 rings")
 
-    def verify_step(self, ids: torch.Tensor, seqlens: List[int], cache: BufferCache, return_logits: bool = False):
-        """One verify step of speculative greedy decoding (include/mistral_hip.h `mi_forward_verify`): sequence b brings
+    def verify_step(self, ids: torch.Tensor, seqlens: List[int], cache: BufferCache, return_logits: bool = False, *,
+                    temperature: float = 0.0, top_p: float = 0.8, seed: int = 0, offset: int = 0):
+        """One verify step of speculative decoding (include/mistral_hip.h `mi_forward_verify`): sequence b brings
         seqlens[b] <= 8 rows - its last emitted token, not yet cached, then drafted tokens - at the positions behind its cache.
         Returns (tokens int64 [T], logprobs fp32 [T], n_accept list [B]): the argmax of every row and its log-softmax; the
         first n_accept[b] + 1 of sequence b's rows are the tokens it emits.  Exactly those rows' K/V entered the rings and
         the cache advanced by n_accept[b] + 1; a rejected draft leaves no trace.  One synchronisation (reading n_accept).
-        return_logits: also the fp32 logits [T, vocab] of every row, as a fourth value."""
-        tok, lp, n_acc, logits = self._verify_launch(ids, seqlens, cache)
+        return_logits: also the fp32 logits [T, vocab] of every row, as a fourth value.
+        temperature > 0: the step verifies by SAMPLING (`mi_verify_sample`'s rule): a draft is accepted with its probability under
+        the nucleus distribution of (temperature, top_p), the first rejected row emits a draw from that distribution without the
+        draft, a row behind all drafts a plain draw; rows behind a rejection hold token -1.  Variates: Philox(seed; counter =
+        offset, row) - `offset` is the index of the verify step within the generation."""
+        tok, lp, n_acc, logits = self._verify_launch(ids, seqlens, cache, temperature=temperature, top_p=top_p, seed=seed, offset=offset)
         n_accept = [int(a) for a in n_acc.tolist()]  # the one synchronisation
         cache.advance_host([a + 1 for a in n_accept])  # (the commit kernel advanced the device copy)
         return (tok, lp, n_accept, logits) if return_logits else (tok, lp, n_accept)
 
-    def _verify_launch(self, ids: torch.Tensor, seqlens: List[int], cache: BufferCache):
+    def _verify_launch(self, ids: torch.Tensor, seqlens: List[int], cache: BufferCache, *, temperature: float = 0.0,
+                       top_p: float = 0.8, seed: int = 0, offset: int = 0):
         """The launches of a verify step, nothing read back: (tokens, logprobs, n_accept, logits) on the device.  The device
         kv_seqlens are advanced by the commit kernel; the host mirror is the caller's to advance (verify_step does)."""
         self.refuse_verify(cache)
+        if temperature < 0 or (temperature > 0 and not 0 <= top_p <= 1):
+            raise ValueError(f"a verify step takes temperature >= 0 and top_p in [0, 1], got {temperature} / {top_p}")
         T, B = sum(seqlens), len(seqlens)
         if any(s < 1 for s in seqlens) or T > _hip.GEMV_MAX_T:
             raise ValueError(f"a verify step takes 1 .. {_hip.GEMV_MAX_T} rows in all and at least one per sequence, got {seqlens}")
@@ -675,7 +688,7 @@ class Transformer(ModelBase):
         lp = torch.empty(T, device=dev, dtype=torch.float32)
         n_acc = torch.empty(B, device=dev, dtype=torch.int32)
         self._backend.run_stack(self, h, ids.to(device=dev, dtype=torch.long), meta, cache, logits, seq_adapter=None,
-                                verify=(tok, lp, n_acc))
+                                verify=(tok, lp, n_acc), temperature=temperature, top_p=top_p, seed=seed, offset=offset)
         return tok, lp, n_acc, logits
 
     def _logits(self, input_ids: torch.Tensor, seqlens: List[int], cache: Optional[BufferCache],

@@ -2,7 +2,7 @@
 """What a verify step of speculative greedy decoding costs at the Mistral-7B dims (32 layers), every ring full at 4096 slots,
 one process on one box:
 
-    python scripts/spec_probe.py [--layers 32] [--steps 64] [--only-rows M]
+    python scripts/spec_probe.py [--layers 32] [--steps 64] [--only-rows M] [--sampled]
 
 Times (HIP events on the launch stream around queued steps, median of three windows, warm-up first - the discipline of
 bench.py and scripts/fp8_probe.py):
@@ -17,7 +17,11 @@ an oracle drafter whose every draft is right with probability r = 0.3, 0.6, 0.9 
 random and say nothing about how often a real model confirms a prompt-lookup draft.  Prints one JSON line.
 The per-layer attention figures of (d) come from Python calls of the leaves and are bound below by the host's ~19 us per call;
 `--only-rows M` runs nothing but the verify step at M rows and the launch-path decode step at batch M: the form to put under
-`rocprofv3 --kernel-trace --stats -- python scripts/spec_probe.py --only-rows 8 --steps 16` for the per-kernel table."""
+`rocprofv3 --kernel-trace --stats -- python scripts/spec_probe.py --only-rows 8 --steps 16` for the per-kernel table.
+`--sampled` runs nothing but (e): the verify step at m = 1, 4, 8 rows with the greedy tail (argmax + acceptance) and with the
+sampled one (temperature 0.7, top-p 0.8: accept / residual draw per row + scan), alternating greedy, sampled, greedy, sampled on
+the same full wrapped rings, and their difference.  The ids are random and the weights too (a nucleus of thousands of tokens),
+so nearly every drafted row rejects and draws: the sampled tail at its dearest."""
 import argparse
 import json
 import os
@@ -38,6 +42,7 @@ W = 4096
 SEEN = 2 * W + 100           # every ring full and wrapped
 ROWS = [1, 2, 3, 4, 6, 8]
 RATES = [0.3, 0.6, 0.9]
+SAMPLED_ROWS = [1, 4, 8]
 DIMS = dict(dim=4096, head_dim=128, hidden_dim=14336, n_heads=32, n_kv_heads=8, norm_eps=1e-5, vocab_size=32768, sliding_window=W)
 
 
@@ -85,15 +90,16 @@ def event_ms(fn, reps=3):
     return sorted(ts)[len(ts) // 2]
 
 
-def verify_step_ms(model, m: int, steps: int) -> float:
+def verify_step_ms(model, m: int, steps: int, temperature: float = 0.0) -> float:
     cache = full_cache(model, 1)
     ids = torch.randint(0, model.args.vocab_size, (m,), generator=torch.Generator().manual_seed(m)).to(DEV)
+    kw = dict(temperature=temperature, top_p=0.8, seed=1) if temperature > 0 else {}
 
     def run():
-        for _ in range(steps):
-            model._verify_launch(ids, [m], cache)   # (the host mirror stays: every step sits at the same positions)
+        for i in range(steps):
+            model._verify_launch(ids, [m], cache, offset=i, **kw)   # (the host mirror stays: every step sits at the same positions)
     for _ in range(4):
-        model._verify_launch(ids, [m], cache)
+        model._verify_launch(ids, [m], cache, **kw)
     torch.cuda.synchronize()
     return event_ms(run) / steps
 
@@ -132,6 +138,7 @@ def main():
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--only-rows", type=int, default=0)
+    ap.add_argument("--sampled", action="store_true")
     o = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("spec_probe: no HIP device (timings come from the GPU only)")
@@ -139,6 +146,17 @@ def main():
     r3 = lambda x: round(x, 4)  # noqa: E731
     with torch.inference_mode():
         model = build(o.layers)
+        if o.sampled:
+            _hip.set_decode_engine(False)
+            res = {"rows": SAMPLED_ROWS, "temperature": 0.7, "top_p": 0.8}
+            for rnd in ("", "_again"):
+                for name, t in (("greedy", 0.0), ("sampled", 0.7)):
+                    res[name + "_verify_ms" + rnd] = {str(m): r3(verify_step_ms(model, m, o.steps, t)) for m in SAMPLED_ROWS}
+            res["sampled_minus_greedy_ms"] = {str(m): r3(res["sampled_verify_ms"][str(m)] - res["greedy_verify_ms"][str(m)]) for m in SAMPLED_ROWS}
+            res["sampled_minus_greedy_ms_again"] = {
+                str(m): r3(res["sampled_verify_ms_again"][str(m)] - res["greedy_verify_ms_again"][str(m)]) for m in SAMPLED_ROWS}
+            print(json.dumps(dict(out, **res)))
+            return
         if o.only_rows:
             _hip.set_decode_engine(False)
             m = o.only_rows
