@@ -635,6 +635,58 @@ int mi_qkv_rope_w4a8(void* qkv, int ldo, const void* x, int ldx, int T, int D, c
 size_t mi_workspace_bytes_w4a8(const mi_model_t* model, const mi_w4_model_t* w4, int T, int B, int max_cache_size, int kv_layout);
 int mi_forward_w4a8(const mi_model_t* model, const mi_w4_model_t* w4, const mi_batch_t* batch, mi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * A quantised LM head for MI_W8_FP8_E4M3 and MI_W4_MXFP4 models: opt-in, additive to ABI v9 like the blocks above (the presence of
+ * these symbols is the feature test; no struct or entry point above changes - mi_linear_w8 / _w4 keep answering MI_EPI_LOGITS with
+ * MI_ERR_UNSUPPORTED).  The head (transformer.py:235, `output`) is then stored in the format of the model's layers: w [vocab, K]
+ * e4m3 bytes with fp32 row scales [vocab], or MXFP4 code bytes [vocab, K / 2] with e8m0 block scales [vocab, K / 32]; K = dim.
+ *   M <= 8:  the weight-streaming GEMV of the format with the bf16 head's epilogue (csrc/gemv_w8.hip, gemv_w4.hip; the final
+ *            RMSNorm fused as there): logit = float(bf16(acc * scale[r])) for FP8, float(bf16(acc)) for MXFP4 - one bf16 rounding
+ *            of the fp32 value, then widened, exactly where the bf16 head rounds;
+ *   M  > 8:  the bf16 image of the head (as mi_linear_w8 / _w4 define it) is written into a scratch in slices of
+ *            MI_LM_HEAD_SLICE_ROWS vocabulary rows - one dequantisation launch and the GEMM launch(es) of mi_linear /
+ *            mi_lm_head_logprobs per slice - so the scratch is min(vocab, MI_LM_HEAD_SLICE_ROWS) * K bf16 (84 MB at K = 5120),
+ *            rounded up to 256 bytes, whatever the vocabulary.  Every column runs on the GEMM kernel that one launch on the whole
+ *            image gives it: logits and log-probabilities are those of mi_linear(MI_EPI_LOGITS) / mi_lm_head_logprobs on the
+ *            dequantised head, bit for bit.
+ * Nothing is claimed about model quality (MXFP4's relative rms weight error is 0.12).  The embedding table stays bf16.
+ * ---------------------------------------------------------------------------------------------- */
+#define MI_LM_HEAD_SLICE_ROWS 8192
+
+/* The quantisation of the LM head: beside an mi_model_t whose `output` then points to the quantised bytes. */
+typedef struct mi_lm_head_quant {
+  int32_t format;     /* MI_W8_FP8_E4M3 / MI_W4_MXFP4: the format of the model's layers */
+  const void* scale;  /* DEVICE: fp32 [vocab] (FP8) or e8m0 bytes [vocab, dim / 32], row-major (MXFP4) */
+} mi_lm_head_quant_t;
+
+/* The head as a leaf: logits[M, ldo] (fp32) = bf16-rounded (rmsnorm(x) or x)[M, K] @ W^T, W as `head` describes `w`.  M > 8 needs
+ * `scratch` of mi_lm_head_q_scratch_bytes(M, K, vocab) bytes (0 for M <= 8, where scratch may be NULL); norm_w as mi_linear (M <= 8
+ * only).  K a multiple of 16 (FP8) / 32 (MXFP4): MI_ERR_SHAPE; another format value: MI_ERR_UNSUPPORTED. */
+size_t mi_lm_head_q_scratch_bytes(int M, int K, int vocab);
+int mi_lm_head_q(float* logits, int ldo, const void* x, int ldx, int M, int K, const void* w, int vocab, const mi_lm_head_quant_t* head,
+                 const void* norm_w, float eps, void* scratch, size_t scratch_bytes, mi_stream_t stream);
+/* mi_lm_head_logprobs on a quantised head.  scratch: mi_lm_head_logprobs_scratch_bytes(M, vocab) rounded up to 256 bytes, and for
+ * M > 8 the slice of mi_lm_head_q_scratch_bytes behind it.  The fused route reduces over the whole vocabulary: the slices write
+ * the per-tile partials of the one launch, so the result does not depend on the slicing. */
+size_t mi_lm_head_logprobs_q_scratch_bytes(int M, int K, int vocab);
+int mi_lm_head_logprobs_q(float* logprob, const void* x, int ldx, int M, int K, const void* w, int vocab, const mi_lm_head_quant_t* head,
+                          const int32_t* target, void* scratch, size_t scratch_bytes, mi_stream_t stream);
+
+/* ONE forward entry for a model with a quantised head.  It covers mi_forward (w8 == w4 == NULL), mi_forward_w8 / _w4 (one of them),
+ * mi_forward_w8a8 / _w4a8 (a8 != 0) and mi_forward_verify (verify_out != NULL); with head == NULL it is, launch for launch, those
+ * entries, error codes included.  head != NULL: the LM head launch reads model->output as quantised bytes with head->scale; at T <= 8
+ * (decode steps, verify steps, short chunks) the format's GEMV, above the sliced route - the a8 routes leave the head on it, as they
+ * leave the bf16 head alone.  Refused before any launch: a head format that is not the layers' (MI_ERR_UNSUPPORTED), a head on a
+ * model without quantised layers (MI_ERR_UNSUPPORTED), a NULL scale (MI_ERR_ARG), and whatever those entries refuse - dim not a
+ * multiple of 16 / 32 among it.
+ * Workspace: mi_workspace_bytes_q with the same w8 / w4 / head / a8 and verify = (verify_out != NULL).  With head == NULL it is
+ * mi_workspace_bytes_kv / _w8a8 / _w4a8 / _verify (verify: B is not read, T stands for it); with a head and T > 8 it is larger by
+ * exactly the slice, min(vocab, MI_LM_HEAD_SLICE_ROWS) * dim * 2 bytes rounded up to 256, behind everything else. */
+size_t mi_workspace_bytes_q(const mi_model_t* model, const mi_w8_model_t* w8, const mi_w4_model_t* w4, const mi_lm_head_quant_t* head,
+                            int T, int B, int max_cache_size, int kv_layout, int a8, int verify);
+int mi_forward_q(const mi_model_t* model, const mi_w8_model_t* w8, const mi_w4_model_t* w4, const mi_lm_head_quant_t* head,
+                 const mi_batch_t* batch, const mi_verify_out_t* verify_out, int a8, mi_stream_t stream);
+
 size_t mi_workspace_bytes_generic(const mi_model_t* model, int T, int dtype);
 int mi_forward_generic(const mi_model_t* model, const mi_batch_t* batch, int dtype, mi_stream_t stream);
 /* Leaf operators in any storage dtype - what module-level callers of an fp16 / fp32 model bind (the Pixtral tower of

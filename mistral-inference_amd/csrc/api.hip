@@ -99,8 +99,20 @@ struct Workspace {
                      //     [n_layers, T, 2 * n_kv_heads * head_dim], which enter the rings once acceptance is known
   uint8_t* x_q;      // FP8 prefill GEMMs (mi_forward_w8a8 / mi_forward_w4a8 only, behind everything else): the e4m3 rows of a linear group's input
   float* s_x;        //     [T, max(dim, n_heads * head_dim, hidden_dim)] and their scales [T]
+  bf16_t* head_deq;  // a quantised LM head at T > 8 (mi_forward_q with a head struct only, behind everything else): one slice of
+                     //     lm_head_slice_rows(vocab) dequantised vocabulary rows
   size_t total;
 };
+
+// A quantised LM head at more than 8 rows is dequantised and multiplied in slices of this many vocabulary rows (the last one
+// shorter), so that its bf16 image never exists as a whole: 1.34 GB at vocab 131072 x dim 5120, against 84 MB for a slice.  8192
+// rows are 32 column tiles of the 256-tile GEMM: from 2048 prompt rows on, a slice still fills the 256 CUs, and a slice's
+// dequantisation moves tens of megabytes, far above the cost of a launch.  A multiple of 256, so that every slice starts on a tile
+// boundary of either GEMM kernel and of the fused log-prob partials.
+constexpr int LM_HEAD_SLICE_ROWS = MI_LM_HEAD_SLICE_ROWS;
+static_assert(LM_HEAD_SLICE_ROWS % 256 == 0, "slices start on tile boundaries");
+inline size_t lm_head_slice_rows(int vocab) { return (size_t)(vocab < LM_HEAD_SLICE_ROWS ? vocab : LM_HEAD_SLICE_ROWS); }
+inline size_t lm_head_slice_bytes(int vocab, int K) { return lm_head_slice_rows(vocab) * (size_t)K * sizeof(bf16_t); }
 
 // bf16 elements of the largest linear group a prefill dequantises at once: q|k|v, wo, w1|w3, w2
 size_t deq_scratch_elems(const mi_model_t* m) {
@@ -118,8 +130,9 @@ size_t verify_stash_bytes(const mi_model_t* m, int T) { return (size_t)m->n_laye
 // quant: the linears are quantised (any format: the same scratch of one dequantised linear group); kv8: the rings hold e4m3 bytes
 // verify: a verify step (mi_forward_verify) - its attention keeps split partials per ROW, so the caller passes B = T, and the stash
 // a8: the entry is mi_forward_w8a8 / mi_forward_w4a8 - the activation rows of its FP8-activation GEMMs
+// qhead: the LM head is quantised (mi_forward_q) - the slice of its bf16 image at T > 8
 Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool quant = false, bool kv8 = false, bool verify = false,
-                bool a8 = false) {
+                bool a8 = false, bool qhead = false) {
   Workspace w;
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -170,6 +183,8 @@ Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool qu
     w.x_q = (uint8_t*)take((size_t)T * (k1 > (size_t)m->hidden_dim ? k1 : (size_t)m->hidden_dim));
     w.s_x = (float*)take((size_t)T * sizeof(float));
   }
+  // (any other forward: layout and total as ever)
+  w.head_deq = (qhead && T > GEMV_MAX_T) ? (bf16_t*)take(lm_head_slice_bytes(m->vocab_size, m->dim)) : nullptr;
   w.total = off;
   return w;
 }
@@ -265,6 +280,8 @@ struct QuantW8 {  // gemv_w8.hip: e4m3 bytes, one fp32 scale per row
                               *kOperandsA8 = "x and the weights 16-byte aligned";
   static constexpr auto launch_gemv = launch_gemv_w8;
   static constexpr auto launch_dequant = launch_dequant_w8;
+  static size_t row_bytes(int K) { return (size_t)K; }  // of a weight row; scale elements of a row
+  static size_t row_scales(int) { return 1; }
 };
 struct QuantW4 {  // gemv_w4.hip: MXFP4 code bytes, one e8m0 scale byte per block of 32
   typedef uint8_t scale_t;
@@ -277,6 +294,8 @@ struct QuantW4 {  // gemv_w4.hip: MXFP4 code bytes, one e8m0 scale byte per bloc
                               *kOperandsA8 = "x and the code matrices 16-byte aligned, the block scale matrices 4-byte aligned";
   static constexpr auto launch_gemv = launch_gemv_w4;
   static constexpr auto launch_dequant = launch_dequant_w4;
+  static size_t row_bytes(int K) { return (size_t)K >> 1; }
+  static size_t row_scales(int K) { return (size_t)K >> 5; }
 };
 template <class Q>
 int gemv_passes_quant(const GemvArgs& a, const Scales<typename Q::scale_t>& sc, int T, hipStream_t s, const char* what) {
@@ -315,6 +334,7 @@ struct QuantModel {
   int format;        // the format the caller's struct names (check_quant: must be the entry's)
   const mi_w8_layer_t* l8;  // host [n_layers]; the table of entry_format, the other one nullptr
   const mi_w4_layer_t* l4;
+  const mi_lm_head_quant_t* head;  // mi_forward_q: the LM head is quantised too (m->output: its bytes), or nullptr - a bf16 head
 };
 // f(trait of the format)
 template <class Fn>
@@ -323,8 +343,8 @@ inline const mi_w8_layer_t* layers_of(const QuantModel& q, QuantW8) { return q.l
 inline const mi_w4_layer_t* layers_of(const QuantModel& q, QuantW4) { return q.l4; }
 // of the one struct that an entry point was handed (neither: not read)
 QuantModel quant_model(const mi_w8_model_t* w8, const mi_w4_model_t* w4) {
-  if (w8) return {MI_W8_FP8_E4M3, w8->format, w8->layers, nullptr};
-  return w4 ? QuantModel{MI_W4_MXFP4, w4->format, nullptr, w4->layers} : QuantModel{};
+  if (w8) return {MI_W8_FP8_E4M3, w8->format, w8->layers, nullptr, nullptr};
+  return w4 ? QuantModel{MI_W4_MXFP4, w4->format, nullptr, w4->layers, nullptr} : QuantModel{};
 }
 
 // ---- MoE FFN of T <= 8 tokens: per (token, slot) gate | up + SwiGLU into hid [T * top_k, F], then per token the down
@@ -547,6 +567,43 @@ struct LinearCall {
   float* s_x;
 };
 
+// A quantised LM head (one matrix, G.format != 0) at more than 8 rows.  g: the GEMM of the whole head on its bf16 image (GEMM_LOGITS
+// or GEMM_LOGPROB; g.w0 is not read).  Per slice of LM_HEAD_SLICE_ROWS vocabulary rows: one dequantisation launch into `deq`
+// (lm_head_slice_bytes), then the GEMM on the slice's columns.  Every column runs on the kernel that the one launch on the whole
+// image would give it (gemm_plan), with the same K loop on the same bf16 weights: the logits are those of the unsliced launch, bit
+// for bit.  The fused log-prob partials of a slice go to the slice's tiles of the whole head's [M][tiles] array (lp_col0, lp_tiles).
+int head_gemm_sliced(const LinearGroup& G, const GemmArgs& g, bf16_t* deq, hipStream_t s, const char* what_dequant, const char* what_gemm) {
+  GemmArgs whole = g;
+  whole.w0 = deq; whole.w1 = whole.w2 = nullptr; whole.n0 = whole.n1 = g.N;
+  const int c256 = g.epi == GEMM_LOGPROB ? g.N : gemm_plan(whole).c256;  // (the logits' tail is the 128-tile kernel's: no half tiles)
+  for (int r0 = 0; r0 < g.N; r0 += LM_HEAD_SLICE_ROWS) {
+    const int r1 = g.N - r0 < LM_HEAD_SLICE_ROWS ? g.N : r0 + LM_HEAD_SLICE_ROWS;
+    MI_TRY(with_format(G.format, [&](auto Q) {
+      typedef decltype(Q) F;
+      const void* w[3] = {(const uint8_t*)G.w[0] + (size_t)r0 * F::row_bytes(G.K), nullptr, nullptr};
+      Scales<typename F::scale_t> sc = {{scales_of(G, Q).s[0] + (size_t)r0 * F::row_scales(G.K), nullptr, nullptr}};
+      const int nr[3] = {r1 - r0, 0, 0};
+      return dequant_group<F>(w, sc, nr, G.K, deq, s, what_dequant);
+    }));
+    const int cut = c256 < r0 ? r0 : (c256 > r1 ? r1 : c256);  // columns [r0, cut) on the 256-tile kernel, [cut, r1) on the 128-tile one
+    const int part[2][2] = {{r0, cut}, {cut, r1}};
+    for (int i = 0; i < 2; ++i) {
+      const int a = part[i][0], b = part[i][1];
+      if (b <= a) continue;
+      GemmArgs p = whole;
+      p.N = p.n0 = p.n1 = b - a;
+      p.w0 = deq + (size_t)(a - r0) * G.K;
+      if (g.epi == GEMM_LOGPROB) {
+        p.lp_col0 = a; p.lp_tiles = (g.N + 255) / 256;
+      } else {
+        p.out = reinterpret_cast<float*>(g.out) + a;
+      }
+      MI_TRY(hip_rc(i == 0 ? launch_gemm256(p, s) : launch_gemm128(p, s), what_gemm));
+    }
+  }
+  return MI_OK;
+}
+
 // M <= GEMV_MAX_T rows: weight-streaming GEMV passes with the RMSNorm, RoPE and (bf16 rings) the ring write fused.  More rows: the
 // RMSNorm into xn, the bf16 image of quantised weights into deq, then the MFMA GEMM (RoPE in its epilogue when it takes the heads).
 // Quantised groups with C.a8 at M >= 256 rows and K % 128 == 0: the per-token e4m3 quantisation of the input rows (the RMSNorm fused
@@ -636,10 +693,12 @@ int linear_group(const LinearGroup& G, const LinearCall& C, int M, hipStream_t s
       x = C.xn; ldx = K;
     }
     const void* w[3] = {G.w[0], G.w[1], G.w[2]};
+    const bool head_slices = G.format && C.epi == MI_EPI_LOGITS;  // a quantised LM head: its bf16 image slice by slice
     if (G.format) {
       if (!C.deq) return fail(MI_ERR_WORKSPACE, "linear group: no scratch for the dequantised weights");
       const int nr[3] = {n0, n1 - n0, n2 - n1};
-      MI_TRY(with_format(G.format, [&](auto Q) { return dequant_group<decltype(Q)>(w, scales_of(G, Q), nr, K, C.deq, s, C.what.dequant); }));
+      if (!head_slices)
+        MI_TRY(with_format(G.format, [&](auto Q) { return dequant_group<decltype(Q)>(w, scales_of(G, Q), nr, K, C.deq, s, C.what.dequant); }));
     }
     GemmArgs g;
     memset(&g, 0, sizeof(g));
@@ -648,7 +707,8 @@ int linear_group(const LinearGroup& G, const LinearCall& C, int M, hipStream_t s
     g.w0 = (const bf16_t*)w[0]; g.w1 = (const bf16_t*)w[1]; g.w2 = (const bf16_t*)w[2]; g.n0 = n0; g.n1 = swiglu ? n0 : n1;
     g.out = C.out; g.ldo = C.ldo; g.residual = (const bf16_t*)C.residual;
     if (fused_rope) { g.rope_cs = C.rope_cs; g.tok_pos = C.tok_pos; g.rope_cols = n1; g.rope_dh = C.head_dim; }
-    MI_TRY(hip_rc(launch_gemm(g, s), C.what.gemm));
+    if (head_slices) MI_TRY(head_gemm_sliced(G, g, C.deq, s, C.what.dequant, C.what.gemm));
+    else MI_TRY(hip_rc(launch_gemm(g, s), C.what.gemm));
   }
   if (qkv && !fused_rope)
     MI_TRY(hip_rc(launch_rope(C.out, C.ldo, M, n0 / C.head_dim, (n1 - n0) / C.head_dim, C.head_dim, C.rope_cs, C.tok_pos, s), "rope"));
@@ -914,18 +974,15 @@ size_t mi_lm_head_logprobs_scratch_bytes(int M, int vocab) {
   return fused > rows ? fused : rows;  // either route may be taken (the fused one needs M >= 256 and K % 64 == 0)
 }
 
-int mi_lm_head_logprobs(float* logprob, const void* x, int ldx, int M, int K, const void* w, int vocab,
-                        const int32_t* target, void* scratch, size_t scratch_bytes, mi_stream_t stream) {
-  if (!logprob || !x || !w || !target || !scratch || M <= 0 || K <= 0 || K % 8 || vocab <= 0)
-    return fail(MI_ERR_ARG, "mi_lm_head_logprobs");
-  if (scratch_bytes < mi_lm_head_logprobs_scratch_bytes(M, vocab))
-    return fail(MI_ERR_WORKSPACE, "mi_lm_head_logprobs: scratch %zu < required %zu", scratch_bytes,
-                mi_lm_head_logprobs_scratch_bytes(M, vocab));
-  hipStream_t s = (hipStream_t)stream;
+// mi_lm_head_logprobs, and mi_lm_head_logprobs_q on a quantised head (head.format != 0: deq holds a slice of its bf16 image).
+// The arguments have been checked; scratch: mi_lm_head_logprobs_scratch_bytes.
+static int lm_head_logprobs(float* logprob, const void* x, int ldx, int M, int K, const LinearGroup& head, const int32_t* target, void* scratch,
+                            bf16_t* deq, hipStream_t s) {
+  const int vocab = head.n_rows[0];
   GemmArgs g;
   memset(&g, 0, sizeof(g));
   g.epi = GEMM_LOGPROB; g.M = M; g.N = vocab; g.K = K; g.a = (const bf16_t*)x; g.lda = ldx;
-  g.w0 = (const bf16_t*)w; g.n0 = g.n1 = vocab;
+  g.w0 = (const bf16_t*)head.w[0]; g.n0 = g.n1 = vocab;
   if (M >= 256 && gemm256_applicable(g)) {
     // one pass over the LM head: per-tile (max, sum-exp) partials + the target logit, then one wave per row
     const int n_tiles = (vocab + 255) / 256;
@@ -933,21 +990,83 @@ int mi_lm_head_logprobs(float* logprob, const void* x, int ldx, int M, int K, co
     g.lp_partial = (float2*)scratch;
     g.lp_tgt = (float*)((char*)scratch + align_up((size_t)M * n_tiles * sizeof(float2)));
     MI_TRY(hip_rc(hipMemsetAsync(g.lp_tgt, 0, (size_t)M * sizeof(float), s), "logprob target memset"));
-    MI_TRY(hip_rc(launch_gemm256(g, s), "lm head logprob gemm"));
+    if (head.format) MI_TRY(head_gemm_sliced(head, g, deq, s, "dequant lm head", "lm head logprob gemm"));
+    else MI_TRY(hip_rc(launch_gemm256(g, s), "lm head logprob gemm"));
     return hip_rc(launch_logprob_finalize(logprob, g.lp_partial, g.lp_tgt, M, n_tiles, s), "logprob finalize");
   }
   // few rows (or a K the 256-tile kernel does not take): fp32 logits of up to 128 rows at a time into the scratch
   // (GEMV / 128-tile GEMM), then a row-wise log-softmax gather
-  const void* ws[3] = {w, nullptr, nullptr};
-  const int nr[3] = {vocab, 0, 0};
   for (int r0 = 0; r0 < M; r0 += LOGPROB_ROW_CHUNK) {
     const int rows = (M - r0 < LOGPROB_ROW_CHUNK) ? M - r0 : LOGPROB_ROW_CHUNK;
-    const int rc = mi_linear(scratch, vocab, (const bf16_t*)x + (size_t)r0 * ldx, ldx, rows, K, ws, nr, MI_EPI_LOGITS, nullptr,
-                             nullptr, 0.f, stream);
-    if (rc) return rc;
+    LinearCall c = {(const bf16_t*)x + (size_t)r0 * ldx, ldx, nullptr, 0.f, scratch, vocab, nullptr, MI_EPI_LOGITS};
+    c.deq = deq;
+    c.what = {"gemv", "gemm", "dequant lm head"};
+    MI_TRY(linear_group(head, c, rows, s));
     MI_TRY(hip_rc(launch_logprob_rows(logprob + r0, (const float*)scratch, vocab, target + r0, rows, vocab, s), "logprob rows"));
   }
   return MI_OK;
+}
+
+int mi_lm_head_logprobs(float* logprob, const void* x, int ldx, int M, int K, const void* w, int vocab,
+                        const int32_t* target, void* scratch, size_t scratch_bytes, mi_stream_t stream) {
+  if (!logprob || !x || !w || !target || !scratch || M <= 0 || K <= 0 || K % 8 || vocab <= 0)
+    return fail(MI_ERR_ARG, "mi_lm_head_logprobs");
+  if (scratch_bytes < mi_lm_head_logprobs_scratch_bytes(M, vocab))
+    return fail(MI_ERR_WORKSPACE, "mi_lm_head_logprobs: scratch %zu < required %zu", scratch_bytes,
+                mi_lm_head_logprobs_scratch_bytes(M, vocab));
+  return lm_head_logprobs(logprob, x, ldx, M, K, group_of(K, w, vocab), target, scratch, nullptr, (hipStream_t)stream);
+}
+
+/* a quantised LM head as leaves (include/mistral_hip.h: mi_lm_head_quant_t) */
+static int check_head_quant(const char* me, const mi_lm_head_quant_t* head, int K, LinearGroup* g) {
+  if (!head || !head->scale) return fail(MI_ERR_ARG, "%s: head (format and scales)", me);
+  if (head->format != MI_W8_FP8_E4M3 && head->format != MI_W4_MXFP4)
+    return fail(MI_ERR_UNSUPPORTED, "%s: LM head format %d (MI_W8_FP8_E4M3 = 1 and MI_W4_MXFP4 = 2 are the formats)", me, head->format);
+  return with_format(head->format, [&](auto Q) {
+    typedef decltype(Q) F;
+    if (K % F::kMod) return fail(MI_ERR_SHAPE, "%s: K = %d must be a multiple of %d (%s)", me, K, F::kMod, F::kWhy);
+    set_scales(*g, Q, (const typename F::scale_t*)head->scale);
+    return (int)MI_OK;
+  });
+}
+
+size_t mi_lm_head_q_scratch_bytes(int M, int K, int vocab) {
+  if (M <= GEMV_MAX_T || K <= 0 || vocab <= 0) return 0;
+  return align_up(lm_head_slice_bytes(vocab, K));
+}
+
+int mi_lm_head_q(float* logits, int ldo, const void* x, int ldx, int M, int K, const void* w, int vocab, const mi_lm_head_quant_t* head,
+                 const void* norm_w, float eps, void* scratch, size_t scratch_bytes, mi_stream_t stream) {
+  const char* me = "mi_lm_head_q";
+  if (!logits || !x || !w || M <= 0 || K <= 0 || vocab <= 0 || ldo < vocab) return fail(MI_ERR_ARG, "%s", me);
+  LinearGroup g = group_of(K, w, vocab);
+  MI_TRY(check_head_quant(me, head, K, &g));
+  if (M > GEMV_MAX_T) {
+    if (norm_w) return fail(MI_ERR_UNSUPPORTED, "%s: fused RMSNorm only on the M <= 8 path", me);
+    const size_t need = mi_lm_head_q_scratch_bytes(M, K, vocab);
+    if (!scratch || scratch_bytes < need) return fail(MI_ERR_WORKSPACE, "%s: scratch %zu < required %zu", me, scratch ? scratch_bytes : (size_t)0, need);
+  }
+  LinearCall c = {x, ldx, norm_w, eps, logits, ldo, nullptr, MI_EPI_LOGITS};
+  c.deq = (bf16_t*)scratch;
+  c.what = {"lm head gemv", "lm head gemm", "dequant lm head"};
+  return linear_group(g, c, M, (hipStream_t)stream);
+}
+
+size_t mi_lm_head_logprobs_q_scratch_bytes(int M, int K, int vocab) {
+  if (M <= 0 || K <= 0 || vocab <= 0) return 0;
+  return align_up(mi_lm_head_logprobs_scratch_bytes(M, vocab)) + mi_lm_head_q_scratch_bytes(M, K, vocab);
+}
+
+int mi_lm_head_logprobs_q(float* logprob, const void* x, int ldx, int M, int K, const void* w, int vocab, const mi_lm_head_quant_t* head,
+                          const int32_t* target, void* scratch, size_t scratch_bytes, mi_stream_t stream) {
+  const char* me = "mi_lm_head_logprobs_q";
+  if (!logprob || !x || !w || !target || !scratch || M <= 0 || K <= 0 || vocab <= 0) return fail(MI_ERR_ARG, "%s", me);
+  LinearGroup g = group_of(K, w, vocab);
+  MI_TRY(check_head_quant(me, head, K, &g));
+  const size_t need = mi_lm_head_logprobs_q_scratch_bytes(M, K, vocab);
+  if (scratch_bytes < need) return fail(MI_ERR_WORKSPACE, "%s: scratch %zu < required %zu", me, scratch_bytes, need);
+  bf16_t* deq = (bf16_t*)((char*)scratch + align_up(mi_lm_head_logprobs_scratch_bytes(M, vocab)));
+  return lm_head_logprobs(logprob, x, ldx, M, K, g, target, scratch, M > GEMV_MAX_T ? deq : nullptr, (hipStream_t)stream);
 }
 
 size_t mi_attn_decode_scratch_bytes(int B, int n_heads, int n_kv_heads, int head_dim, int W) {
@@ -1349,6 +1468,12 @@ static int check_quant(const char* entry, const mi_model_t* m, const QuantModel&
       return fail(MI_ERR_UNSUPPORTED, "%s: un-merged LoRA on an %s base is not implemented; merge the adapter before quantising", entry, F::kName);
     if (m->dim % F::kMod || m->hidden_dim % F::kMod || (m->n_heads * m->head_dim) % F::kMod)
       return fail(MI_ERR_SHAPE, "%s: dim, hidden_dim and n_heads * head_dim must be multiples of %d (%s)", entry, F::kMod, F::kWhy);
+    if (q.head) {  // (its K is dim: the multiple of kMod above)
+      if (q.head->format != F::kFormat)
+        return fail(MI_ERR_UNSUPPORTED, "%s: LM head format %d on layers of format %s (a quantised LM head is in the layers' format)", entry,
+                    q.head->format, F::kFormatName);
+      if (!q.head->scale) return fail(MI_ERR_ARG, "%s: quantised LM head without %s", entry, F::kScales);
+    }
     return (int)MI_OK;
   });
 }
@@ -1391,7 +1516,7 @@ static int forward_body(const char* entry, const mi_model_t* m, const QuantModel
   if (bi.has_cache)
     for (int l = 0; l < m->n_layers; ++l) maxW = bt->cache_sizes[l] > maxW ? bt->cache_sizes[l] : maxW;
   const bool kv8 = bi.has_cache && kv_e4m3(bi.kv_layout);  // rings of e4m3 bytes: written by the e4m3 ring-write kernel only
-  const Workspace ws = carve(m, bi.T, vo ? bi.T : bi.B, maxW, (char*)bt->workspace, q != nullptr, kv8, vo != nullptr, a8);
+  const Workspace ws = carve(m, bi.T, vo ? bi.T : bi.B, maxW, (char*)bt->workspace, q != nullptr, kv8, vo != nullptr, a8, q && q->head);
   MI_TRY(check_workspace_and_sample(entry, bt, ws.total, &bi));
   const int T = bi.T, B = bi.B, branch = bi.branch, kvl = bi.kv_layout;  // (kvl keeps MI_KV_E4M3: the ring write and the decode attention pick their e4m3 kernels by it)
   const bool has_cache = bi.has_cache, want_greedy = bi.want_sample, want_topp = bi.want_topp;
@@ -1556,11 +1681,18 @@ static int forward_body(const char* entry, const mi_model_t* m, const QuantModel
   if (m->final_norm && !bt->logits) {
     MI_TRY(hip_rc(launch_rmsnorm(h, h, m->final_norm, T, D, m->norm_eps, s), "final norm"));
   } else if (m->final_norm) {
-    // the LM head is never quantised and carries no adapters
+    // the LM head carries no adapters; it is bf16 unless the entry was handed its quantisation (mi_forward_q), and then it stays on
+    // the weight-only routes also where the layers take the FP8-activation GEMMs (linear_group: never a8 on MI_EPI_LOGITS)
     LinearCall c = call;
     c.x = h; c.ldx = D; c.norm_w = m->final_norm; c.eps = m->norm_eps; c.out = bt->logits; c.ldo = m->vocab_size; c.epi = MI_EPI_LOGITS;
-    c.what = {"lm head gemv", "lm head gemm", nullptr, "final norm"};
-    MI_TRY(linear_group(group_of(D, m->output, m->vocab_size), c, T, s));
+    c.deq = ws.head_deq;
+    c.what = {"lm head gemv", "lm head gemm", "dequant lm head", "final norm"};
+    LinearGroup head = group_of(D, m->output, m->vocab_size);
+    if (q && q->head) {
+      if (q->entry_format == MI_W4_MXFP4) set_scales(head, QuantW4{}, (const uint8_t*)q->head->scale);
+      else set_scales(head, QuantW8{}, (const float*)q->head->scale);
+    }
+    MI_TRY(linear_group(head, c, T, s));
     if (want_greedy) MI_TRY(sample_step(bt, m, want_topp, engine_ctrl, s));
   }
   if (vo) {
@@ -1625,6 +1757,31 @@ int mi_forward_verify(const mi_model_t* m, const mi_w8_model_t* w8, const mi_w4_
   if (w8 && w4) return fail(MI_ERR_ARG, "mi_forward_verify: both w8 and w4 given; a model has at most one weight format");
   const QuantModel q = quant_model(w8, w4);
   return forward_body("mi_forward_verify", m, (w8 || w4) ? &q : nullptr, bt, stream, out);
+}
+
+/* a quantised LM head (include/mistral_hip.h: mi_lm_head_quant_t) */
+size_t mi_workspace_bytes_q(const mi_model_t* model, const mi_w8_model_t* w8, const mi_w4_model_t* w4, const mi_lm_head_quant_t* head,
+                            int T, int B, int max_cache_size, int kv_layout, int a8, int verify) {
+  if (!model || T <= 0 || B <= 0 || !kv_layout_ok(kv_layout) || (w8 && w4)) return 0;
+  if (a8 && !w8 && !w4) return 0;
+  if (verify && (T > GEMV_MAX_T || kv_e4m3(kv_layout))) return 0;
+  if (head && !w8 && !w4) return 0;
+  return carve(model, T, verify ? T : B, max_cache_size > 0 ? max_cache_size : 1, nullptr, w8 || w4, kv_e4m3(kv_layout), verify != 0, a8 != 0,
+               head != nullptr).total;
+}
+
+int mi_forward_q(const mi_model_t* m, const mi_w8_model_t* w8, const mi_w4_model_t* w4, const mi_lm_head_quant_t* head,
+                 const mi_batch_t* bt, const mi_verify_out_t* verify_out, int a8, mi_stream_t stream) {
+  // head == NULL: the old entries, under their own names in the error details
+  const char* me = head ? "mi_forward_q" : verify_out ? "mi_forward_verify" : a8 ? (w4 ? "mi_forward_w4a8" : "mi_forward_w8a8")
+                   : w8 ? "mi_forward_w8" : w4 ? "mi_forward_w4" : "mi_forward";
+  if (w8 && w4) return fail(MI_ERR_ARG, "%s: both w8 and w4 given; a model has at most one weight format", me);
+  if (a8 && !w8 && !w4) return fail(MI_ERR_ARG, "%s: a8 without w8 or w4 (the FP8-activation prefill GEMMs read quantised weights)", me);
+  if (head && !w8 && !w4)
+    return fail(MI_ERR_UNSUPPORTED, "%s: a quantised LM head on a model without quantised layers (the head is quantised in the layers' format)", me);
+  QuantModel q = quant_model(w8, w4);
+  q.head = head;
+  return forward_body(me, m, (w8 || w4) ? &q : nullptr, bt, stream, verify_out, a8 != 0);
 }
 
 }  // extern "C"

@@ -232,8 +232,6 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
 
 }  // namespace
 
-namespace {
-
 hipError_t launch_gemm128(const GemmArgs& g, hipStream_t s) {
   const int m_tiles = g.tile_tab ? g.max_m_tiles : (g.M + BM - 1) / BM;
   const int nout = (g.epi == GEMM_SWIGLU) ? 64 : 128;
@@ -260,6 +258,8 @@ hipError_t launch_gemm128(const GemmArgs& g, hipStream_t s) {
 #undef MI_LAUNCH_GEMM
   return hipGetLastError();
 }
+
+namespace {
 
 // The same problem restricted to output columns [c0, c1): weight row segments, output and residual shifted.
 GemmArgs column_slice(const GemmArgs& g, int c0, int c1) {
@@ -302,16 +302,14 @@ GemmArgs column_slice(const GemmArgs& g, int c0, int c1) {
 static int split_tail = -1;  // MI_GEMM_TAIL / mi_debug_set_prefill_kernels: 0 no split, 1 tail on the 128 kernel, 2 half-height tiles
 void gemm_set_tail_mode(int mode) { split_tail = mode; }
 
-hipError_t launch_gemm(const GemmArgs& g, hipStream_t s) {
-  if (g.K % 8 != 0 || g.M <= 0 || g.N <= 0) return hipErrorInvalidValue;
+GemmPlan gemm_plan(const GemmArgs& g) {
   static int use_256 = -1;  // MI_GEMM_256=0 keeps every shape on the 128x128 kernel (A/B testing)
   if (use_256 < 0) {
     const char* e = getenv("MI_GEMM_256");
     use_256 = e ? atoi(e) : 1;
   }
-  if (g.tile_tab && g.tile_rows == 256) return gemm256_applicable(g) ? launch_gemm256(g, s) : hipErrorInvalidValue;
-  if (!use_256 || !gemm256_applicable(g)) return launch_gemm128(g, s);
-  if (g.tile_tab) return launch_gemm256(g, s);
+  if (!use_256 || !gemm256_applicable(g)) return {0, false};
+  if (g.tile_tab) return {g.N, false};
   // One 256x256 block per CU: a tile count that is not a multiple of the CU count (256) leaves the last round partly empty
   // (q|k|v of Mistral-7B: 384 tiles = 1.5 rounds cost 2).  When the last round would be under 3/4 full, the columns
   // are split: full rounds on the 256 kernel, the remaining columns on the 128 kernel (two blocks per CU, four times
@@ -335,12 +333,20 @@ hipError_t launch_gemm(const GemmArgs& g, hipStream_t s) {
     const int n_first = (n_tiles / step) * step;
     if (n_first > 0 && n_first < n_tiles) {
       const int c0 = n_first * nout;
-      hipError_t e = launch_gemm256(column_slice(g, 0, c0), s);
-      if (e != hipSuccess) return e;
-      const GemmArgs tail = column_slice(g, c0, g.N);
-      if (split_tail >= 2 && rem * 2 <= cus && gemm256_half_applicable(tail)) return launch_gemm256_half(tail, s);
-      return launch_gemm128(tail, s);
+      return {c0, split_tail >= 2 && rem * 2 <= cus && gemm256_half_applicable(column_slice(g, c0, g.N))};
     }
   }
-  return launch_gemm256(g, s);
+  return {g.N, false};
+}
+
+hipError_t launch_gemm(const GemmArgs& g, hipStream_t s) {
+  if (g.K % 8 != 0 || g.M <= 0 || g.N <= 0) return hipErrorInvalidValue;
+  if (g.tile_tab && g.tile_rows == 256) return gemm256_applicable(g) ? launch_gemm256(g, s) : hipErrorInvalidValue;
+  const GemmPlan p = gemm_plan(g);
+  if (p.c256 == 0) return launch_gemm128(g, s);
+  if (p.c256 == g.N) return launch_gemm256(g, s);
+  hipError_t e = launch_gemm256(column_slice(g, 0, p.c256), s);
+  if (e != hipSuccess) return e;
+  const GemmArgs tail = column_slice(g, p.c256, g.N);
+  return p.half ? launch_gemm256_half(tail, s) : launch_gemm128(tail, s);
 }

@@ -273,7 +273,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmArgs g) {
               const int n = n_tile * 256 + hb * 128 + wc * 32 + j * 16 + (lane & 15);
               v[hb][j] = (n < g.N) ? E::round(acc[ha][hb][i][j][r]) : -INFINITY;
               mx = fmaxf(mx, v[hb][j]);
-              if (n == g.lp_target[row] && row0 + rl < g.M) g.lp_tgt[row] = v[hb][j];
+              if (n + g.lp_col0 == g.lp_target[row] && row0 + rl < g.M) g.lp_tgt[row] = v[hb][j];
             }
           mx = row16_max(mx);
           float sm = 0.f;
@@ -292,7 +292,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmArgs g) {
       float S = 0.f;
 #pragma unroll
       for (int w = 0; w < 4; ++w) S += (part[tid * 4 + w].x == -INFINITY) ? 0.f : part[tid * 4 + w].y * __expf(part[tid * 4 + w].x - M);
-      g.lp_partial[(size_t)(row0 + tid) * n_tiles + n_tile] = make_float2(M, S);
+      g.lp_partial[(size_t)(row0 + tid) * (g.lp_tiles ? g.lp_tiles : n_tiles) + (g.lp_col0 >> 8) + n_tile] = make_float2(M, S);
     }
     return;
   }

@@ -809,6 +809,7 @@ hipError_t launch_gemv_scaled(const Args& a, hipStream_t s) {
     case GEMV_RESIDUAL: return launch_mode<F, GEMV_RESIDUAL>(a, TT, rp, grid, lds, s);
     case GEMV_SWIGLU: return launch_mode<F, GEMV_SWIGLU>(a, TT, rp, grid, lds, s);
     case GEMV_QKV_ROPE: return launch_mode<F, GEMV_QKV_ROPE>(a, TT, rp, grid, lds, s);
+    case GEMV_LOGITS: return launch_mode<F, GEMV_LOGITS>(a, TT, rp, grid, lds, s);  // a quantised LM head (opt-in, mi_forward_q)
     default: return hipErrorInvalidValue;
   }
 }

@@ -18,7 +18,8 @@ namespace {
 
 using namespace gemv_core;
 
-// TT: token rows staged in LDS; MODE: GEMV_STORE / GEMV_RESIDUAL / GEMV_SWIGLU / GEMV_QKV_ROPE; RP: row pairs per unit;
+// TT: token rows staged in LDS; MODE: GEMV_STORE / GEMV_RESIDUAL / GEMV_SWIGLU / GEMV_QKV_ROPE, and GEMV_LOGITS for a quantised LM
+// head (logit = float(bf16(acc)): the one rounding of the bf16 head); RP: row pairs per unit;
 // DMA: the activation rows go to LDS by LDS-DMA.  Two batches are 64 piece + 16 scale registers, and a unit's converted pairs come
 // on top: at the bf16 kernels' 4 blocks per CU (128 VGPRs) every one-token kernel spilled.  The grid is 2 blocks per CU
 // (max_blocks), so 3 (168 VGPRs) costs no occupancy that is used.

@@ -16,7 +16,8 @@ namespace {
 
 using namespace gemv_core;
 
-// TT: token rows staged in LDS; MODE: GEMV_STORE / GEMV_RESIDUAL / GEMV_SWIGLU / GEMV_QKV_ROPE; RP: row pairs per unit;
+// TT: token rows staged in LDS; MODE: GEMV_STORE / GEMV_RESIDUAL / GEMV_SWIGLU / GEMV_QKV_ROPE, and GEMV_LOGITS for a quantised LM
+// head (logit = float(bf16(acc * scale[r])): the one rounding of the bf16 head); RP: row pairs per unit;
 // DMA: the activation rows go to LDS by LDS-DMA
 template <int TT, int MODE, int RP, bool DMA>
 __global__ __launch_bounds__(256, (TT == 1 ? 4 : (TT <= 3 ? 3 : 2))) void gemv_w8_kernel(GemvW8Args a) {

@@ -66,7 +66,7 @@ int gemv_max_tokens_f16(int K);
 hipError_t launch_gemv_f16(const GemvArgs& a, hipStream_t s);
 
 // The same launches on quantised weight rows with their scales (weight-only formats).  GemvArgs is the bf16 kernels' kernarg and
-// stays as it is: the scales ride beside it.  w0 / w1 / w2 point to bytes, modes STORE / RESIDUAL / SWIGLU / QKV_ROPE; scale[i]
+// stays as it is: the scales ride beside it.  w0 / w1 / w2 point to bytes, modes STORE / RESIDUAL / SWIGLU / QKV_ROPE / LOGITS; scale[i]
 // belongs to segment i (SWIGLU: scale[0] = W1's, scale[1] = W3's).
 template <class scale_t>
 struct GemvScaledArgs {
@@ -132,6 +132,11 @@ struct GemmArgs {
   const int32_t* tok_pos;         // device [M]
   int rope_cols, rope_dh;         // rope_cols % rope_dh == 0, rope_dh % 4 == 0
   int rope_col0;                  // column of the whole problem at which this (column-sliced) launch starts (% rope_dh == 0)
+  // GEMM_LOGPROB of a launch that is columns [lp_col0, lp_col0 + N) of a wider head (a quantised LM head dequantised in slices of
+  // vocabulary rows, api.hip): lp_target holds columns of the whole head and lp_partial is [M][lp_tiles] with this launch's tiles
+  // from lp_col0 / 256 on, so that the slices leave exactly the partials of the one launch.  lp_col0 % 256 == 0; lp_tiles 0:
+  // ceil(N / 256).  (Behind everything else: no other field moves, so no other kernel's instruction stream changes.)
+  int lp_col0, lp_tiles;
 };
 // weight row r of up to three matrices side by side (the MFMA GEMMs' DMA sources)
 __device__ __forceinline__ const bf16_t* seg_row(const GemmArgs& g, int r) {
@@ -140,6 +145,15 @@ __device__ __forceinline__ const bf16_t* seg_row(const GemmArgs& g, int r) {
   return g.w2 + (size_t)(r - g.n1) * g.K;
 }
 hipError_t launch_gemm(const GemmArgs& a, hipStream_t s);
+// Which kernel computes which column of launch_gemm(g), plain form: columns [0, c256) on the 256-tile kernel (0: none, g.N: all),
+// the rest on the 128-tile kernel - or, with `half`, on the 256 kernel's half-height tiles.  A caller that runs the problem in column
+// slices (a quantised LM head, api.hip) keeps every column on the kernel the one launch gives it: same kernel, same bits.
+struct GemmPlan {
+  int c256;
+  bool half;
+};
+GemmPlan gemm_plan(const GemmArgs& g);
+hipError_t launch_gemm128(const GemmArgs& g, hipStream_t s);  // the 128-tile kernel, whatever the shape
 bool gemm256_applicable(const GemmArgs& g);  // gemm256.hip: 256x256 tile for the large prefill shapes
 hipError_t launch_gemm256(const GemmArgs& g, hipStream_t s);
 bool gemm256_half_applicable(const GemmArgs& g);  // 128x256 tiles of the same kernel: the columns of a half-filled last round

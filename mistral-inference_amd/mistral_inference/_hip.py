@@ -99,6 +99,13 @@ class MiVerifyOut(C.Structure):
     _fields_ = [("tokens", _vp), ("logprobs", _vp), ("n_accept", _vp)]
 
 
+class MiLmHeadQuant(C.Structure):
+    """`mi_lm_head_quant_t`: the quantisation of the LM head beside an MiModel whose `output` points to quantised bytes."""
+    _fields_ = [("format", C.c_int32), ("scale", _vp)]
+
+
+MI_LM_HEAD_SLICE_ROWS = 8192  # include/mistral_hip.h
+
 _lib: Optional[C.CDLL] = None
 
 _SIGS = {
@@ -181,6 +188,17 @@ _SIGS = {
                                     C.POINTER(MiVerifyOut), _vp]),
     "mi_verify_sample": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_float, C.c_float, C.c_uint64, C.c_uint64,
                                    _vp, _vp, _vp, _vp, _vp]),
+    # a quantised LM head (additive likewise): one forward entry that takes the head's quantisation, and the head as leaves
+    "mi_lm_head_q_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "mi_lm_head_q": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.POINTER(MiLmHeadQuant), _vp, C.c_float,
+                               _vp, C.c_size_t, _vp]),
+    "mi_lm_head_logprobs_q_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "mi_lm_head_logprobs_q": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.POINTER(MiLmHeadQuant), _vp, _vp,
+                                        C.c_size_t, _vp]),
+    "mi_workspace_bytes_q": (C.c_size_t, [C.POINTER(MiModel), C.POINTER(MiW8Model), C.POINTER(MiW4Model), C.POINTER(MiLmHeadQuant),
+                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mi_forward_q": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiW8Model), C.POINTER(MiW4Model), C.POINTER(MiLmHeadQuant),
+                               C.POINTER(MiBatch), C.POINTER(MiVerifyOut), C.c_int, _vp]),
     "mi_workspace_bytes_generic": (C.c_size_t, [C.POINTER(MiModel), C.c_int, C.c_int]),  # ABI v6
     "mi_forward_generic": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiBatch), C.c_int, _vp]),
     "mi_embedding_generic": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
@@ -700,6 +718,50 @@ def lm_head_logprobs(x: torch.Tensor, w: torch.Tensor, target: torch.Tensor) -> 
     check(lib().mi_lm_head_logprobs(dev_ptr(out, torch.float32), dev_ptr(x), x.stride(0), M, K, dev_ptr(w), V,
                                     dev_ptr(tgt, torch.int32), dev_ptr(scratch, torch.uint8), need, stream_ptr(x.device)),
           "mi_lm_head_logprobs")
+    return out
+
+
+def lm_head_quant(q: QuantFormat, scale: torch.Tensor) -> MiLmHeadQuant:
+    """`mi_lm_head_quant_t` of a head in format `q`; the caller keeps `scale` alive while the struct is in use."""
+    hq = MiLmHeadQuant()
+    hq.format, hq.scale = q.format, dev_ptr(scale, q.scale_dtype)
+    return hq
+
+
+def lm_head_q(q: QuantFormat, x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, norm_w: Optional[torch.Tensor] = None,
+              eps: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 [M, vocab] logits of a quantised LM head (mi_lm_head_q): M <= 8 the format's GEMV with the bf16 head's epilogue
+    (norm_w: the final RMSNorm fused), above it the head's bf16 image slice by slice into a per-call scratch + the bf16 GEMM."""
+    assert x.dim() == 2 and x.dtype == torch.bfloat16
+    M, K = x.shape
+    wb = q.prep(w, scale, K)
+    V = wb.shape[0]
+    if out is None:
+        out = torch.empty((M, V), dtype=torch.float32, device=x.device)
+    hq = lm_head_quant(q, scale)
+    need = lib().mi_lm_head_q_scratch_bytes(M, K, V)
+    scratch = torch.empty(need, dtype=torch.uint8, device=x.device) if need else None
+    check(lib().mi_lm_head_q(dev_ptr(out, torch.float32), out.stride(0), dev_ptr(x), x.stride(0), M, K, dev_ptr(wb, torch.uint8), V,
+                             C.byref(hq), dev_ptr(norm_w), float(eps), scratch.data_ptr() if need else None, need,
+                             stream_ptr(x.device)), "mi_lm_head_q")
+    return out
+
+
+def lm_head_logprobs_q(q: QuantFormat, x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """`lm_head_logprobs` on a quantised LM head (mi_lm_head_logprobs_q)."""
+    assert x.dim() == 2 and x.dtype == torch.bfloat16
+    M, K = x.shape
+    wb = q.prep(w, scale, K)
+    V = wb.shape[0]
+    tgt = target.to(device=x.device, dtype=torch.int32).contiguous()
+    assert tgt.numel() == M
+    hq = lm_head_quant(q, scale)
+    need = lib().mi_lm_head_logprobs_q_scratch_bytes(M, K, V)
+    scratch = torch.empty(need, dtype=torch.uint8, device=x.device)
+    out = torch.empty(M, dtype=torch.float32, device=x.device)
+    check(lib().mi_lm_head_logprobs_q(dev_ptr(out, torch.float32), dev_ptr(x), x.stride(0), M, K, dev_ptr(wb, torch.uint8), V,
+                                      C.byref(hq), dev_ptr(tgt, torch.int32), dev_ptr(scratch, torch.uint8), need,
+                                      stream_ptr(x.device)), "mi_lm_head_logprobs_q")
     return out
 
 

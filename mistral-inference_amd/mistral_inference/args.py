@@ -57,6 +57,7 @@ class QuantizationArgs(_FromDict):
     """`quantization` block of params.json: weight-only quantisation of the seven linears of every layer (quant.py)."""
     qformat_weight: str         # "fp8_e4m3": OCP e4m3 bytes + one fp32 scale per output row; "mxfp4": OCP MXFP4, e2m1 codes in
                                 # blocks of 32 along `in` + one e8m0 scale byte per block
+    lm_head: bool = False       # `output.weight` is quantised in the same format too (opt-in; a folder without the key: a bf16 head)
 
     def __post_init__(self) -> None:
         if self.qformat_weight not in QFORMATS:

@@ -87,7 +87,7 @@ def get_model_cls(model_path: str) -> Type[Transformer]:
 def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7, num_pipeline_ranks: int = 1,
                 instruct: bool = False, lora_path: Optional[str] = None, quantize: Optional[str] = None,
                 kv_dtype: Optional[str] = None, speculative: Optional[int] = None, prefill_fp8: bool = False,
-                prefill_w4a8: bool = False) -> None:
+                prefill_w4a8: bool = False, quantize_lm_head: bool = False) -> None:
     """quantize="fp8_e4m3" / "mxfp4": quantise a bf16 checkpoint to weight-only FP8 / MXFP4 while it loads (a folder that
     quant.quantize_checkpoint wrote needs no flag).  kv_dtype="fp8_e4m3": K/V rings of e4m3 bytes (half the bytes; launch path).
     speculative=K: decoding that drafts up to K tokens per step by prompt lookup and verifies them in one pass over the
@@ -95,7 +95,8 @@ def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7,
     generate() names what it does not take).  prefill_fp8: FP8 (e4m3) weights only - prompt
     chunks of 256 tokens or more also quantise their activations per token and run on the FP8 MFMA (quant.py; a speed option, no
     claim about model quality).  prefill_w4a8: the same for MXFP4 weights - the e2m1 codes meet the e4m3 activations on the mixed
-    FP4 x FP8 MFMA, block scales applied by the instruction."""
+    FP4 x FP8 MFMA, block scales applied by the instruction.  quantize_lm_head: the LM head is quantised in the weight format too
+    (opt-in, a weight format only; no claim about model quality)."""
     kv = kv_dtype_arg(kv_dtype)  # (an unknown name is refused before anything is loaded)
     spec = speculative_arg(speculative)
     if spec is not None and temperature > 0:  # (the tool's user asked for both: sampled verify steps)
@@ -106,7 +107,8 @@ def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7,
     tokenizer = mistral_tokenizer.instruct_tokenizer.tokenizer
     model = get_model_cls(model_path).from_folder(Path(model_path), max_batch_size=3,
                                                   num_pipeline_ranks=num_pipeline_ranks, dtype=torch.bfloat16, quantize=quantize,
-                                                  prefill_fp8=bool(prefill_fp8), prefill_w4a8=bool(prefill_w4a8))
+                                                  prefill_fp8=bool(prefill_fp8), prefill_w4a8=bool(prefill_w4a8),
+                                                  quantize_lm_head=bool(quantize_lm_head))
     if lora_path is not None:  # reference main.py:131-132
         model.load_lora(Path(lora_path))
     messages: List = []
@@ -139,8 +141,8 @@ def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7,
 
 def demo(model_path: str, max_tokens: int = 35, temperature: float = 0, lora_path: Optional[str] = None,
          quantize: Optional[str] = None, kv_dtype: Optional[str] = None, speculative: Optional[int] = None,
-         prefill_fp8: bool = False, prefill_w4a8: bool = False) -> None:
-    """quantize, kv_dtype, speculative, prefill_fp8, prefill_w4a8: as `interactive` (a speculative generation takes one prompt: the three run one by one)."""
+         prefill_fp8: bool = False, prefill_w4a8: bool = False, quantize_lm_head: bool = False) -> None:
+    """quantize, kv_dtype, speculative, prefill_fp8, prefill_w4a8, quantize_lm_head: as `interactive` (a speculative generation takes one prompt: the three run one by one)."""
     kv = kv_dtype_arg(kv_dtype)
     spec = speculative_arg(speculative)
     if spec is not None and temperature > 0:  # (the tool's user asked for both: sampled verify steps)
@@ -149,7 +151,8 @@ def demo(model_path: str, max_tokens: int = 35, temperature: float = 0, lora_pat
     should_print = _should_print()
     model = get_model_cls(model_path).from_folder(Path(model_path), max_batch_size=3,
                                                   num_pipeline_ranks=num_pipeline_ranks, dtype=torch.bfloat16, quantize=quantize,
-                                                  prefill_fp8=bool(prefill_fp8), prefill_w4a8=bool(prefill_w4a8))
+                                                  prefill_fp8=bool(prefill_fp8), prefill_w4a8=bool(prefill_w4a8),
+                                                  quantize_lm_head=bool(quantize_lm_head))
     if lora_path is not None:  # reference main.py:224-225
         model.load_lora(Path(lora_path))
     tokenizer = load_tokenizer(Path(model_path)).instruct_tokenizer.tokenizer

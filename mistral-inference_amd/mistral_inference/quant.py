@@ -44,7 +44,14 @@ the block-scaled MFMA, which takes the checkpoint's e8m0 bytes as its block scal
 with the sum in fp32 and no dequantisation pass.  On activations that e4m3 holds exactly under the row scale this is the
 weight-only route up to fp32 summation order (lossless); on real activations it is a coarser model, nobody claims model quality for
 it, and it is off unless asked for.  For scale bytes below 3 the weight-only route's bf16 image holds subnormals, which it may
-flush and this route does not.  Every other shape takes the weight-only MXFP4 routes, bit for bit."""
+flush and this route does not.  Every other shape takes the weight-only MXFP4 routes, bit for bit.
+
+A quantised LM head (`quantization.lm_head`, opt-in: `quantize_checkpoint(..., lm_head=True)`, `from_folder(...,
+quantize_lm_head=True)`): `output.weight` / `output.qscale_weight` in the layers' format, `model.output` the format's QuantLinear.
+On quantised layers the bf16 head is the largest tensor a decode step reads (1.34 GB at vocab 131072 x dim 5120).  At T <= 8 the
+head is the format's GEMV with the bf16 head's epilogue - logit = float(bf16(acc * qscale_weight[r])), MXFP4 float(bf16(acc)); above,
+its bf16 image is made in slices of 8192 vocabulary rows in front of the bf16 GEMM (csrc/api.hip head_gemm_sliced), bit-equal to
+the GEMM on the whole image.  The embedding table stays bf16.  Nobody claims model quality."""
 import json
 import re
 from pathlib import Path
@@ -353,11 +360,34 @@ def quantized_linear_cls(quantization: QuantizationArgs):
     return QUANT_LINEARS[quantization.qformat_weight]
 
 
-def quantize_state_tensor(key: str, t: torch.Tensor, qformat: str = QFORMAT_FP8_E4M3) -> Dict[str, torch.Tensor]:
+LM_HEAD_KEY = "output.weight"                                  # the LM head: quantised only on request (`lm_head`)
+LM_HEAD_SCALE_KEY = "output." + QSCALE_KEY
+
+
+def refuse_lm_head_arg(quantize_lm_head: bool, quantization: Optional[QuantizationArgs]) -> None:
+    """`quantize_lm_head=True` on a model without a weight format, by name, before anything is read from disk."""
+    if quantize_lm_head and quantization is None:
+        raise NotImplementedError("quantize_lm_head=True without a weight format is not implemented: the LM head is quantised in the "
+                                  "format of the model's layers (quantize=\"fp8_e4m3\" / \"mxfp4\", or a folder that quantize_checkpoint wrote)")
+
+
+def check_lm_head_tensors(folder, quantization: QuantizationArgs, keys) -> None:
+    """A quantised folder's `lm_head` flag and its tensors must agree (ValueError otherwise): the flag promises
+    `output.qscale_weight` beside the head's bytes, its absence a bf16 `output.weight` alone."""
+    has_scale = LM_HEAD_SCALE_KEY in keys
+    if quantization.lm_head and not has_scale:
+        raise ValueError(f"{folder}: params.json says quantization.lm_head but the checkpoint has no {LM_HEAD_SCALE_KEY} "
+                         "(the flag and the tensors disagree)")
+    if has_scale and not quantization.lm_head:
+        raise ValueError(f"{folder}: the checkpoint has {LM_HEAD_SCALE_KEY} but params.json does not say quantization.lm_head "
+                         "(the flag and the tensors disagree)")
+
+
+def quantize_state_tensor(key: str, t: torch.Tensor, qformat: str = QFORMAT_FP8_E4M3, lm_head: bool = False) -> Dict[str, torch.Tensor]:
     """One checkpoint tensor -> the tensors that replace it: a quantised linear becomes its bytes and its row (MXFP4: block)
-    scales, anything else stays as it is."""
+    scales, anything else stays as it is.  lm_head: `output.weight` is such a linear too."""
     check_quantize_arg(qformat)
-    if not is_quantized_linear_key(key):
+    if not (is_quantized_linear_key(key) or (lm_head and key == LM_HEAD_KEY)):
         return {key: t}
     cls = QUANT_LINEARS[qformat]
     if t.dtype != torch.bfloat16:
@@ -366,11 +396,13 @@ def quantize_state_tensor(key: str, t: torch.Tensor, qformat: str = QFORMAT_FP8_
     return {key: q, key[:-len("weight")] + QSCALE_KEY: scale}
 
 
-def quantize_checkpoint(src_folder: Union[Path, str], dst_folder: Union[Path, str], qformat: str = QFORMAT_FP8_E4M3) -> Path:
+def quantize_checkpoint(src_folder: Union[Path, str], dst_folder: Union[Path, str], qformat: str = QFORMAT_FP8_E4M3,
+                        lm_head: bool = False) -> Path:
     """bf16 folder (params.json + consolidated.safetensors) -> weight-only quantised folder, tensor by tensor on the CPU: the
     seven linears of every layer become `<linear>.weight` (F8_E4M3) + `<linear>.qscale_weight` (fp32 [out]), or with
-    qformat="mxfp4" U8 [out, in / 2] + U8 [out, in / 32]; everything else is copied.  Other files of the folder (tokenizer) are
-    the caller's to copy."""
+    qformat="mxfp4" U8 [out, in / 2] + U8 [out, in / 32]; everything else is copied.  lm_head=True (opt-in): `output.weight`
+    and `output.qscale_weight` likewise, and `"lm_head": true` in the `quantization` block; without it the block has no such key
+    and the head stays bf16.  Other files of the folder (tokenizer) are the caller's to copy."""
     import safetensors
     from safetensors.torch import save_file
     from .args import TransformerArgs
@@ -389,10 +421,12 @@ def quantize_checkpoint(src_folder: Union[Path, str], dst_folder: Union[Path, st
     out: Dict[str, torch.Tensor] = {}
     with safetensors.safe_open(str(st_file), framework="pt", device="cpu") as f:
         for k in f.keys():
-            out.update(quantize_state_tensor(k, f.get_tensor(k), qformat))
+            out.update(quantize_state_tensor(k, f.get_tensor(k), qformat, lm_head))
+    if lm_head and LM_HEAD_SCALE_KEY not in out:
+        raise ValueError(f"{src}: lm_head=True but the checkpoint has no {LM_HEAD_KEY}")
     dst.mkdir(parents=True, exist_ok=True)
     save_file(out, str(dst / "consolidated.safetensors"))
-    params["quantization"] = {"qformat_weight": qformat}
+    params["quantization"] = {"qformat_weight": qformat, **({"lm_head": True} if lm_head else {})}
     with open(dst / "params.json", "w") as f:
         json.dump(params, f)
     return dst

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import dataclasses
 import json
 import logging
 import math
@@ -33,8 +34,9 @@ from .args import QuantizationArgs, TransformerArgs
 from .cache import BatchMetadata, BufferCache
 from .lora import LoRALinear, check_rank
 from .model import ModelBase
-from .quant import (QSCALE_ACT_KEY, QSCALE_KEY, QuantLinear, check_quantize_arg, quantize_state_tensor, quantized_linear_cls,
-                    refusal, refuse_prefill_fp8, refuse_prefill_w4a8, refuse_quant_combinations)
+from .quant import (LM_HEAD_KEY, QSCALE_ACT_KEY, QSCALE_KEY, QuantLinear, check_lm_head_tensors, check_quantize_arg,
+                    quantize_state_tensor, quantized_linear_cls, refusal, refuse_lm_head_arg, refuse_prefill_fp8, refuse_prefill_w4a8,
+                    refuse_quant_combinations)
 from .rope import precompute_freqs_cis
 from .transformer_layers import LORA_MOE_REFUSAL, RMSNorm, TransformerBlock
 from .vision_encoder import PATCH_MERGE, PatchMerger, VisionLanguageAdapter, VisionTransformer
@@ -102,6 +104,8 @@ class HipStackBackend:
         # set by _build_plan for a weight-only quantised model: (its mi_w8_model_t / mi_w4_model_t, the format's workspace query,
         # the format's forward, that forward's name)
         self._quant: Optional[Tuple[Any, Any, Any, str]] = None
+        # ... whose LM head is quantised too: its mi_lm_head_quant_t (the forwards then go through mi_forward_q)
+        self._head: Optional[Any] = None
 
     # -- one-time: pointer tables of the weights -------------------------------------------------
     def _build_plan(self, model: "Transformer"):
@@ -124,6 +128,7 @@ class HipStackBackend:
                                           "dim / hidden_dim multiples of 8) is not implemented; merge the adapter into the weights")
         self.dtype_code = _hip.DTYPE_CODES[dt]
         keep = []  # python objects that own memory referenced by raw pointers
+        self._head = None
         p = lambda t, d=dt: _hip.dev_ptr(t, d)  # noqa: E731
         qf = quantized_linear_cls(a.quantization).hip if a.quantization is not None else None
         if qf is not None:
@@ -182,7 +187,14 @@ class HipStackBackend:
         m.norm_eps = a.norm_eps
         m.tok_embeddings = p(model.tok_embeddings.weight) if model.tok_embeddings is not None else None
         m.final_norm = p(model.norm.weight) if model.norm is not None else None
-        m.output = p(model.output.weight) if model.output is not None else None
+        # a quantised LM head (quantization.lm_head, the last rank only): `output` points to its bytes and its scales ride in an
+        # mi_lm_head_quant_t, which the one entry that takes it (mi_forward_q) is handed for every forward of this model
+        head_q = qf is not None and isinstance(model.output, QuantLinear)
+        if head_q:
+            assert model.output.hip is qf, "a quantised LM head is in the layers' format"
+            model.output.check_bound("output")
+            self._head = _hip.lm_head_quant(qf, model.output.qscale_weight)
+        m.output = (_hip.dev_ptr(model.output.weight, torch.uint8) if head_q else p(model.output.weight)) if model.output is not None else None
         m.rope_cs, m.rope_len = p(rope, torch.float32), rope.shape[0]
         m.layers = C.cast(layers, C.POINTER(_hip.MiLayer))
         if a.lora is not None:
@@ -228,6 +240,7 @@ class HipStackBackend:
     def invalidate(self) -> None:
         self._plan = None
         self._quant = None
+        self._head = None
         self._workspace = None
 
     def raise_if_flagged(self) -> None:
@@ -279,8 +292,17 @@ class HipStackBackend:
         _hip.set_decode_engine(False)
         HipStackBackend._engine_suspended = True
 
+    def _quant_refs(self):
+        """(w8, w4): the model's quantisation as the entries that take both formats are handed it."""
+        qm = self._quant[0] if self._quant is not None else None
+        return (C.byref(qm) if isinstance(qm, _hip.MiW8Model) else None, C.byref(qm) if isinstance(qm, _hip.MiW4Model) else None)
+
     def _get_workspace(self, model: "Transformer", m, T: int, B: int, max_w: int, kv_layout: int = 0, verify: bool = False) -> torch.Tensor:
-        if verify:  # (split partials per row and the K | V stash of every layer: mi_workspace_bytes_verify)
+        if self._head is not None:  # a quantised LM head: the one query beside the one entry (+ the head's slice at T > 8)
+            w8, w4 = self._quant_refs()
+            need = _hip.lib().mi_workspace_bytes_q(C.byref(m), w8, w4, C.byref(self._head), T, B, max_w, kv_layout,
+                                                   int(model.prefill_fp8 or model.prefill_w4a8), int(verify))
+        elif verify:  # (split partials per row and the K | V stash of every layer: mi_workspace_bytes_verify)
             need = _hip.lib().mi_workspace_bytes_verify(C.byref(m), 1 if self._quant is not None else 0, T, max_w, kv_layout)
         elif self.generic:
             need = _hip.lib().mi_workspace_bytes_generic(C.byref(m), T, self.dtype_code)
@@ -344,6 +366,7 @@ class HipStackBackend:
             bt.seq_adapter = _hip.dev_ptr(seq_adapter, i32)
         wsb = self._get_workspace(model, m, T, B, max_w, bt.kv_layout, verify=verify is not None)
         bt.workspace, bt.workspace_bytes = wsb.data_ptr(), wsb.numel()
+        vo = None
         if verify is not None:
             if temperature > 0:  # (the greedy buffers are NULL in a verify step: these fields mean the sampled verification)
                 bt.sample_temperature, bt.sample_top_p = float(temperature), float(top_p)
@@ -351,9 +374,12 @@ class HipStackBackend:
             vo = _hip.MiVerifyOut()
             vo.tokens, vo.logprobs = _hip.dev_ptr(verify[0], torch.long), _hip.dev_ptr(verify[1], torch.float32)
             vo.n_accept = _hip.dev_ptr(verify[2], i32)
-            qm = self._quant[0] if self._quant is not None else None
-            w8 = C.byref(qm) if isinstance(qm, _hip.MiW8Model) else None
-            w4 = C.byref(qm) if isinstance(qm, _hip.MiW4Model) else None
+        if self._head is not None:  # a quantised LM head: every forward of the model - prefill, decode and verify steps - is this entry
+            w8, w4 = self._quant_refs()
+            _hip.check(_hip.lib().mi_forward_q(C.byref(m), w8, w4, C.byref(self._head), C.byref(bt), C.byref(vo) if vo is not None else None,
+                                               int(model.prefill_fp8 or model.prefill_w4a8), _hip.stream_ptr(h.device)), "mi_forward_q")
+        elif verify is not None:
+            w8, w4 = self._quant_refs()
             _hip.check(_hip.lib().mi_forward_verify(C.byref(m), w8, w4, C.byref(bt), C.byref(vo), _hip.stream_ptr(h.device)),
                        "mi_forward_verify")
         elif self.generic:
@@ -410,7 +436,10 @@ class Transformer(ModelBase):
                                                     spatial_merge_size=ve.spatial_merge_size)
         if pipeline_rank == num_pipeline_ranks - 1:
             self.norm = RMSNorm(args.dim, eps=args.norm_eps)
-            self.output = nn.Linear(args.dim, args.vocab_size, bias=False)
+            if args.quantization is not None and args.quantization.lm_head:  # (opt-in; ranks without a head ignore the flag)
+                self.output = quantized_linear_cls(args.quantization)(args.dim, args.vocab_size, bias=False)
+            else:
+                self.output = nn.Linear(args.dim, args.vocab_size, bias=False)
         # Only this rank's contiguous layer range is ever constructed (the reference builds all n_layers
         # blocks and throws the rest away, transformer.py:80-98); keys stay GLOBAL layer ids.
         per_rank = math.ceil(self.n_layers / self.num_pipeline_ranks)
@@ -830,9 +859,15 @@ class Transformer(ModelBase):
             self.pp_comm.broadcast(targets, src=0)
         if last_rank:
             assert self.output is not None
-            lp = _hip.lm_head_logprobs(h, self.output.weight, targets)
             ends = torch.tensor(seqlens, device=dev).cumsum(dim=0) - 1
-            last = _hip.linear(h.index_select(0, ends).contiguous(), (self.output.weight,), _hip.EPI_LOGITS)
+            h_last = h.index_select(0, ends).contiguous()
+            if isinstance(self.output, QuantLinear):  # a quantised LM head: the same two reductions on its bytes and scales
+                out = self.output
+                lp = _hip.lm_head_logprobs_q(out.hip, h, out.weight, out.qscale_weight, targets)
+                last = _hip.lm_head_q(out.hip, h_last, out.weight, out.qscale_weight)
+            else:
+                lp = _hip.lm_head_logprobs(h, self.output.weight, targets)
+                last = _hip.linear(h_last, (self.output.weight,), _hip.EPI_LOGITS)
         else:
             lp = torch.empty(T, dtype=torch.float32, device=dev)
             last = torch.empty((B, self.vocab_size), dtype=torch.float32, device=dev)
@@ -953,7 +988,7 @@ class Transformer(ModelBase):
     def from_folder(folder: Union[Path, str], max_batch_size: int = 1, num_pipeline_ranks: int = 1,
                     device: Union[torch.device, str] = "cuda", dtype: Optional[torch.dtype] = None,
                     softmax_fp32: bool = True, backend: Optional[Any] = None, quantize: Optional[str] = None,
-                    prefill_fp8: bool = False, prefill_w4a8: bool = False) -> "Transformer":
+                    prefill_fp8: bool = False, prefill_w4a8: bool = False, quantize_lm_head: bool = False) -> "Transformer":
         """params.json + exactly one of consolidated.00.pth / consolidated.safetensors (reference
         transformer.py:297-338).  With safetensors only this rank's tensors are read, straight to `device`
         (the reference loads the whole file to the host on every rank).
@@ -964,7 +999,11 @@ class Transformer(ModelBase):
         device as it arrives, so the bf16 model is never resident.
 
         prefill_fp8=True (FP8 e4m3 weights only, whether quantised here or in the folder): `model.prefill_fp8`, the FP8 prefill GEMMs.
-        prefill_w4a8=True (MXFP4 weights only, likewise): `model.prefill_w4a8`, the MXFP4 x FP8 prefill GEMMs."""
+        prefill_w4a8=True (MXFP4 weights only, likewise): `model.prefill_w4a8`, the MXFP4 x FP8 prefill GEMMs.
+
+        quantize_lm_head=True (opt-in, with a weight format only): the LM head is quantised in the layers' format too while it
+        loads - `model.output` becomes the format's QuantLinear - unless the folder's `quantization.lm_head` says it already is.
+        Ranks that hold no head ignore it."""
         folder = Path(folder)
         check_quantize_arg(quantize)
         with open(folder / "params.json", "r") as f:
@@ -975,6 +1014,12 @@ class Transformer(ModelBase):
         on_load = quantize is not None and model_args.quantization is None  # (an already quantised folder loads as it is)
         if on_load:
             model_args.quantization = QuantizationArgs(quantize)
+        refuse_lm_head_arg(quantize_lm_head, model_args.quantization)
+        # the head is quantised while it loads when it was asked for and the folder has not done it
+        head_on_load = quantize_lm_head and not model_args.quantization.lm_head
+        head_in_folder = model_args.quantization is not None and model_args.quantization.lm_head
+        if head_on_load:
+            model_args.quantization.lm_head = True
         if prefill_fp8:
             refuse_prefill_fp8(model_args, dtype)
         if prefill_w4a8:
@@ -1000,12 +1045,16 @@ class Transformer(ModelBase):
         plain = {k.replace(".linear.weight", ".weight") for k in wanted if k.endswith(".linear.weight")} if model_args.lora else set()
         loaded = {}
         with safetensors.safe_open(str(st_file), framework="pt", device=str(device)) as f:
+            if model_args.quantization is not None and not on_load:  # a quantised folder: its lm_head flag and its tensors agree
+                check_lm_head_tensors(folder, dataclasses.replace(model_args.quantization, lm_head=head_in_folder), set(f.keys()))
             for k in f.keys():
                 if k.endswith(QSCALE_ACT_KEY):
                     raise ValueError(f"Unexpected key {k} (per-tensor activation scales: FP8 activations are not implemented)")
                 if k in wanted or k in plain:
                     if on_load:  # one tensor at a time: a linear becomes its e4m3 bytes and row scales, the rest passes
-                        loaded.update(quantize_state_tensor(k, f.get_tensor(k), quantize))
+                        loaded.update(quantize_state_tensor(k, f.get_tensor(k), quantize, head_on_load))
+                    elif head_on_load and k == LM_HEAD_KEY:  # a quantised folder with a bf16 head: the head alone, in the folder's format
+                        loaded.update(quantize_state_tensor(k, f.get_tensor(k), model_args.quantization.qformat_weight, True))
                     else:
                         loaded[k] = f.get_tensor(k)
                 else:
