@@ -705,6 +705,78 @@ int mi_attention_nocache_generic(void* out, const void* qkv, int ld, int T, int 
 int mi_swiglu_generic(void* a, const void* b, int T, int F, int dtype, mi_stream_t stream);
 int mi_gelu_generic(void* x, int ldx, int T, int N, int dtype, mi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Mamba2 (reference mamba.py:23-83, which hands the whole model to the external mamba_ssm package; args.py:62-76).
+ * Additive to ABI v9: the presence of mi_forward_mamba is the feature test.  csrc/mamba.hip.
+ *
+ * Fixed by the reference's MambaConfig / Mamba2 defaults: d_state N = 128, d_conv = 4, expand = 2 (d_inner I = 2 D), headdim
+ * P = 64 (H = I / 64 heads), conv_dim Cc = I + 2 G N, in_proj width 2 I + 2 G N + H, both eps 1e-5, linears without bias.
+ * The rule of one layer, for hidden rows h_t (bf16) and the residual r_t (fp32; r = 0 in front of the first layer):
+ *   1  r_t += float(h_t);  u_t = bf16(r_t * rsqrt(mean(r_t^2) + eps) * float(w_norm))                  one rounding
+ *   2  zxbcdt_t = bf16(W_in u_t)                      columns z [I] | xBC [Cc] | dt [H]           mi_linear, MI_EPI_STORE
+ *   3  per channel c of xBC: a = bias[c] + sum_{j=0..3} w[c,j] xBC[t-3+j, c] in fp32 (rows before the sequence start: the conv
+ *      state, zeros on a fresh cache);  xBC'_t = bf16(a * sigmoid(a)), split x [H, P] | B [G, N] | C [G, N]
+ *   4  per head h, g = h / (H / G):  dt = softplus(float(dt_raw) + dt_bias[h])  (the argument itself above 20, else log1p(exp));
+ *      a = dt * (-exp(A_log[h]));  S [P, N] fp32:  S <- exp(a) S + dt x_t (x) B_t;  y_t[p] = bf16(sum_n S[p,n] C_t[n] + D[h] x_t[p])
+ *   5  per group of I / G channels: v = float(y) silu(float(z));  o = bf16(v * rsqrt(mean_group(v^2) + eps) * float(w_gn))
+ *   6  h_t = bf16(W_out o_t)                                                                      mi_linear, MI_EPI_STORE
+ * and behind the last layer step 1 with norm_f, then logits = float(bf16(W_head u)) (MI_EPI_LOGITS).
+ * For L >= 2 tokens step 4 runs in the chunked form over chunks of Q = 64 tokens, Lambda_t the fp32 running sum of a in the chunk:
+ *   Y = bf16((C B^T) o M) x + exp(Lambda_t) o (C bf16(S_prev)^T) + D x,      M[t,s] = exp(Lambda_t - Lambda_s) dt_s (s <= t)
+ *   S <- exp(Lambda_Q) S_prev + (bf16(exp(Lambda_Q - Lambda_s) dt_s B_s))^T x
+ * - the three bf16 roundings written out are the only ones beside the rule's; products on the bf16 MFMA, fp32 accumulation.
+ * Two deliberate differences from mamba_ssm: the SSM state stays fp32 between calls (mamba_ssm keeps it in the model dtype
+ * and so rounds it at every decode step); the conv state is the last 3 raw xBC rows in bf16, oldest first.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Step 1.  residual fp32 [T, D] in place, h bf16 [T, D] or NULL (no add: the residual stays as it is), out bf16 [T, D].
+ * D a multiple of 8 up to 8192 (MI_ERR_SHAPE otherwise). */
+int mi_mamba_add_norm(void* out, float* residual, const void* h, const void* w, int T, int D, float eps, mi_stream_t stream);
+
+/* Steps 3 and 4 for B sequences of L tokens each (rows b * L + t of zxbcdt [B * L, ld] and of y [B * L, 64 H]).  L == 1: one
+ * recurrence step on the fp32 VALU; L >= 2: the chunked form.  conv_w bf16 [Cc, 4], conv_b bf16 [Cc]; dt_bias, A_log, Dskip
+ * fp32 [H]; conv_state bf16 [B, 3, Cc] and ssm_state fp32 [B, H, 64, 128] are read and updated in place (the conv state by a
+ * launch of its own behind the scan: the B | C columns of a group are read by all of its heads).  H % G != 0, or ld not a
+ * multiple of 8 or below 2 I + 2 G N + H: MI_ERR_SHAPE. */
+int mi_mamba_scan(void* y, const void* zxbcdt, int ld, const void* conv_w, const void* conv_b, const float* dt_bias,
+                  const float* A_log, const float* Dskip, void* conv_state, float* ssm_state, int B, int L, int H, int G,
+                  mi_stream_t stream);
+
+/* Step 5.  y bf16 [T, I], zxbcdt [T, ld] (its first I columns are z), w bf16 [I], out bf16 [T, I] (may be y).  I / G a multiple of
+ * 8 up to 8192 (MI_ERR_SHAPE otherwise). */
+int mi_mamba_gated_norm(void* out, const void* y, const void* zxbcdt, int ld, const void* w, int T, int I, int G, float eps,
+                        mi_stream_t stream);
+
+typedef struct {
+  const void *norm, *in_proj, *conv_w, *conv_b;   /* bf16 [D], [2I+2GN+H, D], [Cc, 4], [Cc] */
+  const float *dt_bias, *A_log, *D;               /* fp32 [H] */
+  const void *gated_norm, *out_proj;              /* bf16 [I], [D, I] */
+} mi_mamba_layer_t;
+
+typedef struct {
+  int32_t dim, n_layers, vocab_size, n_groups;    /* vocab_size: the rows of the two tables (the padded vocabulary) */
+  float eps;
+  const void *embedding, *norm_f, *lm_head;       /* bf16 [V, D], [D], [V, D] */
+  const mi_mamba_layer_t* layers;                 /* host array [n_layers] */
+} mi_mamba_model_t;
+
+typedef struct {
+  const int64_t* ids;              /* device [B * L], sequence-major */
+  int32_t B, L;
+  void* const* conv_state;         /* host arrays [n_layers] of device pointers: bf16 [B, 3, Cc] ... */
+  float* const* ssm_state;         /* ... and fp32 [B, H, 64, 128], continued from and updated in place */
+  void* workspace;
+  size_t workspace_bytes;          /* >= mi_workspace_bytes_mamba(model, B, L) */
+  float* logits;                   /* fp32 [B * L, V], or [B, V] with last_only */
+  int32_t last_only;               /* != 0: only the last row of every sequence goes through the LM head */
+} mi_mamba_batch_t;
+
+/* 0 for a model the runner refuses */
+size_t mi_workspace_bytes_mamba(const mi_mamba_model_t* model, int B, int L);
+/* The layer stack, launch by launch (no engine, no graph of its own).  dim not a multiple of 64 or above 8192, H % n_groups != 0,
+ * I / n_groups above 8192: MI_ERR_SHAPE naming the value, before any launch. */
+int mi_forward_mamba(const mi_mamba_model_t* model, const mi_mamba_batch_t* batch, mi_stream_t stream);
+
 /* Persistent decode engine (csrc/decode_engine.hip).  A DECODE-branch mi_forward with T == B == 1 on a dense model runs
  * all local layers - TransformerBlock.forward (transformer_layers.py:158-169) x n_layers, the ring write (cache.py:83-92)
  * and the LM head (transformer.py:235) - as ONE persistent launch when the shapes allow it (dim, hidden_dim and

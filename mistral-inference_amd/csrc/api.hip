@@ -2096,3 +2096,128 @@ int mi_forward_generic(const mi_model_t* m, const mi_batch_t* bt, int dtype, mi_
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- Mamba2 (mamba.hip)
+// The leaves of the sequence mixer and the layer-stack runner of a Mamba2 model: per layer the fp32 residual add + RMSNorm, the
+// in_proj linear (linear_group: GEMV up to 8 rows, MFMA GEMM above), the scan, the gated norm and the out_proj linear.
+namespace {
+
+struct MambaDims {
+  int D, I, H, G, Cc, width, ld;  // ld: the zxbcdt row stride the runner uses (width rounded up to 16-byte rows)
+};
+
+int mamba_dims(const char* me, const mi_mamba_model_t* m, MambaDims* d) {
+  if (!m) return fail(MI_ERR_ARG, "%s: null model", me);
+  if (m->dim <= 0 || m->dim % 64) return fail(MI_ERR_SHAPE, "%s: dim %d must be a multiple of 64 (heads of 64 channels)", me, m->dim);
+  if (!mamba_row_ok(m->dim)) return fail(MI_ERR_SHAPE, "%s: dim %d above %d", me, m->dim, MAMBA_MAX_ROW);
+  d->D = m->dim; d->I = 2 * m->dim; d->H = d->I / 64; d->G = m->n_groups;
+  if (d->G <= 0 || d->H % d->G) return fail(MI_ERR_SHAPE, "%s: n_heads %d %% n_groups %d != 0", me, d->H, d->G);
+  if (!mamba_row_ok(d->I / d->G)) return fail(MI_ERR_SHAPE, "%s: d_inner / n_groups = %d above %d", me, d->I / d->G, MAMBA_MAX_ROW);
+  d->Cc = d->I + 2 * d->G * 128;
+  d->width = d->I + d->Cc + d->H;
+  d->ld = (d->width + 7) / 8 * 8;
+  if (m->n_layers <= 0 || m->vocab_size <= 0) return fail(MI_ERR_ARG, "%s: n_layers %d, vocab_size %d", me, m->n_layers, m->vocab_size);
+  return MI_OK;
+}
+
+struct MambaWorkspace {
+  float* res;   // [T, D] fp32 residual stream
+  bf16_t* u;    // [T, D] normed rows
+  bf16_t* h;    // [T, D] hidden rows (embedding, out_proj)
+  bf16_t* zx;   // [T, ld]
+  bf16_t* y;    // [T, I] scan output; the gated norm runs in place
+  size_t total;
+};
+MambaWorkspace mamba_carve(const MambaDims& d, size_t T, char* base) {
+  MambaWorkspace w;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* p = base ? base + off : nullptr;
+    off += align_up(bytes);
+    return p;
+  };
+  w.res = (float*)take(T * d.D * 4);
+  w.u = (bf16_t*)take(T * d.D * 2);
+  w.h = (bf16_t*)take(T * d.D * 2);
+  w.zx = (bf16_t*)take(T * d.ld * 2);
+  w.y = (bf16_t*)take(T * d.I * 2);
+  w.total = off;
+  return w;
+}
+
+int mamba_linear(void* out, int ldo, const void* x, int ldx, int M, int K, const void* w, int n_rows, int epi, const char* gemv,
+                 const char* gemm, hipStream_t s) {
+  const LinearGroup g = group_of(K, w, n_rows);
+  LinearCall c = {x, ldx, nullptr, 0.f, out, ldo, nullptr, epi};
+  c.what = {gemv, gemm};
+  return linear_group(g, c, M, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi_mamba_add_norm(void* out, float* residual, const void* h, const void* w, int T, int D, float eps, mi_stream_t stream) {
+  if (!mamba_row_ok(D)) return fail(MI_ERR_SHAPE, "mi_mamba_add_norm: D = %d must be a multiple of 8 up to %d", D, MAMBA_MAX_ROW);
+  if (!out || !residual || !w || T <= 0) return fail(MI_ERR_ARG, "mi_mamba_add_norm");
+  return hip_rc(launch_mamba_add_norm(out, residual, h, w, T, D, eps, false, (hipStream_t)stream), "mamba add + norm");
+}
+
+int mi_mamba_scan(void* y, const void* zxbcdt, int ld, const void* conv_w, const void* conv_b, const float* dt_bias,
+                  const float* A_log, const float* Dskip, void* conv_state, float* ssm_state, int B, int L, int H, int G,
+                  mi_stream_t stream) {
+  if (B <= 0 || L <= 0 || H <= 0 || G <= 0 || B > 65535) return fail(MI_ERR_ARG, "mi_mamba_scan: B %d, L %d, H %d, G %d", B, L, H, G);
+  if (H % G) return fail(MI_ERR_SHAPE, "mi_mamba_scan: n_heads %d %% n_groups %d != 0", H, G);
+  const int width = 2 * 64 * H + 2 * G * 128 + H;
+  if (ld % 8 || ld < width) return fail(MI_ERR_SHAPE, "mi_mamba_scan: ld = %d must be a multiple of 8 and at least %d", ld, width);
+  if (!y || !zxbcdt || !conv_w || !conv_b || !dt_bias || !A_log || !Dskip || !conv_state || !ssm_state) return fail(MI_ERR_ARG, "mi_mamba_scan");
+  const MambaScanArgs a = {y, zxbcdt, ld, conv_w, conv_b, dt_bias, A_log, Dskip, conv_state, ssm_state, B, L, H, G};
+  return hip_rc(launch_mamba_scan(a, (hipStream_t)stream), L == 1 ? "mamba step" : "mamba chunk scan");
+}
+
+int mi_mamba_gated_norm(void* out, const void* y, const void* zxbcdt, int ld, const void* w, int T, int I, int G, float eps,
+                        mi_stream_t stream) {
+  if (G <= 0 || I <= 0 || I % G || !mamba_row_ok(I / G))
+    return fail(MI_ERR_SHAPE, "mi_mamba_gated_norm: I = %d over G = %d groups: the group must be a multiple of 8 up to %d", I, G, MAMBA_MAX_ROW);
+  if (ld % 8 || ld < I) return fail(MI_ERR_SHAPE, "mi_mamba_gated_norm: ld = %d must be a multiple of 8 and at least %d", ld, I);
+  if (!out || !y || !zxbcdt || !w || T <= 0) return fail(MI_ERR_ARG, "mi_mamba_gated_norm");
+  return hip_rc(launch_mamba_gated_norm(out, y, zxbcdt, ld, w, T, I, G, eps, (hipStream_t)stream), "mamba gated norm");
+}
+
+size_t mi_workspace_bytes_mamba(const mi_mamba_model_t* model, int B, int L) {
+  MambaDims d;
+  if (B <= 0 || L <= 0 || mamba_dims("mi_workspace_bytes_mamba", model, &d) != MI_OK) return 0;
+  return mamba_carve(d, (size_t)B * L, nullptr).total;
+}
+
+int mi_forward_mamba(const mi_mamba_model_t* m, const mi_mamba_batch_t* bt, mi_stream_t stream) {
+  const char* me = "mi_forward_mamba";
+  MambaDims d;
+  MI_TRY(mamba_dims(me, m, &d));
+  if (!m->layers || !m->embedding) return fail(MI_ERR_ARG, "%s: model pointers", me);
+  if (!bt || bt->B <= 0 || bt->L <= 0 || bt->B > 65535 || !bt->ids || !bt->conv_state || !bt->ssm_state || !bt->workspace)
+    return fail(MI_ERR_ARG, "%s: batch", me);
+  if (bt->logits && (!m->norm_f || !m->lm_head)) return fail(MI_ERR_ARG, "%s: logits without norm_f / lm_head", me);
+  const int B = bt->B, L = bt->L, T = B * L;
+  const MambaWorkspace ws = mamba_carve(d, (size_t)T, (char*)bt->workspace);
+  if (ws.total > bt->workspace_bytes) return fail(MI_ERR_WORKSPACE, "workspace %zu < required %zu", bt->workspace_bytes, ws.total);
+  hipStream_t s = (hipStream_t)stream;
+  MI_TRY(hip_rc(launch_embedding(ws.h, m->embedding, bt->ids, T, d.D, m->vocab_size, nullptr, s), "embedding"));
+  for (int l = 0; l < m->n_layers; ++l) {
+    const mi_mamba_layer_t& ly = m->layers[l];
+    MI_TRY(hip_rc(launch_mamba_add_norm(ws.u, ws.res, ws.h, ly.norm, T, d.D, m->eps, l == 0, s), "mamba add + norm"));
+    MI_TRY(mamba_linear(ws.zx, d.ld, ws.u, d.D, T, d.D, ly.in_proj, d.width, MI_EPI_STORE, "in_proj gemv", "in_proj gemm", s));
+    const MambaScanArgs a = {ws.y, ws.zx, d.ld, ly.conv_w, ly.conv_b, ly.dt_bias, ly.A_log, ly.D, bt->conv_state[l], bt->ssm_state[l], B, L, d.H, d.G};
+    MI_TRY(hip_rc(launch_mamba_scan(a, s), L == 1 ? "mamba step" : "mamba chunk scan"));
+    MI_TRY(hip_rc(launch_mamba_gated_norm(ws.y, ws.y, ws.zx, d.ld, ly.gated_norm, T, d.I, d.G, m->eps, s), "mamba gated norm"));
+    MI_TRY(mamba_linear(ws.h, d.D, ws.y, d.I, T, d.I, ly.out_proj, d.D, MI_EPI_STORE, "out_proj gemv", "out_proj gemm", s));
+  }
+  if (!bt->logits) return MI_OK;
+  MI_TRY(hip_rc(launch_mamba_add_norm(ws.u, ws.res, ws.h, m->norm_f, T, d.D, m->eps, false, s), "mamba final add + norm"));
+  if (bt->last_only)  // row L - 1 of every sequence: a view of u with the row stride of a whole sequence
+    return mamba_linear(bt->logits, m->vocab_size, ws.u + (size_t)(L - 1) * d.D, L * d.D, B, d.D, m->lm_head, m->vocab_size, MI_EPI_LOGITS,
+                        "lm head gemv", "lm head gemm", s);
+  return mamba_linear(bt->logits, m->vocab_size, ws.u, d.D, T, d.D, m->lm_head, m->vocab_size, MI_EPI_LOGITS, "lm head gemv", "lm head gemm", s);
+}
+
+}  // extern "C"

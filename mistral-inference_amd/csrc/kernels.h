@@ -591,3 +591,23 @@ hipError_t launch_g_moe_accum(int dt, void* results, const void* y, const int32_
 hipError_t launch_g_add(int dt, void* out, const void* a, const void* b, size_t n, hipStream_t s);
 hipError_t launch_g_zero(int dt, void* p, size_t n, hipStream_t s);
 hipError_t launch_g_gelu(int dt, void* x, int ldx, int T, int N, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------------- Mamba2 mixer (mamba.hip)
+// The rule of include/mistral_hip.h "Mamba2".  N = 128, P = 64, d_conv = 4 are compiled in; I = 64 H, Cc = I + 256 G.
+constexpr int MAMBA_MAX_ROW = 8192;  // widest row (dim; I / G) the two row kernels keep in a wave's registers
+bool mamba_row_ok(int n);            // a multiple of 8 up to MAMBA_MAX_ROW
+struct MambaScanArgs {
+  void* y;                 // [B * L, I] bf16
+  const void* zxbcdt;      // [B * L, ld] bf16: z [I] | xBC [Cc] | dt [H]; ld a multiple of 8
+  int ld;
+  const void *conv_w, *conv_b;           // bf16 [Cc, 4], [Cc]
+  const float *dt_bias, *A_log, *Dskip;  // fp32 [H]
+  void* conv_state;        // bf16 [B, 3, Cc], updated in place (by a launch of its own behind the scan)
+  float* ssm_state;        // fp32 [B, H, 64, 128], updated in place
+  int B, L, H, G;
+};
+// L == 1: mamba_step_kernel; L >= 2: mamba_scan_chunk_kernel (chunks of 64 tokens on the bf16 MFMA); then the conv-state move
+hipError_t launch_mamba_scan(const MambaScanArgs& a, hipStream_t s);
+// first: the stack's first layer, residual = float(h) without reading it.  h == nullptr: no add, the residual stays as it is
+hipError_t launch_mamba_add_norm(void* out, float* residual, const void* h, const void* w, int T, int D, float eps, bool first, hipStream_t s);
+hipError_t launch_mamba_gated_norm(void* out, const void* y, const void* z, int ldz, const void* w, int T, int I, int G, float eps, hipStream_t s);

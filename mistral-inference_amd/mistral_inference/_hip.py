@@ -106,6 +106,22 @@ class MiLmHeadQuant(C.Structure):
 
 MI_LM_HEAD_SLICE_ROWS = 8192  # include/mistral_hip.h
 
+
+class MiMambaLayer(C.Structure):
+    """`mi_mamba_layer_t`: the device pointers of one Mamba2 layer (dt_bias, A_log, D: fp32)."""
+    _fields_ = [(n, _vp) for n in ("norm", "in_proj", "conv_w", "conv_b", "dt_bias", "A_log", "D", "gated_norm", "out_proj")]
+
+
+class MiMambaModel(C.Structure):
+    _fields_ = [("dim", C.c_int32), ("n_layers", C.c_int32), ("vocab_size", C.c_int32), ("n_groups", C.c_int32), ("eps", C.c_float),
+                ("embedding", _vp), ("norm_f", _vp), ("lm_head", _vp), ("layers", C.POINTER(MiMambaLayer))]
+
+
+class MiMambaBatch(C.Structure):
+    _fields_ = [("ids", _vp), ("B", C.c_int32), ("L", C.c_int32), ("conv_state", C.POINTER(_vp)), ("ssm_state", C.POINTER(_vp)),
+                ("workspace", _vp), ("workspace_bytes", C.c_size_t), ("logits", _vp), ("last_only", C.c_int32)]
+
+
 _lib: Optional[C.CDLL] = None
 
 _SIGS = {
@@ -213,6 +229,11 @@ _SIGS = {
     "mi_decode_engine_census": (C.c_int, [C.c_int]),
     "mi_decode_engine_reset": (C.c_int, [_vp, _vp]),
     "mi_decode_engine_status": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint32)]),
+    "mi_mamba_add_norm": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_float, _vp]),
+    "mi_mamba_scan": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "mi_mamba_gated_norm": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_float, _vp]),
+    "mi_workspace_bytes_mamba": (C.c_size_t, [C.POINTER(MiMambaModel), C.c_int, C.c_int]),
+    "mi_forward_mamba": (C.c_int, [C.POINTER(MiMambaModel), C.POINTER(MiMambaBatch), _vp]),
     "mi_rccl_unique_id": (C.c_int, [_vp]),
     "mi_rccl_init": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, _vp]),
     "mi_rccl_destroy": (C.c_int, [_vp]),
@@ -921,6 +942,41 @@ def moe_experts(x: torch.Tensor, expert_tab: torch.Tensor, n_experts: int, hidde
     check(L.mi_moe_grouped_gemm(dev_ptr(out), dev_ptr(residual), dev_ptr(xc), D, T, D, hidden_dim, n_experts, k,
                                 expert_tab.data_ptr(), dev_ptr(sel_idx, torch.int32), dev_ptr(sel_w, torch.float32),
                                 scratch.data_ptr(), need, st), "mi_moe_grouped_gemm")
+    return out
+
+
+def mamba_add_norm(residual: torch.Tensor, h: Optional[torch.Tensor], w: torch.Tensor, eps: float) -> torch.Tensor:
+    """Step 1 of the Mamba2 rule (include/mistral_hip.h): residual fp32 [T, D] += h in place; returns the normed bf16 rows."""
+    T, D = residual.shape
+    assert residual.is_contiguous() and (h is None or (h.shape == residual.shape and h.is_contiguous()))
+    out = torch.empty((T, D), dtype=torch.bfloat16, device=residual.device)
+    check(lib().mi_mamba_add_norm(dev_ptr(out), dev_ptr(residual, torch.float32), dev_ptr(h), dev_ptr(w), T, D, float(eps),
+                                  stream_ptr(residual.device)), "mi_mamba_add_norm")
+    return out
+
+
+def mamba_scan(zxbcdt: torch.Tensor, conv_w: torch.Tensor, conv_b: torch.Tensor, dt_bias: torch.Tensor, A_log: torch.Tensor,
+               D: torch.Tensor, conv_state: torch.Tensor, ssm_state: torch.Tensor, n_groups: int) -> torch.Tensor:
+    """Steps 3 and 4: zxbcdt bf16 [B, L, ld]; conv_state bf16 [B, 3, Cc] and ssm_state fp32 [B, H, 64, 128] are updated in place.
+    Returns y bf16 [B, L, 64 H]."""
+    B, L, ld = zxbcdt.shape
+    H = dt_bias.numel()
+    assert zxbcdt.is_contiguous() and conv_state.is_contiguous() and ssm_state.is_contiguous() and conv_w.is_contiguous()
+    y = torch.empty((B, L, 64 * H), dtype=torch.bfloat16, device=zxbcdt.device)
+    f32 = torch.float32
+    check(lib().mi_mamba_scan(dev_ptr(y), dev_ptr(zxbcdt), ld, dev_ptr(conv_w), dev_ptr(conv_b), dev_ptr(dt_bias, f32), dev_ptr(A_log, f32),
+                              dev_ptr(D, f32), dev_ptr(conv_state), dev_ptr(ssm_state, f32), B, L, H, int(n_groups),
+                              stream_ptr(zxbcdt.device)), "mi_mamba_scan")
+    return y
+
+
+def mamba_gated_norm(y: torch.Tensor, zxbcdt: torch.Tensor, w: torch.Tensor, n_groups: int, eps: float) -> torch.Tensor:
+    """Step 5: y bf16 [T, I], zxbcdt bf16 [T, ld] (z in its first I columns)."""
+    T, I = y.shape
+    assert y.is_contiguous() and zxbcdt.stride(1) == 1
+    out = torch.empty_like(y)
+    check(lib().mi_mamba_gated_norm(dev_ptr(out), dev_ptr(y), dev_ptr(zxbcdt), zxbcdt.stride(0), dev_ptr(w), T, I, int(n_groups), float(eps),
+                                    stream_ptr(y.device)), "mi_mamba_gated_norm")
     return out
 
 

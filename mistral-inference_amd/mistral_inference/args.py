@@ -113,6 +113,25 @@ class TransformerArgs(_FromDict):
         self.sliding_window = self.sliding_window if self.sliding_window is not None else self._sliding_window
 
 
+@dataclass
+class MambaArgs(_FromDict):
+    """params.json of a Mamba2 model (reference args.py:62-76).  The rest of the architecture is fixed by the reference's
+    MambaConfig / Mamba2 defaults (mamba.py): d_state 128, d_conv 4, expand 2, headdim 64, both eps 1e-5."""
+    dim: int
+    n_layers: int
+    vocab_size: int
+    n_groups: int
+    rms_norm: bool
+    residual_in_fp32: bool
+    fused_add_norm: bool        # (a choice of mamba_ssm kernels, not of arithmetic: read and ignored)
+    pad_vocab_size_multiple: int
+    tie_embeddings: bool
+    model_type: str = "mamba"
+
+    def __post_init__(self) -> None:
+        assert self.model_type == "mamba", self.model_type
+
+
 _NESTED = {
     ("TransformerArgs", "moe"): MoeArgs,
     ("TransformerArgs", "lora"): LoraArgs,

@@ -459,3 +459,48 @@ def sample_top_p(probs: torch.Tensor, p: float) -> torch.Tensor:
     sorted_probs = sorted_probs / sorted_probs.sum(dim=-1, keepdim=True)
     pick = torch.multinomial(sorted_probs, num_samples=1)
     return torch.gather(order, -1, pick)
+
+
+@torch.inference_mode()
+def generate_mamba(encoded_prompts: List[List[int]], model, *, max_tokens: int, temperature: float, chunk_size: Optional[int] = None,
+                   eos_id: Optional[int] = None) -> Tuple[List[List[int]], List[List[float]]]:
+    """Reference generate.py:11-40 for a mamba.Mamba model.  The prompts must have equal length (the reference stacks them into
+    one tensor).  The prompt runs through a MambaCache in chunks of `chunk_size` tokens (None: in one call), then one step per
+    token.  temperature == 0: the first argmax (mi_greedy_sample); above: the project's nucleus sampler at top-p 0.8.
+    Generation stops early once every sequence has emitted `eos_id`.  The second return value holds the RAW LOGIT of each chosen
+    token - what the reference's `output.scores` holds - not a log-probability."""
+    from . import _hip
+    from .mamba import MambaCache
+    if not encoded_prompts:
+        return [], []
+    L = len(encoded_prompts[0])
+    if L == 0 or any(len(p) != L for p in encoded_prompts):
+        raise ValueError(f"generate_mamba: prompts must be non-empty and of equal length (got lengths {[len(p) for p in encoded_prompts]})")
+    if chunk_size is not None and chunk_size <= 0:
+        raise ValueError(f"generate_mamba: chunk_size {chunk_size}")
+    B = len(encoded_prompts)
+    ids = torch.tensor(encoded_prompts, dtype=torch.long, device=model.device)
+    cache = MambaCache(model, B)
+    step = L if chunk_size is None else chunk_size
+    for s in range(0, L, step):
+        logits = model.forward(ids[:, s:s + step], cache=cache, last_only=True)
+    tokens: List[torch.Tensor] = []
+    scores: List[torch.Tensor] = []
+    done = torch.zeros(B, dtype=torch.bool, device=model.device)
+    seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if temperature > 0 else 0  # (one seed per generation, from torch's generator)
+    for i in range(max_tokens):
+        if temperature > 0:
+            tok, _ = _hip.sample_top_p(logits, temperature, 0.8, seed=seed, offset=i)
+        else:
+            tok, _ = _hip.greedy_sample(logits)
+        tokens.append(tok)
+        scores.append(logits.gather(1, tok[:, None])[:, 0])
+        if eos_id is not None:
+            done |= tok == eos_id
+            if bool(done.all()):
+                break
+        if i + 1 < max_tokens:
+            logits = model.forward(tok[:, None], cache=cache, last_only=True)
+    if not tokens:
+        return [[] for _ in range(B)], [[] for _ in range(B)]
+    return torch.stack(tokens, 1).tolist(), torch.stack(scores, 1).tolist()

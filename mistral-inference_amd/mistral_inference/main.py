@@ -16,7 +16,8 @@ from typing import List, Optional, Type, Union
 import torch
 
 from .cache import kv_dtype_arg
-from .generate import SpeculativeArgs, generate  # noqa: F401  (the reference's tests import generate from main)
+from .generate import SpeculativeArgs, generate, generate_mamba  # noqa: F401  (the reference's tests import generate from main)
+from .mamba import Mamba
 from .transformer import Transformer
 
 
@@ -76,12 +77,26 @@ def load_tokenizer(model_path: Path):
     return tok
 
 
-def get_model_cls(model_path: str) -> Type[Transformer]:
+def get_model_cls(model_path: str) -> Union[Type[Mamba], Type[Transformer]]:
     with open(Path(model_path) / "params.json", "r") as f:
         kind = json.load(f).get("model_type", "transformer")
-    if kind != "transformer":
-        raise NotImplementedError(f"model_type {kind!r}: only the transformer family is on the hot path")
-    return Transformer
+    if kind not in ("transformer", "mamba"):
+        raise NotImplementedError(f"model_type {kind!r}: the model classes are 'transformer' and 'mamba'")
+    return Mamba if kind == "mamba" else Transformer
+
+
+def refuse_transformer_flags(**flags) -> None:
+    """A Mamba model takes none of the transformer-only options of the tools: each one given is refused by name."""
+    given = [k for k, v in flags.items() if v]
+    if given:
+        raise NotImplementedError(f"Mamba models do not take {', '.join(given)}: LoRA, quantisation, K/V cache dtypes, speculative "
+                                  "decoding and images are transformer-only")
+
+
+def pad_and_convert_to_tensor(list_of_lists: List[List[int]], pad_id: int) -> List[List[int]]:
+    """Left-pads every prompt to the longest one (reference main.py:67-74: generate_mamba takes prompts of equal length)."""
+    n = max(len(p) for p in list_of_lists)
+    return [[pad_id] * (n - len(p)) + p for p in list_of_lists]
 
 
 def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7, num_pipeline_ranks: int = 1,
@@ -105,10 +120,16 @@ def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7,
     should_print = _should_print()
     mistral_tokenizer = load_tokenizer(Path(model_path))
     tokenizer = mistral_tokenizer.instruct_tokenizer.tokenizer
-    model = get_model_cls(model_path).from_folder(Path(model_path), max_batch_size=3,
-                                                  num_pipeline_ranks=num_pipeline_ranks, dtype=torch.bfloat16, quantize=quantize,
-                                                  prefill_fp8=bool(prefill_fp8), prefill_w4a8=bool(prefill_w4a8),
-                                                  quantize_lm_head=bool(quantize_lm_head))
+    model_cls = get_model_cls(model_path)
+    if model_cls is Mamba:
+        refuse_transformer_flags(lora_path=lora_path, quantize=quantize, kv_dtype=kv_dtype, speculative=speculative, prefill_fp8=prefill_fp8,
+                                 prefill_w4a8=prefill_w4a8, quantize_lm_head=quantize_lm_head)
+        model = Mamba.from_folder(Path(model_path), max_batch_size=3, num_pipeline_ranks=num_pipeline_ranks, dtype=torch.bfloat16)
+    else:
+        model = model_cls.from_folder(Path(model_path), max_batch_size=3,
+                                      num_pipeline_ranks=num_pipeline_ranks, dtype=torch.bfloat16, quantize=quantize,
+                                      prefill_fp8=bool(prefill_fp8), prefill_w4a8=bool(prefill_w4a8),
+                                      quantize_lm_head=bool(quantize_lm_head))
     if lora_path is not None:  # reference main.py:131-132
         model.load_lora(Path(lora_path))
     messages: List = []
@@ -128,8 +149,11 @@ def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7,
             n = share_prompt_length(len(tokens))
             if not should_print:
                 tokens = n * [0]
-        generated, _ = generate([tokens], model, max_tokens=max_tokens, temperature=temperature,
-                                eos_id=tokenizer.eos_id, kv_dtype=kv, speculative=spec)
+        if isinstance(model, Mamba):  # (reference main.py:181-190)
+            generated, _ = generate_mamba([tokens], model, max_tokens=max_tokens, temperature=temperature, eos_id=tokenizer.eos_id)
+        else:
+            generated, _ = generate([tokens], model, max_tokens=max_tokens, temperature=temperature,
+                                    eos_id=tokenizer.eos_id, kv_dtype=kv, speculative=spec)
         answer = tokenizer.decode(generated[0])
         if should_print:
             print(answer)
@@ -149,16 +173,26 @@ def demo(model_path: str, max_tokens: int = 35, temperature: float = 0, lora_pat
         spec = dataclasses.replace(spec, sample=True)
     num_pipeline_ranks = init_pipeline()
     should_print = _should_print()
-    model = get_model_cls(model_path).from_folder(Path(model_path), max_batch_size=3,
-                                                  num_pipeline_ranks=num_pipeline_ranks, dtype=torch.bfloat16, quantize=quantize,
-                                                  prefill_fp8=bool(prefill_fp8), prefill_w4a8=bool(prefill_w4a8),
-                                                  quantize_lm_head=bool(quantize_lm_head))
+    model_cls = get_model_cls(model_path)
+    if model_cls is Mamba:
+        refuse_transformer_flags(lora_path=lora_path, quantize=quantize, kv_dtype=kv_dtype, speculative=speculative, prefill_fp8=prefill_fp8,
+                                 prefill_w4a8=prefill_w4a8, quantize_lm_head=quantize_lm_head)
+        model = Mamba.from_folder(Path(model_path), max_batch_size=3, num_pipeline_ranks=num_pipeline_ranks, dtype=torch.bfloat16)
+    else:
+        model = model_cls.from_folder(Path(model_path), max_batch_size=3,
+                                      num_pipeline_ranks=num_pipeline_ranks, dtype=torch.bfloat16, quantize=quantize,
+                                      prefill_fp8=bool(prefill_fp8), prefill_w4a8=bool(prefill_w4a8),
+                                      quantize_lm_head=bool(quantize_lm_head))
     if lora_path is not None:  # reference main.py:224-225
         model.load_lora(Path(lora_path))
-    tokenizer = load_tokenizer(Path(model_path)).instruct_tokenizer.tokenizer
+    mistral_tokenizer = load_tokenizer(Path(model_path))
+    tokenizer = mistral_tokenizer.instruct_tokenizer.tokenizer
     prompts = ["This is a test", "This is another great test", "This is a third test, mistral AI is very good at testing. "]
     encoded = [tokenizer.encode(p, bos=True, eos=False) for p in prompts]
-    if spec is None:
+    if isinstance(model, Mamba):  # (reference main.py:236-246: left-padded with BOS to one length; batched results may differ from single ones)
+        encoded = pad_and_convert_to_tensor(encoded, mistral_tokenizer.instruct_tokenizer.BOS)
+        generated, logprobs = generate_mamba(encoded, model, max_tokens=max_tokens, temperature=temperature, eos_id=tokenizer.eos_id)
+    elif spec is None:
         generated, logprobs = generate(encoded, model, max_tokens=max_tokens, temperature=temperature,
                                        eos_id=tokenizer.eos_id, kv_dtype=kv)
     else:
