@@ -3,7 +3,8 @@
  *
  * NOT part of the drop-in boundary (include/mistral_hip.h): nothing a caller of the hot path needs, no reference
  * counterpart.  Used by scripts/engine_trace.py (phase timeline), the A/B scripts (loader knobs) and
- * tests/test_gpu_greedy.py (residency-gate sabotage).  Results of mi_forward never depend on any of these.
+ * tests/test_gpu_greedy.py (residency-gate sabotage); one test leaf of the generic-storage linear
+ * (tests/test_gpu_generic_linear_structured.py).  Results of mi_forward never depend on any of these.
  */
 #ifndef MISTRAL_HIP_DEBUG_H
 #define MISTRAL_HIP_DEBUG_H
@@ -56,6 +57,16 @@ int mi_debug_set_prefill_kernels(int attn_waves, int gemm_tail);
 /* The row pairs per unit that the MXFP4 GEMV launcher picks at one token for a matrix of `n_pairs` row pairs on a device of
  * `n_cus` compute units (csrc/gemv_w4.hip; MI_GEMV_W4_RP unset): tests size their matrices to both sides of its threshold. */
 int mi_debug_gemv_w4_row_pairs(int n_pairs, int n_cus);
+/* Test leaf of the generic-storage linear (csrc/generic.hip launch_g_linear; tests/test_gpu_generic_linear_structured.py): ONE
+ * launch with the forms that mi_linear_generic, one launch per matrix, cannot reach.  Arguments as mi_linear_generic, plus:
+ * w[0..2] side by side in one launch (output columns [0, n_rows[0]) | [.., + n_rows[1]) | the rest); MI_EPI_SWIGLU with w[0] = W1,
+ * w[1] = W3 of n_rows[0] rows each (out [M, n_rows[0]]); norm_w [K] != NULL: the contraction runs on round(round(x / rms(x)) *
+ * norm_w) with `eps`; residual rows `ldr` apart (MI_EPI_RESIDUAL); active [M] int32 != NULL: the MoE row mask (a tile / launch
+ * none of whose rows is active writes nothing).  dtype: enum mi_dtype.  MI_ERR_UNSUPPORTED where no kernel takes a fused form
+ * (several matrices, norm_w or SwiGLU beyond 8 rows - fp16 from 256 rows excepted - or K, ldx not multiples of 8). */
+int mi_debug_linear_generic_fused(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
+                                  int epilogue, const void* residual, int ldr, const void* norm_w, float eps, const int32_t* active,
+                                  int dtype, mi_stream_t stream);
 
 #ifdef __cplusplus
 }

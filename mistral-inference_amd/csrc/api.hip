@@ -1890,6 +1890,45 @@ int mi_linear_generic(void* out, int ldo, const void* x, int ldx, int M, int K, 
   return MI_OK;
 }
 
+/* Test leaf (include/mistral_hip_debug.h): ONE launch_g_linear call with the forms mi_linear_generic cannot reach - the three
+ * matrices side by side, the fused RMSNorm prologue, the fused SwiGLU (w[0] = W1, w[1] = W3), a residual stride of its own and
+ * the MoE row mask - after the same argument checks. */
+int mi_debug_linear_generic_fused(void* out, int ldo, const void* x, int ldx, int M, int K, const void* const w[3], const int n_rows[3],
+                                  int epilogue, const void* residual, int ldr, const void* norm_w, float eps, const int32_t* active,
+                                  int dtype, mi_stream_t stream) {
+  MI_TRY(check_dt(dtype, "mi_debug_linear_generic_fused"));
+  if (!out || !x || !w || !n_rows || !w[0] || M <= 0 || K <= 0) return fail(MI_ERR_ARG, "mi_debug_linear_generic_fused");
+  GLinearArgs g;
+  memset(&g, 0, sizeof(g));
+  switch (epilogue) {
+    case MI_EPI_STORE: g.epi = G_EPI_STORE; break;
+    case MI_EPI_RESIDUAL: g.epi = G_EPI_RESIDUAL; break;
+    case MI_EPI_LOGITS: g.epi = G_EPI_LOGITS; break;
+    case MI_EPI_SWIGLU: g.epi = G_EPI_SWIGLU; break;
+    default: return fail(MI_ERR_ARG, "mi_debug_linear_generic_fused: epilogue %d", epilogue);
+  }
+  if (g.epi == G_EPI_RESIDUAL && !residual) return fail(MI_ERR_ARG, "mi_debug_linear_generic_fused: residual");
+  if (w[2] && !w[1]) return fail(MI_ERR_ARG, "mi_debug_linear_generic_fused: w[2] without w[1]");
+  int n_w = 0, cols = 0;
+  for (; n_w < 3 && w[n_w]; ++n_w) {
+    if (n_rows[n_w] <= 0) return fail(MI_ERR_ARG, "mi_debug_linear_generic_fused: n_rows[%d]", n_w);
+    cols += n_rows[n_w];
+  }
+  if (g.epi == G_EPI_SWIGLU) {
+    if (n_w != 2 || n_rows[1] != n_rows[0]) return fail(MI_ERR_ARG, "mi_debug_linear_generic_fused: SwiGLU takes W1 and W3 of equal rows");
+    cols = n_rows[0];
+  }
+  g.x = x; g.ldx = ldx; g.w = w[0]; g.w1 = w[1]; g.w2 = n_w == 3 ? w[2] : nullptr;
+  g.n0 = g.epi == G_EPI_SWIGLU ? 0 : n_rows[0]; g.n1 = g.epi == G_EPI_SWIGLU || n_w < 2 ? 0 : n_rows[0] + n_rows[1];
+  g.norm_w = norm_w; g.eps = norm_w ? eps : 0.f;
+  g.out = out; g.ldo = ldo; g.residual = residual; g.ldr = ldr;
+  g.M = M; g.N = cols; g.K = K; g.active = active;
+  const bool fused = g.w1 || g.norm_w || g.epi == G_EPI_SWIGLU;
+  if (fused && !g_linear_fused_ok(dtype, g))
+    return fail(MI_ERR_UNSUPPORTED, "mi_debug_linear_generic_fused: no kernel takes this fused form at M = %d, K = %d, ldx = %d", M, K, ldx);
+  return hip_rc(launch_g_linear(dtype, g, (hipStream_t)stream), "linear (fused forms)");
+}
+
 /* rope.py:13-23 in place on the first n_rot_cols columns (heads of head_dim): pair i of a head turns by rope_cs[tok_pos[t], i] */
 int mi_rope_inplace_generic(void* qkv, int ld, int T, int n_rot_cols, int head_dim, const float* rope_cs, const int32_t* tok_pos,
                             int dtype, mi_stream_t stream) {

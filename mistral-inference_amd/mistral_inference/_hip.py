@@ -252,6 +252,8 @@ _SIGS = {
     "mi_debug_engine_route": (C.c_int, [C.c_int] * 12 + [C.c_char_p, C.c_size_t]),
     "mi_debug_set_prefill_kernels": (C.c_int, [C.c_int, C.c_int]),
     "mi_debug_gemv_w4_row_pairs": (C.c_int, [C.c_int, C.c_int]),
+    "mi_debug_linear_generic_fused": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp), C.POINTER(C.c_int), C.c_int,
+                                                _vp, C.c_int, _vp, C.c_float, _vp, C.c_int, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -1020,6 +1022,24 @@ def debug_engine_sabotage(workspace: torch.Tensor, launches: int) -> None:
 def debug_set_prefill_kernels(attn_waves: int = -1, gemm_tail: int = -1) -> None:
     """Same-process A/B of the prefill kernels' alternative forms (include/mistral_hip_debug.h; negative = keep)."""
     check(lib().mi_debug_set_prefill_kernels(attn_waves, gemm_tail), "mi_debug_set_prefill_kernels")
+
+
+def debug_linear_generic_fused(x: torch.Tensor, weights: Sequence[torch.Tensor], epilogue: int, out: torch.Tensor,
+                               residual: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0,
+                               active: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Test leaf: ONE launch of the generic-storage linear (csrc/generic.hip) in x's dtype, bf16 included, with its fused forms
+    (include/mistral_hip_debug.h).  x, out and residual may be row-strided views; SWIGLU: weights = (W1, W3)."""
+    dt = x.dtype
+    M, K = x.shape
+    assert 1 <= len(weights) <= 3 and all(w.shape[1] == K and w.is_contiguous() for w in weights)
+    wp = (_vp * 3)(*[dev_ptr(w, dt) for w in weights], *([None] * (3 - len(weights))))
+    nr = (C.c_int * 3)(*[w.shape[0] for w in weights], *([0] * (3 - len(weights))))
+    odt = torch.float32 if epilogue == EPI_LOGITS else dt
+    check(lib().mi_debug_linear_generic_fused(dev_ptr(out, odt), out.stride(0), dev_ptr(x, dt), x.stride(0), M, K, wp, nr, epilogue,
+                                              dev_ptr(residual, dt), residual.stride(0) if residual is not None else 0,
+                                              dev_ptr(norm_w, dt), float(eps), dev_ptr(active, torch.int32), _generic_code(dt),
+                                              stream_ptr(x.device)), "mi_debug_linear_generic_fused")
+    return out
 
 
 def decode_engine_reset(workspace: torch.Tensor) -> None:
