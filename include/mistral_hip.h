@@ -185,7 +185,10 @@ int mi_attn_decode(void* out, const void* q, int ldq, const void* cache_k, const
  * causal == 0 is the cache=None quirk (transformer_layers.py:165): one segment, no mask - also what one image of the
  * vision tower's block-diagonal mask is (vision_encoder.py:96-99).
  * softmax_scale <= 0 selects head_dim^-1/2 (the xformers default the reference relies on, transformer_layers.py:48,88);
- * the vision tower runs its 64-wide heads zero-padded to 128 and passes 64^-1/2.
+ * the vision tower passes 64^-1/2 by value.
+ * head_dim is 128, or 64 in ONE form - the vision tower's: causal == 0, cache_k == cache_v == NULL, B == 1,
+ * n_kv_heads == n_heads, ld >= 3 * n_heads * 64 (csrc/attn_prefill64.hip reads q | k | v of max_q_len rows as they are; W,
+ * q_start and kv_before are not read).  Every other head_dim 64 call and every other width: MI_ERR_SHAPE.
  * out: [T, H*Dh]. */
 int mi_attn_prefill(void* out, const void* qkv, int ld, const void* cache_k, const void* cache_v, int W, int B,
                     int max_q_len, int n_heads, int n_kv_heads, int head_dim, const int32_t* q_start,

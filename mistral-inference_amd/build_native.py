@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "lib", "libmistral_hip.so")
-SOURCES = ["api.hip", "gemv.hip", "gemm.hip", "gemm256.hip", "attn_decode.hip", "attn_prefill.hip", "attn_verify.hip", "elementwise.hip",
+SOURCES = ["api.hip", "gemv.hip", "gemm.hip", "gemm256.hip", "attn_decode.hip", "attn_prefill.hip", "attn_prefill64.hip", "attn_verify.hip", "elementwise.hip",
            "decode_engine.hip", "decode_engine_host.hip", "sampling.hip", "rccl_api.hip", "generic.hip", "lora.hip", "gemv_w8.hip", "gemv_w4.hip", "gemm256_w8a8.hip",
            "gemm256_w4a8.hip", "mamba.hip"]
 # (this file is a dependency of every object: a change of flags must rebuild them - round 6: decode_engine_next.o was once shipped
@@ -27,7 +27,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # (decode_engine.hip holds the kernels only; the engine's host side, decode_engine_host.hip, is compiled once with the plain FLAGS.)
 PER_FILE_FLAGS = {"decode_engine.hip": os.environ.get("MI_ENGINE_FLAGS", "-mllvm -amdgpu-sched-strategy=max-memory-clause").split(),
                   # (new sources are compiled without the packed fp32 VALU forms: every product of mamba.hip is a plain fp32 operation)
-                  "mamba.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+                  "mamba.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+                  "attn_prefill64.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 # Second compile of the engine source under other entry-point names (csrc/decode_engine.hip, ENG_WIDE): the shapes the shipped

@@ -1092,12 +1092,20 @@ int mi_attn_prefill(void* out, const void* qkv, int ld, const void* cache_k, con
   if (causal && (!q_start || !kv_before)) return fail(MI_ERR_ARG, "mi_attn_prefill: metadata");
   if (kv_e4m3(kv_layout))
     return fail(MI_ERR_UNSUPPORTED, "mi_attn_prefill: rings of e4m3 bytes (MI_KV_E4M3) are not read here; mi_kv_dequant them into bf16 rings first");
-  if (head_dim != 128) return fail(MI_ERR_SHAPE, "head_dim must be 128");
-  // the kernel forms 32-bit element offsets inside one ring (W * kv_dim) and inside the activation matrix (rows * ld)
+  if (head_dim != 128 && head_dim != 64) return fail(MI_ERR_SHAPE, "mi_attn_prefill: head_dim must be 128, or 64 in the cache-less non-causal form");
+  // 64-wide heads (the vision tower's): attn_prefill64.hip, which has one form - no mask, no ring, one sequence, n_heads == n_kv_heads
+  if (head_dim == 64 && (causal || cache_k || cache_v || B != 1))
+    return fail(MI_ERR_SHAPE, "mi_attn_prefill: head_dim 64: the cache-less non-causal form only (causal = 0, no rings, B = 1)");
+  if (head_dim == 64 && (n_heads <= 0 || n_heads != n_kv_heads))
+    return fail(MI_ERR_SHAPE, "mi_attn_prefill: head_dim 64: n_kv_heads must equal n_heads");
+  if (head_dim == 64 && (ld < 3 * n_heads * 64 || ld % 8))
+    return fail(MI_ERR_SHAPE, "mi_attn_prefill: head_dim 64: ld must hold q | k | v (3 * n_heads * 64 columns) in whole 16-byte pieces");
+  // the kernels form 32-bit element offsets inside one ring (W * kv_dim) and inside the activation matrix (rows * ld)
   if ((size_t)W * n_kv_heads * head_dim >= (1ull << 31) || (size_t)B * max_q_len * (size_t)ld >= (1ull << 31))
     return fail(MI_ERR_UNSUPPORTED, "mi_attn_prefill: ring or activation matrix larger than 2^31 elements");
   const AttnPrefillArgs a = attn_prefill_args(out, qkv, ld, cache_k, cache_v, kv_layout, W, B, max_q_len, n_heads, n_kv_heads, head_dim,
                                               q_start, kv_before, causal, softmax_scale);
+  if (head_dim == 64) return hip_rc(launch_attn_prefill64(a, (hipStream_t)stream), "attn_prefill64");
   return hip_rc(launch_attn_prefill(a, (hipStream_t)stream), "attn_prefill");
 }
 

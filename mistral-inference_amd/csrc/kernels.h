@@ -223,6 +223,8 @@ struct AttnPrefillArgs {
 hipError_t launch_attn_prefill(const AttnPrefillArgs& a, hipStream_t s);
 void attn_prefill_set_mode(int waves);  // mi_debug_set_prefill_kernels (negative: keep)
 hipError_t launch_attn_prefill_f16(const AttnPrefillArgs& a, hipStream_t s);  // attn_prefill.hip compiled with -DATTN_F16=1
+// attn_prefill64.hip: Dh == 64, H == Hkv, causal == 0, no rings, one sequence of max_q_len rows (W, B, q_start, kv_before unread)
+hipError_t launch_attn_prefill64(const AttnPrefillArgs& a, hipStream_t s);
 
 // Verify step (attn_verify.hip): sequence b brings rows q_start[b] .. q_start[b + 1] (at most 8, at positions kv_before[b] + i)
 // that are NOT in its ring; mask of the prefill attention, split geometry of the decode attention.

@@ -2,15 +2,14 @@
 
 Module and parameter names are the reference's, so `vision_encoder.*`, `vision_language_adapter.*`, `patch_merger.*` and
 `pre_mm_projector_norm.*` checkpoint keys load unchanged.  All arithmetic runs in libmistral_hip (GEMMs, RMSNorm, RoPE,
-attention, GELU); torch only reshapes / gathers / pads (im2col of the patch convolution, head padding, the patch-merger
+attention, GELU); torch only reshapes / gathers / pads (im2col of the patch convolution, the patch-merger
 permutation, the final row scatter).
 
 How the tower maps onto the text path's kernels:
   * patch convolution (stride = kernel = patch) = one GEMM over im2col rows [n_patches, C*P*P];
-  * the blocks are the text TransformerBlock with n_kv_heads = n_heads and 64-wide heads.  The attention kernels are
-    built for 128-wide heads, so q/k/v are zero-padded to 128 per head (dot products and P.V are unchanged by zero
-    columns), the softmax scale is passed explicitly (64^-1/2), and the 2-D RoPE table gets identity entries (cos 1,
-    sin 0) for the padded pairs; rotary position = row * max_patches_per_side + column;
+  * the blocks are the text TransformerBlock with n_kv_heads = n_heads and 64-wide heads.  bf16 towers run them on the
+    64-wide attention kernel (csrc/attn_prefill64.hip: non-causal, cache-less, reads the fused q|k|v rows as they are);
+    128-wide heads take the text path's prefill kernel; rotary position = row * max_patches_per_side + column;
   * the reference builds a per-image BlockDiagonalMask but TransformerBlock.forward never hands it to the attention
     (transformer_layers.py:165), so what runs - and what is reproduced here - is ONE unmasked attention over the patches
     of all images (`causal=False` form of mi_attn_prefill);
@@ -81,7 +80,7 @@ class VisionTransformer(nn.Module):
         self.transformer = VisionTransformerBlocks(args)
         head_dim = args.hidden_size // args.num_attention_heads
         assert head_dim % 2 == 0, "ROPE requires even head_dim"
-        self._head_dim = head_dim  # bf16: the MFMA attention takes 128 (64 zero-padded); fp16 / fp32: any head dim <= 256
+        self._head_dim = head_dim  # bf16: the MFMA attention kernels take 64 or 128; fp16 / fp32: any head dim <= 256
         self._rope_cs: Optional[torch.Tensor] = None
         self._conv_w: Optional[torch.Tensor] = None  # K-padded image of patch_conv.weight (rebuilt after a reload)
 
@@ -100,8 +99,8 @@ class VisionTransformer(nn.Module):
         return precompute_freqs_cis_2d(a.hidden_size // a.num_attention_heads, side, side, a.rope_theta).to(self.device)
 
     def _rope_table(self, padded: bool = True) -> torch.Tensor:
-        """fp32 [side*side, 64, 2]: (cos, sin) of the head's real pairs, identity for the zero-padded ones (bf16 kernels);
-        `padded=False`: [side*side, head_dim/2, 2], the real pairs only (generic kernels: heads keep their own width)."""
+        """fp32 [side*side, 64, 2]: (cos, sin) of the head's real pairs, identity beyond them (the 128-wide bf16 form);
+        `padded=False`: [side*side, head_dim/2, 2], the real pairs only (64-wide bf16 heads and the generic kernels)."""
         key = "p" if padded else "r"
         if self._rope_cs is None or self._rope_cs[0] != (key, self.device):
             side = self.max_patches_per_side
@@ -144,25 +143,15 @@ class VisionTransformer(nn.Module):
         pos_id = (pos[:, 0] * self.max_patches_per_side + pos[:, 1]).to(device=dev, dtype=torch.int32)
         generic = x.dtype != torch.bfloat16   # fp16 / fp32 storage: csrc/generic.hip takes the heads as they are
         if not generic and dh not in (64, 128):
-            raise NotImplementedError(f"vision head_dim {dh}: the bf16 attention kernels take 128 (or 64, zero-padded)")
-        cs = self._rope_table(padded=not generic)
+            raise NotImplementedError(f"vision head_dim {dh}: the bf16 attention kernels take 128 or 64")
+        cs = self._rope_table(padded=not generic and dh == 128)
         for blk in self.transformer.layers:
             at = blk.attention
             xn = _hip.rmsnorm(x, blk.attention_norm.weight, 1e-5)
             qkv = _hip.linear(xn, (at.wq.weight, at.wk.weight, at.wv.weight), _hip.EPI_STORE)  # [T, 3*H*dh]
-            if generic:
-                _hip.rope_inplace(qkv, H, H, dh, cs, pos_id)
-                att = _hip.attn_prefill(qkv, H, H, dh, None, None, T, None, None, 1, T, causal=False, softmax_scale=dh ** -0.5)
-            else:
-                if dh != 128:  # zero-pad every head to the kernels' 128 columns
-                    pad = torch.zeros((T, 3 * H, 128), dtype=qkv.dtype, device=dev)
-                    pad[:, :, :dh] = qkv.view(T, 3 * H, dh)
-                    qkv = pad.view(T, 3 * H * 128)
-                _hip.rope_inplace(qkv, H, H, 128, cs, pos_id)
-                att = _hip.attn_prefill(qkv, H, H, 128, None, None, T, None, None, 1, T, causal=False,
-                                        softmax_scale=dh ** -0.5)
-                if dh != 128:
-                    att = att.view(T, H, 128)[:, :, :dh].reshape(T, H * dh).contiguous()
+            # the heads as they are, in every storage type: generic.hip (fp16 / fp32), attn_prefill64.hip / attn_prefill.hip (bf16)
+            _hip.rope_inplace(qkv, H, H, dh, cs, pos_id)
+            att = _hip.attn_prefill(qkv, H, H, dh, None, None, T, None, None, 1, T, causal=False, softmax_scale=dh ** -0.5)
             x = _hip.linear(att, (at.wo.weight,), _hip.EPI_RESIDUAL, residual=x)
             ff = blk.feed_forward
             xn = _hip.rmsnorm(x, blk.ffn_norm.weight, 1e-5)
