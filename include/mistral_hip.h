@@ -690,6 +690,54 @@ size_t mi_workspace_bytes_q(const mi_model_t* model, const mi_w8_model_t* w8, co
 int mi_forward_q(const mi_model_t* model, const mi_w8_model_t* w8, const mi_w4_model_t* w4, const mi_lm_head_quant_t* head,
                  const mi_batch_t* batch, const mi_verify_out_t* verify_out, int a8, mi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * FP8 (e4m3) EXPERT weights of a MoE model: opt-in, additive to ABI v9 like the blocks above (the presence of these symbols is the
+ * feature test; mi_forward_w8 / _w4 / _q keep refusing num_experts > 0 with their present messages).  The format is the dense
+ * MI_W8_FP8_E4M3 one: an expert linear of moe.py:19 / transformer_layers.py:101-103 stands on the real-valued weight
+ * W[r, k] = scale[r] * e4m3(w[r, k]), w bytes [out, in], scale fp32 [out].  The router gate (moe.py:20), norms, embeddings and (unless
+ * a head struct is given) the LM head stay bf16.  Tables: expert_w_dev is the DEVICE array [E][3] of (w1, w2, w3) byte pointers,
+ * expert_scale_dev the DEVICE array [E][3] of their fp32 row-scale pointers ([F], [D], [F]).
+ *   T <= 8 (moe.py:28-32 + transformer_layers.py:168, two launches as mi_moe_experts_decode):
+ *            a = acc1 * scale1[r], b = acc3 * scale3[r] in fp32 enter the SwiGLU exactly where acc1, acc3 enter it there
+ *            (hid = bf16(bf16(silu(bf16 a)) * bf16 b), the FFN RMSNorm fused); then per token, experts in ascending id,
+ *            y = bf16(scale2[r] * acc) - the scale meets the fp32 sum before the first bf16 rounding -
+ *            R = bf16(R + bf16(w * y)) from zero, out = bf16(residual + R)   (csrc/gemv_w8.hip, csrc/gemv.hip moe_w2_w8_kernel);
+ *   T  > 8:  per projection family (W1|W3, then W2) ONE launch writes W' = bf16(scale[r] * e4m3(w[r, k])) of ALL experts into a
+ *            scratch and a device pointer table [E][3] over the images; mi_moe_grouped_gemm's token-grouped GEMMs run on that
+ *            table unchanged.  Scratch of the images: E * 2 * F * D * 2 bytes (the larger family; W2's images reuse it).
+ * With power-of-two scales W' is exact and both forms are the bf16 MoE layer on the dequantised weights up to fp32 summation order.
+ * D and F multiples of 16 (MI_ERR_SHAPE), top_k in {1, 2, 4}, top_k * F * 2 <= 65536 (MI_ERR_SHAPE), NULL tables (MI_ERR_ARG): all
+ * checked before any launch.  MXFP4 experts are not implemented.  Nothing is claimed about model quality.
+ * ---------------------------------------------------------------------------------------------- */
+/* mi_moe_experts_decode on FP8 experts (T <= 8). */
+int mi_moe_experts_decode_w8(void* out, const void* residual, const void* x, int ldx, int T, int D, int F,
+                             const void* const* expert_w_dev, const float* const* expert_scale_dev, const int32_t* sel_idx,
+                             const float* sel_w, int top_k, const void* norm_w, float eps, void* hidden_scratch, mi_stream_t stream);
+/* mi_moe_grouped_gemm on FP8 experts (any T): its scratch, then the pointer table and the images. */
+size_t mi_moe_grouped_gemm_w8_scratch_bytes(int T, int D, int F, int E, int top_k);
+int mi_moe_grouped_gemm_w8(void* out, const void* residual, const void* x, int ldx, int T, int D, int F, int E, int top_k,
+                           const void* const* expert_w_dev, const float* const* expert_scale_dev, const int32_t* sel_idx,
+                           const float* sel_w, void* scratch, size_t scratch_bytes, mi_stream_t stream);
+
+/* The experts' scales of one MoE layer, beside an mi_layer_t whose expert_w_dev / expert_w_host tables then point to e4m3 bytes. */
+typedef struct mi_moe_w8_layer {
+  const float* const* expert_scale_dev; /* DEVICE array [E][3] of fp32 row-scale pointers (w1 [F], w2 [D], w3 [F]) */
+} mi_moe_w8_layer_t;
+
+/* mi_forward (Transformer.forward_partial, transformer.py:163-219, + the LM head, :229-242) on a MoE model whose attention linears
+ * are quantised as `w8` describes (its w1 / w2 / w3 entries are not read) and whose experts as `experts` [n_layers] (host) describes:
+ * the shared layer loop with the attention linears on mi_forward_w8's routes and the MoE branch on the two forms above.  head: as
+ * mi_forward_q (NULL: a bf16 head).  FP8 K/V rings (MI_KV_E4M3) as on any launch-path model; the persistent engine declines.
+ * Refused by name, before any launch (MI_ERR_UNSUPPORTED): w8->format MI_W4_MXFP4 (MXFP4 experts), lora_rank > 0 (un-merged LoRA),
+ * a8 != 0 (the FP8-activation prefill GEMMs: there is no token-grouped W8A8 kernel), verify_out != NULL (a verify step); a dense
+ * model, a NULL w8 or experts: MI_ERR_ARG.  Workspace: mi_workspace_bytes_moe_w8; at T > 8 it is mi_workspace_bytes_q's figure plus
+ * the pointer table and the images (E * 2 * F * D * 2 bytes), behind everything else, for such a model at such a T only. */
+size_t mi_workspace_bytes_moe_w8(const mi_model_t* model, const mi_w8_model_t* w8, const mi_moe_w8_layer_t* experts,
+                                 const mi_lm_head_quant_t* head, int T, int B, int max_cache_size, int kv_layout);
+int mi_forward_moe_w8(const mi_model_t* model, const mi_w8_model_t* w8, const mi_moe_w8_layer_t* experts,
+                      const mi_lm_head_quant_t* head, const mi_batch_t* batch, const mi_verify_out_t* verify_out, int a8,
+                      mi_stream_t stream);
+
 size_t mi_workspace_bytes_generic(const mi_model_t* model, int T, int dtype);
 int mi_forward_generic(const mi_model_t* model, const mi_batch_t* batch, int dtype, mi_stream_t stream);
 /* Leaf operators in any storage dtype - what module-level callers of an fp16 / fp32 model bind (the Pixtral tower of

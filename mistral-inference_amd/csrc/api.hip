@@ -101,6 +101,8 @@ struct Workspace {
   float* s_x;        //     [T, max(dim, n_heads * head_dim, hidden_dim)] and their scales [T]
   bf16_t* head_deq;  // a quantised LM head at T > 8 (mi_forward_q with a head struct only, behind everything else): one slice of
                      //     lm_head_slice_rows(vocab) dequantised vocabulary rows
+  bf16_t* moe_deq;   // FP8 experts at T > 8 (mi_forward_moe_w8 only, behind everything else): the bf16 images of one projection family
+  const void** moe_tab;  //     of every expert (moe_deq_bytes: the larger family, W1|W3) and the pointer table [E][3] over them
   size_t total;
 };
 
@@ -121,6 +123,10 @@ size_t deq_scratch_elems(const mi_model_t* m) {
   return a > b ? a : b;  // (wo: D * nq <= a; w2: D * F <= b)
 }
 
+// bytes of the bf16 images of the larger projection family (W1 | W3) of all experts; W2's images reuse them
+size_t moe_deq_bytes(int E, int D, int F) { return (size_t)E * 2 * F * D * sizeof(bf16_t); }
+constexpr size_t MOE_TAB_BYTES = 16 * 3 * sizeof(void*);  // the pointer table [E <= 16][3] in front of them
+
 // bf16 elements of ONE dequantised ring (K or V) of B sequences of a layer
 size_t kv_scratch_elems(const mi_model_t* m, int B, int maxW) { return (size_t)B * m->n_kv_heads * maxW * m->head_dim; }
 
@@ -132,7 +138,7 @@ size_t verify_stash_bytes(const mi_model_t* m, int T) { return (size_t)m->n_laye
 // a8: the entry is mi_forward_w8a8 / mi_forward_w4a8 - the activation rows of its FP8-activation GEMMs
 // qhead: the LM head is quantised (mi_forward_q) - the slice of its bf16 image at T > 8
 Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool quant = false, bool kv8 = false, bool verify = false,
-                bool a8 = false, bool qhead = false) {
+                bool a8 = false, bool qhead = false, bool qmoe = false) {
   Workspace w;
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -185,6 +191,10 @@ Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool qu
   }
   // (any other forward: layout and total as ever)
   w.head_deq = (qhead && T > GEMV_MAX_T) ? (bf16_t*)take(lm_head_slice_bytes(m->vocab_size, m->dim)) : nullptr;
+  // (any other forward: layout and total as ever)
+  const bool moe_img = qmoe && m->num_experts > 0 && T > GEMV_MAX_T;
+  w.moe_tab = moe_img ? (const void**)take(MOE_TAB_BYTES) : nullptr;
+  w.moe_deq = moe_img ? (bf16_t*)take(moe_deq_bytes(m->num_experts, m->dim, m->hidden_dim)) : nullptr;
   w.total = off;
   return w;
 }
@@ -335,6 +345,7 @@ struct QuantModel {
   const mi_w8_layer_t* l8;  // host [n_layers]; the table of entry_format, the other one nullptr
   const mi_w4_layer_t* l4;
   const mi_lm_head_quant_t* head;  // mi_forward_q: the LM head is quantised too (m->output: its bytes), or nullptr - a bf16 head
+  const mi_moe_w8_layer_t* moe;    // mi_forward_moe_w8: host [n_layers], the experts are e4m3 too; nullptr: a MoE model is refused
 };
 // f(trait of the format)
 template <class Fn>
@@ -343,8 +354,8 @@ inline const mi_w8_layer_t* layers_of(const QuantModel& q, QuantW8) { return q.l
 inline const mi_w4_layer_t* layers_of(const QuantModel& q, QuantW4) { return q.l4; }
 // of the one struct that an entry point was handed (neither: not read)
 QuantModel quant_model(const mi_w8_model_t* w8, const mi_w4_model_t* w4) {
-  if (w8) return {MI_W8_FP8_E4M3, w8->format, w8->layers, nullptr, nullptr};
-  return w4 ? QuantModel{MI_W4_MXFP4, w4->format, nullptr, w4->layers, nullptr} : QuantModel{};
+  if (w8) return {MI_W8_FP8_E4M3, w8->format, w8->layers, nullptr, nullptr, nullptr};
+  return w4 ? QuantModel{MI_W4_MXFP4, w4->format, nullptr, w4->layers, nullptr, nullptr} : QuantModel{};
 }
 
 // ---- MoE FFN of T <= 8 tokens: per (token, slot) gate | up + SwiGLU into hid [T * top_k, F], then per token the down
@@ -361,6 +372,29 @@ int moe_decode(void* out, const void* residual, const void* x, int ldx, int T, i
   return hip_rc(launch_gemv(a, s), "moe w2 gemv");
 }
 
+// ... on FP8 experts: expert_tab points to e4m3 bytes, scale_tab [E][3] (device) to their fp32 row scales
+int moe_decode_w8(void* out, const void* residual, const void* x, int ldx, int T, int D, int F, const void* const* expert_tab,
+                  const float* const* scale_tab, const int32_t* sel_idx, const float* sel_w, int top_k, const void* norm_w, float eps,
+                  void* hid, hipStream_t s) {
+  GemvMoeW8Args a;
+  a.scale_tab = scale_tab;
+  a.g = gemv_common(x, ldx, D, F, norm_w, eps, hid, F);
+  a.g.mode = GEMV_MOE_W13; a.g.T = T;
+  a.g.expert_tab = expert_tab; a.g.sel_idx = sel_idx; a.g.sel_w = sel_w; a.g.top_k = top_k;
+  MI_TRY(hip_rc(launch_gemv_moe_w13_w8(a, s), "moe w13 gemv (w8)"));
+  a.g = gemv_common(hid, F, F, D, nullptr, 0.f, out, D);
+  a.g.mode = GEMV_MOE_W2; a.g.T = T; a.g.residual = (const bf16_t*)residual;
+  a.g.expert_tab = expert_tab; a.g.sel_idx = sel_idx; a.g.sel_w = sel_w; a.g.top_k = top_k;
+  return hip_rc(launch_moe_w2_w8(a, s), "moe w2 gemv (w8)");
+}
+
+// FP8 experts of a prefill: the device tables of the e4m3 bytes and their scales, and where their bf16 images go
+struct MoeW8Images {
+  const float* const* scale_tab;  // device [E][3]
+  bf16_t* deq;                    // moe_deq_bytes
+  const void** tab;               // device [E][3], written by the dequantisation launches
+};
+
 struct MoeScratch {
   bf16_t* hid;       // [T * top_k, F]
   bf16_t* y;         // expert outputs, compact rows      [T * top_k, D]
@@ -373,8 +407,15 @@ struct MoeScratch {
 };
 // ---- MoE FFN of a prefill: x [T, D] dense rows (already normed).  One token-grouped launch per projection covers all experts
 // (tile table built on the device: no host sync), then the weighted combine and the residual.
+// q8 != nullptr: expert_tab points to e4m3 bytes.  In front of each GEMM one launch writes bf16(scale[r] * e4m3(w)) images of that
+// projection family of all experts and the pointer table over them, and the GEMM runs on that table unchanged.
 int moe_grouped(void* out, const void* residual, const void* x, int T, int D, int F, int E, int k, const void* const* expert_tab,
-                const int32_t* sel_idx, const float* sel_w, const MoeScratch& w, hipStream_t s) {
+                const int32_t* sel_idx, const float* sel_w, const MoeScratch& w, hipStream_t s, const MoeW8Images* q8 = nullptr) {
+  auto images = [&](int family) {
+    const DequantMoeW8Args d = {expert_tab, q8->scale_tab, E, D, F, family, q8->deq, q8->tab};
+    return hip_rc(launch_dequant_moe_w8(d, s), family ? "dequant experts w2" : "dequant experts w1|w3");
+  };
+  const void* const* gemm_tab = q8 ? q8->tab : expert_tab;
   // 256-row m-tiles (gemm256.hip) once an expert averages a few of them, else 128-row tiles (gemm.hip)
   const int tile_rows = ((long)T * k >= 512L * E && D % 64 == 0 && F % 64 == 0) ? 256 : 128;
   const int max_m_tiles = (T * k + tile_rows - 1) / tile_rows + E;  // <= the scratch's max_tiles (sized for 128-row tiles)
@@ -384,13 +425,15 @@ int moe_grouped(void* out, const void* residual, const void* x, int T, int D, in
   g.epi = GEMM_SWIGLU; g.M = T * k; g.N = F; g.K = D; g.a = (const bf16_t*)x; g.lda = D; g.n0 = g.n1 = F;
   g.out = w.hid; g.ldo = F;
   g.tile_tab = w.tile_tab; g.n_tiles_ptr = w.n_tiles; g.max_m_tiles = max_m_tiles; g.tile_rows = tile_rows;
-  g.expert_tab = expert_tab; g.w_sel0 = 0; g.w_sel1 = 2; g.a_gather = w.tok_of;
+  g.expert_tab = gemm_tab; g.w_sel0 = 0; g.w_sel1 = 2; g.a_gather = w.tok_of;
+  if (q8) MI_TRY(images(0));
   MI_TRY(hip_rc(launch_gemm(g, s), "moe w13 grouped gemm"));
   memset(&g, 0, sizeof(g));
   g.epi = GEMM_STORE; g.M = T * k; g.N = D; g.K = F; g.a = w.hid; g.lda = F; g.n0 = g.n1 = D;
   g.out = w.y; g.ldo = D;
   g.tile_tab = w.tile_tab; g.n_tiles_ptr = w.n_tiles; g.max_m_tiles = max_m_tiles; g.tile_rows = tile_rows;
-  g.expert_tab = expert_tab; g.w_sel0 = 1; g.w_sel1 = -1;
+  g.expert_tab = gemm_tab; g.w_sel0 = 1; g.w_sel1 = -1;
+  if (q8) MI_TRY(images(1));
   MI_TRY(hip_rc(launch_gemm(g, s), "moe w2 grouped gemm"));
   return hip_rc(launch_moe_combine(out, residual, w.y, sel_idx, sel_w, w.row_of, T, D, k, s), "moe combine");
 }
@@ -1342,6 +1385,56 @@ int mi_moe_grouped_gemm(void* out, const void* residual, const void* x, int ldx,
   return moe_grouped(out, residual, x, T, D, F, E, top_k, expert_w_dev, sel_idx, sel_w, w, (hipStream_t)stream);
 }
 
+/* FP8 experts (include/mistral_hip.h) */
+static int check_moe_w8_args(const char* me, const void* expert_w_dev, const float* const* expert_scale_dev, int D, int F, int top_k) {
+  if (!expert_w_dev || !expert_scale_dev) return fail(MI_ERR_ARG, "%s: the expert table and the expert scale table [E][3] (device)", me);
+  if (D % 16 || F % 16) return fail(MI_ERR_SHAPE, "%s: D = %d and F = %d must be multiples of 16 (a 16-byte piece is 16 e4m3 weights)", me, D, F);
+  if (!(top_k == 1 || top_k == 2 || top_k == 4)) return fail(MI_ERR_SHAPE, "MoE: top_k in {1,2,4}");
+  if ((size_t)top_k * F * 2 > 65536) return fail(MI_ERR_SHAPE, "MoE: top_k * hidden_dim too large for the decode combine kernel");
+  return MI_OK;
+}
+
+int mi_moe_experts_decode_w8(void* out, const void* residual, const void* x, int ldx, int T, int D, int F,
+                             const void* const* expert_w_dev, const float* const* expert_scale_dev, const int32_t* sel_idx,
+                             const float* sel_w, int top_k, const void* norm_w, float eps, void* hidden_scratch, mi_stream_t stream) {
+  if (!out || !residual || !x || !sel_idx || !sel_w || !hidden_scratch || T <= 0 || D <= 0 || F <= 0)
+    return fail(MI_ERR_ARG, "mi_moe_experts_decode_w8");
+  MI_TRY(check_moe_w8_args("mi_moe_experts_decode_w8", expert_w_dev, expert_scale_dev, D, F, top_k));
+  if (T > GEMV_MAX_T) return fail(MI_ERR_UNSUPPORTED, "mi_moe_experts_decode_w8: T = %d > %d (use mi_moe_grouped_gemm_w8)", T, GEMV_MAX_T);
+  if (D > 16384) return fail(MI_ERR_SHAPE, "dim > 16384");
+  return moe_decode_w8(out, residual, x, ldx, T, D, F, expert_w_dev, expert_scale_dev, sel_idx, sel_w, top_k, norm_w, eps, hidden_scratch,
+                       (hipStream_t)stream);
+}
+
+// the bf16 leaf's scratch, then the pointer table and the images
+static MoeW8Images moe_w8_carve(const MoeScratch& w, int D, int F, int E, char* base, size_t* total) {
+  const size_t off = align_up(w.total);
+  *total = off + align_up(MOE_TAB_BYTES) + align_up(moe_deq_bytes(E, D, F));
+  return {nullptr, base ? (bf16_t*)(base + off + align_up(MOE_TAB_BYTES)) : nullptr, base ? (const void**)(base + off) : nullptr};
+}
+
+size_t mi_moe_grouped_gemm_w8_scratch_bytes(int T, int D, int F, int E, int top_k) {
+  if (T <= 0 || D <= 0 || F <= 0 || E <= 0 || top_k <= 0) return 0;
+  size_t total = 0;
+  moe_w8_carve(moe_carve(T, D, F, E, top_k, nullptr), D, F, E, nullptr, &total);
+  return total;
+}
+
+int mi_moe_grouped_gemm_w8(void* out, const void* residual, const void* x, int ldx, int T, int D, int F, int E, int top_k,
+                           const void* const* expert_w_dev, const float* const* expert_scale_dev, const int32_t* sel_idx,
+                           const float* sel_w, void* scratch, size_t scratch_bytes, mi_stream_t stream) {
+  if (!out || !residual || !x || !sel_idx || !sel_w || !scratch || T <= 0 || D <= 0 || F <= 0 || ldx != D)
+    return fail(MI_ERR_ARG, "mi_moe_grouped_gemm_w8 (x must be dense [T, D])");
+  MI_TRY(check_moe_w8_args("mi_moe_grouped_gemm_w8", expert_w_dev, expert_scale_dev, D, F, top_k));
+  if (E > 16 || top_k > E || E < 1) return fail(MI_ERR_SHAPE, "MoE: E <= 16, top_k <= 4");
+  const MoeScratch w = moe_carve(T, D, F, E, top_k, (char*)scratch);
+  size_t total = 0;
+  MoeW8Images img = moe_w8_carve(w, D, F, E, (char*)scratch, &total);
+  img.scale_tab = expert_scale_dev;
+  if (total > scratch_bytes) return fail(MI_ERR_WORKSPACE, "mi_moe_grouped_gemm_w8: scratch %zu < required %zu", scratch_bytes, total);
+  return moe_grouped(out, residual, x, T, D, F, E, top_k, expert_w_dev, sel_idx, sel_w, w, (hipStream_t)stream, &img);
+}
+
 int mi_set_decode_engine(int enabled) {
   const int prev = engine_mode();
   g_engine_mode = enabled != 0;
@@ -1471,7 +1564,8 @@ static int check_quant(const char* entry, const mi_model_t* m, const QuantModel&
     typedef decltype(Q) F;
     if (q.format != F::kFormat) return fail(MI_ERR_UNSUPPORTED, "%s: weight format %d (%s is the only one)", entry, q.format, F::kFormatName);
     if (!layers_of(q, Q)) return fail(MI_ERR_ARG, "%s: %s without layer scales", entry, F::kArg);
-    if (m->num_experts > 0) return fail(MI_ERR_UNSUPPORTED, "%s: %s weights on a MoE model are not implemented (the experts stay bf16)", entry, F::kName);
+    if (m->num_experts > 0 && !q.moe)
+      return fail(MI_ERR_UNSUPPORTED, "%s: %s weights on a MoE model are not implemented (the experts stay bf16)", entry, F::kName);
     if (m->lora_rank > 0)
       return fail(MI_ERR_UNSUPPORTED, "%s: un-merged LoRA on an %s base is not implemented; merge the adapter before quantising", entry, F::kName);
     if (m->dim % F::kMod || m->hidden_dim % F::kMod || (m->n_heads * m->head_dim) % F::kMod)
@@ -1524,7 +1618,8 @@ static int forward_body(const char* entry, const mi_model_t* m, const QuantModel
   if (bi.has_cache)
     for (int l = 0; l < m->n_layers; ++l) maxW = bt->cache_sizes[l] > maxW ? bt->cache_sizes[l] : maxW;
   const bool kv8 = bi.has_cache && kv_e4m3(bi.kv_layout);  // rings of e4m3 bytes: written by the e4m3 ring-write kernel only
-  const Workspace ws = carve(m, bi.T, vo ? bi.T : bi.B, maxW, (char*)bt->workspace, q != nullptr, kv8, vo != nullptr, a8, q && q->head);
+  const Workspace ws = carve(m, bi.T, vo ? bi.T : bi.B, maxW, (char*)bt->workspace, q != nullptr, kv8, vo != nullptr, a8, q && q->head,
+                             q && q->moe);
   MI_TRY(check_workspace_and_sample(entry, bt, ws.total, &bi));
   const int T = bi.T, B = bi.B, branch = bi.branch, kvl = bi.kv_layout;  // (kvl keeps MI_KV_E4M3: the ring write and the decode attention pick their e4m3 kernels by it)
   const bool has_cache = bi.has_cache, want_greedy = bi.want_sample, want_topp = bi.want_topp;
@@ -1603,7 +1698,7 @@ static int forward_body(const char* entry, const mi_model_t* m, const QuantModel
     if (q) {
       MI_TRY(with_format(q->entry_format, [&](auto Q) {
         const auto& S = layers_of(*q, Q)[l];
-        if (!(S.wq && S.wk && S.wv && S.wo && S.w1 && S.w2 && S.w3))
+        if (!(S.wq && S.wk && S.wv && S.wo && (q->moe || (S.w1 && S.w2 && S.w3))))  // (FP8 experts: their scales are in the tables of q->moe)
           return fail(MI_ERR_ARG, "%s: layer %d has a linear without %s", entry, l, decltype(Q)::kScales);
         set_scales(qkv, Q, S.wq, S.wk, S.wv); set_scales(wo, Q, S.wo); set_scales(w13, Q, S.w1, S.w3); set_scales(w2, Q, S.w2);
         return (int)MI_OK;
@@ -1673,7 +1768,20 @@ static int forward_body(const char* entry, const mi_model_t* m, const QuantModel
     } else {
       const int E = m->num_experts, k = m->top_k;
       if (!L.gate || !L.expert_w_dev || !L.expert_w_host) return fail(MI_ERR_ARG, "mi_forward: MoE layer tables");
-      if (gemv) {
+      if (q && q->moe) {  // FP8 experts: the same two routes on the e4m3 tables (the router reads the bf16 gate as ever)
+        const float* const* st = q->moe[l].expert_scale_dev;
+        if (!st) return fail(MI_ERR_ARG, "%s: layer %d has no expert scale table", entry, l);
+        if (gemv) {
+          MI_TRY(hip_rc(launch_moe_router(ws.sel_idx, ws.sel_w, h, D, T, D, L.gate, E, k, L.ffn_norm, m->norm_eps, s), "moe_router"));
+          MI_TRY(moe_decode_w8(h, h, h, D, T, D, F, L.expert_w_dev, st, ws.sel_idx, ws.sel_w, k, L.ffn_norm, m->norm_eps, ws.hid, s));
+        } else {
+          MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, L.ffn_norm, T, D, m->norm_eps, s), "ffn_norm"));
+          MI_TRY(hip_rc(launch_moe_router(ws.sel_idx, ws.sel_w, ws.xn, D, T, D, L.gate, E, k, nullptr, 0.f, s), "moe_router"));
+          const MoeScratch sc = {ws.hid, ws.moe_y, ws.tok_of, ws.row_of, ws.tile_tab, ws.n_tiles, ws.max_tiles, 0};
+          const MoeW8Images img = {st, ws.moe_deq, ws.moe_tab};
+          MI_TRY(moe_grouped(h, h, ws.xn, T, D, F, E, k, L.expert_w_dev, ws.sel_idx, ws.sel_w, sc, s, &img));
+        }
+      } else if (gemv) {
         MI_TRY(hip_rc(launch_moe_router(ws.sel_idx, ws.sel_w, h, D, T, D, L.gate, E, k, L.ffn_norm, m->norm_eps, s), "moe_router"));
         MI_TRY(moe_decode(h, h, h, D, T, D, F, L.expert_w_dev, ws.sel_idx, ws.sel_w, k, L.ffn_norm, m->norm_eps, ws.hid, s));
       } else {
@@ -1790,6 +1898,38 @@ int mi_forward_q(const mi_model_t* m, const mi_w8_model_t* w8, const mi_w4_model
   QuantModel q = quant_model(w8, w4);
   q.head = head;
   return forward_body(me, m, (w8 || w4) ? &q : nullptr, bt, stream, verify_out, a8 != 0);
+}
+
+/* FP8 experts (include/mistral_hip.h: mi_moe_w8_layer_t) */
+static int check_moe_w8_entry(const char* me, const mi_model_t* m, const mi_w8_model_t* w8, const mi_moe_w8_layer_t* experts) {
+  if (!m || !w8 || !experts) return fail(MI_ERR_ARG, "%s: model, w8 and the per-layer expert scale tables", me);
+  if (w8->format == MI_W4_MXFP4)
+    return fail(MI_ERR_UNSUPPORTED, "%s: MXFP4 experts are not implemented (the expert kernels read e4m3 rows: MI_W8_FP8_E4M3 = 1)", me);
+  if (m->num_experts <= 0) return fail(MI_ERR_ARG, "%s: a dense model (num_experts 0) has no experts to quantise; use mi_forward_w8", me);
+  return MI_OK;
+}
+
+size_t mi_workspace_bytes_moe_w8(const mi_model_t* model, const mi_w8_model_t* w8, const mi_moe_w8_layer_t* experts,
+                                 const mi_lm_head_quant_t* head, int T, int B, int max_cache_size, int kv_layout) {
+  if (!model || !w8 || !experts || T <= 0 || B <= 0 || !kv_layout_ok(kv_layout)) return 0;
+  return carve(model, T, B, max_cache_size > 0 ? max_cache_size : 1, nullptr, true, kv_e4m3(kv_layout), false, false, head != nullptr, true).total;
+}
+
+int mi_forward_moe_w8(const mi_model_t* m, const mi_w8_model_t* w8, const mi_moe_w8_layer_t* experts, const mi_lm_head_quant_t* head,
+                      const mi_batch_t* bt, const mi_verify_out_t* verify_out, int a8, mi_stream_t stream) {
+  const char* me = "mi_forward_moe_w8";
+  MI_TRY(check_moe_w8_entry(me, m, w8, experts));
+  if (m->lora_rank > 0)
+    return fail(MI_ERR_UNSUPPORTED, "%s: un-merged LoRA on an FP8 base is not implemented; merge the adapter before quantising", me);
+  if (a8) return fail(MI_ERR_UNSUPPORTED, "%s: the FP8-activation prefill GEMMs (a8, prefill_fp8) on FP8 experts are not implemented "
+                      "(no token-grouped W8A8 kernel)", me);
+  if (verify_out) return fail(MI_ERR_UNSUPPORTED, "%s: a verify step on FP8 experts is not implemented", me);
+  if (m->dim % 16 || m->hidden_dim % 16)
+    return fail(MI_ERR_SHAPE, "%s: dim and hidden_dim must be multiples of 16 (a 16-byte piece is 16 e4m3 weights)", me);
+  QuantModel q = quant_model(w8, nullptr);
+  q.head = head;
+  q.moe = experts;
+  return forward_body(me, m, &q, bt, stream);
 }
 
 }  // extern "C"

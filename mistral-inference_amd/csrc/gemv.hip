@@ -153,6 +153,152 @@ __global__ __launch_bounds__(256) void moe_w2_kernel(GemvArgs a) {
   }
 }
 
+#if !GEMV_F16
+// The same down-projection + combine on e4m3 rows with fp32 row scales (FP8 experts; expert_tab [E][3] points to bytes, scale_tab
+// [E][3] to the scales):  y = bf16(scale[r] * acc) - the scale meets the fp32 wave sum before the first bf16 rounding - then the
+// chain above unchanged: R = bf16(R + bf16(w * y)) over the experts in ascending id, out = bf16(h + R).
+//
+// Same structure: experts sorted by id with the slot_of remap, the TOPK hidden rows (bf16, as ever) sent to LDS by LDS-DMA ahead
+// of two weight batches, one flattened (unit, expert, batch) load cursor.  What half-sized rows change:
+//  - a chunk (one wave instruction of 16-byte pieces) is 1024 weights, so a row of F = 14336 is 14 chunks.  BATCH stays 8 loads
+//    (two batches = 16 KiB per wave in flight, the figure the bf16 kernels were tuned to), split as NR rows x U = 8 / NR chunks.
+//  - NR = 2 (U = 4) keeps the bf16 kernel's row pairs: D / 2 units per token, one per wave of a full grid at D = 4096 - the split
+//    a single token needs to occupy every CU - but 14 chunks are 4 batches of which the last is half padding.  NR = 4 (U = 2)
+//    makes a unit the same BYTES as a bf16 row pair, so the wave sums, the combine chain and the store weigh per byte what they
+//    weigh there, and 14 chunks are exactly 7 batches; it halves the units.  launch_moe_w2_w8 takes NR = 4 from two tokens on
+//    (the grid is T times the blocks, so the units still cover the CUs) and NR = 2 at one token.  Reasoned from the bf16 kernel's
+//    figures, not measured against each other.
+//  - lane i < NR finishes row NR u + i: it holds the row's scale (one 4-byte load per (unit, expert), issued a whole segment
+//    ahead: the first in front of the DMAs, each later one when the segment before it ends) and its running R.
+template <int TOPK, int NR>
+__global__ __launch_bounds__(256) void moe_w2_w8_kernel(GemvMoeW8Args aa) {
+  const GemvArgs& a = aa.g;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bf16_t* xs = reinterpret_cast<bf16_t*>(smem);  // [TOPK][K]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int t = blockIdx.y;
+  const int nwaves = gridDim.x * 4;
+  const int units = (a.N + NR - 1) / NR;
+  constexpr int U = BATCH / NR;
+  const int nch = (a.K + (1 << WE4m3::SHIFT) - 1) >> WE4m3::SHIFT;
+  const int nb = (nch + U - 1) / U;
+
+  int eid[TOPK];
+  float ew[TOPK];
+  const uint8_t* w2[TOPK];
+  const float* sc[TOPK];
+#pragma unroll
+  for (int k = 0; k < TOPK; ++k) {
+    eid[k] = a.sel_idx[t * TOPK + k];
+    ew[k] = a.sel_w[t * TOPK + k];
+  }
+  // visit experts in ascending id (moe.py:29 loop order)
+#pragma unroll
+  for (int i = 0; i < TOPK; ++i)
+#pragma unroll
+    for (int j = i + 1; j < TOPK; ++j)
+      if (eid[j] < eid[i]) {
+        const int te = eid[i]; eid[i] = eid[j]; eid[j] = te;
+        const float tw = ew[i]; ew[i] = ew[j]; ew[j] = tw;
+      }
+  int slot_of[TOPK];  // which hidden row belongs to sorted position k
+#pragma unroll
+  for (int k = 0; k < TOPK; ++k) {
+    slot_of[k] = 0;
+#pragma unroll
+    for (int s = 0; s < TOPK; ++s)
+      if (a.sel_idx[t * TOPK + s] == eid[k]) slot_of[k] = s;
+    w2[k] = reinterpret_cast<const uint8_t*>(a.expert_tab[eid[k] * 3 + 1]);
+    sc[k] = aa.scale_tab[eid[k] * 3 + 1];
+  }
+
+  // flattened load cursor over (unit, expert, batch)
+  int u = blockIdx.x * 4 + wid;
+  int ul = u, kl = 0, jl = 0;
+  u32x4 bufA[BATCH], bufB[BATCH];
+  auto issue = [&](u32x4 (&buf)[BATCH]) {  // branch-free around the loads (see gemv_core.cuh)
+    const bool live = ul < units;
+    const uint8_t* base = w2[0];
+#pragma unroll
+    for (int k = 1; k < TOPK; ++k) base = (kl == k) ? w2[k] : base;
+    const int ue = live ? ul : 0;
+    Rows<WE4m3, NR> r;
+#pragma unroll
+    for (int i = 0; i < NR; ++i)  // rows past N repeat the last one (the epilogue drops them)
+      r.p[i] = live ? base + (size_t)min(NR * ue + i, a.N - 1) * a.K : reinterpret_cast<const uint8_t*>(a.x);
+    load_batch<WE4m3, NR>(r, live ? jl * U : 0, live ? a.K : WE4m3::PIECE, live ? lane : 0, buf);
+    if (live && ++jl == nb) {
+      jl = 0;
+      if (++kl == TOPK) {
+        kl = 0;
+        ul += nwaves;
+      }
+    }
+  };
+  // the scale of this lane's row in segment (unit uu, sorted expert kk); past the last unit or row: a clamped, unused value
+  auto load_scale = [&](int uu, int kk) {
+    const float* p = sc[0];
+#pragma unroll
+    for (int k = 1; k < TOPK; ++k) p = (kk == k) ? sc[k] : p;
+    return p[min(NR * min(uu, units - 1) + (lane & (NR - 1)), a.N - 1)];
+  };
+  float s_cur = load_scale(u, 0);
+  // the TOPK hidden rows by LDS-DMA, one row per sorted position, BEHIND the first scale load and AHEAD of the two weight batches:
+  // vmcnt retires in order and exactly 2 x BATCH = 16 loads (8 per batch whatever NR is: NR rows x 8 / NR chunks) are issued after
+  // the DMAs, so vmcnt(16) = "the scale and the rows have landed" with both weight batches still in flight
+  static_assert(BATCH == 8, "the wait below counts two batches of 8 loads");
+#pragma unroll
+  for (int k = 0; k < TOPK; ++k)
+    dma_rows_to_lds(a.x + ((size_t)t * TOPK + slot_of[k]) * a.ldx, 0, 1, 1, a.K >> 3, reinterpret_cast<char*>(xs + (size_t)k * a.K));
+  issue(bufA);
+  issue(bufB);
+  asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+  __syncthreads();
+
+  float acc[NR][1];
+#pragma unroll
+  for (int i = 0; i < NR; ++i) acc[i][0] = 0.f;
+  int jc = 0, kc = 0;
+  float r = 0.f;
+  auto step = [&](u32x4 (&buf)[BATCH]) {
+    fma_batch<WE4m3, 1, NR>(buf, jc * U, xs + (size_t)kc * a.K, a.K, lane, acc);
+    issue(buf);
+    if (++jc == nb) {
+      jc = 0;
+      float y = 0.f;
+#pragma unroll
+      for (int i = 0; i < NR; ++i) {
+        const float yi = wave_sum(acc[i][0]);
+        acc[i][0] = 0.f;
+        y = (lane == i) ? yi : y;
+      }
+      float w = ew[0];
+#pragma unroll
+      for (int k = 1; k < TOPK; ++k) w = (kc == k) ? ew[k] : w;
+      r = E::round(r + E::round(w * E::round(s_cur * y)));
+      if (++kc == TOPK) {
+        kc = 0;
+        const int n = NR * u + lane;
+        if (lane < NR && u < units && n < a.N) {
+          const size_t o = (size_t)t * a.ldo + n;
+          reinterpret_cast<bf16_t*>(a.out)[o] = E::from_f(E::to_f(a.residual[o]) + r);
+        }
+        r = 0.f;
+        u += nwaves;
+      }
+      s_cur = load_scale(u, kc);
+    }
+  };
+  if (u < units) {  // both steps per trip: see gemv_core.cuh (a step past the last unit stores nothing)
+    do {
+      step(bufA);
+      step(bufB);
+    } while (u < units);
+  }
+}
+#endif
+
 template <int MODE>
 hipError_t launch_mode(const GemvArgs& a, int TT, dim3 grid, size_t lds, hipStream_t s) {
   return for_tt(TT, [&](auto tt) {
@@ -244,3 +390,27 @@ hipError_t launch_gemv(const GemvArgs& a, hipStream_t s) {
     default: return hipErrorInvalidValue;
   }
 }
+
+#if !GEMV_F16
+// a.g: mode GEMV_MOE_W2 as launch_gemv takes it (x = hid [T * top_k, K], N = D rows, K = F, K % 16 == 0)
+hipError_t launch_moe_w2_w8(const GemvMoeW8Args& a, hipStream_t s) {
+  const GemvArgs& g = a.g;
+  const int nr = g.T >= 2 ? 4 : 2;  // rows per unit (moe_w2_w8_kernel)
+  const int units = (g.N + nr - 1) / nr;
+  const int cus = device_cus();
+  int blocks = even_blocks(units, cus);
+  if (!blocks) blocks = spread_blocks(units, max_blocks(cus));
+  const size_t lds = (size_t)g.top_k * g.K * 2;
+  const dim3 grid(blocks, g.T);
+  switch (g.top_k * 8 + nr) {
+    case 1 * 8 + 2: hipLaunchKernelGGL((moe_w2_w8_kernel<1, 2>), grid, dim3(256), lds, s, a); break;
+    case 1 * 8 + 4: hipLaunchKernelGGL((moe_w2_w8_kernel<1, 4>), grid, dim3(256), lds, s, a); break;
+    case 2 * 8 + 2: hipLaunchKernelGGL((moe_w2_w8_kernel<2, 2>), grid, dim3(256), lds, s, a); break;
+    case 2 * 8 + 4: hipLaunchKernelGGL((moe_w2_w8_kernel<2, 4>), grid, dim3(256), lds, s, a); break;
+    case 4 * 8 + 2: hipLaunchKernelGGL((moe_w2_w8_kernel<4, 2>), grid, dim3(256), lds, s, a); break;
+    case 4 * 8 + 4: hipLaunchKernelGGL((moe_w2_w8_kernel<4, 4>), grid, dim3(256), lds, s, a); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+#endif

@@ -7,6 +7,14 @@
 // A row is half the bytes of a bf16 row, so the fixed cost of a unit (wave reductions, epilogue, loop bookkeeping) weighs twice
 // as much.  Units are therefore RP row pairs: RP = 2 (four rows) where the matrix has enough row pairs that every wave of the grid
 // still gets at least two units (W1|W3), else RP = 1 (W8::row_pairs; MI_GEMV_W8_RP: its A/B switch).
+//
+// GEMV_MOE_W13 (FP8 experts: gate | up of the chosen experts, one (token, slot) problem per blockIdx.y): the dense rule does not
+// carry over.  A problem has only F row pairs, and there are T * top_k problems side by side, so what a wave gets is decided by the
+// grid of ALL problems: launch_gemv_moe_w13_w8 gives every problem an equal share of one resident round of blocks (max_blocks /
+// problems, at least one) and takes RP = 2 where each wave of that share still gets two four-row units (F >= 2 * 2 * 4 * share),
+// else RP = 1.  Mixtral-8x7B (F = 14336) at one token: 2 problems x 256 blocks, RP = 2, 7 units per wave; the same F at batch 8
+// (16 problems x 32 blocks) keeps RP = 2 with 56 units per wave.  F % 16 == 0 makes F even: a four-row unit is never ragged.
+// The rule is reasoned from the dense kernels' measurements, not measured itself (profiles/EXPERIMENTS.md).
 #include <cstdlib>
 
 #include "common.cuh"
@@ -23,6 +31,54 @@ template <int TT, int MODE, int RP, bool DMA>
 __global__ __launch_bounds__(256, (TT == 1 ? 4 : (TT <= 3 ? 3 : 2))) void gemv_w8_kernel(GemvW8Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   gemv_body<WE4m3, TT, MODE, 2 * RP, DMA>(a.g, a.scale, smem, blockIdx.x, gridDim.x, 0);
+}
+
+// The expert of problem blockIdx.y and its W1 / W3 scale vectors come from the device tables; gemv_body reads scale[0] beside the W1
+// row and scale[1] beside the W3 row of a pair, and acc * scale enters the SwiGLU epilogue where acc enters it on bf16 rows.
+template <int RP>
+__global__ __launch_bounds__(256, 4) void gemv_w8_moe_w13_kernel(GemvMoeW8Args a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int e = a.g.sel_idx[blockIdx.y];
+  const float* const sc[3] = {a.scale_tab[e * 3 + 0], a.scale_tab[e * 3 + 2], nullptr};
+  gemv_body<WE4m3, 1, GEMV_MOE_W13, 2 * RP, false>(a.g, sc, smem, blockIdx.x, gridDim.x, blockIdx.y);
+}
+
+// ---- the bf16 images of one projection family of every expert, and the pointer table over them (kernels.h DequantMoeW8Args).
+// One 16-byte load and two 16-byte stores per lane, as dequant_w8_kernel.
+__global__ __launch_bounds__(256) void dequant_moe_w8_kernel(DequantMoeW8Args a) {
+  const int K = a.family ? a.F : a.D;
+  const int rows = a.family ? a.D : 2 * a.F;  // of one expert
+  const int ppr = K >> 4;                     // pieces per row
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (blockIdx.x == 0 && (int)threadIdx.x < a.E) {
+    const int e = threadIdx.x;
+    bf16_t* img = a.out + (size_t)e * rows * K;
+    if (a.family) {
+      a.tab_out[e * 3 + 1] = img;
+    } else {
+      a.tab_out[e * 3 + 0] = img;
+      a.tab_out[e * 3 + 2] = img + (size_t)a.F * K;
+    }
+  }
+  if (idx >= (size_t)a.E * rows * ppr) return;
+  const size_t gr = idx / ppr;  // row of the whole image
+  const int pc = (int)(idx - gr * ppr);
+  const int e = (int)(gr / rows), r = (int)(gr - (size_t)e * rows);
+  const int which = a.family ? 1 : (r < a.F ? 0 : 2), rr = (a.family || r < a.F) ? r : r - a.F;
+  const uint8_t* src = reinterpret_cast<const uint8_t*>(a.expert_tab[e * 3 + which]) + (size_t)rr * K + pc * 16;
+  const float sc = a.scale_tab[e * 3 + which][rr];
+  const u32x4 w = ld16_nt(src);
+  u32x4 o[2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    f32x2_t lo, hi;
+    cvt4_e4m3_f32(w[i], lo, hi);
+    o[i >> 1][2 * (i & 1)] = pack_bf2(lo[0] * sc, lo[1] * sc);
+    o[i >> 1][2 * (i & 1) + 1] = pack_bf2(hi[0] * sc, hi[1] * sc);
+  }
+  bf16_t* dst = a.out + gr * K + pc * 16;
+  st16(dst, o[0]);
+  st16(dst + 8, o[1]);
 }
 
 // ---- rows of e4m3 + row scales -> bf16 rows: out[r, k] = bf16(scale[r] * e4m3(W[r, k])).  One 16-byte load and two 16-byte
@@ -55,6 +111,26 @@ hipError_t launch_dequant_w8(const DequantW8Args& a, hipStream_t s) {
   if (pieces == 0) return hipSuccess;
   hipLaunchKernelGGL(dequant_w8_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, s, a);
   return hipGetLastError();
+}
+
+hipError_t launch_dequant_moe_w8(const DequantMoeW8Args& a, hipStream_t s) {
+  const size_t pieces = (size_t)a.E * (a.family ? (size_t)a.D * (a.F >> 4) : 2 * (size_t)a.F * (a.D >> 4));
+  if (pieces == 0 || a.E > 256) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dequant_moe_w8_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// a.g: mode GEMV_MOE_W13 as launch_gemv takes it (N = F row pairs per problem, K = D, K % 16 == 0)
+hipError_t launch_gemv_moe_w13_w8(const GemvMoeW8Args& a, hipStream_t s) {
+  const GemvArgs& g = a.g;
+  const int cus = device_cus(), problems = g.T * g.top_k;
+  int share = max_blocks(cus) / problems;  // blocks of one problem: an equal part of one resident round
+  if (share < 1) share = 1;
+  const int rp = g.N >= 2 * 2 * 4 * share ? 2 : 1;
+  const int units = (g.N + rp - 1) / rp;
+  const dim3 grid(spread_blocks(units, share), problems);
+  const size_t lds = lds_bytes(1, g.K, g.norm_w != nullptr);
+  return rp == 2 ? launch_lds<gemv_w8_moe_w13_kernel<2>>(a, grid, lds, s) : launch_lds<gemv_w8_moe_w13_kernel<1>>(a, grid, lds, s);
 }
 
 namespace {

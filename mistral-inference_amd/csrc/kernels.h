@@ -96,6 +96,26 @@ hipError_t launch_gemv_w4(const GemvW4Args& a, hipStream_t s);
 hipError_t launch_dequant_w4(const DequantW4Args& a, hipStream_t s);
 int gemv_w4_row_pairs(int npairs, int cus);  // row pairs per unit the launcher picks at one token
 
+// MoE experts on e4m3 rows (FP8 experts): g.expert_tab [E][3] points to e4m3 bytes (w1 [F, D], w2 [D, F], w3 [F, D]) and
+// scale_tab [E][3] (device) to their fp32 row scales.  g.mode GEMV_MOE_W13: gemv_w8.hip; GEMV_MOE_W2: gemv.hip (moe_w2_w8_kernel).
+struct GemvMoeW8Args {
+  GemvArgs g;
+  const float* const* scale_tab;
+};
+hipError_t launch_gemv_moe_w13_w8(const GemvMoeW8Args& a, hipStream_t s);
+hipError_t launch_moe_w2_w8(const GemvMoeW8Args& a, hipStream_t s);
+// gemv_w8.hip: the bf16 images of one projection family of ALL experts - family 0: per expert W1 [F, D] then W3 [F, D]; family 1:
+// W2 [D, F] - dense in `out`, expert after expert: out[...] = bf16(scale[r] * e4m3(w[r, k])).  The same launch writes the
+// family's entries of tab_out [E][3] (device), the pointers the token-grouped GEMMs read.  D % 16 == 0, F % 16 == 0.
+struct DequantMoeW8Args {
+  const void* const* expert_tab;  // device [E][3]
+  const float* const* scale_tab;  // device [E][3]
+  int E, D, F, family;
+  bf16_t* out;
+  const void** tab_out;
+};
+hipError_t launch_dequant_moe_w8(const DequantMoeW8Args& a, hipStream_t s);
+
 // ---------------------------------------------------------------------------------------------- GEMM
 enum GemmEpi { GEMM_STORE = 0, GEMM_RESIDUAL = 1, GEMM_SWIGLU = 2, GEMM_LOGITS = 3, GEMM_LOGPROB = 4 };
 

@@ -107,6 +107,11 @@ class MiLmHeadQuant(C.Structure):
 MI_LM_HEAD_SLICE_ROWS = 8192  # include/mistral_hip.h
 
 
+class MiMoeW8Layer(C.Structure):
+    """`mi_moe_w8_layer_t`: the DEVICE table [E][3] of fp32 row-scale pointers of a MoE layer's FP8 experts."""
+    _fields_ = [("expert_scale_dev", _vp)]
+
+
 class MiMambaLayer(C.Structure):
     """`mi_mamba_layer_t`: the device pointers of one Mamba2 layer (dt_bias, A_log, D: fp32)."""
     _fields_ = [(n, _vp) for n in ("norm", "in_proj", "conv_w", "conv_b", "dt_bias", "A_log", "D", "gated_norm", "out_proj")]
@@ -157,6 +162,16 @@ _SIGS = {
     "mi_moe_grouped_gemm_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "mi_moe_grouped_gemm": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
                                       C.c_size_t, _vp]),
+    # FP8 experts (additive to ABI v9: the presence of these symbols is the feature test)
+    "mi_moe_experts_decode_w8": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_float,
+                                           _vp, _vp]),
+    "mi_moe_grouped_gemm_w8_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mi_moe_grouped_gemm_w8": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp,
+                                         C.c_size_t, _vp]),
+    "mi_workspace_bytes_moe_w8": (C.c_size_t, [C.POINTER(MiModel), C.POINTER(MiW8Model), C.POINTER(MiMoeW8Layer), C.POINTER(MiLmHeadQuant),
+                                               C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mi_forward_moe_w8": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiW8Model), C.POINTER(MiMoeW8Layer), C.POINTER(MiLmHeadQuant),
+                                    C.POINTER(MiBatch), C.POINTER(MiVerifyOut), C.c_int, _vp]),
     "mi_workspace_bytes": (C.c_size_t, [C.POINTER(MiModel), C.c_int, C.c_int, C.c_int]),
     "mi_forward": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiBatch), _vp]),
     # weight-only FP8 (additive to ABI v9: the presence of these symbols is the feature test)
@@ -920,11 +935,13 @@ def qkv_rope_kvwrite_w4(x: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, wv:
 
 def moe_experts(x: torch.Tensor, expert_tab: torch.Tensor, n_experts: int, hidden_dim: int, sel_idx: torch.Tensor,
                 sel_w: torch.Tensor, residual: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None,
-                eps: float = 0.0) -> torch.Tensor:
+                eps: float = 0.0, scale_tab: Optional[torch.Tensor] = None) -> torch.Tensor:
     """bf16(residual + sum over each token's picked experts (ascending id) of bf16(w * expert(x))) (reference moe.py:28-32 +
     transformer_layers.py:168).  expert_tab: int64 device tensor [E, 3] of (w1, w2, w3) pointers; sel_idx/sel_w: the
     router's output.  T <= 8 runs the two weight-streaming launches (mi_moe_experts_decode), larger T the token-grouped
-    MFMA GEMMs (mi_moe_grouped_gemm).  residual None: zeros (the bare MoeLayer.forward value)."""
+    MFMA GEMMs (mi_moe_grouped_gemm).  residual None: zeros (the bare MoeLayer.forward value).
+    scale_tab: FP8 experts - expert_tab then points to e4m3 bytes and scale_tab, int64 device tensor [E, 3], to their fp32 row
+    scales; the two routes are mi_moe_experts_decode_w8 and mi_moe_grouped_gemm_w8."""
     T, D = x.shape
     k = sel_idx.shape[1]
     if residual is None:
@@ -933,12 +950,25 @@ def moe_experts(x: torch.Tensor, expert_tab: torch.Tensor, n_experts: int, hidde
     L, st = lib(), stream_ptr(x.device)
     if T <= GEMV_MAX_T:
         hid = torch.empty((T * k, hidden_dim), dtype=x.dtype, device=x.device)
+        if scale_tab is not None:
+            check(L.mi_moe_experts_decode_w8(dev_ptr(out), dev_ptr(residual), dev_ptr(x), x.stride(0), T, D, hidden_dim,
+                                             expert_tab.data_ptr(), scale_tab.data_ptr(), dev_ptr(sel_idx, torch.int32),
+                                             dev_ptr(sel_w, torch.float32), k, dev_ptr(norm_w), float(eps), dev_ptr(hid), st),
+                  "mi_moe_experts_decode_w8")
+            return out
         check(L.mi_moe_experts_decode(dev_ptr(out), dev_ptr(residual), dev_ptr(x), x.stride(0), T, D, hidden_dim,
                                       expert_tab.data_ptr(), dev_ptr(sel_idx, torch.int32), dev_ptr(sel_w, torch.float32), k,
                                       dev_ptr(norm_w), float(eps), dev_ptr(hid), st), "mi_moe_experts_decode")
         return out
     assert norm_w is None, "the grouped path takes already-normalised rows"
     xc = x if x.is_contiguous() else x.contiguous()
+    if scale_tab is not None:
+        need = L.mi_moe_grouped_gemm_w8_scratch_bytes(T, D, hidden_dim, n_experts, k)
+        scratch = torch.empty(need, dtype=torch.uint8, device=x.device)
+        check(L.mi_moe_grouped_gemm_w8(dev_ptr(out), dev_ptr(residual), dev_ptr(xc), D, T, D, hidden_dim, n_experts, k,
+                                       expert_tab.data_ptr(), scale_tab.data_ptr(), dev_ptr(sel_idx, torch.int32),
+                                       dev_ptr(sel_w, torch.float32), scratch.data_ptr(), need, st), "mi_moe_grouped_gemm_w8")
+        return out
     need = L.mi_moe_grouped_gemm_scratch_bytes(T, D, hidden_dim, n_experts, k)
     scratch = torch.empty(need, dtype=torch.uint8, device=x.device)
     check(L.mi_moe_grouped_gemm(dev_ptr(out), dev_ptr(residual), dev_ptr(xc), D, T, D, hidden_dim, n_experts, k,

@@ -58,6 +58,7 @@ class QuantizationArgs(_FromDict):
     qformat_weight: str         # "fp8_e4m3": OCP e4m3 bytes + one fp32 scale per output row; "mxfp4": OCP MXFP4, e2m1 codes in
                                 # blocks of 32 along `in` + one e8m0 scale byte per block
     lm_head: bool = False       # `output.weight` is quantised in the same format too (opt-in; a folder without the key: a bf16 head)
+    experts: bool = False       # a MoE model whose expert linears are quantised too (opt-in, "fp8_e4m3" only; without it a MoE model is refused)
 
     def __post_init__(self) -> None:
         if self.qformat_weight not in QFORMATS:

@@ -12,6 +12,7 @@ from torch import nn
 
 from . import _hip
 from .args import MoeArgs  # noqa: F401  (re-exported like the reference module)
+from .quant import QuantLinear, linear_quant
 
 
 class MoeLayer(nn.Module):
@@ -30,6 +31,17 @@ class MoeLayer(nn.Module):
             self._tab = torch.tensor(ptrs, dtype=torch.int64, device=self.gate.weight.device).view(-1, 3)
         return self._tab
 
+    def _scale_table(self):
+        """FP8 experts: int64 device tensor [E, 3] of the experts' (w1, w2, w3) row-scale pointers, cached beside the weight
+        table; None for bf16 experts."""
+        if not isinstance(self.experts[0].w1, QuantLinear):
+            return None
+        ptrs = [p for ex in self.experts for p in (ex.w1.qscale_weight.data_ptr(), ex.w2.qscale_weight.data_ptr(), ex.w3.qscale_weight.data_ptr())]
+        if getattr(self, "_stab_ptrs", None) != ptrs:
+            self._stab_ptrs = ptrs
+            self._stab = torch.tensor(ptrs, dtype=torch.int64, device=self.gate.weight.device).view(-1, 3)
+        return self._stab
+
     def forward(self, inputs: torch.Tensor) -> torch.Tensor:
         """inputs [T, D] (already ffn-normalised) -> sum over the token's k experts of w * expert(inputs), accumulated in
         bf16 in ascending expert id (the order in which the reference's loop rounds, moe.py:29-31).
@@ -46,7 +58,7 @@ class MoeLayer(nn.Module):
         if not fused:
             return self._forward_general(inputs)
         idx, w = _hip.moe_router(inputs, self.gate.weight, k)          # [T, k] int32 / fp32 (bf16-valued)
-        return _hip.moe_experts(inputs, self._expert_table(), E, F, idx, w)
+        return _hip.moe_experts(inputs, self._expert_table(), E, F, idx, w, scale_tab=self._scale_table())
 
     def _forward_general(self, inputs: torch.Tensor) -> torch.Tensor:
         """Any expert count / top-k (reference moe.py:24-32 literally): the routing bookkeeping in torch on the device, the
@@ -62,7 +74,10 @@ class MoeLayer(nn.Module):
             if tok.numel() == 0:
                 continue
             x = inputs.index_select(0, tok).contiguous()
-            hid = _hip.linear(x, (expert.w1.weight, expert.w3.weight), _hip.EPI_SWIGLU)
-            y = _hip.linear(hid, (expert.w2.weight,), _hip.EPI_STORE)
+            if isinstance(expert.w1, QuantLinear):  # FP8 experts: the same two launches on the quantised linears
+                y = expert.w2(linear_quant(x, (expert.w1, expert.w3), _hip.EPI_SWIGLU))
+            else:
+                hid = _hip.linear(x, (expert.w1.weight, expert.w3.weight), _hip.EPI_SWIGLU)
+                y = _hip.linear(hid, (expert.w2.weight,), _hip.EPI_STORE)
             results[tok] += weights[tok, slot, None] * y
         return results

@@ -11,7 +11,14 @@ shares) stands where its `nn.Linear` stands (reference transformer_layers.py:51-
 `quantize_rows` produces power-of-two row scales only; W' is then exact in bf16 and both forms compute the bf16 model on the
 dequantised weights, up to fp32 summation order.  Other positive finite scales (checkpoints made elsewhere) are accepted; the
 two forms then differ by one bf16 rounding of each weight.  Embeddings, norms, the LM head, the MoE gate, the vision tower and
-the K/V rings stay bf16.  Dense bf16 models without un-merged LoRA only.
+the K/V rings stay bf16.  Dense bf16 models without un-merged LoRA only - and, opt-in, MoE models (below).
+
+FP8 experts (`quantization.experts`, opt-in: `quantize_checkpoint(..., experts=True)`, `from_folder(..., quantize="fp8_e4m3",
+quantize_experts=True)`): the three linears of every expert of a MoE model in the same format, `layers.N.feed_forward.experts.E.
+w{1,2,3}.weight` / `.qscale_weight`, beside the quantised attention linears; the router `gate` stays bf16.  T <= 8: the chosen
+experts' gate | up GEMV and the down-projection + ordered combine read the e4m3 rows (csrc/gemv_w8.hip, csrc/gemv.hip
+moe_w2_w8_kernel), `y = bf16(scale[r] * acc)`; above, one dequantisation launch per projection family in front of the token-grouped
+GEMMs.  "mxfp4" experts, `prefill_fp8` and speculative verify steps on such a model are refused.  Nobody claims model quality.
 
 Checkpoint layout: `<linear>.weight` with dtype F8_E4M3, `<linear>.qscale_weight` fp32 [out] (a scalar or [1] is broadcast at
 load), `params.json` with `"quantization": {"qformat_weight": "fp8_e4m3"}`.  Compatibility is claimed only with checkpoints
@@ -68,12 +75,17 @@ QSCALE_ACT_KEY = "qscale_act"  # per-tensor activation scales of FP8-activation 
 E4M3_MAX = 448.0
 # the linears that are quantised: the seven of every dense layer, nothing else
 _QUANT_KEY = re.compile(r"^layers\.\d+\.(attention\.w[qkvo]|feed_forward\.w[123])\.weight$")
+# ... and with `quantization.experts` the three of every expert of a MoE layer (the router `gate` stays bf16)
+_EXPERT_KEY = re.compile(r"^layers\.\d+\.feed_forward\.experts\.\d+\.w[123]\.weight$")
 
 # What a quantised model cannot be combined with: one text per kind, the format's name filled in (refusal()).
 _REFUSALS = {
     "lora": ("un-merged LoRA on an {name}-quantised base is not implemented; merge the adapter into the bf16 weights "
              "(Transformer.load_lora on a bf16 model) and quantise the result"),
     "moe": "{name} weight-only quantisation of a MoE model is not implemented (the expert kernels read bf16 weights)",
+    "experts_dense": "quantize_experts=True / quantization.experts on a dense model is not implemented: it has no experts to quantise",
+    "experts_format": ("{name} expert weights are not implemented: the expert kernels read FP8 (e4m3) rows "
+                       "(quantize=\"fp8_e4m3\" with quantize_experts=True)"),
     "merge": ("load_lora: merging an adapter into {name}-quantised weights is not implemented (the merge needs the bf16 "
               "weights); merge into the bf16 checkpoint and quantise the result"),
     "storage": ("{name} weight-only quantisation with fp16 / fp32 storage ({dtype}) is not implemented: the "
@@ -107,8 +119,13 @@ def refuse_quant_combinations(args, dtype: Optional[torch.dtype]) -> None:
         return
     if args.lora is not None:
         raise NotImplementedError(refusal("lora", args.quantization))
+    if args.moe is None and args.quantization.experts:
+        raise NotImplementedError(refusal("experts_dense", args.quantization))
     if args.moe is not None:
-        raise NotImplementedError(refusal("moe", args.quantization))
+        if not args.quantization.experts:  # (opt-in: without the switch a MoE model stays refused)
+            raise NotImplementedError(refusal("moe", args.quantization))
+        if args.quantization.qformat_weight != QFORMAT_FP8_E4M3:
+            raise NotImplementedError(refusal("experts_format", args.quantization))
     if dtype is not None and dtype != torch.bfloat16:
         raise NotImplementedError(refusal("storage", args.quantization, dtype=dtype))
 
@@ -122,6 +139,9 @@ def refuse_prefill_fp8(args, dtype: Optional[torch.dtype]) -> None:
         what = f"{quantized_linear_cls(qz).name} weights"
     elif dtype not in (None, torch.bfloat16):
         what = f"{dtype} storage"
+    elif qz.experts:
+        raise NotImplementedError("prefill_fp8=True on a MoE model with FP8 experts is not implemented (there is no token-grouped "
+                                  "W8A8 kernel; its prefills dequantise the experts in front of the bf16 grouped GEMMs)")
     else:
         return
     raise NotImplementedError(_REFUSALS["prefill_fp8"].format(what=what))
@@ -141,8 +161,8 @@ def refuse_prefill_w4a8(args, dtype: Optional[torch.dtype]) -> None:
     raise NotImplementedError(_REFUSALS["prefill_w4a8"].format(what=what))
 
 
-def is_quantized_linear_key(key: str) -> bool:
-    return _QUANT_KEY.match(key) is not None
+def is_quantized_linear_key(key: str, experts: bool = False) -> bool:
+    return _QUANT_KEY.match(key) is not None or (experts and _EXPERT_KEY.match(key) is not None)
 
 
 def quantize_rows(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -383,11 +403,12 @@ def check_lm_head_tensors(folder, quantization: QuantizationArgs, keys) -> None:
                          "(the flag and the tensors disagree)")
 
 
-def quantize_state_tensor(key: str, t: torch.Tensor, qformat: str = QFORMAT_FP8_E4M3, lm_head: bool = False) -> Dict[str, torch.Tensor]:
+def quantize_state_tensor(key: str, t: torch.Tensor, qformat: str = QFORMAT_FP8_E4M3, lm_head: bool = False,
+                          experts: bool = False) -> Dict[str, torch.Tensor]:
     """One checkpoint tensor -> the tensors that replace it: a quantised linear becomes its bytes and its row (MXFP4: block)
-    scales, anything else stays as it is.  lm_head: `output.weight` is such a linear too."""
+    scales, anything else stays as it is.  lm_head: `output.weight` is such a linear too; experts: so are the expert linears."""
     check_quantize_arg(qformat)
-    if not (is_quantized_linear_key(key) or (lm_head and key == LM_HEAD_KEY)):
+    if not (is_quantized_linear_key(key, experts) or (lm_head and key == LM_HEAD_KEY)):
         return {key: t}
     cls = QUANT_LINEARS[qformat]
     if t.dtype != torch.bfloat16:
@@ -397,12 +418,14 @@ def quantize_state_tensor(key: str, t: torch.Tensor, qformat: str = QFORMAT_FP8_
 
 
 def quantize_checkpoint(src_folder: Union[Path, str], dst_folder: Union[Path, str], qformat: str = QFORMAT_FP8_E4M3,
-                        lm_head: bool = False) -> Path:
+                        lm_head: bool = False, experts: bool = False) -> Path:
     """bf16 folder (params.json + consolidated.safetensors) -> weight-only quantised folder, tensor by tensor on the CPU: the
     seven linears of every layer become `<linear>.weight` (F8_E4M3) + `<linear>.qscale_weight` (fp32 [out]), or with
     qformat="mxfp4" U8 [out, in / 2] + U8 [out, in / 32]; everything else is copied.  lm_head=True (opt-in): `output.weight`
     and `output.qscale_weight` likewise, and `"lm_head": true` in the `quantization` block; without it the block has no such key
-    and the head stays bf16.  Other files of the folder (tokenizer) are the caller's to copy."""
+    and the head stays bf16.  experts=True (opt-in, a MoE folder, "fp8_e4m3" only): the three linears of every expert likewise
+    (`layers.N.feed_forward.experts.E.w{1,2,3}.weight` / `.qscale_weight`; the router `gate` stays bf16) and `"experts": true` in
+    the block; without it a MoE folder is refused.  Other files of the folder (tokenizer) are the caller's to copy."""
     import safetensors
     from safetensors.torch import save_file
     from .args import TransformerArgs
@@ -414,19 +437,19 @@ def quantize_checkpoint(src_folder: Union[Path, str], dst_folder: Union[Path, st
     args = TransformerArgs.from_dict(params)
     if args.quantization is not None:
         raise ValueError(f"{src} is already quantised ({args.quantization.qformat_weight})")
-    args.quantization = QuantizationArgs(qformat)
+    args.quantization = QuantizationArgs(qformat, experts=experts)
     refuse_quant_combinations(args, None)
     st_file = src / "consolidated.safetensors"
     assert st_file.exists(), f"{st_file} does not exist (quantize_checkpoint reads safetensors)"
     out: Dict[str, torch.Tensor] = {}
     with safetensors.safe_open(str(st_file), framework="pt", device="cpu") as f:
         for k in f.keys():
-            out.update(quantize_state_tensor(k, f.get_tensor(k), qformat, lm_head))
+            out.update(quantize_state_tensor(k, f.get_tensor(k), qformat, lm_head, experts))
     if lm_head and LM_HEAD_SCALE_KEY not in out:
         raise ValueError(f"{src}: lm_head=True but the checkpoint has no {LM_HEAD_KEY}")
     dst.mkdir(parents=True, exist_ok=True)
     save_file(out, str(dst / "consolidated.safetensors"))
-    params["quantization"] = {"qformat_weight": qformat, **({"lm_head": True} if lm_head else {})}
+    params["quantization"] = {"qformat_weight": qformat, **({"lm_head": True} if lm_head else {}), **({"experts": True} if experts else {})}
     with open(dst / "params.json", "w") as f:
         json.dump(params, f)
     return dst

@@ -106,6 +106,8 @@ class HipStackBackend:
         self._quant: Optional[Tuple[Any, Any, Any, str]] = None
         # ... whose LM head is quantised too: its mi_lm_head_quant_t (the forwards then go through mi_forward_q)
         self._head: Optional[Any] = None
+        # ... or a MoE model with FP8 experts: its mi_moe_w8_layer_t table (every forward then goes through mi_forward_moe_w8)
+        self._moe_q: Optional[Any] = None
 
     # -- one-time: pointer tables of the weights -------------------------------------------------
     def _build_plan(self, model: "Transformer"):
@@ -129,6 +131,7 @@ class HipStackBackend:
         self.dtype_code = _hip.DTYPE_CODES[dt]
         keep = []  # python objects that own memory referenced by raw pointers
         self._head = None
+        self._moe_q = None
         p = lambda t, d=dt: _hip.dev_ptr(t, d)  # noqa: E731
         qf = quantized_linear_cls(a.quantization).hip if a.quantization is not None else None
         if qf is not None:
@@ -140,6 +143,8 @@ class HipStackBackend:
         scales = (qf.layer_t * max(1, model.n_local_layers))() if qf is not None else None
         wp = (lambda mod: _hip.dev_ptr(mod.weight, torch.uint8)) if qf is not None else (lambda mod: p(mod.weight))
         E = a.moe.num_experts if a.moe is not None else 0
+        # FP8 experts: the experts' tables point to e4m3 bytes, their row scales ride in a second device table per layer
+        moe_q = (_hip.MiMoeW8Layer * max(1, model.n_local_layers))() if (qf is not None and E) else None
         layers = (_hip.MiLayer * max(1, model.n_local_layers))()
         adapters = (_hip.MiLoraLayer * max(1, model.n_local_layers))() if a.lora is not None else None
         keep.append(adapters)
@@ -164,7 +169,16 @@ class HipStackBackend:
                 L.gate = p(ff.gate.weight)
                 ptrs = []
                 for ex in ff.experts:
-                    ptrs += [p(ex.w1.weight), p(ex.w2.weight), p(ex.w3.weight)]
+                    ptrs += [wp(ex.w1), wp(ex.w2), wp(ex.w3)]
+                if moe_q is not None:
+                    for ex in ff.experts:
+                        for name, mod in (("w1", ex.w1), ("w2", ex.w2), ("w3", ex.w3)):
+                            assert isinstance(mod, QuantLinear) and mod.hip is qf
+                            mod.check_bound(name)
+                    stab = torch.tensor([_hip.dev_ptr(mod.qscale_weight, qf.scale_dtype) for ex in ff.experts for mod in (ex.w1, ex.w2, ex.w3)],
+                                        dtype=torch.int64, device=dev)
+                    keep.append(stab)
+                    moe_q[j].expert_scale_dev = stab.data_ptr()
                 host = _hip.ptr_array(ptrs)
                 devtab = torch.tensor(ptrs, dtype=torch.int64, device=dev)
                 keep += [host, devtab]
@@ -174,7 +188,8 @@ class HipStackBackend:
                 ff = blk.feed_forward
                 L.w1, L.w2, L.w3 = wp(ff.w1), wp(ff.w2), wp(ff.w3)
             if scales is not None:
-                for name, mod in (("wq", at.wq), ("wk", at.wk), ("wv", at.wv), ("wo", at.wo), ("w1", ff.w1), ("w2", ff.w2), ("w3", ff.w3)):
+                dense_ffn = () if E else (("w1", ff.w1), ("w2", ff.w2), ("w3", ff.w3))
+                for name, mod in (("wq", at.wq), ("wk", at.wk), ("wv", at.wv), ("wo", at.wo)) + dense_ffn:
                     assert isinstance(mod, QuantLinear) and mod.hip is qf
                     mod.check_bound(name)
                     setattr(scales[j], name, _hip.dev_ptr(mod.qscale_weight, qf.scale_dtype))
@@ -207,6 +222,8 @@ class HipStackBackend:
             fwd = "mi_forward_" + qf.suffix
             self._quant = (qm, getattr(_hip.lib(), "mi_workspace_bytes_" + qf.suffix), getattr(_hip.lib(), fwd), fwd)
             keep.append(scales)
+            if moe_q is not None:
+                self._moe_q = moe_q
         return m, keep
 
     @property
@@ -241,6 +258,7 @@ class HipStackBackend:
         self._plan = None
         self._quant = None
         self._head = None
+        self._moe_q = None
         self._workspace = None
 
     def raise_if_flagged(self) -> None:
@@ -298,7 +316,10 @@ class HipStackBackend:
         return (C.byref(qm) if isinstance(qm, _hip.MiW8Model) else None, C.byref(qm) if isinstance(qm, _hip.MiW4Model) else None)
 
     def _get_workspace(self, model: "Transformer", m, T: int, B: int, max_w: int, kv_layout: int = 0, verify: bool = False) -> torch.Tensor:
-        if self._head is not None:  # a quantised LM head: the one query beside the one entry (+ the head's slice at T > 8)
+        if self._moe_q is not None:  # FP8 experts: the one query beside the one entry (+ the experts' bf16 images at T > 8)
+            need = _hip.lib().mi_workspace_bytes_moe_w8(C.byref(m), C.byref(self._quant[0]), self._moe_q,
+                                                        C.byref(self._head) if self._head is not None else None, T, B, max_w, kv_layout)
+        elif self._head is not None:  # a quantised LM head: the one query beside the one entry (+ the head's slice at T > 8)
             w8, w4 = self._quant_refs()
             need = _hip.lib().mi_workspace_bytes_q(C.byref(m), w8, w4, C.byref(self._head), T, B, max_w, kv_layout,
                                                    int(model.prefill_fp8 or model.prefill_w4a8), int(verify))
@@ -374,7 +395,12 @@ class HipStackBackend:
             vo = _hip.MiVerifyOut()
             vo.tokens, vo.logprobs = _hip.dev_ptr(verify[0], torch.long), _hip.dev_ptr(verify[1], torch.float32)
             vo.n_accept = _hip.dev_ptr(verify[2], i32)
-        if self._head is not None:  # a quantised LM head: every forward of the model - prefill, decode and verify steps - is this entry
+        if self._moe_q is not None:  # FP8 experts: every forward is this entry (it refuses a verify step and prefill_fp8 by name)
+            _hip.check(_hip.lib().mi_forward_moe_w8(C.byref(m), C.byref(self._quant[0]), self._moe_q,
+                                                    C.byref(self._head) if self._head is not None else None, C.byref(bt),
+                                                    C.byref(vo) if vo is not None else None, int(model.prefill_fp8),
+                                                    _hip.stream_ptr(h.device)), "mi_forward_moe_w8")
+        elif self._head is not None:  # a quantised LM head: every forward of the model - prefill, decode and verify steps - is this entry
             w8, w4 = self._quant_refs()
             _hip.check(_hip.lib().mi_forward_q(C.byref(m), w8, w4, C.byref(self._head), C.byref(bt), C.byref(vo) if vo is not None else None,
                                                int(model.prefill_fp8 or model.prefill_w4a8), _hip.stream_ptr(h.device)), "mi_forward_q")
@@ -670,6 +696,8 @@ class Transformer(ModelBase):
                                       f"({self.dtype}) is not implemented; load the model in bfloat16")
         if self.args.lora is not None:
             raise NotImplementedError("speculative decoding with un-merged LoRA is not implemented; merge the adapter into the weights")
+        if getattr(getattr(self.args, "quantization", None), "experts", False):
+            raise NotImplementedError("speculative decoding on a MoE model with FP8 experts is not implemented (mi_forward_moe_w8 refuses a verify step)")
         if model_only:
             return
         if cache is None:
@@ -988,7 +1016,8 @@ class Transformer(ModelBase):
     def from_folder(folder: Union[Path, str], max_batch_size: int = 1, num_pipeline_ranks: int = 1,
                     device: Union[torch.device, str] = "cuda", dtype: Optional[torch.dtype] = None,
                     softmax_fp32: bool = True, backend: Optional[Any] = None, quantize: Optional[str] = None,
-                    prefill_fp8: bool = False, prefill_w4a8: bool = False, quantize_lm_head: bool = False) -> "Transformer":
+                    prefill_fp8: bool = False, prefill_w4a8: bool = False, quantize_lm_head: bool = False,
+                    quantize_experts: bool = False) -> "Transformer":
         """params.json + exactly one of consolidated.00.pth / consolidated.safetensors (reference
         transformer.py:297-338).  With safetensors only this rank's tensors are read, straight to `device`
         (the reference loads the whole file to the host on every rank).
@@ -1003,7 +1032,11 @@ class Transformer(ModelBase):
 
         quantize_lm_head=True (opt-in, with a weight format only): the LM head is quantised in the layers' format too while it
         loads - `model.output` becomes the format's QuantLinear - unless the folder's `quantization.lm_head` says it already is.
-        Ranks that hold no head ignore it."""
+        Ranks that hold no head ignore it.
+
+        quantize_experts=True (opt-in, a MoE folder with quantize="fp8_e4m3", or one whose `quantization.experts` says it already
+        is): the three linears of every expert are quantised too (quant.py "FP8 experts").  Without it a MoE model with a weight
+        format stays refused; on a dense model, with "mxfp4" or with fp16 / fp32 storage it is refused by name."""
         folder = Path(folder)
         check_quantize_arg(quantize)
         with open(folder / "params.json", "r") as f:
@@ -1013,7 +1046,11 @@ class Transformer(ModelBase):
             refuse_lora_storage(dtype)   # before anything is read from disk
         on_load = quantize is not None and model_args.quantization is None  # (an already quantised folder loads as it is)
         if on_load:
-            model_args.quantization = QuantizationArgs(quantize)
+            model_args.quantization = QuantizationArgs(quantize, experts=quantize_experts)
+        elif quantize_experts and (model_args.quantization is None or not model_args.quantization.experts):
+            raise NotImplementedError("quantize_experts=True needs quantize=\"fp8_e4m3\" on a bf16 MoE folder (or a folder whose "
+                                      "quantization block says \"experts\": true): the experts are quantised in the layers' format")
+        experts_on_load = on_load and quantize_experts
         refuse_lm_head_arg(quantize_lm_head, model_args.quantization)
         # the head is quantised while it loads when it was asked for and the folder has not done it
         head_on_load = quantize_lm_head and not model_args.quantization.lm_head
@@ -1052,7 +1089,7 @@ class Transformer(ModelBase):
                     raise ValueError(f"Unexpected key {k} (per-tensor activation scales: FP8 activations are not implemented)")
                 if k in wanted or k in plain:
                     if on_load:  # one tensor at a time: a linear becomes its e4m3 bytes and row scales, the rest passes
-                        loaded.update(quantize_state_tensor(k, f.get_tensor(k), quantize, head_on_load))
+                        loaded.update(quantize_state_tensor(k, f.get_tensor(k), quantize, head_on_load, experts_on_load))
                     elif head_on_load and k == LM_HEAD_KEY:  # a quantised folder with a bf16 head: the head alone, in the folder's format
                         loaded.update(quantize_state_tensor(k, f.get_tensor(k), model_args.quantization.qformat_weight, True))
                     else:

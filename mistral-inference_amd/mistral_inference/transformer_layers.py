@@ -145,7 +145,7 @@ class TransformerBlock(nn.Module):
                  quantization: Optional[QuantizationArgs] = None):
         super().__init__()
         _no_lora(lora, moe)
-        if quantization is not None and moe is not None:
+        if quantization is not None and moe is not None and not quantization.experts:  # (FP8 experts are opt-in)
             raise NotImplementedError(refusal("moe", quantization))
         self.n_heads = n_heads
         self.dim = dim
@@ -156,7 +156,7 @@ class TransformerBlock(nn.Module):
         self.feed_forward: nn.Module
         if moe is not None:
             self.feed_forward = MoeLayer(
-                experts=[FeedForward(dim=dim, hidden_dim=hidden_dim, lora=lora) for _ in range(moe.num_experts)],
+                experts=[FeedForward(dim=dim, hidden_dim=hidden_dim, lora=lora, quantization=quantization) for _ in range(moe.num_experts)],
                 gate=nn.Linear(dim, moe.num_experts, bias=False), moe_args=moe)
         else:
             self.feed_forward = FeedForward(dim=dim, hidden_dim=hidden_dim, lora=lora, quantization=quantization)
