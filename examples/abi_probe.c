@@ -42,6 +42,8 @@ int main(int argc, char** argv) {
       return 3;
     }
   printf("sampled verify steps (mi_verify_sample): %s\n", dlsym(h, "mi_verify_sample") ? "yes" : "no"); /* additive: presence is the feature test */
+  printf("FP8 experts on token-grouped W8A8 prefill GEMMs (mi_forward_moe_w8a8, mi_moe_grouped_gemm_w8a8): %s\n",
+         dlsym(h, "mi_forward_moe_w8a8") && dlsym(h, "mi_moe_grouped_gemm_w8a8") ? "yes" : "no"); /* additive likewise */
   if (abi() != MI_ABI_VERSION) {
     fprintf(stderr, "ABI %d, header %d\n", abi(), MI_ABI_VERSION);
     return 4;

@@ -738,6 +738,36 @@ int mi_forward_moe_w8(const mi_model_t* model, const mi_w8_model_t* w8, const mi
                       const mi_lm_head_quant_t* head, const mi_batch_t* batch, const mi_verify_out_t* verify_out, int a8,
                       mi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * FP8 experts on token-grouped W8A8 prefill GEMMs: opt-in, additive to ABI v9 (the presence of these symbols is the feature test;
+ * mi_forward_moe_w8 keeps refusing a8 != 0 and mi_workspace_bytes_moe_w8 keeps its figure).  At T >= 256, D % 128 == 0,
+ * F % 128 == 0 and D, F <= 16384 the MoE FFN of a prefill runs WITHOUT bf16 images of the experts: the normed rows x [T, D] are
+ * quantised once per token and hid once per compact row r (a (token, slot) pair, sorted by expert e) by the rule of
+ * mi_act_quant_e4m3 (mistral_inference.quant.quantize_rows), and two token-grouped launches contract e4m3 x e4m3 on the expert
+ * bytes as they are (csrc/gemm256_moe_w8a8.hip, always 256-row tiles):
+ *   hid[r, f] = swiglu_bf16( (sum_k xq[tok(r), k] w1q[e][f, k]) * (s_x[tok(r)] * s1[e][f]),  same with w3q, s3 )
+ *   y[r, d]   = bf16( (sum_f hq[r, f] w2q[e][d, f]) * (s_h[r] * s2[e][d]) )        then the combine of mi_moe_grouped_gemm
+ * (sums in fp32; the product of the two scales is formed first).  Outside that predicate - 8 < T < 256 or other dims - the route is
+ * mi_moe_grouped_gemm_w8's dequantisation route, launch for launch, and T <= 8 the GEMV route: never a new error.
+ * Scratch of the leaf: mi_moe_grouped_gemm's, then x_q [T, D], s_x [T], h_q [T * top_k, F], s_h [T * top_k] - no pointer table, no
+ * images (outside the predicate: mi_moe_grouped_gemm_w8_scratch_bytes).  Checks: those of mi_moe_grouped_gemm_w8, and x 16-byte
+ * aligned.  Every expert matrix must be 16-byte aligned too (a DMA fetches 16 aligned bytes of a row): the leaf's tables are in
+ * device memory, so that is the caller's duty there; mi_forward_moe_w8a8 checks it on the layers' host tables (MI_ERR_ARG).
+ * ---------------------------------------------------------------------------------------------- */
+size_t mi_moe_grouped_gemm_w8a8_scratch_bytes(int T, int D, int F, int E, int top_k);
+int mi_moe_grouped_gemm_w8a8(void* out, const void* residual, const void* x, int ldx, int T, int D, int F, int E, int top_k,
+                             const void* const* expert_w_dev, const float* const* expert_scale_dev, const int32_t* sel_idx,
+                             const float* sel_w, void* scratch, size_t scratch_bytes, mi_stream_t stream);
+/* mi_forward_moe_w8 with the FP8-activation GEMMs wherever a forward of 256 rows or more has one: the attention linears as
+ * mi_forward_w8a8 runs them (csrc/gemm256_w8a8.hip), the MoE branch as above.  Below 256 rows it is mi_forward_moe_w8 launch for
+ * launch.  There is no verify_out parameter: a verify step cannot reach it.  MXFP4, un-merged LoRA, a dense model and NULL tables
+ * are refused as in mi_forward_moe_w8.  Workspace: mi_workspace_bytes_moe_w8a8 - at a T of the route, mi_workspace_bytes_q's a8
+ * figure plus h_q | s_h (T * top_k * (F + 4) bytes) and NO image block; else mi_workspace_bytes_moe_w8's figure plus x_q | s_x. */
+size_t mi_workspace_bytes_moe_w8a8(const mi_model_t* model, const mi_w8_model_t* w8, const mi_moe_w8_layer_t* experts,
+                                   const mi_lm_head_quant_t* head, int T, int B, int max_cache_size, int kv_layout);
+int mi_forward_moe_w8a8(const mi_model_t* model, const mi_w8_model_t* w8, const mi_moe_w8_layer_t* experts,
+                        const mi_lm_head_quant_t* head, const mi_batch_t* batch, mi_stream_t stream);
+
 size_t mi_workspace_bytes_generic(const mi_model_t* model, int T, int dtype);
 int mi_forward_generic(const mi_model_t* model, const mi_batch_t* batch, int dtype, mi_stream_t stream);
 /* Leaf operators in any storage dtype - what module-level callers of an fp16 / fp32 model bind (the Pixtral tower of

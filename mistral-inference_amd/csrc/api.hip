@@ -103,6 +103,8 @@ struct Workspace {
                      //     lm_head_slice_rows(vocab) dequantised vocabulary rows
   bf16_t* moe_deq;   // FP8 experts at T > 8 (mi_forward_moe_w8 only, behind everything else): the bf16 images of one projection family
   const void** moe_tab;  //     of every expert (moe_deq_bytes: the larger family, W1|W3) and the pointer table [E][3] over them
+  uint8_t* moe_hq;   // FP8 experts on the token-grouped W8A8 GEMMs (mi_forward_moe_w8a8 at a T of that route only, IN PLACE of the two
+  float* moe_sh;     //     above): the e4m3 rows of hid [T * top_k, F] and their scales [T * top_k]; xn's rows and scales are x_q | s_x
   size_t total;
 };
 
@@ -139,6 +141,7 @@ size_t verify_stash_bytes(const mi_model_t* m, int T) { return (size_t)m->n_laye
 // qhead: the LM head is quantised (mi_forward_q) - the slice of its bf16 image at T > 8
 Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool quant = false, bool kv8 = false, bool verify = false,
                 bool a8 = false, bool qhead = false, bool qmoe = false) {
+  // (a8 with qmoe: the entry is mi_forward_moe_w8a8)
   Workspace w;
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -192,9 +195,12 @@ Workspace carve(const mi_model_t* m, int T, int B, int maxW, char* base, bool qu
   // (any other forward: layout and total as ever)
   w.head_deq = (qhead && T > GEMV_MAX_T) ? (bf16_t*)take(lm_head_slice_bytes(m->vocab_size, m->dim)) : nullptr;
   // (any other forward: layout and total as ever)
-  const bool moe_img = qmoe && m->num_experts > 0 && T > GEMV_MAX_T;
+  const bool moe_a8 = qmoe && a8 && m->num_experts > 0 && gemm256_moe_w8a8_applicable(T, m->dim, m->hidden_dim);
+  const bool moe_img = qmoe && m->num_experts > 0 && T > GEMV_MAX_T && !moe_a8;
   w.moe_tab = moe_img ? (const void**)take(MOE_TAB_BYTES) : nullptr;
   w.moe_deq = moe_img ? (bf16_t*)take(moe_deq_bytes(m->num_experts, m->dim, m->hidden_dim)) : nullptr;
+  w.moe_hq = moe_a8 ? (uint8_t*)take((size_t)T * slots * m->hidden_dim) : nullptr;
+  w.moe_sh = moe_a8 ? (float*)take((size_t)T * slots * sizeof(float)) : nullptr;
   w.total = off;
   return w;
 }
@@ -435,6 +441,39 @@ int moe_grouped(void* out, const void* residual, const void* x, int T, int D, in
   g.expert_tab = gemm_tab; g.w_sel0 = 1; g.w_sel1 = -1;
   if (q8) MI_TRY(images(1));
   MI_TRY(hip_rc(launch_gemm(g, s), "moe w2 grouped gemm"));
+  return hip_rc(launch_moe_combine(out, residual, w.y, sel_idx, sel_w, w.row_of, T, D, k, s), "moe combine");
+}
+
+// ---- ... on FP8 experts WITHOUT images (opt-in: mi_moe_grouped_gemm_w8a8, mi_forward_moe_w8a8; gemm256_moe_w8a8_applicable holds):
+// x is quantised once per token, the W1|W3 launch gathers those e4m3 rows per compact row, hid is quantised per compact row, and
+// both launches contract e4m3 x e4m3 on the expert bytes as they are (gemm256_moe_w8a8.hip).  Always 256-row tiles.
+struct MoeA8Scratch {
+  uint8_t* x_q;  // [T, D]
+  float* s_x;    // [T]
+  uint8_t* h_q;  // [T * top_k, F]
+  float* s_h;    // [T * top_k]
+};
+int moe_grouped_w8a8(void* out, const void* residual, const void* x, int T, int D, int F, int E, int k, const void* const* expert_tab,
+                     const float* const* scale_tab, const int32_t* sel_idx, const float* sel_w, const MoeScratch& w, const MoeA8Scratch& q,
+                     hipStream_t s) {
+  const int max_m_tiles = (T * k + 255) / 256 + E;  // <= the scratch's max_tiles (sized for 128-row tiles)
+  MI_TRY(hip_rc(launch_moe_lists(sel_idx, T, E, k, w.tok_of, w.row_of, w.tile_tab, w.n_tiles, 256, s), "moe_lists"));
+  MI_TRY(hip_rc(launch_act_quant_e4m3(q.x_q, q.s_x, x, D, T, D, nullptr, 0.f, s), "act_quant_e4m3 (moe x)"));
+  GemmMoeW8A8Args a;
+  memset(&a, 0, sizeof(a));
+  GemmArgs& g = a.g;
+  g.epi = GEMM_SWIGLU; g.M = T * k; g.N = F; g.K = D; g.a = (const bf16_t*)q.x_q; g.lda = D; g.n0 = g.n1 = F;
+  g.out = w.hid; g.ldo = F;
+  g.tile_tab = w.tile_tab; g.n_tiles_ptr = w.n_tiles; g.max_m_tiles = max_m_tiles; g.tile_rows = 256;
+  g.expert_tab = expert_tab; g.w_sel0 = 0; g.w_sel1 = 2; g.a_gather = w.tok_of;
+  a.sx = q.s_x; a.scale_tab = scale_tab;
+  MI_TRY(hip_rc(launch_gemm256_moe_w8a8(a, s), "moe w13 grouped gemm (w8a8)"));
+  MI_TRY(hip_rc(launch_act_quant_e4m3(q.h_q, q.s_h, w.hid, F, T * k, F, nullptr, 0.f, s), "act_quant_e4m3 (moe hid)"));
+  g.epi = GEMM_STORE; g.N = D; g.K = F; g.a = (const bf16_t*)q.h_q; g.lda = F; g.n0 = g.n1 = D;
+  g.out = w.y; g.ldo = D;
+  g.w_sel0 = 1; g.w_sel1 = -1; g.a_gather = nullptr;
+  a.sx = q.s_h;
+  MI_TRY(hip_rc(launch_gemm256_moe_w8a8(a, s), "moe w2 grouped gemm (w8a8)"));
   return hip_rc(launch_moe_combine(out, residual, w.y, sel_idx, sel_w, w.row_of, T, D, k, s), "moe combine");
 }
 
@@ -988,6 +1027,8 @@ int mi_lora_linear_slots(void* out, int ldo, const void* x, int ldx, int M, int 
 
 namespace {
 constexpr int LOGPROB_ROW_CHUNK = 128;  // rows per pass of the unfused route (bounds its scratch)
+// (the order and alignment of hid | y | tok_of | row_of are mirrored by _hip.moe_grouped_w8a8(debug=True), which reads them back
+// for the tests: change both together)
 MoeScratch moe_carve(int T, int D, int F, int E, int top_k, char* base) {
   MoeScratch w;
   size_t off = 0;
@@ -1435,6 +1476,49 @@ int mi_moe_grouped_gemm_w8(void* out, const void* residual, const void* x, int l
   return moe_grouped(out, residual, x, T, D, F, E, top_k, expert_w_dev, sel_idx, sel_w, w, (hipStream_t)stream, &img);
 }
 
+// the bf16 leaf's scratch, then x_q | s_x | h_q | s_h: no pointer table, no images
+static MoeA8Scratch moe_a8_carve(const MoeScratch& w, int T, int D, int F, int top_k, char* base, size_t* total) {
+  size_t off = align_up(w.total);
+  auto take = [&](size_t bytes) {
+    char* p = base ? base + off : nullptr;
+    off += align_up(bytes);
+    return p;
+  };
+  MoeA8Scratch q;
+  q.x_q = (uint8_t*)take((size_t)T * D);
+  q.s_x = (float*)take((size_t)T * sizeof(float));
+  q.h_q = (uint8_t*)take((size_t)T * top_k * F);
+  q.s_h = (float*)take((size_t)T * top_k * sizeof(float));
+  *total = off;
+  return q;
+}
+
+size_t mi_moe_grouped_gemm_w8a8_scratch_bytes(int T, int D, int F, int E, int top_k) {
+  if (T <= 0 || D <= 0 || F <= 0 || E <= 0 || top_k <= 0) return 0;
+  if (!gemm256_moe_w8a8_applicable(T, D, F)) return mi_moe_grouped_gemm_w8_scratch_bytes(T, D, F, E, top_k);
+  size_t total = 0;
+  moe_a8_carve(moe_carve(T, D, F, E, top_k, nullptr), T, D, F, top_k, nullptr, &total);
+  return total;
+}
+
+int mi_moe_grouped_gemm_w8a8(void* out, const void* residual, const void* x, int ldx, int T, int D, int F, int E, int top_k,
+                             const void* const* expert_w_dev, const float* const* expert_scale_dev, const int32_t* sel_idx,
+                             const float* sel_w, void* scratch, size_t scratch_bytes, mi_stream_t stream) {
+  if (!gemm256_moe_w8a8_applicable(T, D, F))  // the dequantisation route, launch for launch (its own checks and names)
+    return mi_moe_grouped_gemm_w8(out, residual, x, ldx, T, D, F, E, top_k, expert_w_dev, expert_scale_dev, sel_idx, sel_w, scratch,
+                                  scratch_bytes, stream);
+  if (!out || !residual || !x || !sel_idx || !sel_w || !scratch || ldx != D)
+    return fail(MI_ERR_ARG, "mi_moe_grouped_gemm_w8a8 (x must be dense [T, D])");
+  MI_TRY(check_moe_w8_args("mi_moe_grouped_gemm_w8a8", expert_w_dev, expert_scale_dev, D, F, top_k));
+  if (E > 16 || top_k > E || E < 1) return fail(MI_ERR_SHAPE, "MoE: E <= 16, top_k <= 4");
+  if (reinterpret_cast<size_t>(x) & 15) return fail(MI_ERR_ARG, "mi_moe_grouped_gemm_w8a8: x must be 16-byte aligned");
+  const MoeScratch w = moe_carve(T, D, F, E, top_k, (char*)scratch);
+  size_t total = 0;
+  const MoeA8Scratch q = moe_a8_carve(w, T, D, F, top_k, (char*)scratch, &total);
+  if (total > scratch_bytes) return fail(MI_ERR_WORKSPACE, "mi_moe_grouped_gemm_w8a8: scratch %zu < required %zu", scratch_bytes, total);
+  return moe_grouped_w8a8(out, residual, x, T, D, F, E, top_k, expert_w_dev, expert_scale_dev, sel_idx, sel_w, w, q, (hipStream_t)stream);
+}
+
 int mi_set_decode_engine(int enabled) {
   const int prev = engine_mode();
   g_engine_mode = enabled != 0;
@@ -1778,8 +1862,13 @@ static int forward_body(const char* entry, const mi_model_t* m, const QuantModel
           MI_TRY(hip_rc(launch_rmsnorm(ws.xn, h, L.ffn_norm, T, D, m->norm_eps, s), "ffn_norm"));
           MI_TRY(hip_rc(launch_moe_router(ws.sel_idx, ws.sel_w, ws.xn, D, T, D, L.gate, E, k, nullptr, 0.f, s), "moe_router"));
           const MoeScratch sc = {ws.hid, ws.moe_y, ws.tok_of, ws.row_of, ws.tile_tab, ws.n_tiles, ws.max_tiles, 0};
-          const MoeW8Images img = {st, ws.moe_deq, ws.moe_tab};
-          MI_TRY(moe_grouped(h, h, ws.xn, T, D, F, E, k, L.expert_w_dev, ws.sel_idx, ws.sel_w, sc, s, &img));
+          if (ws.moe_hq) {  // mi_forward_moe_w8a8 at a T of the token-grouped W8A8 route: no images
+            const MoeA8Scratch qa = {ws.x_q, ws.s_x, ws.moe_hq, ws.moe_sh};
+            MI_TRY(moe_grouped_w8a8(h, h, ws.xn, T, D, F, E, k, L.expert_w_dev, st, ws.sel_idx, ws.sel_w, sc, qa, s));
+          } else {
+            const MoeW8Images img = {st, ws.moe_deq, ws.moe_tab};
+            MI_TRY(moe_grouped(h, h, ws.xn, T, D, F, E, k, L.expert_w_dev, ws.sel_idx, ws.sel_w, sc, s, &img));
+          }
         }
       } else if (gemv) {
         MI_TRY(hip_rc(launch_moe_router(ws.sel_idx, ws.sel_w, h, D, T, D, L.gate, E, k, L.ffn_norm, m->norm_eps, s), "moe_router"));
@@ -1930,6 +2019,33 @@ int mi_forward_moe_w8(const mi_model_t* m, const mi_w8_model_t* w8, const mi_moe
   q.head = head;
   q.moe = experts;
   return forward_body(me, m, &q, bt, stream);
+}
+
+/* ... with the FP8-activation GEMMs everywhere a prefill of 256 rows or more has one: the attention linears on gemm256_w8a8, the
+ * experts on gemm256_moe_w8a8 (include/mistral_hip.h) */
+size_t mi_workspace_bytes_moe_w8a8(const mi_model_t* model, const mi_w8_model_t* w8, const mi_moe_w8_layer_t* experts,
+                                   const mi_lm_head_quant_t* head, int T, int B, int max_cache_size, int kv_layout) {
+  if (!model || !w8 || !experts || T <= 0 || B <= 0 || !kv_layout_ok(kv_layout)) return 0;
+  return carve(model, T, B, max_cache_size > 0 ? max_cache_size : 1, nullptr, true, kv_e4m3(kv_layout), false, true, head != nullptr, true).total;
+}
+
+int mi_forward_moe_w8a8(const mi_model_t* m, const mi_w8_model_t* w8, const mi_moe_w8_layer_t* experts, const mi_lm_head_quant_t* head,
+                        const mi_batch_t* bt, mi_stream_t stream) {
+  const char* me = "mi_forward_moe_w8a8";
+  MI_TRY(check_moe_w8_entry(me, m, w8, experts));
+  if (m->lora_rank > 0)
+    return fail(MI_ERR_UNSUPPORTED, "%s: un-merged LoRA on an FP8 base is not implemented; merge the adapter before quantising", me);
+  if (m->dim % 16 || m->hidden_dim % 16)
+    return fail(MI_ERR_SHAPE, "%s: dim and hidden_dim must be multiples of 16 (a 16-byte piece is 16 e4m3 weights)", me);
+  // every DMA of the grouped GEMMs fetches 16 aligned bytes of an expert row: the host copy of a layer's table says whether it can
+  for (int l = 0; l < m->n_layers && m->layers; ++l)
+    for (int i = 0; m->layers[l].expert_w_host && i < m->num_experts * 3; ++i)
+      if (reinterpret_cast<size_t>(m->layers[l].expert_w_host[i]) & 15)
+        return fail(MI_ERR_ARG, "%s: layer %d, expert matrix %d.%d is not 16-byte aligned", me, l, i / 3, i % 3);
+  QuantModel q = quant_model(w8, nullptr);
+  q.head = head;
+  q.moe = experts;
+  return forward_body(me, m, &q, bt, stream, nullptr, true);
 }
 
 }  // extern "C"

@@ -186,6 +186,63 @@ __device__ __forceinline__ void k_loop(Ops& op, int nk, int wr) {
   if (STAGGER && wr == 0) raw_barrier();
 }
 
+// The operand policy of the two e4m3 x e4m3 kernels (gemm256_w8a8.hip and its token-grouped form gemm256_moe_w8a8.hip): 16-KiB
+// half tiles of 128 rows x 128 e4m3 bytes, two stages of A0 A1 B0 B1, one 16x16x128 MFMA per (row fragment, column fragment) and
+// K tile, format codes 0, 0 and both block scales 2^(127 - 127).  A kernel fills src[][] (its own addressing) and calls init().
+struct OpsE4m3 {
+  static constexpr int BK = 128;                      // bytes = e4m3 elements of K per tile
+  static constexpr int HALF_BYTES = 128 * BK;         // 16 KiB: 128 rows x 128 B
+  static constexpr int STAGE_BYTES = 4 * HALF_BYTES;  // A0 A1 B0 B1
+  static constexpr int LDS_BYTES = 2 * STAGE_BYTES;   // 128 KiB
+  static constexpr int dmas(int) { return 2; }
+  const char* src[4][2];  // [half][piece]
+  char* my_piece;         // this wave's two 1-KiB pieces inside any half tile of stage 0
+  const char* smem;
+  int a_off, b_off, sw0, sw1;  // fragment addressing
+  f32x4 acc[2][2][4][2];
+  i32x8 af[4];     // [row fragment] of the A half in use
+  i32x8 bf[2][2];  // [B half][column fragment]
+
+  // fragment addressing: lane holds row lane & 15, bytes 32 * (lane >> 4) .. + 32 = the 16-byte slots 2 fq and 2 fq + 1
+  __device__ __forceinline__ void init(char* lds, int wid, int wr, int wc, int lane) {
+    my_piece = lds + wid * 2048;
+    smem = lds;
+    const int fq = lane >> 4;
+    sw0 = ((2 * fq) ^ (lane & 7)) << 4;
+    sw1 = ((2 * fq + 1) ^ (lane & 7)) << 4;
+    a_off = (wr * 64 + (lane & 15)) * 128;
+    b_off = 2 * HALF_BYTES + (wc * 32 + (lane & 15)) * 128;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) acc[a][b][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  __device__ __forceinline__ void stage(int half, int kt, int st) {
+    char* dst = my_piece + st * STAGE_BYTES + half * HALF_BYTES;
+    dma16(src[half][0] + (size_t)kt * BK, dst);
+    dma16(src[half][1] + (size_t)kt * BK, dst + 1024);
+  }
+  __device__ __forceinline__ void read_a(int ha, int st) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) af[i] = frag32(smem + st * STAGE_BYTES + ha * HALF_BYTES + a_off + i * 2048, sw0, sw1);
+  }
+  __device__ __forceinline__ void read_b(int hb, int st) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) bf[hb][j] = frag32(smem + st * STAGE_BYTES + hb * HALF_BYTES + b_off + j * 2048, sw0, sw1);
+  }
+  __device__ __forceinline__ void mfma_quad(int ha, int hb) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        acc[ha][hb][i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(bf[hb][j], af[i], acc[ha][hb][i][j], 0, 0, 0, 127, 0, 127);
+  }
+};
+
 // ---------------------------------------------------------------------------------------------- the 16-bit-output epilogue
 // Scale policy: row(m) is loaded once per output row (ROW_LOAD: it is a load), apply<EPI>(acc, s_row, n, hb) gives what enters E::round / E::swiglu_fast
 // where the 16-bit kernels read acc (n: output column, clamped to N - 1; hb: SWIGLU's matrix, 0 = W1, 1 = W3).
@@ -211,6 +268,17 @@ struct ScaleRowCol {  // ... times one fp32 per weight row (W8A8): the product o
     const GemmArgs& g = a.g;
     const float s_col = EPI == GEMM_SWIGLU ? a.sw[hb][n] : n < g.n0 ? a.sw[0][n] : n < g.n1 ? a.sw[1][n - g.n0] : a.sw[2][n - g.n1];
     return acc * (s_row * s_col);
+  }
+};
+struct ScaleMoe {  // token-grouped W8A8: the activation row's scale (through the gather of the A rows) times the tile's expert's row scale
+  static constexpr bool ROW_LOAD = true;
+  const float* sx;
+  const int32_t* sx_gather;  // nullptr: sx[m]
+  const float* sw[2];        // of the tile's expert: [0] the matrix of w_sel0, [1] of w_sel1 (SWIGLU: W1, W3)
+  __device__ __forceinline__ float row(int m) const { return sx[sx_gather ? sx_gather[m] : m]; }
+  template <int EPI>
+  __device__ __forceinline__ float apply(float acc, float s_row, int n, int hb) const {
+    return acc * (s_row * sw[EPI == GEMM_SWIGLU ? hb : 0][n]);
   }
 };
 

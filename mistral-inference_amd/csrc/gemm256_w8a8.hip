@@ -16,7 +16,7 @@
 // four consecutive output columns, as the shared epilogue expects.
 //
 // Epilogues: GEMM_STORE (with the RoPE epilogue of q|k|v and up to three weight segments), GEMM_RESIDUAL, GEMM_SWIGLU.
-// No LM head, no token-grouped form, no half-height tail tile.
+// No LM head, no half-height tail tile; the token-grouped form (FP8 experts) is gemm256_moe_w8a8.hip.
 #include "gemm256_core.cuh"
 
 using E = Elem16<0>;  // outputs, residual and the RoPE / SwiGLU chains are bf16
@@ -24,10 +24,8 @@ using E = Elem16<0>;  // outputs, residual and the RoPE / SwiGLU chains are bf16
 namespace {
 using namespace gemm256_core;
 
-constexpr int BK = 128;                      // bytes = e4m3 elements of K per tile
-constexpr int HALF_BYTES = 128 * BK;         // 16 KiB: 128 rows x 128 B
-constexpr int STAGE_BYTES = 4 * HALF_BYTES;  // A0 A1 B0 B1
-constexpr int LDS_BYTES = 2 * STAGE_BYTES;   // 128 KiB
+using Ops = OpsE4m3;  // the e4m3 x e4m3 operand policy (gemm256_core.cuh)
+constexpr int BK = Ops::BK, LDS_BYTES = Ops::LDS_BYTES;
 
 // weight row r (bytes) of up to three matrices side by side
 __device__ __forceinline__ const char* seg_row8(const GemmArgs& g, int r) {
@@ -36,39 +34,6 @@ __device__ __forceinline__ const char* seg_row8(const GemmArgs& g, int r) {
   if (r < g.n1) return w1 + (size_t)(r - g.n0) * g.K;
   return w2 + (size_t)(r - g.n1) * g.K;
 }
-
-// The operands of gemm256_core::k_loop: e4m3 x e4m3 (format codes 0, 0), both block scales 2^(127 - 127)
-struct Ops {
-  static constexpr int dmas(int) { return 2; }
-  const char* src[4][2];  // [half][piece]
-  char* my_piece;         // this wave's two 1-KiB pieces inside any half tile of stage 0
-  const char* smem;
-  int a_off, b_off, sw0, sw1;  // fragment addressing
-  f32x4 acc[2][2][4][2];
-  i32x8 af[4];     // [row fragment] of the A half in use
-  i32x8 bf[2][2];  // [B half][column fragment]
-
-  __device__ __forceinline__ void stage(int half, int kt, int st) {
-    char* dst = my_piece + st * STAGE_BYTES + half * HALF_BYTES;
-    dma16(src[half][0] + (size_t)kt * BK, dst);
-    dma16(src[half][1] + (size_t)kt * BK, dst + 1024);
-  }
-  __device__ __forceinline__ void read_a(int ha, int st) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) af[i] = frag32(smem + st * STAGE_BYTES + ha * HALF_BYTES + a_off + i * 2048, sw0, sw1);
-  }
-  __device__ __forceinline__ void read_b(int hb, int st) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) bf[hb][j] = frag32(smem + st * STAGE_BYTES + hb * HALF_BYTES + b_off + j * 2048, sw0, sw1);
-  }
-  __device__ __forceinline__ void mfma_quad(int ha, int hb) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        acc[ha][hb][i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(bf[hb][j], af[i], acc[ha][hb][i][j], 0, 0, 0, 127, 0, 127);
-  }
-};
 
 template <int EPI>
 __global__ __launch_bounds__(512, 1) void gemm256_w8a8_kernel(GemmW8A8Args args) {
@@ -98,22 +63,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_w8a8_kernel(GemmW8A8Args args)
         op.src[2 + h][j] = seg_row8(g, n) + src_slot_bytes(lane);
       }
     }
-  op.my_piece = smem + wid * 2048;
-  op.smem = smem;
-  // ---- fragment addressing: lane holds row lane & 15, bytes 32 * (lane >> 4) .. + 32 = the 16-byte slots 2 fq and 2 fq + 1
-  const int fq = lane >> 4;
-  op.sw0 = ((2 * fq) ^ (lane & 7)) << 4;
-  op.sw1 = ((2 * fq + 1) ^ (lane & 7)) << 4;
-  op.a_off = (wr * 64 + (lane & 15)) * 128;
-  op.b_off = 2 * HALF_BYTES + (wc * 32 + (lane & 15)) * 128;
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) op.acc[a][b][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  op.init(smem, wid, wr, wc, lane);
 
   k_loop<true>(op, g.K / BK, wr);
   epilogue16<E, EPI, 2>(g, op.acc, ScaleRowCol{args}, row0, rows_valid, n_tile, wr, wc, lane);

@@ -199,6 +199,20 @@ typedef GemmA8Args<float> GemmW8A8Args;
 bool gemm256_w8a8_applicable(int M, int K);  // M >= 256 && K % 128 == 0 && K <= 16384 (the quantiser's limit): the route's one shape predicate
 hipError_t launch_gemm256_w8a8(const GemmW8A8Args& a, hipStream_t s);
 
+// gemm256_moe_w8a8.hip: the token-grouped form of gemm256_w8a8 (prefills of MoE models with FP8 experts, opt-in).  g is the
+// token-grouped GemmArgs of gemm256.hip with 256-row tiles (tile_tab, n_tiles_ptr, max_m_tiles, tile_rows = 256, w_sel0 / w_sel1);
+// g.a points to e4m3 bytes [*, K] (lda in bytes) read through g.a_gather where it is set, sx holds one fp32 per A row (indexed as
+// the A row is: through the gather), g.expert_tab [E][3] points to e4m3 bytes with rows of K bytes and scale_tab [E][3] to their
+// fp32 row scales (the device tables of GemvMoeW8Args).  Epilogues SWIGLU (w_sel0 = W1, w_sel1 = W3) / STORE (w_sel0).  GemmArgs
+// itself does not change.
+struct GemmMoeW8A8Args {
+  GemmArgs g;
+  const float* sx;
+  const float* const* scale_tab;
+};
+bool gemm256_moe_w8a8_applicable(int T, int D, int F);  // T >= 256, D and F multiples of 128 and <= 16384: the route's one shape predicate
+hipError_t launch_gemm256_moe_w8a8(const GemmMoeW8A8Args& a, hipStream_t s);
+
 // gemm256_w4a8.hip: the same on MXFP4 weights (MXFP4 models): e2m1 codes meet e4m3 activations on the mixed form of the
 // block-scaled MFMA, which applies the e8m0 block scales itself:
 // out = epilogue((sum_k A_q[m, k] * e2m1(C[n, k]) * 2^(S[n, k / 32] - 127)) * sx[m]).  g.w0 / g.w1 / g.w2 point to code bytes

@@ -6,6 +6,7 @@ device tensor, the call raises.  torch is used only to own device memory and the
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Callable, List, NamedTuple, Optional, Sequence
 
@@ -172,6 +173,14 @@ _SIGS = {
                                                C.c_int, C.c_int, C.c_int, C.c_int]),
     "mi_forward_moe_w8": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiW8Model), C.POINTER(MiMoeW8Layer), C.POINTER(MiLmHeadQuant),
                                     C.POINTER(MiBatch), C.POINTER(MiVerifyOut), C.c_int, _vp]),
+    # FP8 experts on token-grouped W8A8 prefill GEMMs (additive likewise, opt-in)
+    "mi_moe_grouped_gemm_w8a8_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mi_moe_grouped_gemm_w8a8": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp,
+                                           C.c_size_t, _vp]),
+    "mi_workspace_bytes_moe_w8a8": (C.c_size_t, [C.POINTER(MiModel), C.POINTER(MiW8Model), C.POINTER(MiMoeW8Layer),
+                                                 C.POINTER(MiLmHeadQuant), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mi_forward_moe_w8a8": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiW8Model), C.POINTER(MiMoeW8Layer), C.POINTER(MiLmHeadQuant),
+                                      C.POINTER(MiBatch), _vp]),
     "mi_workspace_bytes": (C.c_size_t, [C.POINTER(MiModel), C.c_int, C.c_int, C.c_int]),
     "mi_forward": (C.c_int, [C.POINTER(MiModel), C.POINTER(MiBatch), _vp]),
     # weight-only FP8 (additive to ABI v9: the presence of these symbols is the feature test)
@@ -975,6 +984,38 @@ def moe_experts(x: torch.Tensor, expert_tab: torch.Tensor, n_experts: int, hidde
                                 expert_tab.data_ptr(), dev_ptr(sel_idx, torch.int32), dev_ptr(sel_w, torch.float32),
                                 scratch.data_ptr(), need, st), "mi_moe_grouped_gemm")
     return out
+
+
+def moe_grouped_w8a8(x: torch.Tensor, expert_tab: torch.Tensor, scale_tab: torch.Tensor, n_experts: int, hidden_dim: int,
+                     sel_idx: torch.Tensor, sel_w: torch.Tensor, residual: Optional[torch.Tensor] = None, debug: bool = False):
+    """The prefill MoE FFN on FP8 experts through mi_moe_grouped_gemm_w8a8: at T >= 256 rows and dims that are multiples of 128 the
+    token-grouped W8A8 GEMMs (no bf16 images of the experts), else mi_moe_grouped_gemm_w8's route bit for bit.  Arguments as
+    `moe_experts` with scale_tab, x already normalised, any T > 8.
+    debug: also return views of the scratch the call left behind (the leading blocks are mi_moe_grouped_gemm's on either route):
+    hid [T * k, F] and y [T * k, D] in compact rows, tok_of [T * k], row_of [T, k]."""
+    T, D = x.shape
+    k = sel_idx.shape[1]
+    assert T > GEMV_MAX_T, "T <= 8 is the weight-streaming route (moe_experts)"
+    if residual is None:
+        residual = torch.zeros_like(x)
+    out = torch.empty_like(x)
+    xc = x if x.is_contiguous() else x.contiguous()
+    L = lib()
+    need = L.mi_moe_grouped_gemm_w8a8_scratch_bytes(T, D, hidden_dim, n_experts, k)
+    scratch = torch.empty(need, dtype=torch.uint8, device=x.device)
+    check(L.mi_moe_grouped_gemm_w8a8(dev_ptr(out), dev_ptr(residual), dev_ptr(xc), D, T, D, hidden_dim, n_experts, k,
+                                     expert_tab.data_ptr(), scale_tab.data_ptr(), dev_ptr(sel_idx, torch.int32),
+                                     dev_ptr(sel_w, torch.float32), scratch.data_ptr(), need, stream_ptr(x.device)),
+          "mi_moe_grouped_gemm_w8a8")
+    if not debug:
+        return out
+    off, views = 0, {}
+    for name, dt, shape in (("hid", torch.bfloat16, (T * k, hidden_dim)), ("y", torch.bfloat16, (T * k, D)),
+                            ("tok_of", torch.int32, (T * k,)), ("row_of", torch.int32, (T, k))):
+        n = math.prod(shape) * dt.itemsize
+        views[name] = scratch[off:off + n].view(dt).view(shape)
+        off += (n + 255) // 256 * 256  # (the first four blocks of csrc/api.hip moe_carve, which names this mirror)
+    return out, views
 
 
 def mamba_add_norm(residual: torch.Tensor, h: Optional[torch.Tensor], w: torch.Tensor, eps: float) -> torch.Tensor:

@@ -102,7 +102,8 @@ def pad_and_convert_to_tensor(list_of_lists: List[List[int]], pad_id: int) -> Li
 def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7, num_pipeline_ranks: int = 1,
                 instruct: bool = False, lora_path: Optional[str] = None, quantize: Optional[str] = None,
                 kv_dtype: Optional[str] = None, speculative: Optional[int] = None, prefill_fp8: bool = False,
-                prefill_w4a8: bool = False, quantize_lm_head: bool = False, quantize_experts: bool = False) -> None:
+                prefill_w4a8: bool = False, quantize_lm_head: bool = False, quantize_experts: bool = False,
+                prefill_fp8_experts: bool = False) -> None:
     """quantize="fp8_e4m3" / "mxfp4": quantise a bf16 checkpoint to weight-only FP8 / MXFP4 while it loads (a folder that
     quant.quantize_checkpoint wrote needs no flag).  kv_dtype="fp8_e4m3": K/V rings of e4m3 bytes (half the bytes; launch path).
     speculative=K: decoding that drafts up to K tokens per step by prompt lookup and verifies them in one pass over the
@@ -112,7 +113,9 @@ def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7,
     claim about model quality).  prefill_w4a8: the same for MXFP4 weights - the e2m1 codes meet the e4m3 activations on the mixed
     FP4 x FP8 MFMA, block scales applied by the instruction.  quantize_lm_head: the LM head is quantised in the weight format too
     (opt-in, a weight format only; no claim about model quality).  quantize_experts: a MoE model's expert linears are quantised too
-    (opt-in, quantize="fp8_e4m3" only; without it a MoE model with a weight format is refused)."""
+    (opt-in, quantize="fp8_e4m3" only; without it a MoE model with a weight format is refused).  prefill_fp8_experts: a MoE model with
+    FP8 experts only - prompt chunks of 256 tokens or more run the expert projections on the token-grouped FP8 MFMA GEMMs, without
+    bf16 images of the experts (quant.py; a speed and memory option, no claim about model quality)."""
     kv = kv_dtype_arg(kv_dtype)  # (an unknown name is refused before anything is loaded)
     spec = speculative_arg(speculative)
     if spec is not None and temperature > 0:  # (the tool's user asked for both: sampled verify steps)
@@ -124,13 +127,15 @@ def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7,
     model_cls = get_model_cls(model_path)
     if model_cls is Mamba:
         refuse_transformer_flags(lora_path=lora_path, quantize=quantize, kv_dtype=kv_dtype, speculative=speculative, prefill_fp8=prefill_fp8,
-                                 prefill_w4a8=prefill_w4a8, quantize_lm_head=quantize_lm_head, quantize_experts=quantize_experts)
+                                 prefill_w4a8=prefill_w4a8, quantize_lm_head=quantize_lm_head, quantize_experts=quantize_experts,
+                                 prefill_fp8_experts=prefill_fp8_experts)
         model = Mamba.from_folder(Path(model_path), max_batch_size=3, num_pipeline_ranks=num_pipeline_ranks, dtype=torch.bfloat16)
     else:
         model = model_cls.from_folder(Path(model_path), max_batch_size=3,
                                       num_pipeline_ranks=num_pipeline_ranks, dtype=torch.bfloat16, quantize=quantize,
                                       prefill_fp8=bool(prefill_fp8), prefill_w4a8=bool(prefill_w4a8),
-                                      quantize_lm_head=bool(quantize_lm_head), quantize_experts=bool(quantize_experts))
+                                      quantize_lm_head=bool(quantize_lm_head), quantize_experts=bool(quantize_experts),
+                                      prefill_fp8_experts=bool(prefill_fp8_experts))
     if lora_path is not None:  # reference main.py:131-132
         model.load_lora(Path(lora_path))
     messages: List = []
@@ -166,8 +171,9 @@ def interactive(model_path: str, max_tokens: int = 35, temperature: float = 0.7,
 
 def demo(model_path: str, max_tokens: int = 35, temperature: float = 0, lora_path: Optional[str] = None,
          quantize: Optional[str] = None, kv_dtype: Optional[str] = None, speculative: Optional[int] = None,
-         prefill_fp8: bool = False, prefill_w4a8: bool = False, quantize_lm_head: bool = False, quantize_experts: bool = False) -> None:
-    """quantize, kv_dtype, speculative, prefill_fp8, prefill_w4a8, quantize_lm_head, quantize_experts: as `interactive` (a speculative generation takes one prompt: the three run one by one)."""
+         prefill_fp8: bool = False, prefill_w4a8: bool = False, quantize_lm_head: bool = False, quantize_experts: bool = False,
+         prefill_fp8_experts: bool = False) -> None:
+    """quantize, kv_dtype, speculative, prefill_fp8, prefill_w4a8, quantize_lm_head, quantize_experts, prefill_fp8_experts: as `interactive` (a speculative generation takes one prompt: the three run one by one)."""
     kv = kv_dtype_arg(kv_dtype)
     spec = speculative_arg(speculative)
     if spec is not None and temperature > 0:  # (the tool's user asked for both: sampled verify steps)
@@ -177,13 +183,15 @@ def demo(model_path: str, max_tokens: int = 35, temperature: float = 0, lora_pat
     model_cls = get_model_cls(model_path)
     if model_cls is Mamba:
         refuse_transformer_flags(lora_path=lora_path, quantize=quantize, kv_dtype=kv_dtype, speculative=speculative, prefill_fp8=prefill_fp8,
-                                 prefill_w4a8=prefill_w4a8, quantize_lm_head=quantize_lm_head, quantize_experts=quantize_experts)
+                                 prefill_w4a8=prefill_w4a8, quantize_lm_head=quantize_lm_head, quantize_experts=quantize_experts,
+                                 prefill_fp8_experts=prefill_fp8_experts)
         model = Mamba.from_folder(Path(model_path), max_batch_size=3, num_pipeline_ranks=num_pipeline_ranks, dtype=torch.bfloat16)
     else:
         model = model_cls.from_folder(Path(model_path), max_batch_size=3,
                                       num_pipeline_ranks=num_pipeline_ranks, dtype=torch.bfloat16, quantize=quantize,
                                       prefill_fp8=bool(prefill_fp8), prefill_w4a8=bool(prefill_w4a8),
-                                      quantize_lm_head=bool(quantize_lm_head), quantize_experts=bool(quantize_experts))
+                                      quantize_lm_head=bool(quantize_lm_head), quantize_experts=bool(quantize_experts),
+                                      prefill_fp8_experts=bool(prefill_fp8_experts))
     if lora_path is not None:  # reference main.py:224-225
         model.load_lora(Path(lora_path))
     mistral_tokenizer = load_tokenizer(Path(model_path))

@@ -16,6 +16,8 @@ from .quant import QuantLinear, linear_quant
 
 
 class MoeLayer(nn.Module):
+    prefill_fp8_experts = False  # FP8 experts: Transformer.prefill_fp8_experts sets it (mi_moe_grouped_gemm_w8a8 above 8 rows)
+
     def __init__(self, experts: List[nn.Module], gate: nn.Module, moe_args: MoeArgs):
         super().__init__()
         assert len(experts) > 0
@@ -58,6 +60,8 @@ class MoeLayer(nn.Module):
         if not fused:
             return self._forward_general(inputs)
         idx, w = _hip.moe_router(inputs, self.gate.weight, k)          # [T, k] int32 / fp32 (bf16-valued)
+        if self.prefill_fp8_experts and T > _hip.GEMV_MAX_T and self._scale_table() is not None:
+            return _hip.moe_grouped_w8a8(inputs, self._expert_table(), self._scale_table(), E, F, idx, w)
         return _hip.moe_experts(inputs, self._expert_table(), E, F, idx, w, scale_tab=self._scale_table())
 
     def _forward_general(self, inputs: torch.Tensor) -> torch.Tensor:

@@ -20,6 +20,17 @@ experts' gate | up GEMV and the down-projection + ordered combine read the e4m3 
 moe_w2_w8_kernel), `y = bf16(scale[r] * acc)`; above, one dequantisation launch per projection family in front of the token-grouped
 GEMMs.  "mxfp4" experts, `prefill_fp8` and speculative verify steps on such a model are refused.  Nobody claims model quality.
 
+FP8 experts on token-grouped FP8 prefill GEMMs (`prefill_fp8_experts=True`, such a model only, opt-in): a forward of T >= 256 rows
+with dim and hidden_dim multiples of 128 (at most 16384) makes no bf16 image of any expert.  The normed rows are quantised once per
+token and `hid` once per (token, slot) row r, both by `quantize_rows` (the activation rule, as for `prefill_fp8`), and two
+token-grouped launches contract e4m3 with e4m3 on the expert bytes (csrc/gemm256_moe_w8a8.hip), e the expert of row r:
+
+    hid[r, f] = swiglu_bf16( (sum_k xq[tok(r), k] w1q[e][f, k]) * (s_x[tok(r)] * s1[e][f]),  same with w3q, s3 )
+    y[r, d]   = bf16( (sum_f hq[r, f] w2q[e][d, f]) * (s_h[r] * s2[e][d]) )        then the ordered combine as ever
+
+with the sums in fp32.  The attention linears of such a forward take the `prefill_fp8` route.  Shorter forwards and other dims take
+the routes above, bit for bit.  A coarser model than the weight-only one on real activations; nobody claims model quality.
+
 Checkpoint layout: `<linear>.weight` with dtype F8_E4M3, `<linear>.qscale_weight` fp32 [out] (a scalar or [1] is broadcast at
 load), `params.json` with `"quantization": {"qformat_weight": "fp8_e4m3"}`.  Compatibility is claimed only with checkpoints
 that `quantize_checkpoint` wrote.
@@ -95,6 +106,9 @@ _REFUSALS = {
     "pth": "{name} weight-only models load from consolidated.safetensors (a .pth checkpoint is not implemented)",
     "prefill_fp8": ("prefill_fp8=True on {what} is not implemented: the FP8 prefill GEMMs read FP8 (e4m3) weights beside bfloat16 "
                     "activations (quantize=\"fp8_e4m3\", or a folder that quantize_checkpoint wrote, with bfloat16 storage)"),
+    "prefill_fp8_experts": ("prefill_fp8_experts=True on {what} is not implemented: the token-grouped FP8 prefill GEMMs read FP8 "
+                            "(e4m3) expert weights beside bfloat16 activations (a MoE folder that quantize_checkpoint(..., "
+                            "experts=True) wrote, or quantize=\"fp8_e4m3\" with quantize_experts=True, with bfloat16 storage)"),
     "prefill_w4a8": ("prefill_w4a8=True on {what} is not implemented: the MXFP4 x FP8 prefill GEMMs read MXFP4 weights beside bfloat16 "
                      "activations (quantize=\"mxfp4\", or a folder that quantize_checkpoint wrote, with bfloat16 storage)"),
 }
@@ -145,6 +159,22 @@ def refuse_prefill_fp8(args, dtype: Optional[torch.dtype]) -> None:
     else:
         return
     raise NotImplementedError(_REFUSALS["prefill_fp8"].format(what=what))
+
+
+def refuse_prefill_fp8_experts(args, dtype: Optional[torch.dtype]) -> None:
+    """`prefill_fp8_experts=True` on anything but a MoE model with FP8 (e4m3) experts and bfloat16 storage, by name."""
+    qz = args.quantization
+    if qz is None:
+        what = "a model without FP8 weights" if dtype in (None, torch.bfloat16) else f"a model with {dtype} storage"
+    elif qz.qformat_weight != QFORMAT_FP8_E4M3:
+        what = f"{quantized_linear_cls(qz).name} weights"
+    elif dtype not in (None, torch.bfloat16):
+        what = f"{dtype} storage"
+    elif args.moe is None or not qz.experts:
+        what = "a dense model (it has no experts)"
+    else:
+        return
+    raise NotImplementedError(_REFUSALS["prefill_fp8_experts"].format(what=what))
 
 
 def refuse_prefill_w4a8(args, dtype: Optional[torch.dtype]) -> None:

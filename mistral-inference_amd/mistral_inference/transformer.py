@@ -34,8 +34,9 @@ from .args import QuantizationArgs, TransformerArgs
 from .cache import BatchMetadata, BufferCache
 from .lora import LoRALinear, check_rank
 from .model import ModelBase
+from .moe import MoeLayer
 from .quant import (LM_HEAD_KEY, QSCALE_ACT_KEY, QSCALE_KEY, QuantLinear, check_lm_head_tensors, check_quantize_arg,
-                    quantize_state_tensor, quantized_linear_cls, refusal, refuse_lm_head_arg, refuse_prefill_fp8, refuse_prefill_w4a8,
+                    quantize_state_tensor, quantized_linear_cls, refusal, refuse_lm_head_arg, refuse_prefill_fp8, refuse_prefill_fp8_experts, refuse_prefill_w4a8,
                     refuse_quant_combinations)
 from .rope import precompute_freqs_cis
 from .transformer_layers import LORA_MOE_REFUSAL, RMSNorm, TransformerBlock
@@ -317,8 +318,10 @@ class HipStackBackend:
 
     def _get_workspace(self, model: "Transformer", m, T: int, B: int, max_w: int, kv_layout: int = 0, verify: bool = False) -> torch.Tensor:
         if self._moe_q is not None:  # FP8 experts: the one query beside the one entry (+ the experts' bf16 images at T > 8)
-            need = _hip.lib().mi_workspace_bytes_moe_w8(C.byref(m), C.byref(self._quant[0]), self._moe_q,
-                                                        C.byref(self._head) if self._head is not None else None, T, B, max_w, kv_layout)
+            # (prefill_fp8_experts: x_q | s_x | h_q | s_h in place of the images at a T of the token-grouped W8A8 route)
+            query = _hip.lib().mi_workspace_bytes_moe_w8a8 if model.prefill_fp8_experts else _hip.lib().mi_workspace_bytes_moe_w8
+            need = query(C.byref(m), C.byref(self._quant[0]), self._moe_q, C.byref(self._head) if self._head is not None else None,
+                         T, B, max_w, kv_layout)
         elif self._head is not None:  # a quantised LM head: the one query beside the one entry (+ the head's slice at T > 8)
             w8, w4 = self._quant_refs()
             need = _hip.lib().mi_workspace_bytes_q(C.byref(m), w8, w4, C.byref(self._head), T, B, max_w, kv_layout,
@@ -395,7 +398,11 @@ class HipStackBackend:
             vo = _hip.MiVerifyOut()
             vo.tokens, vo.logprobs = _hip.dev_ptr(verify[0], torch.long), _hip.dev_ptr(verify[1], torch.float32)
             vo.n_accept = _hip.dev_ptr(verify[2], i32)
-        if self._moe_q is not None:  # FP8 experts: every forward is this entry (it refuses a verify step and prefill_fp8 by name)
+        if self._moe_q is not None and model.prefill_fp8_experts and vo is None:  # (the setter has checked; T < 256 is launch for launch mi_forward_moe_w8)
+            _hip.check(_hip.lib().mi_forward_moe_w8a8(C.byref(m), C.byref(self._quant[0]), self._moe_q,
+                                                      C.byref(self._head) if self._head is not None else None, C.byref(bt),
+                                                      _hip.stream_ptr(h.device)), "mi_forward_moe_w8a8")
+        elif self._moe_q is not None:  # FP8 experts: every forward is this entry (it refuses a verify step and prefill_fp8 by name)
             _hip.check(_hip.lib().mi_forward_moe_w8(C.byref(m), C.byref(self._quant[0]), self._moe_q,
                                                     C.byref(self._head) if self._head is not None else None, C.byref(bt),
                                                     C.byref(vo) if vo is not None else None, int(model.prefill_fp8),
@@ -480,6 +487,7 @@ class Transformer(ModelBase):
         self._backend = backend if backend is not None else HipStackBackend()
         self._graphed: Optional[dict] = None  # state of an active graphed_decode() context
         self._prefill_fp8 = False
+        self._prefill_fp8_experts = False
         self._prefill_w4a8 = False
         self.lora_slots = 1                   # adapter sets per LoRA linear (set_lora_slots)
         self._adapters_pinned = False         # between pin_adapters() and unpin_adapters(): forward() leaves the slots alone
@@ -839,6 +847,26 @@ class Transformer(ModelBase):
                 mod.prefill_fp8 = on
 
     @property
+    def prefill_fp8_experts(self) -> bool:
+        """Token-grouped FP8 prefill GEMMs on FP8 experts (quant.py): forwards of 256 rows or more of a MoE model with FP8 experts run
+        the expert projections on the FP8 MFMA without bf16 images of the experts, and the attention linears on the `prefill_fp8`
+        route.  Settable between generations, so one process can A/B; such models only.  The workspace is kept."""
+        return self._prefill_fp8_experts
+
+    @prefill_fp8_experts.setter
+    def prefill_fp8_experts(self, on: bool) -> None:
+        on = bool(on)
+        if on:
+            params = next(self.parameters(), None)
+            refuse_prefill_fp8_experts(self.args, self.dtype if params is not None and not params.is_meta else None)
+        self._prefill_fp8_experts = on
+        for mod in self.modules():  # a block driven module by module takes the route the runner takes
+            if isinstance(mod, QuantLinear):
+                mod.prefill_fp8 = on or self._prefill_fp8  # (off leaves a dense FP8 model's own `prefill_fp8` as it is)
+            elif isinstance(mod, MoeLayer):
+                mod.prefill_fp8_experts = on
+
+    @property
     def prefill_w4a8(self) -> bool:
         """MXFP4 x FP8 prefill GEMMs (quant.py): `prefill_fp8` for a model with MXFP4 weights - forwards of 256 rows or more quantise
         their activations per token and run the four linear groups of every layer on the mixed FP4 x FP8 MFMA, the block scales
@@ -1017,7 +1045,7 @@ class Transformer(ModelBase):
                     device: Union[torch.device, str] = "cuda", dtype: Optional[torch.dtype] = None,
                     softmax_fp32: bool = True, backend: Optional[Any] = None, quantize: Optional[str] = None,
                     prefill_fp8: bool = False, prefill_w4a8: bool = False, quantize_lm_head: bool = False,
-                    quantize_experts: bool = False) -> "Transformer":
+                    quantize_experts: bool = False, prefill_fp8_experts: bool = False) -> "Transformer":
         """params.json + exactly one of consolidated.00.pth / consolidated.safetensors (reference
         transformer.py:297-338).  With safetensors only this rank's tensors are read, straight to `device`
         (the reference loads the whole file to the host on every rank).
@@ -1029,6 +1057,8 @@ class Transformer(ModelBase):
 
         prefill_fp8=True (FP8 e4m3 weights only, whether quantised here or in the folder): `model.prefill_fp8`, the FP8 prefill GEMMs.
         prefill_w4a8=True (MXFP4 weights only, likewise): `model.prefill_w4a8`, the MXFP4 x FP8 prefill GEMMs.
+        prefill_fp8_experts=True (a MoE model with FP8 experts only, likewise): `model.prefill_fp8_experts`, the token-grouped FP8
+        prefill GEMMs on the expert bytes (no bf16 images of the experts).
 
         quantize_lm_head=True (opt-in, with a weight format only): the LM head is quantised in the layers' format too while it
         loads - `model.output` becomes the format's QuantLinear - unless the folder's `quantization.lm_head` says it already is.
@@ -1061,6 +1091,8 @@ class Transformer(ModelBase):
             refuse_prefill_fp8(model_args, dtype)
         if prefill_w4a8:
             refuse_prefill_w4a8(model_args, dtype)
+        if prefill_fp8_experts:
+            refuse_prefill_fp8_experts(model_args, dtype)
         refuse_quant_combinations(model_args, dtype)  # before anything is read from disk
         pipeline_rank = torch.distributed.get_rank() if num_pipeline_ranks > 1 else 0
         with torch.device("meta"):
@@ -1116,6 +1148,7 @@ class Transformer(ModelBase):
         model = model.to(device=device, dtype=dtype)
         model.prefill_fp8 = prefill_fp8
         model.prefill_w4a8 = prefill_w4a8
+        model.prefill_fp8_experts = prefill_fp8_experts
         return model
 
     def _weights_changed(self) -> None:

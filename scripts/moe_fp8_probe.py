@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What FP8 (e4m3) experts buy at the Mixtral-8x7B dims, both models resident in one process on one box:
 
-    python scripts/moe_fp8_probe.py [--layers 4] [--steps 64] [--rounds 3] [--only-fp8-step]
+    python scripts/moe_fp8_probe.py [--layers 4] [--steps 64] [--rounds 3] [--only-fp8-step | --prefill-routes]
 
 The bf16 MoE model and the FP8 one (attention linears and experts e4m3, `quantization.experts`) are built with the same
 number of layers (4 by default: 11.8 GB + 6.0 GB; 32 layers of bf16 experts alone are 90 GB) and timed ALTERNATELY - bf16, FP8,
@@ -13,8 +13,13 @@ graph capture), as scripts/fp8_probe.py.  Both arms on the launch path (engine o
   linears, the router, the LM head, the K/V rings - and the fraction of 8 TB/s each step time stands for.
 Weights are random (timing only; no claim about model quality).  `--only-fp8-step`: nothing but the FP8 model's batch-1 decode
 steps, the form to put under `rocprofv3 --kernel-trace --stats -- python scripts/moe_fp8_probe.py --only-fp8-step`.
+`--prefill-routes`: nothing but prefills of 256, 2048 and 4096 tokens on three arms timed alternately in one process - the bf16
+model, the FP8 model on the dequantisation route, and the same FP8 model with `prefill_fp8_experts` on (attention linears on
+gemm256_w8a8, experts on the token-grouped gemm256_moe_w8a8) - and the workspace bytes of the two FP8 routes at each length.  At 256
+tokens with k = 2, E = 8 an expert has 64 rows on average: mostly-empty 256-row tiles.
 Prints one JSON line."""
 import argparse
+import ctypes as C
 import json
 import os
 import statistics
@@ -115,12 +120,39 @@ def prefill_ms(model, T: int) -> float:
     return event_ms(run, reps=1)
 
 
+def prefill_routes(out, arms, n_rounds: int):
+    """bf16 | FP8 dequantisation route | FP8 token-grouped W8A8 route, alternately; medians, ratios and workspace bytes.  The third
+    arm is the whole switch - its attention linears run on gemm256_w8a8 too, which the second arm cannot take (refused) - so its
+    ratio to the second is not the expert kernel's gain alone."""
+    fp8 = arms["fp8"]
+    routes = {"bf16": (arms["bf16"], False), "fp8_deq": (fp8, False), "fp8_w8a8": (fp8, True)}
+    for T in (256, 2048, 4096):
+        rounds = {n: [] for n in routes}
+        for _ in range(n_rounds):
+            for n, (m, on) in routes.items():
+                if m is fp8:
+                    m.prefill_fp8_experts = on
+                rounds[n].append(round(prefill_ms(m, T), 2))
+        for n in routes:
+            out[f"{n}_prefill{T}_ms_rounds"] = rounds[n]
+            out[f"{n}_prefill{T}_ms"] = statistics.median(rounds[n])
+        for n in ("fp8_deq", "fp8_w8a8"):
+            out[f"{n}_over_bf16_prefill{T}"] = round(out[f"{n}_prefill{T}_ms"] / out[f"bf16_prefill{T}_ms"], 3)
+        out[f"fp8_w8a8_over_deq_prefill{T}"] = round(out[f"fp8_w8a8_prefill{T}_ms"] / out[f"fp8_deq_prefill{T}_ms"], 3)
+        be = fp8._backend
+        m, L = be.plan(fp8), _hip.lib()
+        for n, q in (("fp8_deq", L.mi_workspace_bytes_moe_w8), ("fp8_w8a8", L.mi_workspace_bytes_moe_w8a8)):
+            out[f"{n}_workspace_mb_T{T}"] = round(q(C.byref(m), C.byref(be._quant[0]), be._moe_q, None, T, 1, T, 0) / 1e6, 1)
+    fp8.prefill_fp8_experts = False
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=4)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--only-fp8-step", action="store_true")
+    ap.add_argument("--prefill-routes", action="store_true")
     o = ap.parse_args()
     kv_len = PROMPT + 8 + o.steps * o.rounds // 2
     out = {"layers": o.layers, "steps": o.steps, "rounds": o.rounds}
@@ -133,6 +165,10 @@ def main():
             print(json.dumps(out))
             return
         arms = {"bf16": build(o.layers, False), **arms}
+        if o.prefill_routes:
+            prefill_routes(out, arms, o.rounds)
+            print(json.dumps(out))
+            return
         for B in (1, 3):
             sess = {n: decode_session(m, B) for n, m in arms.items()}
             rounds = {n: [] for n in arms}
