@@ -54,6 +54,11 @@ int mi_debug_engine_sabotage(void* workspace, int launches, mi_stream_t stream);
  * partly filled round of a 256x256-tile GEMM on the 128x128 kernel, 2 = as 128x256 tiles of the 256 kernel (default,
  * bit-identical to 0; MI_GEMM_TAIL). */
 int mi_debug_set_prefill_kernels(int attn_waves, int gemm_tail);
+/* Same-process A/B of the weight-streaming MFMA GEMM that plain bf16 linears of 9 .. 64 rows take (csrc/gemm_skinny.hip): 0 = off,
+ * every shape on the tile kernels; 1 = on with the shipped bounds, 64 rows and 48 for the fp32-logits epilogue (default;
+ * MI_GEMM_SKINNY); above 1 = every epilogue up to that many rows (tests of the kernel and probes: more than 64 rows stream the
+ * weights once per 64); negative = keep.  Returns the previous mode. */
+int mi_debug_set_gemm_skinny(int mode);
 /* The row pairs per unit that the MXFP4 GEMV launcher picks at one token for a matrix of `n_pairs` row pairs on a device of
  * `n_cus` compute units (csrc/gemv_w4.hip; MI_GEMV_W4_RP unset): tests size their matrices to both sides of its threshold. */
 int mi_debug_gemv_w4_row_pairs(int n_pairs, int n_cus);

@@ -658,6 +658,7 @@ int head_gemm_sliced(const LinearGroup& G, const GemmArgs& g, bf16_t* deq, hipSt
   GemmArgs whole = g;
   whole.w0 = deq; whole.w1 = whole.w2 = nullptr; whole.n0 = whole.n1 = g.N;
   const int c256 = g.epi == GEMM_LOGPROB ? g.N : gemm_plan(whole).c256;  // (the logits' tail is the 128-tile kernel's: no half tiles)
+  const bool skinny = gemm_skinny_applicable(whole);  // 9 .. 48 rows: every slice on the weight-streaming kernel (a column's sum does not depend on its unit)
   for (int r0 = 0; r0 < g.N; r0 += LM_HEAD_SLICE_ROWS) {
     const int r1 = g.N - r0 < LM_HEAD_SLICE_ROWS ? g.N : r0 + LM_HEAD_SLICE_ROWS;
     MI_TRY(with_format(G.format, [&](auto Q) {
@@ -680,7 +681,7 @@ int head_gemm_sliced(const LinearGroup& G, const GemmArgs& g, bf16_t* deq, hipSt
       } else {
         p.out = reinterpret_cast<float*>(g.out) + a;
       }
-      MI_TRY(hip_rc(i == 0 ? launch_gemm256(p, s) : launch_gemm128(p, s), what_gemm));
+      MI_TRY(hip_rc(skinny ? launch_gemm_skinny(p, s) : i == 0 ? launch_gemm256(p, s) : launch_gemm128(p, s), what_gemm));
     }
   }
   return MI_OK;
@@ -1606,6 +1607,7 @@ int mi_debug_set_prefill_kernels(int attn_waves, int gemm_tail) {
   if (gemm_tail >= 0) gemm_set_tail_mode(gemm_tail);
   return MI_OK;
 }
+int mi_debug_set_gemm_skinny(int mode) { return gemm_skinny_set_mode(mode); }
 int mi_debug_set_engine_trace(void* dev_buffer) {
   decode_engine_set_trace(dev_buffer);
   return MI_OK;

@@ -1,4 +1,5 @@
-// bf16 MFMA GEMM for the prefill branch (M > 8 tokens): out[M,N] = epilogue(A[M,K] . W[N,K]^T).
+// bf16 MFMA GEMM for the prefill branch (M > 8 tokens): out[M,N] = epilogue(A[M,K] . W[N,K]^T).  (launch_gemm gives the plain
+// form at 9 .. 64 rows and K % 64 == 0 to the weight-streaming kernel of gemm_skinny.hip.)
 //
 // Replaces the reference's nn.Linear GEMMs at prefill (transformer_layers.py:66,93,105-106;
 // transformer.py:235) with the residual add / SiLU*mul / bf16->fp32 widening fused into the epilogue,
@@ -342,6 +343,7 @@ GemmPlan gemm_plan(const GemmArgs& g) {
 hipError_t launch_gemm(const GemmArgs& g, hipStream_t s) {
   if (g.K % 8 != 0 || g.M <= 0 || g.N <= 0) return hipErrorInvalidValue;
   if (g.tile_tab && g.tile_rows == 256) return gemm256_applicable(g) ? launch_gemm256(g, s) : hipErrorInvalidValue;
+  if (gemm_skinny_applicable(g)) return launch_gemm_skinny(g, s);  // 9 .. 64 rows: a weight stream, not tiles (gemm_skinny.hip)
   const GemmPlan p = gemm_plan(g);
   if (p.c256 == 0) return launch_gemm128(g, s);
   if (p.c256 == g.N) return launch_gemm256(g, s);

@@ -179,6 +179,14 @@ hipError_t launch_gemm256(const GemmArgs& g, hipStream_t s);
 bool gemm256_half_applicable(const GemmArgs& g);  // 128x256 tiles of the same kernel: the columns of a half-filled last round
 hipError_t launch_gemm256_half(const GemmArgs& g, hipStream_t s);
 void gemm_set_tail_mode(int mode);  // mi_debug_set_prefill_kernels
+// gemm_skinny.hip: the weight-streaming MFMA kernel for 9 .. GEMM_SKINNY_MAX_M rows (batched decode steps, short prompts): one
+// block per 16 weight rows, the K range split over its four waves.  launch_gemm takes it for the plain form where
+// gemm_skinny_applicable: K % 64 == 0 and the STORE (+ RoPE) / RESIDUAL / SWIGLU / LOGITS epilogues.
+constexpr int GEMM_SKINNY_MAX_M = 64, GEMM_SKINNY_MAX_M_LOGITS = 48;  // (the LM head: measured slower than the 128 tiles at 64 rows)
+bool gemm_skinny_applicable(const GemmArgs& g);
+hipError_t launch_gemm_skinny(const GemmArgs& g, hipStream_t s);  // the kernel itself, whatever M (above 64 rows: launches of 64)
+int gemm_skinny_max_rows(int epi);   // the route's upper bound on M for an epilogue; 0 = off (MI_GEMM_SKINNY=0)
+int gemm_skinny_set_mode(int mode);  // mi_debug_set_gemm_skinny
 // gemm256.hip compiled with -DG256_F16=1 (element ElemF16): the same kernel on fp16 payloads (generic.hip: prefills of fp16 models; gemm256_applicable is the predicate for both elements)
 hipError_t launch_gemm256_f16(const GemmArgs& g, hipStream_t s);
 

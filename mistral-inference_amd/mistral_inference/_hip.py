@@ -276,6 +276,7 @@ _SIGS = {
     "mi_debug_engine_route": (C.c_int, [C.c_int] * 12 + [C.c_char_p, C.c_size_t]),
     "mi_debug_set_prefill_kernels": (C.c_int, [C.c_int, C.c_int]),
     "mi_debug_gemv_w4_row_pairs": (C.c_int, [C.c_int, C.c_int]),
+    "mi_debug_set_gemm_skinny": (C.c_int, [C.c_int]),
     "mi_debug_linear_generic_fused": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp), C.POINTER(C.c_int), C.c_int,
                                                 _vp, C.c_int, _vp, C.c_float, _vp, C.c_int, _vp]),
 }
@@ -1093,6 +1094,12 @@ def debug_engine_sabotage(workspace: torch.Tensor, launches: int) -> None:
 def debug_set_prefill_kernels(attn_waves: int = -1, gemm_tail: int = -1) -> None:
     """Same-process A/B of the prefill kernels' alternative forms (include/mistral_hip_debug.h; negative = keep)."""
     check(lib().mi_debug_set_prefill_kernels(attn_waves, gemm_tail), "mi_debug_set_prefill_kernels")
+
+
+def debug_set_gemm_skinny(mode: int = -1) -> int:
+    """The weight-streaming GEMM of 9 .. 64 rows off (0) / on (1) / keep (negative); returns the previous mode
+    (include/mistral_hip_debug.h)."""
+    return int(lib().mi_debug_set_gemm_skinny(mode))
 
 
 def debug_linear_generic_fused(x: torch.Tensor, weights: Sequence[torch.Tensor], epilogue: int, out: torch.Tensor,
