@@ -361,7 +361,10 @@ int mi_forward(const mi_model_t* model, const mi_batch_t* batch, mi_stream_t str
  * 101-103 on the real-valued weight  W[r, k] = scale[r] * e4m3(w[r, k])  (w: bytes [out, in]; scale: fp32 [out], positive, finite).
  *   M <= 8:  acc[r] = sum_k e4m3(w[r, k]) * x[k] in fp32, y = acc * scale[r] in fp32, and y enters the epilogues of mi_linear /
  *            mi_qkv_rope_kvwrite exactly where acc enters them there (csrc/gemv_w8.hip; activations, norms and rings stay bf16);
- *   M  > 8:  W' = bf16(scale[r] * e4m3(w[r, k])) is written into a scratch and mi_linear's MFMA GEMM runs on W'.
+ *   M  > 8:  W' = bf16(scale[r] * e4m3(w[r, k])) is written into a scratch and mi_linear's MFMA GEMM runs on W';
+ *   9 <= M <= 64 with K % 128 == 0 and 16-byte aligned operands (csrc/gemm_skinny_q.hip; mi_debug_set_gemm_skinny(0) gives the
+ *            M > 8 form back): the rule of M <= 8 on the MFMA - the weight bytes are streamed once, acc runs on e4m3(w) and
+ *            y = acc * scale[r] in fp32 enters the epilogue; nothing is written into the scratch.
  * With power-of-two scales W' is exact and both forms are the bf16 model on the dequantised weights up to fp32 summation order;
  * with other scales the two forms differ by one bf16 rounding of each weight.  K must be a multiple of 16 (MI_ERR_SHAPE).
  * Embeddings, norms, the LM head, the MoE gate and the K/V rings stay bf16.

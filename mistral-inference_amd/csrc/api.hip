@@ -296,6 +296,8 @@ struct QuantW8 {  // gemv_w8.hip: e4m3 bytes, one fp32 scale per row
                               *kOperandsA8 = "x and the weights 16-byte aligned";
   static constexpr auto launch_gemv = launch_gemv_w8;
   static constexpr auto launch_dequant = launch_dequant_w8;
+  static constexpr auto skinny_applicable = gemm_skinny_w8_applicable;  // gemm_skinny_q.hip: 9 .. 64 rows on the weight bytes
+  static constexpr auto launch_skinny = launch_gemm_skinny_w8;
   static size_t row_bytes(int K) { return (size_t)K; }  // of a weight row; scale elements of a row
   static size_t row_scales(int) { return 1; }
 };
@@ -310,6 +312,8 @@ struct QuantW4 {  // gemv_w4.hip: MXFP4 code bytes, one e8m0 scale byte per bloc
                               *kOperandsA8 = "x and the code matrices 16-byte aligned, the block scale matrices 4-byte aligned";
   static constexpr auto launch_gemv = launch_gemv_w4;
   static constexpr auto launch_dequant = launch_dequant_w4;
+  static constexpr auto skinny_applicable = gemm_skinny_w4_applicable;
+  static constexpr auto launch_skinny = launch_gemm_skinny_w4;
   static size_t row_bytes(int K) { return (size_t)K >> 1; }
   static size_t row_scales(int K) { return (size_t)K >> 5; }
 };
@@ -689,6 +693,9 @@ int head_gemm_sliced(const LinearGroup& G, const GemmArgs& g, bf16_t* deq, hipSt
 
 // M <= GEMV_MAX_T rows: weight-streaming GEMV passes with the RMSNorm, RoPE and (bf16 rings) the ring write fused.  More rows: the
 // RMSNorm into xn, the bf16 image of quantised weights into deq, then the MFMA GEMM (RoPE in its epilogue when it takes the heads).
+// Quantised groups of 9 .. 64 rows (gemm_skinny_q_max_rows; K % 128 == 0 at FP8, K % 256 == 0 at MXFP4, operands aligned): the
+// RMSNorm into xn, then ONE launch of the weight-streaming kernel on the weight bytes and their scales (gemm_skinny_q.hip, RoPE in
+// its epilogue under the same condition) - no deq, no dequantisation launch; mi_debug_set_gemm_skinny(0) gives the image route.
 // Quantised groups with C.a8 at M >= 256 rows and K % 128 == 0: the per-token e4m3 quantisation of the input rows (the RMSNorm fused
 // into it) and the format's FP8-activation MFMA GEMM on the weight bytes (gemm256_w8a8.hip / gemm256_w4a8.hip) - no xn, no deq, no
 // dequantisation launch; any other shape takes the routes above.
@@ -775,23 +782,36 @@ int linear_group(const LinearGroup& G, const LinearCall& C, int M, hipStream_t s
       MI_TRY(hip_rc(launch_rmsnorm(C.xn, C.x, C.norm_w, M, K, C.eps, s), C.what.norm));
       x = C.xn; ldx = K;
     }
-    const void* w[3] = {G.w[0], G.w[1], G.w[2]};
     const bool head_slices = G.format && C.epi == MI_EPI_LOGITS;  // a quantised LM head: its bf16 image slice by slice
-    if (G.format) {
-      if (!C.deq) return fail(MI_ERR_WORKSPACE, "linear group: no scratch for the dequantised weights");
-      const int nr[3] = {n0, n1 - n0, n2 - n1};
-      if (!head_slices)
-        MI_TRY(with_format(G.format, [&](auto Q) { return dequant_group<decltype(Q)>(w, scales_of(G, Q), nr, K, C.deq, s, C.what.dequant); }));
-    }
     GemmArgs g;
     memset(&g, 0, sizeof(g));
     g.epi = swiglu ? GEMM_SWIGLU : (C.epi == MI_EPI_STORE || qkv) ? GEMM_STORE : C.epi == MI_EPI_RESIDUAL ? GEMM_RESIDUAL : GEMM_LOGITS;
     g.M = M; g.N = swiglu ? n0 : n2; g.K = K; g.a = x; g.lda = ldx;
-    g.w0 = (const bf16_t*)w[0]; g.w1 = (const bf16_t*)w[1]; g.w2 = (const bf16_t*)w[2]; g.n0 = n0; g.n1 = swiglu ? n0 : n1;
+    g.w0 = (const bf16_t*)G.w[0]; g.w1 = (const bf16_t*)G.w[1]; g.w2 = (const bf16_t*)G.w[2]; g.n0 = n0; g.n1 = swiglu ? n0 : n1;
     g.out = C.out; g.ldo = C.ldo; g.residual = (const bf16_t*)C.residual;
     if (fused_rope) { g.rope_cs = C.rope_cs; g.tok_pos = C.tok_pos; g.rope_cols = n1; g.rope_dh = C.head_dim; }
-    if (head_slices) MI_TRY(head_gemm_sliced(G, g, C.deq, s, C.what.dequant, C.what.gemm));
-    else MI_TRY(hip_rc(launch_gemm(g, s), C.what.gemm));
+    // 9 .. 64 rows of a quantised group: the weight-streaming kernel on the bytes themselves (gemm_skinny_q.hip), no image
+    bool streamed = false;
+    if (G.format && !head_slices)
+      MI_TRY(with_format(G.format, [&](auto Q) {
+        typedef decltype(Q) F;
+        const GemmScaledArgs<typename F::scale_t> qa = {g, {scales_of(G, Q).s[0], scales_of(G, Q).s[1], scales_of(G, Q).s[2]}};
+        streamed = F::skinny_applicable(qa);
+        return streamed ? hip_rc(F::launch_skinny(qa, s), C.what.gemm) : MI_OK;
+      }));
+    if (!streamed) {
+      if (G.format) {
+        if (!C.deq) return fail(MI_ERR_WORKSPACE, "linear group: no scratch for the dequantised weights");
+        const void* w[3] = {G.w[0], G.w[1], G.w[2]};
+        const int nr[3] = {n0, n1 - n0, n2 - n1};
+        if (!head_slices) {
+          MI_TRY(with_format(G.format, [&](auto Q) { return dequant_group<decltype(Q)>(w, scales_of(G, Q), nr, K, C.deq, s, C.what.dequant); }));
+          g.w0 = (const bf16_t*)w[0]; g.w1 = (const bf16_t*)w[1]; g.w2 = (const bf16_t*)w[2];
+        }
+      }
+      if (head_slices) MI_TRY(head_gemm_sliced(G, g, C.deq, s, C.what.dequant, C.what.gemm));
+      else MI_TRY(hip_rc(launch_gemm(g, s), C.what.gemm));
+    }
   }
   if (qkv && !fused_rope)
     MI_TRY(hip_rc(launch_rope(C.out, C.ldo, M, n0 / C.head_dim, (n1 - n0) / C.head_dim, C.head_dim, C.rope_cs, C.tok_pos, s), "rope"));

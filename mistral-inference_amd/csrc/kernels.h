@@ -187,6 +187,25 @@ bool gemm_skinny_applicable(const GemmArgs& g);
 hipError_t launch_gemm_skinny(const GemmArgs& g, hipStream_t s);  // the kernel itself, whatever M (above 64 rows: launches of 64)
 int gemm_skinny_max_rows(int epi);   // the route's upper bound on M for an epilogue; 0 = off (MI_GEMM_SKINNY=0)
 int gemm_skinny_set_mode(int mode);  // mi_debug_set_gemm_skinny
+// gemm_skinny_q.hip: the same frame on weight-only quantised rows - g.w0 / g.w1 / g.w2 point to e4m3 bytes [rows, K] with sw[i] one
+// fp32 per row of segment i (w8: y = acc * scale in the epilogue), or to MXFP4 code bytes [rows, K / 2] with sw[i] the e8m0 block
+// scales [rows, K / 32] (w4: applied in the conversion); SWIGLU: sw[0] = W1's, sw[1] = W3's.  The bytes become bf16 MFMA operands
+// in registers: no dequantised image.  A quantised linear group of 9 .. gemm_skinny_q_max_rows rows takes it (linear_group, api.hip)
+// where *_applicable: K % 128 == 0 (w8) / K % 256 == 0 (w4), STORE (+ RoPE) / RESIDUAL / SWIGLU, x and the weights 16-byte aligned,
+// lda % 8 == 0, the scales aligned to 4 (w8) / 2 (w4) bytes.  GemmArgs stays as it is, the scales ride beside it.
+template <class scale_t>
+struct GemmScaledArgs {
+  GemmArgs g;
+  const scale_t* sw[3];
+};
+typedef GemmScaledArgs<float> GemmSkinnyW8Args;
+typedef GemmScaledArgs<uint8_t> GemmSkinnyW4Args;
+constexpr int GEMM_SKINNY_Q_MAX_M_W8 = 64, GEMM_SKINNY_Q_MAX_M_W4 = 64;  // the shipped row bounds per format (mode 1)
+int gemm_skinny_q_max_rows(int format, int epi);  // with MI_GEMM_SKINNY / mi_debug_set_gemm_skinny as gemm_skinny_max_rows
+bool gemm_skinny_w8_applicable(const GemmSkinnyW8Args& a);
+bool gemm_skinny_w4_applicable(const GemmSkinnyW4Args& a);
+hipError_t launch_gemm_skinny_w8(const GemmSkinnyW8Args& a, hipStream_t s);  // the kernel itself, any M in 1 .. 64
+hipError_t launch_gemm_skinny_w4(const GemmSkinnyW4Args& a, hipStream_t s);
 // gemm256.hip compiled with -DG256_F16=1 (element ElemF16): the same kernel on fp16 payloads (generic.hip: prefills of fp16 models; gemm256_applicable is the predicate for both elements)
 hipError_t launch_gemm256_f16(const GemmArgs& g, hipStream_t s);
 

@@ -455,7 +455,8 @@ def linear_w8(x: torch.Tensor, weights: Sequence[torch.Tensor], scales: Sequence
               residual: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`linear` on weight-only FP8 matrices (mi_linear_w8): weights[i] e4m3 bytes [n_i, K] (uint8 or float8_e4m3fn), scales[i]
-    fp32 [n_i]; STORE / RESIDUAL / SWIGLU.  M <= 8: the e4m3 GEMV; above: dequantise into a per-call scratch + the bf16 GEMM."""
+    fp32 [n_i]; STORE / RESIDUAL / SWIGLU.  M <= 8: the e4m3 GEMV; 9 .. 64 rows with K % 128 == 0: the weight-streaming MFMA kernel on
+    the bytes (y = bf16(scale * acc), as the GEMV); anything else: dequantise into a per-call scratch + the bf16 GEMM."""
     return linear_quant(W8, x, weights, scales, epilogue, residual, norm_w, eps, out)
 
 
@@ -514,8 +515,8 @@ def linear_w4(x: torch.Tensor, weights: Sequence[torch.Tensor], scales: Sequence
               residual: Optional[torch.Tensor] = None, norm_w: Optional[torch.Tensor] = None, eps: float = 0.0,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`linear` on weight-only MXFP4 matrices (mi_linear_w4): weights[i] uint8 code bytes [n_i, K / 2] (low nibble = even k),
-    scales[i] uint8 e8m0 block scales [n_i, K / 32]; STORE / RESIDUAL / SWIGLU.  M <= 8: the MXFP4 GEMV; above: dequantise into a
-    per-call scratch + the bf16 GEMM."""
+    scales[i] uint8 e8m0 block scales [n_i, K / 32]; STORE / RESIDUAL / SWIGLU.  M <= 8: the MXFP4 GEMV; 9 .. 64 rows with
+    K % 256 == 0: the weight-streaming MFMA kernel on the code bytes; anything else: dequantise into a per-call scratch + the bf16 GEMM."""
     return linear_quant(W4, x, weights, scales, epilogue, residual, norm_w, eps, out)
 
 
